@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- StereoDPNet train-step throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 A step = forward + loss + backward + gradient all-reduce (RCCL, N > 1) + fused Adam on one synthetic batch of
 `--batch` dual-pixel pairs of `--height` x `--width` per GPU (weak scaling), inputs resident in HBM before the timed
-region.  Rank 0 prints ONE JSON line (contract in the task description) including
+region.  Every timed step starts from the parameters the model had before the warm-up, with fresh Adam moments, so that what
+the timed path computes is the same in every run.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints `value` (samples/s) and
+`ms_per_step`; `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
+With `--full` the line also carries the measurements that take steps or runs of their own:
+  "restart_ms_per_step": device time of the per-step restart (parameter copy, Adam moment fills), included in `ms_per_step`;
+  "f32_products.value_with_exact_splits_path1": the same step with the exact-split matrix path (5 more steps);
+  "flop_frac_executed", "executed_tflop_per_step": the FLOPs the kernels ran per step, from the per-launch records below;
   "roofline":     the dominant kernel (implicit-GEMM convolution on the fp32 matrix cores) -- algorithmic FLOPs per
                   launch / average launch duration, measured live with HIP events on the launch stream.  `value` is timed with the step's
                   stream overlap on (weight gradients on a side stream, the two feature passes on two streams); kernels of different
@@ -34,6 +40,26 @@ sys.path.insert(0, ROOT)
 FLOP_PER_PIXEL_FWD_BWD = 2.708e6        # SURVEY.md section 8d (fwd 902 764 FLOP/pixel/pair, fwd+bwd = 3x)
 PEAK_F32_TFLOPS = 157.3                 # MI355X_MICROARCH.md: fp32 vector == fp32 MFMA peak
 PEAK_BF16_TFLOPS = 2500.0               # MI355X_MICROARCH.md: ~2.5 PF dense bf16 MFMA
+DUMP_BUDGET_BYTES = 60 * 10 ** 6        # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` ({name: tensor}) as out_dir/<name>.npy, float64 kept, every other dtype as float32.
+    Smallest first, each array may use an equal share of what is left of DUMP_BUDGET_BYTES; a larger one is written as a fixed sample
+    instead: the 1-D array of the elements at sorted flat indices drawn from a generator seeded with 0, so the same shapes give the same
+    indices in every run and every build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = sorted(((v.numel(), k, v.detach()) for k, v in arrays.items() if torch.is_tensor(v)), key=lambda a: a[:2])
+    left = DUMP_BUDGET_BYTES
+    for i, (_, name, t) in enumerate(arrays):
+        t = t if t.dtype == torch.float64 else t.float()
+        cap = left // (len(arrays) - i) // t.element_size()
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        left -= t.numel() * t.element_size()
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy())
 
 
 def cpu_baseline(threads, H=512, W=768):
@@ -84,9 +110,11 @@ def stage_bench(args):
         torch.cuda.synchronize()
         e0.record()
         for _ in range(args.steps):
-            fn()
+            out = fn()
         e1.record()
         torch.cuda.synchronize()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'volume': out})
     secs = e0.elapsed_time(e1) * 1e-3 / args.steps
     gbs = alg_bytes / secs / 1e9
     print(json.dumps({'metric': 'stage throughput (not the BASELINE metric)', 'workload': name, 'value': B / secs, 'unit': 'samples/s',
@@ -207,7 +235,7 @@ def main():
     ap.add_argument('--sync-bn', action='store_true',
                     help='BatchNorm statistics over the global batch (what the reference does under DDP); default per-rank statistics')
     ap.add_argument('--shapes', default=None, help='write a per-convolution-shape timing table to this file')
-    ap.add_argument('--no-detail', action='store_true', help='skip the two extra untimed steps that time the normalisation / activation launches')
+    ap.add_argument('--no-detail', action='store_true', help='with --full: skip the extra untimed steps (exact-split path, one-stream detail steps, shader clock)')
     ap.add_argument('--force-dist', action='store_true',
                     help="with --gpus 1: still create a (world-size-1) 'nccl' process group and send every gradient bucket through it -- the "
                          "staged reducer (tensor-hook launches, side-stream joins, stage_finish, fused Adam) runs through RCCL's stream handling")
@@ -218,7 +246,15 @@ def main():
                          '"dry_run": true -- no GPU call is made (tests/test_host_logic.py covers `--gpus 8` this way)')
     ap.add_argument('--workload', default='train', choices=['train', 'psm_volume', 'cost_volume', 'cost_volume_fix'],
                     help="'train' = the BASELINE metric; the other two time one HBM-bound stage in isolation (BASELINE configs[3], SURVEY a2-a4)")
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure what takes steps or runs of its own: the exact-split matrix path, the per-kernel '
+                         'roofline blocks (one-stream detail steps, shader clock) and the CPU baseline (default: the headline figure only)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed (the train step\'s results, the updated parameters and the gradients; '
+                         'a fixed seeded sample of each large array) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.shapes and not args.full:
+        ap.error('--shapes needs --full (the per-shape table comes from the per-launch records of the full run)')
 
     if args.gpus > 1 and 'RANK' not in os.environ and args.workload == 'train':
         return self_launch(args.gpus)
@@ -282,24 +318,57 @@ def main():
     use_graph = reducer is None and not args.no_graph and os.environ.get('DPF_STEP_GRAPH', '1') != '0'
     if not use_graph:
         os.environ['DPF_STEP_GRAPH'] = '0'
+    # Every timed step is the same train step: from the parameters the model had before the warm-up, with fresh Adam moments.  The
+    # default kernels merge some partial results with float atomics (deterministic mode: 4.5e-3 relative on the gradient
+    # arena) and Adam would carry that noise from step to step; restarting each step from one stored state keeps what the timed path
+    # computes the same in every run.  Three launches, issued like all of the model's own eager work (plugin._behind_replays: on the
+    # step stream once a graph replays there -- an event wait behind a replay does not order the caller's stream);
+    # the graph keeps its addresses.  --full reports their time (`restart_ms_per_step`); it is inside `ms_per_step`.
+    params0 = model.flat_parameters().detach().clone()
+
+    def restart():
+        with torch.no_grad():
+            model.flat_parameters().copy_(params0)
+        if model._adam is not None:
+            model._adam['m'].zero_()
+            model._adam['v'].zero_()
+            model._adam['step'] = 0
     for _ in range(max(args.warmup, 4) if use_graph else args.warmup):
         model.train_step(batch, reducer)
     sync()
     graph_live = bool(use_graph and getattr(model, '_graph_state', None) and model._graph_state.get('graph') is not None)
-    ops.PROFILE = None if graph_live else []             # per-launch event pairs need eager launches: with the graph live they come from the detail steps only
+    # per-launch event pairs need eager launches: with the graph live they come from the detail steps only (--full)
+    ops.PROFILE = None if (graph_live or not args.full) else []
     t0 = time.perf_counter()
     for _ in range(args.steps):
+        model._behind_replays(restart)
         res = model.train_step(batch, reducer)
     sync()
     elapsed = time.perf_counter() - t0
     prof, ops.PROFILE = (ops.PROFILE or []), None
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: the results are the graph's static buffers, the parameters move with the next step
+        dump_outputs(args.dump_outputs, dict(res, parameters=model.flat_parameters(), gradients=model.flat_gradients(zero=False)))
+    restart_ms = None
+    if args.full:
+        r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+        def timed_restarts():                              # (events on the stream the restarts run on)
+            r0.record()
+            for _ in range(20):
+                restart()
+            r1.record()
+        model._behind_replays(timed_restarts)
+        sync()
+        restart_ms = r0.elapsed_time(r1) / 20
     loss = float(res['final_loss'].detach())
     # The same step with the fp32 products formed by the EXACT construction (six bf16 partial products of exact three-way splits,
     # dpf_set_f32_matrix_path(1)) instead of the default three f16 products of block-scaled splits: a short second measurement (the step
     # graph is re-captured: the matrix path is part of its key), reported beside `value`, never as `value`.
     value_path1 = None
     mpath_default = ops.f32_matrix_path()
-    if world == 1 and args.precision == 'f32' and args.model == 'stereodpnet' and mpath_default == 2 and not args.no_detail:
+    detail = args.full and not args.no_detail
+    if world == 1 and args.precision == 'f32' and args.model == 'stereodpnet' and mpath_default == 2 and detail:
         ops.set_f32_matrix_path(1)
         for _ in range(4):
             model.train_step(batch, reducer)
@@ -323,7 +392,7 @@ def main():
     # time, equal to the rocprofv3 averages in profiles/), which also carry the detail timers of the 744 normalisation launches.
     prof_timed, timed_async = prof, (ops.WGRAD_ASYNC or sdn.FEATURES_TWO_STREAMS)
     prof_detail, detail_steps = [], 0
-    if not args.no_detail:
+    if detail:
         set_streams(False)
         for _ in range(2):
             model.train_step(batch, reducer)                      # settling steps in the one-stream mode
@@ -355,7 +424,7 @@ def main():
     else:
         prof_steps = args.steps
     clock_mhz = None
-    if not args.no_detail and args.precision == 'f32' and args.model == 'stereodpnet':
+    if detail and args.precision == 'f32' and args.model == 'stereodpnet':
         clock_mhz = held_clock_mhz(dev)
     ranks_seen = world
     if world > 1 or (args.force_dist and dist.is_initialized()):
@@ -367,140 +436,141 @@ def main():
         global_batch = args.batch * world
         value = global_batch * args.steps / elapsed
 
-        def families(records, steps):
-            fam, shapes = {}, {}
-            for family, flops, e0, e1, tag, nbytes in records:
-                secs = e0.elapsed_time(e1) * 1e-3
-                f = fam.setdefault(family, [0.0, 0.0, 0, 0.0])
-                f[0] += flops; f[1] += secs; f[2] += 1; f[3] += nbytes
-                g = shapes.setdefault(tag, [0.0, 0.0, 0])
-                g[0] += flops; g[1] += secs; g[2] += 1
-            return fam, shapes
-        fam, shapes = families(prof, prof_steps)
-        fam_t, _ = families(prof_timed, args.steps)
-        fam_d, _ = families([r for r in prof_detail if r[0] == 'norm_act'], detail_steps)
-        if args.shapes:
-            with open(args.shapes, 'w') as fh:
-                for tag, (fl, se, n) in sorted(shapes.items(), key=lambda kv: -kv[1][1]):
-                    fh.write('%-60s calls %4d  ms/step %8.3f  TFLOP/s %6.1f\n' % (tag, n, se / prof_steps * 1e3, fl / se / 1e12))
-        # HBM bytes per step and family from the committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (tools/gpu_profiles.sh).  The file
-        # carries a hash of the kernel sources it was collected on; the numbers are only reported for the workload, precision, world size
-        # and kernels they were measured with -- otherwise `traffic` is null and `traffic_source` says why.
-        tname = 'r06_pmc_traffic_bf16.json' if args.precision == 'bf16' else 'r06_pmc_traffic.json'
-        tpath = os.path.join(ROOT, 'profiles', tname)
-        pmc = json.load(open(tpath)) if os.path.exists(tpath) else {}
-        meta = pmc.pop('_meta', {})
-        sys.path.insert(0, os.path.join(ROOT, 'tools'))
-        try:
-            from pmc_traffic import kernel_sources_sha16
-            sha_now = kernel_sources_sha16()
-        except Exception:
-            sha_now = None
-        same_workload = args.model == 'stereodpnet' and (args.batch, args.height, args.width) == (4, 1024, 1536) and world == 1 and not args.sync_bn
-        same_kernels = bool(meta) and meta.get('kernel_sources_sha16') == sha_now
-        if not pmc:
-            why = 'no traffic file'
-        elif not same_workload:
-            why = 'not the workload the counters were collected on (StereoDPNet, 4 x 1024x1536, 1 GPU, per-rank BatchNorm)'
-        elif not same_kernels:
-            why = 'kernel sources changed since the counters were collected'
-        else:
-            why = None
-        traffic_source = {'file': 'profiles/' + tname, 'kernel_sources_sha16': meta.get('kernel_sources_sha16'), 'collected_utc': meta.get('collected_utc'),
-                          'kernel_sources_sha16_now': sha_now, 'used': why is None, 'not_used_because': why}
-        if why is not None:
-            pmc = {}
-            same_workload = False
+        if args.full:
+            def families(records, steps):
+                fam, shapes = {}, {}
+                for family, flops, e0, e1, tag, nbytes in records:
+                    secs = e0.elapsed_time(e1) * 1e-3
+                    f = fam.setdefault(family, [0.0, 0.0, 0, 0.0])
+                    f[0] += flops; f[1] += secs; f[2] += 1; f[3] += nbytes
+                    g = shapes.setdefault(tag, [0.0, 0.0, 0])
+                    g[0] += flops; g[1] += secs; g[2] += 1
+                return fam, shapes
+            fam, shapes = families(prof, prof_steps)
+            fam_t, _ = families(prof_timed, args.steps)
+            fam_d, _ = families([r for r in prof_detail if r[0] == 'norm_act'], detail_steps)
+            if args.shapes:
+                with open(args.shapes, 'w') as fh:
+                    for tag, (fl, se, n) in sorted(shapes.items(), key=lambda kv: -kv[1][1]):
+                        fh.write('%-60s calls %4d  ms/step %8.3f  TFLOP/s %6.1f\n' % (tag, n, se / prof_steps * 1e3, fl / se / 1e12))
+            # HBM bytes per step and family from the committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (tools/gpu_profiles.sh).  The file
+            # carries a hash of the kernel sources it was collected on; the numbers are only reported for the workload, precision, world size
+            # and kernels they were measured with -- otherwise `traffic` is null and `traffic_source` says why.
+            tname = 'r06_pmc_traffic_bf16.json' if args.precision == 'bf16' else 'r06_pmc_traffic.json'
+            tpath = os.path.join(ROOT, 'profiles', tname)
+            pmc = json.load(open(tpath)) if os.path.exists(tpath) else {}
+            meta = pmc.pop('_meta', {})
+            sys.path.insert(0, os.path.join(ROOT, 'tools'))
+            try:
+                from pmc_traffic import kernel_sources_sha16
+                sha_now = kernel_sources_sha16()
+            except Exception:
+                sha_now = None
+            same_workload = args.model == 'stereodpnet' and (args.batch, args.height, args.width) == (4, 1024, 1536) and world == 1 and not args.sync_bn
+            same_kernels = bool(meta) and meta.get('kernel_sources_sha16') == sha_now
+            if not pmc:
+                why = 'no traffic file'
+            elif not same_workload:
+                why = 'not the workload the counters were collected on (StereoDPNet, 4 x 1024x1536, 1 GPU, per-rank BatchNorm)'
+            elif not same_kernels:
+                why = 'kernel sources changed since the counters were collected'
+            else:
+                why = None
+            traffic_source = {'file': 'profiles/' + tname, 'kernel_sources_sha16': meta.get('kernel_sources_sha16'), 'collected_utc': meta.get('collected_utc'),
+                              'kernel_sources_sha16_now': sha_now, 'used': why is None, 'not_used_because': why}
+            if why is not None:
+                pmc = {}
+                same_workload = False
 
-        def hbm_per_step(*keys):
-            recs = [pmc[k] for k in keys if k in pmc]
-            return sum(r['hbm_bytes_per_step'] for r in recs) if (recs and same_workload) else None
-        PMC_KEYS = {'conv_igemm': ('igemm2',), 'conv_wgrad': ('wgrad2',), 'conv_pointwise': ('pointwise',), 'conv_smallk': ('smallk',),
-                    'dcn_fwd': ('dcn_fwd',), 'dcn_bwd': ('dcn_bwd_input', 'dcn_bwd_offset'), 'norm_act': ('bn_',)}
-        MFMA_FAMILIES = ('conv_igemm', 'conv_wgrad', 'conv_bf16', 'dcn_fwd', 'dcn_bwd')
-        fam_out = {}
-        for k, (flops, secs, n, nbytes) in list(fam.items()) + list(fam_d.items()):
-            steps = detail_steps if k == 'norm_act' else prof_steps
-            rec = {'ms_per_step': secs / steps * 1e3, 'launches_per_step': n / steps}
-            if k in MFMA_FAMILIES or k == 'conv_smallk':
-                rec['tflops'] = flops / secs / 1e12
-            if nbytes > 0:
-                rec['algorithmic_gbs'] = nbytes / secs / 1e9
-                rec['algorithmic_bytes_per_step'] = nbytes / steps
-            hb = hbm_per_step(*PMC_KEYS.get(k, ()))
-            if hb is not None:
-                rec['hbm_bytes_per_step'] = hb
+            def hbm_per_step(*keys):
+                recs = [pmc[k] for k in keys if k in pmc]
+                return sum(r['hbm_bytes_per_step'] for r in recs) if (recs and same_workload) else None
+            PMC_KEYS = {'conv_igemm': ('igemm2',), 'conv_wgrad': ('wgrad2',), 'conv_pointwise': ('pointwise',), 'conv_smallk': ('smallk',),
+                        'dcn_fwd': ('dcn_fwd',), 'dcn_bwd': ('dcn_bwd_input', 'dcn_bwd_offset'), 'norm_act': ('bn_',)}
+            MFMA_FAMILIES = ('conv_igemm', 'conv_wgrad', 'conv_bf16', 'dcn_fwd', 'dcn_bwd')
+            fam_out = {}
+            for k, (flops, secs, n, nbytes) in list(fam.items()) + list(fam_d.items()):
+                steps = detail_steps if k == 'norm_act' else prof_steps
+                rec = {'ms_per_step': secs / steps * 1e3, 'launches_per_step': n / steps}
+                if k in MFMA_FAMILIES or k == 'conv_smallk':
+                    rec['tflops'] = flops / secs / 1e12
                 if nbytes > 0:
-                    rec['traffic_over_algorithmic'] = hb / (nbytes / steps)
-            fam_out[k] = rec
-        dom = 'conv_igemm' if 'conv_igemm' in fam else (max(fam, key=lambda k: fam[k][1]) if fam else None)
-        roof = None
-        if dom:
-            flops, secs, n, alg_bytes = fam[dom]
-            ach = flops / secs / 1e12
-            hb = hbm_per_step(*PMC_KEYS.get(dom, ()))
-            # the dense conv kernels contract on the bf16 matrix cores in --precision bf16: price them against THAT peak (they are then
-            # staging-bound -- LDS-DMA / LDS reads of the fp32 patch -- far below it)
-            peak = PEAK_BF16_TFLOPS if args.precision == 'bf16' else PEAK_F32_TFLOPS
-            # how precision "f32" multiplies (dpf_get_f32_matrix_path): 0 = fp32 MFMA only, 1 = six bf16 partial products per fp32 product,
-            # 2 = three f16 partial products of block-scaled two-way splits -- the ceiling of the split paths is the 16-bit pipe's dense peak
-            # divided by the products per fp32 product (x 27/28: 27 taps in 7 groups of 4)
-            from dualpixelface_amd._lib import lib as _dpf_lib
-            mpath = int(_dpf_lib().cdll.dpf_get_f32_matrix_path())
-            nprod = {1: 6.0, 2: 3.0}.get(mpath, 6.0)
-            pipe_name = {1: 'six bf16 partial products of exact three-way splits', 2: 'three f16 partial products of block-scaled two-way splits'}.get(mpath, 'fp32 MFMA')
-            x6_flop_per_clk = 1024 * (32 * 32 * 16 * 2 / 32.0) / nprod * 27.0 / 28.0     # fp32 FLOP per shader clock of the split construction
-            x6_peak = x6_flop_per_clk * 2.4e9 / 1e12
-            f32_frac_pipe = None
-            if args.precision == 'f32' and dom == 'conv_igemm':
-                # The family mixes two pipes: stride-1 launches with >= 8 input channels multiply on the bf16 pipe (six partial products per fp32
-                # product: ceiling 2.5 PFLOP/s / 6 x 27/28), the rest (stride 2, the 3-channel first layer) on v_mfma_f32_32x32x2_f32 (157.3).
-                # `peak` is the FLOP-weighted (harmonic) blend of the two -- the rate at which the family would run with every launch at ITS
-                # pipe's dense peak -- so that `frac` cannot exceed 1 (157.3 is not the peak of a bf16-pipe kernel).
-                on_bf16 = lambda tag: mpath > 0 and (' s1 ' in tag) and not any((' C%d ' % c) in tag for c in range(1, 8)) and ' k111 ' not in tag
-                fl_b = sum(r[1] for r in prof if r[0] == dom and on_bf16(r[4]))
-                fl_f = sum(r[1] for r in prof if r[0] == dom and not on_bf16(r[4]))
-                if fl_b + fl_f > 0:
-                    peak = (fl_b + fl_f) / (fl_b / x6_peak + fl_f / PEAK_F32_TFLOPS)
-                    f32_frac_pipe = fl_b / (fl_b + fl_f)
-            inline_ms = sum(v[1] for v in fam.values()) / prof_steps * 1e3
-            roof = {'bound': 'mfma', 'kernel': dom, 'achieved': ach, 'peak': peak, 'unit': 'TFLOP/s', 'frac': ach / peak,
-                    'traffic': (hb / (n / prof_steps)) if hb is not None else None, 'traffic_source': traffic_source, 'algorithmic_bytes_per_launch': alg_bytes / n, 'launches': n,
-                    'avg_launch_ms': secs / n * 1e3, 'ms_per_step': secs / prof_steps * 1e3,
-                    'measured_in': ('%d steps after the timed region on ONE stream (weight gradients in line, feature passes one after the other: kernels do not overlap, event time = kernel time)' % prof_steps)
-                                   if not args.no_detail else 'the timed region', 'families': fam_out}
-            if args.precision != 'bf16':
-                # (see the blend above: `peak` prices every launch at the dense peak of the pipe it runs on)
-                roof['peak_note'] = ('FLOP-weighted blend of the pipes the launches run on: %.0f %% of the family\'s fp32 FLOPs multiply on the 16-bit matrix pipe '
-                                     '(%s: 2.5 PFLOP/s / %d x 27/28 = %.1f TFLOP/s of fp32 FLOPs at 2.4 GHz), the rest on '
-                                     'v_mfma_f32_32x32x2_f32 (157.3)' % (100.0 * (f32_frac_pipe or 0.0), pipe_name, int(nprod), x6_peak))
-                roof['f32_matrix_path'] = mpath
-                roof['frac_of_f32_mfma_peak'] = ach / PEAK_F32_TFLOPS        # the dtype's own dense peak (individual bf16-pipe launches exceed it)
-                if clock_mhz:
-                    # the bf16-pipe share priced at the clock the chip HOLDS under that stream (power-bound: MI355X_MICROARCH.md, DVFS)
-                    held_b = x6_flop_per_clk * clock_mhz * 1e6 / 1e12
-                    fb = f32_frac_pipe if f32_frac_pipe is not None else 1.0
-                    held = 1.0 / (fb / held_b + (1.0 - fb) / PEAK_F32_TFLOPS)
-                    roof['shader_clock_mhz_under_conv_load'] = clock_mhz
-                    roof['split_pipe_issue_ceiling_at_held_clock'] = held_b
-                    roof['peak_at_held_clock'] = held
-                    roof['frac_of_peak_at_held_clock'] = ach / held
-            if dom in fam_t and timed_async and not args.no_detail:      # the same family as the timed region saw it (overlapped by the side stream)
-                f2 = fam_t[dom]
-                roof['timed_region_overlapped'] = {'achieved': f2[0] / f2[1] / 1e12, 'frac': f2[0] / f2[1] / 1e12 / peak, 'avg_launch_ms': f2[1] / f2[2] * 1e3,
-                                                   'note': 'event pairs of the timed region: kernels of the other streams share the chip with these launches'}
-        roof_hbm = None
-        if 'norm_act' in fam_d:      # the largest HBM-bound family: BatchNorm / InstanceNorm / activations / residual adds
-            flops, secs, n, nbytes = fam_d['norm_act']
-            gbs = nbytes / secs / 1e9
-            hb = hbm_per_step('bn_')
-            roof_hbm = {'bound': 'hbm', 'kernel': 'norm_act', 'achieved': gbs, 'peak': 8000.0, 'unit': 'GB/s', 'frac': gbs / 8000.0,
-                        'traffic': (hb / (n / detail_steps)) if hb is not None else None, 'algorithmic_bytes_per_launch': nbytes / n,
-                        'launches': n, 'avg_launch_ms': secs / n * 1e3, 'ms_per_step': secs / detail_steps * 1e3,
-                        'note': 'a launch = one normalisation+activation op (forward: statistics unless the conv epilogue made them + apply; '
-                                'backward: reduce + apply), timed in %d extra untimed steps' % detail_steps}
+                    rec['algorithmic_gbs'] = nbytes / secs / 1e9
+                    rec['algorithmic_bytes_per_step'] = nbytes / steps
+                hb = hbm_per_step(*PMC_KEYS.get(k, ()))
+                if hb is not None:
+                    rec['hbm_bytes_per_step'] = hb
+                    if nbytes > 0:
+                        rec['traffic_over_algorithmic'] = hb / (nbytes / steps)
+                fam_out[k] = rec
+            dom = 'conv_igemm' if 'conv_igemm' in fam else (max(fam, key=lambda k: fam[k][1]) if fam else None)
+            roof = None
+            if dom:
+                flops, secs, n, alg_bytes = fam[dom]
+                ach = flops / secs / 1e12
+                hb = hbm_per_step(*PMC_KEYS.get(dom, ()))
+                # the dense conv kernels contract on the bf16 matrix cores in --precision bf16: price them against THAT peak (they are then
+                # staging-bound -- LDS-DMA / LDS reads of the fp32 patch -- far below it)
+                peak = PEAK_BF16_TFLOPS if args.precision == 'bf16' else PEAK_F32_TFLOPS
+                # how precision "f32" multiplies (dpf_get_f32_matrix_path): 0 = fp32 MFMA only, 1 = six bf16 partial products per fp32 product,
+                # 2 = three f16 partial products of block-scaled two-way splits -- the ceiling of the split paths is the 16-bit pipe's dense peak
+                # divided by the products per fp32 product (x 27/28: 27 taps in 7 groups of 4)
+                from dualpixelface_amd._lib import lib as _dpf_lib
+                mpath = int(_dpf_lib().cdll.dpf_get_f32_matrix_path())
+                nprod = {1: 6.0, 2: 3.0}.get(mpath, 6.0)
+                pipe_name = {1: 'six bf16 partial products of exact three-way splits', 2: 'three f16 partial products of block-scaled two-way splits'}.get(mpath, 'fp32 MFMA')
+                x6_flop_per_clk = 1024 * (32 * 32 * 16 * 2 / 32.0) / nprod * 27.0 / 28.0     # fp32 FLOP per shader clock of the split construction
+                x6_peak = x6_flop_per_clk * 2.4e9 / 1e12
+                f32_frac_pipe = None
+                if args.precision == 'f32' and dom == 'conv_igemm':
+                    # The family mixes two pipes: stride-1 launches with >= 8 input channels multiply on the bf16 pipe (six partial products per fp32
+                    # product: ceiling 2.5 PFLOP/s / 6 x 27/28), the rest (stride 2, the 3-channel first layer) on v_mfma_f32_32x32x2_f32 (157.3).
+                    # `peak` is the FLOP-weighted (harmonic) blend of the two -- the rate at which the family would run with every launch at ITS
+                    # pipe's dense peak -- so that `frac` cannot exceed 1 (157.3 is not the peak of a bf16-pipe kernel).
+                    on_bf16 = lambda tag: mpath > 0 and (' s1 ' in tag) and not any((' C%d ' % c) in tag for c in range(1, 8)) and ' k111 ' not in tag
+                    fl_b = sum(r[1] for r in prof if r[0] == dom and on_bf16(r[4]))
+                    fl_f = sum(r[1] for r in prof if r[0] == dom and not on_bf16(r[4]))
+                    if fl_b + fl_f > 0:
+                        peak = (fl_b + fl_f) / (fl_b / x6_peak + fl_f / PEAK_F32_TFLOPS)
+                        f32_frac_pipe = fl_b / (fl_b + fl_f)
+                inline_ms = sum(v[1] for v in fam.values()) / prof_steps * 1e3
+                roof = {'bound': 'mfma', 'kernel': dom, 'achieved': ach, 'peak': peak, 'unit': 'TFLOP/s', 'frac': ach / peak,
+                        'traffic': (hb / (n / prof_steps)) if hb is not None else None, 'traffic_source': traffic_source, 'algorithmic_bytes_per_launch': alg_bytes / n, 'launches': n,
+                        'avg_launch_ms': secs / n * 1e3, 'ms_per_step': secs / prof_steps * 1e3,
+                        'measured_in': ('%d steps after the timed region on ONE stream (weight gradients in line, feature passes one after the other: kernels do not overlap, event time = kernel time)' % prof_steps)
+                                       if not args.no_detail else 'the timed region', 'families': fam_out}
+                if args.precision != 'bf16':
+                    # (see the blend above: `peak` prices every launch at the dense peak of the pipe it runs on)
+                    roof['peak_note'] = ('FLOP-weighted blend of the pipes the launches run on: %.0f %% of the family\'s fp32 FLOPs multiply on the 16-bit matrix pipe '
+                                         '(%s: 2.5 PFLOP/s / %d x 27/28 = %.1f TFLOP/s of fp32 FLOPs at 2.4 GHz), the rest on '
+                                         'v_mfma_f32_32x32x2_f32 (157.3)' % (100.0 * (f32_frac_pipe or 0.0), pipe_name, int(nprod), x6_peak))
+                    roof['f32_matrix_path'] = mpath
+                    roof['frac_of_f32_mfma_peak'] = ach / PEAK_F32_TFLOPS        # the dtype's own dense peak (individual bf16-pipe launches exceed it)
+                    if clock_mhz:
+                        # the bf16-pipe share priced at the clock the chip HOLDS under that stream (power-bound: MI355X_MICROARCH.md, DVFS)
+                        held_b = x6_flop_per_clk * clock_mhz * 1e6 / 1e12
+                        fb = f32_frac_pipe if f32_frac_pipe is not None else 1.0
+                        held = 1.0 / (fb / held_b + (1.0 - fb) / PEAK_F32_TFLOPS)
+                        roof['shader_clock_mhz_under_conv_load'] = clock_mhz
+                        roof['split_pipe_issue_ceiling_at_held_clock'] = held_b
+                        roof['peak_at_held_clock'] = held
+                        roof['frac_of_peak_at_held_clock'] = ach / held
+                if dom in fam_t and timed_async and not args.no_detail:      # the same family as the timed region saw it (overlapped by the side stream)
+                    f2 = fam_t[dom]
+                    roof['timed_region_overlapped'] = {'achieved': f2[0] / f2[1] / 1e12, 'frac': f2[0] / f2[1] / 1e12 / peak, 'avg_launch_ms': f2[1] / f2[2] * 1e3,
+                                                       'note': 'event pairs of the timed region: kernels of the other streams share the chip with these launches'}
+            roof_hbm = None
+            if 'norm_act' in fam_d:      # the largest HBM-bound family: BatchNorm / InstanceNorm / activations / residual adds
+                flops, secs, n, nbytes = fam_d['norm_act']
+                gbs = nbytes / secs / 1e9
+                hb = hbm_per_step('bn_')
+                roof_hbm = {'bound': 'hbm', 'kernel': 'norm_act', 'achieved': gbs, 'peak': 8000.0, 'unit': 'GB/s', 'frac': gbs / 8000.0,
+                            'traffic': (hb / (n / detail_steps)) if hb is not None else None, 'algorithmic_bytes_per_launch': nbytes / n,
+                            'launches': n, 'avg_launch_ms': secs / n * 1e3, 'ms_per_step': secs / detail_steps * 1e3,
+                            'note': 'a launch = one normalisation+activation op (forward: statistics unless the conv epilogue made them + apply; '
+                                    'backward: reduce + apply), timed in %d extra untimed steps' % detail_steps}
+            executed = sum(v[0] for k, v in fam.items()) / prof_steps       # FLOPs the kernels really ran per step (GEMM parts; compat mode runs 2 of the 16 attention calls)
         pixels = args.height * args.width
-        executed = sum(v[0] for k, v in fam.items()) / prof_steps       # FLOPs the kernels really ran per step (GEMM parts; compat mode runs 2 of the 16 attention calls)
         line = {
             'metric': 'train samples/sec, %s %dx%d DP pair' % ({'psmnet': 'PSMNet', 'nnet': 'NNet', 'stereonet': 'StereoNet'}.get(args.model, 'StereoDPNet'), args.height, args.width), 'value': value, 'unit': 'samples/s', 'n_gpus': world,
             'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
@@ -525,16 +595,20 @@ def main():
                                      '*_in_block_dynamic_range; tests/test_gpu_e2e.py::test_headline_config_whole_train_step ties it to path 0 at this size)'},
             'rccl_ranks_seen': ranks_seen,
             'collective_backend': (dist.get_backend() if dist.is_initialized() else None),
-            'gradient_collectives_per_step': (reducer.collective_calls / float(args.warmup + args.steps + (0 if args.no_detail else 4))) if reducer is not None else 0,
+            'gradient_collectives_per_step': (reducer.collective_calls / float(args.warmup + args.steps + (4 if detail else 0))) if reducer is not None else 0,
             # whole-model fractions of the fp32 peak: against the reference's algorithmic FLOPs (SURVEY section 8d counts all 16 attention
             # calls) and against the FLOPs the kernels executed (compat mode computes 2 of the 16: identical results)
             'flop_frac_of_f32_peak': (value * FLOP_PER_PIXEL_FWD_BWD * pixels / (world * PEAK_F32_TFLOPS * 1e12)) if args.model == 'stereodpnet' else None,
-            'flop_frac_executed': executed * args.steps / elapsed / (PEAK_F32_TFLOPS * 1e12),
-            'executed_tflop_per_step': executed / 1e12,
-            'roofline': roof,
-            'roofline_hbm': roof_hbm,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line.update({
+                'restart_ms_per_step': restart_ms,
+                'flop_frac_executed': executed * args.steps / elapsed / (PEAK_F32_TFLOPS * 1e12),
+                'executed_tflop_per_step': executed / 1e12,
+                'roofline': roof,
+                'roofline_hbm': roof_hbm,
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # 16 threads: the oracle's small-tensor PyTorch-CPU ops scale badly beyond that (256 threads on the 128-core
             # host took 740 s for the same sample that 8-16 threads finish in ~10-20 s)
             line['cpu_baseline'] = cpu_baseline(min(16, os.cpu_count() or 1))

@@ -244,3 +244,59 @@ def test_bench_force_dist_one_rank_nccl():
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
     assert line['collective_backend'] == 'nccl' and line['rccl_ranks_seen'] == 1 and line['n_gpus'] == 1
     assert abs(line['gradient_collectives_per_step'] - 3.0) < 1e-9, line['gradient_collectives_per_step']
+
+
+def test_bench_plain_full_and_dump_outputs(tmp_path):
+    """bench.py --gpus 1 as every change is measured: a plain run prints the headline fields and nothing that needs steps of its own;
+    --dump-outputs writes what the last timed step computed (results, updated parameters, gradients); --steps sets the number of timed
+    train steps; every timed step restarts from the same state, so two runs -- even with different --steps -- dump the same outputs up
+    to one step's run-to-run noise; --full adds the second matrix path, the roofline blocks and the restart's time."""
+    import json
+    import subprocess
+    import numpy as np
+    # runs bench.py as __main__ with plugin train_step calls counted
+    counted = ("import runpy, sys\n"
+               "import dualpixelface_amd.plugin as p\n"
+               "calls = [0]\n"
+               "step = p._PluginHooks.train_step\n"
+               "def counted(self, *a, **k):\n"
+               "    calls[0] += 1\n"
+               "    return step(self, *a, **k)\n"
+               "p._PluginHooks.train_step = counted\n"
+               "sys.argv = sys.argv[1:]\n"
+               "runpy.run_path(sys.argv[0], run_name='__main__')\n"
+               "print('train_step calls %d' % calls[0])\n")
+
+    def run(steps, *extra):
+        cmd = [sys.executable, '-c', counted, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '1',
+               '--batch', '1', '--height', '64', '--width', '96'] + list(extra)
+        r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:]
+        calls = int([ln for ln in r.stdout.splitlines() if ln.startswith('train_step calls')][-1].split()[-1])
+        return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1]), calls
+
+    def load(d):
+        return {n[:-4]: np.load(str(d / n)) for n in os.listdir(str(d))}
+    plain, calls = run(2, '--dump-outputs', str(tmp_path / 'dump'))
+    assert calls == 4 + 2                                  # warm-up: at least 4 steps (graph capture on the third), then the 2 timed ones
+    assert plain['steps'] == 2 and plain['warmup'] == 1 and plain['unit'] == 'samples/s' and plain['higher_is_better'] is True
+    assert plain['dtype'] == 'f32' and abs(plain['value'] - 1e3 / plain['ms_per_step']) <= 1e-6 * plain['value']
+    assert not {'roofline', 'roofline_hbm', 'cpu_baseline', 'flop_frac_executed', 'restart_ms_per_step'} & set(plain)
+    assert plain['f32_products']['value_with_exact_splits_path1'] is None
+    dump = load(tmp_path / 'dump')
+    assert {'final_loss', 'pred_depth', 'pred_normal', 'parameters', 'gradients'} <= set(dump), sorted(dump)
+    assert sum(v.nbytes for v in dump.values()) <= 64 * 10 ** 6
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in dump.values())
+    assert abs(float(dump['final_loss']) - plain['final_loss']) <= 1e-6 * abs(plain['final_loss'])
+    assert dump['parameters'].size == dump['gradients'].size > 10 ** 6 and np.abs(dump['gradients']).max() > 0
+    again, calls = run(5, '--dump-outputs', str(tmp_path / 'dump2'))
+    assert calls == 4 + 5 and again['steps'] == 5
+    dump2 = load(tmp_path / 'dump2')
+    assert abs(float(dump2['final_loss']) - float(dump['final_loss'])) <= 1e-4 * abs(float(dump['final_loss']))
+    assert np.abs(dump2['pred_depth'] - dump['pred_depth']).max() <= 1e-3 * np.abs(dump['pred_depth']).max()
+    assert np.abs(dump2['parameters'] - dump['parameters']).max() <= 2.1e-4       # one Adam step from the same state: at most 2 x lr apart
+    full, calls = run(2, '--full', '--no-cpu-baseline')
+    assert calls > 4 + 2                                   # the exact-split and one-stream detail steps come after the timed ones
+    assert full['roofline']['kernel'] == 'conv_igemm' and full['roofline_hbm']['kernel'] == 'norm_act' and full['executed_tflop_per_step'] > 0
+    assert full['f32_products']['value_with_exact_splits_path1'] > 0
+    assert 0 < full['restart_ms_per_step'] < 0.01 * full['ms_per_step']

@@ -195,3 +195,26 @@ def test_every_environment_switch_is_documented():
     missing = sorted(v for v in found if v not in switches and v != 'DPF_ONE_DEVICE')
     assert not missing, missing
     assert len(found) <= 40, (len(found), 'collapse switches that have a measured winner')
+
+
+def test_bench_dump_outputs_fixed_sample_within_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: small arrays keep their shape, the rest share what is left of the byte budget as a seeded sample whose
+    indices depend only on the shapes (two dumps of the same arrays are identical); float64 stays float64, everything else is float32."""
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 40000)
+    g = torch.Generator().manual_seed(0)
+    arrays = {'loss': torch.tensor(1.5), 'ab': torch.randn(2, 2, generator=g, dtype=torch.float64), 'big': torch.randn(40, 100, generator=g),
+              'bigger': torch.randn(7000, generator=g), 'mask': torch.ones(3, 4, dtype=torch.uint8), 'none': None}
+    bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    bench.dump_outputs(str(tmp_path / 'b'), arrays)
+    names = sorted(os.listdir(str(tmp_path / 'a')))
+    assert names == ['ab.npy', 'big.npy', 'bigger.npy', 'loss.npy', 'mask.npy']
+    out = {n[:-4]: np.load(str(tmp_path / 'a' / n)) for n in names}
+    for n in names:
+        assert np.array_equal(out[n[:-4]], np.load(str(tmp_path / 'b' / n)))
+    assert out['ab'].dtype == np.float64 and np.array_equal(out['ab'], arrays['ab'].numpy())
+    assert out['loss'].dtype == np.float32 and out['loss'].shape == () and out['loss'] == 1.5
+    assert out['mask'].dtype == np.float32 and out['mask'].shape == (3, 4)
+    assert np.array_equal(out['big'], arrays['big'].numpy())          # 16 kB: within its half of what the small arrays left
+    assert out['bigger'].ndim == 1 and 0 < out['bigger'].size < 7000 and np.isin(out['bigger'], arrays['bigger'].numpy()).all()
+    assert sum(v.nbytes for v in out.values()) <= 40000

@@ -19,7 +19,7 @@ pmc_pass pmc_f FETCH_SIZE; pmc_pass pmc_w WRITE_SIZE
 python3 tools/pmc_traffic.py gpurun_out/pmc_f/p_counter_collection.csv gpurun_out/pmc_w/p_counter_collection.csv "$O/${R}_pmc_traffic.json" 3
 gzip -c gpurun_out/pmc_f/p_counter_collection.csv > "$O/${R}_pmc_fetch_raw.csv.gz"; gzip -c gpurun_out/pmc_w/p_counter_collection.csv > "$O/${R}_pmc_write_raw.csv.gz"
 mkdir -p profiles; cp "$O/${R}_pmc_traffic.json" profiles/
-run python bench.py --steps 10 --warmup 3 --shapes "$O/${R}_conv_shape_table.txt" > "$O/${R}_bench.json"
+run python bench.py --full --steps 10 --warmup 3 --shapes "$O/${R}_conv_shape_table.txt" > "$O/${R}_bench.json"
 bash tools/gpu_prof.sh "$R" > "$O/${R}_bench_family_ms.txt" 2>&1
 cp "gpurun_out/prof_${R}_kernel_stats.csv" "$O/${R}_bench_kernel_stats.csv"
 export PMC_FILTER="igemm3 igemm2 wgrad2 dcn_ pointwise bn_"
@@ -28,13 +28,13 @@ if [ -z "$QUICK" ]; then
   pmc_pass pmc_f3 FETCH_SIZE --precision bf16; pmc_pass pmc_w3 WRITE_SIZE --precision bf16
   python3 tools/pmc_traffic.py gpurun_out/pmc_f3/p_counter_collection.csv gpurun_out/pmc_w3/p_counter_collection.csv "$O/${R}_pmc_traffic_bf16.json" 3
   cp "$O/${R}_pmc_traffic_bf16.json" profiles/
-  run python bench.py --height 512 --width 768 --no-cpu-baseline > "$O/${R}_bench_c2_512x768.json"
-  run python bench.py --model psmnet --batch 2 --no-cpu-baseline > "$O/${R}_bench_c4_psmnet_train.json"
-  run python bench.py --precision bf16 --no-cpu-baseline --shapes "$O/${R}_conv_shape_table_bf16.txt" > "$O/${R}_bench_c5_bf16_b4.json"
-  run python bench.py --precision bf16 --batch 8 --no-cpu-baseline > "$O/${R}_bench_c5_bf16_b8.json"
-  run python bench.py --wgrad-inline --no-cpu-baseline > "$O/${R}_bench_wgrad_inline.json"
-  run python bench.py --model nnet --batch 2 --no-cpu-baseline > "$O/${R}_bench_nnet_train.json"
-  run python bench.py --model stereonet --no-cpu-baseline > "$O/${R}_bench_stereonet_train.json"
+  run python bench.py --full --height 512 --width 768 --no-cpu-baseline > "$O/${R}_bench_c2_512x768.json"
+  run python bench.py --full --model psmnet --batch 2 --no-cpu-baseline > "$O/${R}_bench_c4_psmnet_train.json"
+  run python bench.py --full --precision bf16 --no-cpu-baseline --shapes "$O/${R}_conv_shape_table_bf16.txt" > "$O/${R}_bench_c5_bf16_b4.json"
+  run python bench.py --full --precision bf16 --batch 8 --no-cpu-baseline > "$O/${R}_bench_c5_bf16_b8.json"
+  run python bench.py --full --wgrad-inline --no-cpu-baseline > "$O/${R}_bench_wgrad_inline.json"
+  run python bench.py --full --model nnet --batch 2 --no-cpu-baseline > "$O/${R}_bench_nnet_train.json"
+  run python bench.py --full --model stereonet --no-cpu-baseline > "$O/${R}_bench_stereonet_train.json"
   run python bench.py --workload cost_volume --no-cpu-baseline > "$O/${R}_bench_cost_volume_stage.json"
   run python bench.py --workload cost_volume_fix --no-cpu-baseline > "$O/${R}_bench_cost_volume_fix_stage.json"
   run python bench.py --workload psm_volume --batch 2 --no-cpu-baseline > "$O/${R}_bench_psm_volume.json"
