@@ -113,6 +113,12 @@ def zero_slot(nfloats, device):
     return slot
 
 
+def workspace_buffers():
+    """Every buffer `scratch` and `zero_slot` currently hand out (all devices, tags and streams).  A captured graph bakes their addresses
+    in while the dicts above may replace them later: the train step's graph states hold these references (plugin._graph_step)."""
+    return list(_scratch.values()) + [st[0] for st in _zero_arena.values()]
+
+
 def _host_floats(vals):
     return (ctypes.c_float * len(vals))(*[float(v) for v in vals])
 

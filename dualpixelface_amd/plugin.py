@@ -158,6 +158,7 @@ class _PluginHooks(object):
             counts_before = dict(self._pending_counts)
             step_before = ad['step']
             self._flush_counts()
+            baked = self._baked_buffers()                  # (before AND after: a buffer replaced mid-capture was baked in as well)
             graph = torch.cuda.CUDAGraph()
             try:
                 torch.cuda.synchronize()
@@ -180,6 +181,7 @@ class _PluginHooks(object):
                 st['counts'] = dict(self._pending_counts)            # BatchNorm call counters one step adds (host-side bookkeeping)
                 self._pending_counts = {}
                 ad['step'] -= 1                                      # the capture only RECORDED the step: nothing ran
+                st['owned'] = baked + self._baked_buffers()          # released when the LRU above drops the state
                 st['graph'] = graph
             except Exception as e:                                   # capture refused (unsupported call inside): stay eager, say so once
                 import warnings
@@ -211,6 +213,28 @@ class _PluginHooks(object):
         for name, n in st['counts'].items():
             self._pending_counts[name] = self._pending_counts.get(name, 0) + n
         return dict(st['results'])                         # (a fresh dict; the tensors are the graph's static buffers, valid until the next step)
+
+    def _baked_buffers(self):
+        """The device tensors whose addresses a capture of the step bakes in, besides the state's own inputs, hyper-parameter slot and
+        results.  A graph state holds them for as long as it can replay, so none of them is ever freed and handed to another tensor that
+        the next replay would then overwrite:
+          * ops.workspace_buffers(): the scratch slabs and pre-zeroed arenas of every stream the step runs on (step, second feature pass,
+            weight-gradient side stream).  A later call that needs more room replaces them -- an eager step or a validation at a larger
+            shape, on the replays' own stream (_behind_replays);
+          * lazily built shape constants: StereoDPNet's sampler tables (`_tables`: only added to, but re-created by a device move) and
+            NNet's cost-level volume (`_levels`: replaced whenever the batch shape changes);
+          * the parameter, gradient and Adam arenas and the BatchNorm buffers: updated in place, and the arenas' addresses are part of the
+            key -- held, a key match can never mean a new tensor at a recycled address.
+        Not buffers: `_pairs_cache` (views of the gradient arena), the shared streams (`ops._wgrad_side`, the feature stream); the
+        normal head's lazily registered `grid` is read by no kernel and only ever written in place."""
+        found = ops.workspace_buffers() + list(self.buffers()) + [self.flat_parameters(), self.flat_gradients(zero=False)]
+        if self._adam:
+            found += [self._adam['m'], self._adam['v']]
+        for tables, phase in getattr(self, '_tables', {}).values():
+            found += [t for t in tuple(tables) + tuple(phase or ()) if torch.is_tensor(t)]
+        if getattr(self, '_levels', None) is not None:
+            found.append(self._levels)
+        return found
 
     def _behind_replays(self, fn):
         """Once a train step of this model replays as a HIP graph, everything the model launches one by one (an eager step, forward,

@@ -962,6 +962,139 @@ def _alternate(a, b, batch):
     assert np.isfinite(float(ra['final_loss'])) and torch.isfinite(a.flat_parameters()).all() and torch.isfinite(va['pred_depth']).all()
 
 
+def _workspace_refs(model):
+    """{name: (weak reference, address)} of every process-wide workspace and every sampler table of `model` -- the device buffers a
+    capture of its train step may bake in besides its own arenas (plugin._baked_buffers).  No strong reference is kept."""
+    import weakref
+    from dualpixelface_amd import ops
+    bufs = [(('scratch',) + k, t) for k, t in ops._scratch.items()]
+    bufs += [(('zero',) + k, st[0]) for k, st in ops._zero_arena.items()]
+    bufs += [(('tables',) + k + (i,), t) for k, (tables, _) in model._tables.items() for i, t in enumerate(tables)]
+    return {name: (weakref.ref(t), t.data_ptr()) for name, t in bufs}
+
+
+def _dev(batch):
+    return {k: v.to(DEV) for k, v in batch.items()}
+
+
+def _fresh_workspaces():
+    """Start from no process-wide workspace, as a fresh process does: earlier tests have grown them past the shapes used below, and the
+    larger shape must really replace buffers a graph was captured with.  (The graph states of earlier models own what they baked in.)"""
+    from dualpixelface_amd import ops
+    torch.cuda.synchronize()
+    ops._scratch.clear()
+    ops._zero_arena.clear()
+
+
+def test_graph_state_keeps_the_workspaces_it_was_captured_with_alive():
+    """A captured train step bakes in the addresses of the process-wide scratch slabs and pre-zeroed arenas (ops.scratch / ops.zero_slot),
+    which a later call at a larger shape replaces -- on the replays' own stream, where the caching allocator hands the freed block to the
+    next tensor.  Capture at 2 x 32x48, then run a validation forward and the two eager warm-up steps of 2 x 64x96 (in deterministic mode
+    the deformable convolution's backward workspace grows with the batch volume): at least one slab must have been replaced (else this
+    test probes nothing), and before any further replay every buffer the live graph was captured with must still be alive."""
+    from dualpixelface_amd import ops
+    from dualpixelface_amd.recipe import synthetic_batch
+    small, large = synthetic_batch(2, 32, 48, seed=31, mask_mode='bern'), synthetic_batch(2, 64, 96, seed=32, mask_mode='bern')
+    _fresh_workspaces()
+    with ops.deterministic_mode():
+        model = build_model(True)
+        model.option.step_graph = True
+        for _ in range(4):                                 # eager calls (the first one creates the Adam state), then the capture + replay
+            model.train_step(_dev(small))
+        torch.cuda.synchronize()
+        live = model._graph_state
+        assert live.get('graph') is not None
+        refs = _workspace_refs(model)
+        model.eval()
+        with torch.no_grad():
+            model(_dev(large))
+        model.train()
+        for _ in range(2):
+            model.train_step(_dev(large))
+        torch.cuda.synchronize()
+        assert any(st is live for st in model._graph_states) and model._graph_state['graph'] is None
+        replaced = [name for name, (_, ptr) in refs.items() if name[0] == 'scratch' and ops._scratch[name[1:]].data_ptr() != ptr]
+        assert replaced, 'no workspace grew at the larger shape: the regime is not probed'
+        dead = [name for name, (ref, _) in refs.items() if ref() is None]
+        assert not dead, 'freed while a graph captured with them can still replay: %s' % dead
+
+
+def _assert_twins_equal(a, b, ra, rb, what):
+    """Graph-mode model `a` and eager twin `b` after the same call: results, parameters, Adam state and every state_dict tensor, bitwise."""
+    assert set(ra) == set(rb), (what, sorted(ra), sorted(rb))
+    for k, v in rb.items():
+        if torch.is_tensor(v):
+            assert torch.equal(ra[k], v), (what, k)
+    assert torch.equal(a.flat_parameters(), b.flat_parameters()), what
+    if b._adam is not None:
+        assert a._adam['step'] == b._adam['step'], (what, a._adam['step'], b._adam['step'])
+        assert torch.equal(a._adam['m'], b._adam['m']) and torch.equal(a._adam['v'], b._adam['v']), what
+    sa, sb = a.state_dict(), b.state_dict()
+    assert set(sa) == set(sb), what
+    diff = [k for k in sb if not torch.equal(sa[k], sb[k])]
+    assert not diff, (what, diff[:8])
+
+
+def test_graph_replays_across_shape_changes_equal_an_eager_twin():
+    """Graph replays interleaved with larger shapes, the way an epoch of the shipped recipe runs (0.75-size training crops, full-size
+    validation, a partial last batch): a graph-mode model and an eager twin (step_graph off, same recipe weights, same inputs) must stay
+    bitwise equal in deterministic mode after every step and every validation forward -- results, parameters, Adam moments and step,
+    running statistics and call counters.  Shapes: S = 2 x 32x48 (captured), L = 2 x 64x96, S' = 1 x 32x48 (the partial batch: a second
+    graph), L trained as a third graph (the LRU of three states drops the key of the very first step, taken before the Adam state
+    existed) -- which regrows the workspaces the S and S' graphs were captured with --, then replays of S and S', a 1 x 64x96 key that
+    evicts the L state, and S again.  The outputs of every validation stay alive as GPU tensors and must not change (a replay writing
+    into a freed and reused block would land there).  The second L validation, taken after replays, also matches the fp64 oracle built
+    from the twin's current weights and statistics."""
+    from oracle.stereodpnet import StereoDPNetOracle
+    from dualpixelface_amd import ops
+    from dualpixelface_amd.recipe import synthetic_batch
+    S, L, S1, L1 = (2, 32, 48), (2, 64, 96), (1, 32, 48), (1, 64, 96)
+    plan = [('train', S)] * 4 + [('eval', L)] + [('train', S)] * 2 + [('train', S1)] * 3 + [('eval', L)] + [('train', L)] * 3 + \
+           [('eval', L), ('train', S), ('train', S1), ('train', L1)] + [('train', S)] * 2
+    _fresh_workspaces()
+    with ops.deterministic_mode():
+        a, b = build_model(True), build_model(True)
+        a.option.step_graph, b.option.step_graph = True, False
+        canary, evals, refs = {}, 0, None
+        for i, (kind, shape) in enumerate(plan):
+            batch = synthetic_batch(*shape, seed=40 + i, mask_mode='bern')
+            what = '%d: %s %s' % (i, kind, shape)
+            if kind == 'train':
+                if i == 15:                                # the first replay of S after the L steps: the regime must really be probed
+                    assert [n for n, (_, ptr) in refs.items() if n[0] == 'scratch' and ops._scratch[n[1:]].data_ptr() != ptr], what
+                lr = 2e-4 / (1 + i % 3)
+                ra = a.train_step(_dev(batch), lr=lr)
+                rb = b.train_step(_dev(batch), lr=lr)
+            else:
+                ra, rb = {}, {}
+                for m, r in ((a, ra), (b, rb)):
+                    m.eval()
+                    with torch.no_grad():
+                        r.update(m(_dev(batch)))
+                    m.train()
+            torch.cuda.synchronize()
+            _assert_twins_equal(a, b, ra, rb, what)
+            if i == 3:
+                assert a._graph_state['graph'] is not None
+                refs = _workspace_refs(a)
+            if kind == 'eval':
+                evals += 1
+                canary.update({(i, k): (v, v.cpu()) for k, v in ra.items() if torch.is_tensor(v)})
+                if evals == 2:
+                    state = {k: (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu()) for k, v in b.state_dict().items()}
+                    orc = StereoDPNetOracle(state, training=False)
+                    with torch.no_grad():
+                        ref = orc.forward({k: v.double() for k, v in batch.items()})
+                    close(a.last_taps['volume'], orc.taps['volume'], 2e-4, what + ' volume')
+                    close(ra['pred_depth'], ref['pred_depth'], None, what + ' pred_depth', atol=3e-3)
+                    close(ra['pred_normal'], ref['pred_normal'], None, what + ' pred_normal', atol=1e-3)
+            changed = [k for k, (gpu, cpu) in canary.items() if not torch.equal(gpu.cpu(), cpu)]
+            assert not changed, (what, 'a validation output held on the GPU changed', changed)
+        # left: S' (3 calls + 1 replay), 1 x 64x96 (one warm-up, no graph), S (8 calls: the very first step had a key of its own)
+        states = [(st['calls'], st['graph'] is not None, bool(st.get('failed'))) for st in a._graph_states]
+        assert states == [(4, True, False), (1, False, False), (8, True, False)], states
+
+
 def test_c5_bf16_whole_step_full_size():
     """BASELINE configs[4] as a test: the bf16 mixed-precision mode (option.precision = 'bf16': the dense convolutions round
     their operands to bf16 while staging them -- PL's `precision: 16` for nn.Conv2d / nn.Conv3d, reference hook main.py:53 -- fp32 accumulation,

@@ -185,3 +185,37 @@ def test_main_py_train_checkpoint_then_test_on_a_facedp_dataset(tmp_path):
     assert r.returncode == 0, r.stderr[-3000:]
     for name in ('absolute_dp', 'affine_dp', 'normal_dp'):
         assert name in r.stdout, r.stdout[-2000:]
+
+
+def test_fit_with_step_graphs_equals_eager_fit_across_full_size_validation(tmp_path):
+    """Trainer.fit as the shipped recipe runs it: three epochs of small training crops (7 samples in batches of 2: every epoch ends on a
+    partial batch, a second graph key) with a validation at a larger size after every epoch, once with the train step as a HIP graph
+    and once with eager launches, both in deterministic mode.  Parameters, Adam state, running statistics, logged losses and
+    validation metrics must be the same bits -- and the graph run must really have captured and replayed."""
+    from dualpixelface_amd import load_option, ops
+    from dualpixelface_amd.synthetic_data import synthetic_loader
+    from dualpixelface_amd.trainer import Trainer
+    runs = []
+    with ops.deterministic_mode():
+        for graph in (True, False):
+            opt = load_option()
+            opt.epoch, opt.init_lr, opt.scheduler, opt.step_graph = 3, 1e-3, 'explr', graph
+            m = _model(opt)
+            tr = Trainer(opt, str(tmp_path / ('graph' if graph else 'eager')), log_every=1, rank=0, world_size=1)
+            hist = tr.fit(m, synthetic_loader(7, 32, 48, batch_size=2, seed=5), synthetic_loader(2, 64, 96, batch_size=1, seed=6))
+            torch.cuda.synchronize()
+            assert tr.global_step == 12
+            runs.append((m, [h for h in hist if 'epoch_seconds' not in h]))
+    (a, ha), (b, hb) = runs
+    states = [(st['calls'], st['graph'] is not None, bool(st.get('failed'))) for st in a._graph_states]
+    # the first call (before the Adam state exists) has a key of its own; then 8 full batches and 3 partial ones: both captured
+    assert states == [(1, False, False), (8, True, False), (3, True, False)], states
+    assert not getattr(b, '_graph_states', None)
+    assert sum('metrics' in h for h in ha) == 3 and ha == hb, (ha, hb)
+    assert torch.equal(a.flat_parameters(), b.flat_parameters())
+    assert a._adam['step'] == b._adam['step'] == 12
+    assert torch.equal(a._adam['m'], b._adam['m']) and torch.equal(a._adam['v'], b._adam['v'])
+    sa, sb = a.state_dict(), b.state_dict()
+    assert set(sa) == set(sb)
+    diff = [k for k in sb if not torch.equal(sa[k], sb[k])]
+    assert not diff, diff[:8]
