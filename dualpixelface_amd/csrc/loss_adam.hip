@@ -3,6 +3,7 @@
 //   loss  : reference src/loss/loss_selector.py:29-42, src/loss/depth/smoothL1.py:15-49 ('given' conversion, target
 //           'disp'), src/loss/normal/cosine.py:15-53 (the per-channel, non-summed cosine of SURVEY Q11)
 //   Adam  : torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-5) as configured by src/model/model_selector.py:31-34
+//   SGD / RMSprop : torch.optim.SGD(lr, momentum=0.9, weight_decay=2e-4) / torch.optim.RMSprop(lr, eps=1e-5), model_selector.py:36,38
 // One reduction pass over the full-resolution maps (HBM-bound, reads 4+3+1+3+1 planes once), no boolean-mask gather.
 #include "dpf_common.h"
 
@@ -172,6 +173,76 @@ __global__ void adam_hyper_kernel(float* __restrict__ p, const float* __restrict
   }
 }
 
+// ---- SGD with momentum and RMSprop over the same flat arenas.  One kernel per optimiser serves both entry points (lr as an argument /
+// lr in device memory), so a captured replay and an eager step run the same instructions.  fmaf is written out: the rounding of an
+// element must not depend on whether it sits in the 16-byte body or in the scalar head / tail.
+struct SgdOp {
+  float gscale, momentum, wd;
+  __device__ __forceinline__ void operator()(float& p, float g, float& buf, float lr) const {
+    const float d = fmaf(wd, p, g * gscale);               // weight decay joins the already scaled gradient
+    buf = fmaf(momentum, buf, d);                          // (torch seeds buf = d on the first step: 0.9 * 0 + d is the same float)
+    p = fmaf(-lr, buf, p);
+  }
+};
+struct RmsOp {
+  float gscale, alpha, oma, eps;
+  __device__ __forceinline__ void operator()(float& p, float g, float& sq, float lr) const {
+    const float gi = g * gscale;
+    sq = fmaf(alpha, sq, oma * gi * gi);
+    p = p - lr * gi / (sqrtf(sq) + eps);                   // eps outside the root
+  }
+};
+
+// elements [head, head + 4 * nvec) as 16-byte vectors (the host picks `head` so that all three arenas are 16-byte aligned there, or
+// head = n when they cannot be), the <= 3 + 3 elements around them one by one.  live: one byte per element, 0 = leave parameter and
+// state exactly as they are (nullptr: every element is live).
+template <class Op>
+__global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s,
+                                                    const unsigned char* __restrict__ live, long long n, long long head, float lr_arg,
+                                                    const float* __restrict__ lr_dev, Op op) {
+  const float lr = lr_dev ? lr_dev[0] : lr_arg;
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+  const long long nvec = (n - head) / 4;
+  for (long long v = tid; v < nvec; v += stride) {
+    const long long i = head + 4 * v;
+    f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
+    f32x4 sv = *reinterpret_cast<const f32x4*>(s + i);
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float pk = pv[k], sk = sv[k];
+      op(pk, gv[k], sk, lr);
+      if (!live || live[i + k]) { pv[k] = pk; sv[k] = sk; }   // (a dead element is stored back with the bits it was loaded with)
+    }
+    *reinterpret_cast<f32x4*>(p + i) = pv;
+    *reinterpret_cast<f32x4*>(s + i) = sv;
+  }
+  const long long tail0 = head + 4 * nvec, nscalar = head + (n - tail0);
+  for (long long k = tid; k < nscalar; k += stride) {
+    const long long i = k < head ? k : tail0 + (k - head);
+    if (live && !live[i]) continue;
+    float pk = p[i], sk = s[i];
+    op(pk, g[i], sk, lr);
+    p[i] = pk;
+    s[i] = sk;
+  }
+}
+
+// first element at which param, grad and state are all 16-byte aligned; n (= everything scalar) when they never are together
+long long optim_head(const float* p, const float* g, const float* s, long long n) {
+  const uintptr_t a = (uintptr_t)p & 15, b = (uintptr_t)g & 15, c = (uintptr_t)s & 15;
+  if (a != b || a != c || (a & 3)) return n;
+  const long long head = (long long)((16 - a) & 15) / 4;
+  return head < n ? head : n;
+}
+
+template <class Op>
+int optim_launch(float* p, const float* g, float* s, const unsigned char* live, long long n, double lr, const float* lr_dev, Op op, void* stream) {
+  hipLaunchKernelGGL(optim_kernel<Op>, dim3(dpf_ew_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, g, s, live, n, optim_head(p, g, s, n),
+                     (float)lr, lr_dev, op);
+  return dpf_check_launch();
+}
+
 void fill(LossP& p, int B, int n, int H, int W, const float* w, float l0, float l1) {
   p.B = B; p.n = n; p.H = H; p.W = W;
   for (int i = 0; i < MAXHEADS; ++i) p.wts[i] = i < n ? w[i] : 0.f;
@@ -232,6 +303,41 @@ int dpf_adam_step_hyper(float* param, const float* grad, float* exp_avg, float* 
   hipLaunchKernelGGL(adam_hyper_kernel, dim3(dpf_ew_grid(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, gscale, hyper,
                      (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);
   return dpf_check_launch();
+}
+
+// One SGD step (momentum, weight decay, no dampening, no Nesterov) over a flat arena of n floats: d = grad * gscale + weight_decay * param;
+// buf = momentum * buf + d; param -= lr * buf.  momentum_buf starts zero-filled.  live: n bytes, 0 = the element belongs to a parameter
+// that received no gradient this step and is left untouched, state included (torch skips .grad is None); NULL = all live.
+int dpf_sgd_step(float* param, const float* grad, float* momentum_buf, const unsigned char* live, long long n, double lr, double momentum,
+                 double weight_decay, float gscale, void* stream) {
+  dpf_clear_error();
+  if (!param || !grad || !momentum_buf || n <= 0) return DPF_ERR_INVALID_ARG;
+  return optim_launch(param, grad, momentum_buf, live, n, lr, nullptr, SgdOp{gscale, (float)momentum, (float)weight_decay}, stream);
+}
+
+// dpf_sgd_step with (float)lr read from device memory (lr_dev[0]): the launch a captured train step replays while the schedule moves on
+int dpf_sgd_step_lr(float* param, const float* grad, float* momentum_buf, const unsigned char* live, long long n, const float* lr_dev,
+                    double momentum, double weight_decay, float gscale, void* stream) {
+  dpf_clear_error();
+  if (!param || !grad || !momentum_buf || !lr_dev || n <= 0) return DPF_ERR_INVALID_ARG;
+  return optim_launch(param, grad, momentum_buf, live, n, 0.0, lr_dev, SgdOp{gscale, (float)momentum, (float)weight_decay}, stream);
+}
+
+// One RMSprop step (no momentum, not centred, no weight decay): sq = alpha * sq + (1 - alpha) * (grad * gscale)^2;
+// param -= lr * grad * gscale / (sqrt(sq) + eps).  square_avg starts zero-filled.
+int dpf_rmsprop_step(float* param, const float* grad, float* square_avg, long long n, double lr, double alpha, double eps, float gscale,
+                     void* stream) {
+  dpf_clear_error();
+  if (!param || !grad || !square_avg || n <= 0) return DPF_ERR_INVALID_ARG;
+  return optim_launch(param, grad, square_avg, nullptr, n, lr, nullptr, RmsOp{gscale, (float)alpha, (float)(1.0 - alpha), (float)eps}, stream);
+}
+
+// dpf_rmsprop_step with (float)lr read from device memory (lr_dev[0])
+int dpf_rmsprop_step_lr(float* param, const float* grad, float* square_avg, long long n, const float* lr_dev, double alpha, double eps,
+                        float gscale, void* stream) {
+  dpf_clear_error();
+  if (!param || !grad || !square_avg || !lr_dev || n <= 0) return DPF_ERR_INVALID_ARG;
+  return optim_launch(param, grad, square_avg, nullptr, n, 0.0, lr_dev, RmsOp{gscale, (float)alpha, (float)(1.0 - alpha), (float)eps}, stream);
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 The model keeps all gradients in one flat arena, so the exchange is an all-reduce(SUM) over a few contiguous slices of
 that arena, launched from autograd hooks as soon as a slice is complete so it overlaps the rest of the backward pass
 (3 670 492 fp32 = 14.7 MB per step; the reference relies on PL's DDP for the same exchange,
-main.py:49).  The division by the world size is fused into the Adam kernel (``gscale``).
+main.py:49).  The division by the world size is fused into the optimiser kernel (``gscale`` of the Adam, SGD and RMSprop steps).
 """
 import os
 

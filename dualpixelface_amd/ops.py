@@ -1547,6 +1547,41 @@ def adam_step_hyper(param, grad, exp_avg, exp_avg_sq, hyper, beta1=0.9, beta2=0.
                float(beta2), float(eps), float(gscale), _stream())
 
 
+def sgd_step(param, grad, momentum_buf, lr, momentum=0.9, weight_decay=2e-4, gscale=1.0, live=None):
+    """torch.optim.SGD(momentum, weight_decay) over the flat arenas.  live: uint8 per element, 0 = belongs to a parameter without a gradient
+    this step and stays untouched, buffer included (None: every element is live)."""
+    _need(param, grad, momentum_buf)
+    lib().call('dpf_sgd_step', _ptr(param), _ptr(grad), _ptr(momentum_buf), _ptr(_live_mask(live, param)), param.numel(), float(lr),
+               float(momentum), float(weight_decay), float(gscale), _stream())
+
+
+def sgd_step_lr(param, grad, momentum_buf, lr_dev, momentum=0.9, weight_decay=2e-4, gscale=1.0, live=None):
+    """sgd_step with the rate in device memory (lr_dev: one float) -- the launch a captured train-step graph replays."""
+    _need(param, grad, momentum_buf, lr_dev)
+    lib().call('dpf_sgd_step_lr', _ptr(param), _ptr(grad), _ptr(momentum_buf), _ptr(_live_mask(live, param)), param.numel(), _ptr(lr_dev),
+               float(momentum), float(weight_decay), float(gscale), _stream())
+
+
+def _live_mask(live, param):
+    if live is not None and not (live.is_cuda and live.dtype == torch.uint8 and live.is_contiguous() and live.numel() == param.numel()):
+        raise DpfError('live mask: one contiguous uint8 per arena element on the GPU expected')
+    return live
+
+
+def rmsprop_step(param, grad, square_avg, lr, alpha=0.99, eps=1e-5, gscale=1.0):
+    """torch.optim.RMSprop(alpha, eps; no momentum, not centred) over the flat arenas."""
+    _need(param, grad, square_avg)
+    lib().call('dpf_rmsprop_step', _ptr(param), _ptr(grad), _ptr(square_avg), param.numel(), float(lr), float(alpha), float(eps),
+               float(gscale), _stream())
+
+
+def rmsprop_step_lr(param, grad, square_avg, lr_dev, alpha=0.99, eps=1e-5, gscale=1.0):
+    """rmsprop_step with the rate in device memory (lr_dev: one float)."""
+    _need(param, grad, square_avg, lr_dev)
+    lib().call('dpf_rmsprop_step_lr', _ptr(param), _ptr(grad), _ptr(square_avg), param.numel(), _ptr(lr_dev), float(alpha), float(eps),
+               float(gscale), _stream())
+
+
 def reset_zero_arenas():
     """Forget what is left of the pre-zeroed arenas: the next zero_slot() clears its arena again.  A graph capture of the train step starts
     with this, so that the clearing fill is PART of the captured work (a replay finds the slots zero, as the eager step does)."""

@@ -1,6 +1,7 @@
 """``STEREODPNET``: the class the reference's ``model_selector`` instantiates
 (src/model/model_selector.py:11-15 -> src/model/stereodpnet/mainmodel.py:21), with the same methods PL / main.py call
-(mainmodel.py:67-177) plus an MI355X-native ``train_step`` (flat-arena gradients, fused Adam, optional RCCL all-reduce).
+(mainmodel.py:67-177) plus an MI355X-native ``train_step`` (flat-arena gradients, fused Adam / SGD / RMSprop step as ``option.optim`` selects, optional RCCL
+all-reduce).
 """
 import contextlib
 import os
@@ -22,7 +23,8 @@ class _PluginHooks(object):
     def _init_hooks(self, option):
         self.loss_model = loss_selector(option)
         self.metric_model = metric_selector(option)
-        self._adam = None
+        self._adam = None                                  # optim 'adam': {'m', 'v', 'step'}
+        self._optim = None                                 # optim 'sgd' / 'rmsprop': {'kind', 'buf' | 'sq'} (+ SGD's liveness mask)
 
     # ---- reference surface -------------------------------------------------------------------------------
     def forward(self, batch):
@@ -96,13 +98,17 @@ class _PluginHooks(object):
         return cache[1]
 
     def train_step(self, batch, reducer=None, lr=None):
-        """forward + loss + backward + (gradient all-reduce) + fused Adam; returns the results dict.
+        """forward + loss + backward + (gradient all-reduce) + the fused step of option.optim (Adam, SGD with momentum, RMSprop, configured as
+        selectors.optimizer_selector configures torch's); returns the results dict.
 
         Single-process steps on a fixed batch shape are captured into ONE HIP graph after two eager warm-up steps and replayed from then on
         (option.step_graph / DPF_STEP_GRAPH, default on): the ~2 400 kernel launches of a step leave the host once, so the launch gaps between
         the many short kernels disappear.  The C ABI never allocates or synchronises, which is what makes the step capturable."""
-        if self.option.optim != 'adam':
-            raise NotImplementedError('the fused step implements the shipped Adam configuration')
+        if self.option.optim not in ('adam', 'sgd', 'rmsprop'):
+            raise NotImplementedError('optimizer is not defined, please check your optimizer configuration !')
+        if self.option.optim == 'sgd' and not getattr(self, 'gather_grads', True):
+            raise NotImplementedError("optim 'sgd' needs the gather scheme (model.gather_grads): gradients accumulated into arena views do "
+                                      "not tell an unused parameter, which SGD must skip, from a zero gradient")
         # (eager when a per-launch profile is being recorded -- ops.PROFILE -- or gradients are exchanged between ranks)
         if reducer is None and ops.PROFILE is None and _graph_enabled(self) and all(v.is_cuda for v in batch.values() if torch.is_tensor(v)):
             return self._graph_step(batch, lr)
@@ -116,7 +122,7 @@ class _PluginHooks(object):
         # everything a captured graph has baked in: shapes, the kernel-path switches, the arenas' addresses (a device move re-creates them)
         key = tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(tensors.items())) + (
             bool(ops.deterministic()), ops.CONV_OPERANDS_BF16, ops.f32_matrix_path(), ops.WGRAD_ASYNC, _sdn.FEATURES_TWO_STREAMS, self.flat_parameters().data_ptr(),
-            self.flat_gradients(zero=False).data_ptr(), self._adam['m'].data_ptr() if self._adam else 0, self.stat_exchange is None)
+            self.flat_gradients(zero=False).data_ptr(), self._opt_key(), self.stat_exchange is None)
         # a few graph states are kept (most recently used last): the last, partial batch of an epoch has its own key and must not throw the
         # main shape's graph away
         states = self.__dict__.setdefault('_graph_states', [])
@@ -140,7 +146,7 @@ class _PluginHooks(object):
         if ss is None or ss.device != flat_g.device:
             ss = self._step_stream = ops.shared_stream(flat_g.device, 'step')      # one per process, not per model: ops.shared_stream
         cur = torch.cuda.current_stream(flat_g.device)
-        if st['calls'] <= 2 or self._adam is None:         # warm-up: lazily created streams, scratch buffers, sampler tables, kernel attributes
+        if st['calls'] <= 2 or not self._opt_state():      # warm-up: lazily created streams, scratch buffers, sampler tables, kernel attributes
             ss.wait_stream(cur)
             with torch.cuda.stream(ss):
                 res = self._eager_step(batch, None, lr)
@@ -149,14 +155,14 @@ class _PluginHooks(object):
                 if torch.is_tensor(v):
                     v.record_stream(cur)
             return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in res.items()}
-        ad = self._adam
+        ad = self._opt_state()
         if st['graph'] is None:
             # static inputs (the caller's tensors are copied in before every replay), the hyper-parameter slot, then the capture itself
             st['inputs'] = {k: v.clone() for k, v in tensors.items()}
             st['extra'] = {k: v for k, v in batch.items() if not torch.is_tensor(v)}
             st['hyper'] = torch.zeros(2, dtype=torch.float32, device=flat_g.device)
             counts_before = dict(self._pending_counts)
-            step_before = ad['step']
+            step_before = ad.get('step')                   # (Adam's bias-correction counter; the other optimisers have none)
             self._flush_counts()
             baked = self._baked_buffers()                  # (before AND after: a buffer replaced mid-capture was baked in as well)
             graph = torch.cuda.CUDAGraph()
@@ -180,7 +186,8 @@ class _PluginHooks(object):
                         raise
                 st['counts'] = dict(self._pending_counts)            # BatchNorm call counters one step adds (host-side bookkeeping)
                 self._pending_counts = {}
-                ad['step'] -= 1                                      # the capture only RECORDED the step: nothing ran
+                if step_before is not None:
+                    ad['step'] -= 1                                  # the capture only RECORDED the step: nothing ran
                 st['owned'] = baked + self._baked_buffers()          # released when the LRU above drops the state
                 st['graph'] = graph
             except Exception as e:                                   # capture refused (unsupported call inside): stay eager, say so once
@@ -192,7 +199,8 @@ class _PluginHooks(object):
                 # the aborted capture only RECORDED its work: the clearing fill of the zero arenas never ran although their cursors moved
                 # on (the warm-up steps' slots are still dirty), and the Adam step counter may have been advanced
                 ops.reset_zero_arenas()
-                ad['step'] = step_before
+                if step_before is not None:
+                    ad['step'] = step_before
                 return self._eager_step(batch, None, lr)
         # The replay runs on the dedicated stream, bracketed by explicit event waits in both directions.  Launched into the caller's stream
         # -- the legacy default stream in a plain script -- kernels the caller enqueued right after the replay were observed to start before
@@ -204,10 +212,13 @@ class _PluginHooks(object):
                 if v.data_ptr() != st['inputs'][k].data_ptr():
                     st['inputs'][k].copy_(v, non_blocking=True)
                     v.record_stream(ss)
-            ad['step'] += 1
-            h0, h1 = ops.adam_hyper(ad['step'], lr)
-            st['hyper'][0:1].fill_(float(h0))              # (scalars travel as kernel arguments: no host buffer the next step could overwrite)
-            st['hyper'][1:2].fill_(float(h1))
+            if self.option.optim == 'adam':
+                ad['step'] += 1
+                h0, h1 = ops.adam_hyper(ad['step'], lr)
+                st['hyper'][0:1].fill_(float(h0))          # (scalars travel as kernel arguments: no host buffer the next step could overwrite)
+                st['hyper'][1:2].fill_(float(h1))
+            else:
+                st['hyper'][0:1].fill_(lr)                 # SGD / RMSprop: the rate is the only scalar that changes between replays
             st['graph'].replay()
         cur.wait_stream(ss)
         for name, n in st['counts'].items():
@@ -223,18 +234,32 @@ class _PluginHooks(object):
             shape, on the replays' own stream (_behind_replays);
           * lazily built shape constants: StereoDPNet's sampler tables (`_tables`: only added to, but re-created by a device move) and
             NNet's cost-level volume (`_levels`: replaced whenever the batch shape changes);
-          * the parameter, gradient and Adam arenas and the BatchNorm buffers: updated in place, and the arenas' addresses are part of the
-            key -- held, a key match can never mean a new tensor at a recycled address.
+          * the parameter, gradient and optimiser arenas (SGD's liveness mask among them) and the BatchNorm buffers: updated in place, and
+            the arenas' addresses are part of the key -- held, a key match can never mean a new tensor at a recycled address.
         Not buffers: `_pairs_cache` (views of the gradient arena), the shared streams (`ops._wgrad_side`, the feature stream); the
         normal head's lazily registered `grid` is read by no kernel and only ever written in place."""
         found = ops.workspace_buffers() + list(self.buffers()) + [self.flat_parameters(), self.flat_gradients(zero=False)]
-        if self._adam:
-            found += [self._adam['m'], self._adam['v']]
+        found += self._opt_arenas()
         for tables, phase in getattr(self, '_tables', {}).values():
             found += [t for t in tuple(tables) + tuple(phase or ()) if torch.is_tensor(t)]
         if getattr(self, '_levels', None) is not None:
             found.append(self._levels)
         return found
+
+    def _opt_state(self):
+        """The fused step's optimiser state: `_adam` under optim 'adam', `_optim` under 'sgd' / 'rmsprop' (None before the first step)."""
+        return self._adam if self.option.optim == 'adam' else self._optim
+
+    def _opt_arenas(self):
+        st = self._opt_state() or {}
+        return [st[k] for k in ('m', 'v', 'buf', 'sq', 'live') if st.get(k) is not None]
+
+    def _opt_key(self):
+        """What a captured step bakes in of the optimiser: the state arena's address (0 before it exists)."""
+        arenas = self._opt_arenas()
+        if self.option.optim == 'adam':
+            return arenas[0].data_ptr() if arenas else 0
+        return (self.option.optim,) + tuple(t.data_ptr() for t in arenas)
 
     def _behind_replays(self, fn):
         """Once a train step of this model replays as a HIP graph, everything the model launches one by one (an eager step, forward,
@@ -270,6 +295,7 @@ class _PluginHooks(object):
     def _eager_step_body(self, batch, reducer=None, lr=None, hyper=None):
         self.train()
         gscale = 1.0
+        dead = None                                        # arena ranges of the parameters backward() left without a gradient
         if getattr(self, 'gather_grads', True):
             # Gradients are produced as fresh tensors (autograd hands them over without an accumulate kernel when .grad is None) and
             # gathered into the flat arena by one multi-tensor copy; the 14.7 MB all-reduce then runs once over the arena.  The
@@ -277,6 +303,7 @@ class _PluginHooks(object):
             # all-reduces with the backward pass through hooks -- an overlap worth < 0.1 % of a 400 ms step.
             flat_g = self.flat_gradients(zero=False)
             pairs = self._grad_pairs()
+            dead = []
             for p, _ in pairs:
                 p.grad = None
             ops.wgrad_async_begin([p for p, _ in pairs])
@@ -289,6 +316,7 @@ class _PluginHooks(object):
                         continue
                     if p.grad is None:
                         v.zero_()
+                        dead.append((v.storage_offset(), v.numel()))
                     else:
                         views.append(v)
                         grads.append(p.grad)
@@ -346,6 +374,9 @@ class _PluginHooks(object):
             if reducer is not None:
                 reducer.finish()
                 gscale = 1.0 / reducer.world_size
+        if self.option.optim != 'adam':
+            self._native_optim_step(flat_g, dead, hyper, float(lr if lr is not None else self.option.init_lr), gscale)
+            return results
         if self._adam is None or self._adam['m'].device != flat_g.device:
             self._adam = {'m': torch.zeros_like(flat_g), 'v': torch.zeros_like(flat_g), 'step': 0}
         st = self._adam
@@ -356,6 +387,36 @@ class _PluginHooks(object):
             ops.adam_step(self.flat_parameters(), flat_g, st['m'], st['v'], st['step'], float(lr if lr is not None else self.option.init_lr),
                           0.9, 0.999, 1e-5, gscale)
         return results
+
+    def _native_optim_step(self, flat_g, dead, hyper, lr, gscale):
+        """The SGD / RMSprop tail of a step, hyper-parameters as selectors.optimizer_selector gives torch's (model_selector.py:36,38).
+        hyper: the rate in device memory (graph capture), else it travels as a kernel argument."""
+        kind = self.option.optim
+        name = {'sgd': 'buf', 'rmsprop': 'sq'}[kind]
+        st = self._optim
+        if st is None or st.get('kind') != kind or st.get(name) is None or st[name].device != flat_g.device:
+            st = self._optim = {'kind': kind, name: torch.zeros_like(flat_g)}
+        if kind == 'rmsprop':                              # (a parameter without a gradient has a zero one in the arena: no update, state stays 0)
+            if hyper is not None:
+                ops.rmsprop_step_lr(self.flat_parameters(), flat_g, st['sq'], hyper, 0.99, 1e-5, gscale)
+            else:
+                ops.rmsprop_step(self.flat_parameters(), flat_g, st['sq'], lr, 0.99, 1e-5, gscale)
+            return
+        # SGD: torch skips a parameter whose .grad is None, while weight decay over its zero-filled arena view would shrink it every step.
+        # The kernel gets a byte mask of the live elements, rebuilt only when the set of such parameters changes -- it is a property of
+        # the network, so the warm-up steps settle it and a capture bakes in its address (_opt_key, _baked_buffers).
+        dead = tuple(sorted(set(dead)))                    # (never None here: train_step refuses SGD without the gather scheme)
+        if st.get('dead') != dead or (dead and (st.get('live') is None or st['live'].device != flat_g.device)):
+            live = None
+            if dead:
+                live = torch.ones(flat_g.numel(), dtype=torch.uint8, device=flat_g.device)
+                for off, numel in dead:
+                    live[off:off + numel] = 0
+            st['dead'], st['live'] = dead, live
+        if hyper is not None:
+            ops.sgd_step_lr(self.flat_parameters(), flat_g, st['buf'], hyper, 0.9, 2e-4, gscale, live=st['live'])
+        else:
+            ops.sgd_step(self.flat_parameters(), flat_g, st['buf'], lr, 0.9, 2e-4, gscale, live=st['live'])
 
 
 def _graph_enabled(model):

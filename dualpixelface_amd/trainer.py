@@ -2,15 +2,16 @@
 
 The reference drives its plugin with ``pytorch_lightning.Trainer`` 1.4.9 (main.py:43-58: fit / test, ``ModelCheckpoint`` every epoch
 into the workspace, ``resume_from_checkpoint``, validation every epoch, ``max_epochs = option.epoch``, DDP + SyncBatchNorm under
-``accelerator == 'ddp'``).  pytorch_lightning is not part of this image, and the MI355X step keeps its gradients and Adam moments in
+``accelerator == 'ddp'``).  pytorch_lightning is not part of this image, and the MI355X step keeps its gradients and optimiser state in
 flat arenas that a generic trainer would not know how to checkpoint, so this module provides those behaviours natively:
 
   * ``Trainer(option).fit(model)`` / ``.test(model)`` -- epochs over ``model.train_dataloader()`` (or loaders passed in) calling the
-    fused ``model.train_step`` (forward + loss + backward + bucketed RCCL all-reduce + Adam), the scheduler of
+    fused ``model.train_step`` (forward + loss + backward + bucketed RCCL all-reduce + Adam / SGD / RMSprop), the scheduler of
     ``scheduler_selector`` (StepLR(35, 0.5) / ExponentialLR(0.5) / CosineAnnealingLR(500, 1e-6) stepped per epoch), validation
     with the metric hooks every epoch, one checkpoint per epoch ``checkpoint_epoch=XX.ckpt``.
   * checkpoints hold ``state_dict`` under the reference's parameter names (a PL checkpoint of the reference loads into this
-    model, and the other way round), the flat Adam moments, the step / epoch counters and the learning rate.
+    model, and the other way round), the flat optimiser state (Adam moments, SGD momentum buffer or RMSprop square average), the step /
+    epoch counters and the learning rate.
   * one process per GPU under torchrun: the training set is sharded by SAMPLE with torch's DistributedSampler (own generator
     seeded by (seed, epoch), padded so every rank runs the same number of equal-shape steps -- what PL does for the reference), gradient all-reduce through
     ``distributed.make_reducer``, SyncBatchNorm when ``option.sync_batch``; rank 0 writes checkpoints and logs.
@@ -43,6 +44,24 @@ def epoch_lr(option, epoch):
 
 CKPT_VERSION = 2
 
+# optimizer_states[0]['kind'] of a checkpoint and the one state arena it carries, per option.optim beside Adam ('flat_adam': m, v, step)
+FLAT_STATE = {'sgd': ('flat_sgd', 'buf'), 'rmsprop': ('flat_rmsprop', 'sq')}
+
+
+def _optimizer_state(model, option):
+    """optimizer_states[0] of a checkpoint.  A model that only exposes `_adam` is written as before."""
+    optim = getattr(option, 'optim', 'adam')
+    if optim in FLAT_STATE and hasattr(model, '_optim'):
+        kind, name = FLAT_STATE[optim]
+        st = model._optim or {}
+        if st and st.get('kind') != optim:
+            raise ValueError("the model holds %r optimiser state while option.optim is %r" % (st.get('kind'), optim))
+        return {'kind': kind, name: st[name].detach().cpu() if st.get(name) is not None else None}
+    adam = getattr(model, '_adam', None) or {}
+    return {'kind': 'flat_adam', 'step': int(adam.get('step', 0)),
+            'm': adam['m'].detach().cpu() if 'm' in adam else None,
+            'v': adam['v'].detach().cpu() if 'v' in adam else None}
+
 
 class Trainer(object):
     def __init__(self, option, workspace_path=None, log_every=10, max_steps=None, rank=None, world_size=None):
@@ -63,15 +82,12 @@ class Trainer(object):
 
     def save_checkpoint(self, model, path=None):
         path = path or self.checkpoint_path(self.epoch)
-        adam = model._adam or {}
         ckpt = {
             # PL 1.4.9 dump_checkpoint: the NEXT epoch to run and global_step + 1; 'dpf_ckpt_version' tells load_checkpoint which
             # convention a file follows (absent + no 'pytorch-lightning_version' = round-1 files: 'epoch' was the FINISHED epoch)
             'dpf_ckpt_version': CKPT_VERSION, 'epoch': self.epoch + 1, 'global_step': self.global_step + 1,
             'state_dict': {k: v.detach().cpu() for k, v in model.state_dict().items()},
-            'optimizer_states': [{'kind': 'flat_adam', 'step': int(adam.get('step', 0)),
-                                  'm': adam['m'].detach().cpu() if 'm' in adam else None,
-                                  'v': adam['v'].detach().cpu() if 'v' in adam else None}],
+            'optimizer_states': [_optimizer_state(model, self.option)],
             'lr': epoch_lr(self.option, self.epoch),
             'hyper_parameters': {'model_name': getattr(self.option, 'model_name', 'stereodpnet')},
         }
@@ -112,6 +128,15 @@ class Trainer(object):
                                      "(load_checkpoint(..., resume=False) / --load_model without resume).  Nothing was restored." % (path, epoch))
                 if conv == 'finished':
                     epoch += 1
+            # the same rule for the optimiser: state of another kind than option.optim selects cannot continue this run
+            states = ckpt.get('optimizer_states') or []
+            kind = states[0].get('kind') if states and isinstance(states[0], dict) else None
+            optim = getattr(self.option, 'optim', 'adam')
+            want = FLAT_STATE[optim][0] if optim in FLAT_STATE else 'flat_adam'
+            if kind in ('flat_adam', 'flat_sgd', 'flat_rmsprop') and kind != want:
+                raise ValueError("checkpoint %r holds %s optimiser state, option.optim = %r needs %s: resume with the optimiser the run was "
+                                 "trained with, or load the weights only (load_checkpoint(..., resume=False) / --load_model without "
+                                 "resume).  Nothing was restored." % (path, kind, optim, want))
         model.load_state_dict(weights, strict=bool(getattr(self.option, 'load_strict', True)))
         if resume:
             self.epoch, self.global_step = epoch, global_step
@@ -119,6 +144,9 @@ class Trainer(object):
             if states and states[0].get('kind') == 'flat_adam' and states[0].get('m') is not None:
                 dev = model.flat_parameters().device
                 model._adam = {'m': states[0]['m'].to(dev), 'v': states[0]['v'].to(dev), 'step': int(states[0]['step'])}
+            for optim, (kind, name) in FLAT_STATE.items():
+                if states and states[0].get('kind') == kind and states[0].get(name) is not None:
+                    model._optim = {'kind': optim, name: states[0][name].to(model.flat_parameters().device)}
         return ckpt
 
     # ------------------------------------------------------------------ loops

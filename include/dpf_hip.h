@@ -289,7 +289,7 @@ int dpf_channel_max(const float* x, float* y, int N, int C, long long S, void* s
 int dpf_bn_replay(float* running, const float* a_f, const float* a_b, int C, float decay, float cf, float cb, void* stream);
 
 /* ---- losses (src/loss/loss_selector.py:29-42, src/loss/depth/smoothL1.py:15-49, src/loss/normal/cosine.py:15-53)
- * and Adam (src/model/model_selector.py:31-34) --------------------------------------------------------------------- */
+ * and the optimisers (src/model/model_selector.py:31-38) --------------------------------------------------------------------- */
 int dpf_loss_forward(const float* pred_depth, const float* pred_normal, const float* disp, const float* normal, const float* mask,
                      float* acc_ws, float* out, int B, int n, int H, int W, const float* head_weights_host, float lambda_depth,
                      float lambda_normal, void* stream);
@@ -302,6 +302,21 @@ int dpf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
  * memory (hyper[2]): a captured HIP graph of the whole train step replays this launch unchanged while the host refreshes the two floats */
 int dpf_adam_step_hyper(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, const float* hyper, double beta1,
                         double beta2, double eps, float gscale, void* stream);
+/* the other two optimisers of the config key `optim` (src/model/model_selector.py:36,38), same arenas and conventions as Adam: grad is
+ * pre-scaled by gscale, the state arena starts zero-filled, nothing is allocated or synchronised.
+ * SGD: d = grad * gscale + weight_decay * param; buf = momentum * buf + d; param -= lr * buf (no dampening, no Nesterov; torch's
+ * first-step buf = d is what a zero buffer gives).  live: n bytes, 0 = the element belongs to a parameter without a gradient this step and
+ * keeps parameter and buffer bit for bit (torch skips .grad is None; weight decay would shrink it otherwise); NULL = every element live.
+ * RMSprop: sq = alpha * sq + (1 - alpha) * (grad * gscale)^2; param -= lr * grad * gscale / (sqrt(sq) + eps) (no momentum, not centred).
+ * The *_lr forms read (float)lr from device memory (lr_dev[0]): a captured train step replays them while the scheduler changes the rate. */
+int dpf_sgd_step(float* param, const float* grad, float* momentum_buf, const unsigned char* live, long long n, double lr, double momentum,
+                 double weight_decay, float gscale, void* stream);
+int dpf_sgd_step_lr(float* param, const float* grad, float* momentum_buf, const unsigned char* live, long long n, const float* lr_dev,
+                    double momentum, double weight_decay, float gscale, void* stream);
+int dpf_rmsprop_step(float* param, const float* grad, float* square_avg, long long n, double lr, double alpha, double eps, float gscale,
+                     void* stream);
+int dpf_rmsprop_step_lr(float* param, const float* grad, float* square_avg, long long n, const float* lr_dev, double alpha, double eps,
+                        float gscale, void* stream);
 
 /* ---- FaceDP sample preprocessing: the per-sample host work of the reference's DataLoader workers,
  * dataloader/FaceDP/path_reader.py:150-168 (read_depth), :196-232 (read_disparity), dataloader/preprocess/preprocess.py:46-88
