@@ -493,6 +493,11 @@ int conv_launch(const float* x, const float* wt_ws, const float* bias, float* ou
 int conv_common(const float* x, const float* w, const float* bias, float* out, float* wt_ws, ConvP p, int repack_mode,
                 int wA, int wB, hipStream_t st, int Ktot = 0, int accumulate = 0) {
   const int T = p.kd * p.kh * p.kw;
+  if (T > MAXT && dpf_wide_eligible(T, p.kd, p.kh, p.kw, p.sd, p.sh, p.sw, p.pd, p.dd, p.dh, p.dw)) {     // 28 ... 49 taps, 2-D (conv_wide.hip)
+    DpfConvDesc d{p.N, p.C, p.K, Ktot > 0 ? Ktot : p.K, 0, p.ID, p.IH, p.IW, p.OD, p.OH, p.OW, p.kd, p.kh, p.kw, p.sd, p.sh, p.sw,
+                  p.pd, p.ph, p.pw, p.dd, p.dh, p.dw, p.transposed, wA, wB, repack_mode, accumulate};
+    return dpf_wide_conv(x, w, bias, out, d, st);
+  }
   if (T > MAXT || T < 1) return DPF_ERR_UNSUPPORTED;
   // one launch covers up to 128 output channels (4 MFMA row tiles); wider outputs are split
   const int Kfull = p.K;
@@ -718,7 +723,8 @@ int dpf_conv_transpose_acc(const float* x, const float* w, const float* bias, fl
 // g [N,K,QD,QH,QW] on the small grid, x [N,C,ID,IH,IW] on the dense grid.
 long long dpf_conv_wgrad_workspace_floats(int T, int C, int K) {
   const long long a = dpf_wgrad2_workspace_floats(T, C, K), b = T == 1 ? dpf_pointwise_wgrad_workspace_floats(C, K < 128 ? K : 128) : 0;
-  return a > b ? a : b;
+  const long long c = dpf_wide_wgrad_workspace_floats(T, C, K < 128 ? K : 128);
+  return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
 
 // as dpf_conv_wgrad below, with caller scratch (dpf_conv_wgrad_workspace_floats floats): eligible shapes run the LDS-DMA kernel
@@ -736,6 +742,7 @@ int dpf_conv_wgrad_ws(const float* g, const float* x, float* dw, float* ws, long
     if (ws) {
       DpfWgradDesc d{N, C, Kc, K, k0, ID, IH, IW, QD, QH, QW, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw_};
       if (T == 1) rc = dpf_pointwise_wgrad(g, x, dwk, ws, ws_floats, d, accumulate, (hipStream_t)stream);
+      if (T > MAXT) rc = dpf_wide_wgrad(g, x, dwk, ws, ws_floats, d, accumulate, (hipStream_t)stream);
       if (rc == DPF_ERR_UNSUPPORTED) rc = dpf_wgrad2(g, x, dwk, ws, ws_floats, d, accumulate, (hipStream_t)stream);
     }
     if (rc == DPF_ERR_UNSUPPORTED) {

@@ -53,6 +53,13 @@ int dpf_pointwise_wgrad(const float* g, const float* x, float* dw, float* ws, lo
                         hipStream_t st);
 long long dpf_pointwise_wgrad_workspace_floats(int C, int K);
 
+// Wide 2-D windows, 28 ... 49 taps (conv_wide.hip): plain fp32 FMA kernels for the shapes the MFMA tile kernels (27 taps at most) do not
+// take.  DPF_ERR_UNSUPPORTED -> not such a window (or `accumulate`, which these kernels decline).
+bool dpf_wide_eligible(int T, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int dd, int dh, int dw);
+int dpf_wide_conv(const float* x, const float* w, const float* bias, float* out, const DpfConvDesc& d, hipStream_t st);
+int dpf_wide_wgrad(const float* g, const float* x, float* dw, float* ws, long long ws_floats, const DpfWgradDesc& d, int accumulate, hipStream_t st);
+long long dpf_wide_wgrad_workspace_floats(int T, int C, int K);
+
 // ---- fp32 products on the bf16 matrix pipe: the operand split shared by igemm3_x9_kernel, its weight pack kernel and wgrad2_kernel<.., X9>.
 // x = hi + mid + lo EXACTLY, by rounding to nearest: hi = bf16(x), mid = bf16(x - hi), lo = x - hi - mid (the residuals are exact in fp32 and
 // the last one has at most 8 significant bits, so its conversion is exact too).  |mid| <= 2^-8 |x|, |lo| <= 2^-16 |x|, residuals signed.

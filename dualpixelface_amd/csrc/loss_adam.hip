@@ -1,4 +1,4 @@
-// Training-step tail: masked smooth-L1 (3 heads) + masked "cosine" normal loss, and the fused Adam update over the
+// Training-step tail: masked smooth-L1 (up to MAXHEADS heads) + masked "cosine" normal loss, and the fused Adam update over the
 // flat parameter arena.
 //   loss  : reference src/loss/loss_selector.py:29-42, src/loss/depth/smoothL1.py:15-49 ('given' conversion, target
 //           'disp'), src/loss/normal/cosine.py:15-53 (the per-channel, non-summed cosine of SURVEY Q11)
@@ -9,7 +9,7 @@
 
 namespace {
 
-constexpr int MAXHEADS = 4;
+constexpr int MAXHEADS = 8;      // DPNet trains five heads; <= 4 heads add in the same order as before (same bits)
 struct LossP {
   int B, n, H, W;
   float wts[MAXHEADS];
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restric
   __shared__ float sm[4];
   const long long hw = (long long)p.H * p.W;
   const long long total = (long long)p.B * hw;
-  float s[MAXHEADS] = {0.f, 0.f, 0.f, 0.f};
+  float s[MAXHEADS] = {};
   float sc = 0.f, cnt = 0.f;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     if (!(mask[i] > 0.f)) continue;
@@ -63,8 +63,9 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restric
   }
 #pragma unroll
   for (int k = 0; k < MAXHEADS; ++k) {
+    if (k >= p.n) break;                                  // (block-uniform)
     const float v = dpf_block_sum_256(s[k], sm);
-    if (threadIdx.x == 0 && k < p.n) atomicAdd(&acc[k], v);
+    if (threadIdx.x == 0) atomicAdd(&acc[k], v);
   }
   sc = dpf_block_sum_256(sc, sm);
   cnt = dpf_block_sum_256(cnt, sm);

@@ -500,6 +500,13 @@ def conv_transpose3d(x, w, stride=2, pad=1, outpad=1):
     return ConvTransposeFn.apply(x, w, _t3(stride), _t3(pad), _t3(outpad))
 
 
+def conv_transpose2d(x, w, stride=2, pad=1):
+    """nn.ConvTranspose2d(bias=False, output_padding=0); w is [C_in, C_out, kh, kw].  ``pad`` may exceed k - 1: the output is cropped
+    (DPNet's k4 s2 decoders use padding 1, 2 and 4: 2 * in, 2 * in - 2, 2 * in - 6)."""
+    s, q = int(stride), int(pad)
+    return ConvTransposeFn.apply(x.unsqueeze(2), w.unsqueeze(2), (1, s, s), (0, q, q), (0, 0, 0)).squeeze(2)
+
+
 class DepthwiseFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w):
@@ -525,6 +532,75 @@ class DepthwiseFn(torch.autograd.Function):
 
 def depthwise_conv3x3(x, w):
     return DepthwiseFn.apply(x, w)
+
+
+class DepthwiseGeneralFn(torch.autograd.Function):
+    """nn.Conv2d(C, C, k, padding=pad, groups=C, bias=False), k in {1, 3}, 0 <= pad <= 3."""
+
+    @staticmethod
+    def forward(ctx, x, w, pad):
+        x, w = _c(x), _c(w)
+        _need(x, w)
+        N, C, H, W = x.shape
+        k = int(w.shape[2])
+        if w.shape[0] != C or w.shape[1] != 1 or w.shape[3] != k:
+            raise DpfError('depthwise_conv2d: weight %s does not fit %d channels' % (tuple(w.shape), C))
+        y = torch.empty((N, C, H + 2 * pad - k + 1, W + 2 * pad - k + 1), dtype=torch.float32, device=x.device)
+        lib().call('dpf_depthwise_conv2d_forward', _ptr(x), _ptr(w), _ptr(y), N, C, H, W, k, pad, _stream())
+        ctx.save_for_backward(x, w)
+        ctx.pad = pad
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = _c(gy)
+        N, C, H, W = x.shape
+        k = int(w.shape[2])
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            lib().call('dpf_depthwise_conv2d_backward_data', _ptr(gy), _ptr(w), _ptr(gx), N, C, H, W, k, ctx.pad, _stream())
+        if ctx.needs_input_grad[1]:
+            gw = torch.zeros_like(w)
+            lib().call('dpf_depthwise_conv2d_backward_weight', _ptr(gy), _ptr(x), _ptr(gw), N, C, H, W, k, ctx.pad, _stream())
+        return gx, gw, None
+
+
+def depthwise_conv2d(x, w, pad):
+    return DepthwiseGeneralFn.apply(x, w, int(pad))
+
+
+class MaxPoolFn(torch.autograd.Function):
+    """nn.MaxPool2d(k, stride, pad) with PyTorch's tie rule; the backward is a gather over the stored arg-max plane (no atomics)."""
+
+    @staticmethod
+    def forward(ctx, x, k, stride, pad):
+        x = _c(x)
+        _need(x)
+        N, C, H, W = x.shape
+        oh, ow = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+        y = torch.empty((N, C, oh, ow), dtype=torch.float32, device=x.device)
+        idx = torch.empty((N, C, oh, ow), dtype=torch.int32, device=x.device)
+        lib().call('dpf_maxpool2d_forward', _ptr(x), _ptr(y), _ptr(idx), N, C, H, W, k, stride, pad, _stream())
+        ctx.save_for_backward(idx)
+        ctx.cfg = (N, C, H, W, k, stride, pad)
+        ctx.mark_non_differentiable(idx)
+        return y, idx
+
+    @staticmethod
+    def backward(ctx, gy, _gidx):
+        idx, = ctx.saved_tensors
+        N, C, H, W, k, stride, pad = ctx.cfg
+        gy = _c(gy)
+        gx = torch.empty((N, C, H, W), dtype=torch.float32, device=gy.device)
+        lib().call('dpf_maxpool2d_backward', _ptr(gy), _ptr(idx), _ptr(gx), N, C, H, W, k, stride, pad, _stream())
+        return gx, None, None, None
+
+
+def max_pool2d(x, k, stride, pad=0, return_indices=False):
+    y, idx = MaxPoolFn.apply(x, int(k), int(stride), int(pad))
+    return (y, idx) if return_indices else y
 
 
 # ----------------------------------------------------------------------------------------------- norm + activation

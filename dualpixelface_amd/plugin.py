@@ -11,6 +11,7 @@ import torch
 from . import ops
 from .losses import loss_selector
 from .selectors import metric_selector, optimizer_selector, scheduler_selector
+from .dpnet import DPNetCore
 from .nnet import NNetCore
 from .psmnet import PSMNetCore
 from .stereonet import StereoNetCore
@@ -480,3 +481,21 @@ class STEREONET(_PluginHooks, StereoNetCore):
     def __init__(self, option):
         StereoNetCore.__init__(self, option)
         self._init_hooks(option)
+
+
+class DPNET(_PluginHooks, DPNetCore):
+    """src/model/dpnet/mainmodel.py::DPNET (mainmodel.py:29-270); its validation hooks are no-ops in the reference (mainmodel.py:236-245),
+    test_step runs the metric hooks (mainmodel.py:247-251)."""
+
+    def __init__(self, option):
+        DPNetCore.__init__(self, option)
+        self._init_hooks(option)
+
+    def validation_step(self, batch, batch_idx):
+        return None
+
+    def validation_epoch_end(self, outputs):
+        return None
+
+    def test_step(self, batch, batch_idx):
+        return _PluginHooks.validation_step(self, batch, batch_idx)

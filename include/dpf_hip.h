@@ -33,7 +33,12 @@ extern "C" {
  * call sites: src/module/asm/basics.py:17-36, src/model/stereodpnet/modules.py:26-32,64-69,88-91,208-227,271-296,
  * src/model/stereodpnet/normal_module.py:14-19, src/module/dcn3d/modules/deform_conv.py:310-315 (conv_offset),
  * src/module/asm/asm.py:141-146.  2-D tensors are passed with depth 1 (kd = 1, sd = 1, pd = 0, dd = 1).
- * ws: dpf_conv_workspace_floats(T, reduce_channels, out_channels) floats (repacked weights). */
+ * ws: dpf_conv_workspace_floats(T, reduce_channels, out_channels) floats (repacked weights).
+ * Windows of up to 27 taps run on the matrix-core kernels.  2-D windows of 28 ... 49 taps (kh, kw <= 7; DPNet's 7x7 stem and heads,
+ * src/model/dpnet/modules.py:44, mainmodel.py:81-85), stride 1 or 2, dilation 1, run on plain fp32 FMA kernels (csrc/conv_wide.hip)
+ * behind the same three entry points -- dpf_conv_forward, dpf_conv_transpose* (data gradient; `accumulate` is declined with
+ * DPF_ERR_UNSUPPORTED) and dpf_conv_wgrad_ws (fixed-order slab fold: bitwise reproducible in every mode; needs `ws`).  Their result
+ * does not depend on dpf_set_f32_matrix_path. */
 long long dpf_conv_workspace_floats(int T, int reduce, int outc);
 int dpf_conv_forward(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
                      int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw,
@@ -122,10 +127,20 @@ int dpf_conv2d_bf16_forward(const float* x, const float* w, const float* bias, f
 int dpf_conv2d_bf16_dgrad(const float* go, const float* w, float* dx, void* ws, int N, int C, int IH, int IW, int K, int kh, int kw, int ph, int pw,
                           int dh, int dw, void* stream);
 
-/* ---- depthwise 3x3: depthwise_separable_conv.depthwise (src/module/asm/basics.py:39-58) --------------------------- */
+/* ---- depthwise conv (groups = channels): depthwise_separable_conv.depthwise (src/module/asm/basics.py:39-58) --------
+ * stride 1, dilation 1; k in {1, 3}, 0 <= pad <= 3 (DPF_ERR_UNSUPPORTED otherwise).  x / dx [N,C,H,W]; y / g [N,C,H+2pad-k+1,W+2pad-k+1].
+ * k = 3, pad = 1 (StereoDPNet's DPBlock.conv5) keeps its own kernels; every other window (DPNet: src/model/dpnet/modules.py:13,68-70,
+ * mainmodel.py:68-71) runs the general ones.  backward_weight ADDS into dw [C,1,k,k]. */
 int dpf_depthwise_conv2d_forward(const float* x, const float* w, float* y, int N, int C, int H, int W, int k, int pad, void* stream);
 int dpf_depthwise_conv2d_backward_data(const float* g, const float* w, float* dx, int N, int C, int H, int W, int k, int pad, void* stream);
 int dpf_depthwise_conv2d_backward_weight(const float* g, const float* x, float* dw, int N, int C, int H, int W, int k, int pad, void* stream);
+
+/* ---- nn.MaxPool2d(k, stride, pad), floor output size, padding = -inf (src/model/dpnet/modules.py:20,46): k <= 7, stride 1 or 2,
+ * pad <= k / 2.  y, idx, g [N,C,OH,OW] with OH = (H + 2 pad - k) / stride + 1; idx = iy * W + ix of the chosen element, PyTorch's tie
+ * rule (row-major scan, replaced only by a strictly greater value or a NaN).  backward overwrites dx [N,C,H,W]; it is a gather in a
+ * fixed order (no atomics): bitwise reproducible in every mode. */
+int dpf_maxpool2d_forward(const float* x, float* y, int* idx, int N, int C, int H, int W, int k, int stride, int pad, void* stream);
+int dpf_maxpool2d_backward(const float* g, const int* idx, float* dx, int N, int C, int H, int W, int k, int stride, int pad, void* stream);
 
 /* ---- BatchNorm2d/3d, InstanceNorm3d, ReLU/PReLU/LeakyReLU/Sigmoid, residual adds ---------------------------------
  * src/module/asm/basics.py:17-58, src/model/stereodpnet/modules.py:37-52,241-260,310-325, src/module/asm/asm.py:138-146.
