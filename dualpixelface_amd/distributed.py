@@ -173,10 +173,11 @@ def broadcast_flat(flat, src=0, group=None):
 
 
 def make_reducer(model, nbuckets=3, force_collectives=None):
-    """Reducer for a StereoDPNetCore: buckets cut at the cost-volume and normal-estimator boundaries.  The staged exchange fires NAMED
-    stages ('aggregation' = cost volume + aggregation stack, 'normal' = normal head); a name maps to a bucket only if that bucket's
-    slice holds exactly the parameters of that part of the network -- with other cuts (nbuckets 1 or 2, custom bounds) the name is
-    absent and its gradients travel with stage_finish."""
+    """Reducer for a model over the flat arena (core.ArenaModule): buckets cut where the `cost_volume` and `normal_estimator` parameters
+    begin -- StereoDPNet's layout; a family without those names gets one bucket.  The staged exchange fires NAMED stages ('aggregation'
+    = cost volume + aggregation stack, 'normal' = normal head); a name maps to a bucket only if that bucket's slice holds exactly the
+    parameters of that part of the network -- with other cuts (nbuckets 1 or 2, custom bounds) the name is absent and its gradients
+    travel with stage_finish."""
     flat_g = model.flat_gradients(zero=True)
     pd = dict(model.named_parameters())
     layout = [(pd[name], off, numel) for name, off, numel, _ in model._layout]

@@ -11,8 +11,8 @@ general depthwise window (conv_depthwise.hip), 7x7 convolutions (conv_wide.hip),
 import math
 
 from . import ops
+from .core import ArenaModule, Spec
 from .ops import ACT_PRELU
-from .stereodpnet import StereoDPNetCore, _Spec
 
 # (name, in, infilter, outfilter, stride, pad_basic): mainmodel.py:43-59
 ENCODERS = (('enc_layer1_2', None, 11, 11, 1, 1),
@@ -67,7 +67,7 @@ def _decoder(s, p, cin, f):
 
 def build_dpnet_spec(opt):
     c2 = 2 * int(opt.model.input_channel)
-    s = _Spec()
+    s = Spec()
     _basic(s, 'enc_layer1_1.conv1', c2, 8, 7)
     for name, cin, f, cout, stride, pad in ENCODERS:
         cin = 8 + c2 if cin is None else cin
@@ -132,16 +132,8 @@ def dpnet_shapes(H, W):
     return out
 
 
-class DPNetCore(StereoDPNetCore):
-    def __init__(self, option):
-        m = option.model
-        if not hasattr(m, 'level'):          # (the shared constructor derives its cost range from it; DPNet has no cost volume)
-            m.level = 1
-        super(DPNetCore, self).__init__(option)
-
-    @staticmethod
-    def _spec(option):
-        return build_dpnet_spec(option)
+class DPNetCore(ArenaModule):
+    _spec = staticmethod(build_dpnet_spec)
 
     # ------------------------------------------------------------------ blocks
     def _basic(self, x, p, stride=1, pad=1, deconv=False, res2=None):
@@ -184,14 +176,8 @@ class DPNetCore(StereoDPNetCore):
 
     # ------------------------------------------------------------------ whole network (mainmodel.py:119-197)
     def _network(self, batch):
-        opt, P = self.option, self._P
-        a, b = 'left', 'right'
-        if 'groupname' in batch and not self.training:
-            if batch['groupname'][0] == '2020-2-9_group20':
-                a, b = 'right', 'left'
-        elif opt.dataset.flip_lr:
-            a, b = 'right', 'left'
-        x = ops.concat_channels([batch[a], batch[b]])
+        P = self._P
+        x = ops.concat_channels(list(self._views(batch)))
         H, W = x.shape[2], x.shape[3]
         # Encoder2 (modules.py:48-56): the stem beside a max-pool of the raw input
         x = ops.concat_channels([self._basic(x, 'enc_layer1_1.conv1', 2, 1), ops.max_pool2d(x, 7, 2, 1)])

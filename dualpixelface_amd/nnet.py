@@ -8,12 +8,11 @@ per-level 2-D refinement of the cost slices guided by the reference features, an
 + both aggregation features -> 3-D convs -> three depth-halving (2,3,3) convs -> dilated 2-D stack -> unit normals.
 """
 import torch
-import torch.nn as nn
 
 from . import ops
+from .core import ArenaModule, Spec, cost_levels, set_levels
 from .ops import ACT_LEAKY, ACT_NONE, ACT_RELU
-from .psmnet import PSMNetCore, build_psmnet_spec
-from .stereodpnet import _Spec
+from .psmnet import PSMFeatures, psm_feature_spec
 
 REFINE = ((1, 4, 1), (4, 4, 2), (4, 4, 4), (4, 3, 8), (3, 2, 16), (2, 1, 1))      # (in, out) in units of inplanes, dilation; mainmodel.py:50-58
 NORMAL = ((1, 3, 1), (3, 3, 2), (3, 3, 4), (3, 2, 8), (2, 2, 16), (2, 1, 1))      # normal_module_.py:36-44
@@ -22,9 +21,8 @@ NORMAL = ((1, 3, 1), (3, 3, 2), (3, 3, 4), (3, 2, 8), (2, 2, 16), (2, 1, 1))    
 def build_nnet_spec(opt):
     m = opt.model
     c = m.inplanes
-    s = _Spec()
-    full = build_psmnet_spec(_PsmView(opt))                # the feature extractor's entries, in the reference's registration order
-    s.items = [it for it in full.items if it[0].startswith('feature_extraction.')]
+    s = Spec()
+    psm_feature_spec(s, m)
     for i, (ci, co, _) in enumerate(REFINE):
         s.conv('convs.%d.0' % i, co * c, ci * c + (1 if i == 0 else 0), (3, 3))
     s.conv('convs.6.0', 1, c, (3, 3))
@@ -45,30 +43,22 @@ def build_nnet_spec(opt):
         for i, (ci, co, _) in enumerate(NORMAL):
             s.conv('%s.n_convs.%d.0' % (nm, i), co * c, ci * c, (3, 3))
         s.conv(nm + '.n_convs.6.0', 3, c, (3, 3))
-        s.add(nm + '.costrange', (1, m.level, 1, 1), 'frozen', None)
+        s.add(nm + '.costrange', (1, m.level, 1, 1), 'frozen', cost_levels(m.mindisp, m.maxdisp, m.level))
     return s
 
 
-class _PsmView(object):
-    """option view for build_psmnet_spec: NNet's config has no cost_volume style key."""
-
-    def __init__(self, opt):
-        self.model = _Model(opt.model)
-
-
-class _Model(object):
-    def __init__(self, m):
-        self.__dict__.update(m.__dict__)
-        self.cost_volume = 'psmnet'
-        self.group_num = 0
-
-
-class NNetCore(PSMNetCore):
+class NNetCore(PSMFeatures, ArenaModule):
     spp_align_corners = False       # nnet/modules.py:110-120
+    _spec = staticmethod(build_nnet_spec)
 
-    @staticmethod
-    def _spec(option):
-        return build_nnet_spec(option)
+    def __init__(self, option):
+        super(NNetCore, self).__init__(option)
+        m = option.model
+        set_levels(self, m.mindisp, m.maxdisp, m.level, 4 * int(m.level))
+        self._levels = self._levels_key = None             # the cost-level volume of _normals and the (device, shape) it was built for
+
+    def _shape_constants(self):
+        return [] if self._levels is None else [self._levels]
 
     def _residual3(self, x, p):
         """dresN(x) + x (mainmodel.py:66-80,136-139): convbn_3d - ReLU - convbn_3d, plus the input."""
@@ -98,14 +88,10 @@ class NNetCore(PSMNetCore):
         """NormalModule.forward (normal_module_.py:89-117)."""
         P, p, m = self._P, 'normal_module', self.option.model
         B, C, L, h, w = cost0.shape
-        if 'grid' not in self._modules[p]._parameters:                             # lazily registered by the reference (:60-69)
-            ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing='ij')
-            grid = torch.stack([xs, ys, torch.ones_like(xs)], 0).unsqueeze(0).to(cost0.device)
-            self._modules[p].register_parameter('grid', nn.Parameter(grid, False))
-            self._index()
+        self._register_grid(p, h, w, cost0.device)                                  # lazily registered by the reference (:60-69)
         # (constant of the model and the batch shape: built once -- a host-to-device copy per step would also keep the step out of a HIP graph)
         lk = (str(cost0.device), B, L, h, w)
-        if getattr(self, '_levels_key', None) != lk:
+        if self._levels_key != lk:
             self._levels = torch.tensor(self.costrange, dtype=torch.float32, device=cost0.device).view(1, L, 1, 1).expand(B, L, h, w).contiguous()
             self._levels_key = lk
         levels = self._levels
@@ -129,15 +115,10 @@ class NNetCore(PSMNetCore):
 
     def _network(self, batch):
         """NNET.forward without the loss (mainmodel.py:112-167)."""
-        opt, m = self.option, self.option.model
-        a, b = 'left', 'right'
-        if 'groupname' in batch and not self.training:
-            if batch['groupname'][0] == '2020-2-9_group20':
-                a, b = 'right', 'left'
-        elif opt.dataset.flip_lr:
-            a, b = 'right', 'left'
-        ref = self._features(batch[a])
-        tar = self._features(batch[b])
+        m = self.option.model
+        a, b = self._views(batch)
+        ref = self._features(a)
+        tar = self._features(b)
         vol = ops.psm_volume(ref, tar, [int(d) for d in self.costrange], 0)         # int() truncation (nnet/modules.py:176-178)
         c0 = self._convbn3(vol, 'dres0.0', 1, ACT_RELU)
         cost_in0 = self._convbn3(c0, 'dres0.2', 1, ACT_RELU)

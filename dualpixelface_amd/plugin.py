@@ -21,7 +21,8 @@ from .stereodpnet import StereoDPNetCore, two_stream_grad_warning_off
 class _PluginHooks(object):
     """The methods PL / main.py call on a model plugin (mainmodel.py:67-177), shared by every model family of the build."""
 
-    def _init_hooks(self, option):
+    def __init__(self, option):
+        super(_PluginHooks, self).__init__(option)         # the model family's core (core.ArenaModule)
         self.loss_model = loss_selector(option)
         self.metric_model = metric_selector(option)
         self._adam = None                                  # optim 'adam': {'m', 'v', 'step'}
@@ -119,11 +120,10 @@ class _PluginHooks(object):
     def _graph_step(self, batch, lr):
         self.train()                                       # (a replay runs no Python: the mode flag must not depend on it)
         tensors = {k: v for k, v in batch.items() if torch.is_tensor(v)}
-        from . import stereodpnet as _sdn
         # everything a captured graph has baked in: shapes, the kernel-path switches, the arenas' addresses (a device move re-creates them)
         key = tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(tensors.items())) + (
-            bool(ops.deterministic()), ops.CONV_OPERANDS_BF16, ops.f32_matrix_path(), ops.WGRAD_ASYNC, _sdn.FEATURES_TWO_STREAMS, self.flat_parameters().data_ptr(),
-            self.flat_gradients(zero=False).data_ptr(), self._opt_key(), self.stat_exchange is None)
+            bool(ops.deterministic()), ops.CONV_OPERANDS_BF16, ops.f32_matrix_path(), ops.WGRAD_ASYNC) + self._capture_key() + (
+            self.flat_parameters().data_ptr(), self.flat_gradients(zero=False).data_ptr(), self._opt_key(), self.stat_exchange is None)
         # a few graph states are kept (most recently used last): the last, partial batch of an epoch has its own key and must not throw the
         # main shape's graph away
         states = self.__dict__.setdefault('_graph_states', [])
@@ -233,19 +233,14 @@ class _PluginHooks(object):
           * ops.workspace_buffers(): the scratch slabs and pre-zeroed arenas of every stream the step runs on (step, second feature pass,
             weight-gradient side stream).  A later call that needs more room replaces them -- an eager step or a validation at a larger
             shape, on the replays' own stream (_behind_replays);
-          * lazily built shape constants: StereoDPNet's sampler tables (`_tables`: only added to, but re-created by a device move) and
-            NNet's cost-level volume (`_levels`: replaced whenever the batch shape changes);
+          * the model's lazily built shape constants (_shape_constants): StereoDPNet's sampler tables (only added to, but re-created
+            by a device move) and NNet's cost-level volume (replaced whenever the batch shape changes);
           * the parameter, gradient and optimiser arenas (SGD's liveness mask among them) and the BatchNorm buffers: updated in place, and
             the arenas' addresses are part of the key -- held, a key match can never mean a new tensor at a recycled address.
         Not buffers: `_pairs_cache` (views of the gradient arena), the shared streams (`ops._wgrad_side`, the feature stream); the
         normal head's lazily registered `grid` is read by no kernel and only ever written in place."""
         found = ops.workspace_buffers() + list(self.buffers()) + [self.flat_parameters(), self.flat_gradients(zero=False)]
-        found += self._opt_arenas()
-        for tables, phase in getattr(self, '_tables', {}).values():
-            found += [t for t in tuple(tables) + tuple(phase or ()) if torch.is_tensor(t)]
-        if getattr(self, '_levels', None) is not None:
-            found.append(self._levels)
-        return found
+        return found + self._opt_arenas() + self._shape_constants()
 
     def _opt_state(self):
         """The fused step's optimiser state: `_adam` under optim 'adam', `_optim` under 'sgd' / 'rmsprop' (None before the first step)."""
@@ -448,17 +443,11 @@ def _attach_deferred(pairs):
 
 
 class STEREODPNET(_PluginHooks, StereoDPNetCore):
-    def __init__(self, option):
-        StereoDPNetCore.__init__(self, option)
-        self._init_hooks(option)
+    """src/model/stereodpnet/mainmodel.py::STEREODPNET (mainmodel.py:21-177)."""
 
 
 class PSMNET(_PluginHooks, PSMNetCore):
     """src/model/psmnet/mainmodel.py::PSMNET; its validation hooks are no-ops in the reference (mainmodel.py:143-149)."""
-
-    def __init__(self, option):
-        PSMNetCore.__init__(self, option)
-        self._init_hooks(option)
 
     def validation_step(self, batch, batch_idx):
         return None
@@ -470,26 +459,14 @@ class PSMNET(_PluginHooks, PSMNetCore):
 class NNET(_PluginHooks, NNetCore):
     """src/model/nnet/mainmodel.py::NNET (mainmodel.py:31-240)."""
 
-    def __init__(self, option):
-        NNetCore.__init__(self, option)
-        self._init_hooks(option)
-
 
 class STEREONET(_PluginHooks, StereoNetCore):
     """src/model/stereonet/mainmodel.py::STEREONET (mainmodel.py:30-220)."""
-
-    def __init__(self, option):
-        StereoNetCore.__init__(self, option)
-        self._init_hooks(option)
 
 
 class DPNET(_PluginHooks, DPNetCore):
     """src/model/dpnet/mainmodel.py::DPNET (mainmodel.py:29-270); its validation hooks are no-ops in the reference (mainmodel.py:236-245),
     test_step runs the metric hooks (mainmodel.py:247-251)."""
-
-    def __init__(self, option):
-        DPNetCore.__init__(self, option)
-        self._init_hooks(option)
 
     def validation_step(self, batch, batch_idx):
         return None

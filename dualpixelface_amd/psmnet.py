@@ -3,17 +3,18 @@ the reference's src/model/psmnet/{mainmodel.py:30-111, modules.py:14-416} on the
 
 Only the feature extractor (ResNet-style BasicBlocks + SPP branches, psmnet/modules.py:60-168) and the integer-shift cost
 volume (:215-275) are specific to this model; the 3-D hourglass aggregation and the soft-argmin head are the classes StereoDPNet
-uses and are inherited from ``StereoDPNetCore``.  Same flat parameter arena, fused Adam and reducer as the flagship model.
+uses (``stereodpnet.HourglassAggregation``).  The feature extractor is a mix-in of its own, ``PSMFeatures``: NNet shares it.  Same flat
+parameter arena, fused optimiser step and reducer as the flagship model.
 """
 from . import ops
+from .core import ArenaModule, Spec, set_levels
 from .ops import ACT_NONE, ACT_RELU
-from .stereodpnet import StereoDPNetCore, _Spec
+from .stereodpnet import HourglassAggregation
 
 
-def build_psmnet_spec(opt):
-    m = opt.model
+def psm_feature_spec(s, m):
+    """The feature extractor's entries, in the reference's registration order."""
     c = m.inplanes
-    s = _Spec()
     fe = 'feature_extraction'
     s.convbn2(fe + '.firstconv.0', m.input_channel, c)
     s.convbn2(fe + '.firstconv.2', c, c)
@@ -37,26 +38,21 @@ def build_psmnet_spec(opt):
         s.bn('%s.branch%d.1.1' % (fe, i), c)
     s.convbn2(fe + '.lastconv.0', 10 * c, 4 * c)
     s.conv(fe + '.lastconv.2', c, 4 * c, (1, 1))
-    ag = 'aggregation'
-    first = 2 * c + (int(m.group_num) if m.cost_volume == 'gwcnet' else 0)
-    s.convbn3(ag + '.dres0.0', first, c)
-    s.convbn3(ag + '.dres0.2', c, c)
-    s.convbn3(ag + '.dres1.0', c, c)
-    s.convbn3(ag + '.dres1.2', c, c)
-    for n in ('dres2', 'dres3', 'dres4'):
-        s.hourglass(ag + '.' + n, c)
-    for n in ('classif1', 'classif2', 'classif3'):
-        s.convbn3(ag + '.%s.0' % n, c, c)
-        s.conv(ag + '.%s.2' % n, 1, c, (3, 3, 3))
+
+
+def build_psmnet_spec(opt):
+    m = opt.model
+    s = Spec()
+    psm_feature_spec(s, m)
+    first = 2 * m.inplanes + (int(m.group_num) if m.cost_volume == 'gwcnet' else 0)
+    HourglassAggregation.aggregation_spec(s, first, m.inplanes)
     return s
 
 
-class PSMNetCore(StereoDPNetCore):
-    spp_align_corners = True        # psmnet/modules.py:150-163 resizes the pooled branches with align_corners=True
+class PSMFeatures(object):
+    """The ResNet / SPP feature extractor of PSMNet and NNet: mix-in over core.ArenaModule."""
 
-    @staticmethod
-    def _spec(option):
-        return build_psmnet_spec(option)
+    spp_align_corners = True        # psmnet/modules.py:150-163 resizes the pooled branches with align_corners=True
 
     def _basic_block(self, x, p, stride, pad, dil, downsample):
         """BasicBlock.forward (psmnet/modules.py:14-34): conv-bn-relu, conv-bn, + (downsampled) input."""
@@ -92,17 +88,21 @@ class PSMNetCore(StereoDPNetCore):
         feat = self._convbn2(feat, p + '.lastconv.0', act=ACT_RELU)
         return self._conv2d(feat, P[p + '.lastconv.2.weight'])
 
+
+class PSMNetCore(HourglassAggregation, PSMFeatures, ArenaModule):
+    _spec = staticmethod(build_psmnet_spec)
+
+    def __init__(self, option):
+        super(PSMNetCore, self).__init__(option)
+        m = option.model
+        set_levels(self, m.mindisp, m.maxdisp, m.level, 4 * int(m.level))
+
     def _network(self, batch):
         """PSMNET.forward without the loss (psmnet/mainmodel.py:67-97)."""
-        opt, m = self.option, self.option.model
-        a, b = 'left', 'right'
-        if 'groupname' in batch and not self.training:
-            if batch['groupname'][0] == '2020-2-9_group20':
-                a, b = 'right', 'left'
-        elif opt.dataset.flip_lr:
-            a, b = 'right', 'left'
-        ref = self._features(batch[a])
-        tar = self._features(batch[b])
+        m = self.option.model
+        a, b = self._views(batch)
+        ref = self._features(a)
+        tar = self._features(b)
         groups = int(m.group_num) if m.cost_volume == 'gwcnet' else 0
         if m.cost_volume not in ('psmnet', 'gwcnet'):
             raise NotImplementedError('cost volume style is not defined : %s' % m.cost_volume)

@@ -9,15 +9,15 @@ contract) and stay untouched.
 import math
 
 from . import ops
+from .core import ArenaModule, Spec, set_levels
 from .ops import ACT_LEAKY, ACT_RELU
-from .stereodpnet import StereoDPNetCore, _Spec
 
 ASTROUS = (1, 2, 4, 8, 1, 1)          # modules.py:66
 
 
 def build_stereonet_spec(opt):
     m = opt.model
-    s = _Spec()
+    s = Spec()
     fe = 'feature_extraction'
     cin = m.input_channel
     for i in range(int(m.k)):
@@ -42,29 +42,18 @@ def build_stereonet_spec(opt):
     return s
 
 
-class StereoNetCore(StereoDPNetCore):
-    def __init__(self, option):
-        m = option.model
-        # the shared constructor derives costrange / hypothesis values from (mindisp, maxdisp, level): StereoNet's level is 2^k and
-        # its regression has one hypothesis per level (mainmodel.py:38-40, modules.py:100-104)
-        if not hasattr(m, 'level'):
-            m.level = int(math.pow(2, m.k))
-        super(StereoNetCore, self).__init__(option)
-        L = int(m.level)
-        self.disp_values = [i * ((self.maxdisp - self.mindisp) / float(L)) + self.mindisp for i in range(L)]
+class StereoNetCore(ArenaModule):
+    _spec = staticmethod(build_stereonet_spec)
 
-    @staticmethod
-    def _spec(option):
-        return build_stereonet_spec(option)
+    def __init__(self, option):
+        super(StereoNetCore, self).__init__(option)
+        m = option.model
+        L = 2 ** int(m.k)                  # 2^k cost levels, one regression hypothesis per level (mainmodel.py:38-40, modules.py:100-104)
+        set_levels(self, m.mindisp, m.maxdisp, L, L)
 
     def _block(self, x, p, dil):
         """BasicBlock.forward (modules.py:19-27): LeakyReLU_0.2(bn(conv(x))) + x -- conv2 is never applied."""
         return self._convbn2(x, p + '.conv1.0', 1, 1, dil, ACT_LEAKY, None, None, slope_const=0.2, res2=x)
-
-    def _convbn2(self, x, p, stride=1, pad=1, dil=1, act=0, slope=None, res=None, slope_const=0.0, res2=None):
-        st = self._stats_holder()
-        y = ops.conv2d(x, self._P[p + '.0.weight'], None, stride, dil if dil > 1 else pad, dil, bf16=self.bf16_2d, stats=st)
-        return self._bn(y, p + '.1', act, slope, res, res2, slope_const, stats=st)
 
     def _features(self, img):
         """FeatureExtraction.forward (modules.py:53-59)."""
@@ -91,15 +80,9 @@ class StereoNetCore(StereoDPNetCore):
 
     def _network(self, batch):
         """STEREONET.forward without the loss (mainmodel.py:79-141)."""
-        opt = self.option
-        a, b = 'left', 'right'
-        if 'groupname' in batch and not self.training:
-            if batch['groupname'][0] == '2020-2-9_group20':
-                a, b = 'right', 'left'
-        elif opt.dataset.flip_lr:
-            a, b = 'right', 'left'
-        ref = self._features(batch[a])
-        tar = self._features(batch[b])
+        a, b = self._views(batch)
+        ref = self._features(a)
+        tar = self._features(b)
         vol = ops.diff_volume(ref, tar, [int(d) for d in self.costrange])
         x = vol
         for i in range(4):
