@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from ._lib import lib, DpfError
+from ._lib import lib, DpfError, ERRORS
 
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3, 4
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
@@ -53,6 +53,11 @@ class _Off(object):
 
 
 _Timed.OFF = _Off()
+
+
+def _detail(tag, nbytes=0.0):
+    """The timer of one normalisation / activation launch group: live only in bench.py's detail steps (PROFILE_DETAIL)."""
+    return _Timed('norm_act', 0.0, tag, nbytes) if PROFILE_DETAIL else _Timed.OFF
 
 
 def _ptr(t):
@@ -200,6 +205,31 @@ def _out_dim(i, k, s, p, d):
     return (i + 2 * p - (d * (k - 1) + 1)) // s + 1
 
 
+def _supported(name, *args):
+    """Calls an entry point that may decline a shape: True when it ran, False on DPF_ERR_UNSUPPORTED (the caller falls through to the
+    general launch); any other code raises."""
+    rc = getattr(lib().cdll, name)(*args)
+    if rc not in (0, -3):
+        raise DpfError('%s failed: %s' % (name, ERRORS.get(rc, rc)))
+    return rc == 0
+
+
+def _conv_ws(ksize, C, K, device):
+    """The workspace slab of the dense forward / transposed conv kernels."""
+    return scratch(lib().call('dpf_conv_workspace_floats', ksize[0] * ksize[1] * ksize[2], C, K), device, 'convw')
+
+
+def _dense_timed(kind, x, K, ksize, stride, dil, sites, nfloats):
+    """The PROFILE record of a dense-conv launch.  kind: 'fwd', 'tr ' (transposed) or 'wg ' (weight gradient); x: the tensor whose grid
+    the tag names; sites: output positions of the underlying forward conv (the FLOP count's spatial factor); nfloats: floats moved."""
+    N, C = x.shape[0], x.shape[1]
+    T = ksize[0] * ksize[1] * ksize[2]
+    family = 'conv_pointwise' if T == 1 else ('conv_wgrad' if kind == 'wg ' else 'conv_igemm')
+    tag = '%s N%d C%d K%d %s%dx%dx%d k%d%d%d s%d d%d' % ((kind, N, C, K, 'x' if kind == 'wg ' else 'in') + tuple(x.shape[2:]) + tuple(ksize)
+                                                        + (stride[2], dil[2]))
+    return _Timed(family, 2.0 * N * K * C * T * sites, tag, 4.0 * nfloats)
+
+
 def _conv_fwd_raw(x, w, bias, stride, pad, dil, stats=None):
     """stats: a dict the caller hands to the following training BatchNorm (norm_act(..., stats=...)); when the launch runs on the
     LDS-DMA kernel its epilogue leaves per-tile channel sums there and the BatchNorm skips its own statistics pass."""
@@ -215,21 +245,16 @@ def _conv_fwd_raw(x, w, bias, stride, pad, dil, stats=None):
             L.call('dpf_conv_smallk_forward', _ptr(x), _ptr(w), _ptr(bias), _ptr(out), N, C, ID, IH, IW, K, kd, kh, kw, *stride, *pad, *dil,
                    _stream())
         return out
-    ws = scratch(L.call('dpf_conv_workspace_floats', kd * kh * kw, C, K), x.device, 'convw')
-    with _Timed('conv_pointwise' if kd * kh * kw == 1 else 'conv_igemm', 2.0 * N * K * C * kd * kh * kw * od * oh * ow,
-                'fwd N%d C%d K%d in%dx%dx%d k%d%d%d s%d d%d' % (N, C, K, ID, IH, IW, kd, kh, kw, stride[2], dil[2]),
-                4.0 * (x.numel() + out.numel() + w.numel())):
+    ws = _conv_ws((kd, kh, kw), C, K, x.device)
+    with _dense_timed('fwd', x, K, (kd, kh, kw), stride, dil, od * oh * ow, x.numel() + out.numel() + w.numel()):
         if stats is not None and FUSE_BN_STATS and K <= 128 and IW % 4 == 0 and kd * kh * kw > 1:
             cap = int(L.call('dpf_conv_stats_slab_doubles', N, K, od, oh, ow))
             slab = torch.empty(cap, dtype=torch.float64, device=x.device)
             parts = ctypes.c_int(0)
-            rc = L.cdll.dpf_conv_forward_stats(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), _ptr(ws), N, C, ID, IH, IW, K, kd, kh, kw,
-                                               *stride, *pad, *dil, _ptr(slab), cap, ctypes.byref(parts), _stream())
-            if rc == 0:
+            if _supported('dpf_conv_forward_stats', _ptr(x), _ptr(w), _ptr(bias), _ptr(out), _ptr(ws), N, C, ID, IH, IW, K, kd, kh, kw,
+                          *stride, *pad, *dil, _ptr(slab), cap, ctypes.byref(parts), _stream()):
                 stats.update(slab=slab, parts=int(parts.value), count=N * od * oh * ow, channels=K, ptr=out.data_ptr())
                 return out
-            if rc != -3:                                               # DPF_ERR_UNSUPPORTED -> the plain launch below
-                raise DpfError('dpf_conv_forward_stats failed: %s' % rc)
         L.call('dpf_conv_forward', _ptr(x), _ptr(w), _ptr(bias), _ptr(out), _ptr(ws), N, C, ID, IH, IW, K, kd, kh, kw,
                *stride, *pad, *dil, _stream())
     return out
@@ -248,25 +273,17 @@ def _conv_transpose_raw(x, w, bias, out_dims, ksize, stride, pad, dil, k_needed=
         # data gradient of a conv with <= 4 output channels (cost heads, normal conv): register-window kernel instead of an MFMA tile
         # with one real reduction channel
         with _Timed('conv_smallk', 2.0 * N * K * C * kd * kh * kw * ID * IH * IW, 'skd N%d C%d K%d in%dx%dx%d' % (N, C, K, ID, IH, IW)):
-            rc = L.cdll.dpf_conv_smallk_dgrad(_ptr(x), _ptr(w), _ptr(out), N, K, *out_dims, C, kd, kh, kw, *pad, _stream())
-        if rc == 0:
+            done = _supported('dpf_conv_smallk_dgrad', _ptr(x), _ptr(w), _ptr(out), N, K, *out_dims, C, kd, kh, kw, *pad, _stream())
+        if done:
             return out
-        if rc != -3:
-            raise DpfError('dpf_conv_smallk_dgrad failed: %s' % rc)
     if k_needed is not None and 0 < k_needed < K:
         out[:, k_needed:].zero_()
-        ws = scratch(L.call('dpf_conv_workspace_floats', kd * kh * kw, C, K), x.device, 'convw')
-        with _Timed('conv_igemm', 2.0 * N * k_needed * C * kd * kh * kw * ID * IH * IW,
-                    'tr  N%d C%d K%d in%dx%dx%d k%d%d%d s%d d%d' % (N, C, k_needed, ID, IH, IW, kd, kh, kw, stride[2], dil[2]),
-                    4.0 * (x.numel() + out.numel() * k_needed // K + w.numel())):
-            L.call('dpf_conv_transpose_ex', _ptr(x), _ptr(w), _ptr(bias), _ptr(out), _ptr(ws), N, C, ID, IH, IW, k_needed, K, *out_dims,
-                   kd, kh, kw, *stride, *pad, *dil, _stream())
-        return out
-    ws = scratch(L.call('dpf_conv_workspace_floats', kd * kh * kw, C, K), x.device, 'convw')
-    with _Timed('conv_pointwise' if kd * kh * kw == 1 else 'conv_igemm', 2.0 * N * K * C * kd * kh * kw * ID * IH * IW,
-                'tr  N%d C%d K%d in%dx%dx%d k%d%d%d s%d d%d' % (N, C, K, ID, IH, IW, kd, kh, kw, stride[2], dil[2]),
-                4.0 * (x.numel() + out.numel() + w.numel())):
-        L.call('dpf_conv_transpose', _ptr(x), _ptr(w), _ptr(bias), _ptr(out), _ptr(ws), N, C, ID, IH, IW, K, *out_dims, kd, kh, kw,
+        entry, chans = 'dpf_conv_transpose_ex', (k_needed, K)
+    else:
+        entry, chans = 'dpf_conv_transpose', (K,)
+    ws = _conv_ws(ksize, C, K, x.device)
+    with _dense_timed('tr ', x, chans[0], ksize, stride, dil, ID * IH * IW, x.numel() + out.numel() * chans[0] // K + w.numel()):
+        L.call(entry, _ptr(x), _ptr(w), _ptr(bias), _ptr(out), _ptr(ws), N, C, ID, IH, IW, *chans, *out_dims, kd, kh, kw,
                *stride, *pad, *dil, _stream())
     return out
 
@@ -284,9 +301,7 @@ def _conv_wgrad_raw(g, x, wshape, stride, pad, dil):
         with _Timed('conv_smallk', 2.0 * N * K * C * kd * kh * kw * QD * QH * QW, 'skw N%d C%d K%d x%dx%dx%d' % (N, C, K, ID, IH, IW)):
             lib().call('dpf_conv_smallk_wgrad', _ptr(g), _ptr(x), _ptr(dw), N, C, ID, IH, IW, K, kd, kh, kw, *stride, *pad, *dil, _stream())
         return dw
-    with _Timed('conv_pointwise' if kd * kh * kw == 1 else 'conv_wgrad', 2.0 * N * K * C * kd * kh * kw * QD * QH * QW,
-                'wg  N%d C%d K%d x%dx%dx%d k%d%d%d s%d d%d' % (N, C, K, ID, IH, IW, kd, kh, kw, stride[2], dil[2]),
-                4.0 * (x.numel() + g.numel() + dw.numel())):
+    with _dense_timed('wg ', x, K, (kd, kh, kw), stride, dil, QD * QH * QW, x.numel() + g.numel() + dw.numel()):
         L = lib()
         nws = L.call('dpf_conv_wgrad_workspace_floats', kd * kh * kw, C, K)
         ws = scratch(nws, x.device, 'wgradws')
@@ -507,33 +522,6 @@ def conv_transpose2d(x, w, stride=2, pad=1):
     return ConvTransposeFn.apply(x.unsqueeze(2), w.unsqueeze(2), (1, s, s), (0, q, q), (0, 0, 0)).squeeze(2)
 
 
-class DepthwiseFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w):
-        x, w = _c(x), _c(w)
-        _need(x, w)
-        N, C, H, W = x.shape
-        y = torch.empty_like(x)
-        lib().call('dpf_depthwise_conv2d_forward', _ptr(x), _ptr(w), _ptr(y), N, C, H, W, 3, 1, _stream())
-        ctx.save_for_backward(x, w)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, w = ctx.saved_tensors
-        gy = _c(gy)
-        N, C, H, W = x.shape
-        gx = torch.empty_like(x)
-        lib().call('dpf_depthwise_conv2d_backward_data', _ptr(gy), _ptr(w), _ptr(gx), N, C, H, W, 3, 1, _stream())
-        gw = torch.zeros_like(w)
-        lib().call('dpf_depthwise_conv2d_backward_weight', _ptr(gy), _ptr(x), _ptr(gw), N, C, H, W, 3, 1, _stream())
-        return gx, gw
-
-
-def depthwise_conv3x3(x, w):
-    return DepthwiseFn.apply(x, w)
-
-
 class DepthwiseGeneralFn(torch.autograd.Function):
     """nn.Conv2d(C, C, k, padding=pad, groups=C, bias=False), k in {1, 3}, 0 <= pad <= 3."""
 
@@ -569,6 +557,10 @@ class DepthwiseGeneralFn(torch.autograd.Function):
 
 def depthwise_conv2d(x, w, pad):
     return DepthwiseGeneralFn.apply(x, w, int(pad))
+
+
+def depthwise_conv3x3(x, w):
+    return DepthwiseGeneralFn.apply(x, w, 1)
 
 
 class MaxPoolFn(torch.autograd.Function):
@@ -624,6 +616,64 @@ def _bn_order_after(running_mean):
         BN_ORDER[1][running_mean.data_ptr()] = ev
 
 
+def _bn_sync_gather(xs, exchange):
+    """SyncBatchNorm, first half: every tensor's local {mean, M2} per channel and its element count go into a [2C+1] slice of one packed
+    vector -- the tensors are independent, so they travel in ONE all-gather.  -> per tensor (gathered [W, tot], its slice's offset)."""
+    offs, tot = [], 0
+    for x in xs:
+        offs.append(tot)
+        tot += 2 * x.shape[1] + 1
+    packed = torch.empty(tot, dtype=torch.float32, device=xs[0].device)
+    for x, off in zip(xs, offs):
+        N, C = x.shape[0], x.shape[1]
+        S = x.numel() // (N * C)
+        lib().call('dpf_bn_local_moments', _ptr(x), N, C, S, _ptr(packed[off:]), _ptr(scratch(2 * C, x.device)), _stream())
+        packed[off + 2 * C] = float(N * S)
+    gathered = exchange.all_gather(packed)
+    return [(gathered, off) for off in offs]
+
+
+def _bn_stats(x, mode, running_mean, running_var, holder=None, sync=None):
+    """(mean, invstd, read_x) of x [N, C, ...] for mode 1 batch norm (training: the launch also updates the running statistics, in
+    BN_ORDER), 2 batch norm (eval), 3 instance norm (one statistic per sample and channel: [N * C]); mode 0 -> (None, None, False).
+    holder: the dict the producing convolution got as ``stats`` (_conv_fwd_raw); when it describes exactly this tensor its per-tile
+    channel sums replace the pass over x, and it is cleared.  sync: SyncBatchNorm, x's entry of _bn_sync_gather.  read_x: the
+    statistics cost a pass over x (byte accounting)."""
+    if mode == 0:
+        return None, None, False
+    N, C = x.shape[0], x.shape[1]
+    S = x.numel() // (N * C)
+    if mode == 3:
+        N, C = 1, N * C
+    L = lib()
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    invstd = torch.empty_like(mean)
+    read_x = True
+    if mode == 1:
+        _bn_order_before(running_mean)
+    if mode == 2:
+        L.call('dpf_bn_eval_stats', _ptr(running_mean), _ptr(running_var), C, BN_EPS, _ptr(mean), _ptr(invstd), _stream())
+        read_x = False
+    elif mode == 1 and sync is not None:
+        gathered, off = sync
+        moments = gathered[:, off:off + 2 * C].contiguous()
+        counts = gathered[:, off + 2 * C].contiguous()
+        L.call('dpf_bn_merge_moments', _ptr(moments), _ptr(counts), gathered.shape[0], C, BN_EPS, BN_MOMENTUM, _ptr(running_mean),
+               _ptr(running_var), _ptr(mean), _ptr(invstd), _stream())
+    elif mode == 1 and holder and holder.get('ptr') == x.data_ptr() and holder['channels'] == C and holder['count'] == N * S:
+        L.call('dpf_bn_finalize_partials', _ptr(holder['slab']), holder['parts'], C, N * S, BN_EPS, BN_MOMENTUM, _ptr(running_mean),
+               _ptr(running_var), _ptr(mean), _ptr(invstd), _stream())
+        holder.clear()
+        read_x = False
+    else:
+        momentum, rm, rv = (BN_MOMENTUM, running_mean, running_var) if mode == 1 else (0.0, None, None)
+        L.call('dpf_bn_stats', _ptr(x), N, C, S, BN_EPS, momentum, _ptr(rm), _ptr(rv), _ptr(mean), _ptr(invstd),
+               _ptr(scratch(2 * C, x.device)), _stream())
+    if mode == 1:
+        _bn_order_after(running_mean)
+    return mean, invstd, read_x
+
+
 class NormActFn(torch.autograd.Function):
     """y = act(norm(x) * w + b + res) + res2 with norm = batch norm (training/eval) or instance norm, or no norm."""
 
@@ -638,59 +688,20 @@ class NormActFn(torch.autograd.Function):
         N, C = x.shape[0], x.shape[1]
         S = x.numel() // (N * C)
         L = lib()
-        mean = invstd = None
-        n_, c_, wmod = N, C, C
-        fused_stats = mode == 1 and exchange is None and bool(stats) and stats.get('ptr') == x.data_ptr()
-        # algorithmic bytes: statistics pass (unless the conv epilogue made them) + apply (x and residuals in, y out)
-        nb = 4.0 * x.numel() * ((0 if (mode in (0, 2) or fused_stats) else 1) + 2 + (res is not None) + (res2 is not None))
-        timer = _Timed('norm_act', 0.0, 'naf', nb) if PROFILE_DETAIL else _Timed.OFF
-        timer.__enter__()
-        if mode == 1:
-            _bn_order_before(running_mean)
-        if mode == 1 and exchange is not None:
-            mean = torch.empty(C, dtype=torch.float32, device=x.device)
-            invstd = torch.empty_like(mean)
-            ws = scratch(2 * C, x.device)
-            packed = torch.empty(2 * C + 1, dtype=torch.float32, device=x.device)
-            packed[2 * C] = float(N * S)
-            L.call('dpf_bn_local_moments', _ptr(x), N, C, S, _ptr(packed), _ptr(ws), _stream())
-            gathered = exchange.all_gather(packed)                       # [W, 2C+1]
-            moments = gathered[:, :2 * C].contiguous()
-            counts = gathered[:, 2 * C].contiguous()
-            L.call('dpf_bn_merge_moments', _ptr(moments), _ptr(counts), gathered.shape[0], C, BN_EPS, BN_MOMENTUM, _ptr(running_mean),
-                   _ptr(running_var), _ptr(mean), _ptr(invstd), _stream())
-        elif mode == 1 and stats and stats.get('ptr') == x.data_ptr() and stats['channels'] == C and stats['count'] == N * S:
-            # the producing convolution already left per-tile channel sums (dpf_conv_forward_stats): no pass over x
-            mean = torch.empty(C, dtype=torch.float32, device=x.device)
-            invstd = torch.empty_like(mean)
-            L.call('dpf_bn_finalize_partials', _ptr(stats['slab']), stats['parts'], C, N * S, BN_EPS, BN_MOMENTUM, _ptr(running_mean),
-                   _ptr(running_var), _ptr(mean), _ptr(invstd), _stream())
-            stats.clear()
-        elif mode == 1:
-            mean = torch.empty(C, dtype=torch.float32, device=x.device)
-            invstd = torch.empty_like(mean)
-            ws = scratch(2 * C, x.device)
-            L.call('dpf_bn_stats', _ptr(x), N, C, S, BN_EPS, BN_MOMENTUM, _ptr(running_mean), _ptr(running_var), _ptr(mean), _ptr(invstd),
-                   _ptr(ws), _stream())
-        elif mode == 2:
-            mean = torch.empty(C, dtype=torch.float32, device=x.device)
-            invstd = torch.empty_like(mean)
-            L.call('dpf_bn_eval_stats', _ptr(running_mean), _ptr(running_var), C, BN_EPS, _ptr(mean), _ptr(invstd), _stream())
-        elif mode == 3:
-            n_, c_ = 1, N * C
-            mean = torch.empty(c_, dtype=torch.float32, device=x.device)
-            invstd = torch.empty_like(mean)
-            ws = scratch(2 * c_, x.device)
-            L.call('dpf_bn_stats', _ptr(x), n_, c_, S, BN_EPS, 0.0, None, None, _ptr(mean), _ptr(invstd), _ptr(ws), _stream())
-        if mode == 1:
-            _bn_order_after(running_mean)
-        y = torch.empty_like(x)
-        L.call('dpf_norm_act_forward', _ptr(x), _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias), wmod, _ptr(res), _ptr(res2), act,
-               _ptr(slope), float(slope_const), _ptr(y), n_, c_, S, _stream())
-        timer.__exit__()
+        n_, c_ = (1, N * C) if mode == 3 else (N, C)
+        wmod = C
+        sync = exchange if mode == 1 else None
+        with _detail('naf') as timer:
+            moments = _bn_sync_gather([x], sync)[0] if sync is not None else None
+            mean, invstd, read_x = _bn_stats(x, mode, running_mean, running_var, stats, moments)
+            # algorithmic bytes: statistics pass (unless the conv epilogue made them) + apply (x and residuals in, y out)
+            timer.nbytes = 4.0 * x.numel() * (read_x + 2 + (res is not None) + (res2 is not None))
+            y = torch.empty_like(x)
+            L.call('dpf_norm_act_forward', _ptr(x), _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias), wmod, _ptr(res), _ptr(res2), act,
+                   _ptr(slope), float(slope_const), _ptr(y), n_, c_, S, _stream())
         ctx.save_for_backward(x, weight, bias, slope, res, mean, invstd)
         ctx.cfg = (mode, act, float(slope_const), n_, c_, S, wmod, res2 is not None)
-        ctx.exchange = exchange if mode == 1 else None
+        ctx.exchange = sync
         return y
 
     @staticmethod
@@ -710,21 +721,19 @@ class NormActFn(torch.autograd.Function):
         args = (_ptr(x), _ptr(gy), _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias), wmod, _ptr(res), act, _ptr(slope), slope_const,
                 training, _ptr(dx), _ptr(dres), _ptr(dweight), _ptr(dbias), _ptr(dslope))
         # algorithmic bytes: reduce pass (x, gy) when the norm trains + apply pass (x, gy in; dx, dres out)
-        timer = _Timed('norm_act', 0.0, 'nab', 4.0 * x.numel() * ((2 if training else 0) + 2 + (dx is not None) + (dres is not None))) if PROFILE_DETAIL else _Timed.OFF
-        timer.__enter__()
-        if ctx.exchange is not None:
-            # SyncBatchNorm: local reductions, sum over the ranks, then dx with the global element count
-            # ws[3C] carries this rank's element count through the same all-reduce: uneven per-rank batches need no extra
-            # collective and no host synchronisation
-            ws = torch.empty(3 * c_ + 1, dtype=torch.float32, device=x.device)
-            L.call('dpf_norm_act_backward_ex', *args, _ptr(ws), n_, c_, S, 1, 0.0, _stream())
-            ws[3 * c_:].fill_(float(n_) * float(S))
-            ctx.exchange.all_reduce_sum_(ws)
-            L.call('dpf_norm_act_backward_ex', *args, _ptr(ws), n_, c_, S, 2, -1.0, _stream())
-        else:
-            ws = zero_slot(3 * c_, x.device)                               # pre-zeroed: phase 3 skips the per-layer memset
-            L.call('dpf_norm_act_backward_ex', *args, _ptr(ws), n_, c_, S, 3, 0.0, _stream())
-        timer.__exit__()
+        with _detail('nab', 4.0 * x.numel() * ((2 if training else 0) + 2 + (dx is not None) + (dres is not None))):
+            if ctx.exchange is not None:
+                # SyncBatchNorm: local reductions, sum over the ranks, then dx with the global element count
+                # ws[3C] carries this rank's element count through the same all-reduce: uneven per-rank batches need no extra
+                # collective and no host synchronisation
+                ws = torch.empty(3 * c_ + 1, dtype=torch.float32, device=x.device)
+                L.call('dpf_norm_act_backward_ex', *args, _ptr(ws), n_, c_, S, 1, 0.0, _stream())
+                ws[3 * c_:].fill_(float(n_) * float(S))
+                ctx.exchange.all_reduce_sum_(ws)
+                L.call('dpf_norm_act_backward_ex', *args, _ptr(ws), n_, c_, S, 2, -1.0, _stream())
+            else:
+                ws = zero_slot(3 * c_, x.device)                               # pre-zeroed: phase 3 skips the per-layer memset
+                L.call('dpf_norm_act_backward_ex', *args, _ptr(ws), n_, c_, S, 3, 0.0, _stream())
         dres2 = gy if (has_res2 and ctx.needs_input_grad[5]) else None
         return dx, dweight, dbias, dslope, dres, dres2, None, None, None, None, None, None, None
 
@@ -754,57 +763,16 @@ class NormActCatFn(torch.autograd.Function):
         cat = torch.empty((N, Ctot) + tuple(xs[0].shape[2:]), dtype=torch.float32, device=xs[0].device)
         L = lib()
         saved, c0 = [], 0
-        timer = _Timed('norm_act', 0.0, 'ncf', 4.0 * sum(x.numel() for x in xs) * 2) if PROFILE_DETAIL else _Timed.OFF
-        timer.__enter__()
         sync = exchange if mode == 1 else None
-        if sync is not None:
-            # SyncBatchNorm: the branches are independent, so their {mean, M2, count} vectors travel in ONE all-gather
-            offs, tot = [], 0
-            for C in Cs:
-                offs.append(tot)
-                tot += 2 * C + 1
-            packed = torch.empty(tot, dtype=torch.float32, device=xs[0].device)
+        with _detail('ncf', 4.0 * sum(x.numel() for x in xs) * 2):
+            moments = _bn_sync_gather(xs, sync) if sync is not None else [None] * n
             for i in range(n):
-                wsb = scratch(2 * Cs[i], xs[i].device)
-                L.call('dpf_bn_local_moments', _ptr(xs[i]), N, Cs[i], S, _ptr(packed[offs[i]:]), _ptr(wsb), _stream())
-                packed[offs[i] + 2 * Cs[i]] = float(N * S)
-            gathered = sync.all_gather(packed)                               # [W, tot]
-        for i in range(n):
-            x, C = xs[i], Cs[i]
-            mean = torch.empty(C, dtype=torch.float32, device=x.device)
-            invstd = torch.empty_like(mean)
-            st = holders[i] if holders else None
-            if sync is not None:
-                _bn_order_before(rms[i])
-                moments = gathered[:, offs[i]:offs[i] + 2 * C].contiguous()
-                counts = gathered[:, offs[i] + 2 * C].contiguous()
-                L.call('dpf_bn_merge_moments', _ptr(moments), _ptr(counts), gathered.shape[0], C, BN_EPS, BN_MOMENTUM, _ptr(rms[i]), _ptr(rvs[i]),
-                       _ptr(mean), _ptr(invstd), _stream())
-                _bn_order_after(rms[i])
+                x, C = xs[i], Cs[i]
+                mean, invstd, _ = _bn_stats(x, mode, rms[i], rvs[i], holders[i] if holders else None, moments[i])
                 L.call('dpf_norm_act_forward_slice', _ptr(x), _ptr(mean), _ptr(invstd), _ptr(ws[i]), _ptr(bs[i]), C, None, None, act, None, 0.0,
                        _ptr(cat), Ctot, c0, N, C, S, _stream())
                 saved += [x, ws[i], bs[i], mean, invstd]
                 c0 += C
-                continue
-            if mode == 1:
-                _bn_order_before(rms[i])
-            if mode == 1 and st and st.get('ptr') == x.data_ptr() and st['channels'] == C and st['count'] == N * S:
-                L.call('dpf_bn_finalize_partials', _ptr(st['slab']), st['parts'], C, N * S, BN_EPS, BN_MOMENTUM, _ptr(rms[i]), _ptr(rvs[i]),
-                       _ptr(mean), _ptr(invstd), _stream())
-                st.clear()
-            elif mode == 1:
-                wsb = scratch(2 * C, x.device)
-                L.call('dpf_bn_stats', _ptr(x), N, C, S, BN_EPS, BN_MOMENTUM, _ptr(rms[i]), _ptr(rvs[i]), _ptr(mean), _ptr(invstd), _ptr(wsb),
-                       _stream())
-            else:
-                L.call('dpf_bn_eval_stats', _ptr(rms[i]), _ptr(rvs[i]), C, BN_EPS, _ptr(mean), _ptr(invstd), _stream())
-            if mode == 1:
-                _bn_order_after(rms[i])
-            L.call('dpf_norm_act_forward_slice', _ptr(x), _ptr(mean), _ptr(invstd), _ptr(ws[i]), _ptr(bs[i]), C, None, None, act, None, 0.0,
-                   _ptr(cat), Ctot, c0, N, C, S, _stream())
-            saved += [x, ws[i], bs[i], mean, invstd]
-            c0 += C
-        timer.__exit__()
         ctx.save_for_backward(*saved)
         ctx.cfg = (mode, act, n, N, tuple(Cs), S, Ctot)
         ctx.exchange = sync
@@ -817,47 +785,45 @@ class NormActCatFn(torch.autograd.Function):
         sv = ctx.saved_tensors
         L = lib()
         grads, c0 = [], 0
-        timer = _Timed('norm_act', 0.0, 'ncb', 4.0 * gcat.numel() * 5) if PROFILE_DETAIL else _Timed.OFF
-        timer.__enter__()
-        outs = []
-        for i in range(n):
-            x, w, b, mean, invstd = sv[5 * i:5 * i + 5]
-            outs.append((torch.empty_like(x) if ctx.needs_input_grad[4 + 5 * i] else None,
-                         torch.empty_like(w) if ctx.needs_input_grad[4 + 5 * i + 1] else None,
-                         torch.empty_like(b) if ctx.needs_input_grad[4 + 5 * i + 2] else None))
-        if ctx.exchange is not None:
-            # SyncBatchNorm: local reductions of every branch, ONE all-reduce of the packed [3 C_i + 1] vectors (the last slot of each
-            # carries this rank's element count), then dx with the global counts
-            offs, tot = [], 0
-            for C in Cs:
-                offs.append(tot)
-                tot += 3 * C + 1
-            ws_all = torch.empty(tot, dtype=torch.float32, device=gcat.device)
-            for phase in (1, 2):
-                c0 = 0
-                for i in range(n):
-                    x, w, b, mean, invstd = sv[5 * i:5 * i + 5]
-                    dx, dw, db = outs[i]
-                    L.call('dpf_norm_act_backward_slice_ex', _ptr(x), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(w), _ptr(b), Cs[i], None,
-                           act, None, 0.0, 1, _ptr(dx), None, _ptr(dw), _ptr(db), None, _ptr(ws_all[offs[i]:]), N, Cs[i], S, phase,
-                           0.0 if phase == 1 else -1.0, _stream())
-                    if phase == 1:
-                        ws_all[offs[i] + 3 * Cs[i]] = float(N) * float(S)
-                    c0 += Cs[i]
-                if phase == 1:
-                    ctx.exchange.all_reduce_sum_(ws_all)
-        else:
+        with _detail('ncb', 4.0 * gcat.numel() * 5):
+            outs = []
             for i in range(n):
                 x, w, b, mean, invstd = sv[5 * i:5 * i + 5]
-                C = Cs[i]
-                dx, dw, db = outs[i]
-                wsb = scratch(3 * C, x.device)
-                L.call('dpf_norm_act_backward_slice', _ptr(x), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(w), _ptr(b), C, None, act,
-                       None, 0.0, 1 if mode == 1 else 0, _ptr(dx), None, _ptr(dw), _ptr(db), None, _ptr(wsb), N, C, S, _stream())
-                c0 += C
-        for dx, dw, db in outs:
-            grads += [dx, dw, db, None, None]
-        timer.__exit__()
+                outs.append((torch.empty_like(x) if ctx.needs_input_grad[4 + 5 * i] else None,
+                             torch.empty_like(w) if ctx.needs_input_grad[4 + 5 * i + 1] else None,
+                             torch.empty_like(b) if ctx.needs_input_grad[4 + 5 * i + 2] else None))
+            if ctx.exchange is not None:
+                # SyncBatchNorm: local reductions of every branch, ONE all-reduce of the packed [3 C_i + 1] vectors (the last slot of each
+                # carries this rank's element count), then dx with the global counts
+                offs, tot = [], 0
+                for C in Cs:
+                    offs.append(tot)
+                    tot += 3 * C + 1
+                ws_all = torch.empty(tot, dtype=torch.float32, device=gcat.device)
+                for phase in (1, 2):
+                    c0 = 0
+                    for i in range(n):
+                        x, w, b, mean, invstd = sv[5 * i:5 * i + 5]
+                        dx, dw, db = outs[i]
+                        L.call('dpf_norm_act_backward_slice_ex', _ptr(x), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(w), _ptr(b), Cs[i], None,
+                               act, None, 0.0, 1, _ptr(dx), None, _ptr(dw), _ptr(db), None, _ptr(ws_all[offs[i]:]), N, Cs[i], S, phase,
+                               0.0 if phase == 1 else -1.0, _stream())
+                        if phase == 1:
+                            ws_all[offs[i] + 3 * Cs[i]] = float(N) * float(S)
+                        c0 += Cs[i]
+                    if phase == 1:
+                        ctx.exchange.all_reduce_sum_(ws_all)
+            else:
+                for i in range(n):
+                    x, w, b, mean, invstd = sv[5 * i:5 * i + 5]
+                    C = Cs[i]
+                    dx, dw, db = outs[i]
+                    wsb = scratch(3 * C, x.device)
+                    L.call('dpf_norm_act_backward_slice', _ptr(x), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(w), _ptr(b), C, None, act,
+                           None, 0.0, 1 if mode == 1 else 0, _ptr(dx), None, _ptr(dw), _ptr(db), None, _ptr(wsb), N, C, S, _stream())
+                    c0 += C
+            for dx, dw, db in outs:
+                grads += [dx, dw, db, None, None]
         return (None, None, None, None) + tuple(grads)
 
 
@@ -867,17 +833,12 @@ def _conv_transpose_acc(x, w, out, ksize, stride, pad, dil):
     N, C, ID, IH, IW = x.shape
     K = w.shape[1]
     kd, kh, kw = ksize
-    L = lib()
-    ws = scratch(L.call('dpf_conv_workspace_floats', kd * kh * kw, C, K), x.device, 'convw')
-    with _Timed('conv_igemm', 2.0 * N * K * C * kd * kh * kw * ID * IH * IW,
-                'tr  N%d C%d K%d in%dx%dx%d k%d%d%d s%d d%d' % (N, C, K, ID, IH, IW, kd, kh, kw, stride[2], dil[2]),
-                4.0 * (x.numel() + 2 * out.numel() + w.numel())):
-        rc = L.cdll.dpf_conv_transpose_acc(_ptr(x), _ptr(w), None, _ptr(out), _ptr(ws), N, C, ID, IH, IW, K, K, *out.shape[2:], kd, kh, kw,
-                                           *stride, *pad, *dil, 1, _stream())
-    if rc == -3:
+    ws = _conv_ws(ksize, C, K, x.device)
+    with _dense_timed('tr ', x, K, ksize, stride, dil, ID * IH * IW, x.numel() + 2 * out.numel() + w.numel()):
+        done = _supported('dpf_conv_transpose_acc', _ptr(x), _ptr(w), None, _ptr(out), _ptr(ws), N, C, ID, IH, IW, K, K, *out.shape[2:],
+                          kd, kh, kw, *stride, *pad, *dil, 1, _stream())
+    if not done:
         out.add_(_conv_transpose_raw(x, w, None, out.shape[2:], ksize, stride, pad, dil))
-    elif rc != 0:
-        raise DpfError('dpf_conv_transpose_acc failed: %s' % rc)
     return out
 
 
@@ -909,16 +870,7 @@ class ConvBnCatFn(torch.autograd.Function):
         for i in range(n):
             w, bw, bb, rm, rv = params[5 * i:5 * i + 5]
             y, C, st = ys[i], Cs[i], saved[i]
-            mean = torch.empty(C, dtype=torch.float32, device=x.device)
-            invstd = torch.empty_like(mean)
-            if mode == 1 and st:
-                L.call('dpf_bn_finalize_partials', _ptr(st['slab']), st['parts'], C, N * S, BN_EPS, BN_MOMENTUM, _ptr(rm), _ptr(rv), _ptr(mean),
-                       _ptr(invstd), _stream())
-            elif mode == 1:
-                wsb = scratch(2 * C, x.device)
-                L.call('dpf_bn_stats', _ptr(y), N, C, S, BN_EPS, BN_MOMENTUM, _ptr(rm), _ptr(rv), _ptr(mean), _ptr(invstd), _ptr(wsb), _stream())
-            else:
-                L.call('dpf_bn_eval_stats', _ptr(rm), _ptr(rv), C, BN_EPS, _ptr(mean), _ptr(invstd), _stream())
+            mean, invstd, _ = _bn_stats(y, mode, rm, rv, st)
             L.call('dpf_norm_act_forward_slice', _ptr(y), _ptr(mean), _ptr(invstd), _ptr(bw), _ptr(bb), C, None, None, ACT_NONE, None, 0.0,
                    _ptr(cat), Ctot, c0, N, C, S, _stream())
             keep += [w, y, bw, bb, mean, invstd]

@@ -878,6 +878,29 @@ def test_side_stream_weight_gradients_match_in_line(golden_dir, monkeypatch, bn_
             assert (a - b).norm().item() / n < 1e-3, name
 
 
+def test_conv_bn_cat_running_statistics_keep_the_pass_order_on_two_streams(golden_dir, monkeypatch):
+    """DPF_CONV_BN_CAT=1 with the two feature passes on two streams: the conv_dilate BatchNorms take their statistics through the same
+    ordered launch as every other training BatchNorm (ops.BN_ORDER), so the second pass's running-statistics update waits for the first
+    pass's.  Deterministic mode: after one two-stream step the running statistics are bit-equal to those of the one-stream step."""
+    from dualpixelface_amd import ops
+    import dualpixelface_amd.stereodpnet as sdn
+    monkeypatch.setenv('DPF_CONV_BN_CAT', '1')
+    g = np.load(golden_dir + '/e2e_train_64x96_b1.npz')
+    runs = []
+    with ops.deterministic_mode():
+        for two_streams in (False, True):
+            monkeypatch.setattr(sdn, 'FEATURES_TWO_STREAMS', two_streams)
+            model = build_model(True)
+            model.train_step(load_batch(g))
+            torch.cuda.synchronize()
+            runs.append({k: v.clone() for k, v in model.state_dict().items()
+                         if '.conv_dilate.' in k and k.endswith(('.1.running_mean', '.1.running_var'))})
+    one, two = runs
+    assert len(one) >= 2 and one.keys() == two.keys()
+    for k in one:
+        assert torch.equal(one[k], two[k]), k
+
+
 @pytest.mark.parametrize('family', ['psmnet', 'nnet'])
 def test_other_plugins_honour_bf16_operand_precision(golden_dir, family):
     """option.precision = 'bf16' on the PSMNet / NNet plugins (StereoNet shares their code path; bench.py --model stereonet --precision bf16): same graph, the dense convs round their operands to bf16.  The
