@@ -15,15 +15,6 @@
 
 namespace {
 
-// In-kernel s_memtime stamps of one workgroup (-DDPF_STAMPS builds only; diagnostic)
-#ifdef DPF_STAMPS
-__device__ unsigned long long g_stamps[16 * 128 * 2];
-#define DPF_STAMP(step, slot)                                                                                          \
-  if (blockIdx.x == 3000 && lane == 0 && (step) < 128) g_stamps[(DPF_STAMP_WAVE * 128 + (step)) * 2 + (slot)] = __builtin_readcyclecounter();
-#else
-#define DPF_STAMP(step, slot)
-#endif
-
 // XCD-aware tile order: the dispatcher deals workgroups round-robin over the 8 XCDs (blockIdx % 8 labels the XCD and its L2), so with
 // the plain blockIdx -> tile map x-neighbouring tiles -- which share halo rows, offset / grad_output cache lines -- sit behind eight
 // different L2s and every line is fetched from HBM several times.  Here each label walks a CONTIGUOUS range of tiles (x fastest):
@@ -476,7 +467,6 @@ constexpr float PK_MASS0 = 128.f, PK_MASS_Q = 131072.f;   // first-pass mass bou
 // ONE voxel, so every voxel (an MFMA row) is scaled by its own largest |go| -- exact to fp32 relative to that voxel's output gradient
 typedef _Float16 dcn_f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned dcn_u32x4 __attribute__((ext_vector_type(4)));
-#define DPF_STAMP_WAVE wave
 template <int NST, int NW, bool F16>
 __global__ __launch_bounds__(64 * NW) void dcn_bwd_input_pk_kernel(const float* __restrict__ offset, const float* __restrict__ wt2 /*[T][64][CT], zero rows beyond K*/,
                                                                    const float* __restrict__ go, float* __restrict__ dx, DcnP p, GiP q, int CT,
@@ -694,7 +684,6 @@ __global__ __launch_bounds__(64 * NW) void dcn_bwd_input_pk_kernel(const float* 
     __syncthreads();
     for (int t = 0; t < p.T; ++t) {
       const int cur = t & 1;
-      if (c0 == PK_CH) { DPF_STAMP(2 * t, 0) }
       if (tid == 0) s_far[(t + 2) % 3] = 0;                     // slot of tap t + 2: nobody reads or sets it during this step
       const Off3 ocur = onext;                                  // offsets of tap t + 1
       offp += 3 * p.P;
@@ -703,7 +692,6 @@ __global__ __launch_bounds__(64 * NW) void dcn_bwd_input_pk_kernel(const float* 
         onext = Off3{np[0], np[p.P], np[2 * p.P]};
       }
       if (tables_first && t + 1 < p.T) build_table(t + 1, cur ^ 1, it, ocur);
-      if (c0 == PK_CH) { DPF_STAMP(2 * t, 1) }
       // ---- scatter of tap t
       const int* lidx = s_lidx + cur * npos * 8;
       const float* wtab = s_w + cur * npos * 8;
@@ -797,11 +785,9 @@ __global__ __launch_bounds__(64 * NW) void dcn_bwd_input_pk_kernel(const float* 
           }
         }
       }
-      if (c0 == PK_CH) { DPF_STAMP(2 * t + 1, 0) }
       if (!tables_first && t + 1 < p.T) build_table(t + 1, cur ^ 1, it, ocur);
       it_cur = it;
       tap_next(p, it);
-      if (c0 == PK_CH) { DPF_STAMP(2 * t + 1, 1) }
       __syncthreads();                                          // tables of tap t + 1 complete, those of tap t consumed
     }
     if (need_mass) {      // was the pass scaled for enough mass?
@@ -1224,8 +1210,6 @@ constexpr int STR = 256;   // row of the [CH][256] sample tile (lane-consecutive
 // NW = 8: 4 sampler waves (a voxel per thread, all CH channels) + 4 MFMA waves (64 voxels each).
 // NW = 16: 8 sampler waves (a thread PAIR per voxel, half the channels each) + 8 MFMA waves (32 voxels each): four waves per SIMD --
 //          the kernel is latency bound at one LDS-limited workgroup per CU (measured: MFMA 25 %, VALU 17 %, LDS 20 % busy with 8 waves).
-#undef DPF_STAMP_WAVE
-#define DPF_STAMP_WAVE wave_u
 // TXV: tile width (32: 4 x 2 x 32 = 256 voxels per workgroup; 16: 128 voxels, half the LDS image at the same halo ratio -- two workgroups
 // per CU, out of phase with each other).  Samplers cover the tile once (a voxel per thread, all CH channels) or twice (thread pair
 // per voxel, half the channels each) depending on NW.
@@ -1271,7 +1255,6 @@ __global__ __launch_bounds__(64 * NW) void dcn_fwd_rs_kernel(const float* __rest
       __syncthreads();
 #pragma unroll 1
       for (int t = 0; t < p.T; ++t) {
-        if (c0 == CH) { DPF_STAMP(t, 0) }
         const Off3 ocur = onext;
         offp += 3 * p.P;
         {   // always-valid pointer, unconditional loads (a conditional load is a branch in the tap loop)
@@ -1288,7 +1271,6 @@ __global__ __launch_bounds__(64 * NW) void dcn_fwd_rs_kernel(const float* __rest
           if (half == 0) fwd_sample_half_store<CH, 0, STRV>(p, g, sp, cn, s_reg, xb, c0, chan, dst);
           else fwd_sample_half_store<CH, 1, STRV>(p, g, sp, cn, s_reg, xb, c0, chan, dst);
         }
-        if (c0 == CH) { DPF_STAMP(t, 1) }
         __syncthreads();                               // barrier t: S[t&1] is complete; the MFMA waves have finished reading S[(t-1)&1]
       }
     }
@@ -1332,7 +1314,6 @@ __global__ __launch_bounds__(64 * NW) void dcn_fwd_rs_kernel(const float* __rest
             for (int m = 0; m < MT; ++m) aN[sx][m] = wtt[(2 * sx) * KT + m * 32];
         }
         __syncthreads();                               // barrier t
-        if (c0 == CH) { DPF_STAMP(t, 0) }
         const float* src = s_S + (t & 1) * (CH * STRV) + mw * (32 * NTW) + l31;
 #pragma unroll
         for (int sx = 0; sx < CH / 2; ++sx) {
@@ -1344,7 +1325,6 @@ __global__ __launch_bounds__(64 * NW) void dcn_fwd_rs_kernel(const float* __rest
 #pragma unroll
             for (int nt = 0; nt < NTW; ++nt) acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[sx][m], bv[nt], acc[m][nt], 0, 0, 0);
         }
-        if (c0 == CH) { DPF_STAMP(t, 1) }
       }
     }
 #pragma unroll
@@ -1466,8 +1446,6 @@ __device__ __forceinline__ void rs_sample_half(const DcnP& p, const RegGeo& g, c
   }
 }
 
-#undef DPF_STAMP_WAVE
-#define DPF_STAMP_WAVE wave_u
 template <int CH>
 __global__ __launch_bounds__(1024) void dcn_bwd_offset_rs_kernel(const float* __restrict__ x, const float* __restrict__ offset,
                                                                  const float* __restrict__ wt2 /*[T][64][CT], zero rows beyond K*/,
@@ -1518,7 +1496,6 @@ __global__ __launch_bounds__(1024) void dcn_bwd_offset_rs_kernel(const float* __
         else { atomicAdd(dqp, a0); atomicAdd(dqp + p.P, a1); atomicAdd(dqp + 2 * p.P, a2); }
       }
       if (i == NS) break;
-      DPF_STAMP(i, 0)
       first_chunk = c0 == 0;
       const Off3 ocur = onext;
       const bool last_tap = t + 1 == p.T;
@@ -1540,7 +1517,6 @@ __global__ __launch_bounds__(1024) void dcn_bwd_offset_rs_kernel(const float* __
         pp[0] = gd; pp[256] = gh; pp[512] = gw;
       }
       tap_next(p, it);
-      DPF_STAMP(i, 1)
       __syncthreads();                                 // step barrier
       if (last_tap) {
         t = 0; c0 += CH; it = TapIt{0, 0, 0};
@@ -1581,7 +1557,6 @@ __global__ __launch_bounds__(1024) void dcn_bwd_offset_rs_kernel(const float* __
     for (int j = 0; j <= NS; ++j) {                    // iteration j writes gcol(j) during step j - 1 (j = 0: the prologue)
       int tn = tj + 1, cn0 = cj;                       // step j + 1
       if (tn == p.T) { tn = 0; cn0 += CH; }
-      DPF_STAMP(j, 0)
       if (j < NS) {
         float a[16];
 #pragma unroll
@@ -1608,7 +1583,6 @@ __global__ __launch_bounds__(1024) void dcn_bwd_offset_rs_kernel(const float* __
               if (CH == 16 || 4 * lg + r < CH) dst[(4 * lg + r) * XS + (2 * sp2 + u) * 16] = acc[u][r];   // D row = channel, col = voxel
         }
       }
-      DPF_STAMP(j, 1)
       __syncthreads();                                 // j = 0: prologue barrier; else the barrier of step j - 1
       tj = tn; cj = cn0;                               // now (tap, chunk) of step j + 1
       if (j >= 1 && j < NS && (j % p.T) == 0) {        // step j - 1 was the last tap of its chunk: help re-staging the region for step j
@@ -1639,7 +1613,6 @@ __global__ __launch_bounds__(1024) void dcn_bwd_offset_rs_kernel(const float* __
     int ts = 0, cs = 0;                                // (tap, chunk index) of the step whose samples are contracted next
 #pragma unroll 1
     for (int i = 0; i <= NS; ++i) {                    // iteration i contracts S(i - 1) during step i (i = NS: after the last barrier)
-      DPF_STAMP(i, 0)
       if (i >= 1) {
         const float* src = s_x + ((i - 1) % 3) * XT + brow;
         f32x4 wacc[4];
@@ -1661,7 +1634,6 @@ __global__ __launch_bounds__(1024) void dcn_bwd_offset_rs_kernel(const float* __
         }
         if (++ts == p.T) { ts = 0; ++cs; }
       }
-      DPF_STAMP(i, 1)
       if (i < NS) {
         __syncthreads();                               // barrier of step i
         if (i + 1 < NS && (i + 1) % p.T == 0) {        // step i was the last tap of its chunk
@@ -1721,9 +1693,6 @@ int region_geo(RegGeo& g, const DcnP& p, int CH, int R, bool aligned = false, in
   return DPF_OK;
 }
 
-// chunk width: 12 where it pads the channel count less than 16 does (35 -> 36 vs 48)
-int region_chunk(int C) { return ((C + 11) / 12 * 12 < (C + 15) / 16 * 16) ? 12 : 16; }
-
 int fill_params(DcnP& p, int B, int C, int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
                 int dd, int dh, int dw) {
   if (B <= 0 || C <= 0 || K <= 0 || C > MAXC || K > MAXC) return DPF_ERR_UNSUPPORTED;
@@ -1741,41 +1710,234 @@ int fill_params(DcnP& p, int B, int C, int D, int H, int W, int K, int kd, int k
   return DPF_OK;
 }
 
-template <typename F>
-int set_lds(F f, size_t lds) {
-  if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return DPF_ERR_LAUNCH;
+// The workspace of one layer, as float offsets from its base.  The repacked weights sit at offset 0: every kernel packs its own layout
+// there right before it launches (the packed grad_input kernel, then the lean or the region grad_offset kernel), none relies on what an
+// earlier one left.  Everything behind is placed from that region's size, the same number that sizes the workspace (the replicas once
+// overlapped a lean repack that was larger than the one they were placed behind).
+struct DcnWs {
+  long long dwtmp;    // grad_weight replicas [WG_NREP][T][nchunk][64][16]; also the floats of the repack region in front of them
+  long long wmax;     // max |W| per chunk of GI_CH input channels (packed grad_input kernel; at most 63 entries)
+  long long wexp;     // one int: weight exponent of that kernel's f16-component path
+  long long shadow;   // deterministic mode: integer shadow of grad_input (dcn_internal.h), 4 floats per element
+  long long total;
+};
+
+long long dcn_dwtmp_floats(int T, int nchunk) { return (long long)WG_NREP * T * nchunk * 64 * 16; }
+
+DcnWs dcn_ws_map(int B, int C, int D, int H, int W, int K, int T, int det) {
+  DcnWs m;
+  // the largest of every family's repack (region / gather kernels: reduce index padded; lean forward and lean backward fragment orders,
+  // which can exceed it -- C = 49..60 or 81..84 with 12-wide chunks)
+  m.dwtmp = (long long)T * (((C + 31) / 32) * 32) * (((K + 63) / 64) * 64);
+  if (T == 27 && dcn_lean_workspace_floats(C, K) > m.dwtmp) m.dwtmp = dcn_lean_workspace_floats(C, K);
+  m.wmax = m.dwtmp + dcn_dwtmp_floats(T, (C + 11) / 12);   // chunks of >= 12 channels
+  m.wexp = m.wmax + 63;
+  m.shadow = (m.wexp + 1 + 3) / 4 * 4;
+  m.total = m.shadow + (det ? 4LL * B * C * D * H * W : 0);
+  return m;
+}
+
+// rows that can be staged with float4 loads
+bool rows_vec(const float* input, int W, int sw) { return (W % 4 == 0) && (reinterpret_cast<uintptr_t>(input) % 16 == 0) && sw <= 2; }
+
+// First haloed region whose LDS image (lds_of) fits `cap` bytes: with float4-stageable rows the aligned candidates (x/z halo, y halo), widest
+// first, on a TX x TY tile (returns 1), else the unaligned halos 4 and 3 on a TXu x TYu tile (returns 0).  -1: none fits.
+template <typename LdsOf>
+int region_search(RegGeo& g, const DcnP& p, int CH, bool can_vec, const int (*cand)[2], int ncand, int TX, int TY, int TXu, int TYu, LdsOf lds_of,
+                  size_t cap) {
+  for (int i = 0; can_vec && i < ncand; ++i)
+    if (region_geo(g, p, CH, cand[i][0], true, cand[i][1], TX, TY) == DPF_OK && lds_of(g) <= cap) return 1;
+  for (int R = 4; R >= 3; --R)
+    if (region_geo(g, p, CH, R, false, -1, TXu, TYu) == DPF_OK && lds_of(g) <= cap) return 0;
+  return -1;
+}
+
+// Forward, tier 2 -- any geometry whose haloed LDS image fits: role-split region kernel (sampler waves + MFMA waves, double-buffered sample
+// tile); half-width tile (two workgroups per CU) for 16-channel chunks, full tile for 12-channel ones; with 16-byte aligned rows the region
+// gets an aligned x-origin and is staged with float4 loads.  K <= 64.  DPF_ERR_UNSUPPORTED: no image fits.
+int dcn_fwd_region(const DcnP& p, const float* input, const float* weight, const float* bias, const float* offset, float* output, float* ws,
+                   hipStream_t st) {
+  const int MT = (p.K + 31) / 32, KT = 32 * MT, CH = dcn_chunk(p.C), TXv = CH == 16 ? 16 : 32;
+  auto lds_of = [&](const RegGeo& q) { return sizeof(float) * ((size_t)CH * q.RV + (size_t)2 * CH * 8 * TXv); };
+  const int cand[6][2] = {{4, 6}, {4, 5}, {4, 4}, {3, 5}, {3, 4}, {3, 3}};
+  RegGeo ga{};
+  const int vec = region_search(ga, p, CH, rows_vec(input, p.W, p.sw), cand, 6, TXv, 2, TXv, 2, lds_of, TXv == 16 ? 80 * 1024 : 160 * 1024);
+  if (vec < 0) return DPF_ERR_UNSUPPORTED;
+  const int Cpad = (p.C + CH - 1) / CH * CH;
+  hipLaunchKernelGGL(repack_weights_pad_kernel, dim3(dpf_ew_grid((long long)p.T * Cpad * KT)), dim3(256), 0, st, weight, ws, p.K, p.C, p.T, KT, 0,
+                     Cpad);
+  const dim3 grid((unsigned)((long long)p.B * ga.tilesZ * ga.tilesY * ga.tilesX));
+  auto kern = MT == 1 ? (CH == 16 ? dcn_fwd_rs_kernel<1, 16, 8, 16> : dcn_fwd_rs_kernel<1, 12, 8, 32>)
+                      : (CH == 16 ? dcn_fwd_rs_kernel<2, 16, 8, 16> : dcn_fwd_rs_kernel<2, 12, 8, 32>);
+  if (dcn_launch(kern, grid, dim3(512), lds_of(ga), st, input, offset, ws, bias, output, p, ga, vec) != DPF_OK) return DPF_ERR_LAUNCH;
+  return dpf_check_launch();
+}
+
+// Forward, tier 3 -- everything else: one workgroup per 64 output voxels, samples gathered from global memory
+int dcn_fwd_gather(const DcnP& p, const float* input, const float* weight, const float* bias, const float* offset, float* output, float* ws,
+                   hipStream_t st) {
+  const int MT = (p.K + 31) / 32, KT = 32 * MT;
+  hipLaunchKernelGGL(repack_weights_kernel, dim3(dpf_ew_grid((long long)p.T * p.C * KT)), dim3(256), 0, st, weight, ws, p.K, p.C, p.T, KT, 0);
+  const size_t lds = sizeof(float) * (size_t)p.CP * SP;
+  const decltype(&dcn_fwd_kernel<1>) kern[4] = {dcn_fwd_kernel<1>, dcn_fwd_kernel<2>, dcn_fwd_kernel<3>, dcn_fwd_kernel<4>};   // K <= MAXC: MT <= 4
+  if (dcn_launch(kern[MT - 1], dim3((unsigned)(p.B * p.tiles_per_b)), dim3(256), lds, st, input, offset, ws, bias, output, p) != DPF_OK) return DPF_ERR_LAUNCH;
+  return dpf_check_launch();
+}
+
+// What the tiers of one backward call share
+struct DcnBwd {
+  const float *input, *weight, *offset, *grad_output;
+  float *grad_input, *grad_offset, *grad_weight, *ws;
+  DcnP p;
+  DcnWs m;
+  int CT;                 // row length of the repacked wt2[T][K][CT] (reduce = K, out = C): C rounded up to 32
+  int det;                // deterministic mode (dcn_internal.h)
+  long long* gi_shadow;   // its integer shadow of grad_input, else nullptr
+  hipStream_t st;
+};
+
+// grad_input by LDS-privatised scatter: a packed fixed-point region (two channels per ds_add_u64) with the per-chunk max |W| as the
+// quantisation bound.  DPF_ERR_UNSUPPORTED (nothing launched): K > 64 or the haloed region does not fit; the gather kernel then scatters
+// with reference-style global atomics.
+int dcn_bwd_grad_input(const DcnBwd& b, int grad_input_channels) {
+  const DcnP& p = b.p;
+  if (p.K > 64) return DPF_ERR_UNSUPPORTED;
+  GiP q{};
+  q.TZ = p.Do < 4 ? p.Do : 4;
+  int RZ = (q.TZ - 1) * p.sd + (p.kd - 1) * p.dd + 1 + 2 * GI_R;
+  if (RZ > p.D) RZ = p.D;
+  q.RZmax = RZ;
+  q.RY = (GI_TY - 1) * p.sh + (p.kh - 1) * p.dh + 1 + 2 * GI_R;
+  q.RX = (GI_TX - 1) * p.sw + (p.kw - 1) * p.dw + 1 + 2 * GI_R;
+  q.tilesZ = dpf_div_up(p.Do, q.TZ);
+  q.tilesY = dpf_div_up(p.Ho, GI_TY);
+  q.tilesX = dpf_div_up(p.Wo, GI_TX);
+  q.CG = grad_input_channels < p.C ? (grad_input_channels < 0 ? 0 : grad_input_channels) : p.C;
+  const int npos = 64 * q.TZ;
+  // region (8 packed pairs per cell + dummy cell), 2 x (lidx, w) tables, far flags, mass counters
+  const size_t lds = sizeof(long long) * (size_t)(q.RZmax * q.RY * q.RX + 1) * PK_CS + sizeof(float) * ((size_t)npos * 36 + 4 + 48) +
+                     sizeof(unsigned) * (size_t)((q.RZmax * q.RY * q.RX + 4) & ~3);
+  const long long blocks = (long long)p.B * q.tilesZ * q.tilesY * q.tilesX;
+  if (lds > 160 * 1024 || blocks >= 0x7fffffffLL || (long long)p.D * p.H * p.W >= 0x7fffffffLL) return DPF_ERR_UNSUPPORTED;
+  float* wmaxv = b.ws + b.m.wmax;
+  int* wexp = reinterpret_cast<int*>(b.ws + b.m.wexp);
+  // (matrix path 1 is exact per element everywhere: the f16 components serve path 2 only; the per-chunk maxima must leave the exponent's slot alone)
+  const bool f16 = dcn_env().gcol16 && dpf_conv_f32_x9() == 2 && p.T == 27 && dpf_div_up(p.C, GI_CH) <= 63;
+  if (f16) {
+    // the gcol B operand as f16 fragments ([T][CT / 16][4 KB] -- the bytes of wt2[T][64][CT]), max |W| from the caller's tensor
+    hipLaunchKernelGGL(dcn_repack_pk_h_kernel, dim3(16), dim3(1024), 0, b.st, b.weight, reinterpret_cast<unsigned short*>(b.ws), p.K, p.C, p.T,
+                       b.CT / PK_CH, wexp);
+    hipLaunchKernelGGL(dcn_wmax_w_kernel, dim3(dpf_div_up(p.C, GI_CH)), dim3(256), 0, b.st, b.weight, wmaxv, p.K, p.C, p.T);
+  } else {
+    hipLaunchKernelGGL(repack_weights_pad_kernel, dim3(dpf_ew_grid((long long)p.T * 64 * b.CT)), dim3(256), 0, b.st, b.weight, b.ws, p.K, p.C, p.T,
+                       b.CT, 1, 64);
+    hipLaunchKernelGGL(dcn_wmax_kernel, dim3(dpf_div_up(p.C, GI_CH)), dim3(256), 0, b.st, b.ws, wmaxv, p.T, b.CT, p.C);
+  }
+#define DPF_GIP(NS, NW) (f16 ? dcn_bwd_input_pk_kernel<NS, NW, true> : dcn_bwd_input_pk_kernel<NS, NW, false>)
+  // depth 4 = 256 voxels: 16 waves (four per SIMD, one 16-voxel sub-tile each; the 8-wave variant measured 9.6 vs 8.5 ms)
+  auto kern = q.TZ == 1 ? DPF_GIP(1, 4) : q.TZ == 2 ? DPF_GIP(2, 4) : q.TZ == 3 ? DPF_GIP(3, 4) : DPF_GIP(1, 16);
+#undef DPF_GIP
+  return dcn_launch(kern, dim3((unsigned)blocks), dim3(q.TZ <= 3 ? 256 : 1024), lds, b.st, b.offset, b.ws, b.grad_output, b.grad_input, p, q, b.CT,
+                    wmaxv, b.gi_shadow, wexp);
+}
+
+// grad_offset + grad_weight, tier 2 -- any geometry whose haloed LDS image fits next to three rotating [CH][256] tiles: role-split region
+// kernel (sampler / gcol / wgrad waves).  DPF_ERR_UNSUPPORTED: no image fits.
+int dcn_bwd_offset_region(const DcnBwd& b, int CH, int nchunk) {
+  const DcnP& p = b.p;
+  auto lds_of = [&](const RegGeo& q) { return sizeof(float) * ((size_t)CH * q.RV + (size_t)3 * CH * XS + 2 * 3 * 256); };
+  // compact 4 x 4 x 16 tile: the 256 voxels need a smaller haloed region than 4 x 2 x 32, so a wider halo fits next to the three
+  // rotating tiles -- less staging per tile and fewer samples on the global slow path
+  const int cand[7][2] = {{5, 6}, {4, 6}, {4, 5}, {4, 4}, {3, 5}, {3, 4}, {3, 3}};
+  RegGeo gr{};
+  const int vec = region_search(gr, p, CH, rows_vec(b.input, p.W, p.sw), cand, 7, 16, 4, RG_TX, RG_TY, lds_of, 160 * 1024);
+  if (vec < 0) return DPF_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(repack_weights_pad_kernel, dim3(dpf_ew_grid((long long)p.T * 64 * b.CT)), dim3(256), 0, b.st, b.weight, b.ws, p.K, p.C, p.T,
+                     b.CT, 1, 64);
+  const dim3 grid((unsigned)((long long)p.B * gr.tilesZ * gr.tilesY * gr.tilesX));
+  return dcn_launch(CH == 16 ? dcn_bwd_offset_rs_kernel<16> : dcn_bwd_offset_rs_kernel<12>, grid, dim3(1024), lds_of(gr), b.st, b.input, b.offset, b.ws,
+                    b.grad_output, b.grad_offset, b.ws + b.m.dwtmp, p, gr, b.CT, nchunk, vec, b.det);
+}
+
+// grad_offset + grad_weight on the LDS-image kernels (they rely on the packed grad_input kernel for grad_input): tier 1, the model's
+// configuration: lean-sampler kernel of dcn_lean.hip; tier 2: role-split region kernel.  Both add grad_weight partials into
+// dwtmp[8][T][nchunk][64][16], folded here.  DPF_ERR_UNSUPPORTED: neither ran, the gather kernels have to.
+int dcn_bwd_offset_weight(const DcnBwd& b, bool model_config) {
+  const DcnP& p = b.p;
+  const int CH = dcn_chunk(p.C), nchunk = (p.C + CH - 1) / CH;
+  // (16 weight columns are fetched from each chunk origin)
+  if (p.K > 64 || dcn_env().v1 || (CH == 12 && (p.C + 11) / 12 * 12 + 4 > b.CT)) return DPF_ERR_UNSUPPORTED;
+  float* dwtmp = b.ws + b.m.dwtmp;
+  if (hipMemsetAsync(dwtmp, 0, sizeof(float) * (size_t)dcn_dwtmp_floats(p.T, nchunk), b.st) != hipSuccess) return DPF_ERR_LAUNCH;
+  int rc = DPF_ERR_UNSUPPORTED;
+  if (model_config) rc = dcn_lean_bwd_offset(b.input, b.offset, b.weight, b.grad_output, b.grad_offset, dwtmp, b.ws, p.B, p.C, p.D, p.H, p.W, p.K, b.st, b.det);
+  if (rc == DPF_ERR_UNSUPPORTED) rc = dcn_bwd_offset_region(b, CH, nchunk);
+  if (rc != DPF_OK) return rc;
+  hipLaunchKernelGGL(dcn_wgrad_fold_kernel, dim3(dpf_ew_grid((long long)p.K * p.C * p.T)), dim3(256), 0, b.st, dwtmp, b.grad_weight, p.K, p.C, p.T, nchunk,
+                     CH, b.det);
   return DPF_OK;
 }
 
+// grad_offset + grad_weight, tier 3 -- everything else: samples gathered from global memory; unless dx_done, grad_input too (global atomics)
+int dcn_bwd_gather(const DcnBwd& b, bool dx_done) {
+  DcnP p = b.p;
+  const int MT = (p.K + 31) / 32, MTC = b.CT / 32;
+  hipLaunchKernelGGL(repack_weights_kernel, dim3(dpf_ew_grid((long long)p.T * p.K * b.CT)), dim3(256), 0, b.st, b.weight, b.ws, p.K, p.C, p.T, b.CT, 1);
+  const long long ntile = (long long)p.B * p.tiles_per_b;
+  {
+    const size_t lds = sizeof(float) * ((size_t)p.K * SP + (size_t)b.CT * SP + 3 * 4 * TP);
+    const decltype(&dcn_bwd_data_kernel<1, false>) kern[4][2] = {{dcn_bwd_data_kernel<1, false>, dcn_bwd_data_kernel<1, true>},   // C <= MAXC: MTC <= 4
+                                                                 {dcn_bwd_data_kernel<2, false>, dcn_bwd_data_kernel<2, true>},
+                                                                 {dcn_bwd_data_kernel<3, false>, dcn_bwd_data_kernel<3, true>},
+                                                                 {dcn_bwd_data_kernel<4, false>, dcn_bwd_data_kernel<4, true>}};
+    if (dcn_launch(kern[MTC - 1][dx_done ? 0 : 1], dim3((unsigned)ntile), dim3(256), lds, b.st, b.input, b.offset, b.ws, b.grad_output, b.grad_input, b.grad_offset, p,
+                   b.gi_shadow) != DPF_OK)
+      return DPF_ERR_LAUNCH;
+  }
+  long long nchunkw = 2048 / p.T;
+  if (nchunkw < 1) nchunkw = 1;
+  if (nchunkw > ntile) nchunkw = ntile;
+  if (b.det) nchunkw = 1;            // each dW address then receives ONE atomic add: order-independent
+  p.nchunk = (int)nchunkw;
+  // LDS of the INSTANTIATION that runs (<4, 4> for more than two row tiles on either side lays its tiles out for 4 + 4: sizing it for
+  // the actual counts put the grad_output tile outside the allocation -- C = 84 on this path returned a zero grad_weight)
+  const bool small = MT <= 2 && MTC <= 2;
+  const size_t lds = sizeof(float) * ((size_t)32 * (small ? MTC : 4) * SP + (size_t)32 * (small ? MT : 4) * SP);
+  auto kern = !small ? dcn_wgrad_kernel<4, 4>
+                     : MT == 1 ? (MTC == 1 ? dcn_wgrad_kernel<1, 1> : dcn_wgrad_kernel<1, 2>) : (MTC == 1 ? dcn_wgrad_kernel<2, 1> : dcn_wgrad_kernel<2, 2>);
+  return dcn_launch(kern, dim3((unsigned)(p.T * p.nchunk)), dim3(256), lds, b.st, b.input, b.offset, b.grad_output, b.grad_weight, p);
+}
+
 }  // namespace
+
+const DcnEnv& dcn_env() {
+  static const DcnEnv env = [] {
+    auto num = [](const char* v, int unset) { return v ? atoi(v) : unset; };
+    DcnEnv e;
+    e.v1 = getenv("DPF_DCN_V1") != nullptr;
+    e.lean = num(getenv("DPF_DCN_LEAN"), 1);
+    e.fwd6 = num(getenv("DPF_DCN_FWD6"), 1);
+    e.lean_wide12 = num(getenv("DPF_DCN_LEAN_WIDE12"), 0);
+    e.gcol16 = num(getenv("DPF_DCN_GCOL16"), 1);
+    return e;
+  }();
+  return env;
+}
 
 extern "C" {
 
 int dpf_channel_sum(const float* g, float* out, int N, int C, long long S, void* stream);   // norm_act.hip
 
-// workspace floats for dpf_deform_conv3d_forward / _backward (repacked weights)
-// floats of the repacked-weights region at the head of the workspace: the largest of every kernel family's repack (region / gather kernels:
-// reduce index padded; lean forward and lean backward fragment orders, which can exceed it -- C = 49..60 or 81..84 with 12-wide chunks).
-// The grad_weight replicas start right behind it, so the SAME number sizes the workspace and places them (they overlapped).
-static long long dcn_repack_floats(int C, int K, int T) {
-  long long repack = (long long)T * (((C + 31) / 32) * 32) * (((K + 63) / 64) * 64);
-  if (T == 27 && dcn_lean_workspace_floats(C, K) > repack) repack = dcn_lean_workspace_floats(C, K);
-  return repack;
-}
-
-static long long dcn_workspace_floats(int C, int K, int T) {
-  return (dcn_repack_floats(C, K, T) + (long long)WG_NREP * T * ((C + 11) / 12) * 64 * 16 + 64 + 3) / 4 * 4;   // + grad_weight scratch replicas (chunks of >= 12 channels) + max|W| per channel chunk
-}
-long long dpf_deform_conv3d_workspace_floats(int C, int K, int T) { return dcn_workspace_floats(C, K, T); }
-// workspace of dpf_deform_conv3d_backward*: in deterministic mode (dpf_set_deterministic) grad_input is accumulated as order-independent
-// integer pairs in a shadow behind the ordinary workspace -- 4 more floats per element of the input tensor
+// workspace floats of dpf_deform_conv3d_forward (DcnWs)
+long long dpf_deform_conv3d_workspace_floats(int C, int K, int T) { return dcn_ws_map(0, C, 0, 0, 0, K, T, 0).total; }
+// workspace floats of dpf_deform_conv3d_backward*: in deterministic mode (dpf_set_deterministic) with the integer shadow of grad_input
 long long dpf_deform_conv3d_backward_workspace_floats(int B, int C, int D, int H, int W, int K, int T) {
-  return dcn_workspace_floats(C, K, T) + (dpf_deterministic() ? 4LL * B * C * D * H * W : 0);
+  return dcn_ws_map(B, C, D, H, W, K, T, dpf_deterministic()).total;
 }
 
 // Mirrors DCN.deform_conv_forward(input, weight, bias, offset, kd,kh,kw, sd,sh,sw, pd,ph,pw, dd,dh,dw, group, deformable_group,
 // im2col_step) (deform_conv.h:10-29); group/deformable_group must be 1; im2col_step is accepted and ignored (no columns).
+// Three tiers: lean kernels (the model's configuration) -> role-split region kernel -> gather kernel; DPF_DCN_V1 leaves only the last.
 int dpf_deform_conv3d_forward(const float* input, const float* weight, const float* bias, const float* offset, float* output, float* ws,
                               int B, int C, int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph,
                               int pw, int dd, int dh, int dw, int group, int deformable_group, int im2col_step, void* stream) {
@@ -1787,82 +1949,19 @@ int dpf_deform_conv3d_forward(const float* input, const float* weight, const flo
   int rc = fill_params(p, B, C, D, H, W, K, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw);
   if (rc != DPF_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int MT = (K + 31) / 32, KT = 32 * MT;
-  const int CH = region_chunk(C);
-  // (1) the configuration the model runs (3x3x3, stride 1, padding 1, dilation 1, depth <= 4, aligned rows): lean-sampler kernels of dcn_lean.hip
-  if (kd == 3 && kh == 3 && kw == 3 && sd == 1 && sh == 1 && sw == 1 && pd == 1 && ph == 1 && pw == 1 && dd == 1 && dh == 1 && dw == 1 &&
-      !getenv("DPF_DCN_V1")) {
-    rc = dcn_lean_forward(input, offset, weight, bias, output, ws, B, C, D, H, W, K, st);
-    if (rc != DPF_ERR_UNSUPPORTED) return rc;
+  rc = DPF_ERR_UNSUPPORTED;
+  if (!dcn_env().v1) {
+    if (dcn_is_model_config(kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw)) rc = dcn_lean_forward(input, offset, weight, bias, output, ws, B, C, D, H, W, K, st);
+    if (rc == DPF_ERR_UNSUPPORTED && K <= 64) rc = dcn_fwd_region(p, input, weight, bias, offset, output, ws, st);
   }
-  // (2) any other geometry whose haloed LDS image fits: role-split region kernel (sampler waves + MFMA waves, double-buffered sample tile);
-  // half-width tile (two workgroups per CU) for 16-channel chunks, full tile for 12-channel ones; with 16-byte aligned rows the region
-  // gets an aligned x-origin and is staged with float4 loads
-  if (!getenv("DPF_DCN_V1") && MT <= 2) {
-    RegGeo ga{};
-    const bool can_vec = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(input) % 16 == 0) && sw <= 2;
-    const int TXv = CH == 16 ? 16 : 32;
-    auto lds_of = [&](const RegGeo& q) { return sizeof(float) * ((size_t)CH * q.RV + (size_t)2 * CH * 8 * TXv); };
-    const size_t lds_cap = TXv == 16 ? 80 * 1024 : 160 * 1024;
-    int vec = 0;
-    bool ok = false;
-    if (can_vec) {
-      const int cand[6][2] = {{4, 6}, {4, 5}, {4, 4}, {3, 5}, {3, 4}, {3, 3}};     // (x/z halo, y halo), widest first
-      for (int i = 0; i < 6 && !ok; ++i)
-        if (region_geo(ga, p, CH, cand[i][0], true, cand[i][1], TXv, 2) == DPF_OK && lds_of(ga) <= lds_cap) { ok = true; vec = 1; }
-    }
-    if (!ok) {
-      for (int R = 4; R >= 3 && !ok; --R)
-        if (region_geo(ga, p, CH, R, false, -1, TXv, 2) == DPF_OK && lds_of(ga) <= lds_cap) ok = true;
-    }
-    if (ok) {
-      const int Cpad = (C + CH - 1) / CH * CH;
-      hipLaunchKernelGGL(repack_weights_pad_kernel, dim3(dpf_ew_grid((long long)p.T * Cpad * KT)), dim3(256), 0, st, weight, ws, K, C, p.T, KT, 0,
-                         Cpad);
-      const size_t lds_rs = lds_of(ga);
-      const dim3 grid_rs((unsigned)((long long)B * ga.tilesZ * ga.tilesY * ga.tilesX));
-#define DPF_RS(M, Cw, Nw, Tx)                                                                                              \
-  {                                                                                                                        \
-    if (set_lds(dcn_fwd_rs_kernel<M, Cw, Nw, Tx>, lds_rs) != DPF_OK) return DPF_ERR_LAUNCH;                                \
-    hipLaunchKernelGGL((dcn_fwd_rs_kernel<M, Cw, Nw, Tx>), grid_rs, dim3(64 * Nw), lds_rs, st, input, offset, ws, bias, output, p, ga, vec); \
-  }
-      if (MT == 1) { if (CH == 16) DPF_RS(1, 16, 8, 16) else DPF_RS(1, 12, 8, 32) } else { if (CH == 16) DPF_RS(2, 16, 8, 16) else DPF_RS(2, 12, 8, 32) }
-#undef DPF_RS
-      return dpf_check_launch();
-    }
-  }
-  // (3) everything else: one workgroup per 64 output voxels, samples gathered from global memory
-  hipLaunchKernelGGL(repack_weights_kernel, dim3(dpf_ew_grid((long long)p.T * C * KT)), dim3(256), 0, st, weight, ws, K, C, p.T, KT, 0);
-  const size_t lds = sizeof(float) * (size_t)p.CP * SP;
-  const dim3 grid((unsigned)(B * p.tiles_per_b));
-#define DPF_F(M)                                                                                   \
-  {                                                                                                \
-    if (set_lds(dcn_fwd_kernel<M>, lds) != DPF_OK) return DPF_ERR_LAUNCH;                          \
-    hipLaunchKernelGGL((dcn_fwd_kernel<M>), grid, dim3(256), lds, st, input, offset, ws, bias, output, p); \
-  }
-  switch (MT) { case 1: DPF_F(1); break; case 2: DPF_F(2); break; case 3: DPF_F(3); break; default: DPF_F(4); break; }
-#undef DPF_F
-  return dpf_check_launch();
+  if (rc == DPF_ERR_UNSUPPORTED) rc = dcn_fwd_gather(p, input, weight, bias, offset, output, ws, st);
+  return rc;
 }
 
 // Mirrors DCN.deform_conv_backward(...) -> [grad_input, grad_offset, grad_weight, grad_bias] (deform_conv.h:49-69).
 // grad_input / grad_weight / grad_bias are zero-initialised here, like the reference's at::zeros_like (cu:202-205).
-int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const float* bias, const float* offset, const float* grad_output,
-                                  float* grad_input, float* grad_offset, float* grad_weight, float* grad_bias, float* ws, int B, int C,
-                                  int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd,
-                                  int dh, int dw, int group, int deformable_group, int im2col_step, int grad_input_channels, void* stream);
-
-int dpf_deform_conv3d_backward(const float* input, const float* weight, const float* bias, const float* offset, const float* grad_output,
-                               float* grad_input, float* grad_offset, float* grad_weight, float* grad_bias, float* ws, int B, int C,
-                               int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd,
-                               int dh, int dw, int group, int deformable_group, int im2col_step, void* stream) {
-  return dpf_deform_conv3d_backward_ex(input, weight, bias, offset, grad_output, grad_input, grad_offset, grad_weight, grad_bias, ws, B, C, D, H,
-                                       W, K, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw, group, deformable_group, im2col_step, C, stream);
-}
-
-// Same as dpf_deform_conv3d_backward, but grad_input is only produced for input channels [0, grad_input_channels) (the remaining
-// channels of the zero-initialised tensor stay 0): StereoDPNet's first deformable conv consumes 32 cost channels + 3 constant
-// XYZ channels (normal_module.py:166), whose gradient nobody reads.
+// grad_input is only produced for input channels [0, grad_input_channels) (the remaining channels of the zero-initialised tensor stay 0):
+// StereoDPNet's first deformable conv consumes 32 cost channels + 3 constant XYZ channels (normal_module.py:166), whose gradient nobody reads.
 int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const float* bias, const float* offset, const float* grad_output,
                                   float* grad_input, float* grad_offset, float* grad_weight, float* grad_bias, float* ws, int B, int C,
                                   int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd,
@@ -1871,185 +1970,46 @@ int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const
   (void)im2col_step; (void)bias;
   if (!input || !weight || !offset || !grad_output || !grad_input || !grad_offset || !grad_weight || !ws) return DPF_ERR_INVALID_ARG;
   if (group != 1 || deformable_group != 1) return DPF_ERR_UNSUPPORTED;
-  DcnP p{};
-  int rc = fill_params(p, B, C, D, H, W, K, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw);
+  DcnBwd b{input, weight, offset, grad_output, grad_input, grad_offset, grad_weight, ws};
+  int rc = fill_params(b.p, B, C, D, H, W, K, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw);
   if (rc != DPF_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const int MT = (K + 31) / 32, MTC = (p.CP + 31) / 32, CT = 32 * MTC;
+  b.st = (hipStream_t)stream;
+  b.CT = (b.p.CP + 31) / 32 * 32;
   const long long in_elems = (long long)B * C * D * H * W;
-  if (hipMemsetAsync(grad_input, 0, sizeof(float) * in_elems, st) != hipSuccess) return DPF_ERR_LAUNCH;
+  if (hipMemsetAsync(grad_input, 0, sizeof(float) * in_elems, b.st) != hipSuccess) return DPF_ERR_LAUNCH;
   // deterministic mode: every merge of partial results is order-independent (dcn_internal.h) -- grad_input through an integer shadow behind
   // the workspace (the caller sized it with dpf_deform_conv3d_backward_workspace_floats), the grad_weight scratch as one integer replica
-  const int det = dpf_deterministic();
-  long long* gi_shadow = nullptr;
-  if (det) {
-    gi_shadow = reinterpret_cast<long long*>(ws + dcn_workspace_floats(C, K, p.T));
-    if (reinterpret_cast<uintptr_t>(gi_shadow) & 7) return DPF_ERR_INVALID_ARG;
-    if (hipMemsetAsync(gi_shadow, 0, sizeof(long long) * 2 * (size_t)in_elems, st) != hipSuccess) return DPF_ERR_LAUNCH;
+  b.det = dpf_deterministic();
+  b.m = dcn_ws_map(B, C, D, H, W, K, b.p.T, b.det);
+  if (b.det) {
+    b.gi_shadow = reinterpret_cast<long long*>(ws + b.m.shadow);
+    if (reinterpret_cast<uintptr_t>(b.gi_shadow) & 7) return DPF_ERR_INVALID_ARG;
+    if (hipMemsetAsync(b.gi_shadow, 0, sizeof(long long) * 2 * (size_t)in_elems, b.st) != hipSuccess) return DPF_ERR_LAUNCH;
   }
-  if (hipMemsetAsync(grad_weight, 0, sizeof(float) * (size_t)K * C * p.T, st) != hipSuccess) return DPF_ERR_LAUNCH;
-  // wt2[T][K][CT]: reduce = K (A), out = C (B); the region kernels read it with K zero-padded to 64 rows
-  // grad_input: LDS-privatised scatter when the haloed region fits, else the reference-style global atomics
-  bool dx_done = false;
-  if (K <= 64) {
-    GiP q{};
-    q.TZ = p.Do < 4 ? p.Do : 4;
-    int RZ = (q.TZ - 1) * sd + (kd - 1) * dd + 1 + 2 * GI_R;
-    if (RZ > D) RZ = D;
-    q.RZmax = RZ;
-    q.RY = (GI_TY - 1) * sh + (kh - 1) * dh + 1 + 2 * GI_R;
-    q.RX = (GI_TX - 1) * sw + (kw - 1) * dw + 1 + 2 * GI_R;
-    q.tilesZ = dpf_div_up(p.Do, q.TZ);
-    q.tilesY = dpf_div_up(p.Ho, GI_TY);
-    q.tilesX = dpf_div_up(p.Wo, GI_TX);
-    q.CG = grad_input_channels < C ? (grad_input_channels < 0 ? 0 : grad_input_channels) : C;
-    const int npos = 64 * q.TZ;
-    // region (8 packed pairs per cell + dummy cell), 2 x (lidx, w) tables, far flags, mass counters
-    const size_t lds = sizeof(long long) * (size_t)(q.RZmax * q.RY * q.RX + 1) * PK_CS + sizeof(float) * ((size_t)npos * 36 + 4 + 48) +
-                       sizeof(unsigned) * (size_t)((q.RZmax * q.RY * q.RX + 4) & ~3);
-    const long long blocks = (long long)B * q.tilesZ * q.tilesY * q.tilesX;
-    if (lds <= 160 * 1024 && blocks < 0x7fffffffLL && (long long)D * H * W < 0x7fffffffLL) {
-      const dim3 grid((unsigned)blocks);
-      // packed fixed-point region (two channels per ds_add_u64): per-chunk max |W| for the quantisation bound, kept behind the
-      // grad_weight scratch in ws (the last entry of that 64-float slack: the weight exponent of the f16-component path)
-      float* wmaxv = ws + dcn_repack_floats(C, K, p.T) + (long long)WG_NREP * p.T * ((C + 11) / 12) * 64 * 16;
-      int* wexp = reinterpret_cast<int*>(wmaxv + 63);
-      static const int gh_env = getenv("DPF_DCN_GCOL16") ? atoi(getenv("DPF_DCN_GCOL16")) : 1;
-      // (matrix path 1 is exact per element everywhere: the f16 components serve path 2 only; the per-chunk maxima must leave the exponent's slot alone)
-      const bool f16 = gh_env && dpf_conv_f32_x9() == 2 && p.T == 27 && dpf_div_up(C, GI_CH) <= 63;
-      if (f16) {
-        // the gcol B operand as f16 fragments ([T][CT / 16][4 KB] -- the bytes of wt2[T][64][CT]), max |W| from the caller's tensor
-        hipLaunchKernelGGL(dcn_repack_pk_h_kernel, dim3(16), dim3(1024), 0, st, weight, reinterpret_cast<unsigned short*>(ws), K, C, p.T, CT / PK_CH, wexp);
-        hipLaunchKernelGGL(dcn_wmax_w_kernel, dim3(dpf_div_up(C, GI_CH)), dim3(256), 0, st, weight, wmaxv, K, C, p.T);
-      } else {
-        hipLaunchKernelGGL(repack_weights_pad_kernel, dim3(dpf_ew_grid((long long)p.T * 64 * CT)), dim3(256), 0, st, weight, ws, K, C, p.T, CT, 1,
-                           64);
-        hipLaunchKernelGGL(dcn_wmax_kernel, dim3(dpf_div_up(C, GI_CH)), dim3(256), 0, st, ws, wmaxv, p.T, CT, C);
-      }
-#define DPF_GIP2(NS, NWv, F)                                                                                                   \
-  {                                                                                                                            \
-    if (set_lds(dcn_bwd_input_pk_kernel<NS, NWv, F>, lds) != DPF_OK) return DPF_ERR_LAUNCH;                                    \
-    hipLaunchKernelGGL((dcn_bwd_input_pk_kernel<NS, NWv, F>), grid, dim3(64 * NWv), lds, st, offset, ws, grad_output, grad_input, p, q, CT, wmaxv, gi_shadow, wexp); \
-  }
-#define DPF_GIP(NS, NWv) { if (f16) DPF_GIP2(NS, NWv, true) else DPF_GIP2(NS, NWv, false) }
-      switch (q.TZ) {
-        case 1: DPF_GIP(1, 4); break;
-        case 2: DPF_GIP(2, 4); break;
-        case 3: DPF_GIP(3, 4); break;
-        default: DPF_GIP(1, 16); break;   // 256 voxels: 16 waves (four per SIMD, one 16-voxel sub-tile each; the 8-wave variant measured 9.6 vs 8.5 ms)
-      }
-#undef DPF_GIP
-#undef DPF_GIP2
-      dx_done = true;
-    }
-  }
-  // grad_offset + grad_weight.  (1) the model's configuration: lean-sampler kernel of dcn_lean.hip; (2) any other geometry whose haloed
-  // LDS image fits next to three rotating [CH][256] tiles: role-split region kernel (sampler / gcol / wgrad waves); both write grad_weight
-  // partials into dwtmp[8][T][nchunk][64][16], folded below; (3) everything else: global-memory gather kernels
-  const int CHb = region_chunk(C);
-  const bool can_vec = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(input) % 16 == 0) && sw <= 2;
-  const bool region_ok = dx_done && K <= 64 && !getenv("DPF_DCN_V1") && (CHb == 16 || (C + 11) / 12 * 12 + 4 <= CT);   // 16 weight columns are fetched from each chunk origin
-  float* dwtmp = ws + dcn_repack_floats(C, K, p.T);
-  const int nchunk = (C + CHb - 1) / CHb;
-  bool rs_done = false;
-  if (region_ok) {
-    if (hipMemsetAsync(dwtmp, 0, sizeof(float) * (size_t)WG_NREP * p.T * nchunk * 64 * 16, st) != hipSuccess) return DPF_ERR_LAUNCH;
-    if (kd == 3 && kh == 3 && kw == 3 && sd == 1 && sh == 1 && sw == 1 && pd == 1 && ph == 1 && pw == 1 && dd == 1 && dh == 1 && dw == 1 &&
-        CHb == dcn_lean_chunk(C)) {
-      rc = dcn_lean_bwd_offset(input, offset, weight, grad_output, grad_offset, dwtmp, ws, B, C, D, H, W, K, st, det);
-      if (rc == DPF_OK) rs_done = true;
-      else if (rc != DPF_ERR_UNSUPPORTED) return rc;
-    }
-  }
-  if (!rs_done && region_ok) {
-    RegGeo gr{};
-    auto lds_of = [&](const RegGeo& qq) { return sizeof(float) * ((size_t)CHb * qq.RV + (size_t)3 * CHb * XS + 2 * 3 * 256); };
-    bool ok = false;
-    int vec_rs = 0;
-    if (can_vec) {
-      // compact 4 x 4 x 16 tile: the 256 voxels need a smaller haloed region than 4 x 2 x 32, so a wider halo fits next to the three
-      // rotating tiles -- less staging per tile and fewer samples on the global slow path
-      const int cand[7][2] = {{5, 6}, {4, 6}, {4, 5}, {4, 4}, {3, 5}, {3, 4}, {3, 3}};
-      for (int i = 0; i < 7 && !ok; ++i)
-        if (region_geo(gr, p, CHb, cand[i][0], true, cand[i][1], 16, 4) == DPF_OK && lds_of(gr) <= 160 * 1024) { ok = true; vec_rs = 1; }
-    }
-    if (!ok) {
-      for (int R = 4; R >= 3 && !ok; --R)
-        if (region_geo(gr, p, CHb, R) == DPF_OK && lds_of(gr) <= 160 * 1024) ok = true;
-    }
-    if (ok) {
-      // (the lean kernel may have overwritten ws: wt2[T][64][CT] again)
-      hipLaunchKernelGGL(repack_weights_pad_kernel, dim3(dpf_ew_grid((long long)p.T * 64 * CT)), dim3(256), 0, st, weight, ws, K, C, p.T, CT, 1, 64);
-      const size_t lds = lds_of(gr);
-      const dim3 grid((unsigned)((long long)B * gr.tilesZ * gr.tilesY * gr.tilesX));
-#define DPF_OFFRS(Cw)                                                                                                          \
-  {                                                                                                                            \
-    if (set_lds(dcn_bwd_offset_rs_kernel<Cw>, lds) != DPF_OK) return DPF_ERR_LAUNCH;                                           \
-    hipLaunchKernelGGL((dcn_bwd_offset_rs_kernel<Cw>), grid, dim3(1024), lds, st, input, offset, ws, grad_output, grad_offset, dwtmp, p, gr, \
-                       CT, nchunk, vec_rs, det);                                                                               \
-  }
-      if (CHb == 16) DPF_OFFRS(16) else DPF_OFFRS(12)
-#undef DPF_OFFRS
-      rs_done = true;
-    }
-  }
-  if (rs_done) {
-    hipLaunchKernelGGL(dcn_wgrad_fold_kernel, dim3(dpf_ew_grid((long long)K * C * p.T)), dim3(256), 0, st, dwtmp, grad_weight, K, C, p.T, nchunk, CHb, det);
-  } else {
-    hipLaunchKernelGGL(repack_weights_kernel, dim3(dpf_ew_grid((long long)p.T * K * CT)), dim3(256), 0, st, weight, ws, K, C, p.T, CT, 1);
-    {
-      const size_t lds = sizeof(float) * ((size_t)K * SP + (size_t)CT * SP + 3 * 4 * TP);
-      const dim3 grid((unsigned)(B * p.tiles_per_b));
-#define DPF_D(M)                                                                                                       \
-  {                                                                                                                    \
-    if (dx_done) {                                                                                                     \
-      if (set_lds(dcn_bwd_data_kernel<M, false>, lds) != DPF_OK) return DPF_ERR_LAUNCH;                                \
-      hipLaunchKernelGGL((dcn_bwd_data_kernel<M, false>), grid, dim3(256), lds, st, input, offset, ws, grad_output, grad_input, grad_offset, p, gi_shadow); \
-    } else {                                                                                                           \
-      if (set_lds(dcn_bwd_data_kernel<M, true>, lds) != DPF_OK) return DPF_ERR_LAUNCH;                                 \
-      hipLaunchKernelGGL((dcn_bwd_data_kernel<M, true>), grid, dim3(256), lds, st, input, offset, ws, grad_output, grad_input, grad_offset, p, gi_shadow); \
-    }                                                                                                                  \
-  }
-      switch (MTC) { case 1: DPF_D(1); break; case 2: DPF_D(2); break; case 3: DPF_D(3); break; default: DPF_D(4); break; }
-#undef DPF_D
-    }
-    const long long ntile = (long long)B * p.tiles_per_b;
-    long long nchunkw = 2048 / p.T;
-    if (nchunkw < 1) nchunkw = 1;
-    if (nchunkw > ntile) nchunkw = ntile;
-    if (det) nchunkw = 1;            // each dW address then receives ONE atomic add: order-independent
-    p.nchunk = (int)nchunkw;
-    // LDS of the INSTANTIATION that runs (<4, 4> for more than two row tiles on either side lays its tiles out for 4 + 4: sizing it for
-    // the actual counts put the grad_output tile outside the allocation -- C = 84 on this path returned a zero grad_weight)
-    const bool small = MT <= 2 && MTC <= 2;
-    const size_t lds = sizeof(float) * ((size_t)32 * (small ? MTC : 4) * SP + (size_t)32 * (small ? MT : 4) * SP);
-    const dim3 grid((unsigned)(p.T * p.nchunk));
-#define DPF_W(M, N)                                                                                           \
-  {                                                                                                           \
-    if (set_lds(dcn_wgrad_kernel<M, N>, lds) != DPF_OK) return DPF_ERR_LAUNCH;                                \
-    hipLaunchKernelGGL((dcn_wgrad_kernel<M, N>), grid, dim3(256), lds, st, input, offset, grad_output, grad_weight, p); \
-  }
-    if (MT <= 2 && MTC <= 2) {
-      if (MT == 1 && MTC == 1) DPF_W(1, 1) else if (MT == 1) DPF_W(1, 2) else if (MTC == 1) DPF_W(2, 1) else DPF_W(2, 2)
-    } else {
-      DPF_W(4, 4)
-    }
-#undef DPF_W
-  }
-  if (det) hipLaunchKernelGGL(dcn_gi_finalize_kernel, dim3(dpf_ew_grid(in_elems)), dim3(256), 0, st, gi_shadow, grad_input, in_elems);
+  if (hipMemsetAsync(grad_weight, 0, sizeof(float) * (size_t)K * C * b.p.T, b.st) != hipSuccess) return DPF_ERR_LAUNCH;
+  // grad_input: packed LDS scatter, or left to the gather kernel.  grad_offset + grad_weight: lean -> region (beside the packed scatter
+  // only) -> gather.
+  rc = dcn_bwd_grad_input(b, grad_input_channels);
+  const bool dx_done = rc == DPF_OK;
+  if (dx_done) rc = dcn_bwd_offset_weight(b, dcn_is_model_config(kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw));
+  if (rc == DPF_ERR_UNSUPPORTED) rc = dcn_bwd_gather(b, dx_done);
+  if (rc != DPF_OK) return rc;
+  if (b.det) hipLaunchKernelGGL(dcn_gi_finalize_kernel, dim3(dpf_ew_grid(in_elems)), dim3(256), 0, b.st, b.gi_shadow, grad_input, in_elems);
   if (grad_bias) {
     // grad_bias[k] = sum_{b,p} go[b,k,p]  (cu:277) -- small row reduction
-    if (hipMemsetAsync(grad_bias, 0, sizeof(float) * K, st) != hipSuccess) return DPF_ERR_LAUNCH;
-    rc = dpf_channel_sum(grad_output, grad_bias, B, K, p.P, stream);
+    if (hipMemsetAsync(grad_bias, 0, sizeof(float) * K, b.st) != hipSuccess) return DPF_ERR_LAUNCH;
+    rc = dpf_channel_sum(grad_output, grad_bias, B, K, b.p.P, stream);
     if (rc != DPF_OK) return rc;
   }
   return dpf_check_launch();
 }
 
-#ifdef DPF_STAMPS
-int dpf_debug_stamps(unsigned long long* host_out) {
-  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 16 * 128 * 2) == hipSuccess ? 0 : -1;
+int dpf_deform_conv3d_backward(const float* input, const float* weight, const float* bias, const float* offset, const float* grad_output,
+                               float* grad_input, float* grad_offset, float* grad_weight, float* grad_bias, float* ws, int B, int C,
+                               int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd,
+                               int dh, int dw, int group, int deformable_group, int im2col_step, void* stream) {
+  return dpf_deform_conv3d_backward_ex(input, weight, bias, offset, grad_output, grad_input, grad_offset, grad_weight, grad_bias, ws, B, C, D, H,
+                                       W, K, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw, group, deformable_group, im2col_step, C, stream);
 }
-#endif
 
 }  // extern "C"

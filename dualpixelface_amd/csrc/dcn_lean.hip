@@ -24,7 +24,6 @@
 //     lane, one round trip) instead of 16 serial channel round trips in the one slow lane.
 #include "dcn_internal.h"
 #include "conv_internal.h"
-#include <cstdlib>
 
 namespace {
 
@@ -108,14 +107,6 @@ __device__ __forceinline__ void lean_stage(const LeanP& p, const float* __restri
     *reinterpret_cast<f32x4*>(dst + 48) = f32x4{v[0].w, v[1].w, v[2].w, v[3].w};
   }
 }
-
-#ifdef DPF_STAMPS
-__device__ unsigned long long g_lean_stamps[16 * 128 * 4];
-#define LEAN_STAMP4(step, slot) \
-  if (blockIdx.x == 3000 && lane == 0 && (step) < 128) g_lean_stamps[((wave_u + 8) * 128 + (step)) * 4 + (slot)] = __builtin_readcyclecounter();
-#else
-#define LEAN_STAMP4(step, slot)
-#endif
 
 // Per (voxel, tap) table of the sampler: where the 2 x 2 x 2 corner block sits in the staged region and the eight trilinear weights.
 struct LeanTab {
@@ -308,7 +299,6 @@ __global__ __launch_bounds__(256, 2) void dcn_lean_fwd1_kernel(const float* __re
     };
     // phase 1: k-steps of quads 0, 1 | corner reads of quads 0, 1 of the next tap
     __builtin_amdgcn_sched_barrier(0);
-    if (chunk == 1) { LEAN_STAMP4(t, 0) }
     if (!last) { LEAN_LOAD8(cr[0], 0) LEAN_LOAD8(cr[1], 1) }
     mfmas(0, 4);
 #pragma unroll
@@ -316,10 +306,8 @@ __global__ __launch_bounds__(256, 2) void dcn_lean_fwd1_kernel(const float* __re
     // (hard fences between the phases: vector-ALU work scheduled in between MFMAs costs a pipe switch each time -- 4 v_pk_fma_f32 behind
     // an MFMA: +34 clocks, tools/lean_probe2.hip)
     __builtin_amdgcn_sched_barrier(0);
-    if (chunk == 1) { LEAN_STAMP4(t, 1) }
     if (!last) accum2(tab, cr[0], cr[1], nxt, nxt + 4, true);
     __builtin_amdgcn_sched_barrier(0);
-    if (chunk == 1) { LEAN_STAMP4(t, 2) }
     // phase 2: remaining k-steps | corner reads of the remaining quads
     if (!last) {
       LEAN_LOAD8(cr[0], 2)
@@ -329,7 +317,6 @@ __global__ __launch_bounds__(256, 2) void dcn_lean_fwd1_kernel(const float* __re
 #pragma unroll
     for (int i = 0; i < 4 * (KSTEPS - 4); ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 1); __builtin_amdgcn_sched_group_barrier(0x100, 1, 1); }
     __builtin_amdgcn_sched_barrier(0);
-    if (chunk == 1) { LEAN_STAMP4(t, 3) }
     if (!last) {
       accum2(tab, cr[0], cr[1], nxt + 8, nxt + 12, NQ > 3);
       slow_fix(tab, nxt, c0);
@@ -1084,51 +1071,26 @@ __global__ void lean_repack_gcol_h_kernel(const float* __restrict__ w, unsigned 
   }
 }
 
-template <typename F>
-int lean_set_lds(F f, size_t lds) {
-  if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return DPF_ERR_LAUNCH;
-  return DPF_OK;
-}
-
-template <class G>
-int lean_launch_fwd1(const float* x, const float* offset, const float* weight, const float* bias, float* out, float* ws, LeanP p, hipStream_t st) {
+// Forward on one geometry.  SIX: six bf16 partial products (weights repacked as bf16 components), else the fp32 matrix instruction.
+template <class G, bool SIX>
+int lean_launch_fwd(const float* x, const float* offset, const float* weight, const float* bias, float* out, float* ws, LeanP p, hipStream_t st) {
   p.tilesY = dpf_div_up(p.H, G::TY);
   p.tilesX = dpf_div_up(p.W, G::TX);
   const long long blocks = (long long)p.B * p.tilesY * p.tilesX;
   if (blocks >= 0x7fffffffLL) return DPF_ERR_UNSUPPORTED;
   const int MT = p.KT / 32;
   constexpr int LDS = G::NQ * G::PLANE;
-  hipLaunchKernelGGL((lean_repack_fwd1_kernel<G::CH>), dim3(dpf_ew_grid(27LL * p.nchunk * MT * 512)), dim3(256), 0, st, weight, ws, p.K, p.C, MT, p.nchunk);
-  const dim3 grid((unsigned)blocks), block(256);
-  if (MT == 1) {
-    if (lean_set_lds(dcn_lean_fwd1_kernel<G, 1>, LDS) != DPF_OK) return DPF_ERR_LAUNCH;
-    hipLaunchKernelGGL((dcn_lean_fwd1_kernel<G, 1>), grid, block, LDS, st, x, offset, ws, bias, out, p);
+  const dim3 grid_w(dpf_ew_grid(27LL * p.nchunk * MT * 512)), grid((unsigned)blocks), block(256);
+  int rc;
+  if constexpr (SIX) {
+    unsigned short* wl = reinterpret_cast<unsigned short*>(ws);
+    hipLaunchKernelGGL((lean_repack_fwd6_kernel<G::CH>), grid_w, block, 0, st, weight, wl, p.K, p.C, MT, p.nchunk);
+    rc = dcn_launch(MT == 1 ? dcn_lean_fwd6_kernel<G, 1> : dcn_lean_fwd6_kernel<G, 2>, grid, block, LDS, st, x, offset, wl, bias, out, p);
   } else {
-    if (lean_set_lds(dcn_lean_fwd1_kernel<G, 2>, LDS) != DPF_OK) return DPF_ERR_LAUNCH;
-    hipLaunchKernelGGL((dcn_lean_fwd1_kernel<G, 2>), grid, block, LDS, st, x, offset, ws, bias, out, p);
+    hipLaunchKernelGGL((lean_repack_fwd1_kernel<G::CH>), grid_w, block, 0, st, weight, ws, p.K, p.C, MT, p.nchunk);
+    rc = dcn_launch(MT == 1 ? dcn_lean_fwd1_kernel<G, 1> : dcn_lean_fwd1_kernel<G, 2>, grid, block, LDS, st, x, offset, ws, bias, out, p);
   }
-  return dpf_check_launch();
-}
-
-template <class G>
-int lean_launch_fwd6(const float* x, const float* offset, const float* weight, const float* bias, float* out, float* ws, LeanP p, hipStream_t st) {
-  p.tilesY = dpf_div_up(p.H, G::TY);
-  p.tilesX = dpf_div_up(p.W, G::TX);
-  const long long blocks = (long long)p.B * p.tilesY * p.tilesX;
-  if (blocks >= 0x7fffffffLL) return DPF_ERR_UNSUPPORTED;
-  const int MT = p.KT / 32;
-  constexpr int LDS = G::NQ * G::PLANE;
-  unsigned short* wl = reinterpret_cast<unsigned short*>(ws);
-  hipLaunchKernelGGL((lean_repack_fwd6_kernel<G::CH>), dim3(dpf_ew_grid(27LL * p.nchunk * MT * 512)), dim3(256), 0, st, weight, wl, p.K, p.C, MT, p.nchunk);
-  const dim3 grid((unsigned)blocks), block(256);
-  if (MT == 1) {
-    if (lean_set_lds(dcn_lean_fwd6_kernel<G, 1>, LDS) != DPF_OK) return DPF_ERR_LAUNCH;
-    hipLaunchKernelGGL((dcn_lean_fwd6_kernel<G, 1>), grid, block, LDS, st, x, offset, wl, bias, out, p);
-  } else {
-    if (lean_set_lds(dcn_lean_fwd6_kernel<G, 2>, LDS) != DPF_OK) return DPF_ERR_LAUNCH;
-    hipLaunchKernelGGL((dcn_lean_fwd6_kernel<G, 2>), grid, block, LDS, st, x, offset, wl, bias, out, p);
-  }
-  return dpf_check_launch();
+  return rc != DPF_OK ? rc : dpf_check_launch();
 }
 
 //                  CH TY  TX RYH RXL RXR      voxels  region cells    LDS
@@ -1146,32 +1108,37 @@ int lean_launch_bwd_offset(const float* x, const float* offset, const float* wei
   p.tilesX = dpf_div_up(p.W, G::TX);
   const long long blocks = (long long)p.B * p.tilesY * p.tilesX;
   if (blocks >= 0x7fffffffLL) return DPF_ERR_UNSUPPORTED;
-  static const int gh_env = getenv("DPF_DCN_GCOL16") ? atoi(getenv("DPF_DCN_GCOL16")) : 1;
-  if (gh_env && dpf_conv_f32_x9() == 2) {
+  const dim3 grid((unsigned)blocks), block(512);
+  int rc;
+  if (dcn_env().gcol16 && dpf_conv_f32_x9() == 2) {
     hipLaunchKernelGGL(lean_repack_gcol_h_kernel, dim3(16), dim3(1024), 0, st, weight, reinterpret_cast<unsigned short*>(ws), p.K, p.C, G::CH, p.nchunk);
-    if (lean_set_lds(dcn_lean_bwd_offset_kernel<G, true>, BwdLds<G>::LDS + 64) != DPF_OK) return DPF_ERR_LAUNCH;
-    hipLaunchKernelGGL((dcn_lean_bwd_offset_kernel<G, true>), dim3((unsigned)blocks), dim3(512), BwdLds<G>::LDS + 64, st, x, offset, ws, go, doff, dwtmp, p, det);
-    return dpf_check_launch();
+    rc = dcn_launch(dcn_lean_bwd_offset_kernel<G, true>, grid, block, BwdLds<G>::LDS + 64, st, x, offset, ws, go, doff, dwtmp, p, det);
+  } else {
+    hipLaunchKernelGGL(lean_repack_gcol_kernel, dim3(dpf_ew_grid(27LL * p.nchunk * 1024)), dim3(256), 0, st, weight, ws, p.K, p.C, G::CH, p.nchunk);
+    rc = dcn_launch(dcn_lean_bwd_offset_kernel<G, false>, grid, block, BwdLds<G>::LDS, st, x, offset, ws, go, doff, dwtmp, p, det);
   }
-  hipLaunchKernelGGL(lean_repack_gcol_kernel, dim3(dpf_ew_grid(27LL * p.nchunk * 1024)), dim3(256), 0, st, weight, ws, p.K, p.C, G::CH, p.nchunk);
-  if (lean_set_lds(dcn_lean_bwd_offset_kernel<G, false>, BwdLds<G>::LDS) != DPF_OK) return DPF_ERR_LAUNCH;
-  hipLaunchKernelGGL((dcn_lean_bwd_offset_kernel<G, false>), dim3((unsigned)blocks), dim3(512), BwdLds<G>::LDS, st, x, offset, ws, go, doff, dwtmp, p, det);
-  return dpf_check_launch();
+  return rc != DPF_OK ? rc : dpf_check_launch();
+}
+
+// What the forward and the backward both need of a shape (depth <= 4, 16-byte aligned rows, K <= 64, 32-bit byte offsets inside a channel),
+// and the parameters they launch with.
+bool lean_params(LeanP& p, const float* x, int B, int C, int D, int H, int W, int K) {
+  if (D > 4 || D < 1 || (W & 3) || K > 64 || (reinterpret_cast<uintptr_t>(x) & 15)) return false;
+  if ((long long)D * H * W >= 0x7fffffffLL / 4) return false;
+  const int CH = dcn_chunk(C);
+  p = LeanP{};
+  p.B = B; p.C = C; p.K = K; p.D = D; p.H = H; p.W = W;
+  p.Cpad = (C + CH - 1) / CH * CH;
+  p.nchunk = p.Cpad / CH;
+  p.KT = 32 * ((K + 31) / 32);
+  p.P = (long long)D * H * W;
+  return true;
 }
 
 }  // namespace
 
-#ifdef DPF_STAMPS
-extern "C" int dpf_debug_lean_stamps(unsigned long long* host_out) {
-  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_lean_stamps), sizeof(unsigned long long) * 16 * 128 * 4) == hipSuccess ? 0 : -1;
-}
-#endif
-
-// chunk width: 12 where it pads the channel count less than 16 does (35 -> 36 instead of 48)
-int dcn_lean_chunk(int C) { return ((C + 11) / 12 * 12 < (C + 15) / 16 * 16) ? 12 : 16; }
-
 long long dcn_lean_workspace_floats(int C, int K) {
-  const int CH = dcn_lean_chunk(C);
+  const int CH = dcn_chunk(C);
   const long long nchunk = (C + CH - 1) / CH;
   const long long fwd = 27LL * nchunk * ((K + 31) / 32) * 768;     // lean_repack_fwd6_kernel (3 x 512 bf16; lean_repack_fwd1_kernel: 512 floats)
   const long long bwd = 27LL * nchunk * 1024 + 16;                 // lean_repack_gcol_kernel / lean_repack_gcol_h_kernel (+ its exponent); independent of K
@@ -1180,43 +1147,27 @@ long long dcn_lean_workspace_floats(int C, int K) {
 
 int dcn_lean_forward(const float* x, const float* offset, const float* weight, const float* bias, float* out, float* ws, int B, int C, int D, int H,
                      int W, int K, hipStream_t st) {
-  static const int lean_env = getenv("DPF_DCN_LEAN") ? atoi(getenv("DPF_DCN_LEAN")) : 1;
-  if (!lean_env || D > 4 || D < 1 || (W & 3) || K > 64 || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(out) & 15))
-    return DPF_ERR_UNSUPPORTED;
-  if ((long long)D * H * W >= 0x7fffffffLL / 4) return DPF_ERR_UNSUPPORTED;
-  const int CH = dcn_lean_chunk(C);
-  LeanP p{};
-  p.B = B; p.C = C; p.K = K; p.D = D; p.H = H; p.W = W;
-  p.Cpad = (C + CH - 1) / CH * CH;
-  p.nchunk = p.Cpad / CH;
-  p.KT = 32 * ((K + 31) / 32);
-  p.P = (long long)D * H * W;
+  const DcnEnv& env = dcn_env();
+  LeanP p;
+  if (!env.lean || (reinterpret_cast<uintptr_t>(out) & 15) || !lean_params(p, x, B, C, D, H, W, K)) return DPF_ERR_UNSUPPORTED;
+  const bool ch16 = dcn_chunk(C) == 16;
   // fp32 products: six bf16 partial products on the bf16 matrix pipe (default), or v_mfma_f32_32x32x2_f32 (dpf_set_f32_matrix_path(0), DPF_DCN_FWD6=0)
-  static const int fwd6_env = getenv("DPF_DCN_FWD6") ? atoi(getenv("DPF_DCN_FWD6")) : 1;
-  if (fwd6_env && dpf_conv_f32_x9()) {
-    if (CH == 16) return lean_launch_fwd6<G16c>(x, offset, weight, bias, out, ws, p, st);
-    return lean_launch_fwd6<G12d>(x, offset, weight, bias, out, ws, p, st);
+  if (env.fwd6 && dpf_conv_f32_x9()) {
+    if (ch16) return lean_launch_fwd<G16c, true>(x, offset, weight, bias, out, ws, p, st);
+    return lean_launch_fwd<G12d, true>(x, offset, weight, bias, out, ws, p, st);
   }
-  if (CH == 16) return lean_launch_fwd1<G16c>(x, offset, weight, bias, out, ws, p, st);
-  static const int wide12 = getenv("DPF_DCN_LEAN_WIDE12") ? atoi(getenv("DPF_DCN_LEAN_WIDE12")) : 0;   // 1: wider x halo, one workgroup per CU (3.7 vs 2.6 ms)
-  if (wide12) return lean_launch_fwd1<G12c>(x, offset, weight, bias, out, ws, p, st);
-  return lean_launch_fwd1<G12d>(x, offset, weight, bias, out, ws, p, st);
+  if (ch16) return lean_launch_fwd<G16c, false>(x, offset, weight, bias, out, ws, p, st);
+  if (env.lean_wide12) return lean_launch_fwd<G12c, false>(x, offset, weight, bias, out, ws, p, st);
+  return lean_launch_fwd<G12d, false>(x, offset, weight, bias, out, ws, p, st);
 }
 
-// grad_offset (fully written) + grad_weight partials into dwtmp[LEAN_NREP = 8][27][nchunk][64][16] (zero-initialised by the caller, folded by
-// dcn3d.hip's dcn_wgrad_fold_kernel with chunk width dcn_lean_chunk(C)).  ws: >= 27 * nchunk * 1024 floats.
+// grad_offset (fully written) + grad_weight partials into dwtmp[DCN_WG_NREP = 8][27][nchunk][64][16] (zero-initialised by the caller, folded by
+// dcn3d.hip's dcn_wgrad_fold_kernel with chunk width dcn_chunk(C)).  ws: >= 27 * nchunk * 1024 floats.
 int dcn_lean_bwd_offset(const float* x, const float* offset, const float* weight, const float* go, float* doff, float* dwtmp, float* ws, int B, int C,
                         int D, int H, int W, int K, hipStream_t st, int det) {
-  static const int lean_env = getenv("DPF_DCN_LEAN") ? atoi(getenv("DPF_DCN_LEAN")) : 1;
-  if (!lean_env || (lean_env & 4) || D > 4 || D < 1 || (W & 3) || K > 64 || (reinterpret_cast<uintptr_t>(x) & 15)) return DPF_ERR_UNSUPPORTED;
-  if ((long long)D * H * W >= 0x7fffffffLL / 4) return DPF_ERR_UNSUPPORTED;
-  const int CH = dcn_lean_chunk(C);
-  LeanP p{};
-  p.B = B; p.C = C; p.K = K; p.D = D; p.H = H; p.W = W;
-  p.Cpad = (C + CH - 1) / CH * CH;
-  p.nchunk = p.Cpad / CH;
-  p.KT = 32 * ((K + 31) / 32);
-  p.P = (long long)D * H * W;
-  if (CH == 16) return lean_launch_bwd_offset<B16>(x, offset, weight, go, doff, dwtmp, ws, p, st, det);
+  const int lean = dcn_env().lean;
+  LeanP p;
+  if (!lean || (lean & 4) || !lean_params(p, x, B, C, D, H, W, K)) return DPF_ERR_UNSUPPORTED;
+  if (dcn_chunk(C) == 16) return lean_launch_bwd_offset<B16>(x, offset, weight, go, doff, dwtmp, ws, p, st, det);
   return lean_launch_bwd_offset<B12>(x, offset, weight, go, doff, dwtmp, ws, p, st, det);
 }

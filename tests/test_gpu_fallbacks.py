@@ -12,6 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SETS = [
     # lean-sampler deformable kernels off: the role-split region kernels take the model's shapes too
     ({'DPF_DCN_LEAN': '0'}, 'test_deform_conv and not full_size'),
+    # lean forward, but grad_offset + grad_weight on the role-split region kernel (which re-packs the weights at the head of the workspace once the lean kernel has declined)
+    ({'DPF_DCN_LEAN': '4'}, 'test_deform_conv and not full_size'),
     # first-generation deformable kernels (global-memory gathers: what geometries without a fitting LDS image fall back to)
     ({'DPF_DCN_V1': '1'}, 'test_deform_conv and not full_size'),
     # the deformable conv backward's gcol products (grad_input and grad_offset kernels) on the fp32 matrix instruction instead of the f16 components
