@@ -1,12 +1,12 @@
 // Dual-pixel cost-volume construction.
 //
-//   dpf_shift_triple_{forward,backward}: the three row-shifted copies of a feature map (nearest / bilinear /
-//     Fourier-phase) that subpixel_shift.forward produces (reference: src/module/asm/asm.py:87-127), expressed
+//   dpf_shift_triple_{forward,backward}, dpf_shift_copies_*: the M <= 3 row-shifted copies of a feature map (the enabled
+//     ones of nearest / bilinear / Fourier-phase) that subpixel_shift.forward produces (src/module/asm/asm.py:87-127), expressed
 //     as a table-driven separable 2x2-tap sampler: out[b,c,m,y,x] = sum_{a,e} wy[m][a][y] * wx[m][e][x] *
 //     fea[b,c, iy[m][a][y], ix[m][e][x]].  The host builds the tables with the reference's own float32 op
 //     order (grid normalisation quirks Q2, un-keyed grid cache Q1); an integer phase shift is a row roll.
-//   dpf_cv_select_{forward,backward}: MaskingAttention's tail (asm.py:162-171): softmax over the three copies of
-//     sigmoid(mask), weighted mean, written straight into every cost-volume level that shares this shift
+//   dpf_cv_select_{forward,backward}, dpf_cv_select_m_*: MaskingAttention's tail (asm.py:162-171): softmax over the M copies of
+//     the activated mask, weighted mean (feature_fetch: the variance), written straight into every cost-volume level that shares this shift
 //     (CostVolume.build_concat_volume, src/model/stereodpnet/modules.py:181-197).
 //   dpf_psm_volume_forward: PSMNet's integer-shift concat / group-wise-correlation volume
 //     (src/model/psmnet/modules.py:215-262, int() truncation Q14).
@@ -15,20 +15,21 @@
 
 namespace {
 
-// tables: iy [3][2][h] int32 (-1 = no tap), wy [3][2][h] float, ix [3][2][w], wx [3][2][w]
-// grid (row chunks, BC * 3 planes): the plane index (b, c, mode) comes from blockIdx.y, a thread owns 4 consecutive columns of a row:
+// tables: iy [M][2][h] int32 (-1 = no tap), wy [M][2][h] float, ix [M][2][w], wx [M][2][w]; M = number of enabled shift modes
+// grid (row chunks, BC * M planes): the plane index (b, c, mode) comes from blockIdx.y, a thread owns 4 consecutive columns of a row:
 // one 32-bit division per 4 outputs, the row taps are uniform per row, the column taps are read as vectors, 16-byte stores.
 constexpr int ST_ROWS = 8;
+template <int M>
 __global__ __launch_bounds__(256) void shift_triple_fwd_kernel(const float* __restrict__ fea, float* __restrict__ out, const int* __restrict__ iy,
                                                                const float* __restrict__ wy, const int* __restrict__ ix,
                                                                const float* __restrict__ wx, int h, int w) {
-  const int m = blockIdx.y % 3;
-  const long long bc = blockIdx.y / 3;
+  const int m = blockIdx.y % M;
+  const long long bc = blockIdx.y / M;
   const int y0 = blockIdx.x * ST_ROWS;
   const int nrow = min(ST_ROWS, h - y0);
   const int w4 = (w + 3) >> 2;
   const float* src = fea + bc * h * w;
-  float* dst = out + ((bc * 3 + m) * h + y0) * (long long)w;
+  float* dst = out + ((bc * M + m) * h + y0) * (long long)w;
   const int* ixm = ix + m * 2 * w;
   const float* wxm = wx + m * 2 * w;
   const bool vec = (w & 3) == 0;
@@ -105,10 +106,11 @@ __global__ void shift_triple_bwd_kernel(const float* __restrict__ g, float* __re
   }
 }
 
-// deterministic adjoint (gather form): iyi / ixi are the INVERSE tables [3][2][2][n] (iyi[m][a][s][yy] = the s-th output row y whose
+// deterministic adjoint (gather form): iyi / ixi are the INVERSE tables [M][2][2][n] (iyi[m][a][s][yy] = the s-th output row y whose
 // tap (m, a) reads source row yy, -1 if none; the tap maps are monotone and at most two outputs share a source -- the host checks
-// it), wy / wx stay indexed by the output coordinate.  One thread per dfea element, <= 48 terms in a fixed order, no atomics, no
+// it), wy / wx stay indexed by the output coordinate.  One thread per dfea element, <= 16 M terms in a fixed order, no atomics, no
 // pre-zeroing.
+template <int M>
 __global__ __launch_bounds__(256) void shift_triple_bwd_gather_kernel(const float* __restrict__ g, float* __restrict__ dfea,
                                                                       const int* __restrict__ iyi, const float* __restrict__ wy,
                                                                       const int* __restrict__ ixi, const float* __restrict__ wx, int h, int w) {
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(256) void shift_triple_bwd_gather_kernel(const floa
   const int nrow = min(ST_ROWS, h - y0);
   const int w4 = (w + 3) >> 2;
   const long long hw = (long long)h * w;
-  const float* gp = g + bc * 3 * hw;
+  const float* gp = g + bc * M * hw;
   float* dst = dfea + bc * hw + (long long)y0 * w;
   const bool vec = (w & 3) == 0;
   for (int idx = threadIdx.x; idx < nrow * w4; idx += 256) {
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(256) void shift_triple_bwd_gather_kernel(const floa
     const int yy = y0 + r;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int m = 0; m < 3; ++m) {
+    for (int m = 0; m < M; ++m) {
       // inverse column taps of these 4 source columns and their weights (zero-weight taps are dropped here, once per mode)
       int cx[2][2][4];
       float cw[2][2][4];
@@ -249,7 +251,28 @@ __global__ __launch_bounds__(256) void phase_circ_kernel(const float* __restrict
   }
 }
 
-// x3, s: [B,C,3,h,w]; vol: [B, CV, L, h, w]; writes channels [choff, choff+C) of every level in `levels` (bit mask)
+// x, s: [B,C,M,h,w] (the shifted copies and the already activated mask); vol: [B, CV, L, h, w]; writes channels [choff, choff+C) of
+// every level in `levels` (bit mask).  p = softmax_M(s), z_m = x_m p_m; FETCH = false: mean_m z_m, FETCH = true: the variance
+// mean_m z_m^2 - (mean_m z_m)^2 (asm.py:165-169).  <3, false> is the shipped configuration.
+template <int M>
+__device__ __forceinline__ void cv_softmax(const float* __restrict__ s, long long base, long long hw, float (&p)[M]) {
+  float sv[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) sv[m] = s[base + m * hw];
+  float mx = sv[M - 1];
+#pragma unroll
+  for (int m = M - 2; m >= 0; --m) mx = fmaxf(sv[m], mx);
+  float sum = 0.f;
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    p[m] = expf(sv[m] - mx);
+    sum = m == 0 ? p[0] : sum + p[m];
+  }
+#pragma unroll
+  for (int m = 0; m < M; ++m) p[m] = p[m] / sum;
+}
+
+template <int M, bool FETCH>
 __global__ void cv_select_fwd_kernel(const float* __restrict__ x3, const float* __restrict__ s, float* __restrict__ vol, int B, int C,
                                      int h, int w, int CV, int L, int choff, unsigned levels) {
   const long long hw = (long long)h * w;
@@ -259,18 +282,27 @@ __global__ void cv_select_fwd_kernel(const float* __restrict__ x3, const float* 
     const long long bc = i / hw;
     const int c = (int)(bc % C);
     const int b = (int)(bc / C);
-    const long long base = bc * 3 * hw + pix;
-    const float s0 = s[base], s1 = s[base + hw], s2 = s[base + 2 * hw];
-    const float mx = fmaxf(s0, fmaxf(s1, s2));
-    const float e0 = expf(s0 - mx), e1 = expf(s1 - mx), e2 = expf(s2 - mx);
-    const float sum = e0 + e1 + e2;
-    const float v = (x3[base] * (e0 / sum) + x3[base + hw] * (e1 / sum) + x3[base + 2 * hw] * (e2 / sum)) / 3.0f;
+    const long long base = bc * M * hw + pix;
+    float p[M];
+    cv_softmax<M>(s, base, hw, p);
+    float acc = x3[base] * p[0], sq = 0.f;
+    if (FETCH) sq = acc * acc;
+#pragma unroll
+    for (int m = 1; m < M; ++m) {
+      const float z = x3[base + m * hw] * p[m];
+      acc += z;
+      if (FETCH) sq += z * z;
+    }
+    float v = acc / (float)M;
+    if (FETCH) v = M == 1 ? 0.f : sq / (float)M - v * v;     // (one copy: z^2 - z^2, written as the exact zero it is)
     float* dst = vol + (((long long)b * CV + choff + c) * L) * hw + pix;
     for (int l = 0; l < L; ++l)
       if ((levels >> l) & 1u) dst[(long long)l * hw] = v;
   }
 }
 
+// FETCH: dz_m = g 2 (z_m - mean z) / M; then as for the mean: dx_m = dz_m p_m, ds through the softmax Jacobian of dp_m = dz_m x_m
+template <int M, bool FETCH>
 __global__ void cv_select_bwd_kernel(const float* __restrict__ x3, const float* __restrict__ s, const float* __restrict__ dvol,
                                      float* __restrict__ dx3, float* __restrict__ ds, int B, int C, int h, int w, int CV, int L,
                                      int choff, unsigned levels) {
@@ -281,26 +313,40 @@ __global__ void cv_select_bwd_kernel(const float* __restrict__ x3, const float* 
     const long long bc = i / hw;
     const int c = (int)(bc % C);
     const int b = (int)(bc / C);
-    const long long base = bc * 3 * hw + pix;
+    const long long base = bc * M * hw + pix;
     const float* src = dvol + (((long long)b * CV + choff + c) * L) * hw + pix;
     float g = 0.f;
     for (int l = 0; l < L; ++l)
       if ((levels >> l) & 1u) g += src[(long long)l * hw];
-    g = g / 3.0f;
-    const float s0 = s[base], s1 = s[base + hw], s2 = s[base + 2 * hw];
-    const float mx = fmaxf(s0, fmaxf(s1, s2));
-    const float e0 = expf(s0 - mx), e1 = expf(s1 - mx), e2 = expf(s2 - mx);
-    const float sum = e0 + e1 + e2;
-    const float p0 = e0 / sum, p1 = e1 / sum, p2 = e2 / sum;
-    const float a0 = x3[base], a1 = x3[base + hw], a2 = x3[base + 2 * hw];
-    dx3[base] = p0 * g;
-    dx3[base + hw] = p1 * g;
-    dx3[base + 2 * hw] = p2 * g;
-    const float dp0 = a0 * g, dp1 = a1 * g, dp2 = a2 * g;
-    const float dot = p0 * dp0 + p1 * dp1 + p2 * dp2;
-    ds[base] = p0 * (dp0 - dot);
-    ds[base + hw] = p1 * (dp1 - dot);
-    ds[base + 2 * hw] = p2 * (dp2 - dot);
+    g = g / (float)M;
+    float p[M], a[M], dz[M], dp[M];
+    cv_softmax<M>(s, base, hw, p);
+#pragma unroll
+    for (int m = 0; m < M; ++m) a[m] = x3[base + m * hw];
+    if (FETCH) {
+      float z[M], mean = 0.f;
+#pragma unroll
+      for (int m = 0; m < M; ++m) {
+        z[m] = a[m] * p[m];
+        mean += z[m];
+      }
+      mean = mean / (float)M;
+#pragma unroll
+      for (int m = 0; m < M; ++m) dz[m] = M == 1 ? 0.f : g * (2.f * (z[m] - mean));
+    } else {
+#pragma unroll
+      for (int m = 0; m < M; ++m) dz[m] = g;
+    }
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      dx3[base + m * hw] = p[m] * dz[m];
+      dp[m] = a[m] * dz[m];
+    }
+    float dot = p[0] * dp[0];
+#pragma unroll
+    for (int m = 1; m < M; ++m) dot += p[m] * dp[m];
+#pragma unroll
+    for (int m = 0; m < M; ++m) ds[base + m * hw] = p[m] * (dp[m] - dot);
   }
 }
 
@@ -480,18 +526,27 @@ __global__ __launch_bounds__(256) void diff_volume_bwd_kernel(const float* __res
 
 extern "C" {
 
-int dpf_shift_triple_forward(const float* fea, float* out, const int* iy, const float* wy, const int* ix, const float* wx, int B, int C,
-                             int h, int w, void* stream) {
+// M row-shifted copies, out [B, C, M, h, w]; tables [M][2][h|w] for the enabled modes only (M = 1, 2 or 3)
+int dpf_shift_copies_forward(const float* fea, float* out, const int* iy, const float* wy, const int* ix, const float* wx, int B, int C,
+                             int M, int h, int w, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
-  if (!fea || !out || !iy || !wy || !ix || !wx || B <= 0 || C <= 0 || h <= 0 || w <= 0) return DPF_ERR_INVALID_ARG;
+  if (!fea || !out || !iy || !wy || !ix || !wx || B <= 0 || C <= 0 || M < 1 || M > 3 || h <= 0 || w <= 0) return DPF_ERR_INVALID_ARG;
   const long long BC = (long long)B * C, hw = (long long)h * w;
   // the plane index rides in gridDim.y (<= 65535): larger batch x channel counts are launched in slices
-  for (long long bc0 = 0; bc0 < BC; bc0 += 21845) {
-    const long long n = BC - bc0 < 21845 ? BC - bc0 : 21845;
-    hipLaunchKernelGGL(shift_triple_fwd_kernel, dim3(dpf_div_up(h, ST_ROWS), (unsigned)(n * 3)), dim3(256), 0, (hipStream_t)stream,
-                       fea + bc0 * hw, out + bc0 * 3 * hw, iy, wy, ix, wx, h, w);
+  const long long slice = 65535 / M;
+  for (long long bc0 = 0; bc0 < BC; bc0 += slice) {
+    const long long n = BC - bc0 < slice ? BC - bc0 : slice;
+#define DPF_CALL(MM) hipLaunchKernelGGL(shift_triple_fwd_kernel<MM>, dim3(dpf_div_up(h, ST_ROWS), (unsigned)(n * MM)), dim3(256), 0, \
+                                        (hipStream_t)stream, fea + bc0 * hw, out + bc0 * MM * hw, iy, wy, ix, wx, h, w)
+    if (M == 3) DPF_CALL(3); else if (M == 2) DPF_CALL(2); else DPF_CALL(1);
+#undef DPF_CALL
   }
   return dpf_check_launch();
+}
+
+int dpf_shift_triple_forward(const float* fea, float* out, const int* iy, const float* wy, const int* ix, const float* wx, int B, int C,
+                             int h, int w, void* stream) {
+  return dpf_shift_copies_forward(fea, out, iy, wy, ix, wx, B, C, 3, h, w, stream);
 }
 
 int dpf_shift_triple_backward(const float* g, float* dfea, const int* iy, const float* wy, const int* ix, const float* wx, int B, int C,
@@ -505,17 +560,24 @@ int dpf_shift_triple_backward(const float* g, float* dfea, const int* iy, const 
   return dpf_check_launch();
 }
 
-int dpf_shift_triple_backward_gather(const float* g, float* dfea, const int* iy_inv, const float* wy, const int* ix_inv, const float* wx,
-                                     int B, int C, int h, int w, void* stream) {
+int dpf_shift_copies_backward_gather(const float* g, float* dfea, const int* iy_inv, const float* wy, const int* ix_inv, const float* wx,
+                                     int B, int C, int M, int h, int w, void* stream) {
   dpf_clear_error();
-  if (!g || !dfea || !iy_inv || !wy || !ix_inv || !wx || B <= 0 || C <= 0 || h <= 0 || w <= 0) return DPF_ERR_INVALID_ARG;
+  if (!g || !dfea || !iy_inv || !wy || !ix_inv || !wx || B <= 0 || C <= 0 || M < 1 || M > 3 || h <= 0 || w <= 0) return DPF_ERR_INVALID_ARG;
   const long long BC = (long long)B * C, hw = (long long)h * w;
   for (long long bc0 = 0; bc0 < BC; bc0 += 65535) {      // gridDim.y slices
     const long long n = BC - bc0 < 65535 ? BC - bc0 : 65535;
-    hipLaunchKernelGGL(shift_triple_bwd_gather_kernel, dim3(dpf_div_up(h, ST_ROWS), (unsigned)n), dim3(256), 0, (hipStream_t)stream,
-                       g + bc0 * 3 * hw, dfea + bc0 * hw, iy_inv, wy, ix_inv, wx, h, w);
+#define DPF_CALL(MM) hipLaunchKernelGGL(shift_triple_bwd_gather_kernel<MM>, dim3(dpf_div_up(h, ST_ROWS), (unsigned)n), dim3(256), 0, \
+                                        (hipStream_t)stream, g + bc0 * MM * hw, dfea + bc0 * hw, iy_inv, wy, ix_inv, wx, h, w)
+    if (M == 3) DPF_CALL(3); else if (M == 2) DPF_CALL(2); else DPF_CALL(1);
+#undef DPF_CALL
   }
   return dpf_check_launch();
+}
+
+int dpf_shift_triple_backward_gather(const float* g, float* dfea, const int* iy_inv, const float* wy, const int* ix_inv, const float* wx,
+                                     int B, int C, int h, int w, void* stream) {
+  return dpf_shift_copies_backward_gather(g, dfea, iy_inv, wy, ix_inv, wx, B, C, 3, h, w, stream);
 }
 
 int dpf_phase_shift(const float* src, long long src_plane_stride, float* dst, long long dst_plane_stride, const float* mr, const float* hm,
@@ -546,12 +608,44 @@ int dpf_phase_shift(const float* src, long long src_plane_stride, float* dst, lo
   return dpf_check_launch();
 }
 
+// M = 1, 2 or 3 copies; fetch = 0: the weighted mean, 1: the variance over the copies (feature_fetch)
+#define DPF_CV_DISPATCH(KERNEL, ...)                                                                                                      \
+  do {                                                                                                                                    \
+    const dim3 grid_(dpf_ew_grid((long long)B * C * h * w));                                                                              \
+    if (M == 3 && !fetch) hipLaunchKernelGGL((KERNEL<3, false>), grid_, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);                  \
+    else if (M == 3) hipLaunchKernelGGL((KERNEL<3, true>), grid_, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);                        \
+    else if (M == 2 && !fetch) hipLaunchKernelGGL((KERNEL<2, false>), grid_, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);             \
+    else if (M == 2) hipLaunchKernelGGL((KERNEL<2, true>), grid_, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);                        \
+    else if (!fetch) hipLaunchKernelGGL((KERNEL<1, false>), grid_, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);                       \
+    else hipLaunchKernelGGL((KERNEL<1, true>), grid_, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);                                    \
+  } while (0)
+
+int dpf_cv_select_m_forward(const float* x, const float* s, float* vol, int B, int C, int M, int h, int w, int CV, int L, int choff,
+                            unsigned levels, int fetch, void* stream) {
+  dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
+  if (!x || !s || !vol || B <= 0 || C <= 0 || M < 1 || M > 3 || h <= 0 || w <= 0 || L <= 0 || L > 32 || choff < 0 || choff + C > CV)
+    return DPF_ERR_INVALID_ARG;
+  DPF_CV_DISPATCH(cv_select_fwd_kernel, x, s, vol, B, C, h, w, CV, L, choff, levels);
+  return dpf_check_launch();
+}
+
+int dpf_cv_select_m_backward(const float* x, const float* s, const float* dvol, float* dx, float* ds, int B, int C, int M, int h, int w,
+                             int CV, int L, int choff, unsigned levels, int fetch, void* stream) {
+  dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
+  if (!x || !s || !dvol || !dx || !ds || B <= 0 || C <= 0 || M < 1 || M > 3 || h <= 0 || w <= 0 || L <= 0 || L > 32 || choff < 0 ||
+      choff + C > CV)
+    return DPF_ERR_INVALID_ARG;
+  DPF_CV_DISPATCH(cv_select_bwd_kernel, x, s, dvol, dx, ds, B, C, h, w, CV, L, choff, levels);
+  return dpf_check_launch();
+}
+#undef DPF_CV_DISPATCH
+
 int dpf_cv_select_forward(const float* x3, const float* s, float* vol, int B, int C, int h, int w, int CV, int L, int choff,
                           unsigned levels, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   if (!x3 || !s || !vol || B <= 0 || C <= 0 || L <= 0 || L > 32 || choff < 0 || choff + C > CV) return DPF_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(cv_select_fwd_kernel, dim3(dpf_ew_grid((long long)B * C * h * w)), dim3(256), 0, (hipStream_t)stream, x3, s, vol, B,
-                     C, h, w, CV, L, choff, levels);
+  hipLaunchKernelGGL((cv_select_fwd_kernel<3, false>), dim3(dpf_ew_grid((long long)B * C * h * w)), dim3(256), 0, (hipStream_t)stream, x3, s,
+                     vol, B, C, h, w, CV, L, choff, levels);
   return dpf_check_launch();
 }
 
@@ -559,8 +653,8 @@ int dpf_cv_select_backward(const float* x3, const float* s, const float* dvol, f
                            int L, int choff, unsigned levels, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   if (!x3 || !s || !dvol || !dx3 || !ds || B <= 0 || C <= 0 || L <= 0 || L > 32 || choff < 0 || choff + C > CV) return DPF_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(cv_select_bwd_kernel, dim3(dpf_ew_grid((long long)B * C * h * w)), dim3(256), 0, (hipStream_t)stream, x3, s, dvol,
-                     dx3, ds, B, C, h, w, CV, L, choff, levels);
+  hipLaunchKernelGGL((cv_select_bwd_kernel<3, false>), dim3(dpf_ew_grid((long long)B * C * h * w)), dim3(256), 0, (hipStream_t)stream, x3, s,
+                     dvol, dx3, ds, B, C, h, w, CV, L, choff, levels);
   return dpf_check_launch();
 }
 

@@ -983,61 +983,76 @@ def nearest_up_add(lat, top):
 
 # ----------------------------------------------------------------------------------------------- cost volume
 class ShiftTripleFn(torch.autograd.Function):
+    """The M row-shifted copies [B,C,M,h,w] of fea; M = tables' first dimension (the enabled shift modes).  M = 3 runs the
+    dpf_shift_triple_* entry points, M < 3 dpf_shift_copies_*."""
+
     @staticmethod
     def forward(ctx, fea, iy, wy, ix, wx, iy_inv, ix_inv):
         fea = _c(fea)
         _need(fea, iy, wy, ix, wx, iy_inv, ix_inv)
         B, C, h, w = fea.shape
-        out = torch.empty((B, C, 3, h, w), dtype=torch.float32, device=fea.device)
-        lib().call('dpf_shift_triple_forward', _ptr(fea), _ptr(out), _ptr(iy), _ptr(wy), _ptr(ix), _ptr(wx), B, C, h, w, _stream())
+        M = int(iy.shape[0])
+        out = torch.empty((B, C, M, h, w), dtype=torch.float32, device=fea.device)
+        if M == 3:
+            lib().call('dpf_shift_triple_forward', _ptr(fea), _ptr(out), _ptr(iy), _ptr(wy), _ptr(ix), _ptr(wx), B, C, h, w, _stream())
+        else:
+            lib().call('dpf_shift_copies_forward', _ptr(fea), _ptr(out), _ptr(iy), _ptr(wy), _ptr(ix), _ptr(wx), B, C, M, h, w, _stream())
         ctx.tables = (iy_inv, wy, ix_inv, wx)
-        ctx.dims = (B, C, h, w)
+        ctx.dims = (B, C, M, h, w)
         return out
 
     @staticmethod
     def backward(ctx, g):
         iy_inv, wy, ix_inv, wx = ctx.tables
-        B, C, h, w = ctx.dims
+        B, C, M, h, w = ctx.dims
         g = _c(g)
         dfea = torch.empty((B, C, h, w), dtype=torch.float32, device=g.device)
-        lib().call('dpf_shift_triple_backward_gather', _ptr(g), _ptr(dfea), _ptr(iy_inv), _ptr(wy), _ptr(ix_inv), _ptr(wx), B, C, h, w,
-                   _stream())                                       # gather form: deterministic, no atomics, no zero fill
+        # gather form: deterministic, no atomics, no zero fill
+        if M == 3:
+            lib().call('dpf_shift_triple_backward_gather', _ptr(g), _ptr(dfea), _ptr(iy_inv), _ptr(wy), _ptr(ix_inv), _ptr(wx), B, C, h, w,
+                       _stream())
+        else:
+            lib().call('dpf_shift_copies_backward_gather', _ptr(g), _ptr(dfea), _ptr(iy_inv), _ptr(wy), _ptr(ix_inv), _ptr(wx), B, C, M, h,
+                       w, _stream())
         return dfea, None, None, None, None, None, None
 
 
 class PhaseShiftIntoFn(torch.autograd.Function):
-    """Fills slot 2 of the shifted triple x3 [B,C,3,h,w] with the fractional Fourier-phase shift of fea (dpf_phase_shift)."""
+    """Fills the phase slot of the shifted copies x3 [B,C,M,h,w] with the fractional Fourier-phase shift of fea (dpf_phase_shift).  The
+    phase copy is the last enabled mode: slot M - 1, i.e. 2 only when all three modes are on."""
 
     @staticmethod
     def forward(ctx, x3, fea, mr, hm, scale, mr_t, hm_t):
         fea = _c(fea)
         _need(x3, fea, mr, hm, mr_t, hm_t)
         B, C, h, w = fea.shape
+        M = int(x3.shape[2])
         hw = h * w
         tbuf = torch.empty(B * C * w, dtype=torch.float32, device=fea.device)
-        slot2 = ctypes.c_void_p(x3.data_ptr() + 2 * hw * 4)
-        lib().call('dpf_phase_shift', _ptr(fea), hw, slot2, 3 * hw, _ptr(mr), _ptr(hm), float(scale), _ptr(tbuf), B * C, h, w, _stream())
+        slot = ctypes.c_void_p(x3.data_ptr() + (M - 1) * hw * 4)
+        lib().call('dpf_phase_shift', _ptr(fea), hw, slot, M * hw, _ptr(mr), _ptr(hm), float(scale), _ptr(tbuf), B * C, h, w, _stream())
         ctx.mark_dirty(x3)
         ctx.tabs = (mr_t, hm_t, float(scale))
-        ctx.dims = (B, C, h, w)
+        ctx.dims = (B, C, M, h, w)
         return x3
 
     @staticmethod
     def backward(ctx, g):
         mr_t, hm_t, scale = ctx.tabs
-        B, C, h, w = ctx.dims
+        B, C, M, h, w = ctx.dims
         g = _c(g)
         hw = h * w
         dfea = torch.empty((B, C, h, w), dtype=torch.float32, device=g.device)
         tbuf = torch.empty(B * C * w, dtype=torch.float32, device=g.device)
-        slot2 = ctypes.c_void_p(g.data_ptr() + 2 * hw * 4)
-        lib().call('dpf_phase_shift', slot2, 3 * hw, _ptr(dfea), hw, _ptr(mr_t), _ptr(hm_t), scale, _ptr(tbuf), B * C, h, w, _stream())
-        # the triple's own slot 2 held no taps (zero weights in the table sampler), so its incoming gradient needs no masking
+        slot = ctypes.c_void_p(g.data_ptr() + (M - 1) * hw * 4)
+        lib().call('dpf_phase_shift', slot, M * hw, _ptr(dfea), hw, _ptr(mr_t), _ptr(hm_t), scale, _ptr(tbuf), B * C, h, w, _stream())
+        # the copies' own phase slot held no taps (zero weights in the table sampler), so its incoming gradient needs no masking
         return g, dfea, None, None, None, None, None
 
 
 def shift_triple(fea, tables, phase=None):
-    """tables: build_shift_tables(...) on the device; phase: build_phase_tables(...) on the device for a fractional shift."""
+    """tables: build_shift_tables(...) on the device (M = 1, 2 or 3 enabled modes); phase: build_phase_tables(...) on the device for a
+    fractional shift with the phase mode enabled."""
     x3 = ShiftTripleFn.apply(fea, *tables)
     if phase is not None:
         mr, hm, scale, mr_t, hm_t = phase
@@ -1046,13 +1061,15 @@ def shift_triple(fea, tables, phase=None):
 
 
 class CvSelectFn(torch.autograd.Function):
-    """Writes the [B, 2C, L, h, w] volume from groups of (x3_ref, s_ref, x3_tar, s_tar) sharing a level mask."""
+    """Writes the [B, 2C, L, h, w] volume from groups of (x_ref, s_ref, x_tar, s_tar) [B,C,M,h,w] sharing a level mask.  fetch: the
+    variance over the copies instead of their mean (feature_fetch).  M = 3 without fetch runs the dpf_cv_select_* entry points."""
 
     @staticmethod
-    def forward(ctx, L, masks, *ts):
+    def forward(ctx, L, masks, fetch, *ts):
         ts = [_c(t) for t in ts]
         _need(*ts)
-        B, C, _, h, w = ts[0].shape
+        B, C, M, h, w = ts[0].shape
+        fetch = int(bool(fetch))
         covered = 0
         for m in masks:
             covered |= m
@@ -1061,16 +1078,19 @@ class CvSelectFn(torch.autograd.Function):
         lb = lib()
         for gi, m in enumerate(masks):
             x3f, sf, x3b, sb = ts[4 * gi:4 * gi + 4]
-            lb.call('dpf_cv_select_forward', _ptr(x3f), _ptr(sf), _ptr(vol), B, C, h, w, 2 * C, L, 0, m, _stream())
-            lb.call('dpf_cv_select_forward', _ptr(x3b), _ptr(sb), _ptr(vol), B, C, h, w, 2 * C, L, C, m, _stream())
+            for x3, s, off in ((x3f, sf, 0), (x3b, sb, C)):
+                if M == 3 and not fetch:
+                    lb.call('dpf_cv_select_forward', _ptr(x3), _ptr(s), _ptr(vol), B, C, h, w, 2 * C, L, off, m, _stream())
+                else:
+                    lb.call('dpf_cv_select_m_forward', _ptr(x3), _ptr(s), _ptr(vol), B, C, M, h, w, 2 * C, L, off, m, fetch, _stream())
         ctx.save_for_backward(*ts)
-        ctx.cfg = (L, tuple(masks), B, C, h, w)
+        ctx.cfg = (L, tuple(masks), B, C, M, h, w, fetch)
         return vol
 
     @staticmethod
     def backward(ctx, dvol):
         ts = ctx.saved_tensors
-        L, masks, B, C, h, w = ctx.cfg
+        L, masks, B, C, M, h, w, fetch = ctx.cfg
         dvol = _c(dvol)
         lb = lib()
         grads = []
@@ -1079,13 +1099,17 @@ class CvSelectFn(torch.autograd.Function):
             for x3, s, off in ((x3f, sf, 0), (x3b, sb, C)):
                 dx3 = torch.empty_like(x3)
                 ds = torch.empty_like(s)
-                lb.call('dpf_cv_select_backward', _ptr(x3), _ptr(s), _ptr(dvol), _ptr(dx3), _ptr(ds), B, C, h, w, 2 * C, L, off, m, _stream())
+                if M == 3 and not fetch:
+                    lb.call('dpf_cv_select_backward', _ptr(x3), _ptr(s), _ptr(dvol), _ptr(dx3), _ptr(ds), B, C, h, w, 2 * C, L, off, m, _stream())
+                else:
+                    lb.call('dpf_cv_select_m_backward', _ptr(x3), _ptr(s), _ptr(dvol), _ptr(dx3), _ptr(ds), B, C, M, h, w, 2 * C, L, off, m,
+                            fetch, _stream())
                 grads += [dx3, ds]
-        return (None, None) + tuple(grads)
+        return (None, None, None) + tuple(grads)
 
 
-def cv_select(L, masks, tensors):
-    return CvSelectFn.apply(L, list(masks), *tensors)
+def cv_select(L, masks, tensors, fetch=False):
+    return CvSelectFn.apply(L, list(masks), fetch, *tensors)
 
 
 class PsmVolumeFn(torch.autograd.Function):

@@ -1,4 +1,4 @@
-"""Host-side sampler tables for the row-shift triple (nearest / bilinear / phase).
+"""Host-side sampler tables for the row-shifted copies (the enabled ones of nearest / bilinear / phase).
 
 The tables reproduce, in the reference's own float32 operation order, where ``subpixel_shift.forward``
 (src/module/asm/asm.py:21-127) samples each output pixel:
@@ -10,8 +10,9 @@ The tables reproduce, in the reference's own float32 operation order, where ``su
   * the Fourier-phase branch multiplies the row spectrum by exp(2*pi*i*delta*k/h) (asm.py:59-75,112-125): for an
     integer ``delta`` that is a circular row roll, out[y] = src[(y + delta) mod h]; for a fractional ``delta`` (only reached
     with per-level shifts, ``asm_grid_cache_compat = false``) it is a dense row-circulant plus a rank-one Hilbert term
-    (``build_phase_tables``), evaluated by dpf_phase_shift into slot 2 of the triple.
-Every table mode is expressed as <= 2 row taps x <= 2 column taps: iy/wy [3][2][h], ix/wx [3][2][w] (index -1 = no tap); the
+    (``build_phase_tables``), evaluated by dpf_phase_shift into the phase slot (the last one) of the copies.
+Every table mode is expressed as <= 2 row taps x <= 2 column taps: iy/wy [M][2][h], ix/wx [M][2][w] (index -1 = no tap), M = the number
+of enabled modes; the
 inverse tables iy_inv / ix_inv (source coordinate -> output coordinate, the taps are injective) drive the deterministic adjoint.
 """
 import math
@@ -48,7 +49,7 @@ INV_SLOTS = 2
 
 
 def _invert(idx, n):
-    """idx [3,2,n] (output coordinate -> source coordinate, -1 = none) -> inverse [3,2,INV_SLOTS,n]: the (at most INV_SLOTS) output
+    """idx [M,2,n] (output coordinate -> source coordinate, -1 = none) -> inverse [M,2,INV_SLOTS,n]: the (at most INV_SLOTS) output
     coordinates that read a given source coordinate through tap (m, a), -1 padded.  The maps are monotone; float32 rounding of the
     bilinear coordinate can make two neighbouring outputs share a source row, never more."""
     inv = torch.full((idx.shape[0], idx.shape[1], INV_SLOTS, n), -1, dtype=idx.dtype)
@@ -85,39 +86,43 @@ def build_phase_tables(h, w, delta):
 
 
 def build_shift_tables(h, w, delta, use_nearest=True, use_bilinear=True, use_phase=True):
-    """-> (iy int32 [3,2,h], wy float32 [3,2,h], ix int32 [3,2,w], wx float32 [3,2,w], iy_inv, ix_inv) on the CPU.  For a fractional
-    delta the phase slot (mode 2) has no taps: it is filled by dpf_phase_shift (build_phase_tables)."""
-    if not (use_nearest and use_bilinear and use_phase):
-        raise NotImplementedError('the HIP cost-volume path implements the shipped nearest+bilinear+phase triple')
-    iy = torch.full((3, 2, h), -1, dtype=torch.int32)
-    ix = torch.full((3, 2, w), -1, dtype=torch.int32)
-    wy = torch.zeros((3, 2, h), dtype=torch.float32)
-    wx = torch.zeros((3, 2, w), dtype=torch.float32)
+    """-> (iy int32 [M,2,h], wy float32 [M,2,h], ix int32 [M,2,w], wx float32 [M,2,w], iy_inv, ix_inv) on the CPU, one slot per ENABLED
+    mode in the reference's order nearest, bilinear, phase (asm.py:92-127 appends only the enabled copies), so M = 1, 2 or 3.  For a
+    fractional delta the phase slot (the last one) has no taps: it is filled by dpf_phase_shift (build_phase_tables)."""
+    modes = [name for name, on in (('nearest', use_nearest), ('bilinear', use_bilinear), ('phase', use_phase)) if on]
+    if not modes:
+        raise ValueError('the ASM needs at least one of nearest / bilinear / phase (the reference fails in torch.cat of an empty list)')
+    M = len(modes)
+    iy = torch.full((M, 2, h), -1, dtype=torch.int32)
+    ix = torch.full((M, 2, w), -1, dtype=torch.int32)
+    wy = torch.zeros((M, 2, h), dtype=torch.float32)
+    wx = torch.zeros((M, 2, w), dtype=torch.float32)
     ny, (ylo, yhi, wylo, wyhi) = _axis_tables(h, delta)
     nx, (xlo, xhi, wxlo, wxhi) = _axis_tables(w, 0.0)
-    # mode 0: nearest
-    iy[0, 0], wy[0, 0] = ny, 1.0
-    ix[0, 0], wx[0, 0] = nx, 1.0
-    # mode 1: bilinear
-    iy[1, 0], iy[1, 1], wy[1, 0], wy[1, 1] = ylo, yhi, wylo, wyhi
-    ix[1, 0], ix[1, 1], wx[1, 0], wx[1, 1] = xlo, xhi, wxlo, wxhi
-    # mode 2: phase shift == circular roll for an integer delta
-    if not is_fractional(delta):
-        iy[2, 0] = ((torch.arange(h) + int(delta)) % h).to(torch.int32)
-        wy[2, 0] = 1.0
-        ix[2, 0] = torch.arange(w, dtype=torch.int32)
-        wx[2, 0] = 1.0
+    for m, mode in enumerate(modes):
+        if mode == 'nearest':
+            iy[m, 0], wy[m, 0] = ny, 1.0
+            ix[m, 0], wx[m, 0] = nx, 1.0
+        elif mode == 'bilinear':
+            iy[m, 0], iy[m, 1], wy[m, 0], wy[m, 1] = ylo, yhi, wylo, wyhi
+            ix[m, 0], ix[m, 1], wx[m, 0], wx[m, 1] = xlo, xhi, wxlo, wxhi
+        elif not is_fractional(delta):                  # phase shift == circular roll for an integer delta
+            iy[m, 0] = ((torch.arange(h) + int(delta)) % h).to(torch.int32)
+            wy[m, 0] = 1.0
+            ix[m, 0] = torch.arange(w, dtype=torch.int32)
+            wx[m, 0] = 1.0
     iy, ix = iy.contiguous(), ix.contiguous()
     return iy, wy.contiguous(), ix, wx.contiguous(), _invert(iy, h), _invert(ix, w)
 
 
 def apply_tables_reference(fea, tables):
     """Slow torch evaluation of the table sampler (used by the CPU tests to pin the host logic against the golden
-    vectors; the product path evaluates the same tables in dpf_shift_triple_forward)."""
+    vectors; the product path evaluates the same tables in dpf_shift_triple_forward / dpf_shift_copies_forward)."""
     iy, wy, ix, wx = tables[:4]
     B, C, h, w = fea.shape
-    out = fea.new_zeros(B, C, 3, h, w)
-    for m in range(3):
+    M = iy.shape[0]
+    out = fea.new_zeros(B, C, M, h, w)
+    for m in range(M):
         for a in range(2):
             for e in range(2):
                 ry, rx = iy[m, a].long(), ix[m, e].long()

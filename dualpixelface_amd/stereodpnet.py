@@ -3,7 +3,7 @@
 Mirrors ``STEREODPNET`` of the reference (src/model/stereodpnet/mainmodel.py:21-177): same constructor
 argument (the ``option`` object built from config_/*.json + src/model/stereodpnet/config.json +
 dataloader/FaceDP/config.json), same ``forward(batch) -> dict`` keys, same ``state_dict`` key names and
-shapes (511 entries + the lazily registered ``normal_estimator.grid``), same loss/metric hooks and
+shapes (511 entries, 512 with the PReLU gate of ``asm_activation = 'relu'``, + the lazily registered ``normal_estimator.grid``), same loss/metric hooks and
 optimiser/scheduler selection.  This file is the network alone: its spec and its straight-line forward over the
 HIP operator layer (ops.py); the flat parameter arena and the conv / BatchNorm primitives are core.ArenaModule's.
 """
@@ -131,6 +131,12 @@ def build_spec(opt):
     s.conv(at + '.mask_convs.3.0', c, c, (1, 1, 1))
     s.add(at + '.mask_convs.3.1.weight', (c,), 'alias', at + '.normalize.weight')
     s.add(at + '.mask_convs.3.1.bias', (c,), 'alias', at + '.normalize.bias')
+    if not (m.nearest or m.bilinear or m.phase):
+        raise ValueError('the ASM needs at least one of nearest / bilinear / phase (the reference fails in torch.cat of an empty list)')
+    if m.asm_activation == 'relu':
+        s.prelu(at + '.activation')                       # nn.PReLU(init=0.05) gate (asm.py:151-152); the reference's init loop skips it
+    elif m.asm_activation != 'sigmoid':
+        raise NotImplementedError('activation type is not implemented')
     HourglassAggregation.aggregation_spec(s, 2 * c, c)
     # normal_estimator (normal_module.py:32-78)
     if m.predict_normal:
@@ -270,18 +276,18 @@ class StereoDPNetCore(HourglassAggregation, ArenaModule):
             m = self.option.model
             tables = tuple(t.to(device) for t in build_shift_tables(h, w, delta, m.nearest, m.bilinear, m.phase))
             phase = None
-            if is_fractional(delta):                              # per-level shifts only (asm_grid_cache_compat = false)
+            if m.phase and is_fractional(delta):                  # per-level shifts only (asm_grid_cache_compat = false)
                 phase = tuple(t.to(device) if torch.is_tensor(t) else t for t in build_phase_tables(h, w, delta))
             self._tables[key] = (tables, phase)
         return self._tables[key]
 
     def _attention_parts(self, fea, delta, stat_sink=None):
-        """shifted triple + MaskingAttention up to the sigmoid (asm.py:87-127,141-162).
+        """shifted copies (M = the enabled modes) + MaskingAttention up to the gate activation (asm.py:87-127,141-162).
 
         ``stat_sink`` = (zeroed mean buffer, zeroed var buffer): the BatchNorm EMA of this call is redirected there
         (it then holds momentum * batch statistic) so the caller can replay the reference's update sequence."""
         P, Bf, p = self._P, self._B, 'cost_volume.attention_layer'
-        x3 = ops.shift_triple(fea, *self._shift_tables(fea.shape[2], fea.shape[3], delta, fea.device))  # [B,C,3,h,w]
+        x3 = ops.shift_triple(fea, *self._shift_tables(fea.shape[2], fea.shape[3], delta, fea.device))  # [B,C,M,h,w]
         st = self._stats_holder()
         mk = ops.conv3d(x3, P[p + '.mask_convs.0.weight'], None, 1, (0, 1, 1), 1, stats=st)
         q = p + '.mask_convs.1'
@@ -293,13 +299,17 @@ class StereoDPNetCore(HourglassAggregation, ArenaModule):
             mk = ops.norm_act(mk, P[q + '.weight'], P[q + '.bias'], None, None, None, Bf[q + '.running_mean'], Bf[q + '.running_var'], 2,
                               ACT_RELU)
         mk = ops.conv3d(mk, P[p + '.mask_convs.3.0.weight'])
-        s = ops.norm_act(mk, P[p + '.normalize.weight'], P[p + '.normalize.bias'], mode=3, act=ACT_SIGMOID)
+        if self.option.model.asm_activation == 'relu':
+            s = ops.norm_act(mk, P[p + '.normalize.weight'], P[p + '.normalize.bias'], P[p + '.activation.weight'], mode=3, act=ACT_PRELU)
+        else:
+            s = ops.norm_act(mk, P[p + '.normalize.weight'], P[p + '.normalize.bias'], mode=3, act=ACT_SIGMOID)
         return x3, s
 
     def _cost_volume(self, ref, tar):
         """CostVolume.build_concat_volume (modules.py:181-197)."""
         L = int(self.level)
         q = 'cost_volume.attention_layer.mask_convs.1'
+        fetch = bool(self.option.model.feature_fetch)             # the variance over the copies instead of their mean (asm.py:165-169)
         if self.grid_cache_compat:
             # The reference's shift-grid cache is keyed on nothing: every level reuses costrange[0] (SURVEY Q1), so its
             # 2*L attention calls are L identical (ref, target) pairs.  Compute the pair once, write it to all levels,
@@ -318,7 +328,7 @@ class StereoDPNetCore(HourglassAggregation, ArenaModule):
                 for name, a_f, a_b in (('.running_mean', z[0], z[2]), ('.running_var', z[1], z[3])):
                     ops.bn_replay(self._B[q + name], a_f, a_b, keep ** (2 * L), keep * G, G)
                 self._count(q + '.num_batches_tracked', 2 * L)
-            return ops.cv_select(L, [(1 << L) - 1], [x3f, sf, x3b, sb])
+            return ops.cv_select(L, [(1 << L) - 1], [x3f, sf, x3b, sb], fetch)
         tensors, masks = [], []
         for i, delta in enumerate(self.costrange):
             x3f, sf = self._attention_parts(ref, +delta)
@@ -327,7 +337,7 @@ class StereoDPNetCore(HourglassAggregation, ArenaModule):
                 self._count(q + '.num_batches_tracked', 2)
             tensors += [x3f, sf, x3b, sb]
             masks.append(1 << i)
-        return ops.cv_select(L, masks, tensors)
+        return ops.cv_select(L, masks, tensors, fetch)
 
     # ------------------------------------------------------------------ normal module (normal_module.py:140-194)
     def _deform(self, x, p, gi_channels=None):

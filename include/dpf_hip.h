@@ -206,14 +206,26 @@ int dpf_shift_triple_backward_gather(const float* g, float* dfea, const int* iy_
                                      int B, int C, int h, int w, void* stream);
 /* fractional Fourier-phase row shift of `planes` [h, w] planes (asm.py:59-75,112-125; only reached with per-level shifts):
  * dst[p][y][x] = sum_y' mr[(y - y') mod h] src[p][y'][x] + scale (-1)^y sum_x' hm[(x - x') mod w] sum_y' (-1)^y' src[p][y'][x'].
- * mr [h], hm [w]: device tables; tbuf: planes * w floats of scratch; plane strides in floats (dst may be slot 2 of the [B,C,3,h,w]
- * triple).  The adjoint is the same call with index-reversed tables. */
+ * mr [h], hm [w]: device tables; tbuf: planes * w floats of scratch; plane strides in floats (dst may be the phase slot of the
+ * [B,C,M,h,w] copies).  The adjoint is the same call with index-reversed tables. */
 int dpf_phase_shift(const float* src, long long src_plane_stride, float* dst, long long dst_plane_stride, const float* mr, const float* hm,
                     float scale, float* tbuf, long long planes, int h, int w, void* stream);
 int dpf_cv_select_forward(const float* x3, const float* s, float* vol, int B, int C, int h, int w, int CV, int L, int choff,
                           unsigned levels, void* stream);
 int dpf_cv_select_backward(const float* x3, const float* s, const float* dvol, float* dx3, float* ds, int B, int C, int h, int w, int CV,
                            int L, int choff, unsigned levels, void* stream);
+/* The same two stages for the ASM ablations (src/model/stereodpnet/config.json: nearest / bilinear / phase, feature_fetch): M = 1, 2 or 3
+ * enabled shift modes in the reference's order, out / x / s [B, C, M, h, w], tables [M][2][h|w] (inverse tables [M][2][2][h|w]).
+ * fetch = 0: vol = mean_m z_m with z_m = x_m softmax_M(s)_m; fetch = 1: the variance mean_m z_m^2 - (mean_m z_m)^2 (asm.py:165-169).
+ * M = 3, fetch = 0 runs the kernels of the entry points above. */
+int dpf_shift_copies_forward(const float* fea, float* out, const int* iy, const float* wy, const int* ix, const float* wx, int B, int C,
+                             int M, int h, int w, void* stream);
+int dpf_shift_copies_backward_gather(const float* g, float* dfea, const int* iy_inv, const float* wy, const int* ix_inv, const float* wx,
+                                     int B, int C, int M, int h, int w, void* stream);
+int dpf_cv_select_m_forward(const float* x, const float* s, float* vol, int B, int C, int M, int h, int w, int CV, int L, int choff,
+                            unsigned levels, int fetch, void* stream);
+int dpf_cv_select_m_backward(const float* x, const float* s, const float* dvol, float* dx, float* ds, int B, int C, int M, int h, int w,
+                             int CV, int L, int choff, unsigned levels, int fetch, void* stream);
 int dpf_psm_volume_forward(const float* ref, const float* tar, float* vol, const int* shifts_host, int B, int C, int h, int w, int L,
                            int groups, void* stream);
 
