@@ -11,6 +11,7 @@
 // Forward handles stride 1 / 2 and any dilation; the data gradient of stride-1 convs is the same kernel on grad_output with the
 // taps flipped and the channel roles swapped (strided data gradients and all weight gradients stay on the fp32 kernels).
 #include "dpf_common.h"
+#include "conv_internal.h"
 
 namespace {
 
@@ -182,15 +183,16 @@ int launch(const float* x, const float* w, const float* bias, float* out, void* 
     if (blocks >= 0x7fffffffLL) return DPF_ERR_UNSUPPORTED;
     const long long welems = (long long)T * p.nchunk * KT * 16;
     hipLaunchKernelGGL(repack_bf16_kernel, dim3(dpf_ew_grid(welems)), dim3(256), 0, st, w, (__bf16*)ws, A, B, T, KT, p.nchunk, mode, k0);
-#define DPF_CB(M, Nt)                                                                                                           \
-  {                                                                                                                             \
-    if (lds > 48 * 1024 &&                                                                                                      \
-        hipFuncSetAttribute((const void*)conv2d_bf16_kernel<M, Nt>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-      return DPF_ERR_LAUNCH;                                                                                                    \
-    hipLaunchKernelGGL((conv2d_bf16_kernel<M, Nt>), dim3((unsigned)blocks), dim3(256), lds, st, x, (const __bf16*)ws, bias, out, p); \
-  }
-    switch (MT) { case 1: DPF_CB(1, 4); break; case 2: DPF_CB(2, 2); break; case 3: DPF_CB(3, 2); break; default: DPF_CB(4, 2); break; }
-#undef DPF_CB
+    const dim3 grid((unsigned)blocks);
+    const __bf16* wpk = (const __bf16*)ws;
+    int rc;
+    switch (MT) {
+      case 1: rc = conv_launch<conv2d_bf16_kernel<1, 4>>(grid, dim3(256), lds, st, x, wpk, bias, out, p); break;
+      case 2: rc = conv_launch<conv2d_bf16_kernel<2, 2>>(grid, dim3(256), lds, st, x, wpk, bias, out, p); break;
+      case 3: rc = conv_launch<conv2d_bf16_kernel<3, 2>>(grid, dim3(256), lds, st, x, wpk, bias, out, p); break;
+      default: rc = conv_launch<conv2d_bf16_kernel<4, 2>>(grid, dim3(256), lds, st, x, wpk, bias, out, p); break;
+    }
+    if (rc != DPF_OK) return rc;
   }
   return dpf_check_launch();
 }

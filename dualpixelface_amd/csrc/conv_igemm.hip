@@ -20,7 +20,6 @@
 #include "dpf_common.h"
 #include "dpf_repack.h"
 #include "conv_internal.h"
-#include <cstdlib>
 
 namespace {
 
@@ -474,65 +473,36 @@ __global__ __launch_bounds__(256, (MT == 1 ? 4 : (MT == 2 ? 3 : 2))) void conv_w
   }
 }
 
-int out_dim(int I, int k, int s, int p, int d) { return (I + 2 * p - (d * (k - 1) + 1)) / s + 1; }
-
-template <int MT, int CC, int NT>
-int launch_igemm(const float* x, const float* wt, const float* bias, float* out, const ConvP& p, size_t lds, hipStream_t st) {
+template <int CC>
+int launch_igemm(int MT, const float* x, const float* wt, const float* bias, float* out, const ConvP& p, size_t lds, hipStream_t st) {
   const long long blocks = (long long)p.ncls * p.N * p.QD * p.tilesH * p.tilesW;
   if (blocks <= 0 || blocks > 0x7fffffffLL) return DPF_ERR_INVALID_ARG;
-  if (lds > 48 * 1024) {
-    if (hipFuncSetAttribute((const void*)conv_igemm_kernel<MT, CC, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return DPF_ERR_LAUNCH;
+  const dim3 grid((unsigned)blocks), block(256);
+  switch (MT) {
+    case 1: return conv_launch<conv_igemm_kernel<1, CC, 4>>(grid, block, lds, st, x, wt, bias, out, p);
+    case 2: return conv_launch<conv_igemm_kernel<2, CC, 2>>(grid, block, lds, st, x, wt, bias, out, p);
+    case 3: return conv_launch<conv_igemm_kernel<3, CC, 2>>(grid, block, lds, st, x, wt, bias, out, p);
+    default: return conv_launch<conv_igemm_kernel<4, CC, 2>>(grid, block, lds, st, x, wt, bias, out, p);
   }
-  hipLaunchKernelGGL((conv_igemm_kernel<MT, CC, NT>), dim3((unsigned)blocks), dim3(256), lds, st, x, wt, bias, out, p);
-  return dpf_check_launch();
 }
 
-int conv_launch(const float* x, const float* wt_ws, const float* bias, float* out, ConvP p, hipStream_t st);
+}  // namespace
 
-int conv_common(const float* x, const float* w, const float* bias, float* out, float* wt_ws, ConvP p, int repack_mode,
-                int wA, int wB, hipStream_t st, int Ktot = 0, int accumulate = 0) {
-  const int T = p.kd * p.kh * p.kw;
-  if (T > MAXT && dpf_wide_eligible(T, p.kd, p.kh, p.kw, p.sd, p.sh, p.sw, p.pd, p.dd, p.dh, p.dw)) {     // 28 ... 49 taps, 2-D (conv_wide.hip)
-    DpfConvDesc d{p.N, p.C, p.K, Ktot > 0 ? Ktot : p.K, 0, p.ID, p.IH, p.IW, p.OD, p.OH, p.OW, p.kd, p.kh, p.kw, p.sd, p.sh, p.sw,
-                  p.pd, p.ph, p.pw, p.dd, p.dh, p.dw, p.transposed, wA, wB, repack_mode, accumulate};
-    return dpf_wide_conv(x, w, bias, out, d, st);
-  }
-  if (T > MAXT || T < 1) return DPF_ERR_UNSUPPORTED;
-  // one launch covers up to 128 output channels (4 MFMA row tiles); wider outputs are split
-  const int Kfull = p.K;
-  p.Ktot = Ktot > 0 ? Ktot : Kfull;          // channels of the output tensor (>= the Kfull channels this call computes)
-  for (int k0 = 0; k0 < Kfull; k0 += 128) {
-    const int Kc = Kfull - k0 < 128 ? Kfull - k0 : 128;
-    {   // LDS-DMA double-buffered kernel where the shape is eligible (conv_igemm2.hip)
-      DpfConvDesc d{p.N, p.C, Kc, p.Ktot, k0, p.ID, p.IH, p.IW, p.OD, p.OH, p.OW, p.kd, p.kh, p.kw, p.sd, p.sh, p.sw,
-                    p.pd, p.ph, p.pw, p.dd, p.dh, p.dw, p.transposed, wA, wB, repack_mode, accumulate};
-      if (T == 1 && !accumulate) {                   // pointwise: HBM-bound direct kernel (conv_pointwise.hip)
-        const int rcp = dpf_pointwise_conv(x, w, bias, out, d, st);
-        if (rcp == DPF_OK) continue;
-        if (rcp != DPF_ERR_UNSUPPORTED) return rcp;
-      }
-      const int rc2 = dpf_igemm2_conv(x, w, bias, out, wt_ws, d, st);
-      if (rc2 == DPF_OK) continue;
-      if (rc2 != DPF_ERR_UNSUPPORTED) return rc2;
-    }
-    if (accumulate) return DPF_ERR_UNSUPPORTED;      // the first-generation kernel only stores
-    const int KT = 32 * ((Kc + 31) / 32);
-    const long long total = (long long)T * p.C * KT;
-    hipLaunchKernelGGL(repack_weights_kernel, dim3(dpf_ew_grid(total)), dim3(256), 0, st, w, wt_ws, wA, wB, T, KT, repack_mode, k0, Kc);
-    if (dpf_check_launch() != DPF_OK) return DPF_ERR_LAUNCH;
-    p.K = Kc;
-    p.k0 = k0;
-    const int rc = conv_launch(x, wt_ws, bias, out, p, st);
-    if (rc != DPF_OK) return rc;
-  }
-  return DPF_OK;
-}
-
-int conv_launch(const float* x, const float* wt_ws, const float* bias, float* out, ConvP p, hipStream_t st) {
-  const int T = p.kd * p.kh * p.kw;
-  const int MT = (p.K + 31) / 32;
+// One launch for the output channels [d.k0, d.k0 + d.K), d.K <= 128 (4 MFMA row tiles): the weight slice is repacked into `ws`, then
+// the tile kernel runs.  Stores only: the caller declines `accumulate` before it gets here.
+int dpf_gen1_conv(const float* x, const float* w, const float* bias, float* out, float* ws, const DpfConvDesc& d, hipStream_t st) {
+  const int T = d.kd * d.kh * d.kw;
+  if (T > MAXT || T < 1 || d.K > 128) return DPF_ERR_UNSUPPORTED;
+  const int MT = (d.K + 31) / 32;
   const int KT = 32 * MT;
+  hipLaunchKernelGGL(repack_weights_kernel, dim3(dpf_ew_grid((long long)T * d.C * KT)), dim3(256), 0, st, w, ws, d.wA, d.wB, T, KT, d.mode, d.k0, d.K);
+  if (dpf_check_launch() != DPF_OK) return DPF_ERR_LAUNCH;
+  ConvP p{};
+  p.N = d.N; p.C = d.C; p.K = d.K; p.Ktot = d.Ktot; p.k0 = d.k0;
+  p.ID = d.ID; p.IH = d.IH; p.IW = d.IW; p.OD = d.OD; p.OH = d.OH; p.OW = d.OW;
+  p.kd = d.kd; p.kh = d.kh; p.kw = d.kw; p.sd = d.sd; p.sh = d.sh; p.sw = d.sw;
+  p.pd = d.pd; p.ph = d.ph; p.pw = d.pw; p.dd = d.dd; p.dh = d.dh; p.dw = d.dw;
+  p.transposed = d.transposed;
   const int NT = MT == 1 ? 4 : 2;   // narrow outputs: more position tiles per wave so each weight fragment feeds 4 MFMAs
   const int TH = 4 * NT;
   // tile geometry (host worst case over classes)
@@ -576,230 +546,37 @@ int conv_launch(const float* x, const float* wt_ws, const float* bias, float* ou
   const size_t lds = lds_bytes(CC);
   if (lds > 160 * 1024) return DPF_ERR_UNSUPPORTED;
   p.maxrows = CC * ext_d * ext_h;
-#define DPF_IG(M, Cc, Nt) return launch_igemm<M, Cc, Nt>(x, wt_ws, bias, out, p, lds, st)
-  if (CC == 8) {
-    switch (MT) { case 1: DPF_IG(1, 8, 4); case 2: DPF_IG(2, 8, 2); case 3: DPF_IG(3, 8, 2); default: DPF_IG(4, 8, 2); }
-  } else {
-    switch (MT) { case 1: DPF_IG(1, 4, 4); case 2: DPF_IG(2, 4, 2); case 3: DPF_IG(3, 4, 2); default: DPF_IG(4, 4, 2); }
-  }
-#undef DPF_IG
+  return CC == 8 ? launch_igemm<8>(MT, x, ws, bias, out, p, lds, st) : launch_igemm<4>(MT, x, ws, bias, out, p, lds, st);
 }
 
-}  // namespace
-
-int dpf_conv_wgrad_slice(const float* g, const float* x, float* dw, int N, int C, int ID, int IH, int IW, int K, int kbeg, int kcount, int QD,
-                         int QH, int QW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw_,
-                         void* stream);
-
-namespace { int g_operand_bf16 = 0; }
-int dpf_conv_operand_bf16() { return g_operand_bf16; }
-namespace { int g_f32_x9 = -1; }
-int dpf_conv_f32_x9() {
-  if (g_f32_x9 < 0) {
-    const int v = getenv("DPF_F32_X9") ? atoi(getenv("DPF_F32_X9")) : 2;
-    g_f32_x9 = v < 0 ? 0 : (v > 2 ? 2 : v);
-  }
-  return g_f32_x9;
-}
-namespace { int g_h3_guard = 1; }
-int dpf_h3_range_guard() { return g_h3_guard; }
-
-extern "C" {
-
-// 0: exact fp32 operands (default); 1: the dense convolution kernels (forward, stride-1 data gradient, weight gradient) round their
-// operands to bf16 (RNE) while staging them, accumulate and store in fp32.  Process-wide; the host side sets it around each launch.
-int dpf_set_conv_operand_precision(int bf16) {
-  g_operand_bf16 = bf16 ? 1 : 0;
-  return DPF_OK;
-}
-int dpf_get_conv_operand_precision(void) { return g_operand_bf16; }
-int dpf_set_f32_matrix_path(int split_bf16) {
-  g_f32_x9 = split_bf16 < 0 ? 0 : (split_bf16 > 2 ? 2 : split_bf16);
-  return DPF_OK;
-}
-int dpf_get_f32_matrix_path(void) { return dpf_conv_f32_x9(); }
-// diagnostic: 0 switches the position guard of the f16-component convolutions off (round 5's behaviour) so that a test can show what it buys
-int dpf_debug_set_range_guard(int on) {
-  g_h3_guard = on ? 1 : 0;
-  return DPF_OK;
-}
-
-// workspace (floats) needed for the repacked weights of a conv with `T` taps, `reduce` reduction channels
-// and `outc` output channels
-long long dpf_conv_workspace_floats(int T, int reduce, int outc) {
-  const long long a = (long long)T * reduce * (((outc + 31) / 32) * 32), b = dpf_igemm2_workspace_floats(T, reduce, outc);
-  return a > b ? a : b;
-}
-
-// x [N,C,ID,IH,IW], w [K,C,kd,kh,kw], bias [K] or NULL, out [N,K,OD,OH,OW]
-int dpf_conv_forward(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
-                     int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw,
-                     void* stream) {
-  dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
-  if (!x || !w || !out || !ws || N <= 0 || C <= 0 || K <= 0) return DPF_ERR_INVALID_ARG;
-  ConvP p{};
-  p.N = N; p.C = C; p.K = K; p.ID = ID; p.IH = IH; p.IW = IW;
-  p.kd = kd; p.kh = kh; p.kw = kw; p.sd = sd; p.sh = sh; p.sw = sw; p.pd = pd; p.ph = ph; p.pw = pw; p.dd = dd; p.dh = dh; p.dw = dw;
-  p.OD = out_dim(ID, kd, sd, pd, dd); p.OH = out_dim(IH, kh, sh, ph, dh); p.OW = out_dim(IW, kw, sw, pw, dw);
-  if (p.OD <= 0 || p.OH <= 0 || p.OW <= 0) return DPF_ERR_INVALID_ARG;
-  p.transposed = 0;
-  return conv_common(x, w, bias, out, ws, p, /*mode*/ 0, K, C, (hipStream_t)stream);
-}
-
-// dpf_conv_forward that also leaves, per position tile, the (sum, sum of squares) of every output channel in `slab`
-// ([*parts_host][K][2] doubles, capacity dpf_conv_stats_slab_doubles) for the BatchNorm that follows (dpf_bn_finalize_partials): the
-// separate statistics pass over the output tensor disappears.  DPF_ERR_UNSUPPORTED when the shape does not run on the LDS-DMA
-// kernel (K > 128, rows not 16-byte aligned, 1x1 kernels ...): the caller then uses dpf_conv_forward + dpf_bn_stats.
-long long dpf_conv_stats_slab_doubles(int N, int K, int OD, int OH, int OW) {
-  return 2LL * K * ((long long)N * OD * dpf_div_up(OH, 8) * dpf_div_up(OW, 32) + 64);     // + the 64 folded rows of the finalize step
-}
-
-int dpf_conv_forward_stats(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
-                           int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw,
-                           double* slab, long long slab_doubles, int* parts_host, void* stream) {
-  dpf_clear_error();
-  if (!x || !w || !out || !ws || !slab || !parts_host || N <= 0 || C <= 0 || K <= 0) return DPF_ERR_INVALID_ARG;
-  const int OD = out_dim(ID, kd, sd, pd, dd), OH = out_dim(IH, kh, sh, ph, dh), OW = out_dim(IW, kw, sw, pw, dw);
-  if (OD <= 0 || OH <= 0 || OW <= 0) return DPF_ERR_INVALID_ARG;
-  DpfConvDesc d{N, C, K, K, 0, ID, IH, IW, OD, OH, OW, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw, 0, K, C, 0};
-  DpfConvStats stats{slab, slab_doubles - 2LL * K * 64, 0};
-  const int rc = dpf_igemm2_conv(x, w, bias, out, ws, d, (hipStream_t)stream, &stats);
-  if (rc == DPF_OK) *parts_host = stats.parts;
-  return rc;
-}
-
-// Transposed convolution.  x [N,C,ID,IH,IW] lives on the strided (small) grid, out [N,K,OD,OH,OW] on the dense grid;
-// (OD,OH,OW) are given by the caller (output_padding ambiguity).  `w_is_conv_layout` = 1: w is a forward-conv weight
-// [C(x chans = conv out), K(out chans = conv in), T] and this call is that conv's data gradient;
-// = 0: w is an nn.ConvTranspose3d weight [C_in = C, C_out = K, T].  Both are [C][K][T] in memory.
-int dpf_conv_transpose(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
-                       int K, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
-                       int dd, int dh, int dw, void* stream) {
-  dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
-  if (!x || !w || !out || !ws || N <= 0 || C <= 0 || K <= 0) return DPF_ERR_INVALID_ARG;
-  ConvP p{};
-  p.N = N; p.C = C; p.K = K; p.ID = ID; p.IH = IH; p.IW = IW; p.OD = OD; p.OH = OH; p.OW = OW;
-  p.kd = kd; p.kh = kh; p.kw = kw; p.sd = sd; p.sh = sh; p.sw = sw; p.pd = pd; p.ph = ph; p.pw = pw; p.dd = dd; p.dh = dh; p.dw = dw;
-  p.transposed = 1;
-  // w[C][K][T]: reduce = A (=C), out = B (=K)
-  return conv_common(x, w, bias, out, ws, p, /*mode*/ 1, C, K, (hipStream_t)stream);
-}
-
-// As dpf_conv_transpose for an output tensor (and weight) of Ktot channels of which only the first K are computed (the others
-// are left untouched): data gradients whose trailing input channels have no consumer (the constant XYZ channels of the ANM volume).
-int dpf_conv_transpose_ex(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
-                          int K, int Ktot, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
-                          int dd, int dh, int dw, void* stream) {
-  dpf_clear_error();
-  if (!x || !w || !out || !ws || N <= 0 || C <= 0 || K <= 0 || Ktot < K) return DPF_ERR_INVALID_ARG;
-  ConvP p{};
-  p.N = N; p.C = C; p.K = K; p.ID = ID; p.IH = IH; p.IW = IW; p.OD = OD; p.OH = OH; p.OW = OW;
-  p.kd = kd; p.kh = kh; p.kw = kw; p.sd = sd; p.sh = sh; p.sw = sw; p.pd = pd; p.ph = ph; p.pw = pw; p.dd = dd; p.dh = dh; p.dw = dw;
-  p.transposed = 1;
-  return conv_common(x, w, bias, out, ws, p, /*mode*/ 1, C, Ktot, (hipStream_t)stream, Ktot);
-}
-
-// dpf_conv_transpose_ex with out += result when accumulate != 0: the data gradients of several convolutions that read the same tensor
-// (the three dilated branches of a DPBlock, modules.py:43-45) are summed in the kernel epilogue instead of by separate add passes.
-// DPF_ERR_UNSUPPORTED (nothing written) when the shape would not run on the LDS-DMA kernel: compute into a temporary and add.
-int dpf_conv_transpose_acc(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
-                           int K, int Ktot, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
-                           int dd, int dh, int dw, int accumulate, void* stream) {
-  dpf_clear_error();
-  if (!x || !w || !out || !ws || N <= 0 || C <= 0 || K <= 0 || Ktot < K) return DPF_ERR_INVALID_ARG;
-  if (accumulate && K > 128) return DPF_ERR_UNSUPPORTED;      // split launches: a failure midway would leave a partial sum
-  ConvP p{};
-  p.N = N; p.C = C; p.K = K; p.ID = ID; p.IH = IH; p.IW = IW; p.OD = OD; p.OH = OH; p.OW = OW;
-  p.kd = kd; p.kh = kh; p.kw = kw; p.sd = sd; p.sh = sh; p.sw = sw; p.pd = pd; p.ph = ph; p.pw = pw; p.dd = dd; p.dh = dh; p.dw = dw;
-  p.transposed = 1;
-  return conv_common(x, w, bias, out, ws, p, /*mode*/ 1, C, Ktot, (hipStream_t)stream, Ktot, accumulate ? 1 : 0);
-}
-
-// Forward conv with the weight stored transposed-conv style w[K_reduce=C? ...]:
-// data gradient of nn.ConvTranspose3d: out[n,ci,q] = sum_{co,t} w[ci][co][t] * g[n,co, q*s - p + t*dil]
-// i.e. a forward conv whose weight is indexed [out][reduce][t] -- identical to dpf_conv_forward (w[K][C][T]).
-
-// dW[K][C][T] += ...   (dw must be zero-initialised or hold the running gradient)
-// g [N,K,QD,QH,QW] on the small grid, x [N,C,ID,IH,IW] on the dense grid.
-long long dpf_conv_wgrad_workspace_floats(int T, int C, int K) {
-  const long long a = dpf_wgrad2_workspace_floats(T, C, K), b = T == 1 ? dpf_pointwise_wgrad_workspace_floats(C, K < 128 ? K : 128) : 0;
-  const long long c = dpf_wide_wgrad_workspace_floats(T, C, K < 128 ? K : 128);
-  return a > b ? (a > c ? a : c) : (b > c ? b : c);
-}
-
-// as dpf_conv_wgrad below, with caller scratch (dpf_conv_wgrad_workspace_floats floats): eligible shapes run the LDS-DMA kernel
-// with a deterministic slab reduction (conv_wgrad2.hip) instead of float atomics
-int dpf_conv_wgrad_ws(const float* g, const float* x, float* dw, float* ws, long long ws_floats, int N, int C, int ID, int IH, int IW, int K,
-                      int QD, int QH, int QW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw_,
-                      int accumulate, void* stream) {
-  dpf_clear_error();
-  if (!g || !x || !dw || N <= 0 || C <= 0 || K <= 0) return DPF_ERR_INVALID_ARG;
-  const int T = kd * kh * kw;
-  for (int k0 = 0; k0 < K; k0 += 128) {
-    const int Kc = K - k0 < 128 ? K - k0 : 128;
-    float* dwk = dw + (long long)k0 * C * T;
-    int rc = DPF_ERR_UNSUPPORTED;
-    if (ws) {
-      DpfWgradDesc d{N, C, Kc, K, k0, ID, IH, IW, QD, QH, QW, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw_};
-      if (T == 1) rc = dpf_pointwise_wgrad(g, x, dwk, ws, ws_floats, d, accumulate, (hipStream_t)stream);
-      if (T > MAXT) rc = dpf_wide_wgrad(g, x, dwk, ws, ws_floats, d, accumulate, (hipStream_t)stream);
-      if (rc == DPF_ERR_UNSUPPORTED) rc = dpf_wgrad2(g, x, dwk, ws, ws_floats, d, accumulate, (hipStream_t)stream);
-    }
-    if (rc == DPF_ERR_UNSUPPORTED) {
-      if (!accumulate && hipMemsetAsync(dwk, 0, sizeof(float) * (size_t)Kc * C * T, (hipStream_t)stream) != hipSuccess) return DPF_ERR_LAUNCH;
-      // generic kernel on this channel slice: g viewed with Ktot = K channels, slice [k0, k0 + Kc)
-      rc = dpf_conv_wgrad_slice(g, x, dwk, N, C, ID, IH, IW, K, k0, Kc, QD, QH, QW, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw_, stream);
-    }
-    if (rc != DPF_OK) return rc;
-  }
-  return DPF_OK;
-}
-
-int dpf_conv_wgrad(const float* g, const float* x, float* dw, int N, int C, int ID, int IH, int IW, int K, int QD, int QH, int QW,
-                   int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw_, void* stream) {
-  dpf_clear_error();
-  return dpf_conv_wgrad_slice(g, x, dw, N, C, ID, IH, IW, K, 0, K, QD, QH, QW, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw_, stream);
-}
-
-}  // extern "C"
-
-// generic (first-generation) weight gradient of the g-channel slice [kbeg, kbeg + kcount) of a g tensor with K channels; dw points at
-// row kbeg of dW
-int dpf_conv_wgrad_slice(const float* g, const float* x, float* dw, int N, int C, int ID, int IH, int IW, int K, int kbeg, int kcount, int QD,
-                         int QH, int QW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw_,
-                         void* stream) {   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
-  if (!g || !x || !dw || N <= 0 || C <= 0 || K <= 0) return DPF_ERR_INVALID_ARG;
+// One launch for the g channels [d.k0, d.k0 + d.K) (d.K <= 128) of a g tensor with d.Ktot channels; dw points at row d.k0 of dW and is
+// ADDED into with float atomics (zero-initialised, or the running gradient).  g [N,Ktot,QD,QH,QW] on the small grid, x on the dense grid.
+int dpf_gen1_wgrad(const float* g, const float* x, float* dw, const DpfWgradDesc& d, hipStream_t st) {
   WgP p{};
-  p.N = N; p.C = C; p.K = K; p.ID = ID; p.IH = IH; p.IW = IW; p.QD = QD; p.QH = QH; p.QW = QW;
-  p.kd = kd; p.kh = kh; p.kw = kw; p.T = kd * kh * kw;
-  p.sd = sd; p.sh = sh; p.sw = sw; p.pd = pd; p.ph = ph; p.pw = pw; p.dd = dd; p.dh = dh; p.dw = dw_;
-  if (p.T > MAXT) return DPF_ERR_UNSUPPORTED;
-  p.Ktot = K;
-  const int Kend = kbeg + kcount;
+  p.N = d.N; p.C = d.C; p.K = d.K; p.Ktot = d.Ktot; p.k0 = d.k0;
+  p.ID = d.ID; p.IH = d.IH; p.IW = d.IW; p.QD = d.QD; p.QH = d.QH; p.QW = d.QW;
+  p.kd = d.kd; p.kh = d.kh; p.kw = d.kw; p.T = d.kd * d.kh * d.kw;
+  p.sd = d.sd; p.sh = d.sh; p.sw = d.sw; p.pd = d.pd; p.ph = d.ph; p.pw = d.pw; p.dd = d.dd; p.dh = d.dh; p.dw = d.dw;
+  if (p.T > MAXT || d.K > 128) return DPF_ERR_UNSUPPORTED;
   // Dilated stride-1 convolutions: output (y, x) only meets inputs of its own residue class mod d, so the problem splits into
   // d*d interleaved dilation-1 problems.  Tiles then carry a (kh-1)-wide halo instead of (kh-1)*d, at the price of strided
   // (every d-th element) staging loads, which L2 absorbs.
   p.es = 1;
-  if (sh == 1 && sw == 1 && dh == dw_ && dh > 1) {
-    p.es = dh;
+  if (d.sh == 1 && d.sw == 1 && d.dh == d.dw && d.dh > 1) {
+    p.es = d.dh;
     p.dh = p.dw = 1;
-    dh = dw_ = 1;
   }
-  const int QHp = dpf_div_up(QH, p.es), QWp = dpf_div_up(QW, p.es);   // extent of one phase
-  for (int k0 = kbeg; k0 < Kend; k0 += 128) {   // one launch covers up to 128 g-channels (4 MFMA row tiles)
-  p.k0 = k0;
-  p.K = Kend - k0 < 128 ? Kend - k0 : 128;
-  float* dwk = dw + (long long)(k0 - kbeg) * C * p.T;
+  const int QHp = dpf_div_up(d.QH, p.es), QWp = dpf_div_up(d.QW, p.es);   // extent of one phase
   const int MT = (p.K + 31) / 32;
   const int KT = 32 * MT;
   const int WNT = 2;
   int CCW = (4 * WNT * 32) / p.T;
-  if (CCW > C) CCW = C;
+  if (CCW > d.C) CCW = d.C;
   if (CCW < 1) CCW = 1;
-  const int ext_d = (kd - 1) * dd + 1;
+  const int ext_d = (d.kd - 1) * d.dd + 1;
   const int WTH = 4, WPT = WTH * TW;
-  const int ext_h = (WTH - 1) * sh + (kh - 1) * dh + 1;
-  const int ext_w = (TW - 1) * sw + (kw - 1) * dw_ + 1;
+  const int ext_h = (WTH - 1) * d.sh + (d.kh - 1) * p.dh + 1;
+  const int ext_w = (TW - 1) * d.sw + (d.kw - 1) * p.dw + 1;
   if (ext_w > 128) return DPF_ERR_UNSUPPORTED;
   auto lds_bytes = [&](int ccw) { return (size_t)(ccw * ext_d * ext_h * ext_w + KT * (WPT + 1) + 2 * ccw * ext_d * ext_h) * sizeof(float); };
   while (CCW > 1 && lds_bytes(CCW) > 96 * 1024) --CCW;
@@ -807,25 +584,19 @@ int dpf_conv_wgrad_slice(const float* g, const float* x, float* dw, int N, int C
   p.CCW = CCW;
   p.tilesH = dpf_div_up(QHp, WTH);
   p.tilesW = dpf_div_up(QWp, TW);
-  p.ntiles = (long long)N * QD * p.es * p.es * p.tilesH * p.tilesW;
-  const int cchunks = dpf_div_up(C, CCW);
+  p.ntiles = (long long)d.N * d.QD * p.es * p.es * p.tilesH * p.tilesW;
+  const int cchunks = dpf_div_up(d.C, CCW);
   long long nchunk = 2048 / cchunks;
   if (nchunk < 1) nchunk = 1;
   if (nchunk > p.ntiles) nchunk = p.ntiles;
   if (dpf_deterministic()) nchunk = 1;     // every dW address then receives ONE atomic add per launch: order-independent (dpf_common.h)
   p.nchunk = (int)nchunk;
   const size_t lds = lds_bytes(CCW);
-  const dim3 grid((unsigned)(cchunks * p.nchunk));
-  hipStream_t st = (hipStream_t)stream;
-#define DPF_WG(M)                                                                                                           \
-  {                                                                                                                         \
-    if (lds > 48 * 1024 &&                                                                                                  \
-        hipFuncSetAttribute((const void*)conv_wgrad_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-      return DPF_ERR_LAUNCH;                                                                                                \
-    hipLaunchKernelGGL((conv_wgrad_kernel<M>), grid, dim3(256), lds, st, g, x, dwk, p);                                      \
+  const dim3 grid((unsigned)(cchunks * p.nchunk)), block(256);
+  switch (MT) {
+    case 1: return conv_launch<conv_wgrad_kernel<1>>(grid, block, lds, st, g, x, dw, p);
+    case 2: return conv_launch<conv_wgrad_kernel<2>>(grid, block, lds, st, g, x, dw, p);
+    case 3: return conv_launch<conv_wgrad_kernel<3>>(grid, block, lds, st, g, x, dw, p);
+    default: return conv_launch<conv_wgrad_kernel<4>>(grid, block, lds, st, g, x, dw, p);
   }
-  switch (MT) { case 1: DPF_WG(1); break; case 2: DPF_WG(2); break; case 3: DPF_WG(3); break; default: DPF_WG(4); break; }
-#undef DPF_WG
-  }
-  return dpf_check_launch();
 }

@@ -25,7 +25,6 @@
 // They share the tile geometry (G2P), the XCD-aware tile order and the tile epilogue (g2_epilogue: bias, accumulate, 16-byte stores,
 // fused BatchNorm statistics).
 #include "conv_internal.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -1403,35 +1402,42 @@ __global__ void igemm2_pack_bf16_kernel(const float* __restrict__ w, unsigned sh
 
 unsigned magic20(int d) { return (unsigned)(((1u << 20) + d - 1) / d); }
 
-int env_int(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
+// the arguments every launch of one kernel family shares
+template <typename W, typename P>
+struct TileLaunch {
+  const float* x; const W* wpk; const float* bias; float* out; const P& p; size_t lds; long long blocks; hipStream_t st;
+};
 
 template <int MT, int NT, int CC, bool BF = false>
-int launch_g2(const float* x, const float* wpk, const float* bias, float* out, const G2P& p, size_t lds, long long blocks, hipStream_t st) {
-  if (lds > 48 * 1024) {
-    static bool done = false;   // per instantiation
-    if (!done) {
-      if (hipFuncSetAttribute((const void*)igemm2_kernel<MT, NT, CC, BF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return DPF_ERR_LAUNCH;
-      done = true;
-    }
+int launch_g2(const TileLaunch<float, G2P>& a) {
+  return conv_launch<igemm2_kernel<MT, NT, CC, BF>>(dim3((unsigned)a.blocks), dim3(256), a.lds, a.st, a.x, a.wpk, a.bias, a.out, a.p);
+}
+// igemm3_x9_kernel<MT, NT, CC, SH, NC>: SH = split in the MFMAs' shadow, NC = components per operand
+template <int MT, int NT, int CC>
+int launch_x9(bool sh, int NC, const TileLaunch<unsigned short, G2P>& a) {
+  const dim3 grid((unsigned)a.blocks), block(256);
+  switch (2 * NC + (sh ? 1 : 0)) {
+    case 7: return conv_launch<igemm3_x9_kernel<MT, NT, CC, true, 3>>(grid, block, a.lds, a.st, a.x, a.wpk, a.bias, a.out, a.p);
+    case 6: return conv_launch<igemm3_x9_kernel<MT, NT, CC, false, 3>>(grid, block, a.lds, a.st, a.x, a.wpk, a.bias, a.out, a.p);
+    case 5: return conv_launch<igemm3_x9_kernel<MT, NT, CC, true, 2>>(grid, block, a.lds, a.st, a.x, a.wpk, a.bias, a.out, a.p);
+    case 4: return conv_launch<igemm3_x9_kernel<MT, NT, CC, false, 2>>(grid, block, a.lds, a.st, a.x, a.wpk, a.bias, a.out, a.p);
+    case 3: return conv_launch<igemm3_x9_kernel<MT, NT, CC, true, 1>>(grid, block, a.lds, a.st, a.x, a.wpk, a.bias, a.out, a.p);
+    default: return conv_launch<igemm3_x9_kernel<MT, NT, CC, false, 1>>(grid, block, a.lds, a.st, a.x, a.wpk, a.bias, a.out, a.p);
   }
-  hipLaunchKernelGGL((igemm2_kernel<MT, NT, CC, BF>), dim3((unsigned)blocks), dim3(256), lds, st, x, wpk, bias, out, p);
-  return dpf_check_launch();
+}
+template <int CC, bool BF = false>
+int launch_t2(const TileLaunch<float, T2P>& a) {
+  return conv_launch<igemm2_tr2_kernel<CC, BF>>(dim3((unsigned)a.blocks), dim3(256), a.lds, a.st, a.x, a.wpk, a.bias, a.out, a.p);
 }
 
-
-template <int MT, int NT, int CC, bool SH, int NC>
-int launch_x9(const float* x, const unsigned short* wpk, const float* bias, float* out, const G2P& p, size_t lds, long long blocks, hipStream_t st) {
-  static bool done = false;   // per instantiation
-  if (!done) {
-    if (hipFuncSetAttribute((const void*)igemm3_x9_kernel<MT, NT, CC, SH, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DPF_ERR_LAUNCH;
-    done = true;
+// (MT, NT) in {(1, 4), (1, 2), (2, 2)}, 4- or 8-channel chunks
+int launch_x9(int MT, int NT, int CC9, bool sh, int NC, const TileLaunch<unsigned short, G2P>& a) {
+  if (CC9 == 4) {
+    if (MT == 1) return NT == 4 ? launch_x9<1, 4, 4>(sh, NC, a) : launch_x9<1, 2, 4>(sh, NC, a);
+    return launch_x9<2, 2, 4>(sh, NC, a);
   }
-  hipLaunchKernelGGL((igemm3_x9_kernel<MT, NT, CC, SH, NC>), dim3((unsigned)blocks), dim3(256), lds, st, x, wpk, bias, out, p);
-  return dpf_check_launch();
+  if (MT == 1) return NT == 4 ? launch_x9<1, 4, 8>(sh, NC, a) : launch_x9<1, 2, 8>(sh, NC, a);
+  return launch_x9<2, 2, 8>(sh, NC, a);
 }
 
 // One launch of igemm3_x9_kernel for the output channels [k_off, k_off + kn) of the launch `d` (kn <= 64); `p` carries the
@@ -1440,20 +1446,19 @@ int launch_x9(const float* x, const unsigned short* wpk, const float* bias, floa
 // count, so that every slice picks the same depth split / tile order and the shared BatchNorm statistics slab has one row numbering.
 int x9_try(const float* x, const float* w, const float* bias, float* out, float* ws, const DpfConvDesc& d, const G2P& p, int k_off, int kn, int NT,
            DpfConvStats* stats, hipStream_t st, int NC, int mt_fit = 0) {
-  static const int x9_on = env_int("DPF_IGEMM3", 1), x9_min_c = 8, x9_cc = env_int("DPF_IGEMM3_CC", 0),
-                   x9_sh = env_int("DPF_IGEMM3_SH", -1);
+  const ConvEnv& env = conv_env();
+  constexpr int x9_min_c = 8;
   const int T = d.kd * d.kh * d.kw, MT = (kn + 31) / 32, TH = 4 * NT;
-  if (!x9_on || (NC >= 2 && !dpf_conv_f32_x9()) || MT > 2 || NT * MT > 4 || d.C < x9_min_c) return DPF_ERR_UNSUPPORTED;
+  if (!env.igemm3 || (NC >= 2 && !dpf_conv_f32_x9()) || MT > 2 || NT * MT > 4 || d.C < x9_min_c) return DPF_ERR_UNSUPPORTED;
   G2P q = p;
   q.K = kn; q.k0 = d.k0 + k_off;
   // 2-D layers dilated along H: a tile takes the rows of ONE dilation phase (dh apart), so its patch is thp + kh - 1 image rows fetched dh
   // apart instead of thp + (kh - 1) * dh consecutive ones (dilation 8: 18 rows instead of 32 -- within the staging budget)
-  static const int rstep_on = env_int("DPF_IGEMM3_RSTEP", 1);
-  q.rstep = (rstep_on && d.kd == 1 && d.kh > 1 && d.dh > 1) ? d.dh : 1;
+  q.rstep = (env.igemm3_rstep && d.kd == 1 && d.kh > 1 && d.dh > 1) ? d.dh : 1;
   const int dhl = d.dh / q.rstep;
   // chunk layout with the fewest tap slots (4 channels x tap quadruples or 8 channels x tap pairs); ties: the smaller patch
   int CC9 = ((T + 1) / 2) * 2 < ((T + 3) / 4) * 4 ? 8 : 4;
-  if (x9_cc == 4 || x9_cc == 8) CC9 = x9_cc;
+  if (env.igemm3_cc == 4 || env.igemm3_cc == 8) CC9 = env.igemm3_cc;
   const int NU9 = CC9 == 4 ? 2 : 1, PB9 = 2 * NC * CC9;
   // depth split: among the splits whose patch fits the per-thread unit budget, the one with the fewest staged rows
   auto set_pz = [&](int pz) {
@@ -1468,7 +1473,7 @@ int x9_try(const float* x, const float* w, const float* bias, float* out, float*
   const int TG = (T + 16 / CC9 - 1) / (16 / CC9);
   int best = 0, best_units = 1 << 30, sh = 0;
   for (int shc : {1, 0}) {                                     // split in the MFMAs' shadow (two weight buffers) when the LDS has room
-    if (best || (x9_sh >= 0 && shc != x9_sh)) continue;
+    if (best || (env.igemm3_sh >= 0 && shc != env.igemm3_sh)) continue;
     for (int pz : {1, 2, 4}) {
       if (!(pz == 1 || (d.kd > 1 && pz <= TH / 2 && pz <= d.OD))) continue;
       const int units = set_pz(pz);
@@ -1513,43 +1518,12 @@ int x9_try(const float* x, const float* w, const float* bias, float* out, float*
                        d.C);
   if (dpf_check_launch() != DPF_OK) return DPF_ERR_LAUNCH;
   if (stats) stats->parts = (int)nt9;
-  const long long blocks9 = 8LL * q.cpx;
-#define X9L(M, N_, C_)                                                                                                   \
-  do {                                                                                                                 \
-    if (NC == 3) return sh ? launch_x9<M, N_, C_, true, 3>(x, wp, bias, out, q, lds9, blocks9, st)                      \
-                           : launch_x9<M, N_, C_, false, 3>(x, wp, bias, out, q, lds9, blocks9, st);                     \
-    if (NC == 2) return sh ? launch_x9<M, N_, C_, true, 2>(x, wp, bias, out, q, lds9, blocks9, st)                      \
-                           : launch_x9<M, N_, C_, false, 2>(x, wp, bias, out, q, lds9, blocks9, st);                     \
-    return sh ? launch_x9<M, N_, C_, true, 1>(x, wp, bias, out, q, lds9, blocks9, st)                                   \
-              : launch_x9<M, N_, C_, false, 1>(x, wp, bias, out, q, lds9, blocks9, st);                                  \
-  } while (0)
-  if (CC9 == 4) {
-    if (MT == 1) { if (NT == 4) X9L(1, 4, 4); X9L(1, 2, 4); }
-    X9L(2, 2, 4);
-  }
-  if (MT == 1) { if (NT == 4) X9L(1, 4, 8); X9L(1, 2, 8); }
-  X9L(2, 2, 8);
-#undef X9L
-}
-}  // namespace
-
-
-namespace {
-template <int CC, bool BF = false>
-int launch_t2(const float* x, const float* wpk, const float* bias, float* out, const T2P& p, size_t lds, hipStream_t st) {
-  static bool done = false;
-  if (lds > 48 * 1024 && !done) {
-    if (hipFuncSetAttribute((const void*)igemm2_tr2_kernel<CC, BF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DPF_ERR_LAUNCH;
-    done = true;
-  }
-  hipLaunchKernelGGL((igemm2_tr2_kernel<CC, BF>), dim3(8u * p.cpx), dim3(256), lds, st, x, wpk, bias, out, p);
-  return dpf_check_launch();
+  return launch_x9(MT, NT, CC9, sh != 0, NC, {x, wp, bias, out, q, lds9, 8LL * q.cpx, st});
 }
 
 // stride-2 transposed 3x3x3 (pad 1): loops over 32-channel output slices
 int igemm2_tr2(const float* x, const float* w, const float* bias, float* out, float* ws, const DpfConvDesc& d, hipStream_t st) {
-  static const int enabled = env_int("DPF_IGEMM2_TR2", 1), cc_over = 0;
-  if (!enabled) return DPF_ERR_UNSUPPORTED;
+  if (!conv_env().igemm2_tr2) return DPF_ERR_UNSUPPORTED;
   if (d.kd != 3 || d.kh != 3 || d.kw != 3 || d.sd != 2 || d.sh != 2 || d.sw != 2 || d.pd != 1 || d.ph != 1 || d.pw != 1 || d.dd != 1 ||
       d.dh != 1 || d.dw != 1)
     return DPF_ERR_UNSUPPORTED;
@@ -1558,7 +1532,7 @@ int igemm2_tr2(const float* x, const float* w, const float* bias, float* out, fl
   const long long x_chan = (long long)d.ID * d.IH * d.IW;
   if (9 * x_chan >= (1LL << 30)) return DPF_ERR_UNSUPPORTED;
   const bool bf = dpf_conv_operand_bf16() != 0;
-  const int CC = bf ? 8 : ((cc_over == 4 || cc_over == 8 || cc_over == 2) ? cc_over : 8);
+  const int CC = 8;        // channels per chunk (the kernel is also compiled for 4 and 2; neither is chosen)
   T2P p{};
   p.N = d.N; p.C = d.C; p.Ktot = d.Ktot;
   p.ID = d.ID; p.IH = d.IH; p.IW = d.IW; p.OD = d.OD; p.OH = d.OH; p.OW = d.OW;
@@ -1574,7 +1548,7 @@ int igemm2_tr2(const float* x, const float* w, const float* bias, float* out, fl
   p.ntiles = (int)ntiles;
   p.cpx = (int)((ntiles + 7) / 8);
   p.mSR = magic20(p.SR); p.mRPC = magic20(p.rpc); p.mEH = magic20(5);
-  p.vec = env_int("DPF_G2_VEC_STORE", 1);
+  p.vec = conv_env().g2_vec_store;
   const size_t lds = 2 * (size_t)(CC * p.chanStride + 4 * p.nwseg) * sizeof(float);
   for (int k0 = 0; k0 < d.K; k0 += 32) {
     const int Kc = d.K - k0 < 32 ? d.K - k0 : 32;
@@ -1586,17 +1560,243 @@ int igemm2_tr2(const float* x, const float* w, const float* bias, float* out, fl
     else
       hipLaunchKernelGGL(igemm2_pack_kernel, dim3(dpf_ew_grid(total)), dim3(256), 0, st, w, ws, d.wA, d.wB, 27, 32, CC, p.nchunks, d.mode, p.k0, Kc, d.C);
     if (dpf_check_launch() != DPF_OK) return DPF_ERR_LAUNCH;
+    const TileLaunch<float, T2P> a{x, ws, bias, out, p, lds, 8LL * p.cpx, st};
     int rc;
-    if (bf) {
-      rc = launch_t2<8, true>(x, ws, bias, out, p, lds, st);
-      if (rc != DPF_OK) return rc;
-      continue;
-    }
-    switch (CC) { case 2: rc = launch_t2<2>(x, ws, bias, out, p, lds, st); break; case 4: rc = launch_t2<4>(x, ws, bias, out, p, lds, st); break;
-                  default: rc = launch_t2<8>(x, ws, bias, out, p, lds, st); break; }
+    if (bf) rc = launch_t2<8, true>(a);
+    else switch (CC) { case 2: rc = launch_t2<2>(a); break; case 4: rc = launch_t2<4>(a); break; default: rc = launch_t2<8>(a); break; }
     if (rc != DPF_OK) return rc;
   }
   return DPF_OK;
+}
+
+// ---- dpf_igemm2_conv, step by step.  G2Plan: the kernel's parameters and the host-side choices the steps hand on.
+struct G2Plan {
+  G2P p;
+  int T, MT, KT;
+  int NT;           // position tiles (of 4 rows) per workgroup
+  int single;       // bf16 kernel: 1 = one LDS buffer
+  bool bf_mode;     // operand precision "bf16" asked for
+  bool bf;          // ... and igemm2's bf16 kernel can take the shape
+  int CC;           // channels per chunk
+};
+
+bool g2_eligible(const float* x, const float* ws, const DpfConvDesc& d, const DpfConvStats* stats) {
+  const int T = d.kd * d.kh * d.kw;
+  if (!conv_env().igemm2 || T > MAXT || d.K > 128) return false;
+  if ((d.IW & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(ws) & 15)) return false;
+  if (9LL * d.ID * d.IH * d.IW >= (1LL << 30)) return false;     // per-lane 32-bit source offsets within a chunk
+  if (T == 1 && !conv_env().igemm2_1x1) return false;           // pointwise convs (HBM-bound): 1.8x the generic kernel
+  if (stats && (d.transposed || d.Ktot != d.K)) return false;
+  return !(d.accumulate && d.transposed && (d.sd != 1 || d.sh != 1 || d.sw != 1));   // class-fused kernel: plain stores
+}
+
+// operand precision "bf16" (dpf_set_conv_operand_precision): 8-channel chunks; 16 position rows per workgroup when two buffers of that
+// patch fit the LDS, else 8.  Sets NT, single and bf (false when igemm2's bf16 kernel cannot take the shape, e.g. stride-2 forward
+// patches: the exact-f32 kernel then runs).
+void g2_bf16_tile(const DpfConvDesc& d, G2Plan& g) {
+  const int MT = g.MT;
+  g.NT = MT == 1 ? 4 : 2;
+  g.bf_mode = g.bf = dpf_conv_operand_bf16() != 0 && g.T > 1;
+  if (!g.bf) return;
+  auto patch_for = [&](int nt) {      // bytes of an 8-channel fp32 patch
+    const int sxh = d.transposed ? 1 : d.sh, sxw = d.transposed ? 1 : d.sw;
+    const int e0w = d.transposed ? d.pw - (d.kw - 1) * d.dw : -d.pw;
+    const int ext_d = (d.kd - 1) * d.dd + 1, ext_h = (4 * nt - 1) * sxh + (d.kh - 1) * d.dh + 1, ext_w = 31 * sxw + (d.kw - 1) * d.dw + 1;
+    const int rs = ((((e0w % 4) + 4) % 4 + ext_w + 3) / 4) * 4;
+    return (long long)8 * ext_d * ext_h * rs * 4;
+  };
+  const long long wbytes = (long long)g.T * g.KT * 16;
+  // (rows per workgroup, one or two LDS buffers): the candidate with the most resident workgroups per CU wins (LDS and the
+  // register budget of the instantiation; more than 3 buys nothing) -- at equal residency two buffers beat one and 16 rows beat 8
+  // (less halo).  tools/conv_bf16_bench.py: the 3-D K = 32 convs run 2x faster on 8 rows x 1 buffer (3 resident) than on 2 buffers.
+  auto occ_regs = [&](int nt) {
+    const int est = MT * nt * 16 + 2 * (2 * MT + 4 * nt) + 2 * NLD + 44;
+    return est <= 128 ? 4 : (est <= 168 ? 3 : 2);
+  };
+  int best = -1;
+  for (int nt : {4, 2}) {
+    if ((nt == 4 && MT > 2) || patch_for(nt) > 2LL * NLD * 256 * 16) continue;
+    for (int single = 0; single < 2; ++single) {
+      const long long lds_c = (single ? 1 : 2) * (patch_for(nt) + wbytes);
+      if (lds_c > 160 * 1024) continue;
+      int resid = (int)(160 * 1024 / lds_c);
+      if (resid > occ_regs(nt)) resid = occ_regs(nt);
+      if (resid > 3) resid = 3;
+      const int score = resid * 4 + (single ? 0 : 2) + (nt == 4 ? 1 : 0);
+      if (score > best) { best = score; g.NT = nt; g.single = single; }
+    }
+  }
+  g.bf = best >= 0;
+}
+
+// tile geometry and the depth split of TH = 4 NT position rows
+void g2_geometry(const DpfConvDesc& d, const float* out, G2Plan& g) {
+  G2P& p = g.p;
+  const int TH = 4 * g.NT;
+  p.N = d.N; p.C = d.C; p.K = d.K; p.Ktot = d.Ktot; p.k0 = d.k0;
+  p.ID = d.ID; p.IH = d.IH; p.IW = d.IW; p.OD = d.OD; p.OH = d.OH; p.OW = d.OW;
+  p.T = g.T;
+  p.accum = d.accumulate;
+  p.rstep = 1;
+  p.vec = conv_env().g2_vec_store && (d.OW & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  if (!d.transposed) {
+    p.sxd = d.sd; p.sxh = d.sh; p.sxw = d.sw;
+    p.e0d = -d.pd; p.e0h = -d.ph; p.e0w = -d.pw;
+  } else {
+    p.sxd = p.sxh = p.sxw = 1;
+    p.e0d = d.pd - (d.kd - 1) * d.dd; p.e0h = d.ph - (d.kh - 1) * d.dh; p.e0w = d.pw - (d.kw - 1) * d.dw;
+  }
+  const int ext_w = 31 * p.sxw + (d.kw - 1) * d.dw + 1;
+  p.colshift = ((p.e0w % 4) + 4) % 4;
+  p.RS = ((p.colshift + ext_w + 3) / 4) * 4;
+  // depth tiles: pz output planes x TH / pz rows.  A 3-plane kernel stages kd - 1 halo planes per tile, so one output plane per tile
+  // fetches every input plane three times (16 x 32 tile: 3 x 18 = 54 patch rows per 16 position rows; 4 planes x 4 rows: 6 x 6 = 36).
+  // The split with the fewest staged rows per position row wins; DPF_G2_PZ = 1 | 2 | 4 forces one.
+  const int pz_over = conv_env().g2_pz;
+  auto pz_ok = [&](int pz) { return pz == 1 || (d.kd > 1 && pz <= TH / 2 && pz <= d.OD); };
+  auto pz_cost = [&](int pz) {
+    const int thp = TH / pz;
+    return (double)((pz - 1) * p.sxd + (d.kd - 1) * d.dd + 1) * ((thp - 1) * p.sxh + (d.kh - 1) * d.dh + 1) / (double)(pz * thp);
+  };
+  p.pz = 1;
+  for (int pz : {2, 4})
+    if (pz_ok(pz) && pz_cost(pz) < pz_cost(p.pz) - 1e-9) p.pz = pz;
+  if ((pz_over == 1 || pz_over == 2 || pz_over == 4) && pz_ok(pz_over)) p.pz = pz_over;
+  p.thp = TH / p.pz;
+  p.thp_shift = 0;
+  while ((1 << p.thp_shift) < p.thp) ++p.thp_shift;
+  p.odt = dpf_div_up(d.OD, p.pz);
+  p.ext_d = (p.pz - 1) * p.sxd + (d.kd - 1) * d.dd + 1;
+  p.ext_h = (p.thp - 1) * p.sxh + (d.kh - 1) * d.dh + 1;
+  p.planeStride = p.ext_h * p.RS;
+  p.SR = p.RS / 4;
+  p.rpc = p.ext_d * p.ext_h;
+  p.chanStride = p.rpc * p.RS;
+}
+
+// how the LDS read offset moves from tap t to tap t + 1: two bits per tap (0: along W, 1: next row, 2: next plane, 3: last tap)
+void g2_tap_steps(const DpfConvDesc& d, G2P& p) {
+  const int sgn = d.transposed ? -1 : 1;
+  const int stepA = sgn * d.dd * p.ext_h * p.RS, stepB = sgn * d.dh * p.RS;
+  p.stepC = sgn * d.dw;
+  p.incB = stepB - (d.kw - 1) * p.stepC;
+  p.incA = stepA - (d.kh - 1) * stepB - (d.kw - 1) * p.stepC;
+  p.steps = 0;
+  for (int t = 0; t < p.T; ++t) {
+    const int c = t % d.kw, b = (t / d.kw) % d.kh;
+    const unsigned long long code = t == p.T - 1 ? 3 : (c + 1 < d.kw ? 0 : (b + 1 < d.kh ? 1 : 2));
+    p.steps |= code << (2 * t);
+  }
+  p.tap0 = d.transposed ? ((d.kd - 1) * d.dd * p.ext_h + (d.kh - 1) * d.dh) * p.RS + (d.kw - 1) * d.dw : 0;
+}
+
+// igemm3_x9_kernel: stride-1 launches, output channels in slices of at most 64 -- fp32 products from exact bf16 splits, or (operand
+// precision "bf16") the operands rounded to bf16.  DPF_ERR_UNSUPPORTED: nothing launched, igemm2_kernel takes the launch.
+// (bf16 operands, 2-D kernels with more than 64 output channels: igemm2's bf16 kernel stages the patch once for all of them and is faster)
+int g2_x9_route(const float* x, const float* w, const float* bias, float* out, float* ws, const DpfConvDesc& d, const G2Plan& g, DpfConvStats* stats,
+                hipStream_t st) {
+  const G2P& p = g.p;
+  if (!(g.T > 4 && p.sxd == 1 && p.sxh == 1 && p.sxw == 1 && (!g.bf_mode || (conv_env().igemm3_bf && !(d.K > 64 && d.kd == 1)))))
+    return DPF_ERR_UNSUPPORTED;
+  const int nc = g.bf_mode ? 1 : dpf_conv_f32_nc();
+  // (8-row tiles for <= 32 output channels too, three resident workgroups: measured slower)
+  if (d.K <= 64) return x9_try(x, w, bias, out, ws, d, p, 0, d.K, g.MT == 1 ? 4 : 2, stats, st, nc);
+  for (int k_off = 0; k_off < d.K; k_off += 64) {
+    const int rc = x9_try(x, w, bias, out, ws, d, p, k_off, d.K - k_off < 64 ? d.K - k_off : 64, 2, stats, st, nc, 2);
+    if (rc == DPF_ERR_UNSUPPORTED && k_off == 0) return rc;      // nothing launched yet
+    if (rc != DPF_OK) return rc == DPF_ERR_UNSUPPORTED ? DPF_ERR_LAUNCH : rc;
+  }
+  return DPF_OK;
+}
+
+// igemm2_kernel's LDS: one buffer of the fp32 kernel with `cc` channels per chunk / of the bf16 kernel (8 channels)
+size_t g2_buf_bytes(const G2Plan& g, int cc) { return (size_t)(cc * g.p.chanStride + g.T * cc * g.KT) * sizeof(float); }
+size_t g2_bf_buf_bytes(const G2Plan& g) { return (size_t)8 * g.p.chanStride * sizeof(float) + (size_t)g.T * g.KT * 16; }
+
+// channels per chunk: the largest of {8, 4, 2} whose two buffers leave room for >= 3 resident workgroups.  false: no chunk fits
+bool g2_chunk(const DpfConvDesc& d, G2Plan& g) {
+  constexpr int lds_target = 53 * 1024;
+  const G2P& p = g.p;
+  auto nseg_of = [&](int cc) { return cc * p.rpc * p.SR; };
+  auto fits = [&](int cc) { return 2 * g2_buf_bytes(g, cc) <= (size_t)lds_target && nseg_of(cc) <= NLD * 256; };
+  // Launches that fill the chip several times over run best with the smallest chunk (more resident workgroups hide the DMA
+  // latency: +1..5 % on every large shape, tools/conv_shape_bench.py sweep); small launches (< 2 tiles per CU) keep the larger
+  // chunks, which shorten their few workgroups' barrier chains.
+  const long long ntiles_est = (long long)d.N * p.odt * dpf_div_up(d.OH, p.thp) * dpf_div_up(d.OW, 32);
+  g.CC = g.bf ? 8 : (ntiles_est >= 512 && fits(2)) ? 2 : fits(8) ? 8 : fits(4) ? 4 : 2;
+  return g.bf ? (nseg_of(8) <= 2 * NLD * 256 && 2 * g2_bf_buf_bytes(g) <= 160 * 1024)
+              : (nseg_of(g.CC) <= NLD * 256 && 2 * g2_buf_bytes(g, g.CC) <= 160 * 1024);
+}
+
+// igemm2_kernel<MT, NT, CC, BF>: 16-row tiles (NT = 4) for at most two row tiles; the bf16 kernel always takes 8-channel chunks
+int launch_g2(int MT, int NT, int CC, bool bf, const TileLaunch<float, G2P>& a) {
+  if (bf) {
+    if (NT == 4) return MT == 1 ? launch_g2<1, 4, 8, true>(a) : launch_g2<2, 4, 8, true>(a);
+    switch (MT) {
+      case 1: return launch_g2<1, 2, 8, true>(a);
+      case 2: return launch_g2<2, 2, 8, true>(a);
+      case 3: return launch_g2<3, 2, 8, true>(a);
+      default: return launch_g2<4, 2, 8, true>(a);
+    }
+  }
+  const int cc = CC == 8 ? 0 : (CC == 4 ? 1 : 2);
+  switch ((NT == 4 ? (MT == 1 ? 0 : 1) : (MT < 4 ? MT + 1 : 5)) * 3 + cc) {
+    case 0: return launch_g2<1, 4, 8>(a);
+    case 1: return launch_g2<1, 4, 4>(a);
+    case 2: return launch_g2<1, 4, 2>(a);
+    case 3: return launch_g2<2, 4, 8>(a);
+    case 4: return launch_g2<2, 4, 4>(a);
+    case 5: return launch_g2<2, 4, 2>(a);
+    case 6: return launch_g2<1, 2, 8>(a);
+    case 7: return launch_g2<1, 2, 4>(a);
+    case 8: return launch_g2<1, 2, 2>(a);
+    case 9: return launch_g2<2, 2, 8>(a);
+    case 10: return launch_g2<2, 2, 4>(a);
+    case 11: return launch_g2<2, 2, 2>(a);
+    case 12: return launch_g2<3, 2, 8>(a);
+    case 13: return launch_g2<3, 2, 4>(a);
+    case 14: return launch_g2<3, 2, 2>(a);
+    case 15: return launch_g2<4, 2, 8>(a);
+    case 16: return launch_g2<4, 2, 4>(a);
+    default: return launch_g2<4, 2, 2>(a);
+  }
+}
+
+// pack the weights, point the kernel at the statistics slab, launch
+int g2_pack_and_launch(const float* x, const float* w, const float* bias, float* out, float* ws, const DpfConvDesc& d, G2Plan& g, DpfConvStats* stats,
+                       hipStream_t st) {
+  G2P& p = g.p;
+  const int T = g.T, KT = g.KT, CC = g.CC;
+  p.nseg = CC * p.rpc * p.SR;
+  p.nwseg = g.bf ? T * KT : T * CC * KT / 4;
+  p.nchunks = (d.C + CC - 1) / CC;
+  p.tilesH = dpf_div_up(d.OH, p.thp);
+  p.tilesW = dpf_div_up(d.OW, 32);
+  p.mSR = magic20(p.SR); p.mRPC = magic20(p.rpc); p.mEH = magic20(p.ext_h);
+  if ((long long)(g.bf ? 2 : 1) * NLD * 256 * (p.SR > p.rpc ? p.SR : p.rpc) >= (1LL << 20)) return DPF_ERR_UNSUPPORTED;   // multiply-shift exactness
+  const long long ntiles = (long long)d.N * p.odt * p.tilesH * p.tilesW;
+  if (ntiles <= 0 || ntiles > 0x3fffffffLL) return DPF_ERR_INVALID_ARG;
+  p.ntiles = (int)ntiles;
+  p.cpx = (int)((ntiles + 7) / 8);
+
+  const long long total = (long long)p.nchunks * T * CC * KT + ZPAGE;
+  if (g.bf)
+    hipLaunchKernelGGL(igemm2_pack_bf16_kernel, dim3(dpf_ew_grid(total + ZPAGE)), dim3(256), 0, st, w, reinterpret_cast<unsigned short*>(ws), d.wA,
+                       d.wB, T, KT, p.nchunks, d.mode, d.k0, d.K, d.C);
+  else
+    hipLaunchKernelGGL(igemm2_pack_kernel, dim3(dpf_ew_grid(total)), dim3(256), 0, st, w, ws, d.wA, d.wB, T, KT, CC, p.nchunks, d.mode, d.k0, d.K, d.C);
+  if (dpf_check_launch() != DPF_OK) return DPF_ERR_LAUNCH;
+
+  p.single = g.single;
+  const size_t lds = g.bf ? (p.single ? 1 : 2) * g2_bf_buf_bytes(g) : 2 * g2_buf_bytes(g, CC);
+  p.stats = nullptr;
+  if (stats) {
+    if (ntiles * d.K * 2 > stats->capacity_doubles || lds < (size_t)4 * 2 * g.MT * 16 * 2 * sizeof(double)) return DPF_ERR_UNSUPPORTED;
+    p.stats = stats->slab;
+    p.statsK = d.K; p.statsk0 = 0;
+    stats->parts = (int)ntiles;
+  }
+  return launch_g2(g.MT, g.NT, CC, g.bf, {x, ws, bias, out, p, lds, 8LL * p.cpx, st});
 }
 }  // namespace
 
@@ -1611,217 +1811,19 @@ long long dpf_igemm2_workspace_floats(int T, int reduce, int outc) {
 
 int dpf_igemm2_conv(const float* x, const float* w, const float* bias, float* out, float* ws, const DpfConvDesc& d, hipStream_t st,
                     DpfConvStats* stats) {
-  static const int enabled = env_int("DPF_IGEMM2", 1);
-  if (!enabled) return DPF_ERR_UNSUPPORTED;
-  const int T = d.kd * d.kh * d.kw;
-  if (T > MAXT || d.K > 128) return DPF_ERR_UNSUPPORTED;
-  if ((d.IW & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(ws) & 15)) return DPF_ERR_UNSUPPORTED;
-  const long long x_chan = (long long)d.ID * d.IH * d.IW;
-  if (9 * x_chan >= (1LL << 30)) return DPF_ERR_UNSUPPORTED;      // per-lane 32-bit source offsets within a chunk
-  if (T == 1 && !env_int("DPF_IGEMM2_1x1", 1)) return DPF_ERR_UNSUPPORTED;   // pointwise convs (HBM-bound): 1.8x the generic kernel
-  if (stats && (d.transposed || d.Ktot != d.K)) return DPF_ERR_UNSUPPORTED;
-  if (d.accumulate && d.transposed && (d.sd != 1 || d.sh != 1 || d.sw != 1)) return DPF_ERR_UNSUPPORTED;   // class-fused kernel: plain stores
+  if (!g2_eligible(x, ws, d, stats)) return DPF_ERR_UNSUPPORTED;
   if (d.transposed && (d.sd != 1 || d.sh != 1 || d.sw != 1)) return igemm2_tr2(x, w, bias, out, ws, d, st);
-
-  const int MT = (d.K + 31) / 32, KT = 32 * MT;
-  static const int nt_over = 0, cc_over = 0, lds_target = 53 * 1024;
-  int NT = MT == 1 ? 4 : 2;
-  if (nt_over == 2 || (nt_over == 4 && MT <= 2)) NT = nt_over;
-  // operand precision "bf16" (dpf_set_conv_operand_precision): 8-channel chunks; 16 position rows per workgroup when two buffers
-  // of that patch fit the LDS, else 8
-  bool bf = dpf_conv_operand_bf16() != 0 && T > 1;
-  const bool bf_mode = bf;                                        // (bf is cleared below when the igemm2 bf16 kernel cannot take the shape)
-  static const int bf3_on = env_int("DPF_IGEMM3_BF", 1);
-  int p_single = 0;
-  if (bf) {
-    auto patch_for = [&](int nt) {      // bytes of an 8-channel fp32 patch
-      const int sxh = d.transposed ? 1 : d.sh, sxw = d.transposed ? 1 : d.sw;
-      const int e0w = d.transposed ? d.pw - (d.kw - 1) * d.dw : -d.pw;
-      const int ext_d = (d.kd - 1) * d.dd + 1, ext_h = (4 * nt - 1) * sxh + (d.kh - 1) * d.dh + 1, ext_w = 31 * sxw + (d.kw - 1) * d.dw + 1;
-      const int rs = ((((e0w % 4) + 4) % 4 + ext_w + 3) / 4) * 4;
-      return (long long)8 * ext_d * ext_h * rs * 4;
-    };
-    const long long wbytes = (long long)T * KT * 16;
-    // (rows per workgroup, one or two LDS buffers): the candidate with the most resident workgroups per CU wins (LDS and the
-    // register budget of the instantiation; more than 3 buys nothing) -- at equal residency two buffers beat one and 16 rows beat 8
-    // (less halo).  tools/conv_bf16_bench.py: the 3-D K = 32 convs run 2x faster on 8 rows x 1 buffer (3 resident) than on 2 buffers.
-    static const int single_over = -1;
-    auto occ_regs = [&](int nt) {
-      const int est = MT * nt * 16 + 2 * (2 * MT + 4 * nt) + 2 * NLD + 44;
-      return est <= 128 ? 4 : (est <= 168 ? 3 : 2);
-    };
-    int best = -1;
-    for (int nt : {4, 2}) {
-      if ((nt == 4 && MT > 2) || patch_for(nt) > 2LL * NLD * 256 * 16) continue;
-      if ((nt_over == 2 || nt_over == 4) && nt != nt_over) continue;
-      for (int single = 0; single < 2; ++single) {
-        if (single_over >= 0 && single != single_over) continue;
-        const long long lds_c = (single ? 1 : 2) * (patch_for(nt) + wbytes);
-        if (lds_c > 160 * 1024) continue;
-        int resid = (int)(160 * 1024 / lds_c);
-        if (resid > occ_regs(nt)) resid = occ_regs(nt);
-        if (resid > 3) resid = 3;
-        const int score = resid * 4 + (single ? 0 : 2) + (nt == 4 ? 1 : 0);
-        if (score > best) { best = score; NT = nt; p_single = single; }
-      }
-    }
-    if (best < 0) { bf = false; p_single = 0; }     // e.g. stride-2 forward patches: exact-f32 kernel below
-    if (!bf) { NT = MT == 1 ? 4 : 2; if (nt_over == 2 || (nt_over == 4 && MT <= 2)) NT = nt_over; }
-  }
-  const int TH = 4 * NT;
-
-  G2P p{};
-  p.N = d.N; p.C = d.C; p.K = d.K; p.Ktot = d.Ktot; p.k0 = d.k0;
-  p.ID = d.ID; p.IH = d.IH; p.IW = d.IW; p.OD = d.OD; p.OH = d.OH; p.OW = d.OW;
-  p.T = T;
-  p.accum = d.accumulate;
-  p.rstep = 1;
-  static const int vec_on = env_int("DPF_G2_VEC_STORE", 1);
-  p.vec = vec_on && (d.OW & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-  int ext_w;
-  if (!d.transposed) {
-    p.sxd = d.sd; p.sxh = d.sh; p.sxw = d.sw;
-    p.e0d = -d.pd; p.e0h = -d.ph; p.e0w = -d.pw;
-  } else {
-    p.sxd = p.sxh = p.sxw = 1;
-    p.e0d = d.pd - (d.kd - 1) * d.dd; p.e0h = d.ph - (d.kh - 1) * d.dh; p.e0w = d.pw - (d.kw - 1) * d.dw;
-  }
-  ext_w = 31 * p.sxw + (d.kw - 1) * d.dw + 1;
-  p.colshift = ((p.e0w % 4) + 4) % 4;
-  p.RS = ((p.colshift + ext_w + 3) / 4) * 4;
-  // depth tiles: pz output planes x TH / pz rows.  A 3-plane kernel stages kd - 1 halo planes per tile, so one output plane per tile
-  // fetches every input plane three times (16 x 32 tile: 3 x 18 = 54 patch rows per 16 position rows; 4 planes x 4 rows: 6 x 6 = 36).
-  // The split with the fewest staged rows per position row wins; DPF_G2_PZ = 1 | 2 | 4 forces one.
-  {
-    static const int pz_over = env_int("DPF_G2_PZ", 0);
-    auto pz_ok = [&](int pz) { return pz == 1 || (d.kd > 1 && pz <= TH / 2 && pz <= d.OD); };
-    auto pz_cost = [&](int pz) {
-      const int thp = TH / pz;
-      return (double)((pz - 1) * p.sxd + (d.kd - 1) * d.dd + 1) * ((thp - 1) * p.sxh + (d.kh - 1) * d.dh + 1) / (double)(pz * thp);
-    };
-    int best_pz = 1;
-    for (int pz : {2, 4})
-      if (pz_ok(pz) && pz_cost(pz) < pz_cost(best_pz) - 1e-9) best_pz = pz;
-    if ((pz_over == 1 || pz_over == 2 || pz_over == 4) && pz_ok(pz_over)) best_pz = pz_over;
-    p.pz = best_pz;
-    p.thp = TH / p.pz;
-    p.thp_shift = 0;
-    while ((1 << p.thp_shift) < p.thp) ++p.thp_shift;
-    p.odt = dpf_div_up(d.OD, p.pz);
-  }
-  p.ext_d = (p.pz - 1) * p.sxd + (d.kd - 1) * d.dd + 1;
-  p.ext_h = (p.thp - 1) * p.sxh + (d.kh - 1) * d.dh + 1;
-  p.planeStride = p.ext_h * p.RS;
-  p.SR = p.RS / 4;
-  p.rpc = p.ext_d * p.ext_h;
-  p.chanStride = p.rpc * p.RS;
-  {
-    const int sgn = d.transposed ? -1 : 1;
-    const int stepA = sgn * d.dd * p.ext_h * p.RS, stepB = sgn * d.dh * p.RS;
-    p.stepC = sgn * d.dw;
-    p.incB = stepB - (d.kw - 1) * p.stepC;
-    p.incA = stepA - (d.kh - 1) * stepB - (d.kw - 1) * p.stepC;
-    p.steps = 0;
-    for (int t = 0; t < T; ++t) {
-      const int c = t % d.kw, b = (t / d.kw) % d.kh;
-      const unsigned long long code = t == T - 1 ? 3 : (c + 1 < d.kw ? 0 : (b + 1 < d.kh ? 1 : 2));
-      p.steps |= code << (2 * t);
-    }
-    p.tap0 = d.transposed ? ((d.kd - 1) * d.dd * p.ext_h + (d.kh - 1) * d.dh) * p.RS + (d.kw - 1) * d.dw : 0;
-  }
-  // ---- igemm3_x9_kernel: stride-1 launches, output channels in slices of at most 64 -- fp32 products from exact bf16 splits, or (operand
-  //      precision "bf16") the operands rounded to bf16
-  // (bf16 operands, 2-D kernels with more than 64 output channels: igemm2's bf16 kernel stages the patch once for all of them and is faster)
-  if (T > 4 && p.sxd == 1 && p.sxh == 1 && p.sxw == 1 && (!bf_mode || (bf3_on && !(d.K > 64 && d.kd == 1)))) {
-    const int nc = bf_mode ? 1 : dpf_conv_f32_nc();
-    if (d.K <= 64) {
-      constexpr int nt3 = 0;       // (2 = 8-row tiles for <= 32 output channels too, three resident workgroups: measured slower)
-      const int rc = x9_try(x, w, bias, out, ws, d, p, 0, d.K, MT == 1 ? ((nt3 == 2 || (nt3 == 12 && d.kd == 1)) ? 2 : 4) : 2, stats, st, nc);
-      if (rc != DPF_ERR_UNSUPPORTED) return rc;
-    } else {
-      for (int k_off = 0; k_off < d.K; k_off += 64) {
-        const int rc = x9_try(x, w, bias, out, ws, d, p, k_off, d.K - k_off < 64 ? d.K - k_off : 64, 2, stats, st, nc, 2);
-        if (rc == DPF_ERR_UNSUPPORTED && k_off == 0) break;      // nothing launched yet: the kernels below take the launch
-        if (rc != DPF_OK) return rc == DPF_ERR_UNSUPPORTED ? DPF_ERR_LAUNCH : rc;
-        if (k_off + 64 >= d.K) return DPF_OK;
-      }
-    }
-  }
-  // channels per chunk: the largest of {8, 4, 2} whose two buffers leave room for >= 3 resident workgroups
-  auto buf_bytes = [&](int cc) { return (size_t)(cc * p.chanStride + T * cc * KT) * sizeof(float); };
-  auto nseg_of = [&](int cc) { return cc * p.rpc * p.SR; };
-  // Launches that fill the chip several times over run best with the smallest chunk (more resident workgroups hide the DMA
-  // latency: +1..5 % on every large shape, tools/conv_shape_bench.py sweep); small launches (< 2 tiles per CU) keep the larger
-  // chunks, which shorten their few workgroups' barrier chains.
-  const long long ntiles_est = (long long)d.N * p.odt * dpf_div_up(d.OH, p.thp) * dpf_div_up(d.OW, 32);
-  int CC = 0;
-  if (ntiles_est >= 512 && 2 * buf_bytes(2) <= (size_t)lds_target && nseg_of(2) <= NLD * 256) CC = 2;
-  if (!CC)
-    for (int cc : {8, 4, 2})
-      if (2 * buf_bytes(cc) <= (size_t)lds_target && nseg_of(cc) <= NLD * 256) { CC = cc; break; }
-  if (cc_over == 2 || cc_over == 4 || cc_over == 8) CC = cc_over;
-  if (!CC) CC = 2;
-  if (bf) CC = 8;
-  const size_t bf_buf = (size_t)8 * p.chanStride * sizeof(float) + (size_t)T * KT * 16;
-  if (bf ? (nseg_of(8) > 2 * NLD * 256 || 2 * bf_buf > 160 * 1024) : (nseg_of(CC) > NLD * 256 || 2 * buf_bytes(CC) > 160 * 1024))
-    return DPF_ERR_UNSUPPORTED;
-  p.nseg = nseg_of(CC);
-  p.nwseg = bf ? T * KT : T * CC * KT / 4;
-  p.nchunks = (d.C + CC - 1) / CC;
-  p.tilesH = dpf_div_up(d.OH, p.thp);
-  p.tilesW = dpf_div_up(d.OW, 32);
-  p.mSR = magic20(p.SR); p.mRPC = magic20(p.rpc); p.mEH = magic20(p.ext_h);
-  if ((long long)(bf ? 2 : 1) * NLD * 256 * (p.SR > p.rpc ? p.SR : p.rpc) >= (1LL << 20)) return DPF_ERR_UNSUPPORTED;   // multiply-shift exactness
-  const long long ntiles = (long long)d.N * p.odt * p.tilesH * p.tilesW;
-  if (ntiles <= 0 || ntiles > 0x3fffffffLL) return DPF_ERR_INVALID_ARG;
-  p.ntiles = (int)ntiles;
-  p.cpx = (int)((ntiles + 7) / 8);
-  const long long blocks = 8LL * p.cpx;
-
-  const long long total = (long long)p.nchunks * T * CC * KT + ZPAGE;
-  if (bf)
-    hipLaunchKernelGGL(igemm2_pack_bf16_kernel, dim3(dpf_ew_grid(total + ZPAGE)), dim3(256), 0, st, w, reinterpret_cast<unsigned short*>(ws), d.wA,
-                       d.wB, T, KT, p.nchunks, d.mode, d.k0, d.K, d.C);
-  else
-    hipLaunchKernelGGL(igemm2_pack_kernel, dim3(dpf_ew_grid(total)), dim3(256), 0, st, w, ws, d.wA, d.wB, T, KT, CC, p.nchunks, d.mode, d.k0, d.K, d.C);
-  if (dpf_check_launch() != DPF_OK) return DPF_ERR_LAUNCH;
-
-  p.single = p_single;
-  const size_t lds = bf ? (p_single ? 1 : 2) * bf_buf : 2 * buf_bytes(CC);
-  p.stats = nullptr;
-  if (stats) {
-    if (ntiles * d.K * 2 > stats->capacity_doubles || lds < (size_t)4 * 2 * MT * 16 * 2 * sizeof(double)) return DPF_ERR_UNSUPPORTED;
-    p.stats = stats->slab;
-    p.statsK = d.K; p.statsk0 = 0;
-    stats->parts = (int)ntiles;
-  }
-#define G2B(M, N_) return launch_g2<M, N_, 8, true>(x, ws, bias, out, p, lds, blocks, st)
-  if (bf) {
-    if (NT == 4) {
-      if (MT == 1) { G2B(1, 4); } else { G2B(2, 4); }
-    }
-    switch (MT) {
-      case 1: G2B(1, 2);
-      case 2: G2B(2, 2);
-      case 3: G2B(3, 2);
-      default: G2B(4, 2);
-    }
-  }
-#undef G2B
-#define G2(M, N_, C_) return launch_g2<M, N_, C_>(x, ws, bias, out, p, lds, blocks, st)
-#define G2CC(M, N_)                                                                                                         \
-  switch (CC) { case 8: G2(M, N_, 8); case 4: G2(M, N_, 4); default: G2(M, N_, 2); }
-  if (NT == 4) {
-    if (MT == 1) { G2CC(1, 4) } else { G2CC(2, 4) }
-  }
-  switch (MT) {
-    case 1: G2CC(1, 2)
-    case 2: G2CC(2, 2)
-    case 3: G2CC(3, 2)
-    default: G2CC(4, 2)
-  }
-#undef G2CC
-#undef G2
+  G2Plan g{};
+  g.T = d.kd * d.kh * d.kw;
+  g.MT = (d.K + 31) / 32;
+  g.KT = 32 * g.MT;
+  g2_bf16_tile(d, g);
+  g2_geometry(d, out, g);
+  g2_tap_steps(d, g.p);
+  const int rc = g2_x9_route(x, w, bias, out, ws, d, g, stats, st);
+  if (rc != DPF_ERR_UNSUPPORTED) return rc;
+  if (!g2_chunk(d, g)) return DPF_ERR_UNSUPPORTED;
+  return g2_pack_and_launch(x, w, bias, out, ws, d, g, stats, st);
 }
 
 #ifdef DPF_STAMPS

@@ -14,6 +14,28 @@ struct DpfConvDesc {
   int accumulate;               // 1: out += result (data gradients of several consumers of one tensor summed in the epilogue)
 };
 
+// The family's environment switches (README "Environment switches"), read once per process by conv_env() (conv_api.hip).
+struct ConvEnv {
+  int f32_x9;        // DPF_F32_X9 (2): INITIAL fp32 matrix path, clamped to 0..2; dpf_set_f32_matrix_path overrides it at run time
+  int igemm2;        // DPF_IGEMM2 (1): 0 = LDS-DMA forward / data-gradient kernels off
+  int igemm2_tr2;    // DPF_IGEMM2_TR2 (1): 0 = stride-2 transposed 3x3x3 kernel off
+  int igemm2_1x1;    // DPF_IGEMM2_1x1 (1): 0 = the LDS-DMA kernel declines 1x1x1 windows
+  int igemm3;        // DPF_IGEMM3 (1): 0 = split-operand (x9) kernel off
+  int igemm3_cc;     // DPF_IGEMM3_CC (0): 4 | 8 forces the x9 chunk layout
+  int igemm3_sh;     // DPF_IGEMM3_SH (-1): 0 | 1 forces one / two x9 weight buffers
+  int igemm3_rstep;  // DPF_IGEMM3_RSTEP (1): 0 = x9 tiles take consecutive rows of H-dilated 2-D layers
+  int igemm3_bf;     // DPF_IGEMM3_BF (1): 0 = bf16 operand precision stays on igemm2's bf16 kernel
+  int g2_pz;         // DPF_G2_PZ (0): 1 | 2 | 4 forces igemm2's depth split
+  int g2_vec_store;  // DPF_G2_VEC_STORE (1): 0 = scalar output stores
+  int wgrad2;        // DPF_WGRAD2 (1): 0 = LDS-DMA weight gradient off
+  int w2_sw1;        // DPF_W2_SW1 (1): 0 = wgrad2 without its stride-1 instantiation
+  int w2_rstep;      // DPF_W2_RSTEP (1): 0 = wgrad2 tiles take consecutive rows of H-dilated layers
+  int pointwise;     // DPF_POINTWISE (1): 0 = direct 1x1x1 kernels off
+};
+const ConvEnv& conv_env();
+
+constexpr int DPF_CONV_MAXT = 27;      // taps of the MFMA tile kernels; wider 2-D windows run on conv_wide.hip
+
 // operand precision of the dense convolution kernels (dpf_set_conv_operand_precision): 0 = exact fp32, 1 = operands rounded to bf16
 // (RNE) in the staging path, fp32 accumulation and storage
 int dpf_conv_operand_bf16();
@@ -22,6 +44,22 @@ int dpf_conv_operand_bf16();
 int dpf_conv_f32_x9();
 int dpf_h3_range_guard();              // 1 (always, outside tests): the range guards of the f16-component path are active (dpf_debug_set_range_guard)
 inline int dpf_conv_f32_nc() { return dpf_conv_f32_x9() == 2 ? 2 : 3; }      // components per operand of the split paths
+
+#ifdef __HIPCC__
+// Launch `Kern`.  A kernel that needs more than the 48 KB default of dynamic LDS has its limit raised first; the limit granted so far is
+// remembered per kernel, so the runtime is asked again only when a launch needs more than any before it.  (Per process, not per device:
+// like every once-per-process setting of this library this assumes one device per process.)
+template <auto Kern, typename... A>
+int conv_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+  static size_t granted = 48 * 1024;
+  if (lds > granted) {
+    if (hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return DPF_ERR_LAUNCH;
+    granted = lds;
+  }
+  hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+  return dpf_check_launch();
+}
+#endif
 
 // LDS-DMA double-buffered implicit GEMM (conv_igemm2.hip).  Returns DPF_OK when it launched, DPF_ERR_UNSUPPORTED when the
 // shape is not eligible (the caller then uses the generic kernel), another error code on failure.
@@ -35,6 +73,9 @@ int dpf_igemm2_conv(const float* x, const float* w, const float* bias, float* ou
                     DpfConvStats* stats = nullptr);
 // floats of workspace dpf_igemm2_conv may use for (T taps, `reduce` reduction channels, `outc` output channels)
 long long dpf_igemm2_workspace_floats(int T, int reduce, int outc);
+// First-generation kernels (conv_igemm.hip), the last tier of both dispatch chains (conv_api.hip): one launch of at most 128 channels.
+// They store only (d.accumulate is not theirs to honour); the weight gradient ADDS into dw with float atomics.
+int dpf_gen1_conv(const float* x, const float* w, const float* bias, float* out, float* ws, const DpfConvDesc& d, hipStream_t st);
 
 // One weight-gradient launch for the g-channels [k0, k0 + K) of a g tensor with Ktot channels; dw points at row k0 of dW[Ktot][C][T].
 struct DpfWgradDesc {
@@ -46,6 +87,7 @@ struct DpfWgradDesc {
 // accumulate = 0: dw is overwritten (no zero-initialisation needed), 1: dw += ...
 int dpf_wgrad2(const float* g, const float* x, float* dw, float* ws, long long ws_floats, const DpfWgradDesc& d, int accumulate, hipStream_t st);
 long long dpf_wgrad2_workspace_floats(int T, int C, int K);
+int dpf_gen1_wgrad(const float* g, const float* x, float* dw, const DpfWgradDesc& d, hipStream_t st);
 
 // Pointwise (1x1x1) convolutions, HBM-bound direct kernels (conv_pointwise.hip); DPF_ERR_UNSUPPORTED -> caller falls back.
 int dpf_pointwise_conv(const float* x, const float* w, const float* bias, float* out, const DpfConvDesc& d, hipStream_t st);

@@ -243,17 +243,11 @@ __global__ void pointwise_wgrad_reduce_kernel(const float* __restrict__ part, fl
   dw[i] = s;
 }
 
-int env_flag(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 }  // namespace
 
 // forward / transposed pointwise convolution; DPF_ERR_UNSUPPORTED -> the caller's other kernels take it
 int dpf_pointwise_conv(const float* x, const float* w, const float* bias, float* out, const DpfConvDesc& d, hipStream_t st) {
-  static const int enabled = env_flag("DPF_POINTWISE", 1);
-  if (!enabled || d.kd * d.kh * d.kw != 1 || d.pd || d.ph || d.pw) return DPF_ERR_UNSUPPORTED;
+  if (!conv_env().pointwise || d.kd * d.kh * d.kw != 1 || d.pd || d.ph || d.pw) return DPF_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return DPF_ERR_UNSUPPORTED;
   PwP p{};
   p.N = d.N; p.C = d.C; p.K = d.K; p.Ktot = d.Ktot; p.k0 = d.k0;
@@ -286,25 +280,15 @@ int dpf_pointwise_conv(const float* x, const float* w, const float* bias, float*
   const long long bx = (grid_pos + 511) / 512;
   if (bx > 0x7fffffffLL) return DPF_ERR_UNSUPPORTED;
   dim3 grid((unsigned)bx, (unsigned)d.N, (unsigned)(MT == 1 ? 1 : slices64));
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pointwise_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pointwise_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    attr = true;
-  }
-  if (MT == 1)
-    hipLaunchKernelGGL(pointwise_kernel<1>, grid, dim3(256), lds, st, x, w, bias, out, p);
-  else
-    hipLaunchKernelGGL(pointwise_kernel<2>, grid, dim3(256), lds, st, x, w, bias, out, p);
-  return dpf_check_launch();
+  return MT == 1 ? conv_launch<pointwise_kernel<1>>(grid, dim3(256), lds, st, x, w, bias, out, p)
+                 : conv_launch<pointwise_kernel<2>>(grid, dim3(256), lds, st, x, w, bias, out, p);
 }
 
 long long dpf_pointwise_wgrad_workspace_floats(int C, int K) { return 2048LL * K * C + 1024; }   // slab rows are capped by the workspace
 
 int dpf_pointwise_wgrad(const float* g, const float* x, float* dw, float* ws, long long ws_floats, const DpfWgradDesc& d, int accumulate,
                         hipStream_t st) {
-  static const int enabled = env_flag("DPF_POINTWISE", 1);
-  if (!enabled || !ws || d.kd * d.kh * d.kw != 1 || d.pd || d.ph || d.pw) return DPF_ERR_UNSUPPORTED;
+  if (!conv_env().pointwise || !ws || d.kd * d.kh * d.kw != 1 || d.pd || d.ph || d.pw) return DPF_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(g) & 15)) return DPF_ERR_UNSUPPORTED;
   PwgP p{};
   p.N = d.N; p.C = d.C; p.K = d.K; p.Ktot = d.Ktot; p.k0 = d.k0;
@@ -347,16 +331,12 @@ int dpf_pointwise_wgrad(const float* g, const float* x, float* dw, float* ws, lo
   size_t lds = sizeof(float) * (size_t)(32 * p.MT + 32 * p.CT) * LS;
   if (p.S > 1 && lds < sizeof(float) * (size_t)p.S * p.tiles * 1024) lds = sizeof(float) * (size_t)p.S * p.tiles * 1024;   // slice reduction
   if (lds > 96 * 1024) return DPF_ERR_UNSUPPORTED;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pointwise_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    attr = true;
-  }
   if (p.G == 3) {                                            // slice index = wave / 3: waves 0..2 slice 0, wave 3 would be slice 1
     p.G = 4;                                                 // use 4 groups with the last one possibly empty instead
     p.S = 1;
   }
-  hipLaunchKernelGGL(pointwise_wgrad_kernel, dim3((unsigned)blocks), dim3(256), lds, st, g, x, ws, p);
+  const int rc = conv_launch<pointwise_wgrad_kernel>(dim3((unsigned)blocks), dim3(256), lds, st, g, x, ws, p);
+  if (rc != DPF_OK) return rc;
   const long long n = (long long)d.K * d.C;
   const int groups = (int)((rows + RGROUP - 1) / RGROUP);
   float* part = ws + rows * n;

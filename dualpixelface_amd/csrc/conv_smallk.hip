@@ -4,6 +4,7 @@
 // (read C channels once, write K), so these are direct kernels: forward = one thread per output voxel with the weights
 // broadcast from LDS; weight gradient = one thread per (channel, tap) pair marching over an LDS-staged voxel tile.
 #include "dpf_common.h"
+#include "conv_internal.h"
 
 namespace {
 
@@ -559,18 +560,14 @@ int dpf_conv_smallk_wgrad(const float* g, const float* x, float* dw, int N, int 
   const int ext_d = (kd - 1) * dd + 1, ext_h = (TH - 1) * sh + (kh - 1) * dh + 1, ext_w = TW + kw - 1;
   const size_t lds = sizeof(float) * ((size_t)CCH * ext_d * ext_h * ext_w + (size_t)MAXK * TH * TW + 2 * (size_t)CCH * ext_d * ext_h);
   if (lds > 150 * 1024) return DPF_ERR_UNSUPPORTED;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute((const void*)smallk_wgrad_kernel<CCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return DPF_ERR_LAUNCH;
   const int tilesH = dpf_div_up(p.OH, TH), tilesW = dpf_div_up(p.OW, TW);
   const long long ntiles = (long long)N * p.OD * tilesH * tilesW;
   const int cchunks = dpf_div_up(C, CCH);
   long long nblk = 1024 / cchunks;
   if (nblk < 1) nblk = 1;
   if (nblk > ntiles) nblk = ntiles;
-  hipLaunchKernelGGL((smallk_wgrad_kernel<CCH>), dim3((unsigned)(cchunks * nblk)), dim3(256), lds, (hipStream_t)stream, g, x, dw, p, (int)nblk,
-                     tilesH, tilesW, ntiles);
-  return dpf_check_launch();
+  return conv_launch<smallk_wgrad_kernel<CCH>>(dim3((unsigned)(cchunks * nblk)), dim3(256), lds, (hipStream_t)stream, g, x, dw, p, (int)nblk, tilesH,
+                                               tilesW, ntiles);
 }
 
 }  // extern "C"

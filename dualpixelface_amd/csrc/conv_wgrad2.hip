@@ -629,10 +629,6 @@ __global__ void wgrad2_reduce_kernel(const float* __restrict__ slab, float* __re
 }
 
 unsigned magic20(int d) { return (unsigned)(((1u << 20) + d - 1) / d); }
-int env_int(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
 
 // bank conflicts of the B-operand gather for one candidate (PS, CS): sum over the 32-lane column windows of the extra LDS cycles
 int gather_conflicts(const DpfWgradDesc& d, int T, int ncolmax, int RS, int PS, int CS, int dhl) {
@@ -653,19 +649,11 @@ int gather_conflicts(const DpfWgradDesc& d, int T, int ncolmax, int RS, int PS, 
 
 template <int NCT, bool BF, bool SW1, int X9>
 int launch_w2c(const float* g, const float* x, float* slab, const W2P& p, size_t lds, unsigned blocks, hipStream_t st) {
-  static bool done = false;
-  if (lds > 48 * 1024 && !done) {
-    if (hipFuncSetAttribute((const void*)wgrad2_kernel<NCT, BF, SW1, X9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return DPF_ERR_LAUNCH;
-    done = true;
-  }
-  hipLaunchKernelGGL((wgrad2_kernel<NCT, BF, SW1, X9>), dim3(blocks), dim3(256), lds, st, g, x, slab, p);
-  return dpf_check_launch();
+  return conv_launch<wgrad2_kernel<NCT, BF, SW1, X9>>(dim3(blocks), dim3(256), lds, st, g, x, slab, p);
 }
 template <int NCT, bool BF, int X9>
 int launch_w2b(const float* g, const float* x, float* slab, const W2P& p, size_t lds, unsigned blocks, hipStream_t st) {
-  static const int sw1 = env_int("DPF_W2_SW1", 1);
-  return (p.sw == 1 && sw1) ? launch_w2c<NCT, BF, true, X9>(g, x, slab, p, lds, blocks, st) : launch_w2c<NCT, BF, false, X9>(g, x, slab, p, lds, blocks, st);
+  return (p.sw == 1 && conv_env().w2_sw1) ? launch_w2c<NCT, BF, true, X9>(g, x, slab, p, lds, blocks, st) : launch_w2c<NCT, BF, false, X9>(g, x, slab, p, lds, blocks, st);
 }
 template <int NCT>
 int launch_w2(const float* g, const float* x, float* slab, const W2P& p, size_t lds, unsigned blocks, hipStream_t st) {
@@ -694,8 +682,7 @@ long long dpf_wgrad2_workspace_floats(int T, int C, int K) {
 }
 
 int dpf_wgrad2(const float* g, const float* x, float* dw, float* ws, long long ws_floats, const DpfWgradDesc& d, int accumulate, hipStream_t st) {
-  static const int enabled = env_int("DPF_WGRAD2", 1);
-  if (!enabled || !ws) return DPF_ERR_UNSUPPORTED;
+  if (!conv_env().wgrad2 || !ws) return DPF_ERR_UNSUPPORTED;
   const int T = d.kd * d.kh * d.kw;
   constexpr int min_t = 9;
   if (T > 27 || T < min_t || d.K > 128) return DPF_ERR_UNSUPPORTED;
@@ -713,8 +700,7 @@ int dpf_wgrad2(const float* g, const float* x, float* dw, float* ws, long long w
   p.kd = d.kd; p.kh = d.kh; p.kw = d.kw; p.dd = d.dd; p.dh = d.dh; p.dw = d.dw; p.T = T;
   // rows dilated by dh at stride 1: a tile takes the 4 rows of ONE dilation phase (dh apart), so its patch is kh + 3 image rows instead
   // of 4 + (kh - 1) * dh (20 rows at dilation 8: a fifth of the channels per LDS buffer, 44.7 TFLOP/s on the 64 -> 64 dilation-8 layer)
-  static const int rstep_on = env_int("DPF_W2_RSTEP", 1);
-  p.rstep = (rstep_on && d.sh == 1 && d.dh > 1 && d.kh > 1) ? d.dh : 1;
+  p.rstep = (conv_env().w2_rstep && d.sh == 1 && d.dh > 1 && d.kh > 1) ? d.dh : 1;
   p.dhl = d.dh / p.rstep;
   p.ext_d = (d.kd - 1) * d.dd + 1; p.ext_h = (WTH - 1) * d.sh + (d.kh - 1) * p.dhl + 1;
   const int ext_w = 31 * d.sw + (d.kw - 1) * d.dw + 1;
@@ -723,6 +709,11 @@ int dpf_wgrad2(const float* g, const float* x, float* dw, float* ws, long long w
   p.SR = p.RS / 4;
   // column chunks: whole channels, balanced, at most nct_max tiles of 32 columns; shrink until the two LDS buffers fit
   int NCT = 0, CCW = 0;
+  auto lds_bytes = [&] {      // two staging buffers, or the reduction tiles that reuse them; + the exponent tables of the f16-component path
+    const size_t buf = (size_t)(CCW * p.CS + GFLOATS) * sizeof(float);
+    const size_t red = (size_t)2 * NCT * 16 * 64 * sizeof(float);
+    return (2 * buf > red ? 2 * buf : red) + 576;
+  };
   // stride 2: the x patch of a tile is 2.8x larger per channel; two column tiles (fewer channels per buffer, more resident
   // workgroups) measured 69 vs 56 TFLOP/s against the stride-1 optimum of seven
   const int nct_cap = (d.sh == 2 || d.sw == 2) ? 2 : nct_max;
@@ -740,10 +731,7 @@ int dpf_wgrad2(const float* g, const float* x, float* dw, float* ws, long long w
         const int c = gather_conflicts(d, T, CCW * T, p.RS, PS, CS, p.dhl) * 64 + pp * p.ext_d + cp;
         if (c < bestc) { bestc = c; p.PS = PS; p.CS = CS; }
       }
-    const size_t buf = (size_t)(CCW * p.CS + GFLOATS) * sizeof(float);
-    const size_t red = (size_t)2 * NCT * 16 * 64 * sizeof(float);
-    const size_t lds = (2 * buf > red ? 2 * buf : red) + 576;   // + the exponent tables of the f16-component path
-    if (CCW * p.CS / 4 > NLX * 256 || lds > (size_t)lds_max) { NCT = 0; continue; }
+    if (CCW * p.CS / 4 > NLX * 256 || lds_bytes() > (size_t)lds_max) { NCT = 0; continue; }
     break;
   }
   if (NCT == 0) return DPF_ERR_UNSUPPORTED;
@@ -758,34 +746,26 @@ int dpf_wgrad2(const float* g, const float* x, float* dw, float* ws, long long w
   p.mCS = magic20(p.CSseg); p.mPS = magic20(p.PSseg); p.mSR = magic20(p.SR);
   // as many position chunks as fit the chip at once: (workgroups resident per CU by registers and LDS) x 256 CUs / groups
   p.groups = p.cchunks * p.kslices;
-  const size_t buf0 = (size_t)(CCW * p.CS + GFLOATS) * sizeof(float);
-  const size_t red0 = (size_t)2 * NCT * 16 * 64 * sizeof(float);
-  const size_t lds0 = (2 * buf0 > red0 ? 2 * buf0 : red0) + 576;
+  const size_t lds = lds_bytes();
   int occ = w2_occ_of(NCT);
-  if ((size_t)occ * lds0 > 160 * 1024) occ = (int)((160 * 1024) / lds0);
+  if ((size_t)occ * lds > 160 * 1024) occ = (int)((160 * 1024) / lds);
   if (occ < 1) occ = 1;
-  constexpr int cap_over = 0;
   // one resident round of workgroups; with many (column chunk, k slice) groups the position chunks get coarse, and two rounds
   // balance the CUs better (measured: K = 81 / 96 layers 58 -> 71-86 TFLOP/s, the 32-channel layers unchanged)
-  const int capacity = cap_over ? cap_over : occ * 256 * (p.groups >= 12 ? 2 : 1);
+  const int capacity = occ * 256 * (p.groups >= 12 ? 2 : 1);
   long long nchunk = capacity / p.groups;
   if (nchunk < 1) nchunk = 1;
   if (nchunk > p.ntiles) nchunk = p.ntiles;
   // position chunks in multiples of 16 (8 XCD labels x 2): the workgroups of a chunk share their x / g tiles through one XCD's L2, and
   // an uneven deal of chunks to XCDs costs 15-25 % (K = 81 layers: 42 chunks 73 TFLOP/s, 32 chunks 89; 68 chunks 73, 64 chunks 86)
-  if (!cap_over) {
-    if (nchunk >= 16 && (nchunk & 7)) nchunk &= ~15LL;          // already a multiple of 8: keep (56 chunks beat 48 on the 96-channel layer)
-    else if (nchunk > 8 && nchunk < 16) nchunk = 8;
-  }
+  if (nchunk >= 16 && (nchunk & 7)) nchunk &= ~15LL;          // already a multiple of 8: keep (56 chunks beat 48 on the 96-channel layer)
+  else if (nchunk > 8 && nchunk < 16) nchunk = 8;
   p.per = (p.ntiles + nchunk - 1) / nchunk;
   nchunk = (p.ntiles + p.per - 1) / p.per;
   p.nchunk = (int)nchunk;
   p.slab_stride = (long long)d.K * d.C * T;
   if (nchunk * p.slab_stride > ws_floats) return DPF_ERR_UNSUPPORTED;
 
-  const size_t buf = (size_t)(CCW * p.CS + GFLOATS) * sizeof(float);
-  const size_t red = (size_t)2 * NCT * 16 * 64 * sizeof(float);
-  const size_t lds = (2 * buf > red ? 2 * buf : red) + 576;
   const unsigned blocks = (unsigned)(8 * ((p.nchunk + 7) / 8) * p.groups);
   int rc;
   switch (NCT) {

@@ -309,10 +309,8 @@ int dpf_wide_wgrad(const float* g, const float* x, float* dw, float* ws, long lo
   p.nparts = (int)parts;
   const size_t lds = ((size_t)p.CC * p.PH * p.PW + (size_t)GKB * GH * GW) * sizeof(float);
   if (lds > 64 * 1024 || p.cchunks > 65535 || p.kgroups > 65535) return DPF_ERR_UNSUPPORTED;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute((const void*)wide_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return DPF_ERR_LAUNCH;
-  hipLaunchKernelGGL(wide_wgrad_kernel, dim3((unsigned)p.nparts, (unsigned)p.cchunks, (unsigned)p.kgroups), dim3(256), lds, st, g, x, ws, p);
+  const int rc = conv_launch<wide_wgrad_kernel>(dim3((unsigned)p.nparts, (unsigned)p.cchunks, (unsigned)p.kgroups), dim3(256), lds, st, g, x, ws, p);
+  if (rc != DPF_OK) return rc;
   hipLaunchKernelGGL(wide_wgrad_fold_kernel, dim3(dpf_ew_grid(row)), dim3(256), 0, st, ws, dw, row, p.nparts, accumulate);
   return dpf_check_launch();
 }

@@ -42,6 +42,9 @@ SETS = [
                                  'test_conv_forward_backward or test_sync_batchnorm or test_norm_act_concat or test_conv_transpose3d'),
     # first-generation dense conv kernels (what unaligned shapes fall back to)
     ({'DPF_IGEMM2': '0', 'DPF_WGRAD2': '0', 'DPF_IGEMM2_TR2': '0'}, 'test_conv_forward_backward'),
+    # pointwise (1x1x1) convolutions on the LDS-DMA tile kernels, and on the first-generation kernels, instead of the direct kernels
+    ({'DPF_POINTWISE': '0'}, 'test_conv_forward_backward'),
+    ({'DPF_POINTWISE': '0', 'DPF_IGEMM2_1x1': '0'}, 'test_conv_forward_backward'),
 ]
 
 

@@ -197,6 +197,35 @@ def test_every_environment_switch_is_documented():
     assert len(found) <= 40, (len(found), 'collapse switches that have a measured winner')
 
 
+def test_kernel_switch_records_match_the_readme():
+    """The two switch records of the kernels' host code -- conv_env() (conv_api.hip) and dcn_env() (dcn3d.hip) -- read only switches that the
+    README's "Environment switches" paragraph lists as live (before the word "Retired"), and no switch listed as retired is read anywhere in
+    csrc/."""
+    import glob
+    import re
+    csrc = os.path.join(ROOT, 'dualpixelface_amd', 'csrc')
+    readme = open(os.path.join(ROOT, 'README.md')).read()
+    switches = readme[readme.index('Environment switches'):]
+    live, retired = switches[:switches.index('Retired')], switches[switches.index('Retired'):]
+    retired = retired.split('\n\n')[0]
+    read = set()
+    for fname, record in (('conv_api.hip', 'conv_env'), ('dcn3d.hip', 'dcn_env')):
+        src = open(os.path.join(csrc, fname)).read()
+        body = src[src.index('& %s() {' % record):]
+        body = body[:body.index('\n}\n')]
+        names = set(re.findall(r'getenv\("(DPF_[A-Za-z0-9_]+)"\)', body))
+        assert names, record
+        read |= names
+    assert len(read) == 20, sorted(read)         # 15 dense-conv + 5 deformable-conv switches
+    missing = sorted(n for n in read if '`%s' % n not in live)
+    assert not missing, missing
+    retired_names = set(re.findall(r'`(DPF_[A-Za-z0-9_]+)`', retired))
+    assert len(retired_names) >= 20, sorted(retired_names)
+    sources = ''.join(open(f).read() for f in glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.h')))
+    still_read = sorted(n for n in retired_names if re.search(r'\b%s\b' % n, sources))
+    assert not still_read, still_read
+
+
 def test_bench_dump_outputs_fixed_sample_within_budget(tmp_path, monkeypatch):
     """bench.py --dump-outputs: small arrays keep their shape, the rest share what is left of the byte budget as a seeded sample whose
     indices depend only on the shapes (two dumps of the same arrays are identical); float64 stays float64, everything else is float32."""
