@@ -5,10 +5,13 @@ all-reduce).
 """
 import contextlib
 import os
+import sys
+import traceback
+import warnings
 
 import torch
 
-from . import ops
+from . import ops, optim
 from .losses import loss_selector
 from .selectors import metric_selector, optimizer_selector, scheduler_selector
 from .dpnet import DPNetCore
@@ -25,8 +28,8 @@ class _PluginHooks(object):
         super(_PluginHooks, self).__init__(option)         # the model family's core (core.ArenaModule)
         self.loss_model = loss_selector(option)
         self.metric_model = metric_selector(option)
-        self._adam = None                                  # optim 'adam': {'m', 'v', 'step'}
-        self._optim = None                                 # optim 'sgd' / 'rmsprop': {'kind', 'buf' | 'sq'} (+ SGD's liveness mask)
+        self._adam = None                                  # the fused optimiser's state, kept by optim.py: 'adam' here,
+        self._optim = None                                 # 'sgd' / 'rmsprop' here
 
     # ---- reference surface -------------------------------------------------------------------------------
     def forward(self, batch):
@@ -106,7 +109,7 @@ class _PluginHooks(object):
         Single-process steps on a fixed batch shape are captured into ONE HIP graph after two eager warm-up steps and replayed from then on
         (option.step_graph / DPF_STEP_GRAPH, default on): the ~2 400 kernel launches of a step leave the host once, so the launch gaps between
         the many short kernels disappear.  The C ABI never allocates or synchronises, which is what makes the step capturable."""
-        if self.option.optim not in ('adam', 'sgd', 'rmsprop'):
+        if self.option.optim not in optim.TABLE:
             raise NotImplementedError('optimizer is not defined, please check your optimizer configuration !')
         if self.option.optim == 'sgd' and not getattr(self, 'gather_grads', True):
             raise NotImplementedError("optim 'sgd' needs the gather scheme (model.gather_grads): gradients accumulated into arena views do "
@@ -116,112 +119,115 @@ class _PluginHooks(object):
             return self._graph_step(batch, lr)
         return self._eager_step(batch, reducer, lr)
 
+    def _lr(self, lr):
+        return float(lr if lr is not None else self.option.init_lr)
+
     # ---- the step as one HIP graph ---------------------------------------------------------------------
     def _graph_step(self, batch, lr):
         self.train()                                       # (a replay runs no Python: the mode flag must not depend on it)
         tensors = {k: v for k, v in batch.items() if torch.is_tensor(v)}
-        # everything a captured graph has baked in: shapes, the kernel-path switches, the arenas' addresses (a device move re-creates them)
-        key = tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(tensors.items())) + (
+        st = self._graph_lookup(self._graph_key(tensors))
+        if st.get('failed'):
+            return self._eager_step(batch, None, lr)
+        st['calls'] += 1
+        device = self.flat_gradients(zero=False).device
+        # The step lives on its OWN stream, warm-up included: autograd's gradient-accumulation nodes remember the stream they were created
+        # on, and a capture cannot make the default stream wait for the capturing one.
+        ss = getattr(self, '_step_stream', None)
+        if ss is None or ss.device != device:
+            ss = self._step_stream = ops.shared_stream(device, 'step')             # one per process, not per model: ops.shared_stream
+        if st['calls'] <= 2 or not optim.of(self.option).state(self):
+            # warm-up: lazily created streams, scratch buffers, sampler tables, kernel attributes
+            with _on_stream(ss) as cur:
+                res = self._eager_step(batch, None, lr)
+            for v in (res.values() if cur is not None else ()):
+                if torch.is_tensor(v):
+                    v.record_stream(cur)
+            return _detached(res)
+        if st['graph'] is None and not self._graph_capture(st, ss, tensors, batch, lr):
+            return self._eager_step(batch, None, lr)
+        return self._graph_replay(st, ss, tensors, lr)
+
+    def _graph_key(self, tensors):
+        """Everything a captured graph has baked in: shapes, the kernel-path switches, the arenas' addresses (a device move re-creates them)."""
+        return tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(tensors.items())) + (
             bool(ops.deterministic()), ops.CONV_OPERANDS_BF16, ops.f32_matrix_path(), ops.WGRAD_ASYNC) + self._capture_key() + (
-            self.flat_parameters().data_ptr(), self.flat_gradients(zero=False).data_ptr(), self._opt_key(), self.stat_exchange is None)
-        # a few graph states are kept (most recently used last): the last, partial batch of an epoch has its own key and must not throw the
-        # main shape's graph away
+            self.flat_parameters().data_ptr(), self.flat_gradients(zero=False).data_ptr(), optim.of(self.option).key(self),
+            self.stat_exchange is None)
+
+    def _graph_lookup(self, key):
+        """The graph state of `key`, new if need be.  A few states are kept (most recently used last): the last, partial batch of an epoch
+        has its own key and must not throw the main shape's graph away."""
         states = self.__dict__.setdefault('_graph_states', [])
         st = next((g for g in states if g['key'] == key), None)
         if st is None:
             st = {'key': key, 'calls': 0, 'graph': None}
-            states.append(st)
-            del states[:-3]
         else:
             states.remove(st)
-            states.append(st)
+        states.append(st)
+        del states[:-3]
         self._graph_state = st
-        if st.get('failed'):
-            return self._eager_step(batch, None, lr)
-        st['calls'] += 1
-        lr = float(lr if lr is not None else self.option.init_lr)
-        flat_g = self.flat_gradients(zero=False)
-        # The step lives on its OWN stream, warm-up included: autograd's gradient-accumulation nodes remember the stream they were created
-        # on, and a capture cannot make the default stream wait for the capturing one.
-        ss = getattr(self, '_step_stream', None)
-        if ss is None or ss.device != flat_g.device:
-            ss = self._step_stream = ops.shared_stream(flat_g.device, 'step')      # one per process, not per model: ops.shared_stream
-        cur = torch.cuda.current_stream(flat_g.device)
-        if st['calls'] <= 2 or not self._opt_state():      # warm-up: lazily created streams, scratch buffers, sampler tables, kernel attributes
-            ss.wait_stream(cur)
-            with torch.cuda.stream(ss):
-                res = self._eager_step(batch, None, lr)
-            cur.wait_stream(ss)
-            for v in res.values():
-                if torch.is_tensor(v):
-                    v.record_stream(cur)
-            return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in res.items()}
-        ad = self._opt_state()
-        if st['graph'] is None:
-            # static inputs (the caller's tensors are copied in before every replay), the hyper-parameter slot, then the capture itself
-            st['inputs'] = {k: v.clone() for k, v in tensors.items()}
-            st['extra'] = {k: v for k, v in batch.items() if not torch.is_tensor(v)}
-            st['hyper'] = torch.zeros(2, dtype=torch.float32, device=flat_g.device)
-            counts_before = dict(self._pending_counts)
-            step_before = ad.get('step')                   # (Adam's bias-correction counter; the other optimisers have none)
-            self._flush_counts()
-            baked = self._baked_buffers()                  # (before AND after: a buffer replaced mid-capture was baked in as well)
-            graph = torch.cuda.CUDAGraph()
-            try:
-                torch.cuda.synchronize()
-                ops.reset_zero_arenas()
-                # (thread-local error mode: the data path's worker threads -- facedp.FaceDPBatcher decodes and preprocesses the next batch on
-                # the GPU meanwhile -- make allocator and copy calls of their own, which a global-mode capture takes for violations)
-                with torch.cuda.graph(graph, stream=ss, capture_error_mode='thread_local'):
-                    try:
-                        cap_batch = dict(st['extra'])
-                        cap_batch.update(st['inputs'])
-                        res = self._eager_step(cap_batch, None, lr, hyper=st['hyper'])
-                        st['results'] = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in res.items()}
-                        del res
-                    except BaseException as e:               # (ending an invalidated capture has crashed the process before the error could surface)
-                        import sys
-                        import traceback
-                        sys.stderr.write('train_step: exception inside the graph capture: %r\n%s\n' % (e, traceback.format_exc()))
-                        sys.stderr.flush()
-                        raise
-                st['counts'] = dict(self._pending_counts)            # BatchNorm call counters one step adds (host-side bookkeeping)
-                self._pending_counts = {}
-                if step_before is not None:
-                    ad['step'] -= 1                                  # the capture only RECORDED the step: nothing ran
-                st['owned'] = baked + self._baked_buffers()          # released when the LRU above drops the state
-                st['graph'] = graph
-            except Exception as e:                                   # capture refused (unsupported call inside): stay eager, say so once
-                import warnings
-                warnings.warn('train_step: HIP graph capture failed (%s: %s); continuing with eager launches' % (type(e).__name__, e))
-                st['failed'] = True
-                self._pending_counts = counts_before
-                torch.cuda.synchronize()
-                # the aborted capture only RECORDED its work: the clearing fill of the zero arenas never ran although their cursors moved
-                # on (the warm-up steps' slots are still dirty), and the Adam step counter may have been advanced
-                ops.reset_zero_arenas()
-                if step_before is not None:
-                    ad['step'] = step_before
-                return self._eager_step(batch, None, lr)
+        return st
+
+    def _graph_capture(self, st, ss, tensors, batch, lr):
+        """Record one step into st['graph']; returns whether the state now holds a graph.  After a refused capture (an unsupported call
+        inside) the state is marked `failed`, everything the recording moved is put back, and the caller stays eager."""
+        # static inputs (the caller's tensors are copied in before every replay), the hyper-parameter slot, then the capture itself
+        st['inputs'] = {k: v.clone() for k, v in tensors.items()}
+        st['extra'] = {k: v for k, v in batch.items() if not torch.is_tensor(v)}
+        st['hyper'] = torch.zeros(2, dtype=torch.float32, device=ss.device)
+        rec = optim.of(self.option)
+        counts_before = dict(self._pending_counts)
+        step_before = rec.counter_of(self)                 # (Adam's bias-correction counter; the other optimisers have none)
+        self._flush_counts()
+        baked = self._baked_buffers()                      # (before AND after: a buffer replaced mid-capture was baked in as well)
+        graph = torch.cuda.CUDAGraph()
+        try:
+            torch.cuda.synchronize()
+            ops.reset_zero_arenas()
+            # (thread-local error mode: the data path's worker threads -- facedp.FaceDPBatcher decodes and preprocesses the next batch on
+            # the GPU meanwhile -- make allocator and copy calls of their own, which a global-mode capture takes for violations)
+            with torch.cuda.graph(graph, stream=ss, capture_error_mode='thread_local'):
+                st['results'] = self._captured_step(st, lr)
+            st['counts'] = dict(self._pending_counts)                # BatchNorm call counters one step adds (host-side bookkeeping)
+            self._pending_counts = {}
+            rec.set_counter(self, step_before)                       # the capture only RECORDED the step: nothing ran
+            st['owned'] = baked + self._baked_buffers()              # released when the LRU (_graph_lookup) drops the state
+            st['graph'] = graph
+            return True
+        except Exception as e:                                       # capture refused: stay eager, say so once
+            warnings.warn('train_step: HIP graph capture failed (%s: %s); continuing with eager launches' % (type(e).__name__, e))
+            st['failed'] = True
+            self._pending_counts = counts_before
+            torch.cuda.synchronize()
+            # the aborted capture only RECORDED its work: the clearing fill of the zero arenas never ran although their cursors moved
+            # on (the warm-up steps' slots are still dirty), and the Adam step counter may have been advanced
+            ops.reset_zero_arenas()
+            rec.set_counter(self, step_before)
+            return False
+
+    def _captured_step(self, st, lr):
+        try:
+            cap_batch = dict(st['extra'])
+            cap_batch.update(st['inputs'])
+            return _detached(self._eager_step(cap_batch, None, lr, hyper=st['hyper']))
+        except BaseException as e:                         # (ending an invalidated capture has crashed the process before the error could surface)
+            sys.stderr.write('train_step: exception inside the graph capture: %r\n%s\n' % (e, traceback.format_exc()))
+            sys.stderr.flush()
+            raise
+
+    def _graph_replay(self, st, ss, tensors, lr):
         # The replay runs on the dedicated stream, bracketed by explicit event waits in both directions.  Launched into the caller's stream
         # -- the legacy default stream in a plain script -- kernels the caller enqueued right after the replay were observed to start before
         # the graph had finished (bench.py --wgrad-inline: eager steps behind two replays read parameters the replay was still writing: GPU
         # memory faults and hangs in 2 of 5 runs; none in 12 runs with this ordering).
-        ss.wait_stream(cur)
-        with torch.cuda.stream(ss):
+        with _on_stream(ss):
             for k, v in tensors.items():
                 if v.data_ptr() != st['inputs'][k].data_ptr():
                     st['inputs'][k].copy_(v, non_blocking=True)
                     v.record_stream(ss)
-            if self.option.optim == 'adam':
-                ad['step'] += 1
-                h0, h1 = ops.adam_hyper(ad['step'], lr)
-                st['hyper'][0:1].fill_(float(h0))          # (scalars travel as kernel arguments: no host buffer the next step could overwrite)
-                st['hyper'][1:2].fill_(float(h1))
-            else:
-                st['hyper'][0:1].fill_(lr)                 # SGD / RMSprop: the rate is the only scalar that changes between replays
+            optim.of(self.option).write_hyper(self, st['hyper'], self._lr(lr))
             st['graph'].replay()
-        cur.wait_stream(ss)
         for name, n in st['counts'].items():
             self._pending_counts[name] = self._pending_counts.get(name, 0) + n
         return dict(st['results'])                         # (a fresh dict; the tensors are the graph's static buffers, valid until the next step)
@@ -240,22 +246,7 @@ class _PluginHooks(object):
         Not buffers: `_pairs_cache` (views of the gradient arena), the shared streams (`ops._wgrad_side`, the feature stream); the
         normal head's lazily registered `grid` is read by no kernel and only ever written in place."""
         found = ops.workspace_buffers() + list(self.buffers()) + [self.flat_parameters(), self.flat_gradients(zero=False)]
-        return found + self._opt_arenas() + self._shape_constants()
-
-    def _opt_state(self):
-        """The fused step's optimiser state: `_adam` under optim 'adam', `_optim` under 'sgd' / 'rmsprop' (None before the first step)."""
-        return self._adam if self.option.optim == 'adam' else self._optim
-
-    def _opt_arenas(self):
-        st = self._opt_state() or {}
-        return [st[k] for k in ('m', 'v', 'buf', 'sq', 'live') if st.get(k) is not None]
-
-    def _opt_key(self):
-        """What a captured step bakes in of the optimiser: the state arena's address (0 before it exists)."""
-        arenas = self._opt_arenas()
-        if self.option.optim == 'adam':
-            return arenas[0].data_ptr() if arenas else 0
-        return (self.option.optim,) + tuple(t.data_ptr() for t in arenas)
+        return found + optim.of(self.option).arenas(self) + self._shape_constants()
 
     def _behind_replays(self, fn):
         """Once a train step of this model replays as a HIP graph, everything the model launches one by one (an eager step, forward,
@@ -271,13 +262,10 @@ class _PluginHooks(object):
         ss = getattr(self, '_step_stream', None)
         if ss is None or not any(g.get('graph') is not None for g in getattr(self, '_graph_states', ())):
             return fn()
-        cur = torch.cuda.current_stream(ss.device)
-        if cur == ss:
-            return fn()
-        ss.wait_stream(cur)
-        with torch.cuda.stream(ss):
+        with _on_stream(ss) as cur:
             out = fn()
-        cur.wait_stream(ss)
+        if cur is None:                                    # (already on the step stream)
+            return out
         for v in (out.values() if isinstance(out, dict) else ()):
             if torch.is_tensor(v) and v.is_cuda:
                 v.record_stream(cur)
@@ -290,137 +278,124 @@ class _PluginHooks(object):
 
     def _eager_step_body(self, batch, reducer=None, lr=None, hyper=None):
         self.train()
-        gscale = 1.0
-        dead = None                                        # arena ranges of the parameters backward() left without a gradient
         if getattr(self, 'gather_grads', True):
-            # Gradients are produced as fresh tensors (autograd hands them over without an accumulate kernel when .grad is None) and
-            # gathered into the flat arena by one multi-tensor copy; the 14.7 MB all-reduce then runs once over the arena.  The
-            # alternative below accumulates into arena views (one add kernel per parameter, ~300 per step) and overlaps bucketed
-            # all-reduces with the backward pass through hooks -- an overlap worth < 0.1 % of a 400 ms step.
-            flat_g = self.flat_gradients(zero=False)
-            pairs = self._grad_pairs()
-            dead = []
-            for p, _ in pairs:
-                p.grad = None
-            ops.wgrad_async_begin([p for p, _ in pairs])
-
-            def gather(sel):
-                """Copy the gradients of the selected (parameter, arena view) pairs into the arena; afterwards .grad IS the view."""
-                views, grads = [], []
-                for p, v in sel:
-                    if p.grad is v:
-                        continue
-                    if p.grad is None:
-                        v.zero_()
-                        dead.append((v.storage_offset(), v.numel()))
-                    else:
-                        views.append(v)
-                        grads.append(p.grad)
-                if views:
-                    torch._foreach_copy_(views, grads)
-                for p, v in sel:
-                    p.grad = v
-
-            staged = reducer is not None and getattr(reducer, 'collectives', reducer.world_size > 1) and getattr(self, 'stage_grads', True)
-            if staged:
-                # Data-parallel: the network fires self._grad_stage(bucket) from tensor hooks at its bucket boundaries (normal head done;
-                # aggregation + cost volume done); that bucket is gathered and its all-reduce enqueued while the backward pass continues.
-                reducer.stage_begin()
-                main = torch.cuda.current_stream() if flat_g.is_cuda else None
-
-                def on_stage(name):
-                    # `name`: 'aggregation' | 'normal' (StereoDPNetCore._network).  A reducer cut differently has no bucket of that name:
-                    # nothing is staged then and stage_finish exchanges everything after backward().
-                    bi = reducer.stage_of.get(name) if hasattr(reducer, 'stage_of') else None
-                    if bi is None:
-                        return
-                    # The hook may fire on another stream than the step's (the second feature pass has its own): the bucket's gradients
-                    # were produced on the main stream (and the weight-gradient side stream), and Adam will read the arena there -- so the
-                    # gather and the collective are enqueued on the main stream, after whatever the hook's stream has produced so far.
-                    cur = torch.cuda.current_stream() if main is not None else None
-                    if main is not None and cur != main:
-                        main.wait_stream(cur)
-                    with (torch.cuda.stream(main) if main is not None else contextlib.nullcontext()):
-                        _attach_deferred(ops.wgrad_async_take(lambda q: reducer.bucket_of(q) == bi))
-                        gather([(p, v) for p, v in pairs if reducer.bucket_of(p) == bi])
-                        reducer.stage_launch(bi)
-                self._grad_stage = on_stage
-            self._two_streams_ok = True            # see StereoDPNetCore._network
-            try:
-                with two_stream_grad_warning_off():
-                    results = self.forward(batch)
-                    results['final_loss'].backward()
-            finally:
-                self._grad_stage = None
-                self._two_streams_ok = False
-            _attach_deferred(ops.wgrad_async_finish())
-            gather(pairs)
-            if reducer is not None:
-                if staged:
-                    reducer.stage_finish()
-                else:
-                    reducer.reduce_all()
-                gscale = 1.0 / reducer.world_size
+            results, flat_g, dead = self._grads_gathered(batch, reducer)
         else:
-            flat_g = self.flat_gradients(zero=True)
-            if reducer is not None:
-                reducer.begin()
-            results = self.forward(batch)
-            results['final_loss'].backward()
-            if reducer is not None:
-                reducer.finish()
-                gscale = 1.0 / reducer.world_size
-        if self.option.optim != 'adam':
-            self._native_optim_step(flat_g, dead, hyper, float(lr if lr is not None else self.option.init_lr), gscale)
-            return results
-        if self._adam is None or self._adam['m'].device != flat_g.device:
-            self._adam = {'m': torch.zeros_like(flat_g), 'v': torch.zeros_like(flat_g), 'step': 0}
-        st = self._adam
-        st['step'] += 1
-        if hyper is not None:                              # (graph capture: the step-dependent scalars come from device memory)
-            ops.adam_step_hyper(self.flat_parameters(), flat_g, st['m'], st['v'], hyper, 0.9, 0.999, 1e-5, gscale)
-        else:
-            ops.adam_step(self.flat_parameters(), flat_g, st['m'], st['v'], st['step'], float(lr if lr is not None else self.option.init_lr),
-                          0.9, 0.999, 1e-5, gscale)
+            results, flat_g, dead = self._grads_into_views(batch, reducer)
+        gscale = 1.0 / reducer.world_size if reducer is not None else 1.0
+        optim.of(self.option).step(self, flat_g, dead, hyper, self._lr(lr), gscale)
         return results
 
-    def _native_optim_step(self, flat_g, dead, hyper, lr, gscale):
-        """The SGD / RMSprop tail of a step, hyper-parameters as selectors.optimizer_selector gives torch's (model_selector.py:36,38).
-        hyper: the rate in device memory (graph capture), else it travels as a kernel argument."""
-        kind = self.option.optim
-        name = {'sgd': 'buf', 'rmsprop': 'sq'}[kind]
-        st = self._optim
-        if st is None or st.get('kind') != kind or st.get(name) is None or st[name].device != flat_g.device:
-            st = self._optim = {'kind': kind, name: torch.zeros_like(flat_g)}
-        if kind == 'rmsprop':                              # (a parameter without a gradient has a zero one in the arena: no update, state stays 0)
-            if hyper is not None:
-                ops.rmsprop_step_lr(self.flat_parameters(), flat_g, st['sq'], hyper, 0.99, 1e-5, gscale)
-            else:
-                ops.rmsprop_step(self.flat_parameters(), flat_g, st['sq'], lr, 0.99, 1e-5, gscale)
-            return
-        # SGD: torch skips a parameter whose .grad is None, while weight decay over its zero-filled arena view would shrink it every step.
-        # The kernel gets a byte mask of the live elements, rebuilt only when the set of such parameters changes -- it is a property of
-        # the network, so the warm-up steps settle it and a capture bakes in its address (_opt_key, _baked_buffers).
-        dead = tuple(sorted(set(dead)))                    # (never None here: train_step refuses SGD without the gather scheme)
-        if st.get('dead') != dead or (dead and (st.get('live') is None or st['live'].device != flat_g.device)):
-            live = None
-            if dead:
-                live = torch.ones(flat_g.numel(), dtype=torch.uint8, device=flat_g.device)
-                for off, numel in dead:
-                    live[off:off + numel] = 0
-            st['dead'], st['live'] = dead, live
-        if hyper is not None:
-            ops.sgd_step_lr(self.flat_parameters(), flat_g, st['buf'], hyper, 0.9, 2e-4, gscale, live=st['live'])
-        else:
-            ops.sgd_step(self.flat_parameters(), flat_g, st['buf'], lr, 0.9, 2e-4, gscale, live=st['live'])
+    def _grads_gathered(self, batch, reducer):
+        """forward + backward under the gather scheme; returns (results, gradient arena, arena ranges of the parameters backward() left
+        without a gradient).
+
+        Gradients are produced as fresh tensors (autograd hands them over without an accumulate kernel when .grad is None) and gathered
+        into the flat arena by one multi-tensor copy; the 14.7 MB all-reduce then runs once over the arena.  The alternative
+        (_grads_into_views) accumulates into arena views (one add kernel per parameter, ~300 per step) and overlaps bucketed all-reduces
+        with the backward pass through hooks -- an overlap worth < 0.1 % of a 400 ms step."""
+        flat_g = self.flat_gradients(zero=False)
+        pairs = self._grad_pairs()
+        dead = []
+        for p, _ in pairs:
+            p.grad = None
+        ops.wgrad_async_begin([p for p, _ in pairs])
+        staged = reducer is not None and getattr(reducer, 'collectives', reducer.world_size > 1) and getattr(self, 'stage_grads', True)
+        if staged:
+            # Data-parallel: the network fires self._grad_stage(bucket) from tensor hooks at its bucket boundaries (normal head done;
+            # aggregation + cost volume done); that bucket is gathered and its all-reduce enqueued while the backward pass continues.
+            reducer.stage_begin()
+            main = torch.cuda.current_stream() if flat_g.is_cuda else None
+
+            def on_stage(name):
+                # `name`: 'aggregation' | 'normal' (StereoDPNetCore._network).  A reducer cut differently has no bucket of that name:
+                # nothing is staged then and stage_finish exchanges everything after backward().
+                bi = reducer.stage_of.get(name) if hasattr(reducer, 'stage_of') else None
+                if bi is None:
+                    return
+                # The hook may fire on another stream than the step's (the second feature pass has its own): the bucket's gradients
+                # were produced on the main stream (and the weight-gradient side stream), and Adam will read the arena there -- so the
+                # gather and the collective are enqueued on the main stream, after whatever the hook's stream has produced so far.
+                cur = torch.cuda.current_stream() if main is not None else None
+                if main is not None and cur != main:
+                    main.wait_stream(cur)
+                with (torch.cuda.stream(main) if main is not None else contextlib.nullcontext()):
+                    _attach_deferred(ops.wgrad_async_take(lambda q: reducer.bucket_of(q) == bi))
+                    _gather([(p, v) for p, v in pairs if reducer.bucket_of(p) == bi], dead)
+                    reducer.stage_launch(bi)
+            self._grad_stage = on_stage
+        self._two_streams_ok = True                # see StereoDPNetCore._network
+        try:
+            with two_stream_grad_warning_off():
+                results = self.forward(batch)
+                results['final_loss'].backward()
+        finally:
+            self._grad_stage = None
+            self._two_streams_ok = False
+        _attach_deferred(ops.wgrad_async_finish())
+        _gather(pairs, dead)
+        if staged:
+            reducer.stage_finish()
+        elif reducer is not None:
+            reducer.reduce_all()
+        return results, flat_g, dead
+
+    def _grads_into_views(self, batch, reducer):
+        """forward + backward accumulating into arena views, bucketed all-reduces overlapping through the reducer's hooks; returns
+        (results, gradient arena, None: a parameter without a gradient cannot be told from one with a zero gradient here)."""
+        flat_g = self.flat_gradients(zero=True)
+        if reducer is not None:
+            reducer.begin()
+        results = self.forward(batch)
+        results['final_loss'].backward()
+        if reducer is not None:
+            reducer.finish()
+        return results, flat_g, None
+
+
+@contextlib.contextmanager
+def _on_stream(ss):
+    """Run the body on the stream `ss` between event waits: `ss` waits for the caller's current stream, and the caller's stream waits for
+    `ss` afterwards.  Yields the caller's stream, for a `record_stream` of what the body hands back -- or None when the caller already is on
+    `ss` and nothing is done."""
+    cur = torch.cuda.current_stream(ss.device)
+    if cur == ss:
+        yield None
+        return
+    ss.wait_stream(cur)
+    with torch.cuda.stream(ss):
+        yield cur
+    cur.wait_stream(ss)
+
+
+def _detached(res):
+    return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in res.items()}
 
 
 def _graph_enabled(model):
-    import os
     env = os.environ.get('DPF_STEP_GRAPH')
     if env is not None:
         return env != '0'
     return bool(getattr(model.option, 'step_graph', True))
+
+
+def _gather(sel, dead):
+    """Copy the gradients of the selected (parameter, arena view) pairs into the arena; afterwards .grad IS the view.  A parameter
+    without a gradient gets a zero view, and its arena range is appended to `dead`."""
+    views, grads = [], []
+    for p, v in sel:
+        if p.grad is v:
+            continue
+        if p.grad is None:
+            v.zero_()
+            dead.append((v.storage_offset(), v.numel()))
+        else:
+            views.append(v)
+            grads.append(p.grad)
+    if views:
+        torch._foreach_copy_(views, grads)
+    for p, v in sel:
+        p.grad = v
 
 
 def _attach_deferred(pairs):
@@ -446,14 +421,18 @@ class STEREODPNET(_PluginHooks, StereoDPNetCore):
     """src/model/stereodpnet/mainmodel.py::STEREODPNET (mainmodel.py:21-177)."""
 
 
-class PSMNET(_PluginHooks, PSMNetCore):
-    """src/model/psmnet/mainmodel.py::PSMNET; its validation hooks are no-ops in the reference (mainmodel.py:143-149)."""
+class _NoValidation(object):
+    """The validation hooks are no-ops in the reference (psmnet/mainmodel.py:143-149, dpnet/mainmodel.py:236-245)."""
 
     def validation_step(self, batch, batch_idx):
         return None
 
     def validation_epoch_end(self, outputs):
         return None
+
+
+class PSMNET(_NoValidation, _PluginHooks, PSMNetCore):
+    """src/model/psmnet/mainmodel.py::PSMNET."""
 
 
 class NNET(_PluginHooks, NNetCore):
@@ -464,15 +443,8 @@ class STEREONET(_PluginHooks, StereoNetCore):
     """src/model/stereonet/mainmodel.py::STEREONET (mainmodel.py:30-220)."""
 
 
-class DPNET(_PluginHooks, DPNetCore):
-    """src/model/dpnet/mainmodel.py::DPNET (mainmodel.py:29-270); its validation hooks are no-ops in the reference (mainmodel.py:236-245),
-    test_step runs the metric hooks (mainmodel.py:247-251)."""
-
-    def validation_step(self, batch, batch_idx):
-        return None
-
-    def validation_epoch_end(self, outputs):
-        return None
+class DPNET(_NoValidation, _PluginHooks, DPNetCore):
+    """src/model/dpnet/mainmodel.py::DPNET (mainmodel.py:29-270); test_step runs the metric hooks (mainmodel.py:247-251)."""
 
     def test_step(self, batch, batch_idx):
         return _PluginHooks.validation_step(self, batch, batch_idx)

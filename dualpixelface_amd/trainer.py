@@ -25,6 +25,7 @@ import time
 import torch
 
 from . import distributed as dd
+from . import optim
 
 
 def epoch_lr(option, epoch):
@@ -43,24 +44,6 @@ def epoch_lr(option, epoch):
 
 
 CKPT_VERSION = 2
-
-# optimizer_states[0]['kind'] of a checkpoint and the one state arena it carries, per option.optim beside Adam ('flat_adam': m, v, step)
-FLAT_STATE = {'sgd': ('flat_sgd', 'buf'), 'rmsprop': ('flat_rmsprop', 'sq')}
-
-
-def _optimizer_state(model, option):
-    """optimizer_states[0] of a checkpoint.  A model that only exposes `_adam` is written as before."""
-    optim = getattr(option, 'optim', 'adam')
-    if optim in FLAT_STATE and hasattr(model, '_optim'):
-        kind, name = FLAT_STATE[optim]
-        st = model._optim or {}
-        if st and st.get('kind') != optim:
-            raise ValueError("the model holds %r optimiser state while option.optim is %r" % (st.get('kind'), optim))
-        return {'kind': kind, name: st[name].detach().cpu() if st.get(name) is not None else None}
-    adam = getattr(model, '_adam', None) or {}
-    return {'kind': 'flat_adam', 'step': int(adam.get('step', 0)),
-            'm': adam['m'].detach().cpu() if 'm' in adam else None,
-            'v': adam['v'].detach().cpu() if 'v' in adam else None}
 
 
 class Trainer(object):
@@ -87,7 +70,7 @@ class Trainer(object):
             # convention a file follows (absent + no 'pytorch-lightning_version' = round-1 files: 'epoch' was the FINISHED epoch)
             'dpf_ckpt_version': CKPT_VERSION, 'epoch': self.epoch + 1, 'global_step': self.global_step + 1,
             'state_dict': {k: v.detach().cpu() for k, v in model.state_dict().items()},
-            'optimizer_states': [_optimizer_state(model, self.option)],
+            'optimizer_states': [optim.to_checkpoint(model, self.option)],
             'lr': epoch_lr(self.option, self.epoch),
             'hyper_parameters': {'model_name': getattr(self.option, 'model_name', 'stereodpnet')},
         }
@@ -131,22 +114,16 @@ class Trainer(object):
             # the same rule for the optimiser: state of another kind than option.optim selects cannot continue this run
             states = ckpt.get('optimizer_states') or []
             kind = states[0].get('kind') if states and isinstance(states[0], dict) else None
-            optim = getattr(self.option, 'optim', 'adam')
-            want = FLAT_STATE[optim][0] if optim in FLAT_STATE else 'flat_adam'
-            if kind in ('flat_adam', 'flat_sgd', 'flat_rmsprop') and kind != want:
+            want = optim.of(self.option).ckpt
+            if kind in [r.ckpt for r in optim.TABLE.values()] and kind != want:
                 raise ValueError("checkpoint %r holds %s optimiser state, option.optim = %r needs %s: resume with the optimiser the run was "
                                  "trained with, or load the weights only (load_checkpoint(..., resume=False) / --load_model without "
-                                 "resume).  Nothing was restored." % (path, kind, optim, want))
+                                 "resume).  Nothing was restored." % (path, kind, getattr(self.option, 'optim', 'adam'), want))
         model.load_state_dict(weights, strict=bool(getattr(self.option, 'load_strict', True)))
         if resume:
             self.epoch, self.global_step = epoch, global_step
-            states = ckpt.get('optimizer_states') or []
-            if states and states[0].get('kind') == 'flat_adam' and states[0].get('m') is not None:
-                dev = model.flat_parameters().device
-                model._adam = {'m': states[0]['m'].to(dev), 'v': states[0]['v'].to(dev), 'step': int(states[0]['step'])}
-            for optim, (kind, name) in FLAT_STATE.items():
-                if states and states[0].get('kind') == kind and states[0].get(name) is not None:
-                    model._optim = {'kind': optim, name: states[0][name].to(model.flat_parameters().device)}
+            if states:
+                optim.from_checkpoint(model, states[0])
         return ckpt
 
     # ------------------------------------------------------------------ loops
