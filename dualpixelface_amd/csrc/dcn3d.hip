@@ -1,7 +1,8 @@
 // Deformable 3-D convolution (D3D), im2col-free, 64-bit indexing.
 //
 // Drop-in for the reference's CUDA extension `DCN` (src/module/dcn3d/src/vision.cpp:4-7;
-// deform_conv_cuda.cu:18-285; kernels deform_im2col_cuda.cuh:26-405) for group = deformable_group = 1:
+// deform_conv_cuda.cu:18-285; kernels deform_im2col_cuda.cuh:26-405).  This file: the entry points and the kernels for
+// group = deformable_group = 1; larger group counts run on the kernels of dcn_grouped.hip.
 //   forward : out[b,k,p] = bias[k] + sum_{c,t} W[k,c,t] * trilinear(x[b,c], base(p,t) + offset[b,3t..3t+2,p])
 //   backward: grad_input (adjoint of the sampler), grad_offset (d sample / d coord), grad_weight, grad_bias
 // The reference materialises `columns` [C*27, B*P] (2.7 GB per 1024x1536 sample, int32 indices); here a workgroup
@@ -27,65 +28,6 @@ __device__ __forceinline__ int dpf_xcd_tile(int blk, int n) {
 constexpr int TP = 64;          // output voxels per workgroup
 constexpr int SP = TP + 1;      // padded LDS row
 constexpr int MAXC = 128;
-
-struct DcnP {
-  int B, C, K;
-  int D, H, W;        // input dims
-  int Do, Ho, Wo;     // output dims
-  int kd, kh, kw, T;
-  int sd, sh, sw, pd, ph, pw, dd, dh, dw;
-  int CP;             // C rounded up to even
-  long long P;        // Do*Ho*Wo
-  int tiles_per_b;
-  int nchunk;
-};
-
-struct Corner {   // per output voxel and tap
-  int d0, h0, w0;
-  float ld, lh, lw;
-  int valid;
-};
-
-struct Off3 {
-  float d, h, w;
-};
-
-// the three offset components of tap t at output voxel pos (cuh:238-243); zeros beyond the volume / tap range
-__device__ __forceinline__ Off3 load_off(const DcnP& p, const float* __restrict__ off_b, int t, long long pos) {
-  Off3 o = {0.f, 0.f, 0.f};
-  if (pos < p.P && t < p.T) {
-    o.d = off_b[(long long)(3 * t) * p.P + pos];
-    o.h = off_b[(long long)(3 * t + 1) * p.P + pos];
-    o.w = off_b[(long long)(3 * t + 2) * p.P + pos];
-  }
-  return o;
-}
-
-__device__ __forceinline__ Corner corner_from(const DcnP& p, int t, long long pos, const Off3& o) {
-  Corner c;
-  c.valid = 0;
-  c.d0 = c.h0 = c.w0 = 0;
-  c.ld = c.lh = c.lw = 0.f;
-  if (pos >= p.P) return c;
-  const int xo = (int)(pos % p.Wo);
-  const int yo = (int)((pos / p.Wo) % p.Ho);
-  const int zo = (int)(pos / ((long long)p.Wo * p.Ho));
-  const int tk = t % p.kw, tj = (t / p.kw) % p.kh, ti = t / (p.kw * p.kh);
-  const float fd = (float)(zo * p.sd - p.pd + ti * p.dd) + o.d;
-  const float fh = (float)(yo * p.sh - p.ph + tj * p.dh) + o.h;
-  const float fw = (float)(xo * p.sw - p.pw + tk * p.dw) + o.w;
-  if (fd > -1.f && fh > -1.f && fw > -1.f && fd < (float)p.D && fh < (float)p.H && fw < (float)p.W) {   // cuh:248
-    const float d0 = floorf(fd), h0 = floorf(fh), w0 = floorf(fw);
-    c.d0 = (int)d0; c.h0 = (int)h0; c.w0 = (int)w0;
-    c.ld = fd - d0; c.lh = fh - h0; c.lw = fw - w0;
-    c.valid = 1;
-  }
-  return c;
-}
-
-__device__ __forceinline__ Corner make_corner(const DcnP& p, const float* __restrict__ off_b, int t, long long pos) {
-  return corner_from(p, t, pos, load_off(p, off_b, t, pos));
-}
 
 // ---- division-free variants for the region kernels: the thread knows its output voxel (zo, yo, xo), the tap loop keeps the
 // tap's (ti, tj, tk) in scalars, and the offsets are read through a pointer that advances by 3*P per tap
@@ -149,15 +91,6 @@ __global__ void repack_weights_pad_kernel(const float* __restrict__ w, float* __
     }
     wt[i] = v;
   }
-}
-
-// corner j = (jd, jh, jw) bits; returns flat voxel index or -1 (cuh:43-65), weight (cuh:67-68)
-__device__ __forceinline__ long long corner_index(const DcnP& p, const Corner& c, int j, float& wgt) {
-  const int jd = (j >> 2) & 1, jh = (j >> 1) & 1, jw = j & 1;
-  const int d = c.d0 + jd, h = c.h0 + jh, w = c.w0 + jw;
-  wgt = (jd ? c.ld : 1.f - c.ld) * (jh ? c.lh : 1.f - c.lh) * (jw ? c.lw : 1.f - c.lw);
-  if (!c.valid || d < 0 || d > p.D - 1 || h < 0 || h > p.H - 1 || w < 0 || w > p.W - 1) return -1;
-  return ((long long)d * p.H + h) * p.W + w;
 }
 
 // 32-bit variant (the host checks D*H*W < 2^31)
@@ -1730,6 +1663,7 @@ DcnWs dcn_ws_map(int B, int C, int D, int H, int W, int K, int T, int det) {
   // which can exceed it -- C = 49..60 or 81..84 with 12-wide chunks)
   m.dwtmp = (long long)T * (((C + 31) / 32) * 32) * (((K + 63) / 64) * 64);
   if (T == 27 && dcn_lean_workspace_floats(C, K) > m.dwtmp) m.dwtmp = dcn_lean_workspace_floats(C, K);
+  m.dwtmp = (m.dwtmp + 1) & ~1LL;   // deterministic mode reads the replica region as 8-byte integers (today's repack sizes are all even)
   m.wmax = m.dwtmp + dcn_dwtmp_floats(T, (C + 11) / 12);   // chunks of >= 12 channels
   m.wexp = m.wmax + 63;
   m.shadow = (m.wexp + 1 + 3) / 4 * 4;
@@ -1908,6 +1842,32 @@ int dcn_bwd_gather(const DcnBwd& b, bool dx_done) {
   return dcn_launch(kern, dim3((unsigned)(p.T * p.nchunk)), dim3(256), lds, b.st, b.input, b.offset, b.grad_output, b.grad_weight, p);
 }
 
+// group > 1 or deformable_group > 1: the kernels of dcn_grouped.hip, with the repacked weights in the repack region of the workspace map and
+// the deterministic-mode shadow of grad_weight in its replica region.  Both regions are sized from whole C and K (K (C/group) T <= K C T), so
+// the caller's workspace queries hold for every grouping; the bounds are checked here all the same.
+int dcn_fwd_grouped(const DcnP& p, int group, int deformable_group, const float* input, const float* weight, const float* bias, const float* offset,
+                    float* output, float* ws, hipStream_t st) {
+  if (dcn_grouped_pack_floats(p, false) > dcn_ws_map(0, p.C, 0, 0, 0, p.K, p.T, 0).dwtmp) return DPF_ERR_UNSUPPORTED;
+  return dcn_grouped_forward(p, group, deformable_group, input, weight, bias, offset, output, ws, st);
+}
+
+int dcn_bwd_grouped(const DcnBwd& b, int group, int deformable_group, int grad_input_channels) {
+  const DcnP& p = b.p;
+  const long long dw_elems = (long long)p.K * (p.C / group) * p.T;
+  if (dcn_grouped_pack_floats(p, true) > b.m.dwtmp || (b.det && 4 * dw_elems > b.m.wmax - b.m.dwtmp)) return DPF_ERR_UNSUPPORTED;
+  long long* dw_shadow = nullptr;
+  if (b.det) {
+    dw_shadow = reinterpret_cast<long long*>(b.ws + b.m.dwtmp);
+    if (reinterpret_cast<uintptr_t>(dw_shadow) & 7) return DPF_ERR_INVALID_ARG;
+    if (hipMemsetAsync(dw_shadow, 0, sizeof(long long) * 2 * (size_t)dw_elems, b.st) != hipSuccess) return DPF_ERR_LAUNCH;
+  }
+  const int rc = dcn_grouped_backward(p, group, deformable_group, b.input, b.weight, b.offset, b.grad_output, b.grad_input, b.grad_offset, b.grad_weight,
+                                      b.ws, dw_shadow, b.gi_shadow, grad_input_channels, b.st);
+  if (rc != DPF_OK) return rc;
+  if (b.det) hipLaunchKernelGGL(dcn_gi_finalize_kernel, dim3(dpf_ew_grid(dw_elems)), dim3(256), 0, b.st, dw_shadow, b.grad_weight, dw_elems);
+  return DPF_OK;
+}
+
 }  // namespace
 
 const DcnEnv& dcn_env() {
@@ -1936,19 +1896,24 @@ long long dpf_deform_conv3d_backward_workspace_floats(int B, int C, int D, int H
 }
 
 // Mirrors DCN.deform_conv_forward(input, weight, bias, offset, kd,kh,kw, sd,sh,sw, pd,ph,pw, dd,dh,dw, group, deformable_group,
-// im2col_step) (deform_conv.h:10-29); group/deformable_group must be 1; im2col_step is accepted and ignored (no columns).
-// Three tiers: lean kernels (the model's configuration) -> role-split region kernel -> gather kernel; DPF_DCN_V1 leaves only the last.
+// im2col_step) (deform_conv.h:10-29); im2col_step is accepted and ignored (no columns).
+// weight is [K][C/group][T], offset [B][deformable_group * 3T][P]; group must divide C and K, deformable_group must divide C, else
+// DPF_ERR_INVALID_ARG with nothing launched.
+// group = deformable_group = 1, three tiers: lean kernels (the model's configuration) -> role-split region kernel -> gather kernel; DPF_DCN_V1
+// leaves only the last.  Any other grouping: dcn_grouped.hip (fp32 matrix instruction for every setting of dpf_set_f32_matrix_path).
 int dpf_deform_conv3d_forward(const float* input, const float* weight, const float* bias, const float* offset, float* output, float* ws,
                               int B, int C, int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph,
                               int pw, int dd, int dh, int dw, int group, int deformable_group, int im2col_step, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   (void)im2col_step;
   if (!input || !weight || !offset || !output || !ws) return DPF_ERR_INVALID_ARG;
-  if (group != 1 || deformable_group != 1) return DPF_ERR_UNSUPPORTED;
+  const bool grouped = group != 1 || deformable_group != 1;
+  if (grouped && dcn_group_check(C, K, group, deformable_group) != DPF_OK) return DPF_ERR_INVALID_ARG;
   DcnP p{};
   int rc = fill_params(p, B, C, D, H, W, K, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw);
   if (rc != DPF_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
+  if (grouped) return dcn_fwd_grouped(p, group, deformable_group, input, weight, bias, offset, output, ws, st);
   rc = DPF_ERR_UNSUPPORTED;
   if (!dcn_env().v1) {
     if (dcn_is_model_config(kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw)) rc = dcn_lean_forward(input, offset, weight, bias, output, ws, B, C, D, H, W, K, st);
@@ -1962,6 +1927,9 @@ int dpf_deform_conv3d_forward(const float* input, const float* weight, const flo
 // grad_input / grad_weight / grad_bias are zero-initialised here, like the reference's at::zeros_like (cu:202-205).
 // grad_input is only produced for input channels [0, grad_input_channels) (the remaining channels of the zero-initialised tensor stay 0):
 // StereoDPNet's first deformable conv consumes 32 cost channels + 3 constant XYZ channels (normal_module.py:166), whose gradient nobody reads.
+// Grouping as in the forward (grad_weight is [K][C/group][T], grad_offset [B][deformable_group * 3T][P]); grad_input_channels counts whole-tensor
+// channels whatever group they are in.  A grouped call stores every grad_offset element once (reproducible in every mode); its grad_input and
+// grad_weight merge through float atomics, or in deterministic mode through the same integer shadows as the single-group tiers.
 int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const float* bias, const float* offset, const float* grad_output,
                                   float* grad_input, float* grad_offset, float* grad_weight, float* grad_bias, float* ws, int B, int C,
                                   int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd,
@@ -1969,7 +1937,8 @@ int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   (void)im2col_step; (void)bias;
   if (!input || !weight || !offset || !grad_output || !grad_input || !grad_offset || !grad_weight || !ws) return DPF_ERR_INVALID_ARG;
-  if (group != 1 || deformable_group != 1) return DPF_ERR_UNSUPPORTED;
+  const bool grouped = group != 1 || deformable_group != 1;
+  if (grouped && dcn_group_check(C, K, group, deformable_group) != DPF_OK) return DPF_ERR_INVALID_ARG;
   DcnBwd b{input, weight, offset, grad_output, grad_input, grad_offset, grad_weight, ws};
   int rc = fill_params(b.p, B, C, D, H, W, K, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw);
   if (rc != DPF_OK) return rc;
@@ -1986,13 +1955,17 @@ int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const
     if (reinterpret_cast<uintptr_t>(b.gi_shadow) & 7) return DPF_ERR_INVALID_ARG;
     if (hipMemsetAsync(b.gi_shadow, 0, sizeof(long long) * 2 * (size_t)in_elems, b.st) != hipSuccess) return DPF_ERR_LAUNCH;
   }
-  if (hipMemsetAsync(grad_weight, 0, sizeof(float) * (size_t)K * C * b.p.T, b.st) != hipSuccess) return DPF_ERR_LAUNCH;
-  // grad_input: packed LDS scatter, or left to the gather kernel.  grad_offset + grad_weight: lean -> region (beside the packed scatter
-  // only) -> gather.
-  rc = dcn_bwd_grad_input(b, grad_input_channels);
-  const bool dx_done = rc == DPF_OK;
-  if (dx_done) rc = dcn_bwd_offset_weight(b, dcn_is_model_config(kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw));
-  if (rc == DPF_ERR_UNSUPPORTED) rc = dcn_bwd_gather(b, dx_done);
+  if (hipMemsetAsync(grad_weight, 0, sizeof(float) * (size_t)K * (grouped ? C / group : C) * b.p.T, b.st) != hipSuccess) return DPF_ERR_LAUNCH;
+  if (grouped) {
+    rc = dcn_bwd_grouped(b, group, deformable_group, grad_input_channels);
+  } else {
+    // grad_input: packed LDS scatter, or left to the gather kernel.  grad_offset + grad_weight: lean -> region (beside the packed scatter
+    // only) -> gather.
+    rc = dcn_bwd_grad_input(b, grad_input_channels);
+    const bool dx_done = rc == DPF_OK;
+    if (dx_done) rc = dcn_bwd_offset_weight(b, dcn_is_model_config(kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw));
+    if (rc == DPF_ERR_UNSUPPORTED) rc = dcn_bwd_gather(b, dx_done);
+  }
   if (rc != DPF_OK) return rc;
   if (b.det) hipLaunchKernelGGL(dcn_gi_finalize_kernel, dim3(dpf_ew_grid(in_elems)), dim3(256), 0, b.st, b.gi_shadow, grad_input, in_elems);
   if (grad_bias) {

@@ -17,6 +17,77 @@ __device__ __forceinline__ void dcn_acc_add(float* base, long long* shadow, floa
 }
 #endif
 
+// Geometry of one call and the sampling rule, shared by the translation units of the family (dcn3d.hip, dcn_grouped.hip).
+struct DcnP {
+  int B, C, K;
+  int D, H, W;        // input dims
+  int Do, Ho, Wo;     // output dims
+  int kd, kh, kw, T;
+  int sd, sh, sw, pd, ph, pw, dd, dh, dw;
+  int CP;             // C rounded up to even
+  long long P;        // Do*Ho*Wo
+  int tiles_per_b;
+  int nchunk;
+};
+
+struct Corner {   // per output voxel and tap
+  int d0, h0, w0;
+  float ld, lh, lw;
+  int valid;
+};
+
+struct Off3 {
+  float d, h, w;
+};
+
+#ifdef __HIPCC__
+// the three offset components of tap t at output voxel pos (cuh:238-243); zeros beyond the volume / tap range
+__device__ __forceinline__ Off3 load_off(const DcnP& p, const float* __restrict__ off_b, int t, long long pos) {
+  Off3 o = {0.f, 0.f, 0.f};
+  if (pos < p.P && t < p.T) {
+    o.d = off_b[(long long)(3 * t) * p.P + pos];
+    o.h = off_b[(long long)(3 * t + 1) * p.P + pos];
+    o.w = off_b[(long long)(3 * t + 2) * p.P + pos];
+  }
+  return o;
+}
+
+__device__ __forceinline__ Corner corner_from(const DcnP& p, int t, long long pos, const Off3& o) {
+  Corner c;
+  c.valid = 0;
+  c.d0 = c.h0 = c.w0 = 0;
+  c.ld = c.lh = c.lw = 0.f;
+  if (pos >= p.P) return c;
+  const int xo = (int)(pos % p.Wo);
+  const int yo = (int)((pos / p.Wo) % p.Ho);
+  const int zo = (int)(pos / ((long long)p.Wo * p.Ho));
+  const int tk = t % p.kw, tj = (t / p.kw) % p.kh, ti = t / (p.kw * p.kh);
+  const float fd = (float)(zo * p.sd - p.pd + ti * p.dd) + o.d;
+  const float fh = (float)(yo * p.sh - p.ph + tj * p.dh) + o.h;
+  const float fw = (float)(xo * p.sw - p.pw + tk * p.dw) + o.w;
+  if (fd > -1.f && fh > -1.f && fw > -1.f && fd < (float)p.D && fh < (float)p.H && fw < (float)p.W) {   // cuh:248
+    const float d0 = floorf(fd), h0 = floorf(fh), w0 = floorf(fw);
+    c.d0 = (int)d0; c.h0 = (int)h0; c.w0 = (int)w0;
+    c.ld = fd - d0; c.lh = fh - h0; c.lw = fw - w0;
+    c.valid = 1;
+  }
+  return c;
+}
+
+__device__ __forceinline__ Corner make_corner(const DcnP& p, const float* __restrict__ off_b, int t, long long pos) {
+  return corner_from(p, t, pos, load_off(p, off_b, t, pos));
+}
+
+// corner j = (jd, jh, jw) bits; returns flat voxel index or -1 (cuh:43-65), weight (cuh:67-68)
+__device__ __forceinline__ long long corner_index(const DcnP& p, const Corner& c, int j, float& wgt) {
+  const int jd = (j >> 2) & 1, jh = (j >> 1) & 1, jw = j & 1;
+  const int d = c.d0 + jd, h = c.h0 + jh, w = c.w0 + jw;
+  wgt = (jd ? c.ld : 1.f - c.ld) * (jh ? c.lh : 1.f - c.lh) * (jw ? c.lw : 1.f - c.lw);
+  if (!c.valid || d < 0 || d > p.D - 1 || h < 0 || h > p.H - 1 || w < 0 || w > p.W - 1) return -1;
+  return ((long long)d * p.H + h) * p.W + w;
+}
+#endif
+
 // The family's environment switches (README "Environment switches"), read once per process by dcn_env() (dcn3d.hip).
 struct DcnEnv {
   bool v1;           // DPF_DCN_V1 set: first-generation gather kernels only
@@ -57,3 +128,16 @@ int dcn_lean_forward(const float* x, const float* offset, const float* weight, c
 // det != 0: the partials are added as integer pairs into replica 0 read as long long [27][nchunk][64][16][2] (deterministic mode).
 int dcn_lean_bwd_offset(const float* x, const float* offset, const float* weight, const float* go, float* doff, float* dwtmp, float* ws, int B, int C,
                         int D, int H, int W, int K, hipStream_t st, int det = 0);
+
+// group > 1 or deformable_group > 1 (dcn_grouped.hip): the grouping as a kernel argument, a fixed number of launches per call, every product on
+// the fp32 matrix instruction.  dcn_group_check: DPF_ERR_INVALID_ARG unless group divides C and K and deformable_group divides C.
+// wpack: dcn_grouped_pack_floats(p, backward) floats for the repacked block-diagonal weights.  Backward: grad_input / grad_weight zero-initialised
+// by the caller; deterministic mode: dw_shadow / gi_shadow = zero-initialised integer shadows (dcn_acc_add) of grad_weight [K][C/group][T] and
+// grad_input that the caller folds, else nullptr.  grad_offset is stored once per element in either mode.
+int dcn_group_check(int C, int K, int group, int deformable_group);
+long long dcn_grouped_pack_floats(const DcnP& p, bool backward);
+int dcn_grouped_forward(const DcnP& p, int group, int deformable_group, const float* input, const float* weight, const float* bias,
+                        const float* offset, float* output, float* wpack, hipStream_t st);
+int dcn_grouped_backward(const DcnP& p, int group, int deformable_group, const float* input, const float* weight, const float* offset,
+                         const float* grad_output, float* grad_input, float* grad_offset, float* grad_weight, float* wpack, long long* dw_shadow,
+                         long long* gi_shadow, int grad_input_channels, hipStream_t st);

@@ -1360,24 +1360,25 @@ class DeformConvFn(torch.autograd.Function):
     """Same contract as the reference's DeformConvFunction (src/module/dcn3d/functions/deform_conv_func.py:16-59)."""
 
     @staticmethod
-    def forward(ctx, x, offset, weight, bias, stride, pad, dil, gi_channels=None):
+    def forward(ctx, x, offset, weight, bias, stride, pad, dil, gi_channels=None, group=1, deformable_group=1):
         x, offset, weight, bias = _c(x), _c(offset), _c(weight), _c(bias)
         _need(x, offset, weight, bias)
-        ctx.cfg = (stride, pad, dil)
+        ctx.cfg = (stride, pad, dil, group, deformable_group)
         ctx.gi_channels = gi_channels
         ctx.save_for_backward(x, offset, weight, bias)
-        return deform_conv_forward_raw(x, weight, bias, offset, stride, pad, dil)
+        return deform_conv_forward_raw(x, weight, bias, offset, stride, pad, dil, group, deformable_group)
 
     @staticmethod
     def backward(ctx, go):
         x, offset, weight, bias = ctx.saved_tensors
         gi, goff, gw, gb = deform_conv_backward_raw(x, weight, bias, offset, _c(go), *ctx.cfg, gi_channels=ctx.gi_channels)
-        return gi, goff, gw, gb, None, None, None, None
+        return gi, goff, gw, gb, None, None, None, None, None, None
 
 
-def deform_conv3d(x, offset, weight, bias, stride=1, pad=1, dil=1, gi_channels=None):
-    """gi_channels: only the first gi_channels input channels need a gradient (the others' grad_input stays zero)."""
-    return DeformConvFn.apply(x, offset, weight, bias, _t3(stride), _t3(pad), _t3(dil), gi_channels)
+def deform_conv3d(x, offset, weight, bias, stride=1, pad=1, dil=1, gi_channels=None, group=1, deformable_group=1):
+    """gi_channels: only the first gi_channels input channels need a gradient (the others' grad_input stays zero).
+    group / deformable_group: weight [K, C / group, kd, kh, kw], offset [B, deformable_group * 3 T, Do, Ho, Wo] (the reference's semantics)."""
+    return DeformConvFn.apply(x, offset, weight, bias, _t3(stride), _t3(pad), _t3(dil), gi_channels, group, deformable_group)
 
 
 # ----------------------------------------------------------------------------------------------- normal module glue

@@ -272,7 +272,24 @@ int dpf_get_deterministic(void);
 int dpf_debug_clock_probe(unsigned long long* out4, int spin_us, void* stream);
 
 /* ---- deformable conv3d: the reference's pybind module `DCN` (src/module/dcn3d/src/vision.cpp:4-7,
- * src/module/dcn3d/src/deform_conv.h:10-29,49-69; deform_conv_cuda.cu:18-285) -- same argument order and meaning ----- */
+ * src/module/dcn3d/src/deform_conv.h:10-29,49-69; deform_conv_cuda.cu:18-285) -- same argument order and meaning -----
+ * GROUPING (deform_conv_cuda.cu:65-66,84-121; deform_im2col_cuda.cuh:222-232): weight is [K][C/group][kd][kh][kw], offset
+ * [B][deformable_group * 3 T][Do][Ho][Wo] (T = kd kh kw).  Input channel c is sampled with the offsets of deformable group
+ * c / (C/deformable_group); output channel k of conv group k / (K/group) contracts over input channels [g C/group, (g+1) C/group).  group must
+ * divide C and K and deformable_group must divide C: otherwise DPF_ERR_INVALID_ARG, nothing launched, nothing written.  Whole C, K <= 128 and
+ * T <= 64 for every grouping.
+ * PRECISION: group = deformable_group = 1 follows dpf_set_f32_matrix_path (split-operand matrix paths with their range guards).  Any other
+ * grouping runs every product on the fp32 matrix instruction whatever that switch says; the split-operand paths do not cover it.
+ * NON-FINITE DATA: the grouped path multiplies by a block-diagonal weight, and conv groups narrower than 32 rows share a 32-row tile of the
+ * matrix instruction, so a NaN or Inf in the input samples or in grad_output of one conv group (times an exact zero) becomes a NaN in the
+ * output, grad_input and grad_offset of the other conv groups of that tile.  The reference keeps conv groups independent; for finite data
+ * the results agree.
+ * SPEED: the grouped path is a gather tier (samples from global memory, grad_input through global atomics), several times slower than the
+ * single-group tiers at the same size (profiles/grouped_dcn_timings.txt).
+ * WORKSPACE: the two queries below take whole C and K and are sufficient for every grouping.
+ * grad_input_channels (the _ex entry) counts channels of the whole input tensor: channels at or beyond it stay zero whatever conv or
+ * deformable group they are in.  A grouped call stores each grad_offset element exactly once (bitwise reproducible in every mode); its
+ * grad_input and grad_weight are reproducible under dpf_set_deterministic(1) like the single-group ones. */
 long long dpf_deform_conv3d_workspace_floats(int C, int K, int T);
 /* workspace of dpf_deform_conv3d_backward* for this problem: the above, plus (deterministic mode only) the integer shadow of grad_input */
 long long dpf_deform_conv3d_backward_workspace_floats(int B, int C, int D, int H, int W, int K, int T);
