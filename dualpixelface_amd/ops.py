@@ -1381,6 +1381,82 @@ def deform_conv3d(x, offset, weight, bias, stride=1, pad=1, dil=1, gi_channels=N
     return DeformConvFn.apply(x, offset, weight, bias, _t3(stride), _t3(pad), _t3(dil), gi_channels, group, deformable_group)
 
 
+# ----------------------------------------------------------------------------------------------- deformable conv 2-D (plain / modulated)
+def _t2(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def deform_conv2d_forward_raw(x, weight, bias, offset, mask, stride, pad, dil, group=1, dgroup=1, out=None):
+    """dpf_deform_conv2d_forward: x [B, C, H, W], weight [K, C / group, kh, kw], bias [K] or None, offset [B, dgroup * 2 T, Ho, Wo],
+    mask [B, dgroup * T, Ho, Wo] or None (the plain operator) -> [B, K, Ho, Wo] (written into `out` when the caller brings that tensor)."""
+    B, C, H, W = x.shape
+    K, _, kh, kw = weight.shape
+    L = lib()
+    ho = _out_dim(H, kh, stride[0], pad[0], dil[0])
+    wo = _out_dim(W, kw, stride[1], pad[1], dil[1])
+    if out is None:
+        out = torch.empty((B, K, max(ho, 0), max(wo, 0)), dtype=torch.float32, device=x.device)
+    ws = scratch(L.call('dpf_deform_conv2d_workspace_floats', C, K, kh * kw), x.device, 'convw')
+    # algorithmic work: the GEMM part 2 B P K (C / group) T FLOP (the 4 C T sample FMAs per position are not counted)
+    with _Timed('dcn2d_fwd', 2.0 * B * K * (C // max(group, 1)) * kh * kw * ho * wo, 'dcn2f C%d K%d %dx%d' % (C, K, H, W),
+                4.0 * (x.numel() + offset.numel() + (0 if mask is None else mask.numel()) + out.numel())):
+        L.call('dpf_deform_conv2d_forward', _ptr(x), _ptr(weight), _ptr(bias), _ptr(offset), _ptr(mask), _ptr(out), _ptr(ws), B, C, H, W, K, kh, kw,
+               *stride, *pad, *dil, group, dgroup, _stream())
+    return out
+
+
+def deform_conv2d_backward_raw(x, weight, bias, offset, mask, go, stride, pad, dil, group=1, dgroup=1, want=(True, True, True, True, True),
+                               goff_out=None, gm_out=None):
+    """dpf_deform_conv2d_backward -> (grad_input, grad_offset, grad_mask, grad_weight, grad_bias); grad_mask is None without a mask, grad_bias
+    without a bias.  want: which of the five to produce -- the C ABI launches no data kernel when none of the first three is wanted, no
+    weight kernel without the fourth and no bias reduction without the fifth; an unwanted one comes back as None.  goff_out / gm_out: tensors
+    of the caller's that grad_offset / grad_mask are written into."""
+    B, C, H, W = x.shape
+    K, _, kh, kw = weight.shape
+    L = lib()
+    data = want[0] or want[1] or (want[2] and mask is not None)
+    gi = torch.empty_like(x) if want[0] else None
+    goff = (torch.empty_like(offset) if goff_out is None else goff_out) if data else None
+    gm = (torch.empty_like(mask) if gm_out is None else gm_out) if data and mask is not None else None
+    gw = torch.empty_like(weight) if want[3] else None
+    gb = torch.empty_like(bias) if want[4] and bias is not None else None
+    ws = scratch(L.call('dpf_deform_conv2d_backward_workspace_floats', B, C, H, W, K, kh * kw), x.device, 'convw')
+    cg = C // max(group, 1)
+    with _Timed('dcn2d_bwd', 2.0 * K * cg * kh * kw * go.numel() / K * ((1 if data else 0) + (1 if want[3] else 0)), 'dcn2b C%d K%d %dx%d' % (C, K, H, W),
+                4.0 * (x.numel() + 2 * offset.numel() + go.numel() + (x.numel() if want[0] else 0))):
+        L.call('dpf_deform_conv2d_backward', _ptr(x), _ptr(weight), _ptr(bias), _ptr(offset), _ptr(mask), _ptr(go), _ptr(gi), _ptr(goff), _ptr(gm),
+               _ptr(gw), _ptr(gb), _ptr(ws), B, C, H, W, K, kh, kw, *stride, *pad, *dil, group, dgroup, _stream())
+    return gi, goff, gm, gw, gb
+
+
+class DeformConv2dFn(torch.autograd.Function):
+    """The reference's DeformConvFunction (mask None) and ModulatedDeformConvFunction (src/module/dcn/deform_conv.py:14-97,100-154) in one."""
+
+    @staticmethod
+    def forward(ctx, x, offset, mask, weight, bias, stride, pad, dil, group, deformable_group):
+        x, offset, weight = _c(x), _c(offset), _c(weight)
+        mask = None if mask is None else _c(mask)
+        bias = None if bias is None else _c(bias)
+        _need(x, offset, mask, weight, bias)
+        ctx.cfg = (stride, pad, dil, group, deformable_group)
+        ctx.save_for_backward(x, offset, mask, weight, bias)
+        return deform_conv2d_forward_raw(x, weight, bias, offset, mask, stride, pad, dil, group, deformable_group)
+
+    @staticmethod
+    def backward(ctx, go):
+        x, offset, mask, weight, bias = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = (need[0], need[1], need[2] and mask is not None, need[3], need[4] and bias is not None)
+        gi, goff, gm, gw, gb = deform_conv2d_backward_raw(x, weight, bias, offset, mask, _c(go), *ctx.cfg, want=want)
+        return gi, goff, gm, gw, gb, None, None, None, None, None
+
+
+def deform_conv2d(x, offset, mask, weight, bias=None, stride=1, pad=0, dil=1, group=1, deformable_group=1):
+    """2-D deformable convolution: mask None = DCN v1 (DeformConv), else the modulated v2 (ModulatedDeformConv).  weight [K, C / group, kh, kw],
+    offset [B, deformable_group * 2 T, Ho, Wo] (h, w per tap), mask [B, deformable_group * T, Ho, Wo]: the reference's semantics."""
+    return DeformConv2dFn.apply(x, offset, mask, weight, bias, _t2(stride), _t2(pad), _t2(dil), group, deformable_group)
+
+
 # ----------------------------------------------------------------------------------------------- normal module glue
 class AnmVolumeFn(torch.autograd.Function):
     @staticmethod

@@ -307,6 +307,45 @@ int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const
                                   int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd,
                                   int dh, int dw, int group, int deformable_group, int im2col_step, int grad_input_channels, void* stream);
 
+/* ---- deformable conv2d, plain (DCN v1) and modulated (v2): the reference's pybind module `deform_conv_cuda`
+ * (src/module/dcn/src/deform_conv_cuda.cpp:687-697 over src/deform_conv_cuda_kernel.cu:190,279,373,570,635,695; DeformConv / DeformConvPack /
+ * ModulatedDeformConv / ModulatedDeformConvPack of src/module/dcn/deform_conv.py).  Native 2-D kernels (csrc/dcn2d.hip), not the 3-D entry at
+ * depth 1.
+ * LAYOUTS: input [B][C][H][W], weight [K][C/group][kh][kw], bias [K] or NULL, output / grad_output [B][K][Ho][Wo] with
+ * Ho = (H + 2 ph - (dh (kh - 1) + 1)) / sh + 1.  offset [B][deformable_group * 2 T][Ho][Wo] (T = kh kw): channel 2 (i kw + j) is the h component
+ * and channel 2 (i kw + j) + 1 the w component of tap (i, j).  mask [B][deformable_group * T][Ho][Wo], or NULL for the plain (v1) operator.
+ * SAMPLING: tap (i, j) of output (ho, wo) reads h = ho sh - ph + i dh + off_h, w likewise, bilinearly; it counts only if h > -1, w > -1, h < H,
+ * w < W; corners outside the image contribute 0; the sample is multiplied by its mask value.  The coordinate gradient of a sample that does
+ * not count is 0; grad_mask is the sum over the deformable group's channels of gcol times the unmasked sample.
+ * GROUPING: input channel c uses deformable group c / (C/deformable_group); output channel k of conv group k / (K/group) contracts over input
+ * channels [g C/group, (g+1) C/group).  group must divide C and K and deformable_group must divide C: otherwise DPF_ERR_INVALID_ARG.
+ * LIMITS: whole C, K <= 256, T <= 49 (7 x 7), H W < 2^31; any stride >= 1, padding >= 0, dilation >= 1, non-square windows included.  Beyond
+ * them DPF_ERR_UNSUPPORTED.  Every refusal launches nothing and writes nothing.
+ * PRECISION: every product runs on the fp32 matrix instruction (v_mfma_f32_32x32x2_f32) for every setting of dpf_set_f32_matrix_path; the
+ * split-operand paths and their range guards do not cover this operator.  NON-FINITE DATA: as for the grouped 3-D path above.
+ * RESULTS: every result tensor passed is fully written by the call (pass uninitialised memory; what is accumulated into is zero-filled
+ * here).  Of the backward's results grad_input, grad_offset, grad_mask, grad_weight and grad_bias each may be NULL (not wanted): without
+ * grad_input, grad_offset and grad_mask the data kernel is not launched, without grad_weight the weight kernel is not.  grad_mask needs mask.
+ * REPRODUCIBILITY: output, grad_offset and grad_mask are stored once per element, no atomics: bitwise reproducible in every mode.
+ * grad_input (four-corner scatter) and grad_weight (partials of position chunks) merge through float atomics, or under
+ * dpf_set_deterministic(1) through integer shadows in the workspace; grad_bias is dpf_channel_sum's reduction (float atomics between the
+ * workgroups of a channel, one workgroup per channel in deterministic mode).  These three are bitwise reproducible only under
+ * dpf_set_deterministic(1).
+ * WORKSPACE: the queries take whole C and K and hold for every grouping; the backward query includes the shadows in deterministic mode (ask
+ * in the mode the call runs in).  ws 8-byte aligned.  No allocation, no synchronisation.
+ * SPEED: a gather tier (samples from global memory, grad_input through global atomics).  At B=4, C=K=64, 256x384, 3x3, group 1,
+ * deformable_group 2 the forward takes 1.25 ms (modulated 1.27 ms) and the backward 20.3 ms; the same plain problem through
+ * dpf_deform_conv3d_* at depth 1 takes 1.73 ms and 20.8 ms (profiles/dcn2d_timings.txt).  The backward is bound by the grad_input atomics. */
+long long dpf_deform_conv2d_workspace_floats(int C, int K, int T);
+long long dpf_deform_conv2d_backward_workspace_floats(int B, int C, int H, int W, int K, int T);
+int dpf_deform_conv2d_forward(const float* input, const float* weight, const float* bias, const float* offset, const float* mask, float* output,
+                              float* ws, int B, int C, int H, int W, int K, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                              int group, int deformable_group, void* stream);
+int dpf_deform_conv2d_backward(const float* input, const float* weight, const float* bias, const float* offset, const float* mask,
+                               const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
+                               float* grad_bias, float* ws, int B, int C, int H, int W, int K, int kh, int kw, int sh, int sw, int ph, int pw,
+                               int dh, int dw, int group, int deformable_group, void* stream);
+
 /* ---- Adaptive Normal Module glue (src/model/stereodpnet/normal_module.py:80-138,154-167,185-190) ------------------ */
 int dpf_anm_select(const float* disp_full, int* idx, float* sdisp, const float* costrange_host, int B, int H, int W, int h, int w, int L,
                    int K, void* stream);
