@@ -149,6 +149,8 @@ __device__ __forceinline__ void dpf_split_pair(float x, float y, unsigned& h, un
 //   * wgrad2_kernel (output = sum over positions for a (g channel, x channel) pair): per CHANNEL.  Every g row and every x channel of the
 //     workgroup carries its own running exponent (rows / columns of the MFMA tile may be scaled independently);
 //   * the deformable conv's gcol products (output = sum over the output channels of a voxel): per VOXEL.
+//   * the deformable conv's weight-gradient partial (dcn_lean_bwd_offset_kernel<.., WH>; output = sum over voxels for a (go channel, x channel)
+//     pair): per go ROW of the workgroup's tile and per x CHANNEL of the staged chunk.
 typedef _Float16 dpf_f16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned dpf_pk_f16(float x, float y) {       // round to nearest even (the f16 rounding mode of the kernel)
   unsigned r;

@@ -94,7 +94,7 @@ struct DcnEnv {
   int lean;          // DPF_DCN_LEAN (1): 0 = lean kernels off; bit 2 (4) = only the lean grad_offset kernel off
   int fwd6;          // DPF_DCN_FWD6 (1): 0 = lean forward on the fp32 matrix instruction
   int lean_wide12;   // DPF_DCN_LEAN_WIDE12 (0): 1 = 12-channel lean forward on the wider x halo, one workgroup per CU (3.7 vs 2.6 ms)
-  int gcol16;        // DPF_DCN_GCOL16 (1): 0 = the backward's gcol products on the fp32 matrix instruction
+  int gcol16;        // DPF_DCN_GCOL16 (1): 0 = the backward's gcol and weight-gradient products on the fp32 matrix instruction
 };
 const DcnEnv& dcn_env();
 

@@ -81,10 +81,11 @@ __device__ __forceinline__ void pk_fma_hi(f32x2& acc, f32x2 w, f32x2 v) {   // a
 
 // Stage x[b, c0 .. c0 + CH) over the region rows [ry0, ry0 + RY) x columns [rx0, rx0 + RX) x all D planes into region[q][cell][4];
 // cells outside the volume and channels beyond C are zeros.  A unit = 4 channels x 4 consecutive x: four float4 loads, a register
-// transpose, four ds_write_b128 into 64 consecutive bytes.
-template <class G>
+// transpose, four ds_write_b128 into 64 consecutive bytes.  EXP: the largest biased exponent of every staged channel is folded into
+// exps[channel of the chunk] (LDS, preset by the caller; an integer max, and only by the lanes that would raise it).
+template <class G, bool EXP = false>
 __device__ __forceinline__ void lean_stage(const LeanP& p, const float* __restrict__ xb, int c0, char* region, int ry0, int rx0, int tid,
-                                           int nthreads) {
+                                           int nthreads, int* exps = nullptr) {
   constexpr int SR = G::RX / 4;
   const long long chan = p.P;
   const int units = p.D * G::RY * G::NQ * SR;
@@ -105,6 +106,15 @@ __device__ __forceinline__ void lean_stage(const LeanP& p, const float* __restri
     *reinterpret_cast<f32x4*>(dst + 16) = f32x4{v[0].y, v[1].y, v[2].y, v[3].y};
     *reinterpret_cast<f32x4*>(dst + 32) = f32x4{v[0].z, v[1].z, v[2].z, v[3].z};
     *reinterpret_cast<f32x4*>(dst + 48) = f32x4{v[0].w, v[1].w, v[2].w, v[3].w};
+    if constexpr (EXP) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float m = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v[q].x), __builtin_fabsf(v[q].y)),
+                                        __builtin_fmaxf(__builtin_fabsf(v[q].z), __builtin_fabsf(v[q].w)));
+        const int e = (int)(__builtin_bit_cast(unsigned, m) >> 23);
+        if (e > exps[4 * cg + q]) atomicMax(&exps[4 * cg + q], e);
+      }
+    }
   }
 }
 
@@ -694,23 +704,27 @@ __global__ __launch_bounds__(256, 2) void dcn_lean_fwd6_kernel(const float* __re
 // deform_conv_cuda.cu:220-279).  Per (chunk, tap) step:
 //   gcol[c][v] = sum_k W[k][c][t] go[k][v]                      (matrix waves, v_mfma_f32_16x16x4_f32: rows = channels)
 //   S[c][v]    = trilinear sample of x[c] at (v, t);  grad_offset[3t + axis][v] += sum_c gcol[c][v] dS[c][v] / d(coord)     (samplers)
-//   dW[k][c][t] += sum_v go[k][v] S[c][v]                        (matrix waves)
+//   dW[k][c][t] += sum_v go[k][v] S[c][v]                        (matrix waves; WH: v_mfma_f32_16x16x32_f16, see below)
 // Eight waves: 4 samplers (a voxel per lane, all CH channels -- the lean sampler of the forward kernel plus one dot product per corner)
 // and 4 matrix waves that each run BOTH products (on this chip a wave issuing fp32 MFMAs back to back starves the other waves of its
 // SIMD of vector and LDS issue -- tools/lean_probe.hip -- so the two matrix roles of round 3, one wave each, were serialised anyway).
 // Tiles: G[2][q][voxel][4] (gcol, quad planar: the 16x16 MFMA result of a lane IS one quad of one voxel -> one ds_write_b128; the sampler
 // reads its voxel's CH values as NQ ds_read_b128) and S[2][CH][260] (channel major: the weight-gradient B operands of 4 consecutive voxels
-// are one ds_read_b128).  Step i: matrix waves write G(i + 1) and contract S(i - 1); samplers read G(i), write S(i); one barrier.
+// are one ds_read_b128; with WH the tile is S[2][hi | lo][CH][264 halves] instead, see below).  Step i: matrix waves write G(i + 1) and contract S(i - 1); samplers read G(i), write S(i); one barrier.
 constexpr int LEAN_SS = 260;          // padded row of the S tile (floats)
+constexpr int LEAN_SH = 264;          // WH: padded row of one component plane of the S tile (halves): 132 words = 4 mod 64 banks
 constexpr int LEAN_NREP = DCN_WG_NREP; // replicas of the grad_weight scratch tensor (dcn_internal.h; layout [rep][T][nchunk][64][16], folded by dcn3d.hip)
 
-template <class G>
+template <class G, bool WH>
 struct BwdLds {
   static constexpr int GT = G::NQ * G::SQ;                     // one gcol tile (bytes)
-  static constexpr int ST = G::CH * LEAN_SS * 4;               // one sample tile (bytes)
+  static constexpr int SP = G::CH * LEAN_SH * 2;               // WH: one component plane of a sample tile (bytes)
+  static constexpr int ST = WH ? 2 * SP : G::CH * LEAN_SS * 4; // one sample tile (bytes); WH: hi plane, lo plane
   static constexpr int OFF_G = G::NQ * G::PLANE;
   static constexpr int OFF_S = OFF_G + 2 * GT;
-  static constexpr int LDS = OFF_S + 2 * ST;
+  static constexpr int OFF_E = OFF_S + 2 * ST;                 // WH: channel exponents of the staged region, [chunk parity][16] ints
+  static constexpr int LDS = OFF_E + (WH ? 2 * 16 * 4 : 0);
+  static_assert(LDS <= 160 * 1024 && OFF_E % 16 == 0, "one workgroup per CU");
   static_assert(G::NV == 256, "4 sampler waves + 4 matrix waves of 64 voxels");
 };
 
@@ -720,19 +734,41 @@ struct BwdLds {
 // samplers are unchanged.  RANGE GUARD: a gcol element sums over the OUTPUT CHANNELS of one voxel, and the voxel is the MFMA's column,
 // so every voxel is scaled by its own largest magnitude (a lane and its three partners hold all channels of a voxel: two shuffles) --
 // gcol of a voxel is exact to fp32 relative to that voxel's output gradient, whatever its neighbours hold.
+// WH = true (taken together with GH): the weight-gradient partial dW = go S^T on the same instruction -- 8 k-steps of 32 voxels x 3 partial
+// products (lo*hi, hi*lo, hi*hi) instead of 64 v_mfma_f32_16x16x4_f32 per wave and step.  The SAMPLERS store every sample already scaled
+// and split: S[2][hi | lo][CH][264 halves], one ds_write_b16 per component (the register pair the split produces holds two CHANNELS of
+// a voxel, an operand register two VOXELS of a channel), so the matrix waves read finished operands -- two ds_read_b128 per k-step, no
+// permutes, no conversion.  Lane group lg of a matrix wave takes the voxels 128 (lg & 1) + 64 (lg >> 1) + 8 ks + i: the two lane groups a
+// ds_read_b128 services together then start on the same bank, and the row pitch of 132 words (4 mod 64) spreads the 16 channels over
+// all 64 banks.  RANGE GUARD: a dW element sums over VOXELS, its row is a go channel and its column an x channel, so rows and columns carry
+// their own exponent: a go row that of its largest magnitude over the workgroup's 256 voxels (found when the A fragments are loaded and
+// split, once per workgroup), an x channel that of the largest staged cell of the chunk (lean_stage folds it into LDS with an integer
+// max; a sample of the fast path is a convex combination of staged cells; two sets of slots alternate between chunks because the last
+// tile of a chunk is contracted after the next chunk has been staged).  A sample of the slow path reads cells outside the staged box:
+// one that does not fit the f16 range at its channel's scale is added to grad_weight directly in fp32 and enters the tile as zero.
+// What the guard does NOT do: a sample (or go value) more than 2^17 below its channel's (row's) maximum is split like any other, so its
+// lo half, and below 2^29 its hi half, reach the matrix core as subnormal halves -- as in the gcol code above and in wgrad2_kernel.  Nothing
+// is flushed or deferred: such a value is negligible in the sum over voxels its row / column enters unless every large value of the
+// row / column meets an exact zero, and the in-range products of the same k-step set the adder's alignment (DESIGN section 4;
+// tests/test_gpu_dcn_wgrad_f16.py, layouts xchan / xwbands, holds the result to 2 x the fp32 instruction).
 typedef _Float16 lean_f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned lean_u32x4 __attribute__((ext_vector_type(4)));
-template <class G, bool GH>
+template <class G, bool GH, bool WH>
 __global__ __launch_bounds__(512) void dcn_lean_bwd_offset_kernel(const float* __restrict__ x, const float* __restrict__ offset,
                                                                   const float* __restrict__ wg /*[T][nchunk][64 lanes][16]*/,
                                                                   const float* __restrict__ go, float* __restrict__ doff, float* __restrict__ dwtmp,
                                                                   LeanP p, int det) {
   extern __shared__ __align__(16) char smem[];
   constexpr int CH = G::CH, NQ = G::NQ, T = 27;
-  typedef BwdLds<G> L;
+  typedef BwdLds<G, WH> L;
   char* region = smem;
+  int* exps = reinterpret_cast<int*>(smem + L::OFF_E);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if constexpr (WH) {
+    if (tid < 32) exps[tid] = DPF_H3_EMIN;
+    __syncthreads();                                   // before the first staging folds into them
+  }
   int blk = lean_xcd_tile(blockIdx.x, gridDim.x);
   const int tx = blk % p.tilesX; blk /= p.tilesX;
   const int ty = blk % p.tilesY;
@@ -742,6 +778,8 @@ __global__ __launch_bounds__(512) void dcn_lean_bwd_offset_kernel(const float* _
   const float* xb = x + (long long)b * p.C * p.P;
   const float* gob = go + (long long)b * p.K * p.P;
   const int NS = p.nchunk * T;
+  float* rep = det ? dwtmp : dwtmp + (long long)(blockIdx.x % LEAN_NREP) * T * p.nchunk * 64 * 16;
+  long long* rep_shadow = det ? reinterpret_cast<long long*>(dwtmp) : nullptr;
   if (wave_u < 4) {
     // ------------------------------------------------------------------------------------------------------------ samplers
     const int vox = wave_u * 64 + (lane & 32) + lane_pos32(lane & 31);
@@ -757,14 +795,25 @@ __global__ __launch_bounds__(512) void dcn_lean_bwd_offset_kernel(const float* _
     LeanTab tab = lean_tab<G>(p, pvalid, ry0, rx0, zbf + offp0[0], ybf + offp0[p.P], xbf + offp0[2 * p.P]);
 #pragma unroll
     for (int u = 1; u <= 3; ++u) { od[u % 3] = offp0[u * P3]; oh[u % 3] = offp0[u * P3 + p.P]; ow[u % 3] = offp0[u * P3 + 2 * p.P]; }
-    lean_stage<G>(p, xb, 0, region, ry0, rx0, tid, 512);
+    lean_stage<G, WH>(p, xb, 0, region, ry0, rx0, tid, 512, exps);
     __syncthreads();                                   // prologue: region of chunk 0 staged, gcol(0) written
     int i = 0;
 #pragma unroll 1
-    for (int c0 = 0; c0 < p.C; c0 += CH) {
+    for (int c0 = 0, chunk = 0; c0 < p.C; c0 += CH, ++chunk) {
       if (c0 > 0) {
-        lean_stage<G>(p, xb, c0, region, ry0, rx0, tid, 512);
+        lean_stage<G, WH>(p, xb, c0, region, ry0, rx0, tid, 512, exps + (chunk & 1) * 16);
         __syncthreads();
+      }
+      // WH: the chunk's channel scales.  A sample of the fast path is a convex combination of staged cells, so the staged maximum of its
+      // channel bounds it.  (Kept in vector registers although they are wave uniform: the packed multiplies take them as register pairs.)
+      const int* cexp = exps + (chunk & 1) * 16;
+      float ssc[WH ? CH : 1];
+      if constexpr (WH) {
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+          const int e = cexp[c];
+          ssc[c] = dpf_h3_scale(e > 254 ? 254 : e);
+        }
       }
 #pragma unroll 1
       for (int g = 0; g < 9; ++g) {
@@ -785,6 +834,8 @@ __global__ __launch_bounds__(512) void dcn_lean_bwd_offset_kernel(const float* _
           }
           const char* gt = smem + L::OFF_G + (i & 1) * L::GT + vox * 16;
           float* st = reinterpret_cast<float*>(smem + L::OFF_S + (i & 1) * L::ST);
+          unsigned short* sth = reinterpret_cast<unsigned short*>(st);           // WH: hi plane, then lo plane
+          unsigned short* stl = sth + CH * LEAN_SH;
           const char* r0 = region + tab.a0;
           const char* r1 = region + tab.a1;
           const f32x2 w00 = pk_mul_lo(pk_mul_lo(tab.wz, tab.wy), tab.wx), w01 = pk_mul_hi(pk_mul_lo(tab.wz, tab.wy), tab.wx);
@@ -811,8 +862,20 @@ __global__ __launch_bounds__(512) void dcn_lean_bwd_offset_kernel(const float* _
             pk_fma_hi(lo, w10, c[5].xy); pk_fma_hi(hi, w10, c[5].zw);
             pk_fma_lo(lo, w11, c[6].xy); pk_fma_lo(hi, w11, c[6].zw);
             pk_fma_hi(lo, w11, c[7].xy); pk_fma_hi(hi, w11, c[7].zw);
-            st[(4 * q + 0) * LEAN_SS + vox] = lo.x; st[(4 * q + 1) * LEAN_SS + vox] = lo.y;
-            st[(4 * q + 2) * LEAN_SS + vox] = hi.x; st[(4 * q + 3) * LEAN_SS + vox] = hi.y;
+            if constexpr (WH) {
+              // scaled by the channel's exponent and split: the matrix waves read finished f16 operands (a half per store: the pair in a
+              // register is two CHANNELS of this voxel, an MFMA operand register two VOXELS of a channel)
+              unsigned h0, l0, h1, l1;
+              dpf_split_pair_h(lo.x * ssc[4 * q], lo.y * ssc[4 * q + 1], h0, l0);
+              dpf_split_pair_h(hi.x * ssc[4 * q + 2], hi.y * ssc[4 * q + 3], h1, l1);
+              sth[(4 * q + 0) * LEAN_SH + vox] = (unsigned short)h0; sth[(4 * q + 1) * LEAN_SH + vox] = (unsigned short)(h0 >> 16);
+              sth[(4 * q + 2) * LEAN_SH + vox] = (unsigned short)h1; sth[(4 * q + 3) * LEAN_SH + vox] = (unsigned short)(h1 >> 16);
+              stl[(4 * q + 0) * LEAN_SH + vox] = (unsigned short)l0; stl[(4 * q + 1) * LEAN_SH + vox] = (unsigned short)(l0 >> 16);
+              stl[(4 * q + 2) * LEAN_SH + vox] = (unsigned short)l1; stl[(4 * q + 3) * LEAN_SH + vox] = (unsigned short)(l1 >> 16);
+            } else {
+              st[(4 * q + 0) * LEAN_SS + vox] = lo.x; st[(4 * q + 1) * LEAN_SS + vox] = lo.y;
+              st[(4 * q + 2) * LEAN_SS + vox] = hi.x; st[(4 * q + 3) * LEAN_SS + vox] = hi.y;
+            }
             // dot_j += sum over the quad's channels of gcol * corner j (two channels per lane of the packed multiply-add)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -859,7 +922,26 @@ __global__ __launch_bounds__(512) void dcn_lean_bwd_offset_kernel(const float* _
             float part = (wzj * wyj) * fmaf(slw, v1, (1.f - slw) * v0);
             part += __shfl_xor(part, 16, 64);
             part += __shfl_xor(part, 32, 64);
-            if (lane < CH) st[lane * LEAN_SS + svox] = part;
+            if constexpr (WH) {
+              if (lane < CH) {
+                const int e = cexp[lane];
+                float sv = part * dpf_h3_scale(e > 254 ? 254 : e);
+                // this sample read cells OUTSIDE the staged box, which the channel's exponent does not cover: one that does not fit the
+                // f16 range goes into grad_weight directly (all K rows of its column, fp32) and into the tile as zero
+                if (!(__builtin_fabsf(sv) < 32768.f)) {
+                  const int spx = svox % G::TX, spy = (svox / G::TX) % G::TY, spz = svox / (G::TX * G::TY);
+                  const float* gp = gob + ((long long)spz * p.H + y0 + spy) * p.W + x0 + spx;
+                  float* dq = rep + ((long long)(t * p.nchunk + chunk) * 64) * 16 + lane;
+                  for (int k = 0; k < p.K; ++k) dcn_acc_add(rep, rep_shadow, dq + k * 16, gp[(long long)k * p.P] * part);
+                  sv = 0.f;
+                }
+                unsigned h, l;
+                dpf_split_pair_h(sv, 0.f, h, l);
+                sth[lane * LEAN_SH + svox] = (unsigned short)h; stl[lane * LEAN_SH + svox] = (unsigned short)l;
+              }
+            } else {
+              if (lane < CH) st[lane * LEAN_SS + svox] = part;
+            }
             float e0 = gch * v0, e1 = gch * v1;          // this channel's share of dot(jd, jh, 0 / 1); summed over the 16 channels of the row
 #pragma unroll
             for (int m = 1; m < 16; m <<= 1) { e0 += __shfl_xor(e0, m, 64); e1 += __shfl_xor(e1, m, 64); }
@@ -938,20 +1020,53 @@ __global__ __launch_bounds__(512) void dcn_lean_bwd_offset_kernel(const float* _
       }
     }
     // grad_weight A fragments: go[k = 16 mw + l15][voxel 16 q + 4 lg + u] for k-step 4 q + u
-    float wfrag[64];
+    // WH: the same 64 values as f16 components, go[k][voxel wbase + 8 ks + i] = element i of k-step ks (32 voxels per MFMA; wbase = 128
+    // (lg & 1) + 64 (lg >> 1): the lane groups of a ds_read_b128 pair lg with lg ^ 1, whose rows then start 256 B = 0 banks apart, and a
+    // row pitch of 4 banks mod 64 spreads the 16 channels over all 64 banks).  The row is scaled by its own largest exponent over the
+    // workgroup's 256 voxels (e below; the three other lanes of the row hold the rest of it; Erow = the exponents of this lane's D rows).
+    float wfrag[WH ? 1 : 64];
+    lean_u32x4 wah[WH ? 8 : 1], wal[WH ? 8 : 1];        // [k-step]: hi, lo
+    int Erow[4] = {0, 0, 0, 0};                         // WH: exponents of the D rows 4 lg + r of this lane, minus the two scale offsets
+    const int wbase = 128 * (lg & 1) + 64 * (lg >> 1);
     {
       const int kk = 16 * mw + l15;
+      if constexpr (WH) {
+        float mxg = 0.f, gv[64];
 #pragma unroll
-      for (int ks = 0; ks < 64; ++ks) {
-        const int vox = 16 * (ks >> 2) + 4 * lg + (ks & 3);
-        const int px = vox % G::TX, py = (vox / G::TX) % G::TY, pz = vox / (G::TX * G::TY);
-        const bool ok = kk < p.K && pz < p.D && y0 + py < p.H && x0 + px < p.W;
-        wfrag[ks] = ok ? gob[(long long)kk * p.P + ((long long)pz * p.H + y0 + py) * p.W + x0 + px] : 0.f;
+        for (int j = 0; j < 64; ++j) {
+          const int vox = wbase + j;
+          const int px = vox % G::TX, py = (vox / G::TX) % G::TY, pz = vox / (G::TX * G::TY);
+          const bool ok = kk < p.K && pz < p.D && y0 + py < p.H && x0 + px < p.W;
+          gv[j] = ok ? gob[(long long)kk * p.P + ((long long)pz * p.H + y0 + py) * p.W + x0 + px] : 0.f;
+          mxg = __builtin_fmaxf(mxg, __builtin_fabsf(gv[j]));
+        }
+        mxg = __builtin_fmaxf(mxg, __shfl_xor(mxg, 16, 64));
+        mxg = __builtin_fmaxf(mxg, __shfl_xor(mxg, 32, 64));
+        int e = (int)(__builtin_bit_cast(unsigned, mxg) >> 23);
+        e = e < DPF_H3_EMIN ? DPF_H3_EMIN : (e > 254 ? 254 : e);
+        const float scg = dpf_h3_scale(e);
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            unsigned h, l;
+            dpf_split_pair_h(gv[8 * ks + 2 * i] * scg, gv[8 * ks + 2 * i + 1] * scg, h, l);
+            wah[ks][i] = h; wal[ks][i] = l;
+          }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Erow[r] = __shfl(e, 4 * lg + r, 64) - 282;   // lane 4 lg + r holds row 4 lg + r
+      } else {
+#pragma unroll
+        for (int ks = 0; ks < 64; ++ks) {
+          const int vox = 16 * (ks >> 2) + 4 * lg + (ks & 3);
+          const int px = vox % G::TX, py = (vox / G::TX) % G::TY, pz = vox / (G::TX * G::TY);
+          const bool ok = kk < p.K && pz < p.D && y0 + py < p.H && x0 + px < p.W;
+          wfrag[ks] = ok ? gob[(long long)kk * p.P + ((long long)pz * p.H + y0 + py) * p.W + x0 + px] : 0.f;
+        }
       }
     }
-    float* rep = det ? dwtmp : dwtmp + (long long)(blockIdx.x % LEAN_NREP) * T * p.nchunk * 64 * 16;
-    long long* rep_shadow = det ? reinterpret_cast<long long*>(dwtmp) : nullptr;
-    const int brow = (l15 < CH ? l15 : CH - 1) * LEAN_SS + 4 * lg;
+    const int ccol = l15 < CH ? l15 : CH - 1;
+    const int brow = WH ? (ccol * LEAN_SH + wbase) * 2 /* bytes */ : ccol * LEAN_SS + 4 * lg /* floats */;
     const unsigned wlane = (unsigned)lane * 64u;
     auto gcol = [&](int j) {                           // gcol(j) -> G[j & 1]
       const int chunk = j / T, t = j - chunk * T;
@@ -996,34 +1111,60 @@ __global__ __launch_bounds__(512) void dcn_lean_bwd_offset_kernel(const float* _
       }
     };
     gcol(0);
-    lean_stage<G>(p, xb, 0, region, ry0, rx0, tid, 512);
+    lean_stage<G, WH>(p, xb, 0, region, ry0, rx0, tid, 512, exps);
     __syncthreads();                                   // prologue barrier
 #pragma unroll 1
     for (int i = 0; i <= NS; ++i) {
       if (i + 1 < NS) gcol(i + 1);
       if (i >= 1) {                                    // contract S(i - 1)
         const int j = i - 1, cs = j / T, ts = j - cs * T;
-        const float* src = reinterpret_cast<const float*>(smem + L::OFF_S + (j & 1) * L::ST) + brow;
         f32x4 wacc[4] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+        float wsum[4];
+        if constexpr (WH) {
+          // three f16 partial products per 32 voxels: lo*hi, hi*lo, hi*hi, one accumulator each; the sum goes back to the operands' units
+          // by the row's and the column's exponent (exact)
+          const char* src = smem + L::OFF_S + (j & 1) * L::ST + brow;
+          const int ec = exps[(cs & 1) * 16 + ccol];
+          const int Ecol = ec > 254 ? 254 : ec;
 #pragma unroll
-        for (int qq = 0; qq < 16; ++qq) {
-          const f32x4 bv = *reinterpret_cast<const f32x4*>(src + 16 * qq);
-          wacc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfrag[4 * qq + 0], bv.x, wacc[0], 0, 0, 0);
-          wacc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfrag[4 * qq + 1], bv.y, wacc[1], 0, 0, 0);
-          wacc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfrag[4 * qq + 2], bv.z, wacc[2], 0, 0, 0);
-          wacc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfrag[4 * qq + 3], bv.w, wacc[3], 0, 0, 0);
+          for (int ks = 0; ks < 8; ++ks) {
+            const lean_f16x8 bh = __builtin_bit_cast(lean_f16x8, *reinterpret_cast<const lean_u32x4*>(src + 16 * ks));
+            const lean_f16x8 bl = __builtin_bit_cast(lean_f16x8, *reinterpret_cast<const lean_u32x4*>(src + L::SP + 16 * ks));
+            wacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(lean_f16x8, wal[ks]), bh, wacc[0], 0, 0, 0);
+            wacc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(lean_f16x8, wah[ks]), bl, wacc[1], 0, 0, 0);
+            wacc[2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(lean_f16x8, wah[ks]), bh, wacc[2], 0, 0, 0);
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) wsum[r] = __builtin_ldexpf((wacc[0][r] + wacc[1][r]) + wacc[2][r], Erow[r] + Ecol);
+        } else {
+          const float* src = reinterpret_cast<const float*>(smem + L::OFF_S + (j & 1) * L::ST) + brow;
+#pragma unroll
+          for (int qq = 0; qq < 16; ++qq) {
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(src + 16 * qq);
+            wacc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfrag[4 * qq + 0], bv.x, wacc[0], 0, 0, 0);
+            wacc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfrag[4 * qq + 1], bv.y, wacc[1], 0, 0, 0);
+            wacc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfrag[4 * qq + 2], bv.z, wacc[2], 0, 0, 0);
+            wacc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfrag[4 * qq + 3], bv.w, wacc[3], 0, 0, 0);
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) wsum[r] = (wacc[0][r] + wacc[1][r]) + (wacc[2][r] + wacc[3][r]);
         }
         if (l15 < CH && cs * CH + l15 < p.C) {
           float* dst = rep + ((long long)(ts * p.nchunk + cs) * 64 + 16 * mw + 4 * lg) * 16 + l15;
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            if (16 * mw + 4 * lg + r < p.K) dcn_acc_add(rep, rep_shadow, &dst[r * 16], (wacc[0][r] + wacc[1][r]) + (wacc[2][r] + wacc[3][r]));
+            if (16 * mw + 4 * lg + r < p.K) dcn_acc_add(rep, rep_shadow, &dst[r * 16], wsum[r]);
         }
       }
       if (i < NS) {
         __syncthreads();                               // barrier of step i
+        if constexpr (WH) {
+          // the exponents of chunk i / T - 1 were last read before this barrier (contraction of its last tile): preset their slots
+          // for chunk i / T + 1; the step barriers up to its staging publish that
+          if (i % T == 1 && mw == 0 && lane < 16) exps[((i / T + 1) & 1) * 16 + lane] = DPF_H3_EMIN;
+        }
         if (i + 1 < NS && (i + 1) % T == 0) {          // step i was the last tap of its chunk: re-stage the region
-          lean_stage<G>(p, xb, ((i + 1) / T) * CH, region, ry0, rx0, tid, 512);
+          lean_stage<G, WH>(p, xb, ((i + 1) / T) * CH, region, ry0, rx0, tid, 512, exps + (((i + 1) / T) & 1) * 16);
           __syncthreads();
         }
       }
@@ -1112,10 +1253,10 @@ int lean_launch_bwd_offset(const float* x, const float* offset, const float* wei
   int rc;
   if (dcn_env().gcol16 && dpf_conv_f32_x9() == 2) {
     hipLaunchKernelGGL(lean_repack_gcol_h_kernel, dim3(16), dim3(1024), 0, st, weight, reinterpret_cast<unsigned short*>(ws), p.K, p.C, G::CH, p.nchunk);
-    rc = dcn_launch(dcn_lean_bwd_offset_kernel<G, true>, grid, block, BwdLds<G>::LDS + 64, st, x, offset, ws, go, doff, dwtmp, p, det);
+    rc = dcn_launch(dcn_lean_bwd_offset_kernel<G, true, true>, grid, block, BwdLds<G, true>::LDS, st, x, offset, ws, go, doff, dwtmp, p, det);
   } else {
     hipLaunchKernelGGL(lean_repack_gcol_kernel, dim3(dpf_ew_grid(27LL * p.nchunk * 1024)), dim3(256), 0, st, weight, ws, p.K, p.C, G::CH, p.nchunk);
-    rc = dcn_launch(dcn_lean_bwd_offset_kernel<G, false>, grid, block, BwdLds<G>::LDS, st, x, offset, ws, go, doff, dwtmp, p, det);
+    rc = dcn_launch(dcn_lean_bwd_offset_kernel<G, false, false>, grid, block, BwdLds<G, false>::LDS, st, x, offset, ws, go, doff, dwtmp, p, det);
   }
   return rc != DPF_OK ? rc : dpf_check_launch();
 }

@@ -70,7 +70,7 @@ int dpf_get_conv_operand_precision(void);
  *       position whose values all lie more than 2^17 below the scale contributes exact zeros and is contracted in an extra pass at its own
  *       scale -- up to three extra passes per channel chunk, the last one takes whatever is left) with one exponent per OUTPUT ROW of the
  *       weights, the weight gradient per CHANNEL (every g row and x channel of a workgroup carries its own exponent), the deformable conv's
- *       gcol products per VOXEL.  With the guards an output element is as accurate, relative to the magnitudes of ITS OWN inputs, as on the
+ *       gcol products per VOXEL, its weight-gradient partial per go ROW and x CHANNEL.  With the guards an output element is as accurate, relative to the magnitudes of ITS OWN inputs, as on the
  *       fp32 instruction (tests/test_gpu_ops.py: test_conv_f16_component_path_in_block_dynamic_range and its weight-gradient / deformable
  *       siblings);
  *   1 = the exact round-to-nearest three-way bf16 splits of both operands (x = hi + mid + lo) on the bf16 matrix pipe, the six partial
