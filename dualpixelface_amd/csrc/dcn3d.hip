@@ -2,7 +2,7 @@
 //
 // Drop-in for the reference's CUDA extension `DCN` (src/module/dcn3d/src/vision.cpp:4-7;
 // deform_conv_cuda.cu:18-285; kernels deform_im2col_cuda.cuh:26-405).  This file: the entry points and the kernels for
-// group = deformable_group = 1; larger group counts run on the kernels of dcn_grouped.hip.
+// group = deformable_group = 1; larger group counts run on the kernels of dcn_gather.hip.
 //   forward : out[b,k,p] = bias[k] + sum_{c,t} W[k,c,t] * trilinear(x[b,c], base(p,t) + offset[b,3t..3t+2,p])
 //   backward: grad_input (adjoint of the sampler), grad_offset (d sample / d coord), grad_weight, grad_bias
 // The reference materialises `columns` [C*27, B*P] (2.7 GB per 1024x1536 sample, int32 indices); here a workgroup
@@ -25,7 +25,7 @@ __device__ __forceinline__ int dpf_xcd_tile(int blk, int n) {
   return x * q + (x < r ? x : r) + i;
 }
 
-constexpr int TP = 64;          // output voxels per workgroup
+constexpr int TP = DCN_TP;      // output voxels per workgroup
 constexpr int SP = TP + 1;      // padded LDS row
 constexpr int MAXC = 128;
 
@@ -1592,11 +1592,6 @@ __global__ void dcn_wgrad_fold_kernel(const float* __restrict__ dwtmp, float* __
   }
 }
 
-// deterministic mode: grad_input = value of its integer shadow (every contribution went there; the tensor itself was only zero-filled)
-__global__ void dcn_gi_finalize_kernel(const long long* __restrict__ shadow, float* __restrict__ gi, long long n) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) gi[i] = dpf_det_value(shadow + 2 * i);
-}
-
 size_t region_lds(const RegGeo& g, int CH) { return sizeof(float) * ((size_t)CH * g.RV + (size_t)16 * ST); }
 
 int region_geo(RegGeo& g, const DcnP& p, int CH, int R, bool aligned = false, int RYH = -1, int TX = RG_TX, int TY = RG_TY) {
@@ -1842,29 +1837,29 @@ int dcn_bwd_gather(const DcnBwd& b, bool dx_done) {
   return dcn_launch(kern, dim3((unsigned)(p.T * p.nchunk)), dim3(256), lds, b.st, b.input, b.offset, b.grad_output, b.grad_weight, p);
 }
 
-// group > 1 or deformable_group > 1: the kernels of dcn_grouped.hip, with the repacked weights in the repack region of the workspace map and
+// group > 1 or deformable_group > 1: the rank-3 kernels of dcn_gather.hip, with the repacked weights in the repack region of the workspace map and
 // the deterministic-mode shadow of grad_weight in its replica region.  Both regions are sized from whole C and K (K (C/group) T <= K C T), so
 // the caller's workspace queries hold for every grouping; the bounds are checked here all the same.
 int dcn_fwd_grouped(const DcnP& p, int group, int deformable_group, const float* input, const float* weight, const float* bias, const float* offset,
                     float* output, float* ws, hipStream_t st) {
-  if (dcn_grouped_pack_floats(p, false) > dcn_ws_map(0, p.C, 0, 0, 0, p.K, p.T, 0).dwtmp) return DPF_ERR_UNSUPPORTED;
-  return dcn_grouped_forward(p, group, deformable_group, input, weight, bias, offset, output, ws, st);
+  const long long room = dcn_ws_map(0, p.C, 0, 0, 0, p.K, p.T, 0).dwtmp;
+  return dcn_gather_forward(3, p, group, deformable_group, input, weight, bias, offset, nullptr, output, ws, room, st);
 }
 
 int dcn_bwd_grouped(const DcnBwd& b, int group, int deformable_group, int grad_input_channels) {
   const DcnP& p = b.p;
   const long long dw_elems = (long long)p.K * (p.C / group) * p.T;
-  if (dcn_grouped_pack_floats(p, true) > b.m.dwtmp || (b.det && 4 * dw_elems > b.m.wmax - b.m.dwtmp)) return DPF_ERR_UNSUPPORTED;
+  if (b.det && 4 * dw_elems > b.m.wmax - b.m.dwtmp) return DPF_ERR_UNSUPPORTED;
   long long* dw_shadow = nullptr;
   if (b.det) {
     dw_shadow = reinterpret_cast<long long*>(b.ws + b.m.dwtmp);
     if (reinterpret_cast<uintptr_t>(dw_shadow) & 7) return DPF_ERR_INVALID_ARG;
     if (hipMemsetAsync(dw_shadow, 0, sizeof(long long) * 2 * (size_t)dw_elems, b.st) != hipSuccess) return DPF_ERR_LAUNCH;
   }
-  const int rc = dcn_grouped_backward(p, group, deformable_group, b.input, b.weight, b.offset, b.grad_output, b.grad_input, b.grad_offset, b.grad_weight,
-                                      b.ws, dw_shadow, b.gi_shadow, grad_input_channels, b.st);
+  const int rc = dcn_gather_backward(3, p, group, deformable_group, b.input, b.weight, b.offset, nullptr, b.grad_output, b.grad_input, b.grad_offset, nullptr,
+                                     b.grad_weight, b.ws, b.m.dwtmp, dw_shadow, b.gi_shadow, grad_input_channels, b.st);
   if (rc != DPF_OK) return rc;
-  if (b.det) hipLaunchKernelGGL(dcn_gi_finalize_kernel, dim3(dpf_ew_grid(dw_elems)), dim3(256), 0, b.st, dw_shadow, b.grad_weight, dw_elems);
+  if (b.det) dcn_finalize(dw_shadow, b.grad_weight, dw_elems, b.st);
   return DPF_OK;
 }
 
@@ -1900,7 +1895,7 @@ long long dpf_deform_conv3d_backward_workspace_floats(int B, int C, int D, int H
 // weight is [K][C/group][T], offset [B][deformable_group * 3T][P]; group must divide C and K, deformable_group must divide C, else
 // DPF_ERR_INVALID_ARG with nothing launched.
 // group = deformable_group = 1, three tiers: lean kernels (the model's configuration) -> role-split region kernel -> gather kernel; DPF_DCN_V1
-// leaves only the last.  Any other grouping: dcn_grouped.hip (fp32 matrix instruction for every setting of dpf_set_f32_matrix_path).
+// leaves only the last.  Any other grouping: dcn_gather.hip (fp32 matrix instruction for every setting of dpf_set_f32_matrix_path).
 int dpf_deform_conv3d_forward(const float* input, const float* weight, const float* bias, const float* offset, float* output, float* ws,
                               int B, int C, int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph,
                               int pw, int dd, int dh, int dw, int group, int deformable_group, int im2col_step, void* stream) {
@@ -1967,7 +1962,7 @@ int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const
     if (rc == DPF_ERR_UNSUPPORTED) rc = dcn_bwd_gather(b, dx_done);
   }
   if (rc != DPF_OK) return rc;
-  if (b.det) hipLaunchKernelGGL(dcn_gi_finalize_kernel, dim3(dpf_ew_grid(in_elems)), dim3(256), 0, b.st, b.gi_shadow, grad_input, in_elems);
+  if (b.det) dcn_finalize(b.gi_shadow, grad_input, in_elems, b.st);
   if (grad_bias) {
     // grad_bias[k] = sum_{b,p} go[b,k,p]  (cu:277) -- small row reduction
     if (hipMemsetAsync(grad_bias, 0, sizeof(float) * K, b.st) != hipSuccess) return DPF_ERR_LAUNCH;

@@ -17,7 +17,11 @@ __device__ __forceinline__ void dcn_acc_add(float* base, long long* shadow, floa
 }
 #endif
 
-// Geometry of one call and the sampling rule, shared by the translation units of the family (dcn3d.hip, dcn_grouped.hip).
+// output positions per workgroup of the gather kernels (dcn3d.hip, dcn_gather.hip)
+constexpr int DCN_TP = 64;
+
+// Geometry of one call and the 3-D sampling rule, shared by the translation units of the family (dcn3d.hip, dcn_gather.hip, dcn2d.hip).  A 2-D
+// call (dcn2d.hip) is the same record at depth 1: D = Do = kd = sd = dd = 1, pd = 0.
 struct DcnP {
   int B, C, K;
   int D, H, W;        // input dims
@@ -129,15 +133,20 @@ int dcn_lean_forward(const float* x, const float* offset, const float* weight, c
 int dcn_lean_bwd_offset(const float* x, const float* offset, const float* weight, const float* go, float* doff, float* dwtmp, float* ws, int B, int C,
                         int D, int H, int W, int K, hipStream_t st, int det = 0);
 
-// group > 1 or deformable_group > 1 (dcn_grouped.hip): the grouping as a kernel argument, a fixed number of launches per call, every product on
-// the fp32 matrix instruction.  dcn_group_check: DPF_ERR_INVALID_ARG unless group divides C and K and deformable_group divides C.
-// wpack: dcn_grouped_pack_floats(p, backward) floats for the repacked block-diagonal weights.  Backward: grad_input / grad_weight zero-initialised
-// by the caller; deterministic mode: dw_shadow / gi_shadow = zero-initialised integer shadows (dcn_acc_add) of grad_weight [K][C/group][T] and
-// grad_input that the caller folds, else nullptr.  grad_offset is stored once per element in either mode.
+// The gather family with the grouping as a kernel argument (dcn_gather.hip), rank 3 (dcn3d.hip: group > 1 or deformable_group > 1) or rank 2
+// (dcn2d.hip: every call): a fixed number of launches per call, every product on the fp32 matrix instruction.
+// dcn_group_check: DPF_ERR_INVALID_ARG unless group divides C and K and deformable_group divides C.
+// mask: [B][deformable_group * T][P] or nullptr; rank 3 has none.  wpack: room for wpack_floats floats, where the block-diagonal weights are
+// repacked; DPF_ERR_UNSUPPORTED with nothing launched if they do not fit.
+// Backward: grad_input, grad_offset, grad_mask, grad_weight may each be nullptr (not wanted); grad_input / grad_weight are zero-initialised by
+// the caller; deterministic mode: dw_shadow / gi_shadow = zero-initialised integer shadows (dcn_acc_add) of grad_weight [K][C/group][T] and
+// grad_input that the caller folds with dcn_finalize, else nullptr.  grad_input is produced for the channels [0, grad_input_channels).
+// grad_offset and grad_mask are stored once per element in either mode.
 int dcn_group_check(int C, int K, int group, int deformable_group);
-long long dcn_grouped_pack_floats(const DcnP& p, bool backward);
-int dcn_grouped_forward(const DcnP& p, int group, int deformable_group, const float* input, const float* weight, const float* bias,
-                        const float* offset, float* output, float* wpack, hipStream_t st);
-int dcn_grouped_backward(const DcnP& p, int group, int deformable_group, const float* input, const float* weight, const float* offset,
-                         const float* grad_output, float* grad_input, float* grad_offset, float* grad_weight, float* wpack, long long* dw_shadow,
-                         long long* gi_shadow, int grad_input_channels, hipStream_t st);
+int dcn_gather_forward(int rank, const DcnP& p, int group, int deformable_group, const float* input, const float* weight, const float* bias,
+                       const float* offset, const float* mask, float* output, float* wpack, long long wpack_floats, hipStream_t st);
+int dcn_gather_backward(int rank, const DcnP& p, int group, int deformable_group, const float* input, const float* weight, const float* offset,
+                        const float* mask, const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
+                        float* wpack, long long wpack_floats, long long* dw_shadow, long long* gi_shadow, int grad_input_channels, hipStream_t st);
+// deterministic mode: out[0 .. n) = value of its integer shadow (every contribution went there; the tensor itself was only zero-filled)
+void dcn_finalize(const long long* shadow, float* out, long long n, hipStream_t st);

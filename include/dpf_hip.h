@@ -309,8 +309,8 @@ int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const
 
 /* ---- deformable conv2d, plain (DCN v1) and modulated (v2): the reference's pybind module `deform_conv_cuda`
  * (src/module/dcn/src/deform_conv_cuda.cpp:687-697 over src/deform_conv_cuda_kernel.cu:190,279,373,570,635,695; DeformConv / DeformConvPack /
- * ModulatedDeformConv / ModulatedDeformConvPack of src/module/dcn/deform_conv.py).  Native 2-D kernels (csrc/dcn2d.hip), not the 3-D entry at
- * depth 1.
+ * ModulatedDeformConv / ModulatedDeformConvPack of src/module/dcn/deform_conv.py).  Native 2-D kernels (csrc/dcn2d.hip over
+ * csrc/dcn_gather.hip), not the 3-D entry at depth 1.
  * LAYOUTS: input [B][C][H][W], weight [K][C/group][kh][kw], bias [K] or NULL, output / grad_output [B][K][Ho][Wo] with
  * Ho = (H + 2 ph - (dh (kh - 1) + 1)) / sh + 1.  offset [B][deformable_group * 2 T][Ho][Wo] (T = kh kw): channel 2 (i kw + j) is the h component
  * and channel 2 (i kw + j) + 1 the w component of tap (i, j).  mask [B][deformable_group * T][Ho][Wo], or NULL for the plain (v1) operator.

@@ -1,6 +1,6 @@
-"""GPU parity tests of the 2-D deformable convolution, plain (DCN v1) and modulated (v2) (csrc/dcn2d.hip), called through the C ABI wrappers
-(ops.deform_conv2d_forward_raw / ops.deform_conv2d_backward_raw), against the fp64 restatement tests/dcn2d_cpu.py and its autograd
-(tests/test_dcn2d_host.py pins that to the 3-D oracle at depth 1, to F.conv2d and to shifted taps).
+"""GPU parity tests of the 2-D deformable convolution, plain (DCN v1) and modulated (v2) (csrc/dcn2d.hip over the rank-2 kernels of
+csrc/dcn_gather.hip), called through the C ABI wrappers (ops.deform_conv2d_forward_raw / ops.deform_conv2d_backward_raw), against the fp64
+restatement tests/dcn2d_cpu.py and its autograd (tests/test_dcn2d_host.py pins that to the 3-D oracle at depth 1, to F.conv2d and to shifted taps).
 
 Tolerances: those of the project's fp32-matrix-instruction deformable tier at these operand scales (x 1, weight 0.1, bias 1;
 tests/test_gpu_dcn_grouped.py): forward 1e-4, every gradient 2e-4 of the reference tensor's maximum.  Known answers: 1e-5.
@@ -58,6 +58,7 @@ CASES = [
     ((1, 96, 96, 6, 12), (3, 3), (1, 1), (1, 1), (1, 1), (2, 3)),     # more than one 32-row matrix tile per group
     ((1, 256, 256, 4, 8), (3, 3), (1, 1), (1, 1), (1, 1), (4, 8)),    # channel limit, less than one tile
     ((3, 5, 3, 8, 9), (3, 3), (1, 1), (1, 1), (1, 1), (1, 1)),        # odd C, K < 4
+    ((1, 64, 64, 4, 8), (3, 3), (1, 1), (1, 1), (1, 1), (2, 2)),      # K = 64: four forward tiles, one accumulator on every wave
 ]
 THREE_TILES = ((2, 16, 8, 10, 16), (3, 3), (1, 1), (1, 1), (1, 1), (2, 4))     # 160 positions: two full tiles and a tail of 32
 INT_CASE = ((2, 8, 8, 9, 13), (3, 3), (1, 1), (1, 1), (1, 1), (2, 2))
@@ -155,7 +156,8 @@ def test_integer_offsets_and_the_validity_rule(modulated):
 
 
 def test_plain_operator_equals_the_3d_entry_at_depth_one():
-    """One plain case through dpf_deform_conv3d_* on a depth-1 volume with zero depth offsets, on the GPU: the same bars."""
+    """One plain case through dpf_deform_conv3d_* on a depth-1 volume with zero depth offsets, on the GPU: the same bars, and the forward bit for
+    bit (corners 0-3 of the depth-1 trilinear rule carry the weight 1 a b in the bilinear rule's order, and a tile accumulates in one order)."""
     ops = _ops()
     case = CASES[1]
     (B, C, K, H, W), (kh, kw), s, p, d, (group, dg) = case
@@ -174,6 +176,7 @@ def test_plain_operator_equals_the_3d_entry_at_depth_one():
     gi, goff, gm, gw, gb = ops.deform_conv2d_backward_raw(xg, wg, bg, og, None, gg, s, p, d, group, dg)
     assert gm is None
     close(y, y3.squeeze(2), 1e-4, '2d vs 3d fwd')
+    assert torch.equal(y, y3.squeeze(2))
     close(gi, gi3.squeeze(2), 2e-4, '2d vs 3d grad_input')
     close(goff, goff3.reshape(B, dg, T, 3, Ho, Wo)[:, :, :, 1:].reshape(goff.shape), 2e-4, '2d vs 3d grad_offset')
     close(gw, gw3.squeeze(2), 2e-4, '2d vs 3d grad_weight')

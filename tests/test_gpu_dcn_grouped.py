@@ -1,4 +1,4 @@
-"""GPU parity tests of the deformable convolution with group / deformable_group > 1 (csrc/dcn_grouped.hip), called through the C ABI
+"""GPU parity tests of the deformable convolution with group / deformable_group > 1 (the rank-3 kernels of csrc/dcn_gather.hip), called through the C ABI
 (ops.deform_conv_forward_raw / ops.deform_conv_backward_raw), against oracle.dcn3d.deform_conv3d_forward_grouped in fp64 and its fp64
 autograd (tests/test_oracle_dcn.py pins that to F.conv3d(groups)).
 
@@ -53,6 +53,7 @@ def _cases():
         ((1, 16, 8, 4, 8, 11), K3, ONE, (2, 2, 2), (2, 2, 2), [(2, 4)]),                    # dilated
         ((1, 96, 96, 2, 6, 12), K3, ONE, ONE, ONE, [(2, 3)]),                               # more than one 32-row matrix tile per group
         ((1, 128, 128, 1, 4, 8), K3, ONE, ONE, ONE, [(4, 2)]),                              # the channel limit
+        ((1, 64, 64, 1, 4, 8), K3, ONE, ONE, ONE, [(2, 2)]),                                # K = 64: four forward tiles, one accumulator on every wave
     ]
     return [(shape, k, s, p, d, g) for shape, k, s, p, d, gs in rows for g in gs]
 

@@ -1,4 +1,5 @@
-"""Stand-alone timing of the 2-D deformable-conv kernels (csrc/dcn2d.hip), by default B=4, C=K=64, 256x384, 3x3, padding kernel // 2.
+"""Stand-alone timing of the 2-D deformable-conv kernels (csrc/dcn2d.hip over csrc/dcn_gather.hip), by default B=4, C=K=64, 256x384,
+3x3, padding kernel // 2.
 
     python tools/dcn2d_bench.py [fwd|all] [C ...] [--shape B,H,W] [--k K] [--kernel KH[,KW]] [--group G] [--deformable-group DG]
                                 [--modulated] [--via-3d] [--reps N]
