@@ -1711,6 +1711,60 @@ def rmsprop_step_lr(param, grad, square_avg, lr_dev, alpha=0.99, eps=1e-5, gscal
                float(gscale), _stream())
 
 
+# ---- validation metrics (csrc/metrics.hip): raw wrappers; results stay on the device, nothing here reads the host
+METRIC_TARGET = {'disp': 0, 'idepth': 1, 'depth': 2}
+
+
+def _metric_ws(query, B, n, device):
+    nbytes = lib().call(query, B, n)
+    if nbytes < 0:
+        raise DpfError('%s: shape B=%d n=%d is not supported' % (query, B, n))
+    return scratch((nbytes + 3) // 4, device, 'metric'), nbytes
+
+
+def metric_absolute_dp(pred, abvalue, target, mask=None, target_type='disp', threshold=1.01, out=None):
+    """pred / target / mask [B, H, W] -> device row [abs_rel, abs_diff, sq_rel, rmse, rmse_log, a1, a2, a3] (metrics.depth_errors, after
+    metrics.disp2depth unless target_type == 'depth'); abvalue [B, 2] = [b, a]."""
+    _need(pred, abvalue, target, mask)
+    B, n = pred.shape[0], pred[0].numel()
+    out = torch.empty(8, dtype=torch.float32, device=pred.device) if out is None else out
+    ws, nbytes = _metric_ws('dpf_metric_absolute_dp_workspace_bytes', B, n, pred.device)
+    lib().call('dpf_metric_absolute_dp', _ptr(pred), _ptr(abvalue), _ptr(target), _ptr(mask), B, n, METRIC_TARGET[target_type],
+               float(threshold), _ptr(out), _ptr(ws), nbytes, _stream())
+    return out
+
+
+def metric_normal_dp(pred, target, mask=None, out=None):
+    """pred / target [B, 3, H, W], mask [B, H, W] -> device row [mean, rms] angular error in degrees."""
+    _need(pred, target, mask)
+    B, n = pred.shape[0], pred[0, 0].numel()
+    out = torch.empty(2, dtype=torch.float32, device=pred.device) if out is None else out
+    ws, nbytes = _metric_ws('dpf_metric_normal_dp_workspace_bytes', B, n, pred.device)
+    lib().call('dpf_metric_normal_dp', _ptr(pred), _ptr(target), _ptr(mask), B, n, _ptr(out), _ptr(ws), nbytes, _stream())
+    return out
+
+
+def metric_ranks(values, negate=False, out=None):
+    """values [B, n] -> int32 [B, n]: argsort(argsort(z, stable), stable) per row, of -z with ``negate``."""
+    _need(values)
+    B, n = values.shape[0], values[0].numel()
+    out = torch.empty((B, n), dtype=torch.int32, device=values.device) if out is None else out
+    ws, nbytes = _metric_ws('dpf_metric_ranks_workspace_bytes', B, n, values.device)
+    lib().call('dpf_metric_ranks', _ptr(values), _ptr(out), B, n, int(bool(negate)), _ptr(ws), nbytes, _stream())
+    return out
+
+
+def metric_affine_dp(pred, target, weight, rank_pred, rank_negpred, rank_target, irls_iters=5, epsilon=1e-3, out=None):
+    """pred / target / weight [B, n] and the three rank arrays -> device row [wmae, wrmse, 1 - spearman], batch means."""
+    _need(pred, target, weight, rank_pred, rank_negpred, rank_target)
+    B, n = pred.shape[0], pred[0].numel()
+    out = torch.empty(3, dtype=torch.float32, device=pred.device) if out is None else out
+    ws, nbytes = _metric_ws('dpf_metric_affine_dp_workspace_bytes', B, n, pred.device)
+    lib().call('dpf_metric_affine_dp', _ptr(pred), _ptr(target), _ptr(weight), _ptr(rank_pred), _ptr(rank_negpred), _ptr(rank_target), B, n,
+               int(irls_iters), float(epsilon), _ptr(out), _ptr(ws), nbytes, _stream())
+    return out
+
+
 def reset_zero_arenas():
     """Forget what is left of the pre-zeroed arenas: the next zero_slot() clears its arena again.  A graph capture of the train step starts
     with this, so that the clearing fill is PART of the captured work (a replay finds the slots zero, as the eager step does)."""

@@ -161,19 +161,49 @@ class Trainer(object):
             with open(os.path.join(self.workspace_path, 'log.jsonl'), 'a') as fh:
                 fh.write(json.dumps(record) + '\n')
 
+    def validates_on_all_ranks(self):
+        """Config key ``validate_on_all_ranks`` (default true): with more than one rank every rank validates its share of the batches;
+        false keeps validation on rank 0 while the others wait."""
+        return self.world_size > 1 and bool(getattr(self.option, 'validate_on_all_ranks', True))
+
     def validate(self, model, loader, test=False):
+        """One pass over ``loader`` in deferred metric mode (selectors.metric_selector): no host read per batch, one flush before the
+        epoch-end hook.  On all ranks: rank r takes the batches r, r + world, ... of the same loader order, then ONE all-reduce per
+        benchmark of (sum of its rows, its batch count) -- issued by every rank whatever it counted, a rank without a batch adds zeros --
+        and every rank returns the mean over all batches of the per-batch rows, the figure a single process logs."""
         device = model.flat_parameters().device
+        sel = model.metric_model
+        share = self.validates_on_all_ranks()
         model.eval()
         outputs = []
-        with torch.no_grad():
+        self.validated_batches = []                          # loader positions this rank ran (tests)
+        with torch.no_grad(), sel.deferred():
             for i, batch in enumerate(loader):
+                if share and i % self.world_size != self.rank:
+                    continue
                 batch = self._to_device(batch, device)
                 outputs.append(None if (model.test_step if test else model.validation_step)(batch, i) is None else i)
+                self.validated_batches.append(i)
+        sel.flush()
         (model.test_epoch_end if test else model.validation_epoch_end)(outputs)
-        rows = {n: f.get_value() for n, f in zip(model.metric_model.metric_name, model.metric_model.metric_func) if f.index > 0}
-        for f in model.metric_model.metric_func:
+        if share:
+            rows = self._all_rank_rows(sel, device)
+        else:
+            rows = {n: f.get_value() for n, f in zip(sel.metric_name, sel.metric_func) if f.index > 0}
+        for f in sel.metric_func:
             f.clear()
         model.train()
+        return rows
+
+    def _all_rank_rows(self, sel, device):
+        import torch.distributed as dist
+        rows = {}
+        for name, f in zip(sel.metric_name, sel.metric_func):
+            packed = torch.tensor([math.fsum(f.metric[k]) for k in f.keys] + [float(f.index)], dtype=torch.float64, device=device)
+            dist.all_reduce(packed, op=dist.ReduceOp.SUM)
+            packed = packed.tolist()
+            if packed[-1] > 0:
+                rows[name] = [v / packed[-1] for v in packed[:-1]]
         return rows
 
     def fit(self, model, train_loader=None, val_loader=None):
@@ -212,11 +242,12 @@ class Trainer(object):
             if device.type == 'cuda':
                 torch.cuda.synchronize()
             self._log({'epoch': self.epoch, 'epoch_seconds': time.time() - t0, 'samples_per_s_rank': n / max(time.time() - t0, 1e-9)})
-            if val_loader is not None and self.rank == 0 and not done:
+            share = self.validates_on_all_ranks()
+            if val_loader is not None and (self.rank == 0 or share) and not done:
                 rows = self.validate(model, val_loader)
                 self._log({'epoch': self.epoch, 'metrics': rows})
-            if self.world_size > 1:
-                dd.wait_for_rank0()            # the other ranks wait here (host-side, own long timeout), not inside the next epoch's first all-reduce
+            if self.world_size > 1 and not share:
+                dd.wait_for_rank0()            # rank-0-only validation: the other ranks wait here (host-side, own long timeout), not inside the next epoch's first all-reduce
             self.save_checkpoint(model)
             self.epoch += 1
         if reducer is not None:

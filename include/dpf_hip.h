@@ -428,6 +428,36 @@ int dpf_dp_image(const unsigned char* img, const unsigned char* lut, float* out,
 /* fp32 [H, W, C] window -> [C, ch, cw] (normal / albedo maps through to_tensor) */
 int dpf_dp_hwc_to_chw(const float* src, float* dst, int H, int W, int C, int y0, int x0, int ch, int cw, void* stream);
 
+/* ---- validation metrics on the device (dualpixelface_amd/metrics.py is the definition): fp32 in, element-wise fp32 in the order
+ * metrics.py writes it, every sum fp64 in two phases (per-block partials, one fold in a fixed order; no floating-point atomics, so
+ * results repeat bit for bit).  Every entry point enqueues on `stream`, leaves its result in device memory and never waits.  ws: the
+ * matching *_workspace_bytes() bytes of 16-byte aligned device scratch (-1: shape refused).  Refusals launch nothing:
+ * DPF_ERR_INVALID_ARG for null pointers, B <= 0, n <= 0 or a workspace that is too small, DPF_ERR_UNSUPPORTED for n >= 2^31 - 1 or
+ * B > 65535.  n = H * W pixels per sample; mask NULL = all ones. */
+#define DPF_METRIC_DISP 0
+#define DPF_METRIC_IDEPTH 1
+#define DPF_METRIC_DEPTH 2
+long long dpf_metric_absolute_dp_workspace_bytes(int B, long long n);
+long long dpf_metric_normal_dp_workspace_bytes(int B, long long n);
+long long dpf_metric_ranks_workspace_bytes(int B, long long n);
+long long dpf_metric_affine_dp_workspace_bytes(int B, long long n);
+/* pred [B, n] (target_type DISP / IDEPTH: disparity, depth = a / (pred - b) with abvalue [B, 2] = [b, a], non-finite -> 0; DEPTH: depth,
+ * abvalue unused), target depth and mask [B, n] -> out8 = abs_rel, abs_diff, sq_rel, rmse, rmse_log, a1, a2, a3 over the pixels with
+ * mask > 0 of the whole batch (all NaN when there is none); a_k = fraction with max(gt / pred, pred / gt) < fp32(threshold ** k) */
+int dpf_metric_absolute_dp(const float* pred, const float* abvalue, const float* target, const float* mask, int B, long long n,
+                           int target_type, double threshold, float* out8, void* ws, long long ws_bytes, void* stream);
+/* pred, target [B, 3, n], mask [B, n] -> out2 = mean and RMS angular error in degrees (normal_error_mean / normal_error_rmse) */
+int dpf_metric_normal_dp(const float* pred, const float* target, const float* mask, int B, long long n, float* out2, void* ws,
+                         long long ws_bytes, void* stream);
+/* values [B, n] -> ranks [B, n] int32: position of each element in the stable ascending sort of its sample, i.e.
+ * argsort(argsort(z, stable), stable); -0.0 == +0.0, NaN last, ties in index order.  negate != 0 ranks -z. */
+int dpf_metric_ranks(const float* values, int* ranks, int B, long long n, int negate, void* ws, long long ws_bytes, void* stream);
+/* pred, target, weight [B, n], ranks of pred, of -pred and of target -> out3 = batch means of wmae (irls_iters IRLS fits, weights
+ * c / max(epsilon, |s p + t - d|)), wrmse (the first fit) and 1 - weighted Spearman correlation (maximum over pred ascending / negated) */
+int dpf_metric_affine_dp(const float* pred, const float* target, const float* weight, const int* rank_pred, const int* rank_negpred,
+                         const int* rank_target, int B, long long n, int irls_iters, float epsilon, float* out3, void* ws,
+                         long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
