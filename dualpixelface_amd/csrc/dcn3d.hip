@@ -2,7 +2,8 @@
 //
 // Drop-in for the reference's CUDA extension `DCN` (src/module/dcn3d/src/vision.cpp:4-7;
 // deform_conv_cuda.cu:18-285; kernels deform_im2col_cuda.cuh:26-405).  This file: the entry points and the kernels for
-// group = deformable_group = 1; larger group counts run on the kernels of dcn_gather.hip.
+// group = deformable_group = 1; larger group counts, and the single-group backward whose grad_input the packed scatter declines, run on the
+// kernels of dcn_gather.hip.
 //   forward : out[b,k,p] = bias[k] + sum_{c,t} W[k,c,t] * trilinear(x[b,c], base(p,t) + offset[b,3t..3t+2,p])
 //   backward: grad_input (adjoint of the sampler), grad_offset (d sample / d coord), grad_weight, grad_bias
 // The reference materialises `columns` [C*27, B*P] (2.7 GB per 1024x1536 sample, int32 indices); here a workgroup
@@ -181,12 +182,12 @@ __global__ __launch_bounds__(256) void dcn_fwd_kernel(const float* __restrict__ 
   }
 }
 
-// ------------------------------------------------------------------------------------------ backward: input + offset
-// MTC = ceil(CP/32) row tiles of gcol[c][p] = sum_k W[k][c][t] * go[k][p]
-template <int MTC, bool DO_DX>
+// ------------------------------------------------------------------------------------------ backward: offset
+// grad_offset beside the packed scatter (which has produced grad_input).  MTC = ceil(CP/32) row tiles of gcol[c][p] = sum_k W[k][c][t] * go[k][p]
+template <int MTC>
 __global__ __launch_bounds__(256) void dcn_bwd_data_kernel(const float* __restrict__ x, const float* __restrict__ offset,
                                                            const float* __restrict__ wt2 /*[T][K][CT]*/, const float* __restrict__ go,
-                                                           float* __restrict__ dx, float* __restrict__ doff, DcnP p, long long* gi_shadow) {
+                                                           float* __restrict__ doff, DcnP p) {
   extern __shared__ __align__(16) float smem[];
   constexpr int CT = 32 * MTC;
   float* s_go = smem;                    // [K][SP]
@@ -197,7 +198,6 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_kernel(const float* __restri
   const long long pos0 = (long long)(blockIdx.x % p.tiles_per_b) * TP;
   const long long chan = (long long)p.D * p.H * p.W;
   const float* xb = x + (long long)b * p.C * chan;
-  float* dxb = dx + (long long)b * p.C * chan;
   const float* off_b = offset + (long long)b * 3 * p.T * p.P;
   float* doff_b = doff + (long long)b * 3 * p.T * p.P;
 
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_kernel(const float* __restri
       }
     }
     __syncthreads();
-    // scatter + coordinate gradients: thread = (voxel pp, channel residue q)
+    // coordinate gradients: thread = (voxel pp, channel residue q)
     float gd = 0.f, gh = 0.f, gw = 0.f;
     if (cn.valid) {
       long long idx[8];
@@ -246,12 +246,10 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_kernel(const float* __restri
       for (int c = q; c < p.C; c += 4) {
         const float gcv = s_gc[c * SP + pp];
         const float* xc = xb + (long long)c * chan;
-        float* dxc = dxb + (long long)c * chan;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           if (idx[j] < 0) continue;
           const int jd = (j >> 2) & 1, jh = (j >> 1) & 1, jw = j & 1;
-          if (DO_DX) dcn_acc_add(dx, gi_shadow, &dxc[idx[j]], wg[j] * gcv);       // cuh:313-331 (fallback path)
           const float v = xc[idx[j]] * gcv;
           const float fd = jd ? cn.ld : 1.f - cn.ld, fh = jh ? cn.lh : 1.f - cn.lh, fw = jw ? cn.lw : 1.f - cn.lw;
           gd += (jd ? 1.f : -1.f) * fh * fw * v;                                  // cuh:131-187
@@ -1726,8 +1724,8 @@ struct DcnBwd {
 };
 
 // grad_input by LDS-privatised scatter: a packed fixed-point region (two channels per ds_add_u64) with the per-chunk max |W| as the
-// quantisation bound.  DPF_ERR_UNSUPPORTED (nothing launched): K > 64 or the haloed region does not fit; the gather kernel then scatters
-// with reference-style global atomics.
+// quantisation bound.  DPF_ERR_UNSUPPORTED (nothing launched): K > 64 or the haloed region does not fit; the gather family
+// (dcn_bwd_gather) then produces it with reference-style global atomics.
 int dcn_bwd_grad_input(const DcnBwd& b, int grad_input_channels) {
   const DcnP& p = b.p;
   if (p.K > 64) return DPF_ERR_UNSUPPORTED;
@@ -1790,7 +1788,7 @@ int dcn_bwd_offset_region(const DcnBwd& b, int CH, int nchunk) {
 
 // grad_offset + grad_weight on the LDS-image kernels (they rely on the packed grad_input kernel for grad_input): tier 1, the model's
 // configuration: lean-sampler kernel of dcn_lean.hip; tier 2: role-split region kernel.  Both add grad_weight partials into
-// dwtmp[8][T][nchunk][64][16], folded here.  DPF_ERR_UNSUPPORTED: neither ran, the gather kernels have to.
+// dwtmp[8][T][nchunk][64][16], folded here.  DPF_ERR_UNSUPPORTED: neither ran, dcn_bwd_offset_weight_gather has to.
 int dcn_bwd_offset_weight(const DcnBwd& b, bool model_config) {
   const DcnP& p = b.p;
   const int CH = dcn_chunk(p.C), nchunk = (p.C + CH - 1) / CH;
@@ -1807,20 +1805,18 @@ int dcn_bwd_offset_weight(const DcnBwd& b, bool model_config) {
   return DPF_OK;
 }
 
-// grad_offset + grad_weight, tier 3 -- everything else: samples gathered from global memory; unless dx_done, grad_input too (global atomics)
-int dcn_bwd_gather(const DcnBwd& b, bool dx_done) {
+// grad_offset + grad_weight, tier 3 beside the packed scatter (DPF_DCN_V1, or no haloed image fits): samples gathered from global memory.
+// These two kernels are the ancestors of dcn_gather.hip's and stay for this one case: without the grad_input scatter the data kernel needs 88
+// registers where the family's needs 148, and measured 7-14 % faster at the model's shapes (profiles/dcn_fallback_family_timings.txt).
+int dcn_bwd_offset_weight_gather(const DcnBwd& b) {
   DcnP p = b.p;
   const int MT = (p.K + 31) / 32, MTC = b.CT / 32;
   hipLaunchKernelGGL(repack_weights_kernel, dim3(dpf_ew_grid((long long)p.T * p.K * b.CT)), dim3(256), 0, b.st, b.weight, b.ws, p.K, p.C, p.T, b.CT, 1);
   const long long ntile = (long long)p.B * p.tiles_per_b;
   {
     const size_t lds = sizeof(float) * ((size_t)p.K * SP + (size_t)b.CT * SP + 3 * 4 * TP);
-    const decltype(&dcn_bwd_data_kernel<1, false>) kern[4][2] = {{dcn_bwd_data_kernel<1, false>, dcn_bwd_data_kernel<1, true>},   // C <= MAXC: MTC <= 4
-                                                                 {dcn_bwd_data_kernel<2, false>, dcn_bwd_data_kernel<2, true>},
-                                                                 {dcn_bwd_data_kernel<3, false>, dcn_bwd_data_kernel<3, true>},
-                                                                 {dcn_bwd_data_kernel<4, false>, dcn_bwd_data_kernel<4, true>}};
-    if (dcn_launch(kern[MTC - 1][dx_done ? 0 : 1], dim3((unsigned)ntile), dim3(256), lds, b.st, b.input, b.offset, b.ws, b.grad_output, b.grad_input, b.grad_offset, p,
-                   b.gi_shadow) != DPF_OK)
+    const decltype(&dcn_bwd_data_kernel<1>) kern[4] = {dcn_bwd_data_kernel<1>, dcn_bwd_data_kernel<2>, dcn_bwd_data_kernel<3>, dcn_bwd_data_kernel<4>};   // C <= MAXC: MTC <= 4
+    if (dcn_launch(kern[MTC - 1], dim3((unsigned)ntile), dim3(256), lds, b.st, b.input, b.offset, b.ws, b.grad_output, b.grad_offset, p) != DPF_OK)
       return DPF_ERR_LAUNCH;
   }
   long long nchunkw = 2048 / p.T;
@@ -1837,7 +1833,8 @@ int dcn_bwd_gather(const DcnBwd& b, bool dx_done) {
   return dcn_launch(kern, dim3((unsigned)(p.T * p.nchunk)), dim3(256), lds, b.st, b.input, b.offset, b.grad_output, b.grad_weight, p);
 }
 
-// group > 1 or deformable_group > 1: the rank-3 kernels of dcn_gather.hip, with the repacked weights in the repack region of the workspace map and
+// The rank-3 kernels of dcn_gather.hip: every call with group > 1 or deformable_group > 1, and the single-group backward whose grad_input the
+// packed scatter declined (K > 64, or no haloed region fits).  The repacked weights sit in the repack region of the workspace map and
 // the deterministic-mode shadow of grad_weight in its replica region.  Both regions are sized from whole C and K (K (C/group) T <= K C T), so
 // the caller's workspace queries hold for every grouping; the bounds are checked here all the same.
 int dcn_fwd_grouped(const DcnP& p, int group, int deformable_group, const float* input, const float* weight, const float* bias, const float* offset,
@@ -1846,7 +1843,8 @@ int dcn_fwd_grouped(const DcnP& p, int group, int deformable_group, const float*
   return dcn_gather_forward(3, p, group, deformable_group, input, weight, bias, offset, nullptr, output, ws, room, st);
 }
 
-int dcn_bwd_grouped(const DcnBwd& b, int group, int deformable_group, int grad_input_channels) {
+// all four gradients but grad_bias; grad_input by global atomics or into its shadow
+int dcn_bwd_gather(const DcnBwd& b, int group, int deformable_group, int grad_input_channels) {
   const DcnP& p = b.p;
   const long long dw_elems = (long long)p.K * (p.C / group) * p.T;
   if (b.det && 4 * dw_elems > b.m.wmax - b.m.dwtmp) return DPF_ERR_UNSUPPORTED;
@@ -1951,16 +1949,17 @@ int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const
     if (hipMemsetAsync(b.gi_shadow, 0, sizeof(long long) * 2 * (size_t)in_elems, b.st) != hipSuccess) return DPF_ERR_LAUNCH;
   }
   if (hipMemsetAsync(grad_weight, 0, sizeof(float) * (size_t)K * (grouped ? C / group : C) * b.p.T, b.st) != hipSuccess) return DPF_ERR_LAUNCH;
-  if (grouped) {
-    rc = dcn_bwd_grouped(b, group, deformable_group, grad_input_channels);
-  } else {
-    // grad_input: packed LDS scatter, or left to the gather kernel.  grad_offset + grad_weight: lean -> region (beside the packed scatter
-    // only) -> gather.
+  // Single group: grad_input by the packed LDS scatter, and beside it grad_offset + grad_weight by lean -> region -> gather.  Where the packed
+  // scatter declines, and for every other grouping, the gather family produces all of them.
+  rc = DPF_ERR_UNSUPPORTED;
+  if (!grouped) {
     rc = dcn_bwd_grad_input(b, grad_input_channels);
-    const bool dx_done = rc == DPF_OK;
-    if (dx_done) rc = dcn_bwd_offset_weight(b, dcn_is_model_config(kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw));
-    if (rc == DPF_ERR_UNSUPPORTED) rc = dcn_bwd_gather(b, dx_done);
+    if (rc == DPF_OK) {
+      rc = dcn_bwd_offset_weight(b, dcn_is_model_config(kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw));
+      if (rc == DPF_ERR_UNSUPPORTED) rc = dcn_bwd_offset_weight_gather(b);
+    }
   }
+  if (rc == DPF_ERR_UNSUPPORTED) rc = dcn_bwd_gather(b, group, deformable_group, grad_input_channels);
   if (rc != DPF_OK) return rc;
   if (b.det) dcn_finalize(b.gi_shadow, grad_input, in_elems, b.st);
   if (grad_bias) {

@@ -1,7 +1,9 @@
 // The gather-kernel family of the deformable convolutions with the grouping as a kernel argument, one set of kernels templated on the spatial
 // rank ND:
-//   ND = 3: deformable 3-D convolution with group > 1 and / or deformable_group > 1 (deform_conv_cuda.cu:65-66,84-121;
-//           deform_im2col_cuda.cuh:222-232), reached from dcn3d.hip: weight [K][C/group][T], offset [B][deformable_group * 3T][P], no mask.
+//   ND = 3: deformable 3-D convolution, every grouping (deform_conv_cuda.cu:65-66,84-121; deform_im2col_cuda.cuh:222-232), reached from
+//           dcn3d.hip: every call with group > 1 or deformable_group > 1, and the single-group backward whose grad_input the packed scatter
+//           declines (K > 64, or no haloed region fits; with (1, 1) the reduce spans are the whole of C and K).  Weight [K][C/group][T], offset
+//           [B][deformable_group * 3T][P], no mask.
 //   ND = 2: deformable 2-D convolution, plain (DCN v1) and modulated (v2, per-sample mask), every grouping -- the reference's second compiled
 //           extension `deform_conv_cuda` (src/module/dcn/src/deform_conv_cuda.cpp:687-697 over deform_conv_cuda_kernel.cu:190,279,373,570,635,
 //           695), reached from dcn2d.hip: input [B][C][H][W], weight [K][C/group][kh][kw], offset [B][dg * 2T][Ho][Wo] (channel 2(i kw + j) = h,

@@ -94,7 +94,7 @@ __device__ __forceinline__ long long corner_index(const DcnP& p, const Corner& c
 
 // The family's environment switches (README "Environment switches"), read once per process by dcn_env() (dcn3d.hip).
 struct DcnEnv {
-  bool v1;           // DPF_DCN_V1 set: first-generation gather kernels only
+  bool v1;           // DPF_DCN_V1 set: gather kernels only (grad_input still from the packed scatter where that fits)
   int lean;          // DPF_DCN_LEAN (1): 0 = lean kernels off; bit 2 (4) = only the lean grad_offset kernel off
   int fwd6;          // DPF_DCN_FWD6 (1): 0 = lean forward on the fp32 matrix instruction
   int lean_wide12;   // DPF_DCN_LEAN_WIDE12 (0): 1 = 12-channel lean forward on the wider x halo, one workgroup per CU (3.7 vs 2.6 ms)
@@ -133,7 +133,7 @@ int dcn_lean_forward(const float* x, const float* offset, const float* weight, c
 int dcn_lean_bwd_offset(const float* x, const float* offset, const float* weight, const float* go, float* doff, float* dwtmp, float* ws, int B, int C,
                         int D, int H, int W, int K, hipStream_t st, int det = 0);
 
-// The gather family with the grouping as a kernel argument (dcn_gather.hip), rank 3 (dcn3d.hip: group > 1 or deformable_group > 1) or rank 2
+// The gather family with the grouping as a kernel argument (dcn_gather.hip), rank 3 (dcn3d.hip: group > 1 or deformable_group > 1, and the single-group backward without the packed scatter) or rank 2
 // (dcn2d.hip: every call): a fixed number of launches per call, every product on the fp32 matrix instruction.
 // dcn_group_check: DPF_ERR_INVALID_ARG unless group divides C and K and deformable_group divides C.
 // mask: [B][deformable_group * T][P] or nullptr; rank 3 has none.  wpack: room for wpack_floats floats, where the block-diagonal weights are

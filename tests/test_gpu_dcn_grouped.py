@@ -1,6 +1,7 @@
-"""GPU parity tests of the deformable convolution with group / deformable_group > 1 (the rank-3 kernels of csrc/dcn_gather.hip), called through the C ABI
-(ops.deform_conv_forward_raw / ops.deform_conv_backward_raw), against oracle.dcn3d.deform_conv3d_forward_grouped in fp64 and its fp64
-autograd (tests/test_oracle_dcn.py pins that to F.conv3d(groups)).
+"""GPU parity tests of rank 3 of the gather family (csrc/dcn_gather.hip) for every grouping: the deformable 3-D convolution with group /
+deformable_group > 1, and with (1, 1) at shapes that the lean, region and packed-scatter tiers of csrc/dcn3d.hip decline (K > 64), so that the
+family's backward serves them as the single-group fallback (their forward is the gather kernel of csrc/dcn3d.hip).  Called through the C ABI (ops.deform_conv_forward_raw / ops.deform_conv_backward_raw),
+against oracle.dcn3d.deform_conv3d_forward_grouped in fp64 and its fp64 autograd (tests/test_oracle_dcn.py pins that to F.conv3d(groups)).
 
 Tolerances: the operator's own at these operand scales (x 1, offset 1.2, weight 0.1, bias 1; tests/test_gpu_ops.py): forward 1e-4, every
 gradient 2e-4 of the reference tensor's maximum.  Known answers with plain fp32 summation: 1e-5.
@@ -39,6 +40,10 @@ def rnd(*shape, seed=0, scale=1.0):
 
 K3, ONE = (3, 3, 3), (1, 1, 1)
 BASE = (2, 16, 8, 3, 6, 12)     # 216 voxels: three full 64-voxel tiles and a tail of 24
+# Single-group fallback.  K = 96 > 64: dcn_lean_forward and dcn_fwd_region (forward), dcn_bwd_grad_input and dcn_bwd_offset_weight (backward)
+# all decline on K > 64, so with no switch set the forward comes from the gather kernel of dcn3d.hip and all four gradients from the family,
+# grad_input by atomics.  Three row tiles.
+SINGLE = ((1, 16, 96, 2, 6, 12), K3, ONE, ONE, ONE, (1, 1))
 
 
 def _cases():
@@ -54,6 +59,10 @@ def _cases():
         ((1, 96, 96, 2, 6, 12), K3, ONE, ONE, ONE, [(2, 3)]),                               # more than one 32-row matrix tile per group
         ((1, 128, 128, 1, 4, 8), K3, ONE, ONE, ONE, [(4, 2)]),                              # the channel limit
         ((1, 64, 64, 1, 4, 8), K3, ONE, ONE, ONE, [(2, 2)]),                                # K = 64: four forward tiles, one accumulator on every wave
+        # (1, 1) on the single-group entry; each has K > 64, which every other tier declines (see SINGLE)
+        SINGLE[:5] + ([SINGLE[5]],),
+        ((1, 128, 128, 1, 4, 8), K3, ONE, ONE, ONE, [(1, 1)]),                              # the channel limit: 16 weight-gradient tiles (NA = 4), 8 gcol tiles
+        ((1, 15, 96, 2, 9, 13), (1, 3, 3), (1, 2, 2), (0, 1, 1), ONE, [(1, 1)]),            # odd C (the zeroed pad row), stride 2, 9 taps, a tail tile
     ]
     return [(shape, k, s, p, d, g) for shape, k, s, p, d, gs in rows for g in gs]
 
@@ -142,28 +151,29 @@ def test_integer_offsets_and_the_validity_rule():
     """Random integer offsets in [-2, 2] put samples on voxel centres, on coordinate -1 and on the far border: a sample outside the OPEN interval
     (-1, size) has no value and no coordinate derivative (deform_im2col_cuda.cuh:248) -- forward and gradients against the oracle."""
     _check_case(((1, 8, 8, 3, 5, 6), K3, ONE, ONE, ONE, (2, 2)), integer_offsets=True)
+    _check_case(((1, 8, 96, 3, 5, 6), K3, ONE, ONE, ONE, (1, 1)), integer_offsets=True)     # K > 64: the single-group fallback
 
 
-def test_grad_input_channels_cut_inside_a_group():
-    """gi_channels = 10 of 16 with (2, 2): the cut falls inside conv group 1 and offset group 1.  grad_input[:, :10] is the oracle's,
-    grad_input[:, 10:] exactly zero, the other three gradients are unchanged."""
+@pytest.mark.parametrize('case', [(BASE, K3, ONE, ONE, ONE, (2, 2)), SINGLE], ids=_id)
+def test_grad_input_channels_cut_inside_a_group(case):
+    """gi_channels = 10 of 16 with (2, 2): the cut falls inside conv group 1 and offset group 1; with (1, 1) on the single-group fallback it
+    falls inside the one group.  grad_input[:, :10] is the oracle's, grad_input[:, 10:] exactly zero, the other three gradients are unchanged."""
     ops = _ops()
-    case = (BASE, K3, ONE, ONE, ONE, (2, 2))
     (x, off, w, b, go), _, g_ref = _problem(case)
     xg, og, wg, bg, gg = _gpu((x, off, w, b, go))
-    gi, goff, gw, gb = ops.deform_conv_backward_raw(xg, wg, bg, og, gg, ONE, ONE, ONE, 2, 2, gi_channels=10)
+    gi, goff, gw, gb = ops.deform_conv_backward_raw(xg, wg, bg, og, gg, ONE, ONE, ONE, *case[5], gi_channels=10)
     close(gi[:, :10], g_ref[0][:, :10], 2e-4, 'grad_input[:, :10]')
     assert (gi[:, 10:] == 0).all()
     for a, r, nm in zip((goff, gw, gb), g_ref[1:], GRADS[1:]):
         close(a, r, 2e-4, 'gi_channels: ' + nm)
 
 
-@pytest.mark.parametrize('groups', [(2, 4), (4, 2)])
-def test_deterministic_mode_is_bitwise_reproducible(groups):
+@pytest.mark.parametrize('case', [(BASE, K3, ONE, ONE, ONE, (2, 4)), (BASE, K3, ONE, ONE, ONE, (4, 2)), SINGLE], ids=_id)
+def test_deterministic_mode_is_bitwise_reproducible(case):
     """Under ops.deterministic_mode() five backward launches return the same bits for all four gradients (the first meets the parity
     tolerances); outside it grad_offset is still bitwise equal over five launches: every element is written once, by one workgroup."""
     ops = _ops()
-    case = (BASE, K3, ONE, ONE, ONE, groups)
+    groups = case[5]
     (x, off, w, b, go), _, g_ref = _problem(case)
     xg, og, wg, bg, gg = _gpu((x, off, w, b, go))
     with ops.deterministic_mode():

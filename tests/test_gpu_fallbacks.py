@@ -14,8 +14,11 @@ SETS = [
     ({'DPF_DCN_LEAN': '0'}, 'test_deform_conv and not full_size'),
     # lean forward, but grad_offset + grad_weight on the role-split region kernel (which re-packs the weights at the head of the workspace once the lean kernel has declined)
     ({'DPF_DCN_LEAN': '4'}, 'test_deform_conv and not full_size'),
-    # first-generation deformable kernels (global-memory gathers: what geometries without a fitting LDS image fall back to)
+    # gather kernels only (global-memory gathers: what geometries without a fitting LDS image fall back to); grad_input still from the packed
+    # scatter where that fits, with the gather tier's grad_offset and grad_weight kernels beside it
     ({'DPF_DCN_V1': '1'}, 'test_deform_conv and not full_size'),
+    # the same in deterministic mode: the packed scatter writes the shadow of grad_input, the gather tier's weight gradient runs as one chunk per tap
+    ({'DPF_DCN_V1': '1', 'DPF_DETERMINISTIC': '1'}, 'test_deform_conv and not full_size'),
     # the deformable conv backward's gcol products (grad_input and grad_offset kernels) on the fp32 matrix instruction instead of the f16 components
     ({'DPF_DCN_GCOL16': '0'}, 'test_deform_conv and not full_size'),
     # the 35-channel forward on the wider x halo (one workgroup per CU)
