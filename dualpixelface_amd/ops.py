@@ -1655,6 +1655,58 @@ def stereo_losses(pred_depth, pred_normal, disp, normal, mask, head_weights, lam
     return LossFn.apply(pred_depth, pred_normal, disp, normal, mask, tuple(head_weights), lam_d, lam_n)
 
 
+LOSS_KIND = {'smoothL1': 0, 'silog': 1}
+LOSS_TRANSFORM = {'identity': 0, 'reciprocal': 1}
+LOSS_STATS = 17             # doubles the forward leaves for the backward: M, mean d per head, sqrt of the variance term per head
+
+
+class DepthLossFn(torch.autograd.Function):
+    """The loss bank (csrc/loss_bank.hip) -> 0-dim loss.  Workspace and stats are fresh tensors and nothing is read on the host, so the
+    call is capturable inside the train-step graph like LossFn."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask, conf, head_weights, kind, transform, variance_focus):
+        pred, target = _c(pred), _c(target)
+        mask = None if mask is None else _c(mask)
+        conf = None if conf is None else _c(conf)
+        _need(pred, target, mask, conf)
+        B, n, H, W = pred.shape
+        for name, t in (('target', target), ('mask', mask), ('conf', conf)):
+            if t is not None and tuple(t.shape) != (B, H, W):
+                raise DpfError('depth_loss: %s %s does not match pred %s' % (name, tuple(t.shape), tuple(pred.shape)))
+        if len(head_weights) != n:
+            raise DpfError('depth_loss: %d head weights for %d heads' % (len(head_weights), n))
+        nbytes = lib().call('dpf_depth_loss_workspace_bytes', B, H, W)
+        if nbytes < 0:
+            raise DpfError('depth_loss: shape B=%d H=%d W=%d is not supported' % (B, H, W))
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=pred.device)
+        stats = torch.empty(LOSS_STATS, dtype=torch.float64, device=pred.device)
+        out = torch.empty((), dtype=torch.float32, device=pred.device)
+        cfg = (LOSS_KIND[kind], LOSS_TRANSFORM[transform], B, n, H, W, tuple(float(w) for w in head_weights), float(variance_focus))
+        lib().call('dpf_depth_loss_forward', cfg[0], cfg[1], _ptr(pred), _ptr(target), _ptr(mask), _ptr(conf), B, n, H, W,
+                   _host_floats(cfg[6]), cfg[7], _ptr(ws), nbytes, _ptr(stats), _ptr(out), _stream())
+        ctx.save_for_backward(pred, target, mask, conf, stats)
+        ctx.cfg = cfg
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, target, mask, conf, stats = ctx.saved_tensors
+        kind, transform, B, n, H, W, weights, vf = ctx.cfg
+        gout = _c(gout)
+        _need(gout)
+        dpred = torch.empty_like(pred)
+        lib().call('dpf_depth_loss_backward', kind, transform, _ptr(pred), _ptr(target), _ptr(mask), _ptr(conf), B, n, H, W,
+                   _host_floats(weights), vf, _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
+        return dpred, None, None, None, None, None, None, None
+
+
+def depth_loss(pred, target, mask=None, conf=None, head_weights=(1.0,), kind='smoothL1', transform='identity', variance_focus=0.0):
+    """pred [B, n <= 8, H, W] against target [B, H, W] over the pixels with mask > 0 (None: all), both sides times conf (None: no product);
+    kind 'smoothL1' | 'silog', transform 'identity' | 'reciprocal' (of pred; non-finite -> 0 with a zero gradient) -> 0-dim loss."""
+    return DepthLossFn.apply(pred, target, mask, conf, tuple(head_weights), kind, transform, variance_focus)
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-5, gscale=1.0):
     _need(param, grad, exp_avg, exp_avg_sq)
     lib().call('dpf_adam_step', _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), int(step), float(lr), float(beta1),

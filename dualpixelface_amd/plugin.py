@@ -39,8 +39,11 @@ class _PluginHooks(object):
         results = self.network(batch)
         self.last_taps = results.pop('_taps')
         if self.training and 'disp' in batch:
-            results.update(self.loss_model.forward(results, batch))
+            results.update(self.loss_model.forward(results, batch, target_type=self._target_type()))
         return results
+
+    def _target_type(self):
+        return getattr(self.option.model, 'target_type', 'disp')
 
     def _loaders(self, train, batch_size, shuffle):
         import torch.utils.data as torch_data
@@ -73,7 +76,7 @@ class _PluginHooks(object):
     def validation_step(self, batch, batch_idx):
         results = self.forward(batch)
         if 'depth' in batch:
-            self.metric_model.forward(results, batch)
+            self.metric_model.forward(results, batch, target_type=self._target_type())
         return results
 
     def validation_epoch_end(self, outputs):

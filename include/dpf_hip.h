@@ -379,6 +379,28 @@ int dpf_loss_forward(const float* pred_depth, const float* pred_normal, const fl
 int dpf_loss_backward(const float* pred_depth, const float* pred_normal, const float* disp, const float* normal, const float* mask,
                       const float* acc_ws, const float* gout, float* d_pred_depth, float* d_pred_normal, int B, int n, int H, int W,
                       const float* head_weights_host, float lambda_depth, float lambda_normal, void* stream);
+/* ---- the depth-target loss bank (src/loss/depth/smoothL1.py:41-45, src/loss/depth/silog.py:45-48; csrc/loss_bank.hip).  pred [B, n, H, W]
+ * with 1 <= n <= 8, target [B, H, W], mask [B, H, W] or NULL (every pixel counts; otherwise those with mask > 0), conf [B, H, W] or NULL.
+ * Per element in fp32: p~ = T(pred) * conf, g~ = target * conf; T = identity or the reciprocal with NaN / +-Inf replaced by 0
+ * (src/utils/geometry.py:118-136).  SMOOTHL1: sum_k w_k * mean smoothl1(p~ - g~);  SILOG: d = w_k * (log p~ - log g~),
+ * sum_k 10 * sqrt(mean d^2 - variance_focus * mean(d)^2), no clamp (NaN for a counted non-positive argument or an empty mask).  Sums are
+ * fp64 in two phases, no floating-point atomics: results repeat bit for bit.  ws: dpf_depth_loss_workspace_bytes() bytes of 8-byte
+ * aligned device scratch (-1: shape refused); stats: 17 device doubles the forward leaves for the backward (M, mean d per head, sqrt of the
+ * variance term per head); out: one device float.  The backward writes every element of dpred (0 under the mask); where the reciprocal was
+ * replaced by 0 the gradient is 0 (the reference's autograd gives NaN there).  gout: one device float.  Refusals launch nothing:
+ * DPF_ERR_INVALID_ARG for n < 1, n > 8, an unknown kind or transform, a NULL required pointer, B, H or W <= 0 or a workspace that is
+ * too small; DPF_ERR_UNSUPPORTED for B > 65535. */
+#define DPF_LOSS_SMOOTHL1 0
+#define DPF_LOSS_SILOG 1
+#define DPF_LOSS_T_IDENTITY 0
+#define DPF_LOSS_T_RECIPROCAL 1
+long long dpf_depth_loss_workspace_bytes(int B, int H, int W);
+int dpf_depth_loss_forward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, int B,
+                           int n, int H, int W, const float* head_weights_host, float variance_focus, void* ws, long long ws_bytes,
+                           double* stats, float* out, void* stream);
+int dpf_depth_loss_backward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, int B,
+                            int n, int H, int W, const float* head_weights_host, float variance_focus, const double* stats,
+                            const float* gout, float* dpred, void* stream);
 int dpf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, int step, double lr, double beta1,
                   double beta2, double eps, float gscale, void* stream);
 /* the same update with the two step-dependent scalars { (float)(lr / (1 - beta1^step)), (float)(1 / sqrt(1 - beta2^step)) } read from device
