@@ -91,6 +91,15 @@ class Spec(object):
         self.bn(p + '.1', cout)
 
 
+def geometry_abvalue(batch, what):
+    """batch['abvalue'] for a coordinate volume.  A batch without it can still be trained against (losses.py fits (a, b) to the prediction),
+    but the volume would have to be built from a fit of a prediction that is made after it: not built."""
+    if 'abvalue' not in batch:
+        raise NotImplementedError("%s builds its coordinate volume from batch['abvalue'], which this batch does not have (the 'least_square' "
+                                  "conversion fits it to the prediction, after the volume)" % what)
+    return batch['abvalue'].float()
+
+
 def cost_levels(mindisp, maxdisp, level):
     """The quarter-resolution disparity of every cost level (stereodpnet/modules.py:144-145)."""
     step = (maxdisp / 4.0 - mindisp / 4.0) / float(level)

@@ -3,9 +3,12 @@
 //
 //   dpf_depth_loss_forward    per-workgroup partial sums -> one fold -> the loss (one float) and the stats record of the backward
 //   dpf_depth_loss_backward   one pass that writes every element of d pred (0 under the mask)
+//   dpf_depth_loss_forward_ab / _backward_ab   the same with the target formed from a depth map: the 'least_square' conversion
 //
 // Per element, in fp32 and in this order (this file is built with -ffp-contract=off):
 //   p~ = T(p) * conf, g~ = target * conf          (the products are skipped without conf)
+//   with ab [B, 2] = [b, a]: target = a / depth + b, divide then add, NaN and +-Inf replaced by -100 (src/utils/geometry.py:64-69);
+//   ab is data here, no gradient reaches it (the reference fits it under no_grad)
 //   T  = identity, or 1 / p with NaN and +-Inf replaced by 0 (src/utils/geometry.py:118-136); T' = 0 where it was replaced
 //   smooth-L1: S_k = sum smoothl1(p~ - g~), beta = 1;  loss = sum_k w_k * S_k / M
 //   silog:     d = w_k * (logf(p~) - logf(g~)), m1_k = sum d / M, m2_k = sum d^2 / M;  loss = sum_k 10 * sqrt(m2_k - vf * m1_k^2)
@@ -14,6 +17,8 @@
 // Sums are fp64 in two phases (no floating-point atomics): the bits repeat run to run and in every mode.  Nothing here waits on the host.
 #include "dpf_common.h"
 #include <math.h>
+
+extern "C" long long dpf_depth_loss_workspace_bytes(int B, int H, int W);
 
 namespace {
 
@@ -83,6 +88,13 @@ __device__ __forceinline__ void store_vec(float* __restrict__ p, const Vec<V>& r
   }
 }
 
+// the target as stored, or the disparity of a stored depth under the sample's (a, b)
+__device__ __forceinline__ float target_of(float g, bool from_depth, float a, float b) {
+  if (!from_depth) return g;
+  const float t = a / g + b;
+  return finite_f(t) ? t : -100.f;
+}
+
 // T(p); kept = false where the reciprocal was replaced by 0
 __device__ __forceinline__ float transform(float p, int recip, bool& kept) {
   kept = true;
@@ -96,11 +108,12 @@ __device__ __forceinline__ float transform(float p, int recip, bool& kept) {
 // every plane 16-byte aligned, so a load never straddles a plane).  part: [B][gridDim.x][kValues].
 template <int KIND, int V>
 __global__ __launch_bounds__(256) void bank_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target,
-                                                           const float* __restrict__ mask, const float* __restrict__ conf, BankP P,
-                                                           double* __restrict__ part) {
+                                                           const float* __restrict__ mask, const float* __restrict__ conf,
+                                                           const float* __restrict__ ab, BankP P, double* __restrict__ part) {
   const long long b = blockIdx.y, HW = P.HW;
   const float* __restrict__ predb = pred + (size_t)b * P.n * (size_t)HW;
   const size_t base = (size_t)b * (size_t)HW;
+  const float ta = ab ? ab[2 * b + 1] : 0.f, tb = ab ? ab[2 * b] : 0.f;
   double acc[kValues];
 #pragma unroll
   for (int k = 0; k < kValues; ++k) acc[k] = 0.0;
@@ -114,7 +127,8 @@ __global__ __launch_bounds__(256) void bank_partial_kernel(const float* __restri
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       on[j] = mask ? (m.v[j] > 0.f) : true;
-      gt[j] = conf ? g.v[j] * c.v[j] : g.v[j];
+      const float t = target_of(g.v[j], ab != nullptr, ta, tb);
+      gt[j] = conf ? t * c.v[j] : t;
       if (KIND == KIND_SILOG) gt[j] = logf(gt[j]);
       if (on[j]) acc[2 * kMaxHeads] += 1.0;
     }
@@ -180,11 +194,13 @@ __global__ __launch_bounds__(256) void bank_fold_kernel(const double* __restrict
 // d loss / d pred, every element written (0 under the mask).  Same grid as the forward.
 template <int KIND, int V>
 __global__ __launch_bounds__(256) void bank_backward_kernel(const float* __restrict__ pred, const float* __restrict__ target,
-                                                            const float* __restrict__ mask, const float* __restrict__ conf, BankP P,
+                                                            const float* __restrict__ mask, const float* __restrict__ conf,
+                                                            const float* __restrict__ ab, BankP P,
                                                             const double* __restrict__ stats, const float* __restrict__ gout,
                                                             float* __restrict__ dpred) {
   const long long b = blockIdx.y, HW = P.HW;
   const size_t pbase = (size_t)b * P.n * (size_t)HW, base = (size_t)b * (size_t)HW;
+  const float ta = ab ? ab[2 * b + 1] : 0.f, tb = ab ? ab[2 * b] : 0.f;
   const double M = stats[0], go = (double)gout[0];
   float coef[kMaxHeads], shift[kMaxHeads];
 #pragma unroll
@@ -207,7 +223,8 @@ __global__ __launch_bounds__(256) void bank_backward_kernel(const float* __restr
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       on[j] = mask ? (m.v[j] > 0.f) : true;
-      gt[j] = conf ? g.v[j] * c.v[j] : g.v[j];
+      const float t = target_of(g.v[j], ab != nullptr, ta, tb);
+      gt[j] = conf ? t * c.v[j] : t;
       if (KIND == KIND_SILOG) gt[j] = logf(gt[j]);
     }
 #pragma unroll
@@ -263,6 +280,50 @@ int prepare(int kind, int transform, const float* pred, const float* target, int
   return DPF_OK;
 }
 
+int forward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, const float* ab, int B, int n,
+            int H, int W, const float* weights, float vf, void* ws, long long ws_bytes, double* stats, float* out, void* stream) {
+  dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
+  BankP P;
+  const int rc = prepare(kind, transform, pred, target, B, n, H, W, weights, vf, P);
+  if (rc != DPF_OK) return rc;
+  if (!ws || !stats || !out || ws_bytes < dpf_depth_loss_workspace_bytes(B, H, W) || ((uintptr_t)ws & 7u)) return DPF_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int gx = blocks_per_sample(P.HW);
+  const dim3 grid(gx, B), block(kBlock);
+  double* part = (double*)ws;
+  const bool v4 = P.HW % 4 == 0 && aligned16(pred) && aligned16(target) && aligned16(mask) && aligned16(conf);
+  if (kind == KIND_SILOG) {
+    if (v4) hipLaunchKernelGGL((bank_partial_kernel<KIND_SILOG, 4>), grid, block, 0, st, pred, target, mask, conf, ab, P, part);
+    else hipLaunchKernelGGL((bank_partial_kernel<KIND_SILOG, 1>), grid, block, 0, st, pred, target, mask, conf, ab, P, part);
+    hipLaunchKernelGGL(bank_fold_kernel<KIND_SILOG>, dim3(1), block, 0, st, part, (long long)B * gx, P, stats, out);
+  } else {
+    if (v4) hipLaunchKernelGGL((bank_partial_kernel<KIND_SMOOTHL1, 4>), grid, block, 0, st, pred, target, mask, conf, ab, P, part);
+    else hipLaunchKernelGGL((bank_partial_kernel<KIND_SMOOTHL1, 1>), grid, block, 0, st, pred, target, mask, conf, ab, P, part);
+    hipLaunchKernelGGL(bank_fold_kernel<KIND_SMOOTHL1>, dim3(1), block, 0, st, part, (long long)B * gx, P, stats, out);
+  }
+  return dpf_check_launch();
+}
+
+int backward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, const float* ab, int B, int n,
+             int H, int W, const float* weights, float vf, const double* stats, const float* gout, float* dpred, void* stream) {
+  dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
+  BankP P;
+  const int rc = prepare(kind, transform, pred, target, B, n, H, W, weights, vf, P);
+  if (rc != DPF_OK) return rc;
+  if (!stats || !gout || !dpred) return DPF_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(blocks_per_sample(P.HW), B), block(kBlock);
+  const bool v4 = P.HW % 4 == 0 && aligned16(pred) && aligned16(target) && aligned16(mask) && aligned16(conf) && aligned16(dpred);
+  if (kind == KIND_SILOG) {
+    if (v4) hipLaunchKernelGGL((bank_backward_kernel<KIND_SILOG, 4>), grid, block, 0, st, pred, target, mask, conf, ab, P, stats, gout, dpred);
+    else hipLaunchKernelGGL((bank_backward_kernel<KIND_SILOG, 1>), grid, block, 0, st, pred, target, mask, conf, ab, P, stats, gout, dpred);
+  } else {
+    if (v4) hipLaunchKernelGGL((bank_backward_kernel<KIND_SMOOTHL1, 4>), grid, block, 0, st, pred, target, mask, conf, ab, P, stats, gout, dpred);
+    else hipLaunchKernelGGL((bank_backward_kernel<KIND_SMOOTHL1, 1>), grid, block, 0, st, pred, target, mask, conf, ab, P, stats, gout, dpred);
+  }
+  return dpf_check_launch();
+}
+
 }  // namespace
 
 extern "C" {
@@ -275,47 +336,28 @@ long long dpf_depth_loss_workspace_bytes(int B, int H, int W) {
 int dpf_depth_loss_forward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, int B,
                            int n, int H, int W, const float* head_weights_host, float variance_focus, void* ws, long long ws_bytes,
                            double* stats, float* out, void* stream) {
-  dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
-  BankP P;
-  const int rc = prepare(kind, transform, pred, target, B, n, H, W, head_weights_host, variance_focus, P);
-  if (rc != DPF_OK) return rc;
-  if (!ws || !stats || !out || ws_bytes < dpf_depth_loss_workspace_bytes(B, H, W) || ((uintptr_t)ws & 7u)) return DPF_ERR_INVALID_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int gx = blocks_per_sample(P.HW);
-  const dim3 grid(gx, B), block(kBlock);
-  double* part = (double*)ws;
-  const bool v4 = P.HW % 4 == 0 && aligned16(pred) && aligned16(target) && aligned16(mask) && aligned16(conf);
-  if (kind == KIND_SILOG) {
-    if (v4) hipLaunchKernelGGL((bank_partial_kernel<KIND_SILOG, 4>), grid, block, 0, st, pred, target, mask, conf, P, part);
-    else hipLaunchKernelGGL((bank_partial_kernel<KIND_SILOG, 1>), grid, block, 0, st, pred, target, mask, conf, P, part);
-    hipLaunchKernelGGL(bank_fold_kernel<KIND_SILOG>, dim3(1), block, 0, st, part, (long long)B * gx, P, stats, out);
-  } else {
-    if (v4) hipLaunchKernelGGL((bank_partial_kernel<KIND_SMOOTHL1, 4>), grid, block, 0, st, pred, target, mask, conf, P, part);
-    else hipLaunchKernelGGL((bank_partial_kernel<KIND_SMOOTHL1, 1>), grid, block, 0, st, pred, target, mask, conf, P, part);
-    hipLaunchKernelGGL(bank_fold_kernel<KIND_SMOOTHL1>, dim3(1), block, 0, st, part, (long long)B * gx, P, stats, out);
-  }
-  return dpf_check_launch();
+  return forward(kind, transform, pred, target, mask, conf, nullptr, B, n, H, W, head_weights_host, variance_focus, ws, ws_bytes, stats, out,
+                 stream);
 }
 
 int dpf_depth_loss_backward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, int B,
                             int n, int H, int W, const float* head_weights_host, float variance_focus, const double* stats,
                             const float* gout, float* dpred, void* stream) {
-  dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
-  BankP P;
-  const int rc = prepare(kind, transform, pred, target, B, n, H, W, head_weights_host, variance_focus, P);
-  if (rc != DPF_OK) return rc;
-  if (!stats || !gout || !dpred) return DPF_ERR_INVALID_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(blocks_per_sample(P.HW), B), block(kBlock);
-  const bool v4 = P.HW % 4 == 0 && aligned16(pred) && aligned16(target) && aligned16(mask) && aligned16(conf) && aligned16(dpred);
-  if (kind == KIND_SILOG) {
-    if (v4) hipLaunchKernelGGL((bank_backward_kernel<KIND_SILOG, 4>), grid, block, 0, st, pred, target, mask, conf, P, stats, gout, dpred);
-    else hipLaunchKernelGGL((bank_backward_kernel<KIND_SILOG, 1>), grid, block, 0, st, pred, target, mask, conf, P, stats, gout, dpred);
-  } else {
-    if (v4) hipLaunchKernelGGL((bank_backward_kernel<KIND_SMOOTHL1, 4>), grid, block, 0, st, pred, target, mask, conf, P, stats, gout, dpred);
-    else hipLaunchKernelGGL((bank_backward_kernel<KIND_SMOOTHL1, 1>), grid, block, 0, st, pred, target, mask, conf, P, stats, gout, dpred);
-  }
-  return dpf_check_launch();
+  return backward(kind, transform, pred, target, mask, conf, nullptr, B, n, H, W, head_weights_host, variance_focus, stats, gout, dpred, stream);
+}
+
+int dpf_depth_loss_forward_ab(int kind, int transform, const float* pred, const float* depth, const float* ab, const float* mask,
+                              const float* conf, int B, int n, int H, int W, const float* head_weights_host, float variance_focus, void* ws,
+                              long long ws_bytes, double* stats, float* out, void* stream) {
+  if (!ab) return DPF_ERR_INVALID_ARG;
+  return forward(kind, transform, pred, depth, mask, conf, ab, B, n, H, W, head_weights_host, variance_focus, ws, ws_bytes, stats, out, stream);
+}
+
+int dpf_depth_loss_backward_ab(int kind, int transform, const float* pred, const float* depth, const float* ab, const float* mask,
+                               const float* conf, int B, int n, int H, int W, const float* head_weights_host, float variance_focus,
+                               const double* stats, const float* gout, float* dpred, void* stream) {
+  if (!ab) return DPF_ERR_INVALID_ARG;
+  return backward(kind, transform, pred, depth, mask, conf, ab, B, n, H, W, head_weights_host, variance_focus, stats, gout, dpred, stream);
 }
 
 }  // extern "C"

@@ -11,27 +11,30 @@ from . import ops
 TARGET_TYPES = ('disp', 'depth', 'idepth')
 
 
-_NO_LEAST_SQUARE = "dp_conversion='least_square' (scipy lsq_linear on the host; broken in the reference for masked batches) is not built"
+def takes_least_square(batch):
+    """smoothL1.py:28, silog.py:29: a batch that brings no (a, b) has its disparity conversion fitted (the reference's 'least_square'
+    branch).  The other way into that branch, dataset.dp_conversion == 'least_square' over a batch that does bring one, stays refused."""
+    return 'abvalue' not in batch
 
 
-def _given_only(option):
-    if option.dataset.dp_conversion != 'given':
-        # (the reference's own 'least_square' branch cannot run on a batch with a mask -- which every FaceDP batch has: its target is
-        # [B, 1, H, W] (smoothL1.py:29-30) and is then indexed with the [B, H, W] mask (smoothL1.py:38): IndexError)
-        raise NotImplementedError(_NO_LEAST_SQUARE)
-
-
-def _abvalue(batch):
-    if 'abvalue' not in batch:                  # smoothL1.py:28, silog.py:29: such a batch takes the 'least_square' branch
-        raise NotImplementedError(_NO_LEAST_SQUARE)
-    return batch['abvalue']
+def _fit(preds, batch):
+    """The fitted conversion (src/utils/geometry.py::regress_affine on the device, ops.affine_fit): [b, a] per sample between head 0 of the
+    raw prediction and batch['idepth'], whatever the target type; detached, as the reference fits under no_grad."""
+    missing = [k for k in ('idepth', 'depth') if k not in batch]
+    if missing:
+        raise NotImplementedError("a batch without 'abvalue' takes the 'least_square' disparity conversion, which needs batch[%s]"
+                                  % "] and batch[".join(repr(k) for k in missing))
+    return ops.affine_fit(preds['pred_depth'], batch['idepth'])
 
 
 class _DepthLoss(object):
-    """What the two depth losses share: the 'given' conversion only, and one weight per prediction head (smoothL1.py:22, silog.py:23)."""
+    """What the two depth losses share: the conversion rule, and one weight per prediction head (smoothL1.py:22, silog.py:23)."""
 
     def __init__(self, option):
-        _given_only(option)
+        if option.dataset.dp_conversion != 'given':
+            # the fit itself is built and every batch without 'abvalue' takes it; ignoring an 'abvalue' the batch does bring is not switched on
+            raise NotImplementedError("dp_conversion=%r is not built as a dataset setting (a batch without 'abvalue' takes the 'least_square' "
+                                      "fit under 'given')" % (option.dataset.dp_conversion,))
         self.weights = list(option.model.loss_weight)
 
     def head_weights(self, n):
@@ -39,16 +42,23 @@ class _DepthLoss(object):
 
 
 class SMOOTHL1Loss(_DepthLoss):
-    """Masked smooth-L1 over the prediction heads (src/loss/depth/smoothL1.py:15-49, 'given' conversion)."""
+    """Masked smooth-L1 over the prediction heads (src/loss/depth/smoothL1.py:15-49)."""
 
     def forward(self, preds, batch, target_type='disp'):
         assert target_type in TARGET_TYPES
         pd = preds['pred_depth']
+        transform = 'reciprocal' if target_type == 'depth' else 'identity'          # smoothL1.py:27
+        if takes_least_square(batch):
+            # smoothL1.py:29-30 with the [B, H, W] target the class lacks: depth2disp(batch['depth'], ab) is formed inside the loss kernels
+            ab = _fit(preds, batch)
+            loss = ops.depth_loss(pd, batch['depth'], batch.get('mask'), batch.get('conf'), self.head_weights(pd.shape[1]), 'smoothL1',
+                                  transform, target_ab=ab)
+            return {'loss': loss, 'abvalue': ab}
         if target_type != 'disp':
             # smoothL1.py:27,33: the prediction against batch['idepth'], inverted first when it is a depth; conf is fused (csrc/loss_bank.hip)
             loss = ops.depth_loss(pd, batch['idepth'], batch.get('mask'), batch.get('conf'), self.head_weights(pd.shape[1]), 'smoothL1',
-                                  'reciprocal' if target_type == 'depth' else 'identity')
-            return {'loss': loss, 'abvalue': _abvalue(batch)}
+                                  transform)
+            return {'loss': loss, 'abvalue': batch['abvalue']}
         gt = batch['disp']
         if batch.get('conf') is not None:
             # confidence-weighted variant (smoothL1.py:33-36): both sides of the difference are multiplied by the per-pixel confidence.  No
@@ -60,7 +70,7 @@ class SMOOTHL1Loss(_DepthLoss):
 
 
 class SILOGLoss(_DepthLoss):
-    """Masked scale-invariant log loss over the prediction heads (src/loss/depth/silog.py:16-52, 'given' conversion)."""
+    """Masked scale-invariant log loss over the prediction heads (src/loss/depth/silog.py:16-52)."""
 
     def __init__(self, option):
         super(SILOGLoss, self).__init__(option)
@@ -69,8 +79,15 @@ class SILOGLoss(_DepthLoss):
     def forward(self, preds, batch, target_type='disp'):
         assert target_type in TARGET_TYPES
         pd = preds['pred_depth']
-        abvalue = _abvalue(batch)
-        # silog.py:28-37: prediction and target are both overwritten for 'depth', so no target type inverts the prediction here
+        fitted = takes_least_square(batch)
+        abvalue = _fit(preds, batch) if fitted else batch['abvalue']
+        if fitted and target_type != 'depth':
+            # silog.py:30-31 with the [B, H, W] target; a non-positive a / depth + b gives NaN as in the reference (no clamp)
+            loss = ops.depth_loss(pd, batch['depth'], batch.get('mask'), batch.get('conf'), self.head_weights(pd.shape[1]), 'silog',
+                                  'identity', self.variance_focus, target_ab=abvalue)
+            return {'loss': loss, 'abvalue': abvalue}
+        # silog.py:28-37: prediction and target are both overwritten for 'depth', so no target type inverts the prediction here (and under
+        # the fitted conversion only the returned abvalue is the fit's)
         loss = ops.depth_loss(pd, batch[target_type], batch.get('mask'), batch.get('conf'), self.head_weights(pd.shape[1]), 'silog',
                               'identity', self.variance_focus)
         return {'loss': loss, 'abvalue': abvalue}
@@ -105,9 +122,12 @@ class loss_selector(object):
             self.loss_name.append(name)
             self.lambda_.append(lam)
 
+    def least_square(self, batch):
+        return takes_least_square(batch)
+
     def forward(self, results, batch, target_type='disp'):
-        # shipped configuration (stereodpnet/config.json:2,4): one fused reduction pass for both losses
-        if target_type == 'disp' and self.loss_name == ['smoothL1', 'cosine'] and results.get('pred_normal') is not None and 'mask' in batch and batch.get('conf') is None:
+        # shipped configuration (stereodpnet/config.json:2,4): one fused reduction pass for both losses, against the disparity the batch brings
+        if not self.least_square(batch) and target_type == 'disp' and self.loss_name == ['smoothL1', 'cosine'] and results.get('pred_normal') is not None and 'mask' in batch and batch.get('conf') is None:
             pd, pn = results['pred_depth'], results['pred_normal']
             out = ops.stereo_losses(pd, pn[:, 0], batch['disp'], batch['normal'], batch['mask'],
                                     self.loss_func[0].head_weights(pd.shape[1]), self.lambda_[0], self.lambda_[1])

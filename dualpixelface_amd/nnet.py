@@ -10,7 +10,7 @@ per-level 2-D refinement of the cost slices guided by the reference features, an
 import torch
 
 from . import ops
-from .core import ArenaModule, Spec, cost_levels, set_levels
+from .core import ArenaModule, Spec, cost_levels, geometry_abvalue, set_levels
 from .ops import ACT_LEAKY, ACT_NONE, ACT_RELU
 from .psmnet import PSMFeatures, psm_feature_spec
 
@@ -96,7 +96,7 @@ class NNetCore(PSMFeatures, ArenaModule):
             self._levels_key = lk
         levels = self._levels
         xyz = torch.empty((B, 3, L, h, w), dtype=torch.float32, device=cost0.device)
-        ops.xyz_volume_into(xyz, 0, levels, batch['K'].float(), batch['abvalue'].float())
+        ops.xyz_volume_into(xyz, 0, levels, batch['K'].float(), geometry_abvalue(batch, 'NNet'))
         wc = ops.concat_channels([xyz, cost_in0, cost0])                            # [B, 3 + 2C, L, h, w]
         wc = self._convbn3(wc, p + '.wc0.0', 1, ACT_RELU)
         wc = self._convbn3(wc, p + '.wc0.2', 1, ACT_RELU)
@@ -116,6 +116,8 @@ class NNetCore(PSMFeatures, ArenaModule):
     def _network(self, batch):
         """NNET.forward without the loss (mainmodel.py:112-167)."""
         m = self.option.model
+        if m.predict_normal:
+            geometry_abvalue(batch, 'NNet')                                         # refuse before anything is enqueued
         a, b = self._views(batch)
         ref = self._features(a)
         tar = self._features(b)

@@ -1665,12 +1665,15 @@ class DepthLossFn(torch.autograd.Function):
     call is capturable inside the train-step graph like LossFn."""
 
     @staticmethod
-    def forward(ctx, pred, target, mask, conf, head_weights, kind, transform, variance_focus):
+    def forward(ctx, pred, target, mask, conf, head_weights, kind, transform, variance_focus, target_ab=None):
         pred, target = _c(pred), _c(target)
         mask = None if mask is None else _c(mask)
         conf = None if conf is None else _c(conf)
-        _need(pred, target, mask, conf)
+        target_ab = None if target_ab is None else _c(target_ab.detach())
+        _need(pred, target, mask, conf, target_ab)
         B, n, H, W = pred.shape
+        if target_ab is not None and (tuple(target_ab.shape) != (B, 2) or target_ab.dtype != torch.float32):
+            raise DpfError('depth_loss: target_ab %s %s, float32 [%d, 2] expected' % (tuple(target_ab.shape), target_ab.dtype, B))
         for name, t in (('target', target), ('mask', mask), ('conf', conf)):
             if t is not None and tuple(t.shape) != (B, H, W):
                 raise DpfError('depth_loss: %s %s does not match pred %s' % (name, tuple(t.shape), tuple(pred.shape)))
@@ -1683,28 +1686,63 @@ class DepthLossFn(torch.autograd.Function):
         stats = torch.empty(LOSS_STATS, dtype=torch.float64, device=pred.device)
         out = torch.empty((), dtype=torch.float32, device=pred.device)
         cfg = (LOSS_KIND[kind], LOSS_TRANSFORM[transform], B, n, H, W, tuple(float(w) for w in head_weights), float(variance_focus))
-        lib().call('dpf_depth_loss_forward', cfg[0], cfg[1], _ptr(pred), _ptr(target), _ptr(mask), _ptr(conf), B, n, H, W,
-                   _host_floats(cfg[6]), cfg[7], _ptr(ws), nbytes, _ptr(stats), _ptr(out), _stream())
-        ctx.save_for_backward(pred, target, mask, conf, stats)
+        if target_ab is None:
+            lib().call('dpf_depth_loss_forward', cfg[0], cfg[1], _ptr(pred), _ptr(target), _ptr(mask), _ptr(conf), B, n, H, W,
+                       _host_floats(cfg[6]), cfg[7], _ptr(ws), nbytes, _ptr(stats), _ptr(out), _stream())
+        else:
+            lib().call('dpf_depth_loss_forward_ab', cfg[0], cfg[1], _ptr(pred), _ptr(target), _ptr(target_ab), _ptr(mask), _ptr(conf), B, n,
+                       H, W, _host_floats(cfg[6]), cfg[7], _ptr(ws), nbytes, _ptr(stats), _ptr(out), _stream())
+        ctx.save_for_backward(pred, target, mask, conf, stats, target_ab)
         ctx.cfg = cfg
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        pred, target, mask, conf, stats = ctx.saved_tensors
+        pred, target, mask, conf, stats, target_ab = ctx.saved_tensors
         kind, transform, B, n, H, W, weights, vf = ctx.cfg
         gout = _c(gout)
         _need(gout)
         dpred = torch.empty_like(pred)
-        lib().call('dpf_depth_loss_backward', kind, transform, _ptr(pred), _ptr(target), _ptr(mask), _ptr(conf), B, n, H, W,
-                   _host_floats(weights), vf, _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
-        return dpred, None, None, None, None, None, None, None
+        if target_ab is None:
+            lib().call('dpf_depth_loss_backward', kind, transform, _ptr(pred), _ptr(target), _ptr(mask), _ptr(conf), B, n, H, W,
+                       _host_floats(weights), vf, _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
+        else:
+            lib().call('dpf_depth_loss_backward_ab', kind, transform, _ptr(pred), _ptr(target), _ptr(target_ab), _ptr(mask), _ptr(conf), B, n,
+                       H, W, _host_floats(weights), vf, _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
+        return dpred, None, None, None, None, None, None, None, None
 
 
-def depth_loss(pred, target, mask=None, conf=None, head_weights=(1.0,), kind='smoothL1', transform='identity', variance_focus=0.0):
+def depth_loss(pred, target, mask=None, conf=None, head_weights=(1.0,), kind='smoothL1', transform='identity', variance_focus=0.0,
+               target_ab=None):
     """pred [B, n <= 8, H, W] against target [B, H, W] over the pixels with mask > 0 (None: all), both sides times conf (None: no product);
-    kind 'smoothL1' | 'silog', transform 'identity' | 'reciprocal' (of pred; non-finite -> 0 with a zero gradient) -> 0-dim loss."""
-    return DepthLossFn.apply(pred, target, mask, conf, tuple(head_weights), kind, transform, variance_focus)
+    kind 'smoothL1' | 'silog', transform 'identity' | 'reciprocal' (of pred; non-finite -> 0 with a zero gradient) -> 0-dim loss.
+    With target_ab [B, 2] = [b, a], `target` is the depth map and the kernels compare against a / depth + b (non-finite -> -100); no
+    gradient reaches target_ab."""
+    return DepthLossFn.apply(pred, target, mask, conf, tuple(head_weights), kind, transform, variance_focus, target_ab)
+
+
+AFFINE_FIT_F_SCALE, AFFINE_FIT_MAX_ITERS, AFFINE_FIT_TOL = 0.1, 48, 1e-7      # DESIGN.md section 7 has the probe behind the last two
+AFFINE_FIT_INFO = 6         # doubles per sample: A, B, reweighted solves used, valid pixels, objective at (A, B), objective at the start
+
+
+def affine_fit(pred, idepth, f_scale=AFFINE_FIT_F_SCALE, max_iters=AFFINE_FIT_MAX_ITERS, tol=AFFINE_FIT_TOL, return_info=False):
+    """src/utils/geometry.py::regress_affine on the device (csrc/affine_fit.hip): per sample the soft-L1 line pred[:, 0] = a * idepth + b over
+    the pixels with idepth > 0 -> detached float32 [B, 2] = [b, a]; with return_info also the fp64 [B, 6] record.  Workspace and results are
+    fresh tensors and nothing is read on the host, so the call is capturable inside the train-step graph like DepthLossFn."""
+    pred, idepth = _c(pred.detach()), _c(idepth.detach())
+    _need(pred, idepth)
+    if pred.dim() != 4 or tuple(idepth.shape) != (pred.shape[0],) + tuple(pred.shape[2:]) or idepth.dtype != torch.float32:
+        raise DpfError('affine_fit: idepth %s does not match pred %s' % (tuple(idepth.shape), tuple(pred.shape)))
+    B, n, H, W = pred.shape
+    nbytes = lib().call('dpf_affine_fit_workspace_bytes', B, H, W)
+    if nbytes < 0:
+        raise DpfError('affine_fit: shape B=%d H=%d W=%d is not supported' % (B, H, W))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=pred.device)
+    ab = torch.empty((B, 2), dtype=torch.float32, device=pred.device)
+    info = torch.empty((B, AFFINE_FIT_INFO), dtype=torch.float64, device=pred.device)
+    lib().call('dpf_affine_fit', _ptr(pred), n * H * W, _ptr(idepth), B, H, W, float(f_scale), int(max_iters), float(tol), _ptr(ws), nbytes,
+               _ptr(ab), _ptr(info), _stream())
+    return (ab, info) if return_info else ab
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-5, gscale=1.0):

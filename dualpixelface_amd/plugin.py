@@ -38,8 +38,12 @@ class _PluginHooks(object):
     def _forward(self, batch):
         results = self.network(batch)
         self.last_taps = results.pop('_taps')
-        if self.training and 'disp' in batch:
+        # (a batch without 'abvalue': the loss fits (a, b) and needs depth and inverse depth, not 'disp')
+        fitted = self.loss_model.least_square(batch) and 'depth' in batch and 'idepth' in batch
+        if self.training and ('disp' in batch or fitted):
             results.update(self.loss_model.forward(results, batch, target_type=self._target_type()))
+        elif not self.training and 'idepth' in batch and 'abvalue' not in batch and results.get('pred_depth') is not None:
+            results['abvalue'] = ops.affine_fit(results['pred_depth'], batch['idepth'])       # what metrics.absolute_dp converts with
         return results
 
     def _target_type(self):

@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import ops
-from .core import ArenaModule, Spec, cost_levels, set_levels
+from .core import ArenaModule, Spec, cost_levels, geometry_abvalue, set_levels
 from .ops import ACT_NONE, ACT_RELU, ACT_PRELU, ACT_LEAKY, ACT_SIGMOID
 from .sampler_tables import build_phase_tables, build_shift_tables, is_fractional
 
@@ -348,10 +348,11 @@ class StereoDPNetCore(HourglassAggregation, ArenaModule):
     def _normals(self, cost, disp_full, batch):
         P, p, m = self._P, 'normal_estimator', self.option.model
         B, C, D, h, w = cost.shape
+        abvalue = geometry_abvalue(batch, 'StereoDPNet with predict_normal')
         self._register_grid(p, h, w, cost.device)                                       # lazy, resolution specific
         if not m.use_sampling:
             raise NotImplementedError('use_sampling=false is not on the StereoDPNet hot path')
-        vol, idx = ops.anm_volume(cost, disp_full, batch['K'].float(), batch['abvalue'].float(), self.costrange, int(m.dsample_num),
+        vol, idx = ops.anm_volume(cost, disp_full, batch['K'].float(), abvalue, self.costrange, int(m.dsample_num),
                                   getattr(self, 'anm_idx_override', None))      # (diagnostic hook of the parity tests, see ops.AnmVolumeFn)
         self.last_anm_idx = idx                  # selected cost levels [B, k, h, w] (diagnostics / tests)
         if m.use_deform:
@@ -375,6 +376,8 @@ class StereoDPNetCore(HourglassAggregation, ArenaModule):
     # ------------------------------------------------------------------ whole network (mainmodel.py:67-104)
     def _network(self, batch):
         opt = self.option
+        if opt.model.predict_normal:
+            geometry_abvalue(batch, 'StereoDPNet with predict_normal')         # refuse before anything is enqueued
         a, b = self._views(batch)
         if FEATURES_TWO_STREAMS and getattr(self, '_two_streams_ok', False) and self.training and self.stat_exchange is None and a.is_cuda:
             # (enabled by train_step, which sets _two_streams_ok; plain forward() callers stay on one stream)

@@ -401,6 +401,34 @@ int dpf_depth_loss_forward(int kind, int transform, const float* pred, const flo
 int dpf_depth_loss_backward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, int B,
                             int n, int H, int W, const float* head_weights_host, float variance_focus, const double* stats,
                             const float* gout, float* dpred, void* stream);
+/* The same two passes with the target formed from a depth map (the 'least_square' conversion, src/loss/depth/smoothL1.py:28-30): depth
+ * [B, H, W] takes the place of target and ab [B, 2] = [b, a] comes with it; per pixel in fp32 target = a / depth + b, divide then add, NaN
+ * and +-Inf replaced by -100 (src/utils/geometry.py:64-69), then everything as above.  ab is data: no gradient is formed for it.  Same
+ * workspace, stats record and refusals, and DPF_ERR_INVALID_ARG for a NULL ab. */
+int dpf_depth_loss_forward_ab(int kind, int transform, const float* pred, const float* depth, const float* ab, const float* mask,
+                              const float* conf, int B, int n, int H, int W, const float* head_weights_host, float variance_focus, void* ws,
+                              long long ws_bytes, double* stats, float* out, void* stream);
+int dpf_depth_loss_backward_ab(int kind, int transform, const float* pred, const float* depth, const float* ab, const float* mask,
+                               const float* conf, int B, int n, int H, int W, const float* head_weights_host, float variance_focus,
+                               const double* stats, const float* gout, float* dpred, void* stream);
+
+/* ---- robust affine fit (csrc/affine_fit.hip): src/utils/geometry.py::regress_affine on the device -----------------------------------
+ * Per sample the line y = A x + B between x = idepth [B, H, W] and y = head 0 of pred (a contiguous H W plane per sample,
+ * pred_batch_stride floats apart: n H W for pred [B, n, H, W]) over the pixels with x > 0 (NaN is not valid) that minimises
+ * sum f_scale^2 * 2 (sqrt(1 + (r / f_scale)^2) - 1), r = A x + B - y (scipy's soft_l1), by iteratively reweighted least squares from the
+ * ordinary least-squares line: weights 1 / sqrt(1 + (r / f_scale)^2) at the previous (A, B), 2x2 normal equations, all in fp64.
+ * |det| < 1e-30 gives A = 0, B = sum w y / sum w, or (0, 0) without a valid pixel.  A sample stops once |dA| max x + |dB| < tol (the step
+ * in disparity units) or after max_iters reweighted solves; 1 + max_iters (pass, fold) launch pairs and one closing pair are enqueued
+ * whatever the data, and a stopped sample's launches return at once.  Two-phase fixed-order sums, no floating-point atomics, nothing
+ * waits on the host or on another workgroup: results repeat bit for bit and the call can be captured in a graph.
+ * ab [B, 2] float32 = [b, a] = [B, A] (the order of batch['abvalue']); info [B, 6] doubles = A, B, reweighted solves used, valid pixels,
+ * the objective at (A, B), the objective at the least-squares start.  ws: dpf_affine_fit_workspace_bytes() bytes of 8-byte aligned device
+ * scratch (-1: shape refused); it needs no initialisation.  Refusals launch nothing: DPF_ERR_INVALID_ARG for a NULL pointer, B, H or
+ * W <= 0, max_iters < 0, f_scale <= 0, tol < 0, pred_batch_stride < H W or a workspace that is too small or misaligned;
+ * DPF_ERR_UNSUPPORTED for B > 65535. */
+long long dpf_affine_fit_workspace_bytes(int B, int H, int W);
+int dpf_affine_fit(const float* pred, long long pred_batch_stride, const float* idepth, int B, int H, int W, double f_scale, int max_iters,
+                   double tol, void* ws, long long ws_bytes, float* ab, double* info, void* stream);
 int dpf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, int step, double lr, double beta1,
                   double beta2, double eps, float gscale, void* stream);
 /* the same update with the two step-dependent scalars { (float)(lr / (1 - beta1^step)), (float)(1 / sqrt(1 - beta2^step)) } read from device
