@@ -46,11 +46,13 @@ class LightningModule(nn.Module):
 
 class Trainer(object):
     """main.py:43-58.  Arguments with no meaning on this stack (benchmark, deterministic, amp_level, profiler, gpus -- one process per
-    GPU comes from the launcher) are accepted and ignored."""
+    GPU comes from the launcher) are accepted and ignored.  accumulate_grad_batches, gradient_clip_val, gradient_clip_algorithm and
+    track_grad_norm, when given, override the option keys of the same names (dualpixelface_amd/optim.py::knobs)."""
 
     def __init__(self, logger=None, checkpoint_callback=True, callbacks=None, resume_from_checkpoint=None, check_val_every_n_epoch=1,
                  accelerator=None, benchmark=None, deterministic=None, gpus=None, precision=32, max_epochs=None, sync_batchnorm=False,
-                 amp_level=None, profiler=None, max_steps=None, log_every_n_steps=10, **ignored):
+                 amp_level=None, profiler=None, max_steps=None, log_every_n_steps=10, accumulate_grad_batches=None, gradient_clip_val=None,
+                 gradient_clip_algorithm=None, track_grad_norm=None, **ignored):
         self.logger = logger
         self.callbacks = list(callbacks or [])
         self.checkpoint_callback = bool(checkpoint_callback)
@@ -60,6 +62,9 @@ class Trainer(object):
         self.max_epochs, self.max_steps = max_epochs, max_steps
         self.sync_batchnorm = bool(sync_batchnorm)
         self.log_every_n_steps = int(log_every_n_steps)
+        self.grad_knobs = {k: v for k, v in (('accumulate_grad_batches', accumulate_grad_batches), ('gradient_clip_val', gradient_clip_val),
+                                             ('gradient_clip_algorithm', gradient_clip_algorithm), ('track_grad_norm', track_grad_norm))
+                           if v is not None}
         self.native = None
 
     def _native(self, model):
@@ -69,6 +74,8 @@ class Trainer(object):
         if self.max_epochs is not None:
             opt.epoch = int(self.max_epochs)
         opt.sync_batch = self.sync_batchnorm
+        for key, value in self.grad_knobs.items():
+            setattr(opt, key, value)
         if str(self.precision) in ('16', 'bf16'):
             opt.precision = self.precision
         workspace = None

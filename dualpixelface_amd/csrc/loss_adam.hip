@@ -174,6 +174,22 @@ __global__ void adam_hyper_kernel(float* __restrict__ p, const float* __restrict
   }
 }
 
+// adam_hyper_kernel behind the gradient control record (grad_ctl.hip): hyper[0..1] as above, the gradient multiplier from ctl[4] (gscale times
+// the clip coefficient, written by dpf_grad_finish) and nothing at all when ctl[3] (apply) is 0 -- a micro-step that does not end its group.
+__global__ void adam_ctl_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n,
+                                const float* __restrict__ ctl, float b1, float b2, float omb1, float omb2, float eps) {
+  if (ctl[3] == 0.f) return;
+  const float lr_over_bc1 = ctl[0], inv_sqrt_bc2 = ctl[1], gscale = ctl[4];
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const float gi = g[i] * gscale;
+    const float mi = b1 * m[i] + omb1 * gi;
+    const float vi = b2 * v[i] + omb2 * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = p[i] - lr_over_bc1 * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
+  }
+}
+
 // ---- SGD with momentum and RMSprop over the same flat arenas.  One kernel per optimiser serves both entry points (lr as an argument /
 // lr in device memory), so a captured replay and an eager step run the same instructions.  fmaf is written out: the rounding of an
 // element must not depend on whether it sits in the 16-byte body or in the scalar head / tail.
@@ -196,11 +212,15 @@ struct RmsOp {
 
 // elements [head, head + 4 * nvec) as 16-byte vectors (the host picks `head` so that all three arenas are 16-byte aligned there, or
 // head = n when they cannot be), the <= 3 + 3 elements around them one by one.  live: one byte per element, 0 = leave parameter and
-// state exactly as they are (nullptr: every element is live).
+// state exactly as they are (nullptr: every element is live).  ctl: nullptr, or the record whose multiplier replaces op.gscale.
 template <class Op>
 __global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s,
                                                     const unsigned char* __restrict__ live, long long n, long long head, float lr_arg,
-                                                    const float* __restrict__ lr_dev, Op op) {
+                                                    const float* __restrict__ lr_dev, const float* __restrict__ ctl, Op op) {
+  if (ctl) {                                               // the gradient control record (grad_ctl.hip): apply flag, multiplier
+    if (ctl[3] == 0.f) return;
+    op.gscale = ctl[4];
+  }
   const float lr = lr_dev ? lr_dev[0] : lr_arg;
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
   const long long nvec = (n - head) / 4;
@@ -238,9 +258,10 @@ long long optim_head(const float* p, const float* g, const float* s, long long n
 }
 
 template <class Op>
-int optim_launch(float* p, const float* g, float* s, const unsigned char* live, long long n, double lr, const float* lr_dev, Op op, void* stream) {
+int optim_launch(float* p, const float* g, float* s, const unsigned char* live, long long n, double lr, const float* lr_dev, Op op, void* stream,
+                 const float* ctl = nullptr) {
   hipLaunchKernelGGL(optim_kernel<Op>, dim3(dpf_ew_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, g, s, live, n, optim_head(p, g, s, n),
-                     (float)lr, lr_dev, op);
+                     (float)lr, lr_dev, ctl, op);
   return dpf_check_launch();
 }
 
@@ -339,6 +360,32 @@ int dpf_rmsprop_step_lr(float* param, const float* grad, float* square_avg, long
   dpf_clear_error();
   if (!param || !grad || !square_avg || !lr_dev || n <= 0) return DPF_ERR_INVALID_ARG;
   return optim_launch(param, grad, square_avg, nullptr, n, 0.0, lr_dev, RmsOp{gscale, (float)alpha, (float)(1.0 - alpha), (float)eps}, stream);
+}
+
+// The three steps behind the gradient control record (grad_ctl.hip; ctl: DPF_GRAD_CTL_FLOATS device floats): the per-step scalars come
+// from ctl[0..1] (Adam's two floats; lr for the others), the gradient multiplier from ctl[4] in place of gscale, and with ctl[3] == 0
+// the launch leaves every element of every arena as it is.
+int dpf_adam_step_ctl(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, const float* ctl, double beta1,
+                      double beta2, double eps, void* stream) {
+  dpf_clear_error();
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !ctl || n <= 0) return DPF_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(adam_ctl_kernel, dim3(dpf_ew_grid(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, ctl,
+                     (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);
+  return dpf_check_launch();
+}
+
+int dpf_sgd_step_ctl(float* param, const float* grad, float* momentum_buf, const unsigned char* live, long long n, const float* ctl,
+                     double momentum, double weight_decay, void* stream) {
+  dpf_clear_error();
+  if (!param || !grad || !momentum_buf || !ctl || n <= 0) return DPF_ERR_INVALID_ARG;
+  return optim_launch(param, grad, momentum_buf, live, n, 0.0, ctl, SgdOp{1.f, (float)momentum, (float)weight_decay}, stream, ctl);
+}
+
+int dpf_rmsprop_step_ctl(float* param, const float* grad, float* square_avg, long long n, const float* ctl, double alpha, double eps,
+                         void* stream) {
+  dpf_clear_error();
+  if (!param || !grad || !square_avg || !ctl || n <= 0) return DPF_ERR_INVALID_ARG;
+  return optim_launch(param, grad, square_avg, nullptr, n, 0.0, ctl, RmsOp{1.f, (float)alpha, (float)(1.0 - alpha), (float)eps}, stream, ctl);
 }
 
 }  // extern "C"

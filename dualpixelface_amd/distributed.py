@@ -125,11 +125,13 @@ class FlatGradReducer(object):
         self._work = []
         self._count = None
 
-    def reduce_all(self):
-        """One all-reduce(SUM) per bucket over the (already complete) arena; no hooks involved."""
+    def reduce_all(self, flat=None):
+        """One all-reduce(SUM) per bucket over the (already complete) arena; no hooks involved.  flat: another arena of the same layout
+        in its place -- the sum of a group of micro-steps under gradient accumulation."""
+        flat = self.flat if flat is None else flat
         if self.collectives:
             self.collective_calls += len(self.buckets)
-            work = [dist.all_reduce(self.flat[lo:hi], op=dist.ReduceOp.SUM, group=self.group, async_op=True) for lo, hi in self.buckets]
+            work = [dist.all_reduce(flat[lo:hi], op=dist.ReduceOp.SUM, group=self.group, async_op=True) for lo, hi in self.buckets]
             for w in work:
                 w.wait()
 

@@ -1801,6 +1801,75 @@ def rmsprop_step_lr(param, grad, square_avg, lr_dev, alpha=0.99, eps=1e-5, gscal
                float(gscale), _stream())
 
 
+# ---- gradient accumulation and global-norm clipping (csrc/grad_ctl.hip).  ctl: the control record, GRAD_CTL_FLOATS device floats --
+# [0:2] the optimiser's per-step scalars, [2] first, [3] apply (the host's), [4] gmul, [5] grad_norm (grad_finish's)
+GRAD_CTL_FLOATS = 8
+GRAD_CTL_FIRST, GRAD_CTL_APPLY, GRAD_CTL_GMUL, GRAD_CTL_NORM = 2, 3, 4, 5
+
+
+def _grad_ws(n, device):
+    nbytes = lib().call('dpf_grad_ctl_workspace_bytes', n)
+    if nbytes < 0:
+        raise DpfError('grad_ctl: an arena of %d elements is not supported' % n)
+    return scratch((nbytes + 3) // 4, device, 'grad_ctl'), nbytes
+
+
+def _need_ctl(ctl):
+    _need(ctl)
+    if ctl.dtype != torch.float32 or ctl.numel() < GRAD_CTL_FLOATS:
+        raise DpfError('grad_ctl: the control record is %d float32 on the GPU' % GRAD_CTL_FLOATS)
+
+
+def grad_fold(acc, grad, ctl, partials=False):
+    """acc = grad when ctl[first] is set, else acc + grad, in fp32; with `partials` and ctl[apply] set the same pass leaves the sums of
+    squares of the new acc for grad_finish."""
+    _need(acc, grad)
+    _need_ctl(ctl)
+    if acc.numel() != grad.numel() or acc.dtype != torch.float32 or grad.dtype != torch.float32:
+        raise DpfError('grad_fold: two float32 arenas of one length expected')
+    ws, nbytes = _grad_ws(acc.numel(), acc.device) if partials else (None, 0)
+    lib().call('dpf_grad_fold', _ptr(acc), _ptr(grad), acc.numel(), _ptr(ctl), _ptr(ws), nbytes, _stream())
+
+
+def grad_sumsq(grad):
+    """The per-workgroup fp64 sums of squares of an arena, left for grad_finish."""
+    _need(grad)
+    ws, nbytes = _grad_ws(grad.numel(), grad.device)
+    lib().call('dpf_grad_sumsq', _ptr(grad), grad.numel(), _ptr(ws), nbytes, _stream())
+
+
+def grad_finish(n, ctl, gscale=1.0, clip=0.0):
+    """After grad_fold(partials=True) or grad_sumsq over n elements on this stream: ctl[grad_norm] = gscale * sqrt(sum),
+    ctl[gmul] = gscale * min(1, clip / (norm + 1e-6)) (clip 0: gscale); nothing when ctl[apply] is 0."""
+    _need_ctl(ctl)
+    ws, nbytes = _grad_ws(n, ctl.device)
+    lib().call('dpf_grad_finish', _ptr(ws), nbytes, n, float(gscale), float(clip), _ptr(ctl), _stream())
+
+
+def adam_step_ctl(param, grad, exp_avg, exp_avg_sq, ctl, beta1=0.9, beta2=0.999, eps=1e-5):
+    """adam_step_hyper behind the control record: scalars from ctl[0:2], the gradient times ctl[gmul], a no-op when ctl[apply] is 0."""
+    _need(param, grad, exp_avg, exp_avg_sq)
+    _need_ctl(ctl)
+    lib().call('dpf_adam_step_ctl', _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), _ptr(ctl), float(beta1),
+               float(beta2), float(eps), _stream())
+
+
+def sgd_step_ctl(param, grad, momentum_buf, ctl, momentum=0.9, weight_decay=2e-4, live=None):
+    """sgd_step_lr behind the control record (the rate in ctl[0])."""
+    _need(param, grad, momentum_buf)
+    _need_ctl(ctl)
+    lib().call('dpf_sgd_step_ctl', _ptr(param), _ptr(grad), _ptr(momentum_buf), _ptr(_live_mask(live, param)), param.numel(), _ptr(ctl),
+               float(momentum), float(weight_decay), _stream())
+
+
+def rmsprop_step_ctl(param, grad, square_avg, ctl, alpha=0.99, eps=1e-5):
+    """rmsprop_step_lr behind the control record (the rate in ctl[0])."""
+    _need(param, grad, square_avg)
+    _need_ctl(ctl)
+    lib().call('dpf_rmsprop_step_ctl', _ptr(param), _ptr(grad), _ptr(square_avg), param.numel(), _ptr(ctl), float(alpha), float(eps),
+               _stream())
+
+
 # ---- validation metrics (csrc/metrics.hip): raw wrappers; results stay on the device, nothing here reads the host
 METRIC_TARGET = {'disp': 0, 'idepth': 1, 'depth': 2}
 

@@ -109,9 +109,16 @@ class _PluginHooks(object):
             self._pairs_cache = cache
         return cache[1]
 
-    def train_step(self, batch, reducer=None, lr=None):
+    def train_step(self, batch, reducer=None, lr=None, last_in_epoch=False):
         """forward + loss + backward + (gradient all-reduce) + the fused step of option.optim (Adam, SGD with momentum, RMSprop, configured as
         selectors.optimizer_selector configures torch's); returns the results dict.
+
+        With option.accumulate_grad_batches = N > 1 a call is a MICRO-step: its gradient is added to the group's, the model counts its
+        position inside the group, and the optimiser runs on the N-th call with (sum of the group) / (N * world_size) -- or earlier on the
+        call that passes last_in_epoch=True, which ends a short group (the divisor stays N).  Ranks exchange the accumulated sum once, on
+        that call.  option.gradient_clip_val = c > 0 scales that gradient by min(1, c / (its global 2-norm + 1e-6)); then, or with
+        option.track_grad_norm = 2, a call on which the optimiser ran returns the norm before clipping as results['grad_norm'] (a device
+        scalar).  All of it stays on the device (optim.Record.group_step, csrc/grad_ctl.hip), so such steps are captured like any other.
 
         Single-process steps on a fixed batch shape are captured into ONE HIP graph after two eager warm-up steps and replayed from then on
         (option.step_graph / DPF_STEP_GRAPH, default on): the ~2 400 kernel launches of a step leave the host once, so the launch gaps between
@@ -121,6 +128,25 @@ class _PluginHooks(object):
         if self.option.optim == 'sgd' and not getattr(self, 'gather_grads', True):
             raise NotImplementedError("optim 'sgd' needs the gather scheme (model.gather_grads): gradients accumulated into arena views do "
                                       "not tell an unused parameter, which SGD must skip, from a zero gradient")
+        knobs = optim.knobs(self.option)
+        if not knobs.on:
+            return self._one_step(batch, reducer, lr)
+        if not getattr(self, 'gather_grads', True):
+            raise NotImplementedError('accumulate_grad_batches, gradient_clip_val and track_grad_norm need the gather scheme '
+                                      '(model.gather_grads): they work on the gathered gradient arena')
+        pos = getattr(self, '_group_pos', 0)                               # micro-steps of the current group already taken
+        first, apply = pos == 0, pos + 1 >= knobs.accum or bool(last_in_epoch)
+        self._micro = (first, apply)
+        try:
+            results = self._one_step(batch, reducer, lr)
+        finally:
+            self._micro = None
+        self._group_pos = 0 if apply else pos + 1
+        if not (apply and knobs.reports):
+            results.pop('grad_norm', None)
+        return results
+
+    def _one_step(self, batch, reducer, lr):
         # (eager when a per-launch profile is being recorded -- ops.PROFILE -- or gradients are exchanged between ranks)
         if reducer is None and ops.PROFILE is None and _graph_enabled(self) and all(v.is_cuda for v in batch.values() if torch.is_tensor(v)):
             return self._graph_step(batch, lr)
@@ -160,7 +186,7 @@ class _PluginHooks(object):
         return tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(tensors.items())) + (
             bool(ops.deterministic()), ops.CONV_OPERANDS_BF16, ops.f32_matrix_path(), ops.WGRAD_ASYNC) + self._capture_key() + (
             self.flat_parameters().data_ptr(), self.flat_gradients(zero=False).data_ptr(), optim.of(self.option).key(self),
-            self.stat_exchange is None)
+            self.stat_exchange is None) + ((optim.knobs(self.option),) if getattr(self, '_micro', None) else ())
 
     def _graph_lookup(self, key):
         """The graph state of `key`, new if need be.  A few states are kept (most recently used last): the last, partial batch of an epoch
@@ -182,7 +208,7 @@ class _PluginHooks(object):
         # static inputs (the caller's tensors are copied in before every replay), the hyper-parameter slot, then the capture itself
         st['inputs'] = {k: v.clone() for k, v in tensors.items()}
         st['extra'] = {k: v for k, v in batch.items() if not torch.is_tensor(v)}
-        st['hyper'] = torch.zeros(2, dtype=torch.float32, device=ss.device)
+        st['hyper'] = torch.zeros(ops.GRAD_CTL_FLOATS if getattr(self, '_micro', None) else 2, dtype=torch.float32, device=ss.device)
         rec = optim.of(self.option)
         counts_before = dict(self._pending_counts)
         step_before = rec.counter_of(self)                 # (Adam's bias-correction counter; the other optimisers have none)
@@ -233,7 +259,7 @@ class _PluginHooks(object):
                 if v.data_ptr() != st['inputs'][k].data_ptr():
                     st['inputs'][k].copy_(v, non_blocking=True)
                     v.record_stream(ss)
-            optim.of(self.option).write_hyper(self, st['hyper'], self._lr(lr))
+            optim.of(self.option).write_hyper(self, st['hyper'], self._lr(lr), getattr(self, '_micro', None))
             st['graph'].replay()
         for name, n in st['counts'].items():
             self._pending_counts[name] = self._pending_counts.get(name, 0) + n
@@ -285,12 +311,34 @@ class _PluginHooks(object):
 
     def _eager_step_body(self, batch, reducer=None, lr=None, hyper=None):
         self.train()
+        micro = getattr(self, '_micro', None)
+        if micro is not None:
+            return self._micro_step_body(batch, reducer, lr, hyper, micro)
         if getattr(self, 'gather_grads', True):
             results, flat_g, dead = self._grads_gathered(batch, reducer)
         else:
             results, flat_g, dead = self._grads_into_views(batch, reducer)
         gscale = 1.0 / reducer.world_size if reducer is not None else 1.0
         optim.of(self.option).step(self, flat_g, dead, hyper, self._lr(lr), gscale)
+        return results
+
+    def _micro_step_body(self, batch, reducer, lr, hyper, micro):
+        """The step with a gradient knob on (train_step).  Everything after the gather is launched on the current stream in one order:
+        fold, (all-reduce), norm, finish, optimiser.  Under accumulation the ranks exchange the accumulated arena on the group's last
+        micro-step only, unstaged; at N = 1 the staged bucket exchange during backward stays."""
+        knobs, rec = optim.knobs(self.option), optim.of(self.option)
+        results, flat_g, dead = self._grads_gathered(batch, reducer if knobs.accum == 1 else None)
+        ctl = hyper
+        if ctl is None:                                    # launched one by one: the model's own record, filled here
+            ctl = getattr(self, '_grad_ctl', None)
+            if ctl is None or ctl.device != flat_g.device:
+                ctl = self._grad_ctl = torch.zeros(ops.GRAD_CTL_FLOATS, dtype=torch.float32, device=flat_g.device)
+            rec.ready(self, flat_g, knobs.accum > 1)
+            rec.write_hyper(self, ctl, self._lr(lr), micro)
+        world = reducer.world_size if reducer is not None else 1
+        norm = rec.group_step(self, flat_g, dead, ctl, knobs, world, micro, reducer, capturing=hyper is not None)
+        if norm is not None:
+            results['grad_norm'] = norm.clone()            # (the record is overwritten by the next optimiser step)
         return results
 
     def _grads_gathered(self, batch, reducer):

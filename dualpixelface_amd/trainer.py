@@ -9,6 +9,9 @@ flat arenas that a generic trainer would not know how to checkpoint, so this mod
     fused ``model.train_step`` (forward + loss + backward + bucketed RCCL all-reduce + Adam / SGD / RMSprop), the scheduler of
     ``scheduler_selector`` (StepLR(35, 0.5) / ExponentialLR(0.5) / CosineAnnealingLR(500, 1e-6) stepped per epoch), validation
     with the metric hooks every epoch, one checkpoint per epoch ``checkpoint_epoch=XX.ckpt``.
+  * the option keys ``accumulate_grad_batches`` (N micro-batches per optimiser step; the last group of an epoch may be short),
+    ``gradient_clip_val`` (global 2-norm) and ``track_grad_norm`` (2), with PL's meaning and executed inside ``train_step``:
+    ``global_step``, ``max_steps`` and ``log_every`` count optimiser steps, and the log records carry ``grad_norm``.
   * checkpoints hold ``state_dict`` under the reference's parameter names (a PL checkpoint of the reference loads into this
     model, and the other way round), the flat optimiser state (Adam moments, SGD momentum buffer or RMSprop square average), the step /
     epoch counters and the learning rate.
@@ -224,17 +227,24 @@ class Trainer(object):
         device = model.flat_parameters().device
         model.train()
         done = False
+        accum = optim.knobs(opt).accum                       # (validated here, before the first batch)
         while self.epoch < int(opt.epoch) and not done:
             lr = epoch_lr(opt, self.epoch)
             t0, n = time.time(), 0
-            for batch in self._shard(train_loader, self.epoch):
+            pending = 0                                      # micro-steps since the last optimiser step; 0 again at every epoch end
+            for batch, last in _flag_last(self._shard(train_loader, self.epoch), accum > 1):
                 batch = self._to_device(batch, device)
-                res = model.train_step(batch, reducer, lr=lr)
-                self.global_step += 1
+                # (the keyword only where it says something: a model without the knobs keeps its train_step(batch, reducer, lr))
+                res = model.train_step(batch, reducer, lr=lr, **({'last_in_epoch': True} if last else {}))
                 n += int(next(iter(batch.values())).shape[0])
+                pending += 1
+                if pending < accum and not last:
+                    continue
+                pending = 0
+                self.global_step += 1
                 if self.global_step % self.log_every == 0 or self.max_steps:
                     rec = {'epoch': self.epoch, 'step': self.global_step, 'lr': lr}
-                    rec.update({k: float(v.detach()) for k, v in res.items() if 'loss' in k and torch.is_tensor(v)})
+                    rec.update({k: float(v.detach()) for k, v in res.items() if ('loss' in k or k == 'grad_norm') and torch.is_tensor(v)})
                     self._log(rec)
                 if self.max_steps and self.global_step >= self.max_steps:
                     done = True
@@ -257,3 +267,21 @@ class Trainer(object):
     def test(self, model, loader=None):
         loader = loader if loader is not None else model.test_dataloader()
         return self.validate(model, loader, test=True)
+
+
+def _flag_last(batches, on):
+    """(batch, whether it is the last one) over `batches`, one batch ahead of the caller; with `on` false nothing is looked ahead and
+    every flag is False."""
+    if not on:
+        for batch in batches:
+            yield batch, False
+        return
+    it = iter(batches)
+    try:
+        held = next(it)
+    except StopIteration:
+        return
+    for batch in it:
+        yield held, False
+        held = batch
+    yield held, True

@@ -451,6 +451,32 @@ int dpf_rmsprop_step(float* param, const float* grad, float* square_avg, long lo
 int dpf_rmsprop_step_lr(float* param, const float* grad, float* square_avg, long long n, const float* lr_dev, double alpha, double eps,
                         float gscale, void* stream);
 
+/* ---- gradient accumulation and global-norm clipping over the flat arenas (csrc/grad_ctl.hip; option keys accumulate_grad_batches,
+ * gradient_clip_val, track_grad_norm).  ctl: the control record, DPF_GRAD_CTL_FLOATS floats of device memory --
+ *   [0], [1] the optimiser's per-step scalars (Adam: the two floats of dpf_adam_step_hyper; SGD / RMSprop: (float)lr, unused), [2] first,
+ *   [3] apply (both: 0 = no), written by the host before the launches; [4] gmul, [5] grad_norm, written by dpf_grad_finish.
+ * dpf_grad_fold: acc[i] = first ? grad[i] : acc[i] + grad[i] in fp32; with ws != NULL and apply set, the same pass leaves the
+ * per-workgroup fp64 sums of squares of the new acc in ws.  dpf_grad_sumsq: those sums for an arena on their own.  dpf_grad_finish: one
+ * workgroup adds them in a fixed order; total = gscale * sqrt(sum); coef = clip > 0 ? min(1, clip / (total + 1e-6)) : 1 (a NaN ratio stays
+ * NaN), all fp64; ctl[4] = (float)(gscale * coef), ctl[5] = (float)total; with apply == 0 it writes nothing.  The *_step_ctl forms of the
+ * three optimisers multiply the gradient by ctl[4] instead of gscale, read their per-step scalars from ctl[0..1] and leave every element
+ * untouched when apply == 0.  Squares and sums are fp64, two phases, no floating-point atomics; arenas whose pointers are all 16-byte
+ * aligned are accessed 16 bytes at a time, others element by element, with the same bits either way.  ws: dpf_grad_ctl_workspace_bytes(n)
+ * bytes of 8-byte aligned device scratch (-1 for n <= 0), no initialisation needed.  Nothing allocates or waits.  Refusals launch nothing:
+ * DPF_ERR_INVALID_ARG for a NULL pointer (dpf_grad_fold alone takes ws == NULL: no sums), n <= 0, clip < 0 or a workspace that is too small
+ * or misaligned. */
+#define DPF_GRAD_CTL_FLOATS 8
+long long dpf_grad_ctl_workspace_bytes(long long n);
+int dpf_grad_fold(float* acc, const float* grad, long long n, const float* ctl, void* ws, long long ws_bytes, void* stream);
+int dpf_grad_sumsq(const float* grad, long long n, void* ws, long long ws_bytes, void* stream);
+int dpf_grad_finish(const void* ws, long long ws_bytes, long long n, double gscale, double clip, float* ctl, void* stream);
+int dpf_adam_step_ctl(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, const float* ctl, double beta1,
+                      double beta2, double eps, void* stream);
+int dpf_sgd_step_ctl(float* param, const float* grad, float* momentum_buf, const unsigned char* live, long long n, const float* ctl,
+                     double momentum, double weight_decay, void* stream);
+int dpf_rmsprop_step_ctl(float* param, const float* grad, float* square_avg, long long n, const float* ctl, double alpha, double eps,
+                         void* stream);
+
 /* ---- FaceDP sample preprocessing: the per-sample host work of the reference's DataLoader workers,
  * dataloader/FaceDP/path_reader.py:150-168 (read_depth), :196-232 (read_disparity), dataloader/preprocess/preprocess.py:46-88
  * (basic_transform.apply), dataloader/preprocess/augmentation.py:62-84 (to_tensor step), :165-178 (crop), :236-262 (Lighting),
