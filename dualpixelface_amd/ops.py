@@ -1745,6 +1745,64 @@ def affine_fit(pred, idepth, f_scale=AFFINE_FIT_F_SCALE, max_iters=AFFINE_FIT_MA
     return (ab, info) if return_info else ab
 
 
+def _filter_operands(name, pred, guide_rgb):
+    """The operands both post-processing filters share: pred [B, n, H, W] (a slice along dim 0 or 1 of a wider tensor is taken as it is,
+    through its batch stride), guide_rgb [B, 3, H, W], the Normalizer's constants as six host floats, and a fresh output."""
+    from .facedp import IMAGENET_MEAN, IMAGENET_STD          # the data path's Normalizer: the one place these constants live
+    pred, guide_rgb = pred.detach(), guide_rgb.detach()
+    for t in (pred, guide_rgb):
+        if not t.is_cuda:
+            raise DpfError('dualpixelface_amd ops need GPU tensors (no CPU fallback)')
+        if t.dtype != torch.float32:
+            raise DpfError('unsupported dtype %s' % t.dtype)
+    if pred.dim() != 4 or guide_rgb.dim() != 4 or guide_rgb.shape[1] != 3 or guide_rgb.shape[0] != pred.shape[0] or \
+            tuple(guide_rgb.shape[2:]) != tuple(pred.shape[2:]):
+        raise DpfError('%s: guide %s does not match pred %s (want [B, 3, H, W] beside [B, n, H, W])'
+                       % (name, tuple(guide_rgb.shape), tuple(pred.shape)))
+    B, n, H, W = pred.shape
+    if not (pred[0].is_contiguous() and (B == 1 or pred.stride(0) >= n * H * W)):
+        pred = pred.contiguous()
+    stride = pred.stride(0) if B > 1 else n * H * W
+    out = torch.empty((B, n, H, W), dtype=torch.float32, device=pred.device)
+    return pred, _c(guide_rgb), stride, _host_floats(tuple(IMAGENET_MEAN) + tuple(IMAGENET_STD)), out
+
+
+def _filter_radius(name, radius):
+    """An integer radius as it is (a float such as 2.7 is refused, not truncated)."""
+    if isinstance(radius, bool) or not hasattr(radius, '__index__'):
+        raise DpfError('%s: radius must be an integer, got %r' % (name, radius))
+    return radius.__index__()
+
+
+def guided_filter(pred, guide_rgb, radius, eps):
+    """The guided filter of csrc/postprocess.hip (He et al., grey guide, clipped square window of `radius`, 1 <= radius <= 32, eps > 0) on
+    every head of pred [B, n, H, W], guided by the luminance of the normalised image guide_rgb [B, 3, H, W] -> a fresh [B, n, H, W].  An
+    inference-time operator, not an autograd node: the inputs are detached.  Scratch comes through scratch(), nothing waits on the host."""
+    radius = _filter_radius('guided_filter', radius)
+    with torch.no_grad():
+        pred, guide_rgb, stride, norm, out = _filter_operands('guided_filter', pred, guide_rgb)
+        B, n, H, W = pred.shape
+        nbytes = lib().call('dpf_guided_filter_workspace_bytes', B, n, H, W, radius)
+        if nbytes < 0:
+            raise DpfError('guided_filter: B=%d n=%d H=%d W=%d radius=%d is not supported (1 <= radius <= 32)' % (B, n, H, W, radius))
+        ws = scratch((nbytes + 3) // 4, pred.device, tag='postprocess')
+        lib().call('dpf_guided_filter', _ptr(pred), stride, _ptr(guide_rgb), B, n, H, W, radius, float(eps), norm, _ptr(ws), nbytes,
+                   _ptr(out), _stream())
+    return out
+
+
+def joint_bilateral_filter(pred, guide_rgb, radius, sigma_space, sigma_color):
+    """The joint bilateral filter of csrc/postprocess.hip (clipped (2 radius + 1)^2 window, 1 <= radius <= 16, Gaussian weights in space and
+    in the guide's luminance) on every head of pred [B, n, H, W] -> a fresh [B, n, H, W].  Detached like guided_filter; needs no scratch."""
+    radius = _filter_radius('joint_bilateral_filter', radius)
+    with torch.no_grad():
+        pred, guide_rgb, stride, norm, out = _filter_operands('joint_bilateral_filter', pred, guide_rgb)
+        B, n, H, W = pred.shape
+        lib().call('dpf_joint_bilateral_filter', _ptr(pred), stride, _ptr(guide_rgb), B, n, H, W, radius, float(sigma_space),
+                   float(sigma_color), norm, _ptr(out), _stream())
+    return out
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-5, gscale=1.0):
     _need(param, grad, exp_avg, exp_avg_sq)
     lib().call('dpf_adam_step', _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), int(step), float(lr), float(beta1),

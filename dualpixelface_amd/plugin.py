@@ -11,7 +11,7 @@ import warnings
 
 import torch
 
-from . import ops, optim
+from . import ops, optim, postprocess
 from .losses import loss_selector
 from .selectors import metric_selector, optimizer_selector, scheduler_selector
 from .dpnet import DPNetCore
@@ -40,6 +40,8 @@ class _PluginHooks(object):
         self.last_taps = results.pop('_taps')
         # (a batch without 'abvalue': the loss fits (a, b) and needs depth and inverse depth, not 'disp')
         fitted = self.loss_model.least_square(batch) and 'depth' in batch and 'idepth' in batch
+        if not self.training and postprocess.active(self.option):   # the fit and the metric hooks below see the filtered map
+            postprocess.apply(self.option, results, batch, guide=self._views(batch)[0])
         if self.training and ('disp' in batch or fitted):
             results.update(self.loss_model.forward(results, batch, target_type=self._target_type()))
         elif not self.training and 'idepth' in batch and 'abvalue' not in batch and results.get('pred_depth') is not None:

@@ -534,6 +534,30 @@ int dpf_metric_affine_dp(const float* pred, const float* target, const float* we
                          const int* rank_target, int B, long long n, int irls_iters, float epsilon, float* out3, void* ws,
                          long long ws_bytes, void* stream);
 
+/* ---- edge-aware post-processing of a prediction (csrc/postprocess.hip; option key post_process, dualpixelface_amd/postprocess.py).  The
+ * reference declares the switches use_guided / use_bilateral and implements neither: the definitions are this project's (DESIGN.md
+ * section 7).  Both filters are out of place (q must not overlap p) and take the same operands: p [B, n, H, W] fp32, samples
+ * p_batch_stride floats apart (n H W for a contiguous tensor), every head filtered with the same guide; guide_rgb [B, 3, H, W] fp32, the
+ * normalised image as the batch holds it; norm_host: six host floats mean[3], std[3] of that normalisation, read during the call;
+ * q [B, n, H, W] contiguous.  The guide plane is the luminance I = 0.299 R + 0.587 G + 0.114 B, R = x_0 std_0 + mean_0 and so on, formed
+ * on the device.  Windows are squares of radius r clipped at the image border; an image smaller than the window is supported.
+ * Guided filter (He et al., grey guide), every mean over the window's own in-image pixel count:
+ *   a = (mean(I p) - mean(I) mean(p)) / (mean(I I) - mean(I)^2 + eps),  b = mean(p) - a mean(I),  q = mean(a) I + mean(b),
+ * three launches (luminance plane; I, p -> a, b; a, b, I -> q).  Moments are accumulated about the first pixel of each workgroup's band,
+ * never raw, and b is kept relative to p[sample, head, 0, 0], so an offset of hundreds of pixels costs no structure in fp32.
+ * ws: dpf_guided_filter_workspace_bytes() bytes of 8-byte aligned device scratch (-1: shape refused); it needs no initialisation.
+ * Joint bilateral filter: q(x) = sum_y w_s w_c p(y) / sum_y w_s w_c, w_s = exp(-|x - y|^2 / 2 sigma_space^2),
+ * w_c = exp(-(I(x) - I(y))^2 / 2 sigma_color^2); the centre tap has weight 1, so the denominator is at least 1.  One launch, no scratch.
+ * No floating-point atomics and every sum in a fixed order: two calls return the same bits.  Nothing allocates or waits on the host, so
+ * the calls can be captured.  Refusals launch nothing: DPF_ERR_INVALID_ARG for a NULL pointer, B, n, H or W <= 0, p_batch_stride < n H W,
+ * r < 1, an eps or sigma that is not positive (as a float), or a workspace that is too small or misaligned; DPF_ERR_UNSUPPORTED for
+ * r > 32 (guided) / r > 16 (bilateral), B n > 65535, or H beyond 65535 bands of 8 (guided) / 16 (bilateral) rows. */
+long long dpf_guided_filter_workspace_bytes(int B, int n, int H, int W, int r);
+int dpf_guided_filter(const float* p, long long p_batch_stride, const float* guide_rgb, int B, int n, int H, int W, int r, double eps,
+                      const float* norm_host, void* ws, long long ws_bytes, float* q, void* stream);
+int dpf_joint_bilateral_filter(const float* p, long long p_batch_stride, const float* guide_rgb, int B, int n, int H, int W, int r,
+                               double sigma_space, double sigma_color, const float* norm_host, float* q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
