@@ -13,49 +13,24 @@
 // once |dA| * max x + |dB| < tol; every later pass and fold of that sample returns at once.  Kernel boundaries are the only hand-off
 // between workgroups, no floating-point atomics: the bits repeat run to run.  Nothing here waits on the host.
 #include "dpf_common.h"
+#include "dpf_reduce.h"
 #include <math.h>
 
 namespace {
 
 constexpr int kBlock = 256;              // threads per block of every kernel here (4 waves)
-constexpr int kWaves = 4;
 constexpr int kItems = 4;                // loads of 4 pixels per thread before the grid stops growing
 constexpr int kMaxBlocks = 1024;         // blocks per sample
 constexpr int kMaxB = 65535;             // samples ride on gridDim.y
 constexpr int kSums = 7;                 // partial row: sum w, w x, w y, w x x, w x y, objective term, count; then max x
 constexpr int kRow = 8;
+constexpr int kWsAlign = 8;              // the workspace holds doubles
 constexpr int kState = 8;                // per sample: A, B, done, iterations, count, max x, objective at the start (-1: not yet), spare
 constexpr int kInfo = 6;                 // as include/dpf_hip.h
 constexpr double kDetMin = 1e-30;
 
 enum { S_A = 0, S_B, S_DONE, S_ITERS, S_COUNT, S_XMAX, S_OBJ0 };
 enum { PASS_FIRST = 0, PASS_REWEIGHT = 1, PASS_OBJECTIVE = 2 };
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// block-wide sums of acc[0 .. kSums) and maximum of acc[kSums] (blockDim.x == 256): thread k < kRow writes value k to out[k]
-__device__ __forceinline__ void block_row(const double (&acc)[kRow], double* __restrict__ out) {
-  __shared__ double sm[kRow][kWaves];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kRow; ++k) {
-    const double v = k < kSums ? wave_sum_d(acc[k]) : wave_max_d(acc[k]);
-    if (lane == 0) sm[k][w] = v;
-  }
-  __syncthreads();
-  const int k = threadIdx.x;
-  if (k < kSums) out[k] = ((sm[k][0] + sm[k][1]) + sm[k][2]) + sm[k][3];
-  else if (k == kSums) out[k] = fmax(fmax(sm[k][0], sm[k][1]), fmax(sm[k][2], sm[k][3]));
-}
 
 template <int MODE>
 __device__ __forceinline__ void pixel(float xf, float yf, double A, double B, double f, double (&acc)[kRow]) {
@@ -109,24 +84,7 @@ __global__ __launch_bounds__(256) void fit_pass_kernel(const float* __restrict__
       pixel<MODE>(xb[i], yb[i], A, B, f, acc);
     }
   }
-  block_row(acc, part + ((size_t)b * gridDim.x + blockIdx.x) * kRow);
-}
-
-// one block per sample: the partial rows of that sample added in a fixed order; tot valid in every thread after the call
-__device__ __forceinline__ void fold_rows(const double* __restrict__ part, int rows, double (&tot)[kRow]) {
-  __shared__ double sm[kRow];
-  double acc[kRow];
-#pragma unroll
-  for (int k = 0; k < kRow; ++k) acc[k] = 0.0;
-  for (int r = threadIdx.x; r < rows; r += kBlock) {
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) acc[k] += part[(size_t)r * kRow + k];
-    acc[kSums] = fmax(acc[kSums], part[(size_t)r * kRow + kSums]);
-  }
-  block_row(acc, sm);
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < kRow; ++k) tot[k] = sm[k];
+  dpf_block_reduce_d<kSums, 1>(acc, part + ((size_t)b * gridDim.x + blockIdx.x) * kRow);
 }
 
 // grid (B).  first: the fold of pass 0 (writes the whole state record); it: the number of this reweighted solve otherwise
@@ -134,8 +92,8 @@ __global__ __launch_bounds__(256) void fit_fold_kernel(const double* __restrict_
                                                        double* __restrict__ state) {
   double* st = state + (size_t)blockIdx.x * kState;
   if (!first && st[S_DONE] != 0.0) return;
-  double tot[kRow];
-  fold_rows(part + (size_t)blockIdx.x * rows * kRow, rows, tot);
+  __shared__ double tot[kRow];
+  dpf_fold_rows_d<kSums, 1>(part + (size_t)blockIdx.x * rows * kRow, rows, kRow, tot);
   if (threadIdx.x != 0) return;
   const double sw = tot[0], sx = tot[1], sy = tot[2], sxx = tot[3], sxy = tot[4];
   const double det = sw * sxx - sx * sx;
@@ -167,8 +125,8 @@ __global__ __launch_bounds__(256) void fit_fold_kernel(const double* __restrict_
 __global__ __launch_bounds__(256) void fit_finish_kernel(const double* __restrict__ part, int rows, double f, const double* __restrict__ state,
                                                          float* __restrict__ ab, double* __restrict__ info) {
   const double* st = state + (size_t)blockIdx.x * kState;
-  double tot[kRow];
-  fold_rows(part + (size_t)blockIdx.x * rows * kRow, rows, tot);
+  __shared__ double tot[kRow];
+  dpf_fold_rows_d<kSums, 1>(part + (size_t)blockIdx.x * rows * kRow, rows, kRow, tot);
   if (threadIdx.x != 0) return;
   const double obj = (f * f) * tot[5];
   ab[2 * blockIdx.x] = (float)st[S_B];
@@ -182,14 +140,7 @@ __global__ __launch_bounds__(256) void fit_finish_kernel(const double* __restric
   o[5] = st[S_OBJ0] < 0.0 ? obj : st[S_OBJ0];          // no reweighted solve ran: the result is the start
 }
 
-int blocks_per_sample(long long HW) {
-  long long g = (HW + (long long)kBlock * 4 * kItems - 1) / ((long long)kBlock * 4 * kItems);
-  if (g > kMaxBlocks) g = kMaxBlocks;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+int blocks_per_sample(long long HW) { return dpf_red_rows(HW, (long long)kBlock * 4 * kItems, kMaxBlocks); }
 
 template <int MODE>
 void launch_pass(bool v4, dim3 grid, hipStream_t st, const float* y, long long ystride, const float* x, long long HW, double f,
@@ -215,13 +166,13 @@ int dpf_affine_fit(const float* pred, long long pred_batch_stride, const float* 
   const long long HW = (long long)H * W;
   if (pred_batch_stride < HW) return DPF_ERR_INVALID_ARG;
   if (B > kMaxB) return DPF_ERR_UNSUPPORTED;
-  if (ws_bytes < dpf_affine_fit_workspace_bytes(B, H, W) || ((uintptr_t)ws & 7u)) return DPF_ERR_INVALID_ARG;
+  if (!dpf_ws_ok(ws, ws_bytes, dpf_affine_fit_workspace_bytes(B, H, W), kWsAlign)) return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   const int gx = blocks_per_sample(HW);
   const dim3 grid(gx, B);
   double* state = (double*)ws;
   double* part = state + (size_t)B * kState;
-  const bool v4 = HW % 4 == 0 && pred_batch_stride % 4 == 0 && aligned16(pred) && aligned16(idepth);
+  const bool v4 = HW % 4 == 0 && pred_batch_stride % 4 == 0 && dpf_aligned16(pred) && dpf_aligned16(idepth);
   launch_pass<PASS_FIRST>(v4, grid, st, pred, pred_batch_stride, idepth, HW, f_scale, state, part);
   hipLaunchKernelGGL(fit_fold_kernel, dim3(B), dim3(kBlock), 0, st, part, gx, 1, 0, f_scale, tol, state);
   for (int it = 1; it <= max_iters; ++it) {

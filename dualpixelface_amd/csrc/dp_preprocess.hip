@@ -9,6 +9,7 @@
 //                   through LDS with aligned dword loads because the window's byte offset (3 * x0) is arbitrary
 //   dp_hwc_to_chw   f32 HWC window -> CHW (normal / albedo maps)
 #include "dpf_common.h"
+#include "dpf_reduce.h"
 #include <math.h>
 
 namespace {
@@ -32,11 +33,6 @@ __device__ __forceinline__ double dp_wave_max(double v) {
   for (int o = 32; o > 0; o >>= 1) v = dp_max(v, __shfl_xor(v, o, 64));
   return v;
 }
-__device__ __forceinline__ double dp_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void dp_stats_partial_kernel(const T* __restrict__ depth, const unsigned char* __restrict__ mask,
@@ -52,7 +48,7 @@ __global__ __launch_bounds__(256) void dp_stats_partial_kernel(const T* __restri
   __shared__ double sm[3][4];
   md = dp_wave_max(md);
   mq = dp_wave_max(mq);
-  cnt = dp_wave_sum(cnt);
+  cnt = dpf_wave_sum_d(cnt);
   if ((threadIdx.x & 63) == 0) {
     sm[0][threadIdx.x >> 6] = md;
     sm[1][threadIdx.x >> 6] = mq;
@@ -77,7 +73,7 @@ __global__ __launch_bounds__(64) void dp_stats_final_kernel(double* __restrict__
   }
   md = dp_wave_max(md);
   mq = dp_wave_max(mq);
-  cnt = dp_wave_sum(cnt);
+  cnt = dpf_wave_sum_d(cnt);
   if (threadIdx.x == 0) {
     stats[0] = md;
     stats[1] = mq;
@@ -238,7 +234,6 @@ __global__ __launch_bounds__(256) void dp_hwc_to_chw_kernel(const float* __restr
 bool window_ok(int H, int W, int y0, int x0, int ch, int cw) {
   return H > 0 && W > 0 && ch > 0 && cw > 0 && y0 >= 0 && x0 >= 0 && (long long)y0 + ch <= H && (long long)x0 + cw <= W;
 }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -266,8 +261,8 @@ int dpf_dp_targets(const void* depth, int depth_f64, const unsigned char* mask, 
   if (!depth || !stats || !window_ok(H, W, y0, x0, ch, cw)) return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   dpf_clear_error();
-  const int vec = (cw % 4 == 0) && (!depth_out || aligned16(depth_out)) && (!mask_out || aligned16(mask_out)) &&
-                  (!disp_out || aligned16(disp_out));
+  const int vec = (cw % 4 == 0) && (!depth_out || dpf_aligned16(depth_out)) && (!mask_out || dpf_aligned16(mask_out)) &&
+                  (!disp_out || dpf_aligned16(disp_out));
   const long long total = (long long)ch * ((cw + 3) / 4);
   const int grid = dpf_ew_grid(total);
   if (depth_f64)
@@ -291,7 +286,7 @@ int dpf_dp_image(const unsigned char* img, const unsigned char* lut, float* out,
     par.mean[c] = c < C ? mean_host[c] : 0.f;
     par.scale[c] = c < C ? std_host[c] : 1.f;
   }
-  const int vec = (cw % 4 == 0) && aligned16(out);
+  const int vec = (cw % 4 == 0) && dpf_aligned16(out);
   dim3 grid(dpf_div_up(cw, 1024), ch);
   const long long total_bytes = (long long)H * W * C;
   if (C == 3)
@@ -305,7 +300,7 @@ int dpf_dp_hwc_to_chw(const float* src, float* dst, int H, int W, int C, int y0,
   if (!src || !dst || !window_ok(H, W, y0, x0, ch, cw) || (C != 1 && C != 3)) return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   dpf_clear_error();
-  const int vec = (cw % 4 == 0) && aligned16(dst);
+  const int vec = (cw % 4 == 0) && dpf_aligned16(dst);
   const long long total = (long long)ch * ((cw + 3) / 4);
   const int grid = dpf_ew_grid(total);
   if (C == 3)

@@ -27,6 +27,9 @@ int dpf_deterministic();
 
 static inline int dpf_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// a 16-byte access through p is allowed (nullptr counts as aligned: an absent operand does not decide)
+static inline bool dpf_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
 // grid size for a grid-stride elementwise kernel (guide: cap at ~8 blocks/CU x 256 CUs)
 static inline int dpf_ew_grid(long long n, int block = 256) {
   long long g = (n + block - 1) / block;

@@ -22,30 +22,16 @@
 //   [4]       gmul: what the optimiser multiplies every gradient element by                                                    finish
 //   [5]       grad_norm: the global 2-norm of the scaled gradient before clipping                                              finish
 #include "dpf_common.h"
+#include "dpf_reduce.h"
 #include <math.h>
 
 namespace {
 
 constexpr int kBlock = 256;              // threads per block of every kernel here (4 waves)
-constexpr int kWaves = 4;
 constexpr int kItems = 4;                // quads per thread before the grid stops growing
 constexpr int kMaxBlocks = 1024;         // = rows of partial sums
+constexpr int kWsAlign = 8;              // the workspace holds doubles
 enum { C_FIRST = 2, C_APPLY = 3, C_GMUL = 4, C_NORM = 5 };
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// block-wide sum (blockDim.x == 256), valid in thread 0
-__device__ __forceinline__ double block_sum_d(double v) {
-  __shared__ double sm[kWaves];
-  v = wave_sum_d(v);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sm[0] + sm[1]) + sm[2]) + sm[3];
-}
 
 __device__ __forceinline__ double square(float x) { return (double)x * (double)x; }
 
@@ -60,7 +46,7 @@ __global__ __launch_bounds__(256) void grad_pass_kernel(float* __restrict__ acc,
     sums = PART && ctl[C_APPLY] != 0.f;                  // (uniform over the grid)
   }
   const long long nquads = (n + 3) / 4;
-  double s = 0.0;
+  double s[1] = {0.0};
   for (long long q = (long long)blockIdx.x * kBlock + threadIdx.x; q < nquads; q += (long long)gridDim.x * kBlock) {
     const long long i = 4 * q;
     if (V == 4 && i + 4 <= n) {
@@ -73,7 +59,7 @@ __global__ __launch_bounds__(256) void grad_pass_kernel(float* __restrict__ acc,
       }
       if (sums) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) s += square(a[k]);
+        for (int k = 0; k < 4; ++k) s[0] += square(a[k]);
       }
     } else {
       const int m = n - i < 4 ? (int)(n - i) : 4;
@@ -83,26 +69,24 @@ __global__ __launch_bounds__(256) void grad_pass_kernel(float* __restrict__ acc,
           a = first ? g[i + k] : a + g[i + k];
           acc[i + k] = a;
         }
-        if (sums) s += square(a);
+        if (sums) s[0] += square(a);
       }
     }
   }
   if (PART) {
     if (!sums) return;
-    s = block_sum_d(s);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
+    dpf_block_reduce_d<1>(s, part + blockIdx.x);
   }
 }
 
-// one workgroup: thread t adds the rows t, t + 256, ... in that order, then the block sum
+// one workgroup folds the rows (dpf_reduce.h)
 __global__ __launch_bounds__(256) void grad_finish_kernel(const double* __restrict__ part, int rows, double gscale, double clip,
                                                           float* __restrict__ ctl) {
   if (ctl[C_APPLY] == 0.f) return;
-  double s = 0.0;
-  for (int r = threadIdx.x; r < rows; r += kBlock) s += part[r];
-  s = block_sum_d(s);
+  __shared__ double tot[1];
+  dpf_fold_rows_d<1>(part, rows, 1, tot);
   if (threadIdx.x != 0) return;
-  const double total = gscale * sqrt(s);
+  const double total = gscale * sqrt(tot[0]);
   double coef = 1.0;
   if (clip > 0.0) {
     const double r = clip / (total + 1e-6);
@@ -112,17 +96,10 @@ __global__ __launch_bounds__(256) void grad_finish_kernel(const double* __restri
   ctl[C_NORM] = (float)total;
 }
 
-int rows_of(long long n) {
-  long long g = (n + (long long)kBlock * 4 * kItems - 1) / ((long long)kBlock * 4 * kItems);
-  if (g > kMaxBlocks) g = kMaxBlocks;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+int rows_of(long long n) { return dpf_red_rows(n, (long long)kBlock * 4 * kItems, kMaxBlocks); }
 
 bool ws_ok(const void* ws, long long ws_bytes, long long n) {
-  return ws && !((uintptr_t)ws & 7u) && ws_bytes >= (long long)rows_of(n) * (long long)sizeof(double);
+  return dpf_ws_ok(ws, ws_bytes, (long long)rows_of(n) * (long long)sizeof(double), kWsAlign);
 }
 
 template <bool FOLD, bool PART>
@@ -144,7 +121,7 @@ long long dpf_grad_ctl_workspace_bytes(long long n) {
 int dpf_grad_fold(float* acc, const float* grad, long long n, const float* ctl, void* ws, long long ws_bytes, void* stream) {
   dpf_clear_error();
   if (!acc || !grad || !ctl || n <= 0 || (ws && !ws_ok(ws, ws_bytes, n))) return DPF_ERR_INVALID_ARG;
-  const bool v4 = aligned16(acc) && aligned16(grad);
+  const bool v4 = dpf_aligned16(acc) && dpf_aligned16(grad);
   if (ws) launch_pass<true, true>(v4, acc, grad, n, ctl, (double*)ws, (hipStream_t)stream);
   else launch_pass<true, false>(v4, acc, grad, n, ctl, nullptr, (hipStream_t)stream);
   return dpf_check_launch();
@@ -154,7 +131,7 @@ int dpf_grad_sumsq(const float* grad, long long n, void* ws, long long ws_bytes,
   dpf_clear_error();
   if (!grad || n <= 0 || !ws_ok(ws, ws_bytes, n)) return DPF_ERR_INVALID_ARG;
   // (the arena is only read: the FOLD = false instantiation never stores through acc)
-  launch_pass<false, true>(aligned16(grad), const_cast<float*>(grad), nullptr, n, nullptr, (double*)ws, (hipStream_t)stream);
+  launch_pass<false, true>(dpf_aligned16(grad), const_cast<float*>(grad), nullptr, n, nullptr, (double*)ws, (hipStream_t)stream);
   return dpf_check_launch();
 }
 

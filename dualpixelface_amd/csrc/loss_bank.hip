@@ -16,6 +16,7 @@
 // it holds stays out of the sums.  No clamp, as in the reference: a counted non-positive log argument or M = 0 gives NaN.
 // Sums are fp64 in two phases (no floating-point atomics): the bits repeat run to run and in every mode.  Nothing here waits on the host.
 #include "dpf_common.h"
+#include "dpf_reduce.h"
 #include <math.h>
 
 extern "C" long long dpf_depth_loss_workspace_bytes(int B, int H, int W);
@@ -23,11 +24,11 @@ extern "C" long long dpf_depth_loss_workspace_bytes(int B, int H, int W);
 namespace {
 
 constexpr int kBlock = 256;              // threads per block of every kernel here (4 waves)
-constexpr int kWaves = 4;
 constexpr int kMaxHeads = 8;
 constexpr int kItems = 4;                // loads of kVec pixels per thread before the grid stops growing
 constexpr int kMaxBlocks = 1024;         // blocks per sample: the fold reads B * kMaxBlocks rows at the most with one block
 constexpr int kMaxB = 65535;             // samples ride on gridDim.y
+constexpr int kWsAlign = 8;              // the workspace holds doubles
 constexpr int kValues = 2 * kMaxHeads + 1;      // partial row: sum_k [0, 8), sum of squares_k [8, 16), count
 constexpr int kStats = 2 * kMaxHeads + 1;       // stats record: M, m1_k [1, 9), sqrt(v_k) [9, 17)  (doubles)
 
@@ -40,28 +41,6 @@ struct BankP {
   float w[kMaxHeads];
   float vf;
 };
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// block-wide sums of NV per-thread values (blockDim.x == 256), thread k < NV writes value k to out[k]
-template <int NV>
-__device__ __forceinline__ void block_sums(const double (&acc)[NV], double* __restrict__ out) {
-  __shared__ double sm[NV][kWaves];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const double v = wave_sum_d(acc[k]);
-    if (lane == 0) sm[k][w] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) out[threadIdx.x] = ((sm[threadIdx.x][0] + sm[threadIdx.x][1]) + sm[threadIdx.x][2]) + sm[threadIdx.x][3];
-}
-
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 template <int V> struct Vec { float v[V]; };
 
@@ -92,7 +71,7 @@ __device__ __forceinline__ void store_vec(float* __restrict__ p, const Vec<V>& r
 __device__ __forceinline__ float target_of(float g, bool from_depth, float a, float b) {
   if (!from_depth) return g;
   const float t = a / g + b;
-  return finite_f(t) ? t : -100.f;
+  return dpf_finite_f(t) ? t : -100.f;
 }
 
 // T(p); kept = false where the reciprocal was replaced by 0
@@ -100,7 +79,7 @@ __device__ __forceinline__ float transform(float p, int recip, bool& kept) {
   kept = true;
   if (!recip) return p;
   const float r = 1.0f / p;
-  kept = finite_f(r);
+  kept = dpf_finite_f(r);
   return kept ? r : 0.f;
 }
 
@@ -153,7 +132,7 @@ __global__ __launch_bounds__(256) void bank_partial_kernel(const float* __restri
       }
     }
   }
-  block_sums<kValues>(acc, part + ((size_t)b * gridDim.x + blockIdx.x) * kValues);
+  dpf_block_reduce_d<kValues>(acc, part + ((size_t)b * gridDim.x + blockIdx.x) * kValues);
 }
 
 // one block: folds the partial rows in a fixed order, writes the loss and the stats record
@@ -161,14 +140,7 @@ template <int KIND>
 __global__ __launch_bounds__(256) void bank_fold_kernel(const double* __restrict__ part, long long rows, BankP P, double* __restrict__ stats,
                                                         float* __restrict__ out) {
   __shared__ double tot[kValues];
-  double acc[kValues];
-#pragma unroll
-  for (int k = 0; k < kValues; ++k) acc[k] = 0.0;
-  for (long long r = threadIdx.x; r < rows; r += kBlock)
-#pragma unroll
-    for (int k = 0; k < kValues; ++k) acc[k] += part[r * kValues + k];
-  block_sums<kValues>(acc, tot);
-  __syncthreads();
+  dpf_fold_rows_d<kValues>(part, rows, kValues, tot);
   if (threadIdx.x == 0) {
     const double M = tot[2 * kMaxHeads];                // 0 counted pixels: 0 / 0 = NaN, like the empty mean()
     double loss = 0.0;
@@ -256,14 +228,7 @@ __global__ __launch_bounds__(256) void bank_backward_kernel(const float* __restr
   }
 }
 
-int blocks_per_sample(long long HW) {
-  long long g = (HW + (long long)kBlock * 4 * kItems - 1) / ((long long)kBlock * 4 * kItems);
-  if (g > kMaxBlocks) g = kMaxBlocks;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+int blocks_per_sample(long long HW) { return dpf_red_rows(HW, (long long)kBlock * 4 * kItems, kMaxBlocks); }
 
 // argument checks shared by the two entry points; fills P
 int prepare(int kind, int transform, const float* pred, const float* target, int B, int n, int H, int W, const float* weights, float vf,
@@ -286,12 +251,12 @@ int forward(int kind, int transform, const float* pred, const float* target, con
   BankP P;
   const int rc = prepare(kind, transform, pred, target, B, n, H, W, weights, vf, P);
   if (rc != DPF_OK) return rc;
-  if (!ws || !stats || !out || ws_bytes < dpf_depth_loss_workspace_bytes(B, H, W) || ((uintptr_t)ws & 7u)) return DPF_ERR_INVALID_ARG;
+  if (!stats || !out || !dpf_ws_ok(ws, ws_bytes, dpf_depth_loss_workspace_bytes(B, H, W), kWsAlign)) return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   const int gx = blocks_per_sample(P.HW);
   const dim3 grid(gx, B), block(kBlock);
   double* part = (double*)ws;
-  const bool v4 = P.HW % 4 == 0 && aligned16(pred) && aligned16(target) && aligned16(mask) && aligned16(conf);
+  const bool v4 = P.HW % 4 == 0 && dpf_aligned16(pred) && dpf_aligned16(target) && dpf_aligned16(mask) && dpf_aligned16(conf);
   if (kind == KIND_SILOG) {
     if (v4) hipLaunchKernelGGL((bank_partial_kernel<KIND_SILOG, 4>), grid, block, 0, st, pred, target, mask, conf, ab, P, part);
     else hipLaunchKernelGGL((bank_partial_kernel<KIND_SILOG, 1>), grid, block, 0, st, pred, target, mask, conf, ab, P, part);
@@ -313,7 +278,7 @@ int backward(int kind, int transform, const float* pred, const float* target, co
   if (!stats || !gout || !dpred) return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(blocks_per_sample(P.HW), B), block(kBlock);
-  const bool v4 = P.HW % 4 == 0 && aligned16(pred) && aligned16(target) && aligned16(mask) && aligned16(conf) && aligned16(dpred);
+  const bool v4 = P.HW % 4 == 0 && dpf_aligned16(pred) && dpf_aligned16(target) && dpf_aligned16(mask) && dpf_aligned16(conf) && dpf_aligned16(dpred);
   if (kind == KIND_SILOG) {
     if (v4) hipLaunchKernelGGL((bank_backward_kernel<KIND_SILOG, 4>), grid, block, 0, st, pred, target, mask, conf, ab, P, stats, gout, dpred);
     else hipLaunchKernelGGL((bank_backward_kernel<KIND_SILOG, 1>), grid, block, 0, st, pred, target, mask, conf, ab, P, stats, gout, dpred);

@@ -9,6 +9,7 @@
 // correctly rounded fp32 values); every sum is fp64.  Reductions are two-phase: each block leaves its partial sums in the workspace, one block
 // per result folds them in a fixed order -- no floating-point atomics, so the bits repeat run to run.  Nothing here waits on the host.
 #include "dpf_common.h"
+#include "dpf_reduce.h"
 #include "metrics_plan.h"
 #include <float.h>
 #include <math.h>
@@ -19,41 +20,6 @@ using namespace dpf_metrics;
 
 enum { DPF_METRIC_DISP = 0, DPF_METRIC_IDEPTH = 1, DPF_METRIC_DEPTH = 2 };      // target_type, as include/dpf_hip.h
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// block-wide sums of NV per-thread values (blockDim.x == 256), thread k < NV writes value k to out[k]
-template <int NV>
-__device__ __forceinline__ void block_sums(const double (&acc)[NV], double* __restrict__ out) {
-  __shared__ double sm[NV][kWaves];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();                                      // a second call may not overwrite sm under a reader of the first
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const double v = wave_sum_d(acc[k]);
-    if (lane == 0) sm[k][w] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) out[threadIdx.x] = ((sm[threadIdx.x][0] + sm[threadIdx.x][1]) + sm[threadIdx.x][2]) + sm[threadIdx.x][3];
-}
-
-// one block: the sums over `rows` partial rows of NV doubles, in a fixed order; tot[] (shared) is valid in every thread afterwards
-template <int NV>
-__device__ __forceinline__ void fold_rows(const double* __restrict__ part, long long rows, double* tot) {
-  double acc[NV];
-#pragma unroll
-  for (int k = 0; k < NV; ++k) acc[k] = 0.0;
-  for (long long r = threadIdx.x; r < rows; r += kBlock)
-#pragma unroll
-    for (int k = 0; k < NV; ++k) acc[k] += part[r * NV + k];
-  block_sums<NV>(acc, tot);
-  __syncthreads();
-}
-
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 // torch.maximum / torch.clamp propagate NaN
 __device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? NAN : (a > b ? a : b); }
 __device__ __forceinline__ double max_nan_d(double a, double b) { return (a != a || b != b) ? (double)NAN : (a > b ? a : b); }
@@ -75,7 +41,7 @@ __global__ __launch_bounds__(256) void abs_partial_kernel(const float* __restric
     float p = pred[base + i];
     if (convert) {
       const float depth = fa / (p - fb);
-      p = finite_f(depth) ? depth : 0.f;
+      p = dpf_finite_f(depth) ? depth : 0.f;
     }
     const float thresh = max_nan(g / p, p / g);
     const float d = g - p;
@@ -90,12 +56,12 @@ __global__ __launch_bounds__(256) void abs_partial_kernel(const float* __restric
     acc[7] += thresh < t3 ? 1.0 : 0.0;
     acc[8] += 1.0;
   }
-  block_sums<kAbsValues>(acc, part + ((size_t)b * gridDim.x + blockIdx.x) * kAbsValues);
+  dpf_block_reduce_d<kAbsValues>(acc, part + ((size_t)b * gridDim.x + blockIdx.x) * kAbsValues);
 }
 
 __global__ __launch_bounds__(256) void abs_fold_kernel(const double* __restrict__ part, long long rows, float* __restrict__ out) {
   __shared__ double tot[kAbsValues];
-  fold_rows<kAbsValues>(part, rows, tot);
+  dpf_fold_rows_d<kAbsValues>(part, rows, kAbsValues, tot);
   if (threadIdx.x == 0) {
     const double c = tot[8];                            // 0 selected pixels: 0 / 0 = NaN in every field, like the empty mean()
     out[0] = (float)(tot[0] / c);
@@ -131,12 +97,12 @@ __global__ __launch_bounds__(256) void normal_partial_kernel(const float* __rest
     acc[0] += (double)(((ang * 180.0f) / 3.14159265358979323846f) * m);
     acc[1] += (double)(am * am);
   }
-  block_sums<kNormalValues>(acc, part + ((size_t)b * gridDim.x + blockIdx.x) * kNormalValues);
+  dpf_block_reduce_d<kNormalValues>(acc, part + ((size_t)b * gridDim.x + blockIdx.x) * kNormalValues);
 }
 
 __global__ __launch_bounds__(256) void normal_fold_kernel(const double* __restrict__ part, long long rows, float* __restrict__ out) {
   __shared__ double tot[kNormalValues];
-  fold_rows<kNormalValues>(part, rows, tot);
+  dpf_fold_rows_d<kNormalValues>(part, rows, kNormalValues, tot);
   if (threadIdx.x == 0) {
     out[0] = (float)(tot[0] / tot[2]);
     out[1] = (float)(sqrt(tot[1] / tot[2]) * 180.0 / 3.14159265358979323846);
@@ -270,7 +236,7 @@ __global__ __launch_bounds__(256) void affine_pass_kernel(const float* __restric
     acc[6] += (double)(cc * r);
     acc[7] += (double)(cc * q);
   }
-  block_sums<8>(acc, part + ((size_t)b * gridDim.x + blockIdx.x) * kAffineValues);
+  dpf_block_reduce_d<8>(acc, part + ((size_t)b * gridDim.x + blockIdx.x) * kAffineValues);
 }
 
 // sample blockIdx.x: fold the pass, solve the 2x2 normal equations (the determinant rule of _weighted_affine_fit), leave (s, t) for the
@@ -279,14 +245,7 @@ __global__ __launch_bounds__(256) void affine_fold_kernel(const double* __restri
                                                           double* __restrict__ res, int take_rmse, int take_mae) {
   __shared__ double tot[8];
   const int b = blockIdx.x;
-  double acc[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) acc[k] = 0.0;
-  for (int r = threadIdx.x; r < rows; r += kBlock)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) acc[k] += part[((size_t)b * rows + r) * kAffineValues + k];
-  block_sums<8>(acc, tot);
-  __syncthreads();
+  dpf_fold_rows_d<8>(part + (size_t)b * rows * kAffineValues, rows, kAffineValues, tot);      // 8 of the 9-wide row
   if (threadIdx.x == 0) {
     const double sw = tot[0], sx = tot[1], sy = tot[2], sxx = tot[3], sxy = tot[4];
     const double det = sw * sxx - sx * sx;
@@ -330,7 +289,7 @@ __global__ __launch_bounds__(256) void rank_moment_kernel(const float* __restric
     acc[7] += w * (x * y);
     acc[8] += w * (xn * y);
   }
-  block_sums<kAffineValues>(acc, part + ((size_t)b * gridDim.x + blockIdx.x) * kAffineValues);
+  dpf_block_reduce_d<kAffineValues>(acc, part + ((size_t)b * gridDim.x + blockIdx.x) * kAffineValues);
 }
 
 __device__ __forceinline__ double pearson(double ws, double sx, double sy, double sxx, double syy, double sxy) {
@@ -341,7 +300,7 @@ __device__ __forceinline__ double pearson(double ws, double sx, double sy, doubl
 __global__ __launch_bounds__(256) void rank_fold_kernel(const double* __restrict__ part, int rows, double* __restrict__ res) {
   __shared__ double tot[kAffineValues];
   const int b = blockIdx.x;
-  fold_rows<kAffineValues>(part + (size_t)b * rows * kAffineValues, rows, tot);
+  dpf_fold_rows_d<kAffineValues>(part + (size_t)b * rows * kAffineValues, rows, kAffineValues, tot);
   if (threadIdx.x == 0)
     res[3 * b + 2] = 1.0 - max_nan_d(pearson(tot[0], tot[1], tot[3], tot[4], tot[6], tot[7]),
                                      pearson(tot[0], tot[2], tot[3], tot[5], tot[6], tot[8]));
@@ -356,7 +315,7 @@ __global__ void affine_mean_kernel(const double* __restrict__ res, int B, float*
   }
 }
 
-bool ws_ok(const void* ws, long long have, long long need) { return ws && need > 0 && have >= need && ((uintptr_t)ws & 15) == 0; }
+constexpr int kWsAlign = 16;             // workspace alignment: the plans hand out 16-byte aligned sections
 
 }  // namespace
 
@@ -374,7 +333,7 @@ int dpf_metric_absolute_dp(const float* pred, const float* abvalue, const float*
   const int convert = target_type != DPF_METRIC_DEPTH;
   if (convert && !abvalue) return DPF_ERR_INVALID_ARG;
   if (!shape_ok(B, n)) return DPF_ERR_UNSUPPORTED;
-  if (!ws_ok(ws, ws_bytes, reduce_bytes(B, n, kAbsValues))) return DPF_ERR_INVALID_ARG;
+  if (!dpf_ws_ok(ws, ws_bytes, reduce_bytes(B, n, kAbsValues), kWsAlign)) return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   const int gx = red_blocks(n);
   double* part = (double*)ws;
@@ -390,7 +349,7 @@ int dpf_metric_normal_dp(const float* pred, const float* target, const float* ma
   dpf_clear_error();
   if (!pred || !target || !out2 || B <= 0 || n <= 0) return DPF_ERR_INVALID_ARG;
   if (!shape_ok(B, n)) return DPF_ERR_UNSUPPORTED;
-  if (!ws_ok(ws, ws_bytes, reduce_bytes(B, n, kNormalValues))) return DPF_ERR_INVALID_ARG;
+  if (!dpf_ws_ok(ws, ws_bytes, reduce_bytes(B, n, kNormalValues), kWsAlign)) return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   const int gx = red_blocks(n);
   double* part = (double*)ws;
@@ -404,7 +363,7 @@ int dpf_metric_ranks(const float* values, int* ranks, int B, long long n, int ne
   if (!values || !ranks || B <= 0 || n <= 0) return DPF_ERR_INVALID_ARG;
   if (!shape_ok(B, n)) return DPF_ERR_UNSUPPORTED;
   const RanksPlan pl = ranks_plan(B, n);
-  if (!ws_ok(ws, ws_bytes, pl.bytes)) return DPF_ERR_INVALID_ARG;
+  if (!dpf_ws_ok(ws, ws_bytes, pl.bytes, kWsAlign)) return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   char* w = (char*)ws;
   unsigned* keys[2] = {(unsigned*)(w + pl.keys[0]), (unsigned*)(w + pl.keys[1])};
@@ -440,7 +399,7 @@ int dpf_metric_affine_dp(const float* pred, const float* target, const float* we
     return DPF_ERR_INVALID_ARG;
   if (!shape_ok(B, n)) return DPF_ERR_UNSUPPORTED;
   const AffinePlan pl = affine_plan(B, n);
-  if (!ws_ok(ws, ws_bytes, pl.bytes)) return DPF_ERR_INVALID_ARG;
+  if (!dpf_ws_ok(ws, ws_bytes, pl.bytes, kWsAlign)) return DPF_ERR_INVALID_ARG;
   hipStream_t stm = (hipStream_t)stream;
   char* w = (char*)ws;
   double* part = (double*)(w + pl.part);

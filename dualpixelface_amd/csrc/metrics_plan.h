@@ -3,6 +3,7 @@
 // histogram -> scan -> scatter on the CPU with exactly these functions.
 #pragma once
 #include <stdint.h>
+#include "dpf_reduce.h"
 
 #ifdef __HIPCC__
 #define DPF_HD __host__ __device__
@@ -25,12 +26,7 @@ constexpr int kMaxB = 65535;             // samples ride on gridDim.y
 inline long long align16(long long v) { return (v + 15) & ~15LL; }
 
 // blocks per sample of a reduction pass
-inline int red_blocks(long long n) {
-  long long g = (n + (long long)kBlock * kRedItems - 1) / ((long long)kBlock * kRedItems);
-  if (g > kMaxRedBlocks) g = kMaxRedBlocks;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+inline int red_blocks(long long n) { return dpf_red_rows(n, (long long)kBlock * kRedItems, kMaxRedBlocks); }
 
 inline bool shape_ok(long long B, long long n) { return B > 0 && B <= kMaxB && n > 0 && n <= kMaxN; }
 

@@ -274,8 +274,6 @@ __global__ __launch_bounds__(256) void bilateral_kernel(const float* __restrict_
   }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 bool shape_ok(int B, int n, int H, int W) { return B > 0 && n > 0 && H > 0 && W > 0; }
 
 // rows per band: 32, halved while the grid is small and the band still is as tall as the halo above it
@@ -323,7 +321,7 @@ int dpf_guided_filter(const float* p, long long p_batch_stride, const float* gui
   hipLaunchKernelGGL(luma_kernel, dim3(dpf_ew_grid(HW), B), dim3(kBlock), 0, st, guide_rgb, HW, nm, I);
   const int bh = band_rows(B, n, H, W, r);
   const dim3 grid(dpf_div_up(W, kBlock - 2 * r), dpf_div_up(H, bh), B * n);
-  const int vec = W % 4 == 0 && r % 2 == 0 && aligned16(ws) && aligned16(q);      // (the planes of ws are H W floats apart: aligned with it)
+  const int vec = W % 4 == 0 && r % 2 == 0 && dpf_aligned16(ws) && dpf_aligned16(q);      // (the planes of ws are H W floats apart: aligned with it)
   hipLaunchKernelGGL((guided_kernel<1>), grid, dim3(kBlock), 0, st, (const float*)I, p, p_batch_stride, (const float*)I, p, p_batch_stride, n,
                      H, W, r, bh, (float)eps, vec, a, bq);
   hipLaunchKernelGGL((guided_kernel<2>), grid, dim3(kBlock), 0, st, (const float*)a, (const float*)bq, 0LL, (const float*)I, p,

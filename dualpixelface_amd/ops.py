@@ -98,6 +98,17 @@ def scratch(nfloats, device, tag='ws'):
     return buf
 
 
+def _workspace(query, what, *shape, device, tag=None):
+    """(tensor, nbytes) for what the C side's `query`(*shape) asks: the scratch() slab of `tag`, or without a tag a fresh float64 tensor
+    (what a captured call needs to keep its buffer alive).  A negative answer raises DpfError(what % shape)."""
+    nbytes = lib().call(query, *shape)
+    if nbytes < 0:
+        raise DpfError(what % shape)
+    if tag is None:
+        return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device), nbytes
+    return scratch((nbytes + 3) // 4, device, tag), nbytes
+
+
 _zero_arena = {}
 
 
@@ -1679,10 +1690,8 @@ class DepthLossFn(torch.autograd.Function):
                 raise DpfError('depth_loss: %s %s does not match pred %s' % (name, tuple(t.shape), tuple(pred.shape)))
         if len(head_weights) != n:
             raise DpfError('depth_loss: %d head weights for %d heads' % (len(head_weights), n))
-        nbytes = lib().call('dpf_depth_loss_workspace_bytes', B, H, W)
-        if nbytes < 0:
-            raise DpfError('depth_loss: shape B=%d H=%d W=%d is not supported' % (B, H, W))
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=pred.device)
+        ws, nbytes = _workspace('dpf_depth_loss_workspace_bytes', 'depth_loss: shape B=%d H=%d W=%d is not supported', B, H, W,
+                                device=pred.device)
         stats = torch.empty(LOSS_STATS, dtype=torch.float64, device=pred.device)
         out = torch.empty((), dtype=torch.float32, device=pred.device)
         cfg = (LOSS_KIND[kind], LOSS_TRANSFORM[transform], B, n, H, W, tuple(float(w) for w in head_weights), float(variance_focus))
@@ -1734,10 +1743,8 @@ def affine_fit(pred, idepth, f_scale=AFFINE_FIT_F_SCALE, max_iters=AFFINE_FIT_MA
     if pred.dim() != 4 or tuple(idepth.shape) != (pred.shape[0],) + tuple(pred.shape[2:]) or idepth.dtype != torch.float32:
         raise DpfError('affine_fit: idepth %s does not match pred %s' % (tuple(idepth.shape), tuple(pred.shape)))
     B, n, H, W = pred.shape
-    nbytes = lib().call('dpf_affine_fit_workspace_bytes', B, H, W)
-    if nbytes < 0:
-        raise DpfError('affine_fit: shape B=%d H=%d W=%d is not supported' % (B, H, W))
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=pred.device)
+    ws, nbytes = _workspace('dpf_affine_fit_workspace_bytes', 'affine_fit: shape B=%d H=%d W=%d is not supported', B, H, W,
+                            device=pred.device)
     ab = torch.empty((B, 2), dtype=torch.float32, device=pred.device)
     info = torch.empty((B, AFFINE_FIT_INFO), dtype=torch.float64, device=pred.device)
     lib().call('dpf_affine_fit', _ptr(pred), n * H * W, _ptr(idepth), B, H, W, float(f_scale), int(max_iters), float(tol), _ptr(ws), nbytes,
@@ -1782,10 +1789,9 @@ def guided_filter(pred, guide_rgb, radius, eps):
     with torch.no_grad():
         pred, guide_rgb, stride, norm, out = _filter_operands('guided_filter', pred, guide_rgb)
         B, n, H, W = pred.shape
-        nbytes = lib().call('dpf_guided_filter_workspace_bytes', B, n, H, W, radius)
-        if nbytes < 0:
-            raise DpfError('guided_filter: B=%d n=%d H=%d W=%d radius=%d is not supported (1 <= radius <= 32)' % (B, n, H, W, radius))
-        ws = scratch((nbytes + 3) // 4, pred.device, tag='postprocess')
+        ws, nbytes = _workspace('dpf_guided_filter_workspace_bytes',
+                                'guided_filter: B=%d n=%d H=%d W=%d radius=%d is not supported (1 <= radius <= 32)', B, n, H, W, radius,
+                                device=pred.device, tag='postprocess')
         lib().call('dpf_guided_filter', _ptr(pred), stride, _ptr(guide_rgb), B, n, H, W, radius, float(eps), norm, _ptr(ws), nbytes,
                    _ptr(out), _stream())
     return out
@@ -1866,10 +1872,7 @@ GRAD_CTL_FIRST, GRAD_CTL_APPLY, GRAD_CTL_GMUL, GRAD_CTL_NORM = 2, 3, 4, 5
 
 
 def _grad_ws(n, device):
-    nbytes = lib().call('dpf_grad_ctl_workspace_bytes', n)
-    if nbytes < 0:
-        raise DpfError('grad_ctl: an arena of %d elements is not supported' % n)
-    return scratch((nbytes + 3) // 4, device, 'grad_ctl'), nbytes
+    return _workspace('dpf_grad_ctl_workspace_bytes', 'grad_ctl: an arena of %d elements is not supported', n, device=device, tag='grad_ctl')
 
 
 def _need_ctl(ctl):
@@ -1933,10 +1936,7 @@ METRIC_TARGET = {'disp': 0, 'idepth': 1, 'depth': 2}
 
 
 def _metric_ws(query, B, n, device):
-    nbytes = lib().call(query, B, n)
-    if nbytes < 0:
-        raise DpfError('%s: shape B=%d n=%d is not supported' % (query, B, n))
-    return scratch((nbytes + 3) // 4, device, 'metric'), nbytes
+    return _workspace(query, query + ': shape B=%d n=%d is not supported', B, n, device=device, tag='metric')
 
 
 def metric_absolute_dp(pred, abvalue, target, mask=None, target_type='disp', threshold=1.01, out=None):

@@ -125,6 +125,15 @@ def test_fit_iteration_cap():
     assert torch.equal(info0[:, 4], info0[:, 5]) and torch.equal(info0[:, 5], info[:, 5])
 
 
+def test_fit_fold_of_more_rows_than_threads():
+    """1024 x 1028: 257 partial rows in the sample's fold, so its first thread adds two of them (every other shape here folds <= 3).
+    Two forced steps, as above: only the order of the fp64 sums separates the two sides."""
+    pred, idepth, _ = _fields(1, 1, 1024, 1028, seed=17)
+    _, info = _fit(pred, idepth, max_iters=2)
+    assert [int(v) for v in info[:, 2]] == [2]
+    _against_restatement(pred, idepth, info, '1024x1028', max_iters=2, bar=1e-9)
+
+
 def test_fit_ignores_what_lies_at_invalid_pixels():
     pred, idepth, _ = _fields(2, 2, 40, 56, seed=15)
     ab, info = _fit(pred, idepth)

@@ -153,6 +153,25 @@ def test_families_within_the_yardstick(shape, mask):
         np.testing.assert_array_equal(rows['absolute_dp'][5:], ref['absolute_dp'][1][5:])
 
 
+def test_fold_of_more_rows_than_threads():
+    """B = 2 at 512 x 512: 256 partial rows per sample, 512 in the one fold of absolute_dp and of normal_dp, so every fold thread adds two
+    rows (fx.SHAPES fold <= 9).  affine_dp folds per sample and never exceeds 256 rows; it stays out to keep the CPU side short."""
+    from dualpixelface_amd.config import load_option
+    from dualpixelface_amd.selectors import metric_selector
+    pred_, batch = fx.make_case(2, 512, 512, 'bern', seed=11)
+    opt = load_option()
+    opt.model.metric_type = ['absolute_dp', 'normal_dp']
+    T = metric_selector(opt).forward(fx.cast(pred_, torch.float64), fx.cast(batch, torch.float64), log=False)
+    F = metric_selector(opt).forward(pred_, batch, log=False)
+    sel = metric_selector(opt)
+    with sel.deferred():
+        out = sel.forward(fx.cast(pred_, device=DEV), fx.cast(batch, device=DEV), log=False)
+    rows = {n: r.cpu().tolist() for n, r in out.items()}
+    for name in ('absolute_dp', 'normal_dp'):
+        fx.assert_yardstick(rows[name], T[name], F[name], '%s 512 rows' % name)
+    np.testing.assert_array_equal(rows['absolute_dp'][5:], F['absolute_dp'][5:])
+
+
 @pytest.mark.parametrize('target_type', ['idepth', 'depth'])
 def test_other_target_types_select_the_same_inputs(target_type):
     pred_, batch = fx.make_case(2, 16, 24, 'bern', seed=3)

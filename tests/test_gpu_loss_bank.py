@@ -91,6 +91,18 @@ def test_partial_fold_and_tails(kind, transform, mask, conf, shape):
 
 
 @pytest.mark.parametrize('kind', ['silog', 'smoothL1'])
+def test_fold_of_more_rows_than_threads(kind):
+    """B = 3 at 512 x 704: 88 partial rows per sample, 264 in the one fold, so a fold thread adds more than one row (SHAPES fold <= 9)."""
+    pred, target, m, _ = _fields(3, 2, 512, 704, 12, True, False)
+    weights = WEIGHTS8[:2]
+    loss, grad = _run(pred, target, m, None, weights, kind, 'identity', 0.85)
+    ref_loss, ref_grad = lb.depth_loss(pred, target, m, None, weights, kind, 'identity', 0.85)
+    assert torch.isfinite(ref_loss)
+    lb.close(loss, ref_loss, 1e-5, kind + ' 264 rows loss')
+    lb.close_elem(grad, ref_grad, kind + ' 264 rows grad')
+
+
+@pytest.mark.parametrize('kind', ['silog', 'smoothL1'])
 def test_one_head_weighs_one(kind):
     """One head: weight [1.0] even though loss_weight is longer and starts elsewhere (smoothL1.py:22, silog.py:23)."""
     pred, target, m, _ = _fields(2, 1, 67, 129, 6, True, False)
