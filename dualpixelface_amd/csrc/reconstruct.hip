@@ -1,0 +1,470 @@
+// Camera-space surface of a predicted map at evaluation time (option key reconstruct; dualpixelface_amd/reconstruct.py): the point map, the
+// geometric normals of the depth, and a compacted triangle mesh with per-vertex normal and colour.  The reference defines none of this, so
+// the definitions below are this project's own.  They follow anm.hip's conventions: pixel grid x = 0..W-1,
+// y = 0..H-1, rays r(x, y) = Kinv [x, y, 1] (no quarter scale here), depth = a / (pred - b) with a non-finite value -> 0.
+//
+//   dpf_backproject      points = z r, valid                                             1 launch
+//   dpf_depth_normals    normal, normal_valid from a depth tile with a 1-pixel halo      1 launch
+//   dpf_depth_mesh       counts per block, scan per sample, vertices, faces              4 launches
+//
+// Every fp32 expression is written operation by operation and the file is compiled with -ffp-contract=off, so tests/reconstruct_cpu.py
+// can restate it in numpy and the integer outputs (validity, connectivity, counts, faces) compare exactly.
+// Depth (fp32): z = a / (pred - b) for target types 0 (disp) and 1 (idepth), z = pred for 2 (depth); non-finite -> 0.
+// Validity: z finite, near < z < far (near >= 0, so the 0 of a non-finite value is never valid), mask NULL or mask > 0, K regular.
+// Kinv: the 3 x 3 adjugate over the determinant in fp64 from the fp32 K, each entry rounded to fp32 once; |det| < 1e-30 (or a
+// non-finite det) makes the whole sample invalid.  Ray: (Kinv[k][0] x + Kinv[k][1] y) + Kinv[k][2] in fp32.
+// Connected(p, q): both valid and |z_p - z_q| <= max_edge_ratio * min(z_p, z_q) (fp32: multiply, then compare).
+// Step from p to q, q to the right of p by D columns: (z_q - z_p) r_q + (z_p D) Kinv[:, 0] -- the difference of the two points with the
+// nearly equal parts cancelled analytically; rows below use Kinv[:, 1].
+// No floating-point atomics, no workgroup waits for another inside a launch, every count in a fixed order: the bits repeat.
+#include "dpf_common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kTW = 32, kTH = 8;               // normals: output tile, one pixel per thread
+constexpr int kPerThread = 4;                  // mesh: grid nodes per thread
+constexpr int kNodes = kBlock * kPerThread;    // and per workgroup
+constexpr int kMaxBatch = 65535;               // B rides on gridDim.y / gridDim.z
+constexpr int kMaxTileRows = 65535;            // and the normals' tile rows on gridDim.y
+
+struct Norm { float mean[3], std[3]; };
+
+struct Cam {
+  float inv[9];       // Kinv, row-major
+  float a, b;         // depth = a / (pred - b)
+  int ok;             // K regular
+};
+
+struct Scene {        // the operands backproject, depth_normals and depth_mesh share
+  const float* pred;
+  long long pstride;
+  const float* ab;
+  const float* Kmat;
+  const float* mask;
+  int target_type, H, W;
+  float z_near, z_far;
+};
+
+// one thread per workgroup forms the sample's camera; the caller publishes it with a barrier
+__device__ void cam_setup(const Scene& sc, int s, Cam* cam) {
+  const float* Kf = sc.Kmat + (size_t)s * 9;
+  double m[9];
+  for (int k = 0; k < 9; ++k) m[k] = (double)Kf[k];
+  const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
+  const double det = (m[0] * c00 + m[1] * c01) + m[2] * c02;
+  cam->ok = isfinite(det) && fabs(det) >= 1e-30;
+  const double adj[9] = {c00, m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
+                         c01, m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
+                         c02, m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]};
+  for (int k = 0; k < 9; ++k) cam->inv[k] = cam->ok ? (float)(adj[k] / det) : 0.f;
+  cam->b = sc.target_type == 2 ? 0.f : sc.ab[2 * (size_t)s];
+  cam->a = sc.target_type == 2 ? 0.f : sc.ab[2 * (size_t)s + 1];
+}
+
+// the depth of pixel (y, x) of sample s where it is valid, else 0
+__device__ __forceinline__ float valid_depth(const Scene& sc, const Cam& cam, int s, int y, int x) {
+  const size_t o = (size_t)y * sc.W + x;
+  const float p = sc.pred[(size_t)s * (size_t)sc.pstride + o];
+  float z = sc.target_type == 2 ? p : cam.a / (p - cam.b);
+  if (!isfinite(z)) z = 0.f;
+  bool ok = cam.ok && z > sc.z_near && z < sc.z_far;
+  if (sc.mask) ok = ok && sc.mask[(size_t)s * sc.H * sc.W + o] > 0.f;
+  return ok ? z : 0.f;
+}
+
+__device__ __forceinline__ void ray_of(const Cam& cam, int y, int x, float (&r)[3]) {
+  const float xf = (float)x, yf = (float)y;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) r[k] = (cam.inv[3 * k] * xf + cam.inv[3 * k + 1] * yf) + cam.inv[3 * k + 2];
+}
+
+__device__ __forceinline__ bool connected(float zp, float zq, float ratio) {
+  return zp > 0.f && zq > 0.f && fabsf(zp - zq) <= ratio * fminf(zp, zq);
+}
+
+// grid (blocks, B)
+__global__ __launch_bounds__(256) void backproject_kernel(Scene sc, float* __restrict__ points, unsigned char* __restrict__ valid) {
+  __shared__ Cam scam;
+  const int s = blockIdx.y;
+  if (threadIdx.x == 0) cam_setup(sc, s, &scam);
+  __syncthreads();
+  const Cam cam = scam;
+  const long long HW = (long long)sc.H * sc.W;
+  float* P = points + (size_t)s * 3 * (size_t)HW;
+  unsigned char* V = valid + (size_t)s * (size_t)HW;
+  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < HW; i += (long long)gridDim.x * kBlock) {
+    const int y = (int)(i / sc.W), x = (int)(i - (long long)y * sc.W);
+    const float z = valid_depth(sc, cam, s, y, x);
+    float r[3];
+    ray_of(cam, y, x, r);
+    P[i] = z * r[0];
+    P[i + HW] = z * r[1];
+    P[i + 2 * HW] = z * r[2];
+    V[i] = z > 0.f ? 1 : 0;
+  }
+}
+
+// The step between two neighbours along one image axis (col: column k of Kinv, 0 for a row step, 1 for a column step).  zm, zc, zp: the
+// depths before, at and after the centre (0: invalid); rc, rp: the rays at the centre and after it.  Central where the centre is connected
+// to both sides, else one-sided towards the single connected side, oriented before -> after; false: no step.
+__device__ __forceinline__ bool step_of(const Cam& cam, int col, float zm, float zc, float zp, const float (&rc)[3], const float (&rp)[3],
+                                        float ratio, float (&d)[3]) {
+  const bool cm = connected(zm, zc, ratio), cp = connected(zc, zp, ratio);
+  if (!cm && !cp) return false;
+  const float zfrom = cm ? zm : zc, zto = cp ? zp : zc;
+  const float delta = cm && cp ? 2.f : 1.f;
+  const float dz = zto - zfrom, t = zfrom * delta;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float rq = cp ? rp[k] : rc[k];
+    d[k] = dz * rq + t * cam.inv[3 * k + col];
+  }
+  return true;
+}
+
+// grid (ceil(W / 32), ceil(H / 8), B), 256 threads = 8 rows x 32 columns
+__global__ __launch_bounds__(256) void normals_kernel(Scene sc, float ratio, int towards_camera, float* __restrict__ normal,
+                                                      unsigned char* __restrict__ nvalid) {
+  __shared__ Cam scam;
+  __shared__ float tile[kTH + 2][kTW + 2];
+  const int s = blockIdx.z, t = threadIdx.x;
+  if (t == 0) cam_setup(sc, s, &scam);
+  __syncthreads();
+  const Cam cam = scam;
+  const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+  for (int i = t; i < (kTH + 2) * (kTW + 2); i += kBlock) {
+    const int ly = i / (kTW + 2), lx = i - ly * (kTW + 2);
+    const int y = y0 - 1 + ly, x = x0 - 1 + lx;
+    tile[ly][lx] = y >= 0 && y < sc.H && x >= 0 && x < sc.W ? valid_depth(sc, cam, s, y, x) : 0.f;
+  }
+  __syncthreads();
+  const int tx = t & (kTW - 1), ty = t / kTW;
+  const int x = x0 + tx, y = y0 + ty;
+  if (x >= sc.W || y >= sc.H) return;                      // (no barrier below)
+  const float zc = tile[ty + 1][tx + 1];
+  float n[3] = {0.f, 0.f, 0.f};
+  bool ok = zc > 0.f;
+  if (ok) {
+    float rc[3], rr[3], rd[3], drow[3], dcol[3];
+    ray_of(cam, y, x, rc);
+    ray_of(cam, y, x + 1, rr);
+    ray_of(cam, y + 1, x, rd);
+    const bool hrow = step_of(cam, 0, tile[ty + 1][tx], zc, tile[ty + 1][tx + 2], rc, rr, ratio, drow);
+    const bool hcol = step_of(cam, 1, tile[ty][tx + 1], zc, tile[ty + 2][tx + 1], rc, rd, ratio, dcol);
+    ok = hrow && hcol;
+    if (ok) {
+      const float cx = drow[1] * dcol[2] - drow[2] * dcol[1];
+      const float cy = drow[2] * dcol[0] - drow[0] * dcol[2];
+      const float cz = drow[0] * dcol[1] - drow[1] * dcol[0];
+      const float len = sqrtf((cx * cx + cy * cy) + cz * cz);
+      ok = len > 0.f && isfinite(len);
+      if (ok) {
+        n[0] = cx / len;
+        n[1] = cy / len;
+        n[2] = cz / len;
+        const float dot = (n[0] * (zc * rc[0]) + n[1] * (zc * rc[1])) + n[2] * (zc * rc[2]);
+        if (towards_camera ? dot > 0.f : dot < 0.f) {
+          n[0] = -n[0];
+          n[1] = -n[1];
+          n[2] = -n[2];
+        }
+      }
+    }
+  }
+  const size_t HW = (size_t)sc.H * sc.W, o = (size_t)y * sc.W + x;
+  float* N = normal + (size_t)s * 3 * HW;
+  N[o] = n[0];
+  N[o + HW] = n[1];
+  N[o + 2 * HW] = n[2];
+  nvalid[(size_t)s * HW + o] = ok ? 1 : 0;
+}
+
+// ---- mesh
+struct Grid { int stride, Hs, Ws, nodes, nb; };           // nodes = Hs Ws per sample, nb workgroups of kNodes nodes per sample
+
+// exclusive scan of one int per thread over the 256 threads of a workgroup, in thread order; *total: the sum, in every thread
+__device__ __forceinline__ int block_scan(int v, int* sm4, int* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += u;
+  }
+  __syncthreads();                                         // (sm4 may still be read from the scan before)
+  if (lane == 63) sm4[w] = inc;
+  __syncthreads();
+  int base = 0;
+  for (int k = 0; k < w; ++k) base += sm4[k];
+  *total = (sm4[0] + sm4[1]) + (sm4[2] + sm4[3]);
+  return base + inc - v;
+}
+
+__device__ __forceinline__ float node_depth(const Scene& sc, const Cam& cam, const Grid& g, int s, int i, int j) {
+  return valid_depth(sc, cam, s, i * g.stride, j * g.stride);
+}
+
+// the two triangles of the quad whose corner a is node (i, j): bit 0 = T0 (a, c, b), bit 1 = T1 (b, c, d)
+__device__ __forceinline__ int quad_flags(const Scene& sc, const Cam& cam, const Grid& g, int s, int i, int j, float ratio) {
+  if (i >= g.Hs - 1 || j >= g.Ws - 1) return 0;
+  const float za = node_depth(sc, cam, g, s, i, j), zb = node_depth(sc, cam, g, s, i, j + 1);
+  const float zc = node_depth(sc, cam, g, s, i + 1, j), zd = node_depth(sc, cam, g, s, i + 1, j + 1);
+  const bool bc = connected(zb, zc, ratio);
+  const int t0 = bc && connected(za, zc, ratio) && connected(zb, za, ratio);
+  const int t1 = bc && connected(zc, zd, ratio) && connected(zd, zb, ratio);
+  return t0 | (t1 << 1);
+}
+
+// grid (nb, B): blockcnt [B][nb][2] = (valid nodes, triangles) of the workgroup's kNodes nodes
+__global__ __launch_bounds__(256) void mesh_count_kernel(Scene sc, Grid g, float ratio, int* __restrict__ blockcnt) {
+  __shared__ Cam scam;
+  __shared__ int sm4[4];
+  const int s = blockIdx.y;
+  if (threadIdx.x == 0) cam_setup(sc, s, &scam);
+  __syncthreads();
+  const Cam cam = scam;
+  int packed = 0;                                          // vertices in the low 16 bits (<= 1024 per workgroup), triangles above (<= 2048)
+  const int n0 = blockIdx.x * kNodes + threadIdx.x * kPerThread;
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    const int n = n0 + k;
+    if (n >= g.nodes) break;
+    const int i = n / g.Ws, j = n - i * g.Ws;
+    const int q = quad_flags(sc, cam, g, s, i, j, ratio);
+    packed += (node_depth(sc, cam, g, s, i, j) > 0.f ? 1 : 0) + (((q & 1) + (q >> 1)) << 16);
+  }
+  int total;
+  block_scan(packed, sm4, &total);
+  if (threadIdx.x == 0) {
+    int* out = blockcnt + ((size_t)s * g.nb + blockIdx.x) * 2;
+    out[0] = total & 0xffff;
+    out[1] = total >> 16;
+  }
+}
+
+// grid (B): one workgroup folds the sample's nb workgroup counts, 256 at a time in order, into exclusive offsets and the totals
+__global__ __launch_bounds__(256) void mesh_scan_kernel(int nb, const int* __restrict__ blockcnt, int* __restrict__ blockoff,
+                                                        int* __restrict__ counts) {
+  __shared__ int sm4[4];
+  const int s = blockIdx.x;
+  const int* cnt = blockcnt + (size_t)s * nb * 2;
+  int* off = blockoff + (size_t)s * nb * 2;
+  int carry_v = 0, carry_t = 0;
+  for (int c0 = 0; c0 < nb; c0 += kBlock) {
+    const int c = c0 + threadIdx.x;
+    const int v = c < nb ? cnt[2 * c] : 0, t = c < nb ? cnt[2 * c + 1] : 0;
+    int tot_v, tot_t;
+    const int ev = block_scan(v, sm4, &tot_v), et = block_scan(t, sm4, &tot_t);
+    if (c < nb) {
+      off[2 * c] = carry_v + ev;
+      off[2 * c + 1] = carry_t + et;
+    }
+    carry_v += tot_v;
+    carry_t += tot_t;
+  }
+  if (threadIdx.x == 0) {
+    counts[2 * s] = carry_v;
+    counts[2 * s + 1] = carry_t;
+  }
+}
+
+// grid (nb, B): the vertex index of every node (-1: none) and the vertex records
+__global__ __launch_bounds__(256) void mesh_vertex_kernel(Scene sc, Grid g, const int* __restrict__ blockoff, const float* __restrict__ nmap,
+                                                          const float* __restrict__ view, Norm nm, int* __restrict__ vidx,
+                                                          float* __restrict__ vertices, float* __restrict__ vnormals,
+                                                          unsigned char* __restrict__ vcolours) {
+  __shared__ Cam scam;
+  __shared__ int sm4[4];
+  const int s = blockIdx.y;
+  if (threadIdx.x == 0) cam_setup(sc, s, &scam);
+  __syncthreads();
+  const Cam cam = scam;
+  const int n0 = blockIdx.x * kNodes + threadIdx.x * kPerThread;
+  float z[kPerThread];
+  int mine = 0;
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    const int n = n0 + k;
+    z[k] = 0.f;
+    if (n < g.nodes) {
+      const int i = n / g.Ws;
+      z[k] = node_depth(sc, cam, g, s, i, n - i * g.Ws);
+    }
+    mine += z[k] > 0.f ? 1 : 0;
+  }
+  int total;
+  int at = blockoff[((size_t)s * g.nb + blockIdx.x) * 2] + block_scan(mine, sm4, &total);
+  const size_t HW = (size_t)sc.H * sc.W;
+  int* vi = vidx + (size_t)s * g.nodes;
+  float* V = vertices + (size_t)s * g.nodes * 3;
+  float* N = vnormals + (size_t)s * g.nodes * 3;
+  unsigned char* C = vcolours + (size_t)s * g.nodes * 3;
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    const int n = n0 + k;
+    if (n >= g.nodes) break;
+    if (!(z[k] > 0.f)) {
+      vi[n] = -1;
+      continue;
+    }
+    const int i = n / g.Ws, j = n - i * g.Ws;
+    const int y = i * g.stride, x = j * g.stride;
+    const size_t o = (size_t)s * 3 * HW + (size_t)y * sc.W + x;
+    float r[3];
+    ray_of(cam, y, x, r);
+    vi[n] = at;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      V[(size_t)at * 3 + c] = z[k] * r[c];
+      N[(size_t)at * 3 + c] = nmap[o + c * HW];
+      float col = 255.f;
+      if (view) col = fminf(fmaxf(rintf(255.f * (view[o + c * HW] * nm.std[c] + nm.mean[c])), 0.f), 255.f);
+      C[(size_t)at * 3 + c] = (unsigned char)col;
+    }
+    ++at;
+  }
+}
+
+// grid (nb, B): the faces, quads in row-major order, T0 before T1, through the vertex indices of the pass before
+__global__ __launch_bounds__(256) void mesh_face_kernel(Scene sc, Grid g, float ratio, int towards_camera, const int* __restrict__ blockoff,
+                                                        const int* __restrict__ vidx, int* __restrict__ faces) {
+  __shared__ Cam scam;
+  __shared__ int sm4[4];
+  const int s = blockIdx.y;
+  if (threadIdx.x == 0) cam_setup(sc, s, &scam);
+  __syncthreads();
+  const Cam cam = scam;
+  const int n0 = blockIdx.x * kNodes + threadIdx.x * kPerThread;
+  int q[kPerThread];
+  int mine = 0;
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    const int n = n0 + k;
+    q[k] = 0;
+    if (n < g.nodes) {
+      const int i = n / g.Ws;
+      q[k] = quad_flags(sc, cam, g, s, i, n - i * g.Ws, ratio);
+    }
+    mine += (q[k] & 1) + (q[k] >> 1);
+  }
+  int total;
+  int at = blockoff[((size_t)s * g.nb + blockIdx.x) * 2 + 1] + block_scan(mine, sm4, &total);
+  const int* vi = vidx + (size_t)s * g.nodes;
+  const size_t quads = (size_t)(g.Hs - 1) * (size_t)(g.Ws - 1);
+  int* F = faces + (size_t)s * 2 * quads * 3;
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    if (!q[k]) continue;
+    const int n = n0 + k;
+    const int a = vi[n], b = vi[n + 1], c = vi[n + g.Ws], d = vi[n + g.Ws + 1];
+    if (q[k] & 1) {
+      F[(size_t)at * 3] = a;
+      F[(size_t)at * 3 + 1] = towards_camera ? c : b;
+      F[(size_t)at * 3 + 2] = towards_camera ? b : c;
+      ++at;
+    }
+    if (q[k] & 2) {
+      F[(size_t)at * 3] = b;
+      F[(size_t)at * 3 + 1] = towards_camera ? c : d;
+      F[(size_t)at * 3 + 2] = towards_camera ? d : c;
+      ++at;
+    }
+  }
+}
+
+bool scene_ok(const float* pred, long long pstride, int target_type, const float* ab, const float* Kmat, int B, int H, int W, float z_near,
+              float z_far) {
+  return pred && Kmat && B > 0 && H > 0 && W > 0 && target_type >= 0 && target_type <= 2 && (target_type == 2 || ab) &&
+         pstride >= (long long)H * W && z_near >= 0.f && z_far > z_near;      // (a NaN limit fails both comparisons)
+}
+
+bool scene_supported(int B, int H, int W) { return B <= kMaxBatch && (long long)H * W <= 0x7fffffffLL; }
+
+Scene scene_of(const float* pred, long long pstride, int target_type, const float* ab, const float* Kmat, const float* mask, int H, int W,
+               float z_near, float z_far) {
+  Scene sc;
+  sc.pred = pred, sc.pstride = pstride, sc.ab = ab, sc.Kmat = Kmat, sc.mask = mask;
+  sc.target_type = target_type, sc.H = H, sc.W = W, sc.z_near = z_near, sc.z_far = z_far;
+  return sc;
+}
+
+bool grid_of(int B, int H, int W, int stride, Grid* g) {
+  if (B <= 0 || H <= 0 || W <= 0 || !(stride == 1 || stride == 2 || stride == 4 || stride == 8) || !scene_supported(B, H, W)) return false;
+  g->stride = stride;
+  g->Hs = dpf_div_up(H, stride);
+  g->Ws = dpf_div_up(W, stride);
+  g->nodes = g->Hs * g->Ws;
+  g->nb = dpf_div_up(g->nodes, kNodes);
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dpf_backproject(const float* pred, long long pred_batch_stride, int target_type, const float* ab, const float* Kmat, const float* mask,
+                    int B, int H, int W, float z_near, float z_far, float* points, unsigned char* valid, void* stream) {
+  dpf_clear_error();
+  if (!scene_ok(pred, pred_batch_stride, target_type, ab, Kmat, B, H, W, z_near, z_far) || !points || !valid) return DPF_ERR_INVALID_ARG;
+  if (!scene_supported(B, H, W)) return DPF_ERR_UNSUPPORTED;
+  const Scene sc = scene_of(pred, pred_batch_stride, target_type, ab, Kmat, mask, H, W, z_near, z_far);
+  hipLaunchKernelGGL(backproject_kernel, dim3(dpf_ew_grid((long long)H * W), B), dim3(kBlock), 0, (hipStream_t)stream, sc, points, valid);
+  return dpf_check_launch();
+}
+
+int dpf_depth_normals(const float* pred, long long pred_batch_stride, int target_type, const float* ab, const float* Kmat, const float* mask,
+                      int B, int H, int W, float z_near, float z_far, float max_edge_ratio, int towards_camera, float* normal,
+                      unsigned char* normal_valid, void* stream) {
+  dpf_clear_error();
+  if (!scene_ok(pred, pred_batch_stride, target_type, ab, Kmat, B, H, W, z_near, z_far) || !normal || !normal_valid ||
+      !(max_edge_ratio > 0.f))
+    return DPF_ERR_INVALID_ARG;
+  if (!scene_supported(B, H, W) || dpf_div_up(H, kTH) > kMaxTileRows) return DPF_ERR_UNSUPPORTED;
+  const Scene sc = scene_of(pred, pred_batch_stride, target_type, ab, Kmat, mask, H, W, z_near, z_far);
+  hipLaunchKernelGGL(normals_kernel, dim3(dpf_div_up(W, kTW), dpf_div_up(H, kTH), B), dim3(kBlock), 0, (hipStream_t)stream, sc,
+                     max_edge_ratio, towards_camera, normal, normal_valid);
+  return dpf_check_launch();
+}
+
+long long dpf_depth_mesh_workspace_bytes(int B, int H, int W, int stride) {
+  Grid g;
+  if (!grid_of(B, H, W, stride, &g)) return -1;
+  const long long ints = 4LL * B * g.nb + (long long)B * g.nodes;            // workgroup counts, their offsets, the vertex index of a node
+  return ((ints * 4 + 7) / 8) * 8;
+}
+
+int dpf_depth_mesh(const float* pred, long long pred_batch_stride, int target_type, const float* ab, const float* Kmat, const float* mask,
+                   const float* normal_map, const float* view, const float* norm_host, int B, int H, int W, int stride, float z_near,
+                   float z_far, float max_edge_ratio, int towards_camera, void* ws, long long ws_bytes, float* vertices,
+                   float* vertex_normals, unsigned char* vertex_colours, int* faces, int* counts, void* stream) {
+  dpf_clear_error();
+  if (!scene_ok(pred, pred_batch_stride, target_type, ab, Kmat, B, H, W, z_near, z_far) || !normal_map || (view && !norm_host) || !ws ||
+      !vertices || !vertex_normals || !vertex_colours || !counts || !(max_edge_ratio > 0.f) || stride < 1)
+    return DPF_ERR_INVALID_ARG;
+  Grid g;
+  if (!grid_of(B, H, W, stride, &g)) return DPF_ERR_UNSUPPORTED;
+  if (!faces && g.Hs > 1 && g.Ws > 1) return DPF_ERR_INVALID_ARG;            // (a grid of one row or column has no quad: faces is empty)
+  if (ws_bytes < dpf_depth_mesh_workspace_bytes(B, H, W, stride) || ((uintptr_t)ws & 7u)) return DPF_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const Scene sc = scene_of(pred, pred_batch_stride, target_type, ab, Kmat, mask, H, W, z_near, z_far);
+  Norm nm;
+  for (int c = 0; c < 3; ++c) {
+    nm.mean[c] = view ? norm_host[c] : 0.f;
+    nm.std[c] = view ? norm_host[3 + c] : 0.f;
+  }
+  int* blockcnt = (int*)ws;
+  int* blockoff = blockcnt + 2 * (size_t)B * g.nb;
+  int* vidx = blockoff + 2 * (size_t)B * g.nb;
+  const dim3 grid(g.nb, B);
+  hipLaunchKernelGGL(mesh_count_kernel, grid, dim3(kBlock), 0, st, sc, g, max_edge_ratio, blockcnt);
+  hipLaunchKernelGGL(mesh_scan_kernel, dim3(B), dim3(kBlock), 0, st, g.nb, (const int*)blockcnt, blockoff, counts);
+  hipLaunchKernelGGL(mesh_vertex_kernel, grid, dim3(kBlock), 0, st, sc, g, (const int*)blockoff, normal_map, view, nm, vidx, vertices,
+                     vertex_normals, vertex_colours);
+  hipLaunchKernelGGL(mesh_face_kernel, grid, dim3(kBlock), 0, st, sc, g, max_edge_ratio, towards_camera, (const int*)blockoff,
+                     (const int*)vidx, faces);
+  return dpf_check_launch();
+}
+
+}  // extern "C"

@@ -1809,6 +1809,116 @@ def joint_bilateral_filter(pred, guide_rgb, radius, sigma_space, sigma_color):
     return out
 
 
+TARGET_TYPES = {'disp': 0, 'idepth': 1, 'depth': 2}       # the codes of csrc/reconstruct.hip
+MESH_STRIDES = (1, 2, 4, 8)
+
+
+def _scene_operands(name, pred, target_type, ab, Kmat, mask, near, far):
+    """The operands the three surface operators share -> (the leading arguments of the C call, the tensors behind its pointers, (B, H, W)):
+    head 0 of pred [B, n, H, W] (or a [B, H, W] map; a slice of a wider tensor is taken as it is, through its batch stride), ab [B, 2] =
+    [b, a] (None with target type 'depth'), Kmat [B, 3, 3], mask [B, H, W] or None, and the depth limits (far None: no limit).  The caller
+    holds the tensors until its launches are enqueued."""
+    if target_type not in TARGET_TYPES:
+        raise DpfError('%s: target_type must be one of %s, got %r' % (name, sorted(TARGET_TYPES), target_type))
+    for t in (pred, Kmat, ab, mask):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise DpfError('dualpixelface_amd ops need GPU tensors (no CPU fallback)')
+        if t.dtype != torch.float32:
+            raise DpfError('unsupported dtype %s' % t.dtype)
+    pred = pred.detach()
+    if pred.dim() == 3:
+        pred = pred.unsqueeze(1)
+    if pred.dim() != 4:
+        raise DpfError('%s: pred %s is neither [B, n, H, W] nor [B, H, W]' % (name, tuple(pred.shape)))
+    B, n, H, W = pred.shape
+    if tuple(Kmat.shape) != (B, 3, 3):
+        raise DpfError('%s: K %s does not match pred %s (want [B, 3, 3])' % (name, tuple(Kmat.shape), tuple(pred.shape)))
+    if ab is None and target_type != 'depth':
+        raise DpfError('%s: target_type %r needs ab [B, 2] = [b, a]' % (name, target_type))
+    if ab is not None and tuple(ab.shape) != (B, 2):
+        raise DpfError('%s: ab %s does not match pred %s (want [B, 2])' % (name, tuple(ab.shape), tuple(pred.shape)))
+    if mask is not None and tuple(mask.shape) != (B, H, W):
+        raise DpfError('%s: mask %s does not match pred %s (want [B, H, W])' % (name, tuple(mask.shape), tuple(pred.shape)))
+    if not (pred[0].is_contiguous() and (B == 1 or pred.stride(0) >= H * W)):
+        pred = pred.contiguous()
+    stride = pred.stride(0) if B > 1 else n * H * W
+    held = (pred, None if ab is None else _c(ab.detach()), _c(Kmat.detach()), None if mask is None else _c(mask.detach()))
+    head = (_ptr(held[0]), stride, TARGET_TYPES[target_type], _ptr(held[1]), _ptr(held[2]), _ptr(held[3]), B, H, W, float(near),
+            float('inf') if far is None else float(far))
+    return head, held, (B, H, W)
+
+
+def backproject(pred, Kmat, ab=None, mask=None, target_type='disp', near=0.0, far=None):
+    """csrc/reconstruct.hip: head 0 of pred [B, n, H, W] (or [B, H, W]) -> points [B, 3, H, W] fp32 = z K^-1 [x, y, 1] (0 where invalid) and
+    valid [B, H, W] uint8.  z = a / (pred - b) with ab [B, 2] = [b, a] for 'disp' / 'idepth', z = pred for 'depth'; valid where z is finite,
+    near < z < far and mask (None: everywhere) > 0.  An inference-time operator: detached, fresh outputs, nothing read on the host."""
+    with torch.no_grad():
+        head, held, (B, H, W) = _scene_operands('backproject', pred, target_type, ab, Kmat, mask, near, far)
+        points = torch.empty((B, 3, H, W), dtype=torch.float32, device=held[0].device)
+        valid = torch.empty((B, H, W), dtype=torch.uint8, device=held[0].device)
+        lib().call('dpf_backproject', *head, _ptr(points), _ptr(valid), _stream())
+    return points, valid
+
+
+def depth_normals(pred, Kmat, ab=None, mask=None, target_type='disp', near=0.0, far=None, max_edge_ratio=0.01, towards_camera=True):
+    """csrc/reconstruct.hip: geometric normals of the depth of head 0 of pred -> normal [B, 3, H, W] fp32 (unit, or 0 where there is none) and
+    normal_valid [B, H, W] uint8.  Per image axis the central step where a pixel is connected to both neighbours
+    (|z_p - z_q| <= max_edge_ratio min(z_p, z_q)), the one-sided step to the single connected one otherwise; operands as backproject."""
+    with torch.no_grad():
+        head, held, (B, H, W) = _scene_operands('depth_normals', pred, target_type, ab, Kmat, mask, near, far)
+        normal = torch.empty((B, 3, H, W), dtype=torch.float32, device=held[0].device)
+        nvalid = torch.empty((B, H, W), dtype=torch.uint8, device=held[0].device)
+        lib().call('dpf_depth_normals', *head, float(max_edge_ratio), int(bool(towards_camera)), _ptr(normal), _ptr(nvalid), _stream())
+    return normal, nvalid
+
+
+def depth_mesh(pred, Kmat, normal_map, ab=None, mask=None, view=None, target_type='disp', stride=1, near=0.0, far=None, max_edge_ratio=0.01,
+               towards_camera=True, out=None):
+    """csrc/reconstruct.hip: the compacted triangle mesh over every `stride`-th pixel (1, 2, 4 or 8) of head 0 of pred ->
+    (vertices [B, Hs Ws, 3] fp32, vertex_normals [B, Hs Ws, 3] fp32 gathered from normal_map [B, 3, H, W], vertex_colours [B, Hs Ws, 3] uint8
+    from the normalised view [B, 3, H, W] (None: 255), faces [B, 2 (Hs - 1)(Ws - 1), 3] int32 with sample-local indices, counts [B, 2] int32 =
+    (vertices, faces)).  The buffers are worst-case sized and entries past the counts are left as torch.empty (or `out`, a tuple of the five
+    to write into) had them; counts stays on the device: nothing is read on the host."""
+    from .facedp import IMAGENET_MEAN, IMAGENET_STD          # the data path's Normalizer: the one place these constants live
+    if isinstance(stride, bool) or not hasattr(stride, '__index__'):
+        raise DpfError('depth_mesh: stride must be an integer, got %r' % (stride,))
+    stride = stride.__index__()
+    with torch.no_grad():
+        head, held, (B, H, W) = _scene_operands('depth_mesh', pred, target_type, ab, Kmat, mask, near, far)
+        for name, t in (('normal_map', normal_map), ('view', view)):
+            if t is None and name == 'view':
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise DpfError('dualpixelface_amd ops need GPU tensors (no CPU fallback)')
+            if t.dtype != torch.float32:
+                raise DpfError('unsupported dtype %s' % t.dtype)
+            if tuple(t.shape) != (B, 3, H, W):
+                raise DpfError('depth_mesh: %s %s does not match pred %s (want [B, 3, H, W])' % (name, tuple(t.shape), tuple(held[0].shape)))
+        nmap, view = _c(normal_map.detach()), None if view is None else _c(view.detach())
+        dev = held[0].device
+        ws, nbytes = _workspace('dpf_depth_mesh_workspace_bytes', 'depth_mesh: B=%d H=%d W=%d stride=%d is not supported (stride 1, 2, 4 or 8)',
+                                B, H, W, stride, device=dev, tag='reconstruct')
+        Hs, Ws = -(-H // stride), -(-W // stride)
+        if out is None:
+            out = (torch.empty((B, Hs * Ws, 3), dtype=torch.float32, device=dev), torch.empty((B, Hs * Ws, 3), dtype=torch.float32, device=dev),
+                   torch.empty((B, Hs * Ws, 3), dtype=torch.uint8, device=dev),
+                   torch.empty((B, 2 * (Hs - 1) * (Ws - 1), 3), dtype=torch.int32, device=dev), torch.empty((B, 2), dtype=torch.int32, device=dev))
+        want = ((B, Hs * Ws, 3), (B, Hs * Ws, 3), (B, Hs * Ws, 3), (B, 2 * (Hs - 1) * (Ws - 1), 3), (B, 2))
+        kinds = (torch.float32, torch.float32, torch.uint8, torch.int32, torch.int32)
+        for t, shape, kind in zip(out, want, kinds):
+            if tuple(t.shape) != shape or t.dtype != kind or not t.is_cuda or not t.is_contiguous():
+                raise DpfError('depth_mesh: an output buffer %s %s is not the contiguous %s %s the shape asks for'
+                               % (tuple(t.shape), t.dtype, shape, kind))
+        vertices, vnormals, vcolours, faces, counts = out
+        norm = _host_floats(tuple(IMAGENET_MEAN) + tuple(IMAGENET_STD))
+        lib().call('dpf_depth_mesh', *head[:6], _ptr(nmap), _ptr(view), norm, *head[6:9], stride, head[9], head[10], float(max_edge_ratio),
+                   int(bool(towards_camera)), _ptr(ws), nbytes, _ptr(vertices), _ptr(vnormals), _ptr(vcolours), _ptr(faces), _ptr(counts),
+                   _stream())
+    return vertices, vnormals, vcolours, faces, counts
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-5, gscale=1.0):
     _need(param, grad, exp_avg, exp_avg_sq)
     lib().call('dpf_adam_step', _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), int(step), float(lr), float(beta1),

@@ -29,6 +29,7 @@ import torch
 
 from . import distributed as dd
 from . import optim
+from . import reconstruct
 
 
 def epoch_lr(option, epoch):
@@ -173,8 +174,13 @@ class Trainer(object):
         """One pass over ``loader`` in deferred metric mode (selectors.metric_selector): no host read per batch, one flush before the
         epoch-end hook.  On all ranks: rank r takes the batches r, r + world, ... of the same loader order, then ONE all-reduce per
         benchmark of (sum of its rows, its batch count) -- issued by every rank whatever it counted, a rank without a batch adds zeros --
-        and every rank returns the mean over all batches of the per-batch rows, the figure a single process logs."""
+        and every rank returns the mean over all batches of the per-batch rows, the figure a single process logs.
+        A test pass with option.reconstruct.write_ply on also writes the mesh of every sample it evaluates to
+        <output_path or workspace_path/output>/recon/<loader position>_<sample>.ply (self.written_meshes lists them); validation during fit
+        writes nothing."""
         device = model.flat_parameters().device
+        write = test and reconstruct.settings(self.option).write_ply
+        self.written_meshes = []
         sel = model.metric_model
         share = self.validates_on_all_ranks()
         model.eval()
@@ -185,7 +191,11 @@ class Trainer(object):
                 if share and i % self.world_size != self.rank:
                     continue
                 batch = self._to_device(batch, device)
-                outputs.append(None if (model.test_step if test else model.validation_step)(batch, i) is None else i)
+                results = (model.test_step if test else model.validation_step)(batch, i)
+                outputs.append(None if results is None else i)
+                if write and results is not None:
+                    guide = model._views(batch)[0] if hasattr(model, '_views') else None
+                    self.written_meshes += reconstruct.write_batch(self.option, self.workspace_path, i, results, batch, guide)
                 self.validated_batches.append(i)
         sel.flush()
         (model.test_epoch_end if test else model.validation_epoch_end)(outputs)

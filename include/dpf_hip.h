@@ -558,6 +558,48 @@ int dpf_guided_filter(const float* p, long long p_batch_stride, const float* gui
 int dpf_joint_bilateral_filter(const float* p, long long p_batch_stride, const float* guide_rgb, int B, int n, int H, int W, int r,
                                double sigma_space, double sigma_color, const float* norm_host, float* q, void* stream);
 
+/* ---- camera-space surface of a prediction (csrc/reconstruct.hip; option key reconstruct, dualpixelface_amd/reconstruct.py).  The
+ * reference defines none of it: the definitions are this project's.  Shared operands: pred, head 0 of a prediction as
+ * an H W plane per sample, pred_batch_stride floats apart; target_type 0 = disp, 1 = idepth, 2 = depth; ab [B, 2] fp32 = [b, a] (may be
+ * NULL for target type 2); Kmat [B, 3, 3] fp32; mask [B, H, W] fp32 or NULL, valid where mask > 0; 0 <= z_near < z_far, z_far = +inf for
+ * no limit.
+ *   depth     z = a / (pred - b) (types 0, 1) or pred (type 2), fp32, non-finite -> 0
+ *   valid     z finite, z_near < z < z_far, mask NULL or > 0, K regular
+ *   rays      r(x, y) = Kinv [x, y, 1], x = 0..W-1, y = 0..H-1; Kinv = adjugate / det in fp64 from the fp32 K, rounded to fp32 once;
+ *             |det| < 1e-30 makes every pixel of the sample invalid
+ *   connected two neighbours are, iff both are valid and |z_p - z_q| <= max_edge_ratio * min(z_p, z_q)
+ * dpf_backproject: points [B, 3, H, W] = z r (0 where invalid), valid [B, H, W] uint8.
+ * dpf_depth_normals: normal [B, 3, H, W], normal_valid [B, H, W] uint8 from the depth alone (a tile with a 1-pixel halo; stored points are
+ * never read).  Step from p to q, q right of p by D columns: (z_q - z_p) r_q + z_p D Kinv[:, 0]; rows below use Kinv[:, 1].  Per axis the
+ * central step (D = 2) where the centre is connected to both neighbours, else the one-sided step to the single connected one (D = 1,
+ * oriented left -> right / up -> down), else none.  n = normalize(cross(d_row, d_col)), negated to face the camera (n . P <= 0) when
+ * towards_camera, away from it otherwise; (0, 0, 0) and normal_valid 0 where the pixel is invalid, an axis has no step or the cross
+ * product has no length.
+ * dpf_depth_mesh: stride s in {1, 2, 4, 8}; node (i, j) = pixel (i s, j s), Hs = ceil(H / s), Ws = ceil(W / s).  Vertices: the valid nodes
+ * in row-major order.  Quad (i, j), corners a = (i, j), b = (i, j + 1), c = (i + 1, j), d = (i + 1, j + 1): T0 = (a, c, b) and
+ * T1 = (b, c, d), each emitted iff its three nodes are valid and its three edges connected; quads in row-major order, T0 first; the last
+ * two indices swapped when towards_camera is 0.  Outputs, worst-case sized, entries past the counts untouched: vertices [B, Hs Ws, 3]
+ * fp32, vertex_normals [B, Hs Ws, 3] fp32 gathered from normal_map [B, 3, H, W], vertex_colours [B, Hs Ws, 3] uint8 =
+ * clamp(round(255 (view std + mean)), 0, 255) from the normalised view [B, 3, H, W] and norm_host (six host floats mean[3], std[3], read
+ * during the call), 255 for a NULL view; faces [B, 2 (Hs - 1)(Ws - 1), 3] int32 with sample-local vertex indices; counts [B, 2] int32 =
+ * (vertices, faces).  Four launches: counts per workgroup, one workgroup per sample scanning them in order, vertices, faces.
+ * ws: dpf_depth_mesh_workspace_bytes() bytes of 8-byte aligned device scratch (-1: shape refused); it needs no initialisation.
+ * No floating-point atomics, no workgroup waits for another, nothing allocates or waits on the host: the bits repeat and the calls can be
+ * captured.  Refusals launch nothing: DPF_ERR_INVALID_ARG for a NULL pointer (but mask, view, ab with target type 2, and faces where Hs or Ws is 1), B, H or W <= 0, a
+ * target_type outside 0..2, pred_batch_stride < H W, z_near < 0, z_far <= z_near, max_edge_ratio <= 0, stride < 1, or a workspace that is
+ * too small or misaligned; DPF_ERR_UNSUPPORTED for B > 65535, H W >= 2^31, H beyond 65535 tiles of 8 rows (normals), or a stride that is
+ * not 1, 2, 4 or 8. */
+int dpf_backproject(const float* pred, long long pred_batch_stride, int target_type, const float* ab, const float* Kmat, const float* mask,
+                    int B, int H, int W, float z_near, float z_far, float* points, unsigned char* valid, void* stream);
+int dpf_depth_normals(const float* pred, long long pred_batch_stride, int target_type, const float* ab, const float* Kmat, const float* mask,
+                      int B, int H, int W, float z_near, float z_far, float max_edge_ratio, int towards_camera, float* normal,
+                      unsigned char* normal_valid, void* stream);
+long long dpf_depth_mesh_workspace_bytes(int B, int H, int W, int stride);
+int dpf_depth_mesh(const float* pred, long long pred_batch_stride, int target_type, const float* ab, const float* Kmat, const float* mask,
+                   const float* normal_map, const float* view, const float* norm_host, int B, int H, int W, int stride, float z_near,
+                   float z_far, float max_edge_ratio, int towards_camera, void* ws, long long ws_bytes, float* vertices,
+                   float* vertex_normals, unsigned char* vertex_colours, int* faces, int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

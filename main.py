@@ -4,7 +4,8 @@
 
 builds the layered option object, instantiates the plugin through ``src/model/model_selector.py`` and runs fit / test with the
 native trainer (dualpixelface_amd/trainer.py) instead of pytorch_lightning.  One process per GPU under torchrun.
-``--synthetic N`` replaces the FaceDP loaders by N synthetic samples (no dataset is needed for a smoke run).
+``--synthetic N`` replaces the FaceDP loaders by N synthetic samples (no dataset is needed for a smoke run): N to train on and N // 4 to
+evaluate, or all N to evaluate where the config writes a mesh per sample (reconstruct.write_ply).
 """
 import argparse
 import os
@@ -51,7 +52,9 @@ def main():
     if args.synthetic:
         from dualpixelface_amd.synthetic_data import synthetic_loader
         train_loader = synthetic_loader(args.synthetic, args.height, args.width, opt.batch_size, shuffle=True, seed=1)
-        val_loader = synthetic_loader(max(1, args.synthetic // 4), args.height, args.width, 1, seed=2)
+        from dualpixelface_amd import reconstruct
+        held_out = args.synthetic if reconstruct.settings(opt).write_ply else max(1, args.synthetic // 4)
+        val_loader = synthetic_loader(held_out, args.height, args.width, 1, seed=2)
     if opt.mode == 'train':
         trainer.fit(model, train_loader, val_loader)
     elif opt.mode == 'test':
