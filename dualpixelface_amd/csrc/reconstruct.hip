@@ -18,6 +18,7 @@
 // nearly equal parts cancelled analytically; rows below use Kinv[:, 1].
 // No floating-point atomics, no workgroup waits for another inside a launch, every count in a fixed order: the bits repeat.
 #include "dpf_common.h"
+#include "dpf_geometry.h"      // Cam, cam_setup, ray_of, connected: shared with normal_geo.hip
 #include <math.h>
 
 namespace {
@@ -31,12 +32,6 @@ constexpr int kMaxTileRows = 65535;            // and the normals' tile rows on 
 
 struct Norm { float mean[3], std[3]; };
 
-struct Cam {
-  float inv[9];       // Kinv, row-major
-  float a, b;         // depth = a / (pred - b)
-  int ok;             // K regular
-};
-
 struct Scene {        // the operands backproject, depth_normals and depth_mesh share
   const float* pred;
   long long pstride;
@@ -46,22 +41,6 @@ struct Scene {        // the operands backproject, depth_normals and depth_mesh 
   int target_type, H, W;
   float z_near, z_far;
 };
-
-// one thread per workgroup forms the sample's camera; the caller publishes it with a barrier
-__device__ void cam_setup(const Scene& sc, int s, Cam* cam) {
-  const float* Kf = sc.Kmat + (size_t)s * 9;
-  double m[9];
-  for (int k = 0; k < 9; ++k) m[k] = (double)Kf[k];
-  const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
-  const double det = (m[0] * c00 + m[1] * c01) + m[2] * c02;
-  cam->ok = isfinite(det) && fabs(det) >= 1e-30;
-  const double adj[9] = {c00, m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
-                         c01, m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
-                         c02, m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]};
-  for (int k = 0; k < 9; ++k) cam->inv[k] = cam->ok ? (float)(adj[k] / det) : 0.f;
-  cam->b = sc.target_type == 2 ? 0.f : sc.ab[2 * (size_t)s];
-  cam->a = sc.target_type == 2 ? 0.f : sc.ab[2 * (size_t)s + 1];
-}
 
 // the depth of pixel (y, x) of sample s where it is valid, else 0
 __device__ __forceinline__ float valid_depth(const Scene& sc, const Cam& cam, int s, int y, int x) {
@@ -74,21 +53,11 @@ __device__ __forceinline__ float valid_depth(const Scene& sc, const Cam& cam, in
   return ok ? z : 0.f;
 }
 
-__device__ __forceinline__ void ray_of(const Cam& cam, int y, int x, float (&r)[3]) {
-  const float xf = (float)x, yf = (float)y;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) r[k] = (cam.inv[3 * k] * xf + cam.inv[3 * k + 1] * yf) + cam.inv[3 * k + 2];
-}
-
-__device__ __forceinline__ bool connected(float zp, float zq, float ratio) {
-  return zp > 0.f && zq > 0.f && fabsf(zp - zq) <= ratio * fminf(zp, zq);
-}
-
 // grid (blocks, B)
 __global__ __launch_bounds__(256) void backproject_kernel(Scene sc, float* __restrict__ points, unsigned char* __restrict__ valid) {
   __shared__ Cam scam;
   const int s = blockIdx.y;
-  if (threadIdx.x == 0) cam_setup(sc, s, &scam);
+  if (threadIdx.x == 0) cam_setup(sc.Kmat, sc.ab, sc.target_type, s, &scam);
   __syncthreads();
   const Cam cam = scam;
   const long long HW = (long long)sc.H * sc.W;
@@ -130,7 +99,7 @@ __global__ __launch_bounds__(256) void normals_kernel(Scene sc, float ratio, int
   __shared__ Cam scam;
   __shared__ float tile[kTH + 2][kTW + 2];
   const int s = blockIdx.z, t = threadIdx.x;
-  if (t == 0) cam_setup(sc, s, &scam);
+  if (t == 0) cam_setup(sc.Kmat, sc.ab, sc.target_type, s, &scam);
   __syncthreads();
   const Cam cam = scam;
   const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
@@ -222,7 +191,7 @@ __global__ __launch_bounds__(256) void mesh_count_kernel(Scene sc, Grid g, float
   __shared__ Cam scam;
   __shared__ int sm4[4];
   const int s = blockIdx.y;
-  if (threadIdx.x == 0) cam_setup(sc, s, &scam);
+  if (threadIdx.x == 0) cam_setup(sc.Kmat, sc.ab, sc.target_type, s, &scam);
   __syncthreads();
   const Cam cam = scam;
   int packed = 0;                                          // vertices in the low 16 bits (<= 1024 per workgroup), triangles above (<= 2048)
@@ -278,7 +247,7 @@ __global__ __launch_bounds__(256) void mesh_vertex_kernel(Scene sc, Grid g, cons
   __shared__ Cam scam;
   __shared__ int sm4[4];
   const int s = blockIdx.y;
-  if (threadIdx.x == 0) cam_setup(sc, s, &scam);
+  if (threadIdx.x == 0) cam_setup(sc.Kmat, sc.ab, sc.target_type, s, &scam);
   __syncthreads();
   const Cam cam = scam;
   const int n0 = blockIdx.x * kNodes + threadIdx.x * kPerThread;
@@ -333,7 +302,7 @@ __global__ __launch_bounds__(256) void mesh_face_kernel(Scene sc, Grid g, float 
   __shared__ Cam scam;
   __shared__ int sm4[4];
   const int s = blockIdx.y;
-  if (threadIdx.x == 0) cam_setup(sc, s, &scam);
+  if (threadIdx.x == 0) cam_setup(sc.Kmat, sc.ab, sc.target_type, s, &scam);
   __syncthreads();
   const Cam cam = scam;
   const int n0 = blockIdx.x * kNodes + threadIdx.x * kPerThread;

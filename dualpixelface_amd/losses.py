@@ -5,7 +5,7 @@ Class names follow the reference's lookup rule ``<NAME.upper()>Loss`` (loss_sele
 """
 import torch
 
-from . import ops
+from . import normal_geo, ops
 
 
 TARGET_TYPES = ('disp', 'depth', 'idepth')
@@ -108,7 +108,35 @@ class COSINELoss(object):
         return {'loss': out[1]}
 
 
-_BANK = {'smoothL1': SMOOTHL1Loss, 'silog': SILOGLoss, 'cosine': COSINELoss}
+class NORMAL_GEOLoss(_DepthLoss):
+    """The geometric-normal loss (not in the reference; DESIGN.md section 7, csrc/normal_geo.hip): the normals of the depth every head of
+    pred_depth predicts against batch['normal'], the gradient going back into pred_depth.  Settings: the model config block normal_geo
+    (normal_geo.settings).  The conversion is the depth losses': batch['abvalue'], else the fit."""
+
+    def __init__(self, option):
+        super(NORMAL_GEOLoss, self).__init__(option)
+        self.settings = normal_geo.settings(option)
+
+    def forward(self, preds, batch, target_type='disp'):
+        assert target_type in TARGET_TYPES
+        for key in ('K', 'depth', 'normal'):
+            if key not in batch:
+                raise NotImplementedError("the 'normal_geo' loss needs batch[%r], which is missing from the batch" % key)
+        pd = preds['pred_depth']
+        out, ab = {}, None
+        if target_type != 'depth':
+            ab = out['abvalue'] = _fit(preds, batch) if takes_least_square(batch) else batch['abvalue']
+        elif 'abvalue' in batch:
+            out['abvalue'] = batch['abvalue']              # (a depth prediction needs no conversion; handed on as the depth losses do)
+        s = self.settings
+        out['loss'] = ops.normal_geo_loss(pd, batch['depth'], batch['normal'], batch['K'], ab=ab, mask=batch.get('mask'),
+                                          head_weights=self.head_weights(pd.shape[1]), target_type=target_type,
+                                          max_edge_ratio=s.max_edge_ratio, step=s.step, towards_camera=s.towards_camera,
+                                          target_signs=s.target_signs)
+        return out
+
+
+_BANK = {'smoothL1': SMOOTHL1Loss, 'silog': SILOGLoss, 'cosine': COSINELoss, 'normal_geo': NORMAL_GEOLoss}
 
 
 class loss_selector(object):

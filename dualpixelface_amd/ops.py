@@ -1919,6 +1919,90 @@ def depth_mesh(pred, Kmat, normal_map, ab=None, mask=None, view=None, target_typ
     return vertices, vnormals, vcolours, faces, counts
 
 
+NORMAL_GEO_STEPS = (1, 2, 4)
+NORMAL_GEO_STATS = 16       # doubles the forward leaves for the backward: count per head [0, 8), term sum per head [8, 16)
+
+
+class NormalGeoFn(torch.autograd.Function):
+    """The geometric-normal loss (csrc/normal_geo.hip) -> 0-dim loss (and, for tests and tools, the normals and the counted map).  Like
+    DepthLossFn: workspace and stats are fresh tensors, gout is read on the device and nothing is read on the host, so the call is
+    capturable inside the train-step graph.  Only pred receives a gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, depth, normal, Kmat, ab, mask, cfg, return_normals):
+        B, n, H, W = pred.shape
+        ws, nbytes = _workspace('dpf_normal_geo_workspace_bytes', 'normal_geo_loss: shape B=%d n=%d H=%d W=%d is not supported', B, n, H, W,
+                                device=pred.device)
+        stats = torch.empty(NORMAL_GEO_STATS, dtype=torch.float64, device=pred.device)
+        out = torch.empty((), dtype=torch.float32, device=pred.device)
+        nrm = cnt = None
+        if return_normals:
+            nrm = torch.empty((B, n, 3, H, W), dtype=torch.float32, device=pred.device)
+            cnt = torch.empty((B, n, H, W), dtype=torch.uint8, device=pred.device)
+        target_type, ratio, step, towards, signs, weights = cfg
+        lib().call('dpf_normal_geo_forward', _ptr(pred), _ptr(depth), _ptr(normal), _ptr(Kmat), _ptr(ab), _ptr(mask), B, n, H, W, target_type,
+                   ratio, step, towards, _host_floats(signs), _host_floats(weights), _ptr(ws), nbytes, _ptr(stats), _ptr(out), _ptr(nrm),
+                   _ptr(cnt), _stream())
+        ctx.save_for_backward(pred, depth, normal, Kmat, ab, mask, stats)
+        ctx.cfg = cfg
+        if return_normals:
+            ctx.mark_non_differentiable(nrm, cnt)
+            return out, nrm, cnt
+        return out
+
+    @staticmethod
+    def backward(ctx, gout, *unused):
+        pred, depth, normal, Kmat, ab, mask, stats = ctx.saved_tensors
+        target_type, ratio, step, towards, signs, weights = ctx.cfg
+        gout = _c(gout)
+        _need(gout)
+        B, n, H, W = pred.shape
+        dpred = torch.empty_like(pred)
+        lib().call('dpf_normal_geo_backward', _ptr(pred), _ptr(depth), _ptr(normal), _ptr(Kmat), _ptr(ab), _ptr(mask), B, n, H, W, target_type,
+                   ratio, step, towards, _host_floats(signs), _host_floats(weights), _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
+        return dpred, None, None, None, None, None, None, None
+
+
+def normal_geo_loss(pred, depth, normal, Kmat, ab=None, mask=None, head_weights=(1.0,), target_type='disp', max_edge_ratio=0.01, step=1,
+                    towards_camera=True, target_signs=(1, 1, 1), return_normals=False):
+    """csrc/normal_geo.hip: the normals of the depth every head of pred [B, n <= 8, H, W] predicts against normal [B, 3, H, W] -> the 0-dim
+    loss sum_h w_h mean over the counted pixels of 1 - clamp(n . g^, -1, 1), g = target_signs * normal.  depth
+    [B, H, W] is the target depth: it decides which pixels are usable and which neighbours (`step` = 1, 2 or 4 pixels away) lie on one
+    surface, the predicted depth a / (pred - b) (ab [B, 2] = [b, a]; pred itself for target type 'depth') gives the step vectors.  The
+    gradient reaches pred only.  With return_normals also normal [B, n, 3, H, W] fp32 and counted [B, n, H, W] uint8."""
+    if target_type not in TARGET_TYPES:
+        raise DpfError('normal_geo_loss: target_type must be one of %s, got %r' % (sorted(TARGET_TYPES), target_type))
+    for t in (pred, depth, normal, Kmat, ab, mask):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise DpfError('dualpixelface_amd ops need GPU tensors (no CPU fallback)')
+        if t.dtype != torch.float32:
+            raise DpfError('unsupported dtype %s' % t.dtype)
+    if pred.dim() != 4:
+        raise DpfError('normal_geo_loss: pred %s is not [B, n, H, W]' % (tuple(pred.shape),))
+    B, n, H, W = pred.shape
+    for name, t, shape in (('depth', depth, (B, H, W)), ('normal', normal, (B, 3, H, W)), ('K', Kmat, (B, 3, 3)), ('ab', ab, (B, 2)),
+                           ('mask', mask, (B, H, W))):
+        if t is not None and tuple(t.shape) != shape:
+            raise DpfError('normal_geo_loss: %s %s does not match pred %s (want %s)' % (name, tuple(t.shape), tuple(pred.shape), list(shape)))
+    if ab is None and target_type != 'depth':
+        raise DpfError('normal_geo_loss: target_type %r needs ab [B, 2] = [b, a]' % (target_type,))
+    if len(head_weights) != n:
+        raise DpfError('normal_geo_loss: %d head weights for %d heads' % (len(head_weights), n))
+    if isinstance(step, bool) or not hasattr(step, '__index__') or step.__index__() not in NORMAL_GEO_STEPS:
+        raise DpfError('normal_geo_loss: step must be 1, 2 or 4, got %r' % (step,))
+    signs = tuple(float(v) for v in target_signs)
+    if len(signs) != 3 or any(v not in (1.0, -1.0) for v in signs):
+        raise DpfError('normal_geo_loss: target_signs must be three values of +1 or -1, got %r' % (target_signs,))
+    if not float(max_edge_ratio) > 0:
+        raise DpfError('normal_geo_loss: max_edge_ratio must be positive, got %r' % (max_edge_ratio,))
+    cfg = (TARGET_TYPES[target_type], float(max_edge_ratio), step.__index__(), int(bool(towards_camera)), signs,
+           tuple(float(w) for w in head_weights))
+    held = [None if t is None else _c(t.detach()) for t in (depth, normal, Kmat, None if target_type == 'depth' else ab, mask)]
+    return NormalGeoFn.apply(_c(pred), held[0], held[1], held[2], held[3], held[4], cfg, bool(return_normals))
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-5, gscale=1.0):
     _need(param, grad, exp_avg, exp_avg_sq)
     lib().call('dpf_adam_step', _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), int(step), float(lr), float(beta1),

@@ -600,6 +600,46 @@ int dpf_depth_mesh(const float* pred, long long pred_batch_stride, int target_ty
                    float z_far, float max_edge_ratio, int towards_camera, void* ws, long long ws_bytes, float* vertices,
                    float* vertex_normals, unsigned char* vertex_colours, int* faces, int* counts, void* stream);
 
+/* ---- geometric-normal loss (csrc/normal_geo.hip; loss_type 'normal_geo', dualpixelface_amd/losses.py): the normals
+ * of the PREDICTED depth against target normals, and the gradient into the prediction.  The geometry is the surface export's above
+ * (rays, Kinv, connected; csrc/dpf_geometry.h).  pred [B, n <= 8, H, W]; depth [B, H, W], the target depth z_t; normal [B, 3, H, W];
+ * Kmat [B, 3, 3]; ab [B, 2] = [b, a] (NULL allowed for target type 2); mask [B, H, W] or NULL; target_signs_host: three host floats,
+ * each +1 or -1; head_weights_host: n host floats; both read during the call.
+ *   z_p      a / (pred - b) (types 0, 1) or pred (type 2), non-finite -> 0
+ *   usable   z_t finite and > 0, mask NULL or > 0, z_p > 0, K regular
+ *   stencil  neighbours `step` (1, 2 or 4) pixels away.  Two of them are connected iff both are usable and
+ *            |z_t(p) - z_t(q)| <= max_edge_ratio min(z_t(p), z_t(q)): the structure comes from the TARGET.  Per axis the central step
+ *            (D = 2 step) where the centre is connected to both neighbours, else the one-sided one (D = step, left -> right / up -> down),
+ *            else none; the step vector (z_to - z_from) r_to + (z_from D) Kinv[:, axis] is formed with the PREDICTED depths
+ *   n        normalize(cross(d_row, d_col)), negated so that n . (z_p r) <= 0 when towards_camera (>= 0 otherwise)
+ *   g^       g / |g|, g = target_signs * normal
+ *   counted  usable, a step on both axes, |cross| > 0 and finite, |g| > 1e-6 and finite
+ *   loss     sum_h w_h (sum over the counted pixels of head h of 1 - clamp(n . g^, -1, 1)) / count_h, count_h over the whole batch; a head
+ *            with count_h = 0 adds 0
+ * dpf_normal_geo_forward: out[0] = the loss (fp32), stats = 16 doubles: count_h [0, 8), the term sum of head h [8, 16).  normal_out
+ * [B, n, 3, H, W] fp32 (0 where not counted) and counted_out [B, n, H, W] uint8: both NULL or both given.  Two launches: one workgroup per
+ * 32 x 8 tile leaves (term sum, count) in ws, one workgroup folds the rows head by head.  ws: dpf_normal_geo_workspace_bytes() bytes of
+ * 8-byte aligned device scratch (-1: shape refused); it needs no initialisation.
+ * dpf_normal_geo_backward: dpred [B, n, H, W], EVERY element written (0 where nothing contributes or the pixel is not usable) =
+ * gout[0] (a device float) * d loss / d pred.  Validity, connectivity, the choice of step and the orientation sign are constants; the
+ * clamp passes the gradient on [-1, 1]; nothing flows to ab, K, depth or normal.  One launch, a gather: each workgroup recomputes the
+ * centres of its tile and of a halo of `step` around it from depths with a halo of 2 step and sums per pixel in the fixed order centre,
+ * left, right, up, down.  It needs the forward's stats and no scratch.
+ * No floating-point atomics, no workgroup waits for another, nothing allocates or waits on the host: the bits repeat and the calls can be
+ * captured.  Refusals launch nothing: DPF_ERR_INVALID_ARG for a NULL pointer (but mask, ab with target type 2, and the optional output
+ * pair), B, H or W <= 0, n outside 1..8, a target_type outside 0..2, max_edge_ratio <= 0, step < 1, a sign that is not +-1, or a workspace
+ * that is too small or misaligned; DPF_ERR_UNSUPPORTED for B n > 65535, H W >= 2^31, H beyond 65535 tiles of 8 rows, or a step that is not
+ * 1, 2 or 4. */
+long long dpf_normal_geo_workspace_bytes(int B, int n, int H, int W);
+int dpf_normal_geo_forward(const float* pred, const float* depth, const float* normal, const float* Kmat, const float* ab, const float* mask,
+                           int B, int n, int H, int W, int target_type, float max_edge_ratio, int step, int towards_camera,
+                           const float* target_signs_host, const float* head_weights_host, void* ws, long long ws_bytes, double* stats,
+                           float* out, float* normal_out, unsigned char* counted_out, void* stream);
+int dpf_normal_geo_backward(const float* pred, const float* depth, const float* normal, const float* Kmat, const float* ab, const float* mask,
+                            int B, int n, int H, int W, int target_type, float max_edge_ratio, int step, int towards_camera,
+                            const float* target_signs_host, const float* head_weights_host, const double* stats, const float* gout,
+                            float* dpred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
