@@ -164,34 +164,21 @@ int dpf_conv_forward_stats(const float* x, const float* w, const float* bias, fl
   return rc;
 }
 
-// Transposed convolution (below) with out += result when accumulate != 0: the data gradients of several convolutions that read the same tensor
-// (the three dilated branches of a DPBlock, modules.py:43-45) are summed in the kernel epilogue instead of by separate add passes.
-// DPF_ERR_UNSUPPORTED (nothing written) when the shape would not run on the LDS-DMA kernel: compute into a temporary and add.
-int dpf_conv_transpose_acc(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
-                           int K, int Ktot, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
-                           int dd, int dh, int dw, int accumulate, void* stream) {
+// Transposed convolution.  x [N,C,ID,IH,IW] lives on the strided (small) grid, out [N,Ktot,OD,OH,OW] on the dense grid;
+// (OD,OH,OW) are given by the caller (output_padding ambiguity).  w is [C][Ktot][T] in memory: a forward-conv weight
+// [C(x chans = conv out), Ktot(out chans = conv in), T] when this call is that conv's data gradient, or an nn.ConvTranspose3d weight
+// [C_in = C, C_out = Ktot, T].  Only the first K <= Ktot output channels are computed, the others are left untouched: data gradients
+// whose trailing input channels have no consumer (the constant XYZ channels of the ANM volume).
+// accumulate != 0: out += result -- the data gradients of several convolutions that read the same tensor (the three dilated branches of
+// a DPBlock, modules.py:43-45) are summed in the kernel epilogue instead of by separate add passes.  DPF_ERR_UNSUPPORTED (nothing
+// written) when the shape would not run on the LDS-DMA kernel: compute into a temporary and add.
+int dpf_conv_transpose(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
+                       int K, int Ktot, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
+                       int dd, int dh, int dw, int accumulate, void* stream) {
   dpf_clear_error();
   if (bad_args(x, w, out, N, C, K) || !ws || Ktot < K) return DPF_ERR_INVALID_ARG;
   const DpfConvDesc d = transposed_desc(N, C, ID, IH, IW, K, Ktot, OD, OH, OW, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw, accumulate ? 1 : 0);
   return conv_dispatch(x, w, bias, out, ws, d, nullptr, (hipStream_t)stream);
-}
-
-// Transposed convolution.  x [N,C,ID,IH,IW] lives on the strided (small) grid, out [N,K,OD,OH,OW] on the dense grid;
-// (OD,OH,OW) are given by the caller (output_padding ambiguity).  `w_is_conv_layout` = 1: w is a forward-conv weight
-// [C(x chans = conv out), K(out chans = conv in), T] and this call is that conv's data gradient;
-// = 0: w is an nn.ConvTranspose3d weight [C_in = C, C_out = K, T].  Both are [C][K][T] in memory.
-int dpf_conv_transpose(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
-                       int K, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
-                       int dd, int dh, int dw, void* stream) {
-  return dpf_conv_transpose_acc(x, w, bias, out, ws, N, C, ID, IH, IW, K, K, OD, OH, OW, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw, 0, stream);
-}
-
-// As dpf_conv_transpose for an output tensor (and weight) of Ktot channels of which only the first K are computed (the others
-// are left untouched): data gradients whose trailing input channels have no consumer (the constant XYZ channels of the ANM volume).
-int dpf_conv_transpose_ex(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
-                          int K, int Ktot, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
-                          int dd, int dh, int dw, void* stream) {
-  return dpf_conv_transpose_acc(x, w, bias, out, ws, N, C, ID, IH, IW, K, Ktot, OD, OH, OW, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw, 0, stream);
 }
 
 long long dpf_conv_wgrad_workspace_floats(int T, int C, int K) {
@@ -202,7 +189,8 @@ long long dpf_conv_wgrad_workspace_floats(int T, int C, int K) {
 
 // dW[K][C][T] = (accumulate: +=) sum g[n,k,q] * x[n,c, q*s - p + t*dil]; g [N,K,QD,QH,QW] on the small grid, x [N,C,ID,IH,IW] on the dense
 // grid.  With caller scratch (dpf_conv_wgrad_workspace_floats floats) eligible shapes run the kernels with a deterministic slab reduction
-// (conv_pointwise.hip, conv_wide.hip, conv_wgrad2.hip) instead of float atomics.
+// (conv_pointwise.hip, conv_wide.hip, conv_wgrad2.hip) instead of float atomics; ws == NULL: every shape runs the
+// first-generation kernel (float atomics into a dw that is cleared here unless `accumulate`).
 int dpf_conv_wgrad_ws(const float* g, const float* x, float* dw, float* ws, long long ws_floats, int N, int C, int ID, int IH, int IW, int K,
                       int QD, int QH, int QW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw_,
                       int accumulate, void* stream) {
@@ -210,12 +198,6 @@ int dpf_conv_wgrad_ws(const float* g, const float* x, float* dw, float* ws, long
   if (bad_args(g, x, dw, N, C, K)) return DPF_ERR_INVALID_ARG;
   const DpfWgradDesc d{N, C, K, K, 0, ID, IH, IW, QD, QH, QW, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw_};
   return wgrad_dispatch(g, x, dw, ws, ws_floats, d, accumulate, (hipStream_t)stream);
-}
-
-// dW += ... without scratch (dw must be zero-initialised or hold the running gradient): the first-generation kernel
-int dpf_conv_wgrad(const float* g, const float* x, float* dw, int N, int C, int ID, int IH, int IW, int K, int QD, int QH, int QW,
-                   int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw_, void* stream) {
-  return dpf_conv_wgrad_ws(g, x, dw, nullptr, 0, N, C, ID, IH, IW, K, QD, QH, QW, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw_, 1, stream);
 }
 
 }  // extern "C"

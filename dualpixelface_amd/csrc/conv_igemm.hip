@@ -7,7 +7,7 @@
 //   dpf_conv_forward   out[n,k,o] = bias[k] + sum_{c,t} W[k,c,t] * x[n,c, o*s - p + t*dil]
 //   dpf_conv_transpose out[n,k,o] = bias[k] + sum_{c,t} W'[c,k,t] * x[n,c, (o + p - t*dil)/s]   (exact division only)
 //                      (= data gradient of the forward conv, and nn.ConvTranspose3d's forward)
-//   dpf_conv_wgrad     dW[k,c,t] += sum_{n,q} g[n,k,q] * x[n,c, q*s - p + t*dil]
+//   dpf_conv_wgrad_ws  dW[k,c,t] += sum_{n,q} g[n,k,q] * x[n,c, q*s - p + t*dil]
 //
 // Mapping (MI355X-first, not a cuDNN/CUDA tiling): v_mfma_f32_32x32x2_f32, exact f32 (bitwise an
 // fmaf chain) at the f32 vector peak.  D[row = out channel][col = position]: the weight fragment is

@@ -1,11 +1,11 @@
 // Dual-pixel cost-volume construction.
 //
-//   dpf_shift_triple_{forward,backward}, dpf_shift_copies_*: the M <= 3 row-shifted copies of a feature map (the enabled
+//   dpf_shift_copies_{forward,backward_gather}: the M <= 3 row-shifted copies of a feature map (the enabled
 //     ones of nearest / bilinear / Fourier-phase) that subpixel_shift.forward produces (src/module/asm/asm.py:87-127), expressed
 //     as a table-driven separable 2x2-tap sampler: out[b,c,m,y,x] = sum_{a,e} wy[m][a][y] * wx[m][e][x] *
 //     fea[b,c, iy[m][a][y], ix[m][e][x]].  The host builds the tables with the reference's own float32 op
 //     order (grid normalisation quirks Q2, un-keyed grid cache Q1); an integer phase shift is a row roll.
-//   dpf_cv_select_{forward,backward}, dpf_cv_select_m_*: MaskingAttention's tail (asm.py:162-171): softmax over the M copies of
+//   dpf_cv_select_{forward,backward}: MaskingAttention's tail (asm.py:162-171): softmax over the M copies of
 //     the activated mask, weighted mean (feature_fetch: the variance), written straight into every cost-volume level that shares this shift
 //     (CostVolume.build_concat_volume, src/model/stereodpnet/modules.py:181-197).
 //   dpf_psm_volume_forward: PSMNet's integer-shift concat / group-wise-correlation volume
@@ -74,34 +74,6 @@ __global__ __launch_bounds__(256) void shift_triple_fwd_kernel(const float* __re
       *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     } else {
       for (int j = 0; j < 4 && x + j < w; ++j) o[j] = acc[j];
-    }
-  }
-}
-
-// adjoint: dfea (pre-zeroed) += scatter of g[B,C,3,h,w]
-__global__ void shift_triple_bwd_kernel(const float* __restrict__ g, float* __restrict__ dfea, const int* __restrict__ iy,
-                                        const float* __restrict__ wy, const int* __restrict__ ix, const float* __restrict__ wx,
-                                        long long BC, int h, int w) {
-  const long long total = BC * 3 * h * w;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int x = (int)(i % w);
-    const int y = (int)((i / w) % h);
-    const int m = (int)((i / ((long long)w * h)) % 3);
-    const long long bc = i / ((long long)w * h * 3);
-    float* dst = dfea + bc * h * w;
-    const float gv = g[i];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const int yy = iy[(m * 2 + a) * h + y];
-      if (yy < 0) continue;
-      const float wa = wy[(m * 2 + a) * h + y];
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int xx = ix[(m * 2 + e) * w + x];
-        if (xx < 0) continue;
-        const float wgt = wa * wx[(m * 2 + e) * w + x];
-        if (wgt != 0.f) atomicAdd(&dst[(long long)yy * w + xx], wgt * gv);
-      }
     }
   }
 }
@@ -544,22 +516,6 @@ int dpf_shift_copies_forward(const float* fea, float* out, const int* iy, const 
   return dpf_check_launch();
 }
 
-int dpf_shift_triple_forward(const float* fea, float* out, const int* iy, const float* wy, const int* ix, const float* wx, int B, int C,
-                             int h, int w, void* stream) {
-  return dpf_shift_copies_forward(fea, out, iy, wy, ix, wx, B, C, 3, h, w, stream);
-}
-
-int dpf_shift_triple_backward(const float* g, float* dfea, const int* iy, const float* wy, const int* ix, const float* wx, int B, int C,
-                              int h, int w, void* stream) {
-  dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
-  if (!g || !dfea || !iy || !wy || !ix || !wx || B <= 0 || C <= 0 || h <= 0 || w <= 0) return DPF_ERR_INVALID_ARG;
-  const long long BC = (long long)B * C;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(dfea, 0, sizeof(float) * (size_t)BC * h * w, st) != hipSuccess) return DPF_ERR_LAUNCH;
-  hipLaunchKernelGGL(shift_triple_bwd_kernel, dim3(dpf_ew_grid(BC * 3 * h * w)), dim3(256), 0, st, g, dfea, iy, wy, ix, wx, BC, h, w);
-  return dpf_check_launch();
-}
-
 int dpf_shift_copies_backward_gather(const float* g, float* dfea, const int* iy_inv, const float* wy, const int* ix_inv, const float* wx,
                                      int B, int C, int M, int h, int w, void* stream) {
   dpf_clear_error();
@@ -573,11 +529,6 @@ int dpf_shift_copies_backward_gather(const float* g, float* dfea, const int* iy_
 #undef DPF_CALL
   }
   return dpf_check_launch();
-}
-
-int dpf_shift_triple_backward_gather(const float* g, float* dfea, const int* iy_inv, const float* wy, const int* ix_inv, const float* wx,
-                                     int B, int C, int h, int w, void* stream) {
-  return dpf_shift_copies_backward_gather(g, dfea, iy_inv, wy, ix_inv, wx, B, C, 3, h, w, stream);
 }
 
 int dpf_phase_shift(const float* src, long long src_plane_stride, float* dst, long long dst_plane_stride, const float* mr, const float* hm,
@@ -620,7 +571,7 @@ int dpf_phase_shift(const float* src, long long src_plane_stride, float* dst, lo
     else hipLaunchKernelGGL((KERNEL<1, true>), grid_, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);                                    \
   } while (0)
 
-int dpf_cv_select_m_forward(const float* x, const float* s, float* vol, int B, int C, int M, int h, int w, int CV, int L, int choff,
+int dpf_cv_select_forward(const float* x, const float* s, float* vol, int B, int C, int M, int h, int w, int CV, int L, int choff,
                             unsigned levels, int fetch, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   if (!x || !s || !vol || B <= 0 || C <= 0 || M < 1 || M > 3 || h <= 0 || w <= 0 || L <= 0 || L > 32 || choff < 0 || choff + C > CV)
@@ -629,7 +580,7 @@ int dpf_cv_select_m_forward(const float* x, const float* s, float* vol, int B, i
   return dpf_check_launch();
 }
 
-int dpf_cv_select_m_backward(const float* x, const float* s, const float* dvol, float* dx, float* ds, int B, int C, int M, int h, int w,
+int dpf_cv_select_backward(const float* x, const float* s, const float* dvol, float* dx, float* ds, int B, int C, int M, int h, int w,
                              int CV, int L, int choff, unsigned levels, int fetch, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   if (!x || !s || !dvol || !dx || !ds || B <= 0 || C <= 0 || M < 1 || M > 3 || h <= 0 || w <= 0 || L <= 0 || L > 32 || choff < 0 ||
@@ -639,24 +590,6 @@ int dpf_cv_select_m_backward(const float* x, const float* s, const float* dvol, 
   return dpf_check_launch();
 }
 #undef DPF_CV_DISPATCH
-
-int dpf_cv_select_forward(const float* x3, const float* s, float* vol, int B, int C, int h, int w, int CV, int L, int choff,
-                          unsigned levels, void* stream) {
-  dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
-  if (!x3 || !s || !vol || B <= 0 || C <= 0 || L <= 0 || L > 32 || choff < 0 || choff + C > CV) return DPF_ERR_INVALID_ARG;
-  hipLaunchKernelGGL((cv_select_fwd_kernel<3, false>), dim3(dpf_ew_grid((long long)B * C * h * w)), dim3(256), 0, (hipStream_t)stream, x3, s,
-                     vol, B, C, h, w, CV, L, choff, levels);
-  return dpf_check_launch();
-}
-
-int dpf_cv_select_backward(const float* x3, const float* s, const float* dvol, float* dx3, float* ds, int B, int C, int h, int w, int CV,
-                           int L, int choff, unsigned levels, void* stream) {
-  dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
-  if (!x3 || !s || !dvol || !dx3 || !ds || B <= 0 || C <= 0 || L <= 0 || L > 32 || choff < 0 || choff + C > CV) return DPF_ERR_INVALID_ARG;
-  hipLaunchKernelGGL((cv_select_bwd_kernel<3, false>), dim3(dpf_ew_grid((long long)B * C * h * w)), dim3(256), 0, (hipStream_t)stream, x3, s,
-                     dvol, dx3, ds, B, C, h, w, CV, L, choff, levels);
-  return dpf_check_launch();
-}
 
 // shifts: L host ints (int(costrange[l]) truncated toward zero by the caller); groups = 0 -> 'psmnet', > 0 -> 'gwcnet'
 int dpf_psm_volume_forward(const float* ref, const float* tar, float* vol, const int* shifts_host, int B, int C, int h, int w, int L,

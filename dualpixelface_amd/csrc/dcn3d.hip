@@ -1923,10 +1923,10 @@ int dpf_deform_conv3d_forward(const float* input, const float* weight, const flo
 // Grouping as in the forward (grad_weight is [K][C/group][T], grad_offset [B][deformable_group * 3T][P]); grad_input_channels counts whole-tensor
 // channels whatever group they are in.  A grouped call stores every grad_offset element once (reproducible in every mode); its grad_input and
 // grad_weight merge through float atomics, or in deterministic mode through the same integer shadows as the single-group tiers.
-int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const float* bias, const float* offset, const float* grad_output,
-                                  float* grad_input, float* grad_offset, float* grad_weight, float* grad_bias, float* ws, int B, int C,
-                                  int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd,
-                                  int dh, int dw, int group, int deformable_group, int im2col_step, int grad_input_channels, void* stream) {
+int dpf_deform_conv3d_backward(const float* input, const float* weight, const float* bias, const float* offset, const float* grad_output,
+                               float* grad_input, float* grad_offset, float* grad_weight, float* grad_bias, float* ws, int B, int C,
+                               int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd,
+                               int dh, int dw, int group, int deformable_group, int im2col_step, int grad_input_channels, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   (void)im2col_step; (void)bias;
   if (!input || !weight || !offset || !grad_output || !grad_input || !grad_offset || !grad_weight || !ws) return DPF_ERR_INVALID_ARG;
@@ -1969,14 +1969,6 @@ int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const
     if (rc != DPF_OK) return rc;
   }
   return dpf_check_launch();
-}
-
-int dpf_deform_conv3d_backward(const float* input, const float* weight, const float* bias, const float* offset, const float* grad_output,
-                               float* grad_input, float* grad_offset, float* grad_weight, float* grad_bias, float* ws, int B, int C,
-                               int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd,
-                               int dh, int dw, int group, int deformable_group, int im2col_step, void* stream) {
-  return dpf_deform_conv3d_backward_ex(input, weight, bias, offset, grad_output, grad_input, grad_offset, grad_weight, grad_bias, ws, B, C, D, H,
-                                       W, K, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw, group, deformable_group, im2col_step, C, stream);
 }
 
 }  // extern "C"

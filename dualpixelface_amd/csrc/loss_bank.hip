@@ -3,7 +3,7 @@
 //
 //   dpf_depth_loss_forward    per-workgroup partial sums -> one fold -> the loss (one float) and the stats record of the backward
 //   dpf_depth_loss_backward   one pass that writes every element of d pred (0 under the mask)
-//   dpf_depth_loss_forward_ab / _backward_ab   the same with the target formed from a depth map: the 'least_square' conversion
+//   with ab != NULL both form the target from a depth map: the 'least_square' conversion
 //
 // Per element, in fp32 and in this order (this file is built with -ffp-contract=off):
 //   p~ = T(p) * conf, g~ = target * conf          (the products are skipped without conf)
@@ -18,8 +18,6 @@
 #include "dpf_common.h"
 #include "dpf_reduce.h"
 #include <math.h>
-
-extern "C" long long dpf_depth_loss_workspace_bytes(int B, int H, int W);
 
 namespace {
 
@@ -245,8 +243,18 @@ int prepare(int kind, int transform, const float* pred, const float* target, int
   return DPF_OK;
 }
 
-int forward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, const float* ab, int B, int n,
-            int H, int W, const float* weights, float vf, void* ws, long long ws_bytes, double* stats, float* out, void* stream) {
+}  // namespace
+
+extern "C" {
+
+long long dpf_depth_loss_workspace_bytes(int B, int H, int W) {
+  if (B <= 0 || B > kMaxB || H <= 0 || W <= 0) return -1;
+  return (long long)B * blocks_per_sample((long long)H * W) * kValues * (long long)sizeof(double);
+}
+
+int dpf_depth_loss_forward(int kind, int transform, const float* pred, const float* target, const float* ab, const float* mask,
+                           const float* conf, int B, int n, int H, int W, const float* weights, float vf, void* ws, long long ws_bytes,
+                           double* stats, float* out, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   BankP P;
   const int rc = prepare(kind, transform, pred, target, B, n, H, W, weights, vf, P);
@@ -269,8 +277,9 @@ int forward(int kind, int transform, const float* pred, const float* target, con
   return dpf_check_launch();
 }
 
-int backward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, const float* ab, int B, int n,
-             int H, int W, const float* weights, float vf, const double* stats, const float* gout, float* dpred, void* stream) {
+int dpf_depth_loss_backward(int kind, int transform, const float* pred, const float* target, const float* ab, const float* mask,
+                            const float* conf, int B, int n, int H, int W, const float* weights, float vf, const double* stats,
+                            const float* gout, float* dpred, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   BankP P;
   const int rc = prepare(kind, transform, pred, target, B, n, H, W, weights, vf, P);
@@ -287,42 +296,6 @@ int backward(int kind, int transform, const float* pred, const float* target, co
     else hipLaunchKernelGGL((bank_backward_kernel<KIND_SMOOTHL1, 1>), grid, block, 0, st, pred, target, mask, conf, ab, P, stats, gout, dpred);
   }
   return dpf_check_launch();
-}
-
-}  // namespace
-
-extern "C" {
-
-long long dpf_depth_loss_workspace_bytes(int B, int H, int W) {
-  if (B <= 0 || B > kMaxB || H <= 0 || W <= 0) return -1;
-  return (long long)B * blocks_per_sample((long long)H * W) * kValues * (long long)sizeof(double);
-}
-
-int dpf_depth_loss_forward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, int B,
-                           int n, int H, int W, const float* head_weights_host, float variance_focus, void* ws, long long ws_bytes,
-                           double* stats, float* out, void* stream) {
-  return forward(kind, transform, pred, target, mask, conf, nullptr, B, n, H, W, head_weights_host, variance_focus, ws, ws_bytes, stats, out,
-                 stream);
-}
-
-int dpf_depth_loss_backward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, int B,
-                            int n, int H, int W, const float* head_weights_host, float variance_focus, const double* stats,
-                            const float* gout, float* dpred, void* stream) {
-  return backward(kind, transform, pred, target, mask, conf, nullptr, B, n, H, W, head_weights_host, variance_focus, stats, gout, dpred, stream);
-}
-
-int dpf_depth_loss_forward_ab(int kind, int transform, const float* pred, const float* depth, const float* ab, const float* mask,
-                              const float* conf, int B, int n, int H, int W, const float* head_weights_host, float variance_focus, void* ws,
-                              long long ws_bytes, double* stats, float* out, void* stream) {
-  if (!ab) return DPF_ERR_INVALID_ARG;
-  return forward(kind, transform, pred, depth, mask, conf, ab, B, n, H, W, head_weights_host, variance_focus, ws, ws_bytes, stats, out, stream);
-}
-
-int dpf_depth_loss_backward_ab(int kind, int transform, const float* pred, const float* depth, const float* ab, const float* mask,
-                               const float* conf, int B, int n, int H, int W, const float* head_weights_host, float variance_focus,
-                               const double* stats, const float* gout, float* dpred, void* stream) {
-  if (!ab) return DPF_ERR_INVALID_ARG;
-  return backward(kind, transform, pred, depth, mask, conf, ab, B, n, H, W, head_weights_host, variance_focus, stats, gout, dpred, stream);
 }
 
 }  // extern "C"

@@ -546,25 +546,15 @@ int dpf_bn_eval_stats(const float* running_mean, const float* running_var, int C
 
 // y = act((x-mean)*invstd*w + b + res) + res2 ; mean == NULL -> pure activation/add.  slope: device pointer (PReLU) or NULL
 // (then slope_const is used, LeakyReLU).  w/b are indexed c % wmod (instance norm over a [1, B*C, S] view: wmod = C).
+// y_channels == 0 (with y_c0 == 0): y is the dense [N, C, S].  Otherwise the result goes into the channel slice [y_c0, y_c0 + C) of
+// y [N, y_channels, S]: the normalised branches of a torch.cat(dim=1) are written straight into the concatenated tensor
+// (DPBlock.conv_dilate, src/model/stereodpnet/modules.py:43-45).
 int dpf_norm_act_forward(const float* x, const float* mean, const float* invstd, const float* w, const float* b, int wmod,
-                         const float* res, const float* res2, int act, const float* slope, float slope_const, float* y, int N, int C,
-                         long long S, void* stream) {
+                         const float* res, const float* res2, int act, const float* slope, float slope_const, float* y, int y_channels,
+                         int y_c0, int N, int C, long long S, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   if (!x || !y || N <= 0 || C <= 0 || S <= 0 || (long long)N * C > 65535) return DPF_ERR_INVALID_ARG;
-  if (wmod <= 0) wmod = C;
-#define DPF_CALL(A, R) hipLaunchKernelGGL((bn_apply_kernel<A, R>), row_grid(N * C, S), dim3(256), 0, (hipStream_t)stream, x, mean, invstd, w, b, wmod, res, res2, act, slope, slope_const, y, C, S, 0, 0)
-  DPF_ACT_DISPATCH(act, (res != nullptr || res2 != nullptr), DPF_CALL)
-#undef DPF_CALL
-  return dpf_check_launch();
-}
-
-// dpf_norm_act_forward writing into the channel slice [y_c0, y_c0 + C) of y [N, y_channels, S]: the normalised branches of a
-// torch.cat(dim=1) go straight into the concatenated tensor (DPBlock.conv_dilate, src/model/stereodpnet/modules.py:43-45)
-int dpf_norm_act_forward_slice(const float* x, const float* mean, const float* invstd, const float* w, const float* b, int wmod,
-                               const float* res, const float* res2, int act, const float* slope, float slope_const, float* y, int y_channels,
-                               int y_c0, int N, int C, long long S, void* stream) {
-  dpf_clear_error();
-  if (!x || !y || N <= 0 || C <= 0 || S <= 0 || (long long)N * C > 65535 || y_c0 < 0 || y_c0 + C > y_channels) return DPF_ERR_INVALID_ARG;
+  if (y_channels != 0 ? (y_c0 < 0 || y_c0 + C > y_channels) : y_c0 != 0) return DPF_ERR_INVALID_ARG;
   if (wmod <= 0) wmod = C;
 #define DPF_CALL(A, R) hipLaunchKernelGGL((bn_apply_kernel<A, R>), row_grid(N * C, S), dim3(256), 0, (hipStream_t)stream, x, mean, invstd, w, b, wmod, res, res2, act, slope, slope_const, y, C, S, y_channels, y_c0)
   DPF_ACT_DISPATCH(act, (res != nullptr || res2 != nullptr), DPF_CALL)
@@ -577,12 +567,16 @@ int dpf_norm_act_forward_slice(const float* x, const float* mean, const float* i
 // phase 0: everything.  phase 1: only the per-channel reductions (ws[3c] = sum dz, ws[3c+1] = sum dz*xhat) and the parameter
 // gradients; phase 2: only dx / dres from a ws the caller has summed over the ranks, with count = global N*S (SyncBatchNorm), or
 // count < 0: the global count is read from ws[3*C] (the caller put its local count there before the all-reduce: no host sync).
-static int norm_act_backward_impl(const float* x, const float* dy, int gC, int gc0, const float* mean, const float* invstd, const float* w,
-                                  const float* b, int wmod, const float* res, int act, const float* slope, float slope_const, int training,
-                                  float* dx, float* dres, float* dweight, float* dbias, float* dslope, float* ws, int N, int C, long long S,
-                                  int phase, double count, void* stream) {
+// dy_channels == 0 (with dy_c0 == 0): dy is the dense [N, C, S]; otherwise it is the channel slice [dy_c0, dy_c0 + C) of a
+// [N, dy_channels, S] tensor (the gradient of the concatenation the forward wrote into).
+int dpf_norm_act_backward(const float* x, const float* dy, int dy_channels, int dy_c0, const float* mean, const float* invstd, const float* w,
+                          const float* b, int wmod, const float* res, int act, const float* slope, float slope_const, int training, float* dx,
+                          float* dres, float* dweight, float* dbias, float* dslope, float* ws, int N, int C, long long S, int phase,
+                          double count, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   if (!x || !dy || !ws || N <= 0 || C <= 0 || S <= 0 || (long long)N * C > 65535 || phase < 0 || phase > 3) return DPF_ERR_INVALID_ARG;
+  if (dy_channels != 0 ? (dy_c0 < 0 || dy_c0 + C > dy_channels) : dy_c0 != 0) return DPF_ERR_INVALID_ARG;
+  const int gC = dy_channels, gc0 = dy_c0;
   if (wmod <= 0) wmod = C;
   hipStream_t st = (hipStream_t)stream;
   const bool need_reduce = (mean != nullptr) || (act == DPF_ACT_PRELU && dslope);
@@ -620,42 +614,6 @@ static int norm_act_backward_impl(const float* x, const float* dy, int gC, int g
 #undef DPF_CALL
   }
   return dpf_check_launch();
-}
-
-int dpf_norm_act_backward_ex(const float* x, const float* dy, const float* mean, const float* invstd, const float* w, const float* b,
-                             int wmod, const float* res, int act, const float* slope, float slope_const, int training, float* dx,
-                             float* dres, float* dweight, float* dbias, float* dslope, float* ws, int N, int C, long long S, int phase,
-                             double count, void* stream) {
-  return norm_act_backward_impl(x, dy, 0, 0, mean, invstd, w, b, wmod, res, act, slope, slope_const, training, dx, dres, dweight, dbias,
-                                dslope, ws, N, C, S, phase, count, stream);
-}
-
-// dpf_norm_act_backward with dy given as the channel slice [dy_c0, dy_c0 + C) of a [N, dy_channels, S] tensor (the gradient of
-// the concatenation the forward wrote into)
-int dpf_norm_act_backward_slice(const float* x, const float* dy, int dy_channels, int dy_c0, const float* mean, const float* invstd,
-                                const float* w, const float* b, int wmod, const float* res, int act, const float* slope, float slope_const,
-                                int training, float* dx, float* dres, float* dweight, float* dbias, float* dslope, float* ws, int N, int C,
-                                long long S, void* stream) {
-  if (dy_c0 < 0 || dy_c0 + C > dy_channels) return DPF_ERR_INVALID_ARG;
-  return norm_act_backward_impl(x, dy, dy_channels, dy_c0, mean, invstd, w, b, wmod, res, act, slope, slope_const, training, dx, dres,
-                                dweight, dbias, dslope, ws, N, C, S, 0, 0.0, stream);
-}
-
-// the same with the phases of dpf_norm_act_backward_ex (SyncBatchNorm of a branch that wrote a channel slice of a concatenation)
-int dpf_norm_act_backward_slice_ex(const float* x, const float* dy, int dy_channels, int dy_c0, const float* mean, const float* invstd,
-                                   const float* w, const float* b, int wmod, const float* res, int act, const float* slope, float slope_const,
-                                   int training, float* dx, float* dres, float* dweight, float* dbias, float* dslope, float* ws, int N, int C,
-                                   long long S, int phase, double count, void* stream) {
-  if (dy_c0 < 0 || dy_c0 + C > dy_channels) return DPF_ERR_INVALID_ARG;
-  return norm_act_backward_impl(x, dy, dy_channels, dy_c0, mean, invstd, w, b, wmod, res, act, slope, slope_const, training, dx, dres,
-                                dweight, dbias, dslope, ws, N, C, S, phase, count, stream);
-}
-
-int dpf_norm_act_backward(const float* x, const float* dy, const float* mean, const float* invstd, const float* w, const float* b,
-                          int wmod, const float* res, int act, const float* slope, float slope_const, int training, float* dx,
-                          float* dres, float* dweight, float* dbias, float* dslope, float* ws, int N, int C, long long S, void* stream) {
-  return dpf_norm_act_backward_ex(x, dy, mean, invstd, w, b, wmod, res, act, slope, slope_const, training, dx, dres, dweight, dbias, dslope,
-                                  ws, N, C, S, 0, 0.0, stream);
 }
 
 // out[C] += sum over n, s of g[N,C,S]

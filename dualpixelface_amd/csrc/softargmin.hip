@@ -375,11 +375,17 @@ __global__ __launch_bounds__(256) void head_bwd_8x32_kernel(const float* __restr
 
 extern "C" {
 
-// logits [B,D,h,w] -> pred [B,H,W], prob [B,L,H,W] (NULL to skip).  disp: L host floats (hypothesis values).
-static int softargmin_fwd(const float* logits, float* pred, float* prob, const float* disp_host, int B, int D, int h, int w, int L, int H, int W,
-                          float off, hipStream_t st, long long prob_batch_stride = 0) {
+// logits [B,D,h,w] -> pred [B,H,W], prob [B,L,H,W] (NULL to skip).  disp: L host floats (hypothesis values).  prob_batch_stride (floats):
+// 0 = the dense volume; otherwise head i of n writes slice [:, i] of a [B, n, L, H, W] tensor directly -- the torch.stack of the per-head
+// volumes (modules.py:352-362 + mainmodel.py:98-99) costs no copy.  align_corners = 0 is F.interpolate(scale_factor=4, mode='trilinear',
+// align_corners=False) of src/model/nnet/mainmodel.py:150-153.
+int dpf_softargmin_forward(const float* logits, float* pred, float* prob, long long prob_batch_stride, const float* disp_host, int B, int D,
+                           int h, int w, int L, int H, int W, int align_corners, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   if (!logits || !pred || !disp_host || B <= 0 || D <= 0 || D > MAXD || L <= 0 || L > MAXL) return DPF_ERR_INVALID_ARG;
+  if (prob && prob_batch_stride != 0 && prob_batch_stride < (long long)L * H * W) return DPF_ERR_INVALID_ARG;
+  const float off = align_corners ? 0.f : 0.5f;
+  hipStream_t st = (hipStream_t)stream;
   HeadP p;
   p.B = B; p.D = D; p.h = h; p.w = w; p.L = L; p.H = H; p.W = W; p.off = off; p.pbs = prob_batch_stride;
   for (int i = 0; i < MAXL; ++i) p.disp[i] = i < L ? disp_host[i] : 0.f;
@@ -391,10 +397,12 @@ static int softargmin_fwd(const float* logits, float* pred, float* prob, const f
 }
 
 // d logits [B,D,h,w] (zeroed here) from d pred [B,H,W]
-static int softargmin_bwd(const float* logits, const float* gpred, float* dlogits, const float* disp_host, int B, int D, int h, int w, int L,
-                          int H, int W, float off, hipStream_t st) {
+int dpf_softargmin_backward(const float* logits, const float* gpred, float* dlogits, const float* disp_host, int B, int D, int h, int w,
+                            int L, int H, int W, int align_corners, void* stream) {
   dpf_clear_error();   // drop any stale error left by other runtime users (e.g. PyTorch) in this thread
   if (!logits || !gpred || !dlogits || !disp_host || B <= 0 || D <= 0 || D > MAXD || L <= 0 || L > MAXL) return DPF_ERR_INVALID_ARG;
+  const float off = align_corners ? 0.f : 0.5f;
+  hipStream_t st = (hipStream_t)stream;
   HeadP p;
   p.B = B; p.D = D; p.h = h; p.w = w; p.L = L; p.H = H; p.W = W; p.off = off; p.pbs = 0;
   for (int i = 0; i < MAXL; ++i) p.disp[i] = i < L ? disp_host[i] : 0.f;
@@ -416,33 +424,6 @@ static int softargmin_bwd(const float* logits, const float* gpred, float* dlogit
   else
     hipLaunchKernelGGL(head_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, logits, gpred, dlogits, p, 1, 1, 0, 0);
   return dpf_check_launch();
-}
-
-int dpf_softargmin_forward(const float* logits, float* pred, float* prob, const float* disp_host, int B, int D, int h, int w, int L,
-                           int H, int W, void* stream) {
-  return softargmin_fwd(logits, pred, prob, disp_host, B, D, h, w, L, H, W, 0.f, (hipStream_t)stream);
-}
-int dpf_softargmin_backward(const float* logits, const float* gpred, float* dlogits, const float* disp_host, int B, int D, int h, int w,
-                            int L, int H, int W, void* stream) {
-  return softargmin_bwd(logits, gpred, dlogits, disp_host, B, D, h, w, L, H, W, 0.f, (hipStream_t)stream);
-}
-// the same head with the trilinear upsampling in either convention: align_corners = 0 is F.interpolate(scale_factor=4,
-// mode='trilinear', align_corners=False) of src/model/nnet/mainmodel.py:150-153
-int dpf_softargmin_forward_ex(const float* logits, float* pred, float* prob, const float* disp_host, int B, int D, int h, int w, int L,
-                              int H, int W, int align_corners, void* stream) {
-  return softargmin_fwd(logits, pred, prob, disp_host, B, D, h, w, L, H, W, align_corners ? 0.f : 0.5f, (hipStream_t)stream);
-}
-// forward with the probability volume written at a batch stride (floats): head i of n writes slice [:, i] of a [B, n, L, H, W]
-// tensor directly -- the torch.stack of the per-head volumes (modules.py:352-362 + mainmodel.py:98-99) costs no copy
-int dpf_softargmin_forward_strided(const float* logits, float* pred, float* prob, long long prob_batch_stride, const float* disp_host, int B,
-                                   int D, int h, int w, int L, int H, int W, int align_corners, void* stream) {
-  if (prob && prob_batch_stride < (long long)L * H * W) return DPF_ERR_INVALID_ARG;
-  return softargmin_fwd(logits, pred, prob, disp_host, B, D, h, w, L, H, W, align_corners ? 0.f : 0.5f, (hipStream_t)stream,
-                        prob_batch_stride);
-}
-int dpf_softargmin_backward_ex(const float* logits, const float* gpred, float* dlogits, const float* disp_host, int B, int D, int h, int w,
-                               int L, int H, int W, int align_corners, void* stream) {
-  return softargmin_bwd(logits, gpred, dlogits, disp_host, B, D, h, w, L, H, W, align_corners ? 0.f : 0.5f, (hipStream_t)stream);
 }
 
 }  // extern "C"

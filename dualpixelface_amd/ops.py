@@ -68,20 +68,49 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _need(*ts):
+_F32 = (torch.float32,)
+
+
+def _need(*ts, dtypes=(torch.float32, torch.int32), contiguous=True):
+    """THE operand check: every entry that is not None is a tensor on the GPU with one of `dtypes`, contiguous unless the caller makes
+    it so afterwards (contiguous=False)."""
     for t in ts:
         if t is None:
             continue
-        if not t.is_cuda:
+        if not torch.is_tensor(t) or not t.is_cuda:
             raise DpfError('dualpixelface_amd ops need GPU tensors (no CPU fallback)')
-        if t.dtype != torch.float32 and t.dtype != torch.int32:
+        if t.dtype not in dtypes:
             raise DpfError('unsupported dtype %s' % t.dtype)
-        if not t.is_contiguous():
+        if contiguous and not t.is_contiguous():
             raise DpfError('non-contiguous tensor passed to a HIP op')
 
 
 def _c(t):
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _int_arg(op, name, value, allowed=None):
+    """An integer argument as it is (a bool, a string or a float such as 2.7 is refused, not truncated), one of `allowed` when given."""
+    if not isinstance(value, bool) and hasattr(value, '__index__') and (allowed is None or value.__index__() in allowed):
+        return value.__index__()
+    what = 'an integer' if allowed is None else '%s or %d' % (', '.join(str(v) for v in allowed[:-1]), allowed[-1])
+    raise DpfError('%s: %s must be %s, got %r' % (op, name, what, value))
+
+
+def _match_pred(op, pred, *named):
+    """named: (name, tensor or None, shape) -- every tensor there has that shape, the one pred's shape asks for."""
+    for name, t, shape in named:
+        if t is not None and tuple(t.shape) != tuple(shape):
+            raise DpfError('%s: %s %s does not match pred %s (want %s)' % (op, name, tuple(t.shape), tuple(pred.shape), list(shape)))
+
+
+def _batch_view(pred, min_stride):
+    """(pred, its batch stride in floats) for a kernel that walks the samples of pred [B, ...] through that stride: a slice along dim 0 or
+    1 of a wider tensor is taken as it is, contiguous samples at least min_stride apart; anything else is copied."""
+    B = pred.shape[0]
+    if not (pred[0].is_contiguous() and (B == 1 or pred.stride(0) >= min_stride)):
+        pred = pred.contiguous()
+    return pred, pred.stride(0) if B > 1 else pred[0].numel()
 
 
 def scratch(nfloats, device, tag='ws'):
@@ -287,15 +316,14 @@ def _conv_transpose_raw(x, w, bias, out_dims, ksize, stride, pad, dil, k_needed=
             done = _supported('dpf_conv_smallk_dgrad', _ptr(x), _ptr(w), _ptr(out), N, K, *out_dims, C, kd, kh, kw, *pad, _stream())
         if done:
             return out
+    kc = K                                  # output channels computed
     if k_needed is not None and 0 < k_needed < K:
         out[:, k_needed:].zero_()
-        entry, chans = 'dpf_conv_transpose_ex', (k_needed, K)
-    else:
-        entry, chans = 'dpf_conv_transpose', (K,)
+        kc = k_needed
     ws = _conv_ws(ksize, C, K, x.device)
-    with _dense_timed('tr ', x, chans[0], ksize, stride, dil, ID * IH * IW, x.numel() + out.numel() * chans[0] // K + w.numel()):
-        L.call(entry, _ptr(x), _ptr(w), _ptr(bias), _ptr(out), _ptr(ws), N, C, ID, IH, IW, *chans, *out_dims, kd, kh, kw,
-               *stride, *pad, *dil, _stream())
+    with _dense_timed('tr ', x, kc, ksize, stride, dil, ID * IH * IW, x.numel() + out.numel() * kc // K + w.numel()):
+        L.call('dpf_conv_transpose', _ptr(x), _ptr(w), _ptr(bias), _ptr(out), _ptr(ws), N, C, ID, IH, IW, kc, K, *out_dims, kd, kh, kw,
+               *stride, *pad, *dil, 0, _stream())
     return out
 
 
@@ -709,7 +737,7 @@ class NormActFn(torch.autograd.Function):
             timer.nbytes = 4.0 * x.numel() * (read_x + 2 + (res is not None) + (res2 is not None))
             y = torch.empty_like(x)
             L.call('dpf_norm_act_forward', _ptr(x), _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias), wmod, _ptr(res), _ptr(res2), act,
-                   _ptr(slope), float(slope_const), _ptr(y), n_, c_, S, _stream())
+                   _ptr(slope), float(slope_const), _ptr(y), 0, 0, n_, c_, S, _stream())
         ctx.save_for_backward(x, weight, bias, slope, res, mean, invstd)
         ctx.cfg = (mode, act, float(slope_const), n_, c_, S, wmod, res2 is not None)
         ctx.exchange = sync
@@ -729,7 +757,7 @@ class NormActFn(torch.autograd.Function):
         dbias = torch.empty_like(bias) if (bias is not None and ctx.needs_input_grad[2]) else None
         dslope = torch.empty_like(slope) if (slope is not None and ctx.needs_input_grad[3]) else None
         training = 1 if mode in (1, 3) else 0
-        args = (_ptr(x), _ptr(gy), _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias), wmod, _ptr(res), act, _ptr(slope), slope_const,
+        args = (_ptr(x), _ptr(gy), 0, 0, _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias), wmod, _ptr(res), act, _ptr(slope), slope_const,
                 training, _ptr(dx), _ptr(dres), _ptr(dweight), _ptr(dbias), _ptr(dslope))
         # algorithmic bytes: reduce pass (x, gy) when the norm trains + apply pass (x, gy in; dx, dres out)
         with _detail('nab', 4.0 * x.numel() * ((2 if training else 0) + 2 + (dx is not None) + (dres is not None))):
@@ -738,13 +766,13 @@ class NormActFn(torch.autograd.Function):
                 # ws[3C] carries this rank's element count through the same all-reduce: uneven per-rank batches need no extra
                 # collective and no host synchronisation
                 ws = torch.empty(3 * c_ + 1, dtype=torch.float32, device=x.device)
-                L.call('dpf_norm_act_backward_ex', *args, _ptr(ws), n_, c_, S, 1, 0.0, _stream())
+                L.call('dpf_norm_act_backward', *args, _ptr(ws), n_, c_, S, 1, 0.0, _stream())
                 ws[3 * c_:].fill_(float(n_) * float(S))
                 ctx.exchange.all_reduce_sum_(ws)
-                L.call('dpf_norm_act_backward_ex', *args, _ptr(ws), n_, c_, S, 2, -1.0, _stream())
+                L.call('dpf_norm_act_backward', *args, _ptr(ws), n_, c_, S, 2, -1.0, _stream())
             else:
                 ws = zero_slot(3 * c_, x.device)                               # pre-zeroed: phase 3 skips the per-layer memset
-                L.call('dpf_norm_act_backward_ex', *args, _ptr(ws), n_, c_, S, 3, 0.0, _stream())
+                L.call('dpf_norm_act_backward', *args, _ptr(ws), n_, c_, S, 3, 0.0, _stream())
         dres2 = gy if (has_res2 and ctx.needs_input_grad[5]) else None
         return dx, dweight, dbias, dslope, dres, dres2, None, None, None, None, None, None, None
 
@@ -756,7 +784,7 @@ def norm_act(x, weight=None, bias=None, slope=None, res=None, res2=None, running
 
 class NormActCatFn(torch.autograd.Function):
     """torch.cat([act(batch_norm(x_i)) for i], dim=1) without the copies: every branch's normalisation kernel writes its channel
-    slice of the concatenated tensor, the backward reads its slice of the incoming gradient (dpf_norm_act_*_slice)."""
+    slice of the concatenated tensor, the backward reads its slice of the incoming gradient (the y_channels / dy_channels arguments)."""
 
     @staticmethod
     def forward(ctx, mode, act, holders, exchange, *tensors):
@@ -780,7 +808,7 @@ class NormActCatFn(torch.autograd.Function):
             for i in range(n):
                 x, C = xs[i], Cs[i]
                 mean, invstd, _ = _bn_stats(x, mode, rms[i], rvs[i], holders[i] if holders else None, moments[i])
-                L.call('dpf_norm_act_forward_slice', _ptr(x), _ptr(mean), _ptr(invstd), _ptr(ws[i]), _ptr(bs[i]), C, None, None, act, None, 0.0,
+                L.call('dpf_norm_act_forward', _ptr(x), _ptr(mean), _ptr(invstd), _ptr(ws[i]), _ptr(bs[i]), C, None, None, act, None, 0.0,
                        _ptr(cat), Ctot, c0, N, C, S, _stream())
                 saved += [x, ws[i], bs[i], mean, invstd]
                 c0 += C
@@ -816,7 +844,7 @@ class NormActCatFn(torch.autograd.Function):
                     for i in range(n):
                         x, w, b, mean, invstd = sv[5 * i:5 * i + 5]
                         dx, dw, db = outs[i]
-                        L.call('dpf_norm_act_backward_slice_ex', _ptr(x), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(w), _ptr(b), Cs[i], None,
+                        L.call('dpf_norm_act_backward', _ptr(x), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(w), _ptr(b), Cs[i], None,
                                act, None, 0.0, 1, _ptr(dx), None, _ptr(dw), _ptr(db), None, _ptr(ws_all[offs[i]:]), N, Cs[i], S, phase,
                                0.0 if phase == 1 else -1.0, _stream())
                         if phase == 1:
@@ -830,8 +858,8 @@ class NormActCatFn(torch.autograd.Function):
                     C = Cs[i]
                     dx, dw, db = outs[i]
                     wsb = scratch(3 * C, x.device)
-                    L.call('dpf_norm_act_backward_slice', _ptr(x), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(w), _ptr(b), C, None, act,
-                           None, 0.0, 1 if mode == 1 else 0, _ptr(dx), None, _ptr(dw), _ptr(db), None, _ptr(wsb), N, C, S, _stream())
+                    L.call('dpf_norm_act_backward', _ptr(x), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(w), _ptr(b), C, None, act,
+                           None, 0.0, 1 if mode == 1 else 0, _ptr(dx), None, _ptr(dw), _ptr(db), None, _ptr(wsb), N, C, S, 0, 0.0, _stream())
                     c0 += C
             for dx, dw, db in outs:
                 grads += [dx, dw, db, None, None]
@@ -846,7 +874,7 @@ def _conv_transpose_acc(x, w, out, ksize, stride, pad, dil):
     kd, kh, kw = ksize
     ws = _conv_ws(ksize, C, K, x.device)
     with _dense_timed('tr ', x, K, ksize, stride, dil, ID * IH * IW, x.numel() + 2 * out.numel() + w.numel()):
-        done = _supported('dpf_conv_transpose_acc', _ptr(x), _ptr(w), None, _ptr(out), _ptr(ws), N, C, ID, IH, IW, K, K, *out.shape[2:],
+        done = _supported('dpf_conv_transpose', _ptr(x), _ptr(w), None, _ptr(out), _ptr(ws), N, C, ID, IH, IW, K, K, *out.shape[2:],
                           kd, kh, kw, *stride, *pad, *dil, 1, _stream())
     if not done:
         out.add_(_conv_transpose_raw(x, w, None, out.shape[2:], ksize, stride, pad, dil))
@@ -882,7 +910,7 @@ class ConvBnCatFn(torch.autograd.Function):
             w, bw, bb, rm, rv = params[5 * i:5 * i + 5]
             y, C, st = ys[i], Cs[i], saved[i]
             mean, invstd, _ = _bn_stats(y, mode, rm, rv, st)
-            L.call('dpf_norm_act_forward_slice', _ptr(y), _ptr(mean), _ptr(invstd), _ptr(bw), _ptr(bb), C, None, None, ACT_NONE, None, 0.0,
+            L.call('dpf_norm_act_forward', _ptr(y), _ptr(mean), _ptr(invstd), _ptr(bw), _ptr(bb), C, None, None, ACT_NONE, None, 0.0,
                    _ptr(cat), Ctot, c0, N, C, S, _stream())
             keep += [w, y, bw, bb, mean, invstd]
             c0 += C
@@ -908,8 +936,8 @@ class ConvBnCatFn(torch.autograd.Function):
             dbw = torch.empty_like(bw) if ctx.needs_input_grad[3 + 5 * i + 1] else None
             dbb = torch.empty_like(bb) if ctx.needs_input_grad[3 + 5 * i + 2] else None
             wsb = scratch(3 * C, x.device)
-            L.call('dpf_norm_act_backward_slice', _ptr(y), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(bw), _ptr(bb), C, None, ACT_NONE,
-                   None, 0.0, 1 if mode == 1 else 0, _ptr(dy), None, _ptr(dbw), _ptr(dbb), None, _ptr(wsb), N, C, S, _stream())
+            L.call('dpf_norm_act_backward', _ptr(y), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(bw), _ptr(bb), C, None, ACT_NONE,
+                   None, 0.0, 1 if mode == 1 else 0, _ptr(dy), None, _ptr(dbw), _ptr(dbb), None, _ptr(wsb), N, C, S, 0, 0.0, _stream())
             w5 = w.unsqueeze(2)
             gw = None
             if ctx.needs_input_grad[3 + 5 * i]:
@@ -994,8 +1022,7 @@ def nearest_up_add(lat, top):
 
 # ----------------------------------------------------------------------------------------------- cost volume
 class ShiftTripleFn(torch.autograd.Function):
-    """The M row-shifted copies [B,C,M,h,w] of fea; M = tables' first dimension (the enabled shift modes).  M = 3 runs the
-    dpf_shift_triple_* entry points, M < 3 dpf_shift_copies_*."""
+    """The M row-shifted copies [B,C,M,h,w] of fea; M = tables' first dimension (the enabled shift modes)."""
 
     @staticmethod
     def forward(ctx, fea, iy, wy, ix, wx, iy_inv, ix_inv):
@@ -1004,10 +1031,7 @@ class ShiftTripleFn(torch.autograd.Function):
         B, C, h, w = fea.shape
         M = int(iy.shape[0])
         out = torch.empty((B, C, M, h, w), dtype=torch.float32, device=fea.device)
-        if M == 3:
-            lib().call('dpf_shift_triple_forward', _ptr(fea), _ptr(out), _ptr(iy), _ptr(wy), _ptr(ix), _ptr(wx), B, C, h, w, _stream())
-        else:
-            lib().call('dpf_shift_copies_forward', _ptr(fea), _ptr(out), _ptr(iy), _ptr(wy), _ptr(ix), _ptr(wx), B, C, M, h, w, _stream())
+        lib().call('dpf_shift_copies_forward', _ptr(fea), _ptr(out), _ptr(iy), _ptr(wy), _ptr(ix), _ptr(wx), B, C, M, h, w, _stream())
         ctx.tables = (iy_inv, wy, ix_inv, wx)
         ctx.dims = (B, C, M, h, w)
         return out
@@ -1019,12 +1043,8 @@ class ShiftTripleFn(torch.autograd.Function):
         g = _c(g)
         dfea = torch.empty((B, C, h, w), dtype=torch.float32, device=g.device)
         # gather form: deterministic, no atomics, no zero fill
-        if M == 3:
-            lib().call('dpf_shift_triple_backward_gather', _ptr(g), _ptr(dfea), _ptr(iy_inv), _ptr(wy), _ptr(ix_inv), _ptr(wx), B, C, h, w,
-                       _stream())
-        else:
-            lib().call('dpf_shift_copies_backward_gather', _ptr(g), _ptr(dfea), _ptr(iy_inv), _ptr(wy), _ptr(ix_inv), _ptr(wx), B, C, M, h,
-                       w, _stream())
+        lib().call('dpf_shift_copies_backward_gather', _ptr(g), _ptr(dfea), _ptr(iy_inv), _ptr(wy), _ptr(ix_inv), _ptr(wx), B, C, M, h, w,
+                   _stream())
         return dfea, None, None, None, None, None, None
 
 
@@ -1073,7 +1093,7 @@ def shift_triple(fea, tables, phase=None):
 
 class CvSelectFn(torch.autograd.Function):
     """Writes the [B, 2C, L, h, w] volume from groups of (x_ref, s_ref, x_tar, s_tar) [B,C,M,h,w] sharing a level mask.  fetch: the
-    variance over the copies instead of their mean (feature_fetch).  M = 3 without fetch runs the dpf_cv_select_* entry points."""
+    variance over the copies instead of their mean (feature_fetch)."""
 
     @staticmethod
     def forward(ctx, L, masks, fetch, *ts):
@@ -1090,10 +1110,7 @@ class CvSelectFn(torch.autograd.Function):
         for gi, m in enumerate(masks):
             x3f, sf, x3b, sb = ts[4 * gi:4 * gi + 4]
             for x3, s, off in ((x3f, sf, 0), (x3b, sb, C)):
-                if M == 3 and not fetch:
-                    lb.call('dpf_cv_select_forward', _ptr(x3), _ptr(s), _ptr(vol), B, C, h, w, 2 * C, L, off, m, _stream())
-                else:
-                    lb.call('dpf_cv_select_m_forward', _ptr(x3), _ptr(s), _ptr(vol), B, C, M, h, w, 2 * C, L, off, m, fetch, _stream())
+                lb.call('dpf_cv_select_forward', _ptr(x3), _ptr(s), _ptr(vol), B, C, M, h, w, 2 * C, L, off, m, fetch, _stream())
         ctx.save_for_backward(*ts)
         ctx.cfg = (L, tuple(masks), B, C, M, h, w, fetch)
         return vol
@@ -1110,11 +1127,8 @@ class CvSelectFn(torch.autograd.Function):
             for x3, s, off in ((x3f, sf, 0), (x3b, sb, C)):
                 dx3 = torch.empty_like(x3)
                 ds = torch.empty_like(s)
-                if M == 3 and not fetch:
-                    lb.call('dpf_cv_select_backward', _ptr(x3), _ptr(s), _ptr(dvol), _ptr(dx3), _ptr(ds), B, C, h, w, 2 * C, L, off, m, _stream())
-                else:
-                    lb.call('dpf_cv_select_m_backward', _ptr(x3), _ptr(s), _ptr(dvol), _ptr(dx3), _ptr(ds), B, C, M, h, w, 2 * C, L, off, m,
-                            fetch, _stream())
+                lb.call('dpf_cv_select_backward', _ptr(x3), _ptr(s), _ptr(dvol), _ptr(dx3), _ptr(ds), B, C, M, h, w, 2 * C, L, off, m, fetch,
+                        _stream())
                 grads += [dx3, ds]
         return (None, None, None) + tuple(grads)
 
@@ -1284,20 +1298,19 @@ class SoftArgminFn(torch.autograd.Function):
         Lh, H, W = D * scale, h * scale, w * scale
         pred = torch.empty((B, H, W), dtype=torch.float32, device=logits.device)
         hd = _host_floats(disp_values)
+        prob = None
         if prob_into is not None:
             # (stacked [B, n, Lh, H, W], head index): this head's probabilities go straight into their slice of the stacked tensor
             stacked, head = prob_into
             assert stacked.is_contiguous() and tuple(stacked.shape[2:]) == (Lh, H, W) and stacked.shape[0] == B
-            slice_ptr = ctypes.c_void_p(stacked.data_ptr() + 4 * head * Lh * H * W)
-            lib().call('dpf_softargmin_forward_strided', _ptr(logits), _ptr(pred), slice_ptr, stacked.shape[1] * Lh * H * W, hd, B, D, h, w, Lh,
-                       H, W, int(align_corners), _stream())
-            prob = pred.new_empty(0)
+            prob_ptr, pbs = ctypes.c_void_p(stacked.data_ptr() + 4 * head * Lh * H * W), stacked.shape[1] * Lh * H * W
         else:
-            prob = torch.empty((B, Lh, H, W), dtype=torch.float32, device=logits.device) if want_prob else None
-            lib().call('dpf_softargmin_forward_ex', _ptr(logits), _ptr(pred), _ptr(prob), hd, B, D, h, w, Lh, H, W, int(align_corners),
-                       _stream())
-            if prob is None:
-                prob = pred.new_empty(0)
+            if want_prob:
+                prob = torch.empty((B, Lh, H, W), dtype=torch.float32, device=logits.device)
+            prob_ptr, pbs = _ptr(prob), 0
+        lib().call('dpf_softargmin_forward', _ptr(logits), _ptr(pred), prob_ptr, pbs, hd, B, D, h, w, Lh, H, W, int(align_corners), _stream())
+        if prob is None:
+            prob = pred.new_empty(0)
         ctx.save_for_backward(logits)
         ctx.cfg = (tuple(disp_values), B, D, h, w, Lh, H, W, int(align_corners))
         ctx.mark_non_differentiable(prob)
@@ -1309,7 +1322,7 @@ class SoftArgminFn(torch.autograd.Function):
         disp_values, B, D, h, w, Lh, H, W, ac = ctx.cfg
         gpred = _c(gpred)
         dl = torch.empty_like(logits)
-        lib().call('dpf_softargmin_backward_ex', _ptr(logits), _ptr(gpred), _ptr(dl), _host_floats(disp_values), B, D, h, w, Lh, H, W, ac,
+        lib().call('dpf_softargmin_backward', _ptr(logits), _ptr(gpred), _ptr(dl), _host_floats(disp_values), B, D, h, w, Lh, H, W, ac,
                    _stream())
         return dl, None, None, None, None, None
 
@@ -1362,7 +1375,7 @@ def deform_conv_backward_raw(x, weight, bias, offset, go, stride, pad, dil, grou
     # grad_output read, grad_input (cg channels) and grad_offset written, once each
     with _Timed('dcn_bwd', 2.0 * B * K * (2 * C + cg) * kd * kh * kw * go.numel() / (B * K), 'dcnb C%d K%d %dx%dx%d' % (C, K, D, H, W),
                 4.0 * (x.numel() + 2 * offset.numel() + go.numel() + gi.numel() * cg // C)):
-        L.call('dpf_deform_conv3d_backward_ex', _ptr(x), _ptr(weight), _ptr(bias), _ptr(offset), _ptr(go), _ptr(gi), _ptr(goff), _ptr(gw), _ptr(gb),
+        L.call('dpf_deform_conv3d_backward', _ptr(x), _ptr(weight), _ptr(bias), _ptr(offset), _ptr(go), _ptr(gi), _ptr(goff), _ptr(gw), _ptr(gb),
                _ptr(ws), B, C, D, H, W, K, kd, kh, kw, *stride, *pad, *dil, group, dgroup, step, cg, _stream())
     return gi, goff, gw, gb
 
@@ -1685,9 +1698,7 @@ class DepthLossFn(torch.autograd.Function):
         B, n, H, W = pred.shape
         if target_ab is not None and (tuple(target_ab.shape) != (B, 2) or target_ab.dtype != torch.float32):
             raise DpfError('depth_loss: target_ab %s %s, float32 [%d, 2] expected' % (tuple(target_ab.shape), target_ab.dtype, B))
-        for name, t in (('target', target), ('mask', mask), ('conf', conf)):
-            if t is not None and tuple(t.shape) != (B, H, W):
-                raise DpfError('depth_loss: %s %s does not match pred %s' % (name, tuple(t.shape), tuple(pred.shape)))
+        _match_pred('depth_loss', pred, ('target', target, (B, H, W)), ('mask', mask, (B, H, W)), ('conf', conf, (B, H, W)))
         if len(head_weights) != n:
             raise DpfError('depth_loss: %d head weights for %d heads' % (len(head_weights), n))
         ws, nbytes = _workspace('dpf_depth_loss_workspace_bytes', 'depth_loss: shape B=%d H=%d W=%d is not supported', B, H, W,
@@ -1695,12 +1706,8 @@ class DepthLossFn(torch.autograd.Function):
         stats = torch.empty(LOSS_STATS, dtype=torch.float64, device=pred.device)
         out = torch.empty((), dtype=torch.float32, device=pred.device)
         cfg = (LOSS_KIND[kind], LOSS_TRANSFORM[transform], B, n, H, W, tuple(float(w) for w in head_weights), float(variance_focus))
-        if target_ab is None:
-            lib().call('dpf_depth_loss_forward', cfg[0], cfg[1], _ptr(pred), _ptr(target), _ptr(mask), _ptr(conf), B, n, H, W,
-                       _host_floats(cfg[6]), cfg[7], _ptr(ws), nbytes, _ptr(stats), _ptr(out), _stream())
-        else:
-            lib().call('dpf_depth_loss_forward_ab', cfg[0], cfg[1], _ptr(pred), _ptr(target), _ptr(target_ab), _ptr(mask), _ptr(conf), B, n,
-                       H, W, _host_floats(cfg[6]), cfg[7], _ptr(ws), nbytes, _ptr(stats), _ptr(out), _stream())
+        lib().call('dpf_depth_loss_forward', cfg[0], cfg[1], _ptr(pred), _ptr(target), _ptr(target_ab), _ptr(mask), _ptr(conf), B, n, H, W,
+                   _host_floats(cfg[6]), cfg[7], _ptr(ws), nbytes, _ptr(stats), _ptr(out), _stream())
         ctx.save_for_backward(pred, target, mask, conf, stats, target_ab)
         ctx.cfg = cfg
         return out
@@ -1712,12 +1719,8 @@ class DepthLossFn(torch.autograd.Function):
         gout = _c(gout)
         _need(gout)
         dpred = torch.empty_like(pred)
-        if target_ab is None:
-            lib().call('dpf_depth_loss_backward', kind, transform, _ptr(pred), _ptr(target), _ptr(mask), _ptr(conf), B, n, H, W,
-                       _host_floats(weights), vf, _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
-        else:
-            lib().call('dpf_depth_loss_backward_ab', kind, transform, _ptr(pred), _ptr(target), _ptr(target_ab), _ptr(mask), _ptr(conf), B, n,
-                       H, W, _host_floats(weights), vf, _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
+        lib().call('dpf_depth_loss_backward', kind, transform, _ptr(pred), _ptr(target), _ptr(target_ab), _ptr(mask), _ptr(conf), B, n, H, W,
+                   _host_floats(weights), vf, _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
         return dpred, None, None, None, None, None, None, None, None
 
 
@@ -1739,10 +1742,11 @@ def affine_fit(pred, idepth, f_scale=AFFINE_FIT_F_SCALE, max_iters=AFFINE_FIT_MA
     the pixels with idepth > 0 -> detached float32 [B, 2] = [b, a]; with return_info also the fp64 [B, 6] record.  Workspace and results are
     fresh tensors and nothing is read on the host, so the call is capturable inside the train-step graph like DepthLossFn."""
     pred, idepth = _c(pred.detach()), _c(idepth.detach())
-    _need(pred, idepth)
-    if pred.dim() != 4 or tuple(idepth.shape) != (pred.shape[0],) + tuple(pred.shape[2:]) or idepth.dtype != torch.float32:
-        raise DpfError('affine_fit: idepth %s does not match pred %s' % (tuple(idepth.shape), tuple(pred.shape)))
+    _need(pred, idepth, dtypes=_F32)
+    if pred.dim() != 4:
+        raise DpfError('affine_fit: pred %s is not [B, n, H, W]' % (tuple(pred.shape),))
     B, n, H, W = pred.shape
+    _match_pred('affine_fit', pred, ('idepth', idepth, (B, H, W)))
     ws, nbytes = _workspace('dpf_affine_fit_workspace_bytes', 'affine_fit: shape B=%d H=%d W=%d is not supported', B, H, W,
                             device=pred.device)
     ab = torch.empty((B, 2), dtype=torch.float32, device=pred.device)
@@ -1752,40 +1756,31 @@ def affine_fit(pred, idepth, f_scale=AFFINE_FIT_F_SCALE, max_iters=AFFINE_FIT_MA
     return (ab, info) if return_info else ab
 
 
+def _normalizer_floats():
+    """The Normalizer's mean and std as six host floats."""
+    from .facedp import IMAGENET_MEAN, IMAGENET_STD          # the data path's Normalizer: the one place these constants live
+    return _host_floats(tuple(IMAGENET_MEAN) + tuple(IMAGENET_STD))
+
+
 def _filter_operands(name, pred, guide_rgb):
     """The operands both post-processing filters share: pred [B, n, H, W] (a slice along dim 0 or 1 of a wider tensor is taken as it is,
     through its batch stride), guide_rgb [B, 3, H, W], the Normalizer's constants as six host floats, and a fresh output."""
-    from .facedp import IMAGENET_MEAN, IMAGENET_STD          # the data path's Normalizer: the one place these constants live
+    _need(pred, guide_rgb, dtypes=_F32, contiguous=False)
     pred, guide_rgb = pred.detach(), guide_rgb.detach()
-    for t in (pred, guide_rgb):
-        if not t.is_cuda:
-            raise DpfError('dualpixelface_amd ops need GPU tensors (no CPU fallback)')
-        if t.dtype != torch.float32:
-            raise DpfError('unsupported dtype %s' % t.dtype)
-    if pred.dim() != 4 or guide_rgb.dim() != 4 or guide_rgb.shape[1] != 3 or guide_rgb.shape[0] != pred.shape[0] or \
-            tuple(guide_rgb.shape[2:]) != tuple(pred.shape[2:]):
-        raise DpfError('%s: guide %s does not match pred %s (want [B, 3, H, W] beside [B, n, H, W])'
-                       % (name, tuple(guide_rgb.shape), tuple(pred.shape)))
+    if pred.dim() != 4:
+        raise DpfError('%s: pred %s is not [B, n, H, W]' % (name, tuple(pred.shape)))
     B, n, H, W = pred.shape
-    if not (pred[0].is_contiguous() and (B == 1 or pred.stride(0) >= n * H * W)):
-        pred = pred.contiguous()
-    stride = pred.stride(0) if B > 1 else n * H * W
+    _match_pred(name, pred, ('guide', guide_rgb, (B, 3, H, W)))
+    pred, stride = _batch_view(pred, n * H * W)
     out = torch.empty((B, n, H, W), dtype=torch.float32, device=pred.device)
-    return pred, _c(guide_rgb), stride, _host_floats(tuple(IMAGENET_MEAN) + tuple(IMAGENET_STD)), out
-
-
-def _filter_radius(name, radius):
-    """An integer radius as it is (a float such as 2.7 is refused, not truncated)."""
-    if isinstance(radius, bool) or not hasattr(radius, '__index__'):
-        raise DpfError('%s: radius must be an integer, got %r' % (name, radius))
-    return radius.__index__()
+    return pred, _c(guide_rgb), stride, _normalizer_floats(), out
 
 
 def guided_filter(pred, guide_rgb, radius, eps):
     """The guided filter of csrc/postprocess.hip (He et al., grey guide, clipped square window of `radius`, 1 <= radius <= 32, eps > 0) on
     every head of pred [B, n, H, W], guided by the luminance of the normalised image guide_rgb [B, 3, H, W] -> a fresh [B, n, H, W].  An
     inference-time operator, not an autograd node: the inputs are detached.  Scratch comes through scratch(), nothing waits on the host."""
-    radius = _filter_radius('guided_filter', radius)
+    radius = _int_arg('guided_filter', 'radius', radius)
     with torch.no_grad():
         pred, guide_rgb, stride, norm, out = _filter_operands('guided_filter', pred, guide_rgb)
         B, n, H, W = pred.shape
@@ -1800,7 +1795,7 @@ def guided_filter(pred, guide_rgb, radius, eps):
 def joint_bilateral_filter(pred, guide_rgb, radius, sigma_space, sigma_color):
     """The joint bilateral filter of csrc/postprocess.hip (clipped (2 radius + 1)^2 window, 1 <= radius <= 16, Gaussian weights in space and
     in the guide's luminance) on every head of pred [B, n, H, W] -> a fresh [B, n, H, W].  Detached like guided_filter; needs no scratch."""
-    radius = _filter_radius('joint_bilateral_filter', radius)
+    radius = _int_arg('joint_bilateral_filter', 'radius', radius)
     with torch.no_grad():
         pred, guide_rgb, stride, norm, out = _filter_operands('joint_bilateral_filter', pred, guide_rgb)
         B, n, H, W = pred.shape
@@ -1809,8 +1804,17 @@ def joint_bilateral_filter(pred, guide_rgb, radius, sigma_space, sigma_color):
     return out
 
 
-TARGET_TYPES = {'disp': 0, 'idepth': 1, 'depth': 2}       # the codes of csrc/reconstruct.hip
+TARGET_TYPES = {'disp': 0, 'idepth': 1, 'depth': 2}       # the codes of csrc/reconstruct.hip, normal_geo.hip and metrics.hip
 MESH_STRIDES = (1, 2, 4, 8)
+
+
+def _target_code(name, target_type, ab):
+    """The code of a known target type; every type but 'depth' needs ab."""
+    if target_type not in TARGET_TYPES:
+        raise DpfError('%s: target_type must be one of %s, got %r' % (name, sorted(TARGET_TYPES), target_type))
+    if ab is None and target_type != 'depth':
+        raise DpfError('%s: target_type %r needs ab [B, 2] = [b, a]' % (name, target_type))
+    return TARGET_TYPES[target_type]
 
 
 def _scene_operands(name, pred, target_type, ab, Kmat, mask, near, far):
@@ -1818,34 +1822,18 @@ def _scene_operands(name, pred, target_type, ab, Kmat, mask, near, far):
     head 0 of pred [B, n, H, W] (or a [B, H, W] map; a slice of a wider tensor is taken as it is, through its batch stride), ab [B, 2] =
     [b, a] (None with target type 'depth'), Kmat [B, 3, 3], mask [B, H, W] or None, and the depth limits (far None: no limit).  The caller
     holds the tensors until its launches are enqueued."""
-    if target_type not in TARGET_TYPES:
-        raise DpfError('%s: target_type must be one of %s, got %r' % (name, sorted(TARGET_TYPES), target_type))
-    for t in (pred, Kmat, ab, mask):
-        if t is None:
-            continue
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise DpfError('dualpixelface_amd ops need GPU tensors (no CPU fallback)')
-        if t.dtype != torch.float32:
-            raise DpfError('unsupported dtype %s' % t.dtype)
+    code = _target_code(name, target_type, ab)
+    _need(pred, Kmat, ab, mask, dtypes=_F32, contiguous=False)
     pred = pred.detach()
     if pred.dim() == 3:
         pred = pred.unsqueeze(1)
     if pred.dim() != 4:
         raise DpfError('%s: pred %s is neither [B, n, H, W] nor [B, H, W]' % (name, tuple(pred.shape)))
     B, n, H, W = pred.shape
-    if tuple(Kmat.shape) != (B, 3, 3):
-        raise DpfError('%s: K %s does not match pred %s (want [B, 3, 3])' % (name, tuple(Kmat.shape), tuple(pred.shape)))
-    if ab is None and target_type != 'depth':
-        raise DpfError('%s: target_type %r needs ab [B, 2] = [b, a]' % (name, target_type))
-    if ab is not None and tuple(ab.shape) != (B, 2):
-        raise DpfError('%s: ab %s does not match pred %s (want [B, 2])' % (name, tuple(ab.shape), tuple(pred.shape)))
-    if mask is not None and tuple(mask.shape) != (B, H, W):
-        raise DpfError('%s: mask %s does not match pred %s (want [B, H, W])' % (name, tuple(mask.shape), tuple(pred.shape)))
-    if not (pred[0].is_contiguous() and (B == 1 or pred.stride(0) >= H * W)):
-        pred = pred.contiguous()
-    stride = pred.stride(0) if B > 1 else n * H * W
+    _match_pred(name, pred, ('K', Kmat, (B, 3, 3)), ('ab', ab, (B, 2)), ('mask', mask, (B, H, W)))
+    pred, stride = _batch_view(pred, H * W)
     held = (pred, None if ab is None else _c(ab.detach()), _c(Kmat.detach()), None if mask is None else _c(mask.detach()))
-    head = (_ptr(held[0]), stride, TARGET_TYPES[target_type], _ptr(held[1]), _ptr(held[2]), _ptr(held[3]), B, H, W, float(near),
+    head = (_ptr(held[0]), stride, code, _ptr(held[1]), _ptr(held[2]), _ptr(held[3]), B, H, W, float(near),
             float('inf') if far is None else float(far))
     return head, held, (B, H, W)
 
@@ -1881,21 +1869,13 @@ def depth_mesh(pred, Kmat, normal_map, ab=None, mask=None, view=None, target_typ
     from the normalised view [B, 3, H, W] (None: 255), faces [B, 2 (Hs - 1)(Ws - 1), 3] int32 with sample-local indices, counts [B, 2] int32 =
     (vertices, faces)).  The buffers are worst-case sized and entries past the counts are left as torch.empty (or `out`, a tuple of the five
     to write into) had them; counts stays on the device: nothing is read on the host."""
-    from .facedp import IMAGENET_MEAN, IMAGENET_STD          # the data path's Normalizer: the one place these constants live
-    if isinstance(stride, bool) or not hasattr(stride, '__index__'):
-        raise DpfError('depth_mesh: stride must be an integer, got %r' % (stride,))
-    stride = stride.__index__()
+    stride = _int_arg('depth_mesh', 'stride', stride)
     with torch.no_grad():
         head, held, (B, H, W) = _scene_operands('depth_mesh', pred, target_type, ab, Kmat, mask, near, far)
-        for name, t in (('normal_map', normal_map), ('view', view)):
-            if t is None and name == 'view':
-                continue
-            if not torch.is_tensor(t) or not t.is_cuda:
-                raise DpfError('dualpixelface_amd ops need GPU tensors (no CPU fallback)')
-            if t.dtype != torch.float32:
-                raise DpfError('unsupported dtype %s' % t.dtype)
-            if tuple(t.shape) != (B, 3, H, W):
-                raise DpfError('depth_mesh: %s %s does not match pred %s (want [B, 3, H, W])' % (name, tuple(t.shape), tuple(held[0].shape)))
+        _need(normal_map, view, dtypes=_F32, contiguous=False)
+        if normal_map is None:
+            raise DpfError('depth_mesh: normal_map [B, 3, H, W] is needed')
+        _match_pred('depth_mesh', held[0], ('normal_map', normal_map, (B, 3, H, W)), ('view', view, (B, 3, H, W)))
         nmap, view = _c(normal_map.detach()), None if view is None else _c(view.detach())
         dev = held[0].device
         ws, nbytes = _workspace('dpf_depth_mesh_workspace_bytes', 'depth_mesh: B=%d H=%d W=%d stride=%d is not supported (stride 1, 2, 4 or 8)',
@@ -1912,10 +1892,9 @@ def depth_mesh(pred, Kmat, normal_map, ab=None, mask=None, view=None, target_typ
                 raise DpfError('depth_mesh: an output buffer %s %s is not the contiguous %s %s the shape asks for'
                                % (tuple(t.shape), t.dtype, shape, kind))
         vertices, vnormals, vcolours, faces, counts = out
-        norm = _host_floats(tuple(IMAGENET_MEAN) + tuple(IMAGENET_STD))
-        lib().call('dpf_depth_mesh', *head[:6], _ptr(nmap), _ptr(view), norm, *head[6:9], stride, head[9], head[10], float(max_edge_ratio),
-                   int(bool(towards_camera)), _ptr(ws), nbytes, _ptr(vertices), _ptr(vnormals), _ptr(vcolours), _ptr(faces), _ptr(counts),
-                   _stream())
+        lib().call('dpf_depth_mesh', *head[:6], _ptr(nmap), _ptr(view), _normalizer_floats(), *head[6:9], stride, head[9], head[10],
+                   float(max_edge_ratio), int(bool(towards_camera)), _ptr(ws), nbytes, _ptr(vertices), _ptr(vnormals), _ptr(vcolours),
+                   _ptr(faces), _ptr(counts), _stream())
     return vertices, vnormals, vcolours, faces, counts
 
 
@@ -1970,34 +1949,22 @@ def normal_geo_loss(pred, depth, normal, Kmat, ab=None, mask=None, head_weights=
     [B, H, W] is the target depth: it decides which pixels are usable and which neighbours (`step` = 1, 2 or 4 pixels away) lie on one
     surface, the predicted depth a / (pred - b) (ab [B, 2] = [b, a]; pred itself for target type 'depth') gives the step vectors.  The
     gradient reaches pred only.  With return_normals also normal [B, n, 3, H, W] fp32 and counted [B, n, H, W] uint8."""
-    if target_type not in TARGET_TYPES:
-        raise DpfError('normal_geo_loss: target_type must be one of %s, got %r' % (sorted(TARGET_TYPES), target_type))
-    for t in (pred, depth, normal, Kmat, ab, mask):
-        if t is None:
-            continue
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise DpfError('dualpixelface_amd ops need GPU tensors (no CPU fallback)')
-        if t.dtype != torch.float32:
-            raise DpfError('unsupported dtype %s' % t.dtype)
+    code = _target_code('normal_geo_loss', target_type, ab)
+    _need(pred, depth, normal, Kmat, ab, mask, dtypes=_F32, contiguous=False)
     if pred.dim() != 4:
         raise DpfError('normal_geo_loss: pred %s is not [B, n, H, W]' % (tuple(pred.shape),))
     B, n, H, W = pred.shape
-    for name, t, shape in (('depth', depth, (B, H, W)), ('normal', normal, (B, 3, H, W)), ('K', Kmat, (B, 3, 3)), ('ab', ab, (B, 2)),
-                           ('mask', mask, (B, H, W))):
-        if t is not None and tuple(t.shape) != shape:
-            raise DpfError('normal_geo_loss: %s %s does not match pred %s (want %s)' % (name, tuple(t.shape), tuple(pred.shape), list(shape)))
-    if ab is None and target_type != 'depth':
-        raise DpfError('normal_geo_loss: target_type %r needs ab [B, 2] = [b, a]' % (target_type,))
+    _match_pred('normal_geo_loss', pred, ('depth', depth, (B, H, W)), ('normal', normal, (B, 3, H, W)), ('K', Kmat, (B, 3, 3)), ('ab', ab, (B, 2)),
+                ('mask', mask, (B, H, W)))
     if len(head_weights) != n:
         raise DpfError('normal_geo_loss: %d head weights for %d heads' % (len(head_weights), n))
-    if isinstance(step, bool) or not hasattr(step, '__index__') or step.__index__() not in NORMAL_GEO_STEPS:
-        raise DpfError('normal_geo_loss: step must be 1, 2 or 4, got %r' % (step,))
+    step = _int_arg('normal_geo_loss', 'step', step, NORMAL_GEO_STEPS)
     signs = tuple(float(v) for v in target_signs)
     if len(signs) != 3 or any(v not in (1.0, -1.0) for v in signs):
         raise DpfError('normal_geo_loss: target_signs must be three values of +1 or -1, got %r' % (target_signs,))
     if not float(max_edge_ratio) > 0:
         raise DpfError('normal_geo_loss: max_edge_ratio must be positive, got %r' % (max_edge_ratio,))
-    cfg = (TARGET_TYPES[target_type], float(max_edge_ratio), step.__index__(), int(bool(towards_camera)), signs,
+    cfg = (code, float(max_edge_ratio), step, int(bool(towards_camera)), signs,
            tuple(float(w) for w in head_weights))
     held = [None if t is None else _c(t.detach()) for t in (depth, normal, Kmat, None if target_type == 'depth' else ab, mask)]
     return NormalGeoFn.apply(_c(pred), held[0], held[1], held[2], held[3], held[4], cfg, bool(return_normals))
@@ -2126,9 +2093,6 @@ def rmsprop_step_ctl(param, grad, square_avg, ctl, alpha=0.99, eps=1e-5):
 
 
 # ---- validation metrics (csrc/metrics.hip): raw wrappers; results stay on the device, nothing here reads the host
-METRIC_TARGET = {'disp': 0, 'idepth': 1, 'depth': 2}
-
-
 def _metric_ws(query, B, n, device):
     return _workspace(query, query + ': shape B=%d n=%d is not supported', B, n, device=device, tag='metric')
 
@@ -2140,7 +2104,7 @@ def metric_absolute_dp(pred, abvalue, target, mask=None, target_type='disp', thr
     B, n = pred.shape[0], pred[0].numel()
     out = torch.empty(8, dtype=torch.float32, device=pred.device) if out is None else out
     ws, nbytes = _metric_ws('dpf_metric_absolute_dp_workspace_bytes', B, n, pred.device)
-    lib().call('dpf_metric_absolute_dp', _ptr(pred), _ptr(abvalue), _ptr(target), _ptr(mask), B, n, METRIC_TARGET[target_type],
+    lib().call('dpf_metric_absolute_dp', _ptr(pred), _ptr(abvalue), _ptr(target), _ptr(mask), B, n, TARGET_TYPES[target_type],
                float(threshold), _ptr(out), _ptr(ws), nbytes, _stream())
     return out
 

@@ -117,7 +117,7 @@ def build_shift_tables(h, w, delta, use_nearest=True, use_bilinear=True, use_pha
 
 def apply_tables_reference(fea, tables):
     """Slow torch evaluation of the table sampler (used by the CPU tests to pin the host logic against the golden
-    vectors; the product path evaluates the same tables in dpf_shift_triple_forward / dpf_shift_copies_forward)."""
+    vectors; the product path evaluates the same tables in dpf_shift_copies_forward)."""
     iy, wy, ix, wx = tables[:4]
     B, C, h, w = fea.shape
     M = iy.shape[0]

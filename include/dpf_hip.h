@@ -36,26 +36,23 @@ extern "C" {
  * ws: dpf_conv_workspace_floats(T, reduce_channels, out_channels) floats (repacked weights).
  * Windows of up to 27 taps run on the matrix-core kernels.  2-D windows of 28 ... 49 taps (kh, kw <= 7; DPNet's 7x7 stem and heads,
  * src/model/dpnet/modules.py:44, mainmodel.py:81-85), stride 1 or 2, dilation 1, run on plain fp32 FMA kernels (csrc/conv_wide.hip)
- * behind the same three entry points -- dpf_conv_forward, dpf_conv_transpose* (data gradient; `accumulate` is declined with
+ * behind the same three entry points -- dpf_conv_forward, dpf_conv_transpose (data gradient; `accumulate` is declined with
  * DPF_ERR_UNSUPPORTED) and dpf_conv_wgrad_ws (fixed-order slab fold: bitwise reproducible in every mode; needs `ws`).  Their result
  * does not depend on dpf_set_f32_matrix_path. */
 long long dpf_conv_workspace_floats(int T, int reduce, int outc);
 int dpf_conv_forward(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
                      int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw,
                      void* stream);
+/* Transposed convolution: x [N,C,ID,IH,IW] on the strided (small) grid, out [N,Ktot,OD,OH,OW] on the dense grid, (OD,OH,OW) given by the
+ * caller.  w is [C][Ktot][T] in memory, either a forward-conv weight [C = conv out][Ktot = conv in][T] (this call is then that conv's data
+ * gradient) or an nn.ConvTranspose3d weight [C_in = C][C_out = Ktot][T].  Only output channels [0, K), K <= Ktot, are computed; the others
+ * are left untouched (a caller that needs only k_needed leading channels of a gradient passes K = k_needed and zeroes the rest itself).
+ * accumulate != 0: out += result (data gradients of several convolutions reading one tensor summed in the epilogue);
+ * DPF_ERR_UNSUPPORTED with nothing written when the shape does not run on the LDS-DMA kernel */
 int dpf_conv_transpose(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
-                       int K, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
-                       int dd, int dh, int dw, void* stream);
-/* dpf_conv_transpose into an output tensor / weight of Ktot >= K channels, computing only channels [0, K) */
-int dpf_conv_transpose_ex(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
-                          int K, int Ktot, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
-                          int dd, int dh, int dw, void* stream);
-/* dpf_conv_transpose_ex with out += result when accumulate != 0 (data gradients of several convolutions reading one tensor summed in
- * the epilogue); DPF_ERR_UNSUPPORTED with nothing written when the shape does not run on the LDS-DMA kernel */
-int dpf_conv_transpose_acc(const float* x, const float* w, const float* bias, float* out, float* ws, int N, int C, int ID, int IH, int IW,
-                           int K, int Ktot, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
-                           int dd, int dh, int dw, int accumulate, void* stream);
-/* Operand precision of the dense convolution kernels behind dpf_conv_forward* / dpf_conv_transpose* / dpf_conv_wgrad*: 0 = exact fp32
+                       int K, int Ktot, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
+                       int dd, int dh, int dw, int accumulate, void* stream);
+/* Operand precision of the dense convolution kernels behind dpf_conv_forward* / dpf_conv_transpose / dpf_conv_wgrad_ws: 0 = exact fp32
  * (default), 1 = operands rounded to bf16 (round to nearest even) while they are staged, fp32 accumulation and fp32 tensors in HBM --
  * the reference's `precision: 16` (PL autocast, config_/train_faceDP.json) for its nn.Conv2d / nn.Conv3d layers.  Process-wide state;
  * shapes the bf16 kernels do not cover run exact fp32. */
@@ -83,11 +80,10 @@ int dpf_get_f32_matrix_path(void);
 /* test aid: 0 switches the position guard of path 2's convolutions off (one scale per channel chunk, no extra passes), 1 (the default
  * and the only setting the product uses) on */
 int dpf_debug_set_range_guard(int on);
-int dpf_conv_wgrad(const float* g, const float* x, float* dw, int N, int C, int ID, int IH, int IW, int K, int QD, int QH, int QW,
-                   int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw_, void* stream);
-/* same, with caller scratch `ws` of dpf_conv_wgrad_workspace_floats(T, C, K) floats: eligible shapes (16-byte aligned rows, 3x3 /
- * 3x3x3 kernels, dilation 1) then run without float atomics -- partial tiles are reduced in a fixed order, so the gradient is
- * bitwise reproducible; other shapes use the same kernel as dpf_conv_wgrad.  accumulate = 0: dw is overwritten (any content), 1: dw += */
+/* dW[K][C][T] for g [N,K,QD,QH,QW] on the strided grid and x [N,C,ID,IH,IW] on the dense grid.  With caller scratch `ws` of
+ * dpf_conv_wgrad_workspace_floats(T, C, K) floats eligible shapes (16-byte aligned rows, 3x3 / 3x3x3 kernels, dilation 1) run without float
+ * atomics -- partial tiles are reduced in a fixed order, so the gradient is bitwise reproducible; other shapes, and every shape with
+ * ws == NULL, use the first-generation kernel (float atomics).  accumulate = 0: dw is overwritten (any content), 1: dw += */
 long long dpf_conv_wgrad_workspace_floats(int T, int C, int K);
 int dpf_conv_wgrad_ws(const float* g, const float* x, float* dw, float* ws, long long ws_floats, int N, int C, int ID, int IH, int IW, int K,
                       int QD, int QH, int QW, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw_,
@@ -107,7 +103,7 @@ int dpf_bn_finalize_partials(double* slab, int parts, int C, long long count, fl
                              float* running_var, float* mean, float* invstd, void* stream);
 
 /* narrow outputs (K <= 4): the 32 -> 1 cost heads (modules.py:286-296) and the 32 -> 3 normal conv (normal_module.py:65);
- * same conventions as dpf_conv_forward / dpf_conv_wgrad, direct (non-MFMA) HBM-bound kernels */
+ * same conventions as dpf_conv_forward / dpf_conv_wgrad_ws, direct (non-MFMA) HBM-bound kernels */
 int dpf_conv_smallk_forward(const float* x, const float* w, const float* bias, float* out, int N, int C, int ID, int IH, int IW, int K, int kd,
                             int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd, int dh, int dw, void* stream);
 /* data gradient of the same shapes (replaces cuDNN's dgrad behind the 32 -> 1 cost heads, modules.py:331-337, and the 32 -> 3 normal
@@ -148,39 +144,27 @@ int dpf_maxpool2d_backward(const float* g, const int* idx, float* dx, int N, int
 int dpf_bn_stats(const float* x, int N, int C, long long S, float eps, float momentum, float* running_mean, float* running_var,
                  float* mean, float* invstd, float* ws, void* stream);
 int dpf_bn_eval_stats(const float* running_mean, const float* running_var, int C, float eps, float* mean, float* invstd, void* stream);
+/* y = act((x - mean) * invstd * w + b + res) + res2; mean == NULL: activation / adds only.  y_channels == 0 (and y_c0 == 0): y is the dense
+ * [N, C, S].  Otherwise y is the channel slice [y_c0, y_c0 + C) of a wider [N, y_channels, S] tensor: the normalised branches of a
+ * torch.cat(dim=1) are written straight into the concatenated tensor (DPBlock.conv_dilate, modules.py:43-45); a slice that does not fit
+ * is DPF_ERR_INVALID_ARG.  The backward reads dy the same way (dy_channels, dy_c0): the gradient of the concatenation. */
 int dpf_norm_act_forward(const float* x, const float* mean, const float* invstd, const float* w, const float* b, int wmod,
-                         const float* res, const float* res2, int act, const float* slope, float slope_const, float* y, int N, int C,
-                         long long S, void* stream);
-int dpf_norm_act_backward(const float* x, const float* dy, const float* mean, const float* invstd, const float* w, const float* b,
-                          int wmod, const float* res, int act, const float* slope, float slope_const, int training, float* dx,
-                          float* dres, float* dweight, float* dbias, float* dslope, float* ws, int N, int C, long long S, void* stream);
-/* the same pair with y / dy given as a channel slice of a wider tensor: the normalised branches of a torch.cat(dim=1) are written
- * straight into the concatenated tensor and their gradients read from its gradient (DPBlock.conv_dilate, modules.py:43-45) */
-int dpf_norm_act_forward_slice(const float* x, const float* mean, const float* invstd, const float* w, const float* b, int wmod,
-                               const float* res, const float* res2, int act, const float* slope, float slope_const, float* y, int y_channels,
-                               int y_c0, int N, int C, long long S, void* stream);
-int dpf_norm_act_backward_slice(const float* x, const float* dy, int dy_channels, int dy_c0, const float* mean, const float* invstd,
-                                const float* w, const float* b, int wmod, const float* res, int act, const float* slope, float slope_const,
-                                int training, float* dx, float* dres, float* dweight, float* dbias, float* dslope, float* ws, int N, int C,
-                                long long S, void* stream);
+                         const float* res, const float* res2, int act, const float* slope, float slope_const, float* y, int y_channels,
+                         int y_c0, int N, int C, long long S, void* stream);
 /* SyncBatchNorm (the reference enables torch SyncBatchNorm under DDP: config_manager.py:57, main.py:55).  Statistics: each rank
  * computes dpf_bn_local_moments -> moments[2*C] = {mean, M2}; the host all-gathers them (RCCL) and dpf_bn_merge_moments produces
- * the global mean / invstd and the running-statistics update.  Backward: dpf_norm_act_backward_ex phase 1 (local reductions
+ * the global mean / invstd and the running-statistics update.  Backward: dpf_norm_act_backward phase 1 (local reductions
  * into ws + parameter gradients), host all-reduce(sum) of ws[3*C], phase 2 (dx / dres) with count = global N*S.
- * phase 0 = everything; phase 3 = everything with a ws the caller guarantees to be zero (no memset: slots of a pre-zeroed arena). */
+ * phase 0 = everything; phase 3 = everything with a ws the caller guarantees to be zero (no memset: slots of a pre-zeroed arena).
+ * Branches that wrote channel slices of one concatenated tensor run the phases on their slices of dy, so their exchanges travel in one
+ * collective. */
 int dpf_bn_local_moments(const float* x, int N, int C, long long S, float* moments, float* ws, void* stream);
 int dpf_bn_merge_moments(const float* moments, const float* counts, int W, int C, float eps, float momentum, float* running_mean,
                          float* running_var, float* mean, float* invstd, void* stream);
-int dpf_norm_act_backward_ex(const float* x, const float* dy, const float* mean, const float* invstd, const float* w, const float* b,
-                             int wmod, const float* res, int act, const float* slope, float slope_const, int training, float* dx,
-                             float* dres, float* dweight, float* dbias, float* dslope, float* ws, int N, int C, long long S, int phase,
-                             double count, void* stream);
-/* dpf_norm_act_backward_slice with the phases of dpf_norm_act_backward_ex: SyncBatchNorm of branches that wrote channel slices of one
- * concatenated tensor (DPBlock.conv_dilate, modules.py:43-45) -- their exchanges travel in one collective */
-int dpf_norm_act_backward_slice_ex(const float* x, const float* dy, int dy_channels, int dy_c0, const float* mean, const float* invstd,
-                                   const float* w, const float* b, int wmod, const float* res, int act, const float* slope, float slope_const,
-                                   int training, float* dx, float* dres, float* dweight, float* dbias, float* dslope, float* ws, int N, int C,
-                                   long long S, int phase, double count, void* stream);
+int dpf_norm_act_backward(const float* x, const float* dy, int dy_channels, int dy_c0, const float* mean, const float* invstd, const float* w,
+                          const float* b, int wmod, const float* res, int act, const float* slope, float slope_const, int training, float* dx,
+                          float* dres, float* dweight, float* dbias, float* dslope, float* ws, int N, int C, long long S, int phase,
+                          double count, void* stream);
 int dpf_channel_sum(const float* g, float* out, int N, int C, long long S, void* stream);
 
 /* ---- resampling: F.interpolate(bilinear, align_corners=True) (modules.py:127-128, normal_module.py:22-29), FPN's
@@ -195,37 +179,28 @@ int dpf_upsample_nearest_backward(const float* g, float* dtop, long long NC, int
 
 /* ---- dual-pixel cost volume: subpixel_shift.forward (src/module/asm/asm.py:87-127), MaskingAttention tail
  * (asm.py:162-171), CostVolume.build_concat_volume (src/model/stereodpnet/modules.py:181-197); PSMNet volume
- * (src/model/psmnet/modules.py:215-262).  Sampler tables: iy/wy [3][2][h], ix/wx [3][2][w] (device). */
-int dpf_shift_triple_forward(const float* fea, float* out, const int* iy, const float* wy, const int* ix, const float* wx, int B, int C,
-                             int h, int w, void* stream);
-int dpf_shift_triple_backward(const float* g, float* dfea, const int* iy, const float* wy, const int* ix, const float* wx, int B, int C,
-                              int h, int w, void* stream);
-/* deterministic adjoint of dpf_shift_triple_forward in gather form: iy_inv / ix_inv [3][2][2][h|w] are the inverse tap tables (the up to two
- * output coordinates that read a given source coordinate through tap (mode, a), -1 padded), wy / wx as in forward */
-int dpf_shift_triple_backward_gather(const float* g, float* dfea, const int* iy_inv, const float* wy, const int* ix_inv, const float* wx,
-                                     int B, int C, int h, int w, void* stream);
+ * (src/model/psmnet/modules.py:215-262).  Sampler tables: iy/wy [M][2][h], ix/wx [M][2][w] (device). */
+/* The M = 1, 2 or 3 row-shifted copies (the enabled ones of nearest / bilinear / phase, in the reference's order:
+ * src/model/stereodpnet/config.json): out [B, C, M, h, w], tables [M][2][h|w].  backward_gather is the deterministic adjoint in gather form:
+ * iy_inv / ix_inv [M][2][2][h|w] are the inverse tap tables (the up to two output coordinates that read a given source coordinate through
+ * tap (mode, a), -1 padded), wy / wx as in forward. */
+int dpf_shift_copies_forward(const float* fea, float* out, const int* iy, const float* wy, const int* ix, const float* wx, int B, int C,
+                             int M, int h, int w, void* stream);
+int dpf_shift_copies_backward_gather(const float* g, float* dfea, const int* iy_inv, const float* wy, const int* ix_inv, const float* wx,
+                                     int B, int C, int M, int h, int w, void* stream);
 /* fractional Fourier-phase row shift of `planes` [h, w] planes (asm.py:59-75,112-125; only reached with per-level shifts):
  * dst[p][y][x] = sum_y' mr[(y - y') mod h] src[p][y'][x] + scale (-1)^y sum_x' hm[(x - x') mod w] sum_y' (-1)^y' src[p][y'][x'].
  * mr [h], hm [w]: device tables; tbuf: planes * w floats of scratch; plane strides in floats (dst may be the phase slot of the
  * [B,C,M,h,w] copies).  The adjoint is the same call with index-reversed tables. */
 int dpf_phase_shift(const float* src, long long src_plane_stride, float* dst, long long dst_plane_stride, const float* mr, const float* hm,
                     float scale, float* tbuf, long long planes, int h, int w, void* stream);
-int dpf_cv_select_forward(const float* x3, const float* s, float* vol, int B, int C, int h, int w, int CV, int L, int choff,
-                          unsigned levels, void* stream);
-int dpf_cv_select_backward(const float* x3, const float* s, const float* dvol, float* dx3, float* ds, int B, int C, int h, int w, int CV,
-                           int L, int choff, unsigned levels, void* stream);
-/* The same two stages for the ASM ablations (src/model/stereodpnet/config.json: nearest / bilinear / phase, feature_fetch): M = 1, 2 or 3
- * enabled shift modes in the reference's order, out / x / s [B, C, M, h, w], tables [M][2][h|w] (inverse tables [M][2][2][h|w]).
- * fetch = 0: vol = mean_m z_m with z_m = x_m softmax_M(s)_m; fetch = 1: the variance mean_m z_m^2 - (mean_m z_m)^2 (asm.py:165-169).
- * M = 3, fetch = 0 runs the kernels of the entry points above. */
-int dpf_shift_copies_forward(const float* fea, float* out, const int* iy, const float* wy, const int* ix, const float* wx, int B, int C,
-                             int M, int h, int w, void* stream);
-int dpf_shift_copies_backward_gather(const float* g, float* dfea, const int* iy_inv, const float* wy, const int* ix_inv, const float* wx,
-                                     int B, int C, int M, int h, int w, void* stream);
-int dpf_cv_select_m_forward(const float* x, const float* s, float* vol, int B, int C, int M, int h, int w, int CV, int L, int choff,
-                            unsigned levels, int fetch, void* stream);
-int dpf_cv_select_m_backward(const float* x, const float* s, const float* dvol, float* dx, float* ds, int B, int C, int M, int h, int w,
-                             int CV, int L, int choff, unsigned levels, int fetch, void* stream);
+/* MaskingAttention's tail over the M copies x / s [B, C, M, h, w], written into channels [choff, choff + C) of every level of vol
+ * [B, CV, L, h, w] whose bit is set in `levels`.  fetch = 0: vol = mean_m z_m with z_m = x_m softmax_M(s)_m; fetch = 1 (feature_fetch): the
+ * variance mean_m z_m^2 - (mean_m z_m)^2 (asm.py:165-169). */
+int dpf_cv_select_forward(const float* x, const float* s, float* vol, int B, int C, int M, int h, int w, int CV, int L, int choff,
+                          unsigned levels, int fetch, void* stream);
+int dpf_cv_select_backward(const float* x, const float* s, const float* dvol, float* dx, float* ds, int B, int C, int M, int h, int w,
+                           int CV, int L, int choff, unsigned levels, int fetch, void* stream);
 int dpf_psm_volume_forward(const float* ref, const float* tar, float* vol, const int* shifts_host, int B, int C, int h, int w, int L,
                            int groups, void* stream);
 
@@ -244,19 +219,14 @@ int dpf_avg_pool2d_forward(const float* x, float* y, long long NC, int H, int W,
 int dpf_avg_pool2d_backward(const float* g, float* dx, long long NC, int H, int W, int k, void* stream);
 
 /* ---- disparity head: trilinear x4 + softmax + soft-argmin (modules.py:327-334,341-362) ---------------------------- */
-int dpf_softargmin_forward(const float* logits, float* pred, float* prob, const float* disp_host, int B, int D, int h, int w, int L,
-                           int H, int W, void* stream);
+/* logits [B, D, h, w] -> pred [B, H, W] and prob [B, L, H, W] (NULL: not wanted); disp_host: the L hypothesis values.  align_corners picks the
+ * convention of the x4 trilinear upsampling (0: src/model/nnet/mainmodel.py:150-153).  prob_batch_stride (floats): 0 = prob is the dense
+ * volume; otherwise the distance between samples -- head i of n fills slice [:, i] of a [B, n, L, H, W] tensor -- and a stride below L H W is
+ * DPF_ERR_INVALID_ARG.  backward: dlogits (cleared by the call) from gpred [B, H, W]. */
+int dpf_softargmin_forward(const float* logits, float* pred, float* prob, long long prob_batch_stride, const float* disp_host, int B, int D,
+                           int h, int w, int L, int H, int W, int align_corners, void* stream);
 int dpf_softargmin_backward(const float* logits, const float* gpred, float* dlogits, const float* disp_host, int B, int D, int h, int w,
-                            int L, int H, int W, void* stream);
-
-/* the same head with the x4 trilinear upsampling in either convention (align_corners = 0: src/model/nnet/mainmodel.py:150-153) */
-int dpf_softargmin_forward_ex(const float* logits, float* pred, float* prob, const float* disp_host, int B, int D, int h, int w, int L,
-                              int H, int W, int align_corners, void* stream);
-/* forward with the probability volume written at a batch stride: head i of n fills slice [:, i] of a [B, n, L, H, W] tensor */
-int dpf_softargmin_forward_strided(const float* logits, float* pred, float* prob, long long prob_batch_stride, const float* disp_host, int B,
-                                   int D, int h, int w, int L, int H, int W, int align_corners, void* stream);
-int dpf_softargmin_backward_ex(const float* logits, const float* gpred, float* dlogits, const float* disp_host, int B, int D, int h, int w,
-                               int L, int H, int W, int align_corners, void* stream);
+                            int L, int H, int W, int align_corners, void* stream);
 
 /* ---- deterministic mode (SURVEY section 5 "race detection"; the reference scatters with float atomics, deform_im2col_cuda.cuh:313-331, and
  * is not reproducible either).  0 (default; environment DPF_DETERMINISTIC=1 changes the default): partial results of overlapping tiles /
@@ -287,11 +257,12 @@ int dpf_debug_clock_probe(unsigned long long* out4, int spin_us, void* stream);
  * SPEED: the grouped path is a gather tier (samples from global memory, grad_input through global atomics), several times slower than the
  * single-group tiers at the same size (profiles/grouped_dcn_timings.txt).
  * WORKSPACE: the two queries below take whole C and K and are sufficient for every grouping.
- * grad_input_channels (the _ex entry) counts channels of the whole input tensor: channels at or beyond it stay zero whatever conv or
+ * grad_input_channels (an extension to the reference's argument list) counts channels of the whole input tensor: grad_input is produced
+ * only for input channels [0, grad_input_channels), channels at or beyond it stay zero whatever conv or
  * deformable group they are in.  A grouped call stores each grad_offset element exactly once (bitwise reproducible in every mode); its
  * grad_input and grad_weight are reproducible under dpf_set_deterministic(1) like the single-group ones. */
 long long dpf_deform_conv3d_workspace_floats(int C, int K, int T);
-/* workspace of dpf_deform_conv3d_backward* for this problem: the above, plus (deterministic mode only) the integer shadow of grad_input */
+/* workspace of dpf_deform_conv3d_backward for this problem: the above, plus (deterministic mode only) the integer shadow of grad_input */
 long long dpf_deform_conv3d_backward_workspace_floats(int B, int C, int D, int H, int W, int K, int T);
 int dpf_deform_conv3d_forward(const float* input, const float* weight, const float* bias, const float* offset, float* output, float* ws,
                               int B, int C, int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph,
@@ -299,13 +270,7 @@ int dpf_deform_conv3d_forward(const float* input, const float* weight, const flo
 int dpf_deform_conv3d_backward(const float* input, const float* weight, const float* bias, const float* offset, const float* grad_output,
                                float* grad_input, float* grad_offset, float* grad_weight, float* grad_bias, float* ws, int B, int C,
                                int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd,
-                               int dh, int dw, int group, int deformable_group, int im2col_step, void* stream);
-
-/* extension: grad_input only for input channels [0, grad_input_channels) (the rest of the zero-initialised tensor stays 0) */
-int dpf_deform_conv3d_backward_ex(const float* input, const float* weight, const float* bias, const float* offset, const float* grad_output,
-                                  float* grad_input, float* grad_offset, float* grad_weight, float* grad_bias, float* ws, int B, int C,
-                                  int D, int H, int W, int K, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int dd,
-                                  int dh, int dw, int group, int deformable_group, int im2col_step, int grad_input_channels, void* stream);
+                               int dh, int dw, int group, int deformable_group, int im2col_step, int grad_input_channels, void* stream);
 
 /* ---- deformable conv2d, plain (DCN v1) and modulated (v2): the reference's pybind module `deform_conv_cuda`
  * (src/module/dcn/src/deform_conv_cuda.cpp:687-697 over src/deform_conv_cuda_kernel.cu:190,279,373,570,635,695; DeformConv / DeformConvPack /
@@ -389,28 +354,21 @@ int dpf_loss_backward(const float* pred_depth, const float* pred_normal, const f
  * variance term per head); out: one device float.  The backward writes every element of dpred (0 under the mask); where the reciprocal was
  * replaced by 0 the gradient is 0 (the reference's autograd gives NaN there).  gout: one device float.  Refusals launch nothing:
  * DPF_ERR_INVALID_ARG for n < 1, n > 8, an unknown kind or transform, a NULL required pointer, B, H or W <= 0 or a workspace that is
- * too small; DPF_ERR_UNSUPPORTED for B > 65535. */
+ * too small; DPF_ERR_UNSUPPORTED for B > 65535.
+ * ab [B, 2] = [b, a] or NULL.  With ab the target is formed from a depth map (the 'least_square' conversion, src/loss/depth/smoothL1.py:28-30):
+ * `target` is then the depth [B, H, W] and per pixel in fp32 target = a / depth + b, divide then add, NaN and +-Inf replaced by -100
+ * (src/utils/geometry.py:64-69), then everything as above.  ab is data: no gradient is formed for it. */
 #define DPF_LOSS_SMOOTHL1 0
 #define DPF_LOSS_SILOG 1
 #define DPF_LOSS_T_IDENTITY 0
 #define DPF_LOSS_T_RECIPROCAL 1
 long long dpf_depth_loss_workspace_bytes(int B, int H, int W);
-int dpf_depth_loss_forward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, int B,
-                           int n, int H, int W, const float* head_weights_host, float variance_focus, void* ws, long long ws_bytes,
-                           double* stats, float* out, void* stream);
-int dpf_depth_loss_backward(int kind, int transform, const float* pred, const float* target, const float* mask, const float* conf, int B,
-                            int n, int H, int W, const float* head_weights_host, float variance_focus, const double* stats,
-                            const float* gout, float* dpred, void* stream);
-/* The same two passes with the target formed from a depth map (the 'least_square' conversion, src/loss/depth/smoothL1.py:28-30): depth
- * [B, H, W] takes the place of target and ab [B, 2] = [b, a] comes with it; per pixel in fp32 target = a / depth + b, divide then add, NaN
- * and +-Inf replaced by -100 (src/utils/geometry.py:64-69), then everything as above.  ab is data: no gradient is formed for it.  Same
- * workspace, stats record and refusals, and DPF_ERR_INVALID_ARG for a NULL ab. */
-int dpf_depth_loss_forward_ab(int kind, int transform, const float* pred, const float* depth, const float* ab, const float* mask,
-                              const float* conf, int B, int n, int H, int W, const float* head_weights_host, float variance_focus, void* ws,
-                              long long ws_bytes, double* stats, float* out, void* stream);
-int dpf_depth_loss_backward_ab(int kind, int transform, const float* pred, const float* depth, const float* ab, const float* mask,
-                               const float* conf, int B, int n, int H, int W, const float* head_weights_host, float variance_focus,
-                               const double* stats, const float* gout, float* dpred, void* stream);
+int dpf_depth_loss_forward(int kind, int transform, const float* pred, const float* target, const float* ab, const float* mask,
+                           const float* conf, int B, int n, int H, int W, const float* head_weights_host, float variance_focus, void* ws,
+                           long long ws_bytes, double* stats, float* out, void* stream);
+int dpf_depth_loss_backward(int kind, int transform, const float* pred, const float* target, const float* ab, const float* mask,
+                            const float* conf, int B, int n, int H, int W, const float* head_weights_host, float variance_focus,
+                            const double* stats, const float* gout, float* dpred, void* stream);
 
 /* ---- robust affine fit (csrc/affine_fit.hip): src/utils/geometry.py::regress_affine on the device -----------------------------------
  * Per sample the line y = A x + B between x = idepth [B, H, W] and y = head 0 of pred (a contiguous H W plane per sample,
@@ -429,6 +387,7 @@ int dpf_depth_loss_backward_ab(int kind, int transform, const float* pred, const
 long long dpf_affine_fit_workspace_bytes(int B, int H, int W);
 int dpf_affine_fit(const float* pred, long long pred_batch_stride, const float* idepth, int B, int H, int W, double f_scale, int max_iters,
                    double tol, void* ws, long long ws_bytes, float* ab, double* info, void* stream);
+/* the nine optimiser entry points stay separate: the *_hyper / *_lr / *_ctl forms each refuse a NULL scalar pointer of their own */
 int dpf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, int step, double lr, double beta1,
                   double beta2, double eps, float gscale, void* stream);
 /* the same update with the two step-dependent scalars { (float)(lr / (1 - beta1^step)), (float)(1 / sqrt(1 - beta2^step)) } read from device

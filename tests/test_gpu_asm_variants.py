@@ -183,34 +183,33 @@ def test_instance_norm_prelu_gate():
         close(a, r, 2e-4, 'in + prelu ' + nm)
 
 
-def test_default_path_same_bits_through_new_and_old_entry_points():
-    """M = 3 without fetch: dpf_shift_copies_* / dpf_cv_select_m_* return the bits of dpf_shift_triple_* / dpf_cv_select_*."""
+def test_default_path_same_bits_through_new_and_old_entry_points(golden_dir):
+    """M = 3 without fetch: dpf_shift_copies_* / dpf_cv_select_* return the bits the M = 3-only entry points they replaced returned.
+    tests/golden/asm_default_path_bits.npz holds what those returned for these shapes and seeds, recorded on an MI355X from the library
+    of commit 947c290 (the last one that had them)."""
     from dualpixelface_amd._lib import lib
     from dualpixelface_amd.ops import _ptr, _stream
     from dualpixelface_amd.sampler_tables import build_shift_tables
+    rec = {k: torch.from_numpy(v).to(DEV) for k, v in np.load(golden_dir + '/asm_default_path_bits.npz').items()}
     B, C, h, w, L = 2, 5, 10, 13, 8
     iy, wy, ix, wx, iyi, ixi = (t.to(DEV) for t in build_shift_tables(h, w, -1.0))
     fea = rnd(B, C, h, w, seed=1).to(DEV)
-    a, b_ = torch.empty(B, C, 3, h, w, device=DEV), torch.empty(B, C, 3, h, w, device=DEV)
-    lib().call('dpf_shift_triple_forward', _ptr(fea), _ptr(a), _ptr(iy), _ptr(wy), _ptr(ix), _ptr(wx), B, C, h, w, _stream())
+    b_ = torch.empty(B, C, 3, h, w, device=DEV)
     lib().call('dpf_shift_copies_forward', _ptr(fea), _ptr(b_), _ptr(iy), _ptr(wy), _ptr(ix), _ptr(wx), B, C, 3, h, w, _stream())
-    assert torch.equal(a, b_)
+    assert torch.equal(rec['shift_forward'], b_)
     g = rnd(B, C, 3, h, w, seed=2).to(DEV)
-    da, db = torch.empty_like(fea), torch.empty_like(fea)
-    lib().call('dpf_shift_triple_backward_gather', _ptr(g), _ptr(da), _ptr(iyi), _ptr(wy), _ptr(ixi), _ptr(wx), B, C, h, w, _stream())
+    db = torch.empty_like(fea)
     lib().call('dpf_shift_copies_backward_gather', _ptr(g), _ptr(db), _ptr(iyi), _ptr(wy), _ptr(ixi), _ptr(wx), B, C, 3, h, w, _stream())
-    assert torch.equal(da, db)
+    assert torch.equal(rec['shift_backward_gather'], db)
     x, s = rnd(B, C, 3, h, w, seed=3).to(DEV), torch.sigmoid(rnd(B, C, 3, h, w, seed=4)).to(DEV)
-    va, vb = torch.zeros(B, 2 * C, L, h, w, device=DEV), torch.zeros(B, 2 * C, L, h, w, device=DEV)
-    lib().call('dpf_cv_select_forward', _ptr(x), _ptr(s), _ptr(va), B, C, h, w, 2 * C, L, C, 0xA5, _stream())
-    lib().call('dpf_cv_select_m_forward', _ptr(x), _ptr(s), _ptr(vb), B, C, 3, h, w, 2 * C, L, C, 0xA5, 0, _stream())
-    assert torch.equal(va, vb) and float(va.abs().max()) > 0
+    vb = torch.zeros(B, 2 * C, L, h, w, device=DEV)
+    lib().call('dpf_cv_select_forward', _ptr(x), _ptr(s), _ptr(vb), B, C, 3, h, w, 2 * C, L, C, 0xA5, 0, _stream())
+    assert torch.equal(rec['cv_select_forward'], vb) and float(vb.abs().max()) > 0
     dv = rnd(B, 2 * C, L, h, w, seed=5).to(DEV)
-    outs = [torch.empty_like(x) for _ in range(4)]
-    lib().call('dpf_cv_select_backward', _ptr(x), _ptr(s), _ptr(dv), _ptr(outs[0]), _ptr(outs[1]), B, C, h, w, 2 * C, L, C, 0xA5, _stream())
-    lib().call('dpf_cv_select_m_backward', _ptr(x), _ptr(s), _ptr(dv), _ptr(outs[2]), _ptr(outs[3]), B, C, 3, h, w, 2 * C, L, C, 0xA5, 0,
+    outs = [torch.empty_like(x) for _ in range(2)]
+    lib().call('dpf_cv_select_backward', _ptr(x), _ptr(s), _ptr(dv), _ptr(outs[0]), _ptr(outs[1]), B, C, 3, h, w, 2 * C, L, C, 0xA5, 0,
                _stream())
-    assert torch.equal(outs[0], outs[2]) and torch.equal(outs[1], outs[3])
+    assert torch.equal(rec['cv_select_backward_dx'], outs[0]) and torch.equal(rec['cv_select_backward_ds'], outs[1])
 
 
 # ------------------------------------------------------------------------------------------------ end to end against the reference

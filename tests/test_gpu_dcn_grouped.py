@@ -213,7 +213,8 @@ def test_refused_groupings_write_nothing(C, K, group, dg):
     with pytest.raises(DpfError, match='DPF_ERR_INVALID_ARG'):
         L.call('dpf_deform_conv3d_forward', ptr(x), ptr(w), ptr(b), ptr(off), ptr(out), ptr(ws), *geo, st)
     with pytest.raises(DpfError, match='DPF_ERR_INVALID_ARG'):
-        L.call('dpf_deform_conv3d_backward', ptr(x), ptr(w), ptr(b), ptr(off), ptr(go), ptr(gi), ptr(goff), ptr(gw), ptr(gb), ptr(ws), *geo, st)
+        L.call('dpf_deform_conv3d_backward', ptr(x), ptr(w), ptr(b), ptr(off), ptr(go), ptr(gi), ptr(goff), ptr(gw), ptr(gb), ptr(ws), *geo, C,
+               st)
     torch.cuda.synchronize()
     for t in (out, gi, goff, gw, gb):
         assert (t == -7.25).all()

@@ -190,10 +190,10 @@ def test_abi_refuses_bad_arguments(n, kind, transform):
     weights = (ctypes.c_float * 9)(*([1.0] * 9))
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     with pytest.raises(DpfError, match='DPF_ERR_INVALID_ARG'):
-        lib().call('dpf_depth_loss_forward', kind, transform, ptr(pred), ptr(target), None, None, B, n, H, W, weights, 0.85, ptr(ws), nbytes,
+        lib().call('dpf_depth_loss_forward', kind, transform, ptr(pred), ptr(target), None, None, None, B, n, H, W, weights, 0.85, ptr(ws), nbytes,
                    ptr(stats), ptr(out), stream)
     with pytest.raises(DpfError, match='DPF_ERR_INVALID_ARG'):
-        lib().call('dpf_depth_loss_backward', kind, transform, ptr(pred), ptr(target), None, None, B, n, H, W, weights, 0.85, ptr(stats),
+        lib().call('dpf_depth_loss_backward', kind, transform, ptr(pred), ptr(target), None, None, None, B, n, H, W, weights, 0.85, ptr(stats),
                    ptr(out), ptr(dpred), stream)
     torch.cuda.synchronize()
     assert float(out) == -7.0 and bool((stats == -7.0).all()) and bool((dpred == -7.0).all()) and bool((ws == 0).all())
@@ -215,10 +215,10 @@ def test_abi_refuses_missing_pointers():
                  (pred, target, ws, stats, None)):
         p, t, w_, s, o = args
         with pytest.raises(DpfError, match='DPF_ERR_INVALID_ARG'):
-            lib().call('dpf_depth_loss_forward', 0, 0, ptr(p), ptr(t), None, None, B, n, H, W, weights, 0.0, ptr(w_), nbytes, ptr(s), ptr(o),
+            lib().call('dpf_depth_loss_forward', 0, 0, ptr(p), ptr(t), None, None, None, B, n, H, W, weights, 0.0, ptr(w_), nbytes, ptr(s), ptr(o),
                        stream)
     with pytest.raises(DpfError, match='DPF_ERR_INVALID_ARG'):            # a workspace that is too small
-        lib().call('dpf_depth_loss_forward', 0, 0, ptr(pred), ptr(target), None, None, B, n, H, W, weights, 0.0, ptr(ws), nbytes - 8, ptr(stats),
+        lib().call('dpf_depth_loss_forward', 0, 0, ptr(pred), ptr(target), None, None, None, B, n, H, W, weights, 0.0, ptr(ws), nbytes - 8, ptr(stats),
                    ptr(out), stream)
     assert lib().call('dpf_depth_loss_workspace_bytes', 0, H, W) == -1
 

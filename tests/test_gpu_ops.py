@@ -1507,7 +1507,7 @@ def test_diff_volume():
 
 
 def test_norm_act_concat_matches_separate_norm_and_cat():
-    """BatchNorm branches written straight into their slice of the concatenation (dpf_norm_act_*_slice) against
+    """BatchNorm branches written straight into their slice of the concatenation (y_channels / dy_channels of dpf_norm_act_*) against
     torch.cat([batch_norm(x_i)]) with autograd, training and eval, running statistics included."""
     ops = _ops()
     N, H, W = 2, 12, 20
