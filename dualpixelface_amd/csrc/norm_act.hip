@@ -32,14 +32,26 @@ __device__ __forceinline__ float red_block_sum(double v, float* sm4) {
   return (float)((smd[0] + smd[1]) + (smd[2] + smd[3]));
 }
 
-// sums[c] = { sum(x - K_c), sum((x - K_c)^2) } with the shift K_c = x[0, c, 0] (single pass, cancellation-safe)
+// The shift K_c of the single-pass statistics: the median of the first, middle and last element of sample 0's row.  The pass is free of
+// cancellation as long as K_c lies within a few standard deviations of the channel's mean, and no single element can move the median
+// away from the other two (with one element as the shift, an outlier there costs every element of its channel 2 - 4 digits:
+// tests/test_gpu_norm_act.py::test_hard_statistics_batch_norm).
+// bn_stats_kernel, bn_finalize_kernel and bn_local_moments_kernel all read it here, so they cannot disagree.
+__device__ __forceinline__ float bn_shift(const float* __restrict__ x, int c, long long S) {
+  const float* xr = x + (long long)c * S;
+  const float a = xr[0], b = xr[S / 2], d = xr[S - 1];
+  return fmaxf(fminf(a, b), fminf(fmaxf(a, b), d));
+}
+
+// sums[c] = { sum(x - K_c), sum((x - K_c)^2) } with K_c = bn_shift(): single pass; safe against a common offset of the channel (the
+// differences are small and exact) and against any one atypical element, not against a channel whose three probes are all atypical
 template <bool DET>
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, float* __restrict__ sums, int N, int C, long long S,
                                                        int chunk) {
   __shared__ float sm[8];
   typedef typename RedAcc<DET>::type acc_t;
   const int c = blockIdx.y % C;
-  const float K = x[(long long)c * S];
+  const float K = bn_shift(x, c, S);
   acc_t a = 0, b = 0;
   for (int row = blockIdx.y; row < (DET ? N * C : blockIdx.y + 1); row += C) {   // row = n*C + c
     const float* xr = x + (long long)row * S;
@@ -74,7 +86,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ x, const float* __r
                                    float* __restrict__ mean, float* __restrict__ invstd) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const double K = x[(long long)c * S];
+  const double K = bn_shift(x, c, S);
   const double m1 = sums[2 * c] / count;
   double var = sums[2 * c + 1] / count - m1 * m1;
   if (var < 0) var = 0;
@@ -150,7 +162,7 @@ __global__ void bn_local_moments_kernel(const float* __restrict__ x, const float
                                         float* __restrict__ moments) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const double K = x[(long long)c * S];
+  const double K = bn_shift(x, c, S);
   const double m1 = sums[2 * c] / count;
   double m2 = sums[2 * c + 1] - count * m1 * m1;
   if (m2 < 0) m2 = 0;
