@@ -1,0 +1,518 @@
+// The two label-free losses (loss_type 'photometric' and 'smoothness'; losses.PHOTOMETRICLoss / SMOOTHNESSLoss, ops.photometric_loss /
+// ops.smoothness_loss): the target view warped onto the reference view by the predicted displacement and compared
+// with it, and the edge-aware first-order smoothness of the prediction, each with a hand-written gradient into the prediction.  Every
+// fp32 expression is written operation by operation under -ffp-contract=off, so that tests/photometric_cpu.py restates the warped
+// values and the counted map bit for bit.
+//
+//   Y        (0.299 R + 0.587 G) + 0.114 B of the de-normalised image, R = x_0 std_0 + mean_0 and so on (postprocess.hip's definition)
+//   D        pred (target types 0, 1) or a / pred + b (2; pred <= 0 is not usable)
+//   sample   sx = x + shift_x D, sy = y + shift_y D
+//   warpable pred finite (and > 0 for type 2), mask NULL or > 0, 0 <= sx <= W - 1 and 0 <= sy <= H - 1
+//   J        bilinear sample of Y_tgt: x0 = floor(sx), fx = sx - x0, x1 = min(x0 + 1, W - 1), likewise in y;
+//            top = v00 + fx (v01 - v00), bot = v10 + fx (v11 - v10), J = top + fy (bot - top); 0 where not warpable
+//   counted  the 3 x 3 window lies in the image and its nine pixels are warpable
+//   window   i = I - I_centre, j = J - I_centre; sums of i, j, i i, j j, i j over the nine pixels in row-major order; m = sum / 9,
+//            mu = I_centre + m, var = mean of squares - m^2, cov = mean of products - m_I m_J
+//   term     alpha clamp((1 - SSIM) / 2, 0, 1) + (1 - alpha) sqrt((J - I)^2 + eps^2) at the centre
+//   loss     sum_h w_h (sum terms_h / count_h), 0 for a head with count_h = 0
+//
+// Photometric forward: a luminance launch fills the caller's two planes, then one workgroup per 32 x 8 tile of one head of one sample
+// (I, J and the warpable flag in LDS with a halo of 1) leaves one row (term sum, count) of fp64 in the workspace, and one workgroup
+// folds the rows head by head (dpf_reduce.h).  Backward: a gather.  The workgroup warps its tile with a halo of 2, evaluates the windows
+// of the tile and a halo of 1 -- d term / d J_k of a window is c0 + cI (I_k - mu_I) + cJ (J_k - mu_J), five numbers per window, zeros for
+// a window that is not counted -- then every pixel adds what the nine windows through it owe it in row-major order, then the intensity term of its own
+// window, and multiplies by d J / d D = shift_x d_x + shift_y d_y of its bilinear sample (the piecewise, right-sided derivative) and
+// d D / d pred.  Windows on a tile edge are recomputed by both neighbours from the same inputs by the same instructions: no scratch, no
+// atomics, and the bits repeat.  Samples are gathered from global memory wherever the displacement sends them.
+//
+//   pairs    (p, p + x^) and (p, p + y^); usable: both pred finite and both masks > 0
+//   term     sqrt((pred_q - pred_p)^2 + eps^2) exp(-(gamma |Y_q - Y_p|))
+//   loss     sum_h w_h (sum x-pairs / count_x,h + sum y-pairs / count_y,h)
+//
+// Smoothness forward: luminance launch, one workgroup per 32 x 8 tile leaves (x sum, x count, y sum, y count), one workgroup folds.
+// Backward: every pixel gathers its left, right, upper and lower pair, in that order.
+#include "dpf_common.h"
+#include "dpf_reduce.h"
+#include <math.h>
+
+extern "C" long long dpf_photometric_workspace_bytes(int B, int n, int H, int W);
+extern "C" long long dpf_smoothness_workspace_bytes(int B, int n, int H, int W);
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kTW = 32, kTH = 8;               // output tile, one pixel per thread
+constexpr int kMaxHeads = 8;
+constexpr int kMaxGridZ = 65535;               // B n rides on gridDim.z, the 2 B luminance planes on gridDim.y
+constexpr int kMaxTileRows = 65535;            // the tile rows on gridDim.y
+constexpr float kC1 = 0.0001f, kC2 = 0.0009f;  // 0.01^2, 0.03^2
+constexpr float kLumaR = 0.299f, kLumaG = 0.587f, kLumaB = 0.114f;
+
+struct Norm { float mean[3], std[3]; };
+struct HeadW { float w[kMaxHeads]; };
+
+struct Photo {
+  const float* pred;       // [B, n, H, W]
+  const float* yref;       // [B, H, W]   luminance of the reference view
+  const float* ytgt;       // [B, H, W]   luminance of the target view
+  const float* ab;         // [B, 2] or NULL (types 0, 1)
+  const float* mask;       // [B, H, W] or NULL
+  int n, H, W, target_type;
+  float sx, sy, alpha, eps;
+};
+
+struct Smooth {
+  const float* pred;       // [B, n, H, W]
+  const float* y;          // [B, H, W]   luminance of the guide
+  const float* mask;       // [B, H, W] or NULL
+  int n, H, W;
+  float gamma, eps;
+};
+
+// grid (blocks over H W, planes): plane p of out [planes][HW] from the image p of img [planes][3][HW]
+__global__ __launch_bounds__(256) void luma_kernel(const float* __restrict__ img0, const float* __restrict__ img1, int B, long long HW, Norm nm,
+                                                   float* __restrict__ out) {
+  const int p = blockIdx.y;
+  const float* __restrict__ g = (p < B ? img0 + (size_t)p * 3 * HW : img1 + (size_t)(p - B) * 3 * HW);
+  float* __restrict__ o = out + (size_t)p * HW;
+  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < HW; i += (long long)gridDim.x * kBlock) {
+    const float r = g[i] * nm.std[0] + nm.mean[0], gr = g[i + HW] * nm.std[1] + nm.mean[1], b = g[i + 2 * HW] * nm.std[2] + nm.mean[2];
+    o[i] = (kLumaR * r + kLumaG * gr) + kLumaB * b;
+  }
+}
+
+// the warp of pixel (y, x), which lies in the image: -> warpable; J, and where asked the derivative of J with respect to pred
+__device__ __forceinline__ bool warp_at(const Photo& g, const float* __restrict__ predh, const float* __restrict__ yt, size_t sbase, float a,
+                                        float b, int y, int x, float& J, float* dJdpred) {
+  J = 0.f;
+  const size_t o = (size_t)y * g.W + x;
+  const float p = predh[o];
+  if (!dpf_finite_f(p)) return false;
+  if (g.mask && !(g.mask[sbase + o] > 0.f)) return false;
+  float D = p;
+  if (g.target_type == 2) {
+    if (!(p > 0.f)) return false;
+    D = a / p + b;
+  }
+  const float sx = (float)x + g.sx * D, sy = (float)y + g.sy * D;
+  if (!(sx >= 0.f && sx <= (float)(g.W - 1) && sy >= 0.f && sy <= (float)(g.H - 1))) return false;
+  const float fx0 = floorf(sx), fy0 = floorf(sy);
+  const float fx = sx - fx0, fy = sy - fy0;
+  const int x0 = min((int)fx0, g.W - 1), y0 = min((int)fy0, g.H - 1);      // (the clamp acts only where W - 1 is no fp32 number)
+  const int x1 = min(x0 + 1, g.W - 1), y1 = min(y0 + 1, g.H - 1);
+  const float* __restrict__ r0 = yt + (size_t)y0 * g.W;
+  const float* __restrict__ r1 = yt + (size_t)y1 * g.W;
+  const float v00 = r0[x0], v01 = r0[x1], v10 = r1[x0], v11 = r1[x1];
+  const float dt = v01 - v00, db = v11 - v10;
+  const float top = v00 + fx * dt, bot = v10 + fx * db;
+  const float dv = bot - top;
+  J = top + fy * dv;
+  if (dJdpred) {
+    const float gx = dt + fy * (db - dt);
+    float dD = 1.f;                                        // d D / d pred = -a / pred^2
+    if (g.target_type == 2) dD = -(a / (p * p));
+    *dJdpred = (g.sx * gx + g.sy * dv) * dD;
+  }
+  return true;
+}
+
+struct Window {
+  float muI, muJ, vI, vJ, cov, A1, A2, B1, B2, ssim;
+};
+
+// the window whose centre is (ly, lx) of the LDS tiles (row pitch LW): sums in row-major order of the values less the centre's I, so
+// that the variances are differences of small numbers
+template <int LW>
+__device__ __forceinline__ void window_of(const float* __restrict__ tI, const float* __restrict__ tJ, int ly, int lx, Window& w) {
+  const float c = tI[ly * LW + lx];
+  float sI = 0.f, sJ = 0.f, sII = 0.f, sJJ = 0.f, sIJ = 0.f;
+#pragma unroll
+  for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) {
+      const float i = tI[(ly + dy) * LW + lx + dx] - c, j = tJ[(ly + dy) * LW + lx + dx] - c;
+      sI = sI + i;
+      sJ = sJ + j;
+      sII = sII + i * i;
+      sJJ = sJJ + j * j;
+      sIJ = sIJ + i * j;
+    }
+  const float mI = sI / 9.f, mJ = sJ / 9.f;
+  w.muI = c + mI, w.muJ = c + mJ;
+  w.vI = sII / 9.f - mI * mI;
+  w.vJ = sJJ / 9.f - mJ * mJ;
+  w.cov = sIJ / 9.f - mI * mJ;
+  w.A1 = (2.f * w.muI) * w.muJ + kC1;
+  w.A2 = 2.f * w.cov + kC2;
+  w.B1 = (w.muI * w.muI + w.muJ * w.muJ) + kC1;
+  w.B2 = (w.vI + w.vJ) + kC2;
+  w.ssim = (w.A1 * w.A2) / (w.B1 * w.B2);
+}
+
+template <int LW>
+__device__ __forceinline__ bool all_nine(const unsigned char* __restrict__ tw, int ly, int lx) {
+  bool ok = true;
+#pragma unroll
+  for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) ok = ok && tw[(ly + dy) * LW + lx + dx];
+  return ok;
+}
+
+// grid (ceil(W / 32), ceil(H / 8), B n), 256 threads = 8 rows x 32 columns.  part: [n][B tiles][2]
+__global__ __launch_bounds__(256) void photo_forward_kernel(Photo g, double* __restrict__ part, float* __restrict__ warped_out,
+                                                            unsigned char* __restrict__ counted_out) {
+  constexpr int LW = kTW + 2, LH = kTH + 2;
+  __shared__ float tI[LH * LW], tJ[LH * LW];
+  __shared__ unsigned char tw[LH * LW];
+  const int t = threadIdx.x;
+  const int s = blockIdx.z / g.n, h = blockIdx.z - s * g.n;
+  const size_t HW = (size_t)g.H * g.W, sbase = (size_t)s * HW;
+  const float* __restrict__ predh = g.pred + ((size_t)s * g.n + h) * HW;
+  const float* __restrict__ yr = g.yref + sbase;
+  const float* __restrict__ yt = g.ytgt + sbase;
+  const float b = g.target_type == 2 ? g.ab[2 * (size_t)s] : 0.f, a = g.target_type == 2 ? g.ab[2 * (size_t)s + 1] : 0.f;
+  const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+  for (int i = t; i < LH * LW; i += kBlock) {
+    const int ly = i / LW, lx = i - ly * LW;
+    const int y = y0 - 1 + ly, x = x0 - 1 + lx;
+    float I = 0.f, J = 0.f;
+    bool ok = false;
+    if (y >= 0 && y < g.H && x >= 0 && x < g.W) {
+      I = yr[(size_t)y * g.W + x];
+      ok = warp_at(g, predh, yt, sbase, a, b, y, x, J, nullptr);
+    }
+    tI[i] = I, tJ[i] = J, tw[i] = ok ? 1 : 0;
+  }
+  __syncthreads();
+  const int tx = t & (kTW - 1), ty = t / kTW;
+  const int x = x0 + tx, y = y0 + ty;
+  double acc[2] = {0.0, 0.0};
+  if (x < g.W && y < g.H) {
+    const int ly = ty + 1, lx = tx + 1;
+    const bool counted = x >= 1 && x + 1 < g.W && y >= 1 && y + 1 < g.H && all_nine<LW>(tw, ly, lx);
+    if (counted) {
+      Window w;
+      window_of<LW>(tI, tJ, ly, lx, w);
+      const float ds = fminf(fmaxf((1.f - w.ssim) / 2.f, 0.f), 1.f);
+      const float d = tJ[ly * LW + lx] - tI[ly * LW + lx];
+      const float ch = sqrtf(d * d + g.eps * g.eps);
+      acc[0] = (double)(g.alpha * ds + (1.f - g.alpha) * ch);
+      acc[1] = 1.0;
+    }
+    if (warped_out) {
+      const size_t o = ((size_t)s * g.n + h) * HW + (size_t)y * g.W + x;
+      warped_out[o] = tJ[ly * LW + lx];
+      counted_out[o] = counted ? 1 : 0;
+    }
+  }
+  const size_t tiles = (size_t)gridDim.x * gridDim.y, rows = (size_t)(gridDim.z / g.n) * tiles;
+  const size_t row = (size_t)h * rows + (size_t)s * tiles + (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+  dpf_block_reduce_d<2>(acc, part + row * 2);
+}
+
+// one block: folds the rows of every head in a fixed order, writes the stats record and the loss.  A row holds NP (sum, count) pairs;
+// stats: for pair q the counts at [16 q, 16 q + 8) and the sums at [16 q + 8, 16 q + 16)
+template <int NP>
+__global__ __launch_bounds__(256) void fold_kernel(const double* __restrict__ part, long long rows, int n, HeadW hw, double* __restrict__ stats,
+                                                   float* __restrict__ out) {
+  __shared__ double tot[2 * NP];
+  double loss = 0.0;
+  for (int k = 0; k < kMaxHeads; ++k) {
+    double sum[NP], cnt[NP];
+#pragma unroll
+    for (int q = 0; q < NP; ++q) sum[q] = 0.0, cnt[q] = 0.0;
+    if (k < n) {
+      dpf_fold_rows_d<2 * NP>(part + (size_t)k * (size_t)rows * 2 * NP, rows, 2 * NP, tot);
+#pragma unroll
+      for (int q = 0; q < NP; ++q) {
+        sum[q] = tot[2 * q], cnt[q] = tot[2 * q + 1];
+        if (cnt[q] > 0.0) loss += (double)hw.w[k] * (sum[q] / cnt[q]);
+      }
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int q = 0; q < NP; ++q) {
+        stats[2 * kMaxHeads * q + k] = cnt[q];
+        stats[2 * kMaxHeads * q + kMaxHeads + k] = sum[q];
+      }
+    }
+  }
+  if (threadIdx.x == 0) out[0] = (float)loss;
+}
+
+// grid as the forward's
+__global__ __launch_bounds__(256) void photo_backward_kernel(Photo g, HeadW hw, const double* __restrict__ stats, const float* __restrict__ gout,
+                                                             float* __restrict__ dpred) {
+  constexpr int ZW = kTW + 4, ZH = kTH + 4;               // I, J, warpable: halo 2
+  constexpr int CW = kTW + 2, CH = kTH + 2;               // windows: halo 1
+  __shared__ float tI[ZH * ZW], tJ[ZH * ZW];
+  __shared__ unsigned char tw[ZH * ZW];
+  __shared__ float coef[5][CH * CW];
+  const int t = threadIdx.x;
+  const int s = blockIdx.z / g.n, h = blockIdx.z - s * g.n;
+  const size_t HW = (size_t)g.H * g.W, sbase = (size_t)s * HW;
+  const float* __restrict__ predh = g.pred + ((size_t)s * g.n + h) * HW;
+  const float* __restrict__ yr = g.yref + sbase;
+  const float* __restrict__ yt = g.ytgt + sbase;
+  const float b = g.target_type == 2 ? g.ab[2 * (size_t)s] : 0.f, a = g.target_type == 2 ? g.ab[2 * (size_t)s + 1] : 0.f;
+  const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+  for (int i = t; i < ZH * ZW; i += kBlock) {
+    const int ly = i / ZW, lx = i - ly * ZW;
+    const int y = y0 - 2 + ly, x = x0 - 2 + lx;
+    float I = 0.f, J = 0.f;
+    bool ok = false;
+    if (y >= 0 && y < g.H && x >= 0 && x < g.W) {
+      I = yr[(size_t)y * g.W + x];
+      ok = warp_at(g, predh, yt, sbase, a, b, y, x, J, nullptr);
+    }
+    tI[i] = I, tJ[i] = J, tw[i] = ok ? 1 : 0;
+  }
+  __syncthreads();
+  for (int i = t; i < CH * CW; i += kBlock) {
+    const int cy = i / CW, cx = i - cy * CW;
+    const int y = y0 - 1 + cy, x = x0 - 1 + cx;
+    const int ly = cy + 1, lx = cx + 1;
+    float c0 = 0.f, cI = 0.f, cJ = 0.f, mI = 0.f, mJ = 0.f;
+    if (x >= 1 && x + 1 < g.W && y >= 1 && y + 1 < g.H && all_nine<ZW>(tw, ly, lx)) {
+      Window w;
+      window_of<ZW>(tI, tJ, ly, lx, w);
+      const float ds = (1.f - w.ssim) / 2.f;
+      if (ds >= 0.f && ds <= 1.f) {
+        // d ssim / d J_k = (2 / 9) (muI A2 / (B1 B2) - ssim muJ / B1 + A1 / (B1 B2) (I_k - muI) - ssim / B2 (J_k - muJ)), and
+        // d term / d ssim = -alpha / 2
+        const float k = -(g.alpha / 9.f);
+        const float den = w.B1 * w.B2;
+        c0 = k * ((w.muI * w.A2) / den - (w.ssim * w.muJ) / w.B1);
+        cI = k * (w.A1 / den);
+        cJ = -(k * (w.ssim / w.B2));
+        mI = w.muI, mJ = w.muJ;
+      }
+    }
+    coef[0][i] = c0, coef[1][i] = cI, coef[2][i] = cJ, coef[3][i] = mI, coef[4][i] = mJ;
+  }
+  __syncthreads();
+  const int tx = t & (kTW - 1), ty = t / kTW;
+  const int x = x0 + tx, y = y0 + ty;
+  if (x >= g.W || y >= g.H) return;                        // (no barrier below)
+  const int ly = ty + 2, lx = tx + 2, cy = ty + 1, cx = tx + 1;
+  float out = 0.f;
+  if (tw[ly * ZW + lx]) {
+    const float I = tI[ly * ZW + lx], J = tJ[ly * ZW + lx];
+    float sum = 0.f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+      for (int dx = -1; dx <= 1; ++dx) {
+        const int c = (cy + dy) * CW + cx + dx;
+        sum = sum + ((coef[0][c] + coef[1][c] * (I - coef[3][c])) + coef[2][c] * (J - coef[4][c]));
+      }
+    if (x >= 1 && x + 1 < g.W && y >= 1 && y + 1 < g.H && all_nine<ZW>(tw, ly, lx)) {
+      const float d = J - I;
+      sum = sum + (1.f - g.alpha) * (d / sqrtf(d * d + g.eps * g.eps));
+    }
+    if (sum != 0.f) {
+      float dJ = 0.f, Jagain;
+      warp_at(g, predh, yt, sbase, a, b, y, x, Jagain, &dJ);
+      const double cnt = stats[h];
+      const float wk = cnt > 0.0 ? (float)((double)hw.w[h] / cnt) : 0.f;
+      out = ((sum * dJ) * wk) * gout[0];
+    }
+  }
+  dpred[((size_t)s * g.n + h) * HW + (size_t)y * g.W + x] = out;
+}
+
+// ---- smoothness
+__device__ __forceinline__ bool smooth_ok(const Smooth& g, const float* __restrict__ predh, size_t sbase, size_t o) {
+  return dpf_finite_f(predh[o]) && (!g.mask || g.mask[sbase + o] > 0.f);
+}
+
+// the pair (p, q), both usable: its term, and where asked d term / d pred_q (= -d term / d pred_p)
+__device__ __forceinline__ float pair_term(const Smooth& g, const float* __restrict__ predh, const float* __restrict__ ys, size_t p, size_t q,
+                                           float* dq) {
+  const float d = predh[q] - predh[p];
+  const float r = sqrtf(d * d + g.eps * g.eps);
+  const float w = expf(-(g.gamma * fabsf(ys[q] - ys[p])));
+  if (dq) *dq = (d / r) * w;
+  return r * w;
+}
+
+// grid (ceil(W / 32), ceil(H / 8), B n).  part: [n][B tiles][4] = (x sum, x count, y sum, y count)
+__global__ __launch_bounds__(256) void smooth_forward_kernel(Smooth g, double* __restrict__ part) {
+  const int t = threadIdx.x;
+  const int s = blockIdx.z / g.n, h = blockIdx.z - s * g.n;
+  const size_t HW = (size_t)g.H * g.W, sbase = (size_t)s * HW;
+  const float* __restrict__ predh = g.pred + ((size_t)s * g.n + h) * HW;
+  const float* __restrict__ ys = g.y + sbase;
+  const int x = blockIdx.x * kTW + (t & (kTW - 1)), y = blockIdx.y * kTH + t / kTW;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  if (x < g.W && y < g.H) {
+    const size_t o = (size_t)y * g.W + x;
+    if (smooth_ok(g, predh, sbase, o)) {
+      if (x + 1 < g.W && smooth_ok(g, predh, sbase, o + 1)) acc[0] = (double)pair_term(g, predh, ys, o, o + 1, nullptr), acc[1] = 1.0;
+      if (y + 1 < g.H && smooth_ok(g, predh, sbase, o + g.W)) acc[2] = (double)pair_term(g, predh, ys, o, o + g.W, nullptr), acc[3] = 1.0;
+    }
+  }
+  const size_t tiles = (size_t)gridDim.x * gridDim.y, rows = (size_t)(gridDim.z / g.n) * tiles;
+  const size_t row = (size_t)h * rows + (size_t)s * tiles + (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+  dpf_block_reduce_d<4>(acc, part + row * 4);
+}
+
+// grid as the forward's, no LDS
+__global__ __launch_bounds__(256) void smooth_backward_kernel(Smooth g, HeadW hw, const double* __restrict__ stats, const float* __restrict__ gout,
+                                                              float* __restrict__ dpred) {
+  const int t = threadIdx.x;
+  const int s = blockIdx.z / g.n, h = blockIdx.z - s * g.n;
+  const size_t HW = (size_t)g.H * g.W, sbase = (size_t)s * HW;
+  const float* __restrict__ predh = g.pred + ((size_t)s * g.n + h) * HW;
+  const float* __restrict__ ys = g.y + sbase;
+  const int x = blockIdx.x * kTW + (t & (kTW - 1)), y = blockIdx.y * kTH + t / kTW;
+  if (x >= g.W || y >= g.H) return;
+  const size_t o = (size_t)y * g.W + x;
+  float out = 0.f;
+  if (smooth_ok(g, predh, sbase, o)) {
+    const double cx = stats[h], cy = stats[2 * kMaxHeads + h];
+    const float wx = cx > 0.0 ? (float)((double)hw.w[h] / cx) : 0.f, wy = cy > 0.0 ? (float)((double)hw.w[h] / cy) : 0.f;
+    float sx = 0.f, sy = 0.f, d;
+    if (x >= 1 && smooth_ok(g, predh, sbase, o - 1)) pair_term(g, predh, ys, o - 1, o, &d), sx = sx + d;
+    if (x + 1 < g.W && smooth_ok(g, predh, sbase, o + 1)) pair_term(g, predh, ys, o, o + 1, &d), sx = sx - d;
+    if (y >= 1 && smooth_ok(g, predh, sbase, o - g.W)) pair_term(g, predh, ys, o - g.W, o, &d), sy = sy + d;
+    if (y + 1 < g.H && smooth_ok(g, predh, sbase, o + g.W)) pair_term(g, predh, ys, o, o + g.W, &d), sy = sy - d;
+    out = (sx * wx + sy * wy) * gout[0];
+  }
+  dpred[((size_t)s * g.n + h) * HW + o] = out;
+}
+
+bool shape_ok(int B, int n, int H, int W) { return B > 0 && n >= 1 && n <= kMaxHeads && H > 0 && W > 0; }
+
+long long tile_rows(int B, int n, int H, int W) {
+  if ((long long)B * n > kMaxGridZ || 2LL * B > kMaxGridZ || dpf_div_up(H, kTH) > kMaxTileRows || (long long)H * W > 0x7fffffffLL) return -1;
+  return (long long)n * B * dpf_div_up(H, kTH) * dpf_div_up(W, kTW);
+}
+
+void norm_of(const float* norm_host, Norm& nm) {
+  for (int c = 0; c < 3; ++c) nm.mean[c] = norm_host[c], nm.std[c] = norm_host[3 + c];
+}
+
+int launch_luma(const float* img0, const float* img1, int B, int planes, long long HW, const Norm& nm, float* out, hipStream_t st) {
+  long long blocks = (HW + kBlock - 1) / kBlock;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(luma_kernel, dim3((unsigned)blocks, planes), dim3(kBlock), 0, st, img0, img1, B, HW, nm, out);
+  return 0;
+}
+
+// argument checks shared by the photometric entry points; fills g and hw (the luminance planes are the caller's)
+int prepare_photo(const float* pred, const float* ref_rgb, const float* tgt_rgb, const float* ab, const float* mask, int B, int n, int H, int W,
+                  int target_type, float shift_x, float shift_y, float alpha, float eps, const float* norm_host, const float* weights,
+                  const float* luma, Photo& g, HeadW& hw) {
+  if (!pred || !ref_rgb || !tgt_rgb || !norm_host || !weights || !luma || !shape_ok(B, n, H, W) || target_type < 0 || target_type > 2 ||
+      (target_type == 2 && !ab) || !(alpha >= 0.f && alpha <= 1.f) || !(eps > 0.f) || !isfinite(eps) || !isfinite(shift_x) ||
+      !isfinite(shift_y) || (shift_x == 0.f && shift_y == 0.f))
+    return DPF_ERR_INVALID_ARG;
+  if (tile_rows(B, n, H, W) < 0) return DPF_ERR_UNSUPPORTED;
+  g.pred = pred, g.yref = luma, g.ytgt = luma + (size_t)B * H * W, g.ab = ab, g.mask = mask;
+  g.n = n, g.H = H, g.W = W, g.target_type = target_type, g.sx = shift_x, g.sy = shift_y, g.alpha = alpha, g.eps = eps;
+  for (int k = 0; k < kMaxHeads; ++k) hw.w[k] = k < n ? weights[k] : 0.f;
+  return DPF_OK;
+}
+
+int prepare_smooth(const float* pred, const float* guide_rgb, const float* mask, int B, int n, int H, int W, float gamma, float eps,
+                   const float* norm_host, const float* weights, const float* luma, Smooth& g, HeadW& hw) {
+  if (!pred || !guide_rgb || !norm_host || !weights || !luma || !shape_ok(B, n, H, W) || !(gamma >= 0.f) || !isfinite(gamma) || !(eps > 0.f) ||
+      !isfinite(eps))
+    return DPF_ERR_INVALID_ARG;
+  if (tile_rows(B, n, H, W) < 0) return DPF_ERR_UNSUPPORTED;
+  g.pred = pred, g.y = luma, g.mask = mask, g.n = n, g.H = H, g.W = W, g.gamma = gamma, g.eps = eps;
+  for (int k = 0; k < kMaxHeads; ++k) hw.w[k] = k < n ? weights[k] : 0.f;
+  return DPF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+long long dpf_photometric_workspace_bytes(int B, int n, int H, int W) {
+  if (!shape_ok(B, n, H, W) || tile_rows(B, n, H, W) < 0) return -1;
+  return tile_rows(B, n, H, W) * 2 * (long long)sizeof(double);
+}
+
+long long dpf_smoothness_workspace_bytes(int B, int n, int H, int W) {
+  if (!shape_ok(B, n, H, W) || tile_rows(B, n, H, W) < 0) return -1;
+  return tile_rows(B, n, H, W) * 4 * (long long)sizeof(double);
+}
+
+int dpf_photometric_forward(const float* pred, const float* ref_rgb, const float* tgt_rgb, const float* ab, const float* mask, int B, int n,
+                            int H, int W, int target_type, float shift_x, float shift_y, float alpha, float eps, const float* norm_host,
+                            const float* head_weights_host, void* ws, long long ws_bytes, float* luma, double* stats, float* out,
+                            float* warped_out, unsigned char* counted_out, void* stream) {
+  dpf_clear_error();
+  Photo g;
+  HeadW hw;
+  const int rc = prepare_photo(pred, ref_rgb, tgt_rgb, ab, mask, B, n, H, W, target_type, shift_x, shift_y, alpha, eps, norm_host,
+                               head_weights_host, luma, g, hw);
+  if (rc != DPF_OK) return rc;
+  if (!stats || !out || (warped_out != nullptr) != (counted_out != nullptr) ||
+      !dpf_ws_ok(ws, ws_bytes, dpf_photometric_workspace_bytes(B, n, H, W), 8))
+    return DPF_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  Norm nm;
+  norm_of(norm_host, nm);
+  launch_luma(ref_rgb, tgt_rgb, B, 2 * B, (long long)H * W, nm, luma, st);
+  const dim3 grid(dpf_div_up(W, kTW), dpf_div_up(H, kTH), B * n), block(kBlock);
+  double* part = (double*)ws;
+  hipLaunchKernelGGL(photo_forward_kernel, grid, block, 0, st, g, part, warped_out, counted_out);
+  hipLaunchKernelGGL(fold_kernel<1>, dim3(1), block, 0, st, (const double*)part, (long long)B * grid.x * grid.y, n, hw, stats, out);
+  return dpf_check_launch();
+}
+
+int dpf_photometric_backward(const float* pred, const float* ref_rgb, const float* tgt_rgb, const float* ab, const float* mask, int B, int n,
+                             int H, int W, int target_type, float shift_x, float shift_y, float alpha, float eps, const float* norm_host,
+                             const float* head_weights_host, const float* luma, const double* stats, const float* gout, float* dpred,
+                             void* stream) {
+  dpf_clear_error();
+  Photo g;
+  HeadW hw;
+  const int rc = prepare_photo(pred, ref_rgb, tgt_rgb, ab, mask, B, n, H, W, target_type, shift_x, shift_y, alpha, eps, norm_host,
+                               head_weights_host, luma, g, hw);
+  if (rc != DPF_OK) return rc;
+  if (!stats || !gout || !dpred) return DPF_ERR_INVALID_ARG;
+  const dim3 grid(dpf_div_up(W, kTW), dpf_div_up(H, kTH), B * n), block(kBlock);
+  hipLaunchKernelGGL(photo_backward_kernel, grid, block, 0, (hipStream_t)stream, g, hw, stats, gout, dpred);
+  return dpf_check_launch();
+}
+
+int dpf_smoothness_forward(const float* pred, const float* guide_rgb, const float* mask, int B, int n, int H, int W, float gamma, float eps,
+                           const float* norm_host, const float* head_weights_host, void* ws, long long ws_bytes, float* luma, double* stats,
+                           float* out, void* stream) {
+  dpf_clear_error();
+  Smooth g;
+  HeadW hw;
+  const int rc = prepare_smooth(pred, guide_rgb, mask, B, n, H, W, gamma, eps, norm_host, head_weights_host, luma, g, hw);
+  if (rc != DPF_OK) return rc;
+  if (!stats || !out || !dpf_ws_ok(ws, ws_bytes, dpf_smoothness_workspace_bytes(B, n, H, W), 8)) return DPF_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  Norm nm;
+  norm_of(norm_host, nm);
+  launch_luma(guide_rgb, guide_rgb, B, B, (long long)H * W, nm, luma, st);
+  const dim3 grid(dpf_div_up(W, kTW), dpf_div_up(H, kTH), B * n), block(kBlock);
+  double* part = (double*)ws;
+  hipLaunchKernelGGL(smooth_forward_kernel, grid, block, 0, st, g, part);
+  hipLaunchKernelGGL(fold_kernel<2>, dim3(1), block, 0, st, (const double*)part, (long long)B * grid.x * grid.y, n, hw, stats, out);
+  return dpf_check_launch();
+}
+
+int dpf_smoothness_backward(const float* pred, const float* guide_rgb, const float* mask, int B, int n, int H, int W, float gamma, float eps,
+                            const float* norm_host, const float* head_weights_host, const float* luma, const double* stats,
+                            const float* gout, float* dpred, void* stream) {
+  dpf_clear_error();
+  Smooth g;
+  HeadW hw;
+  const int rc = prepare_smooth(pred, guide_rgb, mask, B, n, H, W, gamma, eps, norm_host, head_weights_host, luma, g, hw);
+  if (rc != DPF_OK) return rc;
+  if (!stats || !gout || !dpred) return DPF_ERR_INVALID_ARG;
+  const dim3 grid(dpf_div_up(W, kTW), dpf_div_up(H, kTH), B * n), block(kBlock);
+  hipLaunchKernelGGL(smooth_backward_kernel, grid, block, 0, (hipStream_t)stream, g, hw, stats, gout, dpred);
+  return dpf_check_launch();
+}
+
+}  // extern "C"

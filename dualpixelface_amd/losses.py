@@ -5,7 +5,7 @@ Class names follow the reference's lookup rule ``<NAME.upper()>Loss`` (loss_sele
 """
 import torch
 
-from . import normal_geo, ops
+from . import normal_geo, ops, photometric
 
 
 TARGET_TYPES = ('disp', 'depth', 'idepth')
@@ -136,7 +136,62 @@ class NORMAL_GEOLoss(_DepthLoss):
         return out
 
 
-_BANK = {'smoothL1': SMOOTHL1Loss, 'silog': SILOGLoss, 'cosine': COSINELoss, 'normal_geo': NORMAL_GEOLoss}
+class _LabelFreeLoss(object):
+    """What the two label-free losses share (not in the reference; DESIGN.md section 7, csrc/photometric.hip): the settings of the model
+    config block photometric (photometric.settings), one weight per prediction head, and the two views, swapped under dataset.flip_lr
+    as the training branch of core._views swaps them.  Neither reads a label, so neither refuses a dp_conversion."""
+    name = None
+
+    def __init__(self, option):
+        self.settings = photometric.settings(option)
+        self.weights = list(option.model.loss_weight)
+        self.flip = bool(option.dataset.flip_lr)
+
+    def head_weights(self, n):
+        return [1.0] if n == 1 else self.weights[:n]
+
+    def views(self, batch):
+        """(reference view, target view)"""
+        for key in ('left', 'right'):
+            if key not in batch:
+                raise NotImplementedError("the %r loss needs batch[%r], which is missing from the batch" % (self.name, key))
+        return (batch['right'], batch['left']) if self.flip else (batch['left'], batch['right'])
+
+
+class PHOTOMETRICLoss(_LabelFreeLoss):
+    """The photometric loss: the target view warped by the displacement every head of pred_depth predicts against the reference view.
+    (a, b) is needed for target_type 'depth' only: batch['abvalue'], else the fit, as in NORMAL_GEOLoss."""
+    name = 'photometric'
+
+    def forward(self, preds, batch, target_type='disp'):
+        assert target_type in TARGET_TYPES
+        ref, tgt = self.views(batch)
+        pd = preds['pred_depth']
+        out, ab = {}, None
+        if target_type == 'depth':
+            ab = out['abvalue'] = _fit(preds, batch) if takes_least_square(batch) else batch['abvalue']
+        s = self.settings
+        out['loss'] = ops.photometric_loss(pd, ref, tgt, ab=ab, mask=batch.get('mask'), head_weights=self.head_weights(pd.shape[1]),
+                                           target_type=target_type, shift=s.shift, alpha=s.alpha, eps=s.charbonnier_eps)
+        return out
+
+
+class SMOOTHNESSLoss(_LabelFreeLoss):
+    """The edge-aware smoothness of every head of pred_depth under the luminance of the reference view."""
+    name = 'smoothness'
+
+    def forward(self, preds, batch, target_type='disp'):
+        assert target_type in TARGET_TYPES
+        ref, _ = self.views(batch)
+        pd = preds['pred_depth']
+        s = self.settings
+        return {'loss': ops.smoothness_loss(pd, ref, mask=batch.get('mask'), head_weights=self.head_weights(pd.shape[1]),
+                                            gamma=s.smooth_gamma, eps=s.charbonnier_eps)}
+
+
+LABEL_FREE = ('photometric', 'smoothness')
+_BANK = {'smoothL1': SMOOTHL1Loss, 'silog': SILOGLoss, 'cosine': COSINELoss, 'normal_geo': NORMAL_GEOLoss, 'photometric': PHOTOMETRICLoss,
+         'smoothness': SMOOTHNESSLoss}
 
 
 class loss_selector(object):
@@ -152,6 +207,10 @@ class loss_selector(object):
 
     def least_square(self, batch):
         return takes_least_square(batch)
+
+    def label_free(self):
+        """Every configured loss is one of the two that read no label: a batch of only the two views trains."""
+        return bool(self.loss_name) and all(name in LABEL_FREE for name in self.loss_name)
 
     def forward(self, results, batch, target_type='disp'):
         # shipped configuration (stereodpnet/config.json:2,4): one fused reduction pass for both losses, against the disparity the batch brings

@@ -1970,6 +1970,138 @@ def normal_geo_loss(pred, depth, normal, Kmat, ab=None, mask=None, head_weights=
     return NormalGeoFn.apply(_c(pred), held[0], held[1], held[2], held[3], held[4], cfg, bool(return_normals))
 
 
+PHOTOMETRIC_STATS = 16      # doubles: count per head [0, 8), term sum per head [8, 16)
+SMOOTHNESS_STATS = 32       # doubles: x-pair count [0, 8) and sum [8, 16), y-pair count [16, 24) and sum [24, 32)
+
+
+class PhotometricFn(torch.autograd.Function):
+    """The photometric loss (csrc/photometric.hip) -> 0-dim loss (and, for tests and tools, the warped luminance and the counted map).
+    Like NormalGeoFn: workspace, stats and the luminance planes are fresh tensors (the planes and the stats are saved for the backward, the
+    workspace is not needed again), gout is read on the device and nothing is read on the host, so the call is capturable inside the
+    train-step graph.  Only pred receives a gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, ref_rgb, tgt_rgb, ab, mask, cfg, return_warped):
+        B, n, H, W = pred.shape
+        ws, nbytes = _workspace('dpf_photometric_workspace_bytes', 'photometric_loss: shape B=%d n=%d H=%d W=%d is not supported', B, n, H, W,
+                                device=pred.device)
+        stats = torch.empty(PHOTOMETRIC_STATS, dtype=torch.float64, device=pred.device)
+        luma = torch.empty((2, B, H, W), dtype=torch.float32, device=pred.device)
+        out = torch.empty((), dtype=torch.float32, device=pred.device)
+        warped = cnt = None
+        if return_warped:
+            warped = torch.empty((B, n, H, W), dtype=torch.float32, device=pred.device)
+            cnt = torch.empty((B, n, H, W), dtype=torch.uint8, device=pred.device)
+        target_type, shift, alpha, eps, weights = cfg
+        lib().call('dpf_photometric_forward', _ptr(pred), _ptr(ref_rgb), _ptr(tgt_rgb), _ptr(ab), _ptr(mask), B, n, H, W, target_type, shift[0],
+                   shift[1], alpha, eps, _normalizer_floats(), _host_floats(weights), _ptr(ws), nbytes, _ptr(luma), _ptr(stats), _ptr(out),
+                   _ptr(warped), _ptr(cnt), _stream())
+        ctx.save_for_backward(pred, ref_rgb, tgt_rgb, ab, mask, luma, stats)
+        ctx.cfg = cfg
+        if return_warped:
+            ctx.mark_non_differentiable(warped, cnt)
+            return out, warped, cnt
+        return out
+
+    @staticmethod
+    def backward(ctx, gout, *unused):
+        pred, ref_rgb, tgt_rgb, ab, mask, luma, stats = ctx.saved_tensors
+        target_type, shift, alpha, eps, weights = ctx.cfg
+        gout = _c(gout)
+        _need(gout)
+        B, n, H, W = pred.shape
+        dpred = torch.empty_like(pred)
+        lib().call('dpf_photometric_backward', _ptr(pred), _ptr(ref_rgb), _ptr(tgt_rgb), _ptr(ab), _ptr(mask), B, n, H, W, target_type, shift[0],
+                   shift[1], alpha, eps, _normalizer_floats(), _host_floats(weights), _ptr(luma), _ptr(stats), _ptr(gout), _ptr(dpred),
+                   _stream())
+        return dpred, None, None, None, None, None, None
+
+
+def _label_free_operands(name, pred, images, ab, mask, head_weights):
+    """The operands the two label-free losses share, checked: pred [B, n, H, W], the named images [B, 3, H, W], ab [B, 2], mask [B, H, W]
+    and one weight per head -> (contiguous pred, the detached contiguous images, ab, mask, the weights as floats)."""
+    _need(pred, ab, mask, *[t for _, t in images], dtypes=_F32, contiguous=False)
+    if pred.dim() != 4:
+        raise DpfError('%s: pred %s is not [B, n, H, W]' % (name, tuple(pred.shape)))
+    B, n, H, W = pred.shape
+    for key, t in images:
+        if t is None:
+            raise DpfError('%s: %s [B, 3, H, W] is needed' % (name, key))
+    _match_pred(name, pred, *[(key, t, (B, 3, H, W)) for key, t in images], ('ab', ab, (B, 2)), ('mask', mask, (B, H, W)))
+    if len(head_weights) != n:
+        raise DpfError('%s: %d head weights for %d heads' % (name, len(head_weights), n))
+    held = [None if t is None else _c(t.detach()) for t in [t for _, t in images] + [ab, mask]]
+    return _c(pred), held[:-2], held[-2], held[-1], tuple(float(w) for w in head_weights)
+
+
+def photometric_loss(pred, ref_rgb, tgt_rgb, ab=None, mask=None, head_weights=(1.0,), target_type='disp', shift=(0.0, -2.0), alpha=0.85,
+                     eps=1e-3, return_warped=False):
+    """csrc/photometric.hip: the luminance of tgt_rgb [B, 3, H, W] sampled bilinearly at (x + shift[0] D, y + shift[1] D) against the
+    luminance of ref_rgb, for every head of pred [B, n <= 8, H, W] -> the 0-dim loss sum_h w_h mean over the counted pixels of
+    alpha clamp((1 - SSIM_3x3) / 2, 0, 1) + (1 - alpha) sqrt((J - I)^2 + eps^2).  D = pred for 'disp' / 'idepth',
+    a / pred + b for 'depth' (ab [B, 2] = [b, a], needed then only).  A pixel is counted when the nine pixels of its window are warpable:
+    pred finite, mask (None: everywhere) > 0, the sample point inside the image.  The gradient reaches pred only.  With return_warped also
+    the warped luminance [B, n, H, W] fp32 (0 where not warpable) and counted [B, n, H, W] uint8."""
+    code = _target_code('photometric_loss', target_type, ())       # the name only: here the conversion is needed the other way round,
+    if target_type == 'depth' and ab is None:                      # from a depth to the displacement
+        raise DpfError("photometric_loss: target_type 'depth' needs ab [B, 2] = [b, a]")
+    pred, (ref_rgb, tgt_rgb), ab, mask, weights = _label_free_operands('photometric_loss', pred, (('ref_rgb', ref_rgb), ('tgt_rgb', tgt_rgb)),
+                                                                       ab if target_type == 'depth' else None, mask, head_weights)
+    shift = tuple(float(v) for v in shift)
+    if len(shift) != 2 or any(v != v or v in (float('inf'), -float('inf')) for v in shift) or shift == (0.0, 0.0):
+        raise DpfError('photometric_loss: shift must be two finite numbers (x, y), not both 0, got %r' % (shift,))
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise DpfError('photometric_loss: alpha must lie in [0, 1], got %r' % (alpha,))
+    if not 0.0 < float(eps) < float('inf'):
+        raise DpfError('photometric_loss: eps must be positive, got %r' % (eps,))
+    cfg = (code, shift, float(alpha), float(eps), weights)
+    return PhotometricFn.apply(pred, ref_rgb, tgt_rgb, ab, mask, cfg, bool(return_warped))
+
+
+class SmoothnessFn(torch.autograd.Function):
+    """The edge-aware smoothness loss (csrc/photometric.hip) -> 0-dim loss; built as PhotometricFn is."""
+
+    @staticmethod
+    def forward(ctx, pred, guide_rgb, mask, cfg):
+        B, n, H, W = pred.shape
+        ws, nbytes = _workspace('dpf_smoothness_workspace_bytes', 'smoothness_loss: shape B=%d n=%d H=%d W=%d is not supported', B, n, H, W,
+                                device=pred.device)
+        stats = torch.empty(SMOOTHNESS_STATS, dtype=torch.float64, device=pred.device)
+        luma = torch.empty((B, H, W), dtype=torch.float32, device=pred.device)
+        out = torch.empty((), dtype=torch.float32, device=pred.device)
+        gamma, eps, weights = cfg
+        lib().call('dpf_smoothness_forward', _ptr(pred), _ptr(guide_rgb), _ptr(mask), B, n, H, W, gamma, eps, _normalizer_floats(),
+                   _host_floats(weights), _ptr(ws), nbytes, _ptr(luma), _ptr(stats), _ptr(out), _stream())
+        ctx.save_for_backward(pred, guide_rgb, mask, luma, stats)
+        ctx.cfg = cfg
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, guide_rgb, mask, luma, stats = ctx.saved_tensors
+        gamma, eps, weights = ctx.cfg
+        gout = _c(gout)
+        _need(gout)
+        B, n, H, W = pred.shape
+        dpred = torch.empty_like(pred)
+        lib().call('dpf_smoothness_backward', _ptr(pred), _ptr(guide_rgb), _ptr(mask), B, n, H, W, gamma, eps, _normalizer_floats(),
+                   _host_floats(weights), _ptr(luma), _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
+        return dpred, None, None, None
+
+
+def smoothness_loss(pred, guide_rgb, mask=None, head_weights=(1.0,), gamma=10.0, eps=1e-3):
+    """csrc/photometric.hip: the edge-aware first-order smoothness of every head of pred [B, n <= 8, H, W] under the luminance Y of
+    guide_rgb [B, 3, H, W] -> the 0-dim loss sum_h w_h (mean over the x-pairs + mean over the y-pairs) of
+    sqrt((pred_q - pred_p)^2 + eps^2) exp(-gamma |Y_q - Y_p|), a pair being two pixels one apart whose pred are finite and whose mask
+    (None: everywhere) is > 0.  The gradient reaches pred only."""
+    pred, (guide_rgb,), _, mask, weights = _label_free_operands('smoothness_loss', pred, (('guide_rgb', guide_rgb),), None, mask, head_weights)
+    if not 0.0 <= float(gamma) < float('inf'):
+        raise DpfError('smoothness_loss: gamma must be a finite number >= 0, got %r' % (gamma,))
+    if not 0.0 < float(eps) < float('inf'):
+        raise DpfError('smoothness_loss: eps must be positive, got %r' % (eps,))
+    return SmoothnessFn.apply(pred, guide_rgb, mask, (float(gamma), float(eps), weights))
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-5, gscale=1.0):
     _need(param, grad, exp_avg, exp_avg_sq)
     lib().call('dpf_adam_step', _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), int(step), float(lr), float(beta1),

@@ -42,7 +42,7 @@ class _PluginHooks(object):
         fitted = self.loss_model.least_square(batch) and 'depth' in batch and 'idepth' in batch
         if not self.training and postprocess.active(self.option):   # the fit and the metric hooks below see the filtered map
             postprocess.apply(self.option, results, batch, guide=self._views(batch)[0])
-        if self.training and ('disp' in batch or fitted):
+        if self.training and ('disp' in batch or fitted or self.loss_model.label_free()):     # (label-free: the two views are enough)
             results.update(self.loss_model.forward(results, batch, target_type=self._target_type()))
         elif not self.training and 'idepth' in batch and 'abvalue' not in batch and results.get('pred_depth') is not None:
             results['abvalue'] = ops.affine_fit(results['pred_depth'], batch['idepth'])       # what metrics.absolute_dp converts with

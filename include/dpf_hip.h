@@ -599,6 +599,62 @@ int dpf_normal_geo_backward(const float* pred, const float* depth, const float* 
                             const float* target_signs_host, const float* head_weights_host, const double* stats, const float* gout,
                             float* dpred, void* stream);
 
+/* ---- photometric and smoothness losses (csrc/photometric.hip; loss_type 'photometric' / 'smoothness', dualpixelface_amd/losses.py;
+ * DESIGN.md section 7): the two views of a dual-pixel pair as their own supervision.  pred [B, n <= 8, H, W]; ref_rgb, tgt_rgb,
+ * guide_rgb [B, 3, H, W], normalised images; ab [B, 2] = [b, a] (needed for target type 2 only, else NULL allowed); mask [B, H, W] or
+ * NULL; norm_host: six host floats, the Normalizer's mean then std (as dpf_guided_filter takes them); head_weights_host: n host floats;
+ * both read during the call.  luma: device floats the CALLER owns, [2, B, H, W] (photometric: reference plane, target plane) or
+ * [B, H, W] (smoothness); the forward fills it and the backward reads it, so it has to live from one to the other (ws need not).
+ *   Y        (0.299 R + 0.587 G) + 0.114 B of the de-normalised image, R = x_0 std_0 + mean_0 and so on
+ *   D        pred (target types 0, 1) or a / pred + b (type 2; pred <= 0 is not usable)
+ *   sample   (x + shift_x D, y + shift_y D)
+ *   warpable pred finite (type 2: and > 0), mask NULL or > 0, the sample point in [0, W - 1] x [0, H - 1]
+ *   J        the bilinear sample of Y_tgt: x0 = floor, fx = sx - x0, second tap clamped to the last column and row,
+ *            top = v00 + fx (v01 - v00), bot = v10 + fx (v11 - v10), J = top + fy (bot - top)
+ *   counted  the whole 3 x 3 window lies in the image and all nine pixels are warpable
+ *   SSIM     (2 mu_I mu_J + C1)(2 cov + C2) / ((mu_I^2 + mu_J^2 + C1)(var_I + var_J + C2)), box means over the nine pixels,
+ *            C1 = 0.01^2, C2 = 0.03^2
+ *   term     alpha clamp((1 - SSIM) / 2, 0, 1) + (1 - alpha) sqrt((J - I)^2 + eps^2)
+ *   loss     sum_h w_h (sum over the counted pixels of head h of term) / count_h, count_h over the whole batch; a head with
+ *            count_h = 0 adds 0
+ * dpf_photometric_forward: out[0] = the loss (fp32), stats = 16 doubles: count_h [0, 8), the term sum of head h [8, 16).  warped_out
+ * [B, n, H, W] fp32 (J, 0 where not warpable) and counted_out [B, n, H, W] uint8: both NULL or both given.  Three launches: the
+ * luminance planes, one workgroup per 32 x 8 tile leaves (term sum, count) in ws, one workgroup folds the rows head by head.  ws:
+ * dpf_photometric_workspace_bytes() bytes of 8-byte aligned device scratch (-1: shape refused); it needs no initialisation.
+ * dpf_photometric_backward: dpred [B, n, H, W], EVERY element written = gout[0] (a device float) * d loss / d pred.  One launch, a
+ * gather: each workgroup recomputes J of its tile with a halo of 2 and the windows with a halo of 1, and sums per pixel the nine
+ * windows through it in row-major order, then its own intensity term; d J / d D = shift_x d_x + shift_y d_y of the bilinear sample (the
+ * piecewise, right-sided derivative), d D / d pred = 1, 1, -a / pred^2.  Warpability, counting and the clamp's ends are constants (the
+ * clamp passes the gradient on [0, 1]); nothing flows to the images, ab or mask.  |shift| |D| is not bounded: the samples are gathered
+ * from global memory wherever they fall.
+ *   pairs    pixels one apart along x and along y; usable iff both pred are finite and both masks > 0 (or mask NULL)
+ *   term     sqrt((pred_q - pred_p)^2 + eps^2) exp(-gamma |Y_q - Y_p|)
+ *   loss     sum_h w_h (sum x-pairs / count_x,h + sum y-pairs / count_y,h), a count of 0 adds 0
+ * dpf_smoothness_forward: out[0] and stats = 32 doubles: count_x,h [0, 8), sum_x,h [8, 16), count_y,h [16, 24), sum_y,h [24, 32); ws:
+ * dpf_smoothness_workspace_bytes().  dpf_smoothness_backward: dpred, every element written; each pixel gathers its left, right, upper
+ * and lower pair in that order.
+ * No floating-point atomics, no workgroup waits for another, nothing allocates or waits on the host: the bits repeat and the calls can be
+ * captured.  Refusals launch nothing: DPF_ERR_INVALID_ARG for a NULL pointer (but mask, ab unless the target type is 2, and the optional
+ * output pair), B, H or W <= 0, n outside 1..8, a target_type outside 0..2, alpha outside [0, 1], eps <= 0 or not finite, gamma < 0 or
+ * not finite, a shift that is not finite or is (0, 0), or a workspace that is too small or misaligned; DPF_ERR_UNSUPPORTED for
+ * B n > 65535, 2 B > 65535, H W >= 2^31 or H beyond 65535 tiles of 8 rows. */
+long long dpf_photometric_workspace_bytes(int B, int n, int H, int W);
+int dpf_photometric_forward(const float* pred, const float* ref_rgb, const float* tgt_rgb, const float* ab, const float* mask, int B, int n,
+                            int H, int W, int target_type, float shift_x, float shift_y, float alpha, float eps, const float* norm_host,
+                            const float* head_weights_host, void* ws, long long ws_bytes, float* luma, double* stats, float* out,
+                            float* warped_out, unsigned char* counted_out, void* stream);
+int dpf_photometric_backward(const float* pred, const float* ref_rgb, const float* tgt_rgb, const float* ab, const float* mask, int B, int n,
+                             int H, int W, int target_type, float shift_x, float shift_y, float alpha, float eps, const float* norm_host,
+                             const float* head_weights_host, const float* luma, const double* stats, const float* gout, float* dpred,
+                             void* stream);
+long long dpf_smoothness_workspace_bytes(int B, int n, int H, int W);
+int dpf_smoothness_forward(const float* pred, const float* guide_rgb, const float* mask, int B, int n, int H, int W, float gamma, float eps,
+                           const float* norm_host, const float* head_weights_host, void* ws, long long ws_bytes, float* luma, double* stats,
+                           float* out, void* stream);
+int dpf_smoothness_backward(const float* pred, const float* guide_rgb, const float* mask, int B, int n, int H, int W, float gamma, float eps,
+                            const float* norm_host, const float* head_weights_host, const float* luma, const double* stats,
+                            const float* gout, float* dpred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
