@@ -100,6 +100,12 @@ def geometry_abvalue(batch, what):
     return batch['abvalue'].float()
 
 
+def reference_key(option):
+    """The batch key of the reference view, the one a prediction is aligned to: 'right' under dataset.flip_lr, else 'left'.  (An option
+    without a dataset block reads as not flipped.)  ArenaModule._views adds its capture-group rule to this."""
+    return 'right' if getattr(getattr(option, 'dataset', None), 'flip_lr', False) else 'left'
+
+
 def cost_levels(mindisp, maxdisp, level):
     """The quarter-resolution disparity of every cost level (stereodpnet/modules.py:144-145)."""
     step = (maxdisp / 4.0 - mindisp / 4.0) / float(level)
@@ -249,12 +255,12 @@ class ArenaModule(_Base):
     # ------------------------------------------------------------------ hooks of a model family
     def _views(self, batch):
         """(reference image, target image): left / right, swapped for the one capture group recorded the other way round (evaluation)
-        or by dataset.flip_lr (mainmodel.py:69-77 of every family)."""
+        or by dataset.flip_lr (reference_key; mainmodel.py:69-77 of every family)."""
         a, b = batch['left'], batch['right']
         if 'groupname' in batch and not self.training:
             if batch['groupname'][0] == '2020-2-9_group20':
                 a, b = b, a
-        elif self.option.dataset.flip_lr:
+        elif reference_key(self.option) == 'right':
             a, b = b, a
         return a, b
 

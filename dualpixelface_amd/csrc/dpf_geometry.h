@@ -1,4 +1,4 @@
-// The camera geometry reconstruct.hip and normal_geo.hip share, stated once (DESIGN.md section 7): Kinv, the ray of a pixel and the test
+// The camera geometry reconstruct.hip and normal_geo.hip share, stated once (DESIGN.md section 11): Kinv, the ray of a pixel and the test
 // that ties two neighbouring depths to one surface.  Every fp32 expression is written operation by operation; both files are compiled
 // with -ffp-contract=off so that the numpy restatements (tests/reconstruct_cpu.py, tests/normal_geo_cpu.py) give the same bits.
 // Kinv: the 3 x 3 adjugate over the determinant in fp64 from the fp32 K, each entry rounded to fp32 once; |det| < 1e-30 (or a non-finite

@@ -1,4 +1,4 @@
-// Gradient accumulation and global-norm clipping over the flat arenas (DESIGN.md section 7), the device side of the option keys
+// Gradient accumulation and global-norm clipping over the flat arenas (DESIGN.md section 11), the device side of the option keys
 // accumulate_grad_batches, gradient_clip_val and track_grad_norm:
 //
 //   dpf_grad_fold     acc[i] = first ? g[i] : acc[i] + g[i] in fp32 (bitwise the left-to-right sum of a group's gradients) and, when the

@@ -15,14 +15,13 @@
 // M counts the pixels with mask > 0 (every pixel without a mask).  A pixel under the mask is skipped, never multiplied by 0, so whatever
 // it holds stays out of the sums.  No clamp, as in the reference: a counted non-positive log argument or M = 0 gives NaN.
 // Sums are fp64 in two phases (no floating-point atomics): the bits repeat run to run and in every mode.  Nothing here waits on the host.
-#include "dpf_common.h"
-#include "dpf_reduce.h"
+#include "dpf_head_loss.h"      // kDpfMaxHeads and the weight fill; the fold here is kind-specific and stays
 #include <math.h>
 
 namespace {
 
 constexpr int kBlock = 256;              // threads per block of every kernel here (4 waves)
-constexpr int kMaxHeads = 8;
+constexpr int kMaxHeads = kDpfMaxHeads;
 constexpr int kItems = 4;                // loads of kVec pixels per thread before the grid stops growing
 constexpr int kMaxBlocks = 1024;         // blocks per sample: the fold reads B * kMaxBlocks rows at the most with one block
 constexpr int kMaxB = 65535;             // samples ride on gridDim.y
@@ -238,7 +237,7 @@ int prepare(int kind, int transform, const float* pred, const float* target, int
   P.HW = (long long)H * W;
   P.n = n;
   P.recip = transform == T_RECIPROCAL;
-  for (int k = 0; k < kMaxHeads; ++k) P.w[k] = k < n ? weights[k] : 0.f;
+  dpf_fill_head_weights(P.w, weights, n);
   P.vf = vf;
   return DPF_OK;
 }

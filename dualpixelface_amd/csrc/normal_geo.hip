@@ -1,4 +1,4 @@
-// The geometric-normal loss (loss_type 'normal_geo'; losses.NORMAL_GEOLoss, ops.normal_geo_loss; DESIGN.md section 7): the normals of
+// The geometric-normal loss (loss_type 'normal_geo'; losses.NORMAL_GEOLoss, ops.normal_geo_loss; DESIGN.md section 11): the normals of
 // the PREDICTED depth against the target normals, with a hand-written gradient into the prediction.  The geometry is reconstruct.hip's
 // (dpf_geometry.h), and like it every fp32 expression is written operation by operation under -ffp-contract=off, so that
 // tests/normal_geo_cpu.py restates the forward bit for bit.
@@ -23,7 +23,7 @@
 // constants of the derivative; the clamp passes the gradient on [-1, 1].
 #include "dpf_common.h"
 #include "dpf_geometry.h"
-#include "dpf_reduce.h"
+#include "dpf_head_loss.h"
 #include <math.h>
 
 extern "C" long long dpf_normal_geo_workspace_bytes(int B, int n, int H, int W);
@@ -31,11 +31,7 @@ extern "C" long long dpf_normal_geo_workspace_bytes(int B, int n, int H, int W);
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kTW = 32, kTH = 8;               // output tile, one pixel per thread
-constexpr int kMaxHeads = 8;
-constexpr int kMaxGridZ = 65535;               // B n rides on gridDim.z
-constexpr int kMaxTileRows = 65535;            // the tile rows on gridDim.y
-constexpr int kStats = 2 * kMaxHeads;          // stats record: count_h [0, 8), term sum_h [8, 16)  (doubles)
+constexpr int kTW = kDpfTileW, kTH = kDpfTileH;      // output tile, one pixel per thread (dpf_head_loss.h has the plan)
 
 struct Geo {
   const float* pred;       // [B, n, H, W]
@@ -48,8 +44,6 @@ struct Geo {
   float ratio;
   float sg[3];
 };
-
-struct HeadW { float w[kMaxHeads]; };
 
 // z_p and z_t of pixel (y, x) where it is usable, else 0 and 0; outside the image 0 and 0
 __device__ __forceinline__ void usable_depths(const Geo& g, const Cam& cam, const float* __restrict__ predh, size_t sbase, int y, int x,
@@ -169,35 +163,13 @@ __global__ __launch_bounds__(256) void geo_forward_kernel(Geo g, double* __restr
       counted_out[((size_t)s * g.n + h) * HW + o] = counted ? 1 : 0;
     }
   }
-  const size_t tiles = (size_t)gridDim.x * gridDim.y, rows = (size_t)(gridDim.z / g.n) * tiles;
-  const size_t row = (size_t)h * rows + (size_t)s * tiles + (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-  dpf_block_reduce_d<2>(acc, part + row * 2);
-}
-
-// one block: folds the rows of every head in a fixed order, writes the stats record and the loss
-__global__ __launch_bounds__(256) void geo_fold_kernel(const double* __restrict__ part, long long rows, int n, HeadW hw, double* __restrict__ stats,
-                                                       float* __restrict__ out) {
-  __shared__ double tot[2];
-  double loss = 0.0;
-  for (int k = 0; k < kMaxHeads; ++k) {
-    double sum = 0.0, cnt = 0.0;
-    if (k < n) {
-      dpf_fold_rows_d<2>(part + (size_t)k * (size_t)rows * 2, rows, 2, tot);
-      sum = tot[0], cnt = tot[1];
-      if (cnt > 0.0) loss += (double)hw.w[k] * (sum / cnt);
-    }
-    if (threadIdx.x == 0) {
-      stats[k] = cnt;
-      stats[kMaxHeads + k] = sum;
-    }
-  }
-  if (threadIdx.x == 0) out[0] = (float)loss;
+  dpf_block_reduce_d<2>(acc, part + dpf_tile_part_row(s, h, g.n) * 2);
 }
 
 // grid as the forward's.  coef: per centre of the tile and its halo of S the derivative of its term with respect to the depth its row
 // step ends at [0] and starts from [1], and its column step ends at [2] and starts from [3]
 template <int S>
-__global__ __launch_bounds__(256) void geo_backward_kernel(Geo g, HeadW hw, const double* __restrict__ stats, const float* __restrict__ gout,
+__global__ __launch_bounds__(256) void geo_backward_kernel(Geo g, DpfHeadW hw, const double* __restrict__ stats, const float* __restrict__ gout,
                                                            float* __restrict__ dpred) {
   constexpr int ZW = kTW + 4 * S, ZH = kTH + 4 * S;       // z tiles: halo 2 S
   constexpr int CW = kTW + 2 * S, CH = kTH + 2 * S;       // centres: halo S
@@ -277,8 +249,8 @@ __global__ __launch_bounds__(256) void geo_backward_kernel(Geo g, HeadW hw, cons
 
 // argument checks shared by the entry points; fills g and hw
 int prepare(const float* pred, const float* depth, const float* normal, const float* Kmat, const float* ab, const float* mask, int B, int n,
-            int H, int W, int target_type, float ratio, int step, int towards, const float* signs, const float* weights, Geo& g, HeadW& hw) {
-  if (!pred || !depth || !normal || !Kmat || !signs || !weights || B <= 0 || n < 1 || n > kMaxHeads || H <= 0 || W <= 0 || target_type < 0 ||
+            int H, int W, int target_type, float ratio, int step, int towards, const float* signs, const float* weights, Geo& g, DpfHeadW& hw) {
+  if (!pred || !depth || !normal || !Kmat || !signs || !weights || B <= 0 || n < 1 || n > kDpfMaxHeads || H <= 0 || W <= 0 || target_type < 0 ||
       target_type > 2 || (target_type != 2 && !ab) || !(ratio > 0.f) || step < 1)
     return DPF_ERR_INVALID_ARG;
   for (int k = 0; k < 3; ++k)
@@ -287,7 +259,7 @@ int prepare(const float* pred, const float* depth, const float* normal, const fl
   g.pred = pred, g.depth = depth, g.normal = normal, g.Kmat = Kmat, g.ab = ab, g.mask = mask;
   g.n = n, g.H = H, g.W = W, g.target_type = target_type, g.towards = towards ? 1 : 0, g.ratio = ratio;
   for (int k = 0; k < 3; ++k) g.sg[k] = signs[k];
-  for (int k = 0; k < kMaxHeads; ++k) hw.w[k] = k < n ? weights[k] : 0.f;
+  dpf_fill_head_weights(hw.w, weights, n);
   return DPF_OK;
 }
 
@@ -296,10 +268,8 @@ int prepare(const float* pred, const float* depth, const float* normal, const fl
 extern "C" {
 
 long long dpf_normal_geo_workspace_bytes(int B, int n, int H, int W) {
-  if (B <= 0 || n < 1 || n > kMaxHeads || H <= 0 || W <= 0 || (long long)B * n > kMaxGridZ || dpf_div_up(H, kTH) > kMaxTileRows ||
-      (long long)H * W > 0x7fffffffLL)
-    return -1;
-  return (long long)n * B * dpf_div_up(H, kTH) * dpf_div_up(W, kTW) * 2 * (long long)sizeof(double);
+  const long long rows = dpf_tile_rows(B, n, H, W);
+  return rows < 0 ? -1 : rows * 2 * (long long)sizeof(double);
 }
 
 int dpf_normal_geo_forward(const float* pred, const float* depth, const float* normal, const float* Kmat, const float* ab, const float* mask,
@@ -308,7 +278,7 @@ int dpf_normal_geo_forward(const float* pred, const float* depth, const float* n
                            float* out, float* normal_out, unsigned char* counted_out, void* stream) {
   dpf_clear_error();
   Geo g;
-  HeadW hw;
+  DpfHeadW hw;
   const int rc = prepare(pred, depth, normal, Kmat, ab, mask, B, n, H, W, target_type, max_edge_ratio, step, towards_camera,
                          target_signs_host, head_weights_host, g, hw);
   if (rc != DPF_OK) return rc;
@@ -316,12 +286,12 @@ int dpf_normal_geo_forward(const float* pred, const float* depth, const float* n
       !dpf_ws_ok(ws, ws_bytes, dpf_normal_geo_workspace_bytes(B, n, H, W), 8))
     return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(dpf_div_up(W, kTW), dpf_div_up(H, kTH), B * n), block(kBlock);
+  const dim3 grid = dpf_tile_grid(B, n, H, W), block(kBlock);
   double* part = (double*)ws;
   if (step == 1) hipLaunchKernelGGL(geo_forward_kernel<1>, grid, block, 0, st, g, part, normal_out, counted_out);
   else if (step == 2) hipLaunchKernelGGL(geo_forward_kernel<2>, grid, block, 0, st, g, part, normal_out, counted_out);
   else hipLaunchKernelGGL(geo_forward_kernel<4>, grid, block, 0, st, g, part, normal_out, counted_out);
-  hipLaunchKernelGGL(geo_fold_kernel, dim3(1), block, 0, st, (const double*)part, (long long)B * grid.x * grid.y, n, hw, stats, out);
+  dpf_launch_head_fold<1>(part, B, n, H, W, hw, stats, out, st);
   return dpf_check_launch();
 }
 
@@ -331,13 +301,13 @@ int dpf_normal_geo_backward(const float* pred, const float* depth, const float* 
                             float* dpred, void* stream) {
   dpf_clear_error();
   Geo g;
-  HeadW hw;
+  DpfHeadW hw;
   const int rc = prepare(pred, depth, normal, Kmat, ab, mask, B, n, H, W, target_type, max_edge_ratio, step, towards_camera,
                          target_signs_host, head_weights_host, g, hw);
   if (rc != DPF_OK) return rc;
   if (!stats || !gout || !dpred) return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(dpf_div_up(W, kTW), dpf_div_up(H, kTH), B * n), block(kBlock);
+  const dim3 grid = dpf_tile_grid(B, n, H, W), block(kBlock);
   if (step == 1) hipLaunchKernelGGL(geo_backward_kernel<1>, grid, block, 0, st, g, hw, stats, gout, dpred);
   else if (step == 2) hipLaunchKernelGGL(geo_backward_kernel<2>, grid, block, 0, st, g, hw, stats, gout, dpred);
   else hipLaunchKernelGGL(geo_backward_kernel<4>, grid, block, 0, st, g, hw, stats, gout, dpred);

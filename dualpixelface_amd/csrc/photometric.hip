@@ -1,10 +1,10 @@
 // The two label-free losses (loss_type 'photometric' and 'smoothness'; losses.PHOTOMETRICLoss / SMOOTHNESSLoss, ops.photometric_loss /
-// ops.smoothness_loss; DESIGN.md section 7): the target view warped onto the reference view by the predicted displacement and compared
+// ops.smoothness_loss; DESIGN.md section 11): the target view warped onto the reference view by the predicted displacement and compared
 // with it, and the edge-aware first-order smoothness of the prediction, each with a hand-written gradient into the prediction.  Every
 // fp32 expression is written operation by operation under -ffp-contract=off, so that tests/photometric_cpu.py restates the warped
 // values and the counted map bit for bit.
 //
-//   Y        (0.299 R + 0.587 G) + 0.114 B of the de-normalised image, R = x_0 std_0 + mean_0 and so on (postprocess.hip's definition)
+//   Y        (0.299 R + 0.587 G) + 0.114 B of the de-normalised image, R = x_0 std_0 + mean_0 and so on (dpf_image.h)
 //   D        pred (target types 0, 1) or a / pred + b (2; pred <= 0 is not usable)
 //   sample   sx = x + shift_x D, sy = y + shift_y D
 //   warpable pred finite (and > 0 for type 2), mask NULL or > 0, 0 <= sx <= W - 1 and 0 <= sy <= H - 1
@@ -31,8 +31,8 @@
 //
 // Smoothness forward: luminance launch, one workgroup per 32 x 8 tile leaves (x sum, x count, y sum, y count), one workgroup folds.
 // Backward: every pixel gathers its left, right, upper and lower pair, in that order.
-#include "dpf_common.h"
-#include "dpf_reduce.h"
+#include "dpf_head_loss.h"
+#include "dpf_image.h"
 #include <math.h>
 
 extern "C" long long dpf_photometric_workspace_bytes(int B, int n, int H, int W);
@@ -41,15 +41,8 @@ extern "C" long long dpf_smoothness_workspace_bytes(int B, int n, int H, int W);
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kTW = 32, kTH = 8;               // output tile, one pixel per thread
-constexpr int kMaxHeads = 8;
-constexpr int kMaxGridZ = 65535;               // B n rides on gridDim.z, the 2 B luminance planes on gridDim.y
-constexpr int kMaxTileRows = 65535;            // the tile rows on gridDim.y
+constexpr int kTW = kDpfTileW, kTH = kDpfTileH;      // output tile, one pixel per thread (dpf_head_loss.h has the plan)
 constexpr float kC1 = 0.0001f, kC2 = 0.0009f;  // 0.01^2, 0.03^2
-constexpr float kLumaR = 0.299f, kLumaG = 0.587f, kLumaB = 0.114f;
-
-struct Norm { float mean[3], std[3]; };
-struct HeadW { float w[kMaxHeads]; };
 
 struct Photo {
   const float* pred;       // [B, n, H, W]
@@ -70,15 +63,13 @@ struct Smooth {
 };
 
 // grid (blocks over H W, planes): plane p of out [planes][HW] from the image p of img [planes][3][HW]
-__global__ __launch_bounds__(256) void luma_kernel(const float* __restrict__ img0, const float* __restrict__ img1, int B, long long HW, Norm nm,
+__global__ __launch_bounds__(256) void luma_kernel(const float* __restrict__ img0, const float* __restrict__ img1, int B, long long HW, DpfNorm nm,
                                                    float* __restrict__ out) {
   const int p = blockIdx.y;
   const float* __restrict__ g = (p < B ? img0 + (size_t)p * 3 * HW : img1 + (size_t)(p - B) * 3 * HW);
   float* __restrict__ o = out + (size_t)p * HW;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < HW; i += (long long)gridDim.x * kBlock) {
-    const float r = g[i] * nm.std[0] + nm.mean[0], gr = g[i + HW] * nm.std[1] + nm.mean[1], b = g[i + 2 * HW] * nm.std[2] + nm.mean[2];
-    o[i] = (kLumaR * r + kLumaG * gr) + kLumaB * b;
-  }
+  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < HW; i += (long long)gridDim.x * kBlock)
+    o[i] = dpf_luma(g[i], g[i + HW], g[i + 2 * HW], nm);
 }
 
 // the warp of pixel (y, x), which lies in the image: -> warpable; J, and where asked the derivative of J with respect to pred
@@ -206,43 +197,11 @@ __global__ __launch_bounds__(256) void photo_forward_kernel(Photo g, double* __r
       counted_out[o] = counted ? 1 : 0;
     }
   }
-  const size_t tiles = (size_t)gridDim.x * gridDim.y, rows = (size_t)(gridDim.z / g.n) * tiles;
-  const size_t row = (size_t)h * rows + (size_t)s * tiles + (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-  dpf_block_reduce_d<2>(acc, part + row * 2);
-}
-
-// one block: folds the rows of every head in a fixed order, writes the stats record and the loss.  A row holds NP (sum, count) pairs;
-// stats: for pair q the counts at [16 q, 16 q + 8) and the sums at [16 q + 8, 16 q + 16)
-template <int NP>
-__global__ __launch_bounds__(256) void fold_kernel(const double* __restrict__ part, long long rows, int n, HeadW hw, double* __restrict__ stats,
-                                                   float* __restrict__ out) {
-  __shared__ double tot[2 * NP];
-  double loss = 0.0;
-  for (int k = 0; k < kMaxHeads; ++k) {
-    double sum[NP], cnt[NP];
-#pragma unroll
-    for (int q = 0; q < NP; ++q) sum[q] = 0.0, cnt[q] = 0.0;
-    if (k < n) {
-      dpf_fold_rows_d<2 * NP>(part + (size_t)k * (size_t)rows * 2 * NP, rows, 2 * NP, tot);
-#pragma unroll
-      for (int q = 0; q < NP; ++q) {
-        sum[q] = tot[2 * q], cnt[q] = tot[2 * q + 1];
-        if (cnt[q] > 0.0) loss += (double)hw.w[k] * (sum[q] / cnt[q]);
-      }
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int q = 0; q < NP; ++q) {
-        stats[2 * kMaxHeads * q + k] = cnt[q];
-        stats[2 * kMaxHeads * q + kMaxHeads + k] = sum[q];
-      }
-    }
-  }
-  if (threadIdx.x == 0) out[0] = (float)loss;
+  dpf_block_reduce_d<2>(acc, part + dpf_tile_part_row(s, h, g.n) * 2);
 }
 
 // grid as the forward's
-__global__ __launch_bounds__(256) void photo_backward_kernel(Photo g, HeadW hw, const double* __restrict__ stats, const float* __restrict__ gout,
+__global__ __launch_bounds__(256) void photo_backward_kernel(Photo g, DpfHeadW hw, const double* __restrict__ stats, const float* __restrict__ gout,
                                                              float* __restrict__ dpred) {
   constexpr int ZW = kTW + 4, ZH = kTH + 4;               // I, J, warpable: halo 2
   constexpr int CW = kTW + 2, CH = kTH + 2;               // windows: halo 1
@@ -353,13 +312,11 @@ __global__ __launch_bounds__(256) void smooth_forward_kernel(Smooth g, double* _
       if (y + 1 < g.H && smooth_ok(g, predh, sbase, o + g.W)) acc[2] = (double)pair_term(g, predh, ys, o, o + g.W, nullptr), acc[3] = 1.0;
     }
   }
-  const size_t tiles = (size_t)gridDim.x * gridDim.y, rows = (size_t)(gridDim.z / g.n) * tiles;
-  const size_t row = (size_t)h * rows + (size_t)s * tiles + (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-  dpf_block_reduce_d<4>(acc, part + row * 4);
+  dpf_block_reduce_d<4>(acc, part + dpf_tile_part_row(s, h, g.n) * 4);
 }
 
 // grid as the forward's, no LDS
-__global__ __launch_bounds__(256) void smooth_backward_kernel(Smooth g, HeadW hw, const double* __restrict__ stats, const float* __restrict__ gout,
+__global__ __launch_bounds__(256) void smooth_backward_kernel(Smooth g, DpfHeadW hw, const double* __restrict__ stats, const float* __restrict__ gout,
                                                               float* __restrict__ dpred) {
   const int t = threadIdx.x;
   const int s = blockIdx.z / g.n, h = blockIdx.z - s * g.n;
@@ -371,7 +328,7 @@ __global__ __launch_bounds__(256) void smooth_backward_kernel(Smooth g, HeadW hw
   const size_t o = (size_t)y * g.W + x;
   float out = 0.f;
   if (smooth_ok(g, predh, sbase, o)) {
-    const double cx = stats[h], cy = stats[2 * kMaxHeads + h];
+    const double cx = stats[h], cy = stats[2 * kDpfMaxHeads + h];
     const float wx = cx > 0.0 ? (float)((double)hw.w[h] / cx) : 0.f, wy = cy > 0.0 ? (float)((double)hw.w[h] / cy) : 0.f;
     float sx = 0.f, sy = 0.f, d;
     if (x >= 1 && smooth_ok(g, predh, sbase, o - 1)) pair_term(g, predh, ys, o - 1, o, &d), sx = sx + d;
@@ -383,18 +340,12 @@ __global__ __launch_bounds__(256) void smooth_backward_kernel(Smooth g, HeadW hw
   dpred[((size_t)s * g.n + h) * HW + o] = out;
 }
 
-bool shape_ok(int B, int n, int H, int W) { return B > 0 && n >= 1 && n <= kMaxHeads && H > 0 && W > 0; }
+bool shape_ok(int B, int n, int H, int W) { return B > 0 && n >= 1 && n <= kDpfMaxHeads && H > 0 && W > 0; }
 
-long long tile_rows(int B, int n, int H, int W) {
-  if ((long long)B * n > kMaxGridZ || 2LL * B > kMaxGridZ || dpf_div_up(H, kTH) > kMaxTileRows || (long long)H * W > 0x7fffffffLL) return -1;
-  return (long long)n * B * dpf_div_up(H, kTH) * dpf_div_up(W, kTW);
-}
+// the tile plan, refused as well where the 2 B luminance planes do not fit on gridDim.y of the luminance launch
+long long tile_rows(int B, int n, int H, int W) { return 2LL * B > kDpfMaxGridZ ? -1 : dpf_tile_rows(B, n, H, W); }
 
-void norm_of(const float* norm_host, Norm& nm) {
-  for (int c = 0; c < 3; ++c) nm.mean[c] = norm_host[c], nm.std[c] = norm_host[3 + c];
-}
-
-int launch_luma(const float* img0, const float* img1, int B, int planes, long long HW, const Norm& nm, float* out, hipStream_t st) {
+int launch_luma(const float* img0, const float* img1, int B, int planes, long long HW, const DpfNorm& nm, float* out, hipStream_t st) {
   long long blocks = (HW + kBlock - 1) / kBlock;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(luma_kernel, dim3((unsigned)blocks, planes), dim3(kBlock), 0, st, img0, img1, B, HW, nm, out);
@@ -404,7 +355,7 @@ int launch_luma(const float* img0, const float* img1, int B, int planes, long lo
 // argument checks shared by the photometric entry points; fills g and hw (the luminance planes are the caller's)
 int prepare_photo(const float* pred, const float* ref_rgb, const float* tgt_rgb, const float* ab, const float* mask, int B, int n, int H, int W,
                   int target_type, float shift_x, float shift_y, float alpha, float eps, const float* norm_host, const float* weights,
-                  const float* luma, Photo& g, HeadW& hw) {
+                  const float* luma, Photo& g, DpfHeadW& hw) {
   if (!pred || !ref_rgb || !tgt_rgb || !norm_host || !weights || !luma || !shape_ok(B, n, H, W) || target_type < 0 || target_type > 2 ||
       (target_type == 2 && !ab) || !(alpha >= 0.f && alpha <= 1.f) || !(eps > 0.f) || !isfinite(eps) || !isfinite(shift_x) ||
       !isfinite(shift_y) || (shift_x == 0.f && shift_y == 0.f))
@@ -412,18 +363,18 @@ int prepare_photo(const float* pred, const float* ref_rgb, const float* tgt_rgb,
   if (tile_rows(B, n, H, W) < 0) return DPF_ERR_UNSUPPORTED;
   g.pred = pred, g.yref = luma, g.ytgt = luma + (size_t)B * H * W, g.ab = ab, g.mask = mask;
   g.n = n, g.H = H, g.W = W, g.target_type = target_type, g.sx = shift_x, g.sy = shift_y, g.alpha = alpha, g.eps = eps;
-  for (int k = 0; k < kMaxHeads; ++k) hw.w[k] = k < n ? weights[k] : 0.f;
+  dpf_fill_head_weights(hw.w, weights, n);
   return DPF_OK;
 }
 
 int prepare_smooth(const float* pred, const float* guide_rgb, const float* mask, int B, int n, int H, int W, float gamma, float eps,
-                   const float* norm_host, const float* weights, const float* luma, Smooth& g, HeadW& hw) {
+                   const float* norm_host, const float* weights, const float* luma, Smooth& g, DpfHeadW& hw) {
   if (!pred || !guide_rgb || !norm_host || !weights || !luma || !shape_ok(B, n, H, W) || !(gamma >= 0.f) || !isfinite(gamma) || !(eps > 0.f) ||
       !isfinite(eps))
     return DPF_ERR_INVALID_ARG;
   if (tile_rows(B, n, H, W) < 0) return DPF_ERR_UNSUPPORTED;
   g.pred = pred, g.y = luma, g.mask = mask, g.n = n, g.H = H, g.W = W, g.gamma = gamma, g.eps = eps;
-  for (int k = 0; k < kMaxHeads; ++k) hw.w[k] = k < n ? weights[k] : 0.f;
+  dpf_fill_head_weights(hw.w, weights, n);
   return DPF_OK;
 }
 
@@ -432,13 +383,13 @@ int prepare_smooth(const float* pred, const float* guide_rgb, const float* mask,
 extern "C" {
 
 long long dpf_photometric_workspace_bytes(int B, int n, int H, int W) {
-  if (!shape_ok(B, n, H, W) || tile_rows(B, n, H, W) < 0) return -1;
-  return tile_rows(B, n, H, W) * 2 * (long long)sizeof(double);
+  const long long rows = tile_rows(B, n, H, W);
+  return rows < 0 ? -1 : rows * 2 * (long long)sizeof(double);
 }
 
 long long dpf_smoothness_workspace_bytes(int B, int n, int H, int W) {
-  if (!shape_ok(B, n, H, W) || tile_rows(B, n, H, W) < 0) return -1;
-  return tile_rows(B, n, H, W) * 4 * (long long)sizeof(double);
+  const long long rows = tile_rows(B, n, H, W);
+  return rows < 0 ? -1 : rows * 4 * (long long)sizeof(double);
 }
 
 int dpf_photometric_forward(const float* pred, const float* ref_rgb, const float* tgt_rgb, const float* ab, const float* mask, int B, int n,
@@ -447,7 +398,7 @@ int dpf_photometric_forward(const float* pred, const float* ref_rgb, const float
                             float* warped_out, unsigned char* counted_out, void* stream) {
   dpf_clear_error();
   Photo g;
-  HeadW hw;
+  DpfHeadW hw;
   const int rc = prepare_photo(pred, ref_rgb, tgt_rgb, ab, mask, B, n, H, W, target_type, shift_x, shift_y, alpha, eps, norm_host,
                                head_weights_host, luma, g, hw);
   if (rc != DPF_OK) return rc;
@@ -455,13 +406,11 @@ int dpf_photometric_forward(const float* pred, const float* ref_rgb, const float
       !dpf_ws_ok(ws, ws_bytes, dpf_photometric_workspace_bytes(B, n, H, W), 8))
     return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
-  Norm nm;
-  norm_of(norm_host, nm);
-  launch_luma(ref_rgb, tgt_rgb, B, 2 * B, (long long)H * W, nm, luma, st);
-  const dim3 grid(dpf_div_up(W, kTW), dpf_div_up(H, kTH), B * n), block(kBlock);
+  launch_luma(ref_rgb, tgt_rgb, B, 2 * B, (long long)H * W, dpf_norm_of(norm_host), luma, st);
+  const dim3 grid = dpf_tile_grid(B, n, H, W), block(kBlock);
   double* part = (double*)ws;
   hipLaunchKernelGGL(photo_forward_kernel, grid, block, 0, st, g, part, warped_out, counted_out);
-  hipLaunchKernelGGL(fold_kernel<1>, dim3(1), block, 0, st, (const double*)part, (long long)B * grid.x * grid.y, n, hw, stats, out);
+  dpf_launch_head_fold<1>(part, B, n, H, W, hw, stats, out, st);
   return dpf_check_launch();
 }
 
@@ -471,12 +420,12 @@ int dpf_photometric_backward(const float* pred, const float* ref_rgb, const floa
                              void* stream) {
   dpf_clear_error();
   Photo g;
-  HeadW hw;
+  DpfHeadW hw;
   const int rc = prepare_photo(pred, ref_rgb, tgt_rgb, ab, mask, B, n, H, W, target_type, shift_x, shift_y, alpha, eps, norm_host,
                                head_weights_host, luma, g, hw);
   if (rc != DPF_OK) return rc;
   if (!stats || !gout || !dpred) return DPF_ERR_INVALID_ARG;
-  const dim3 grid(dpf_div_up(W, kTW), dpf_div_up(H, kTH), B * n), block(kBlock);
+  const dim3 grid = dpf_tile_grid(B, n, H, W), block(kBlock);
   hipLaunchKernelGGL(photo_backward_kernel, grid, block, 0, (hipStream_t)stream, g, hw, stats, gout, dpred);
   return dpf_check_launch();
 }
@@ -486,18 +435,16 @@ int dpf_smoothness_forward(const float* pred, const float* guide_rgb, const floa
                            float* out, void* stream) {
   dpf_clear_error();
   Smooth g;
-  HeadW hw;
+  DpfHeadW hw;
   const int rc = prepare_smooth(pred, guide_rgb, mask, B, n, H, W, gamma, eps, norm_host, head_weights_host, luma, g, hw);
   if (rc != DPF_OK) return rc;
   if (!stats || !out || !dpf_ws_ok(ws, ws_bytes, dpf_smoothness_workspace_bytes(B, n, H, W), 8)) return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
-  Norm nm;
-  norm_of(norm_host, nm);
-  launch_luma(guide_rgb, guide_rgb, B, B, (long long)H * W, nm, luma, st);
-  const dim3 grid(dpf_div_up(W, kTW), dpf_div_up(H, kTH), B * n), block(kBlock);
+  launch_luma(guide_rgb, guide_rgb, B, B, (long long)H * W, dpf_norm_of(norm_host), luma, st);
+  const dim3 grid = dpf_tile_grid(B, n, H, W), block(kBlock);
   double* part = (double*)ws;
   hipLaunchKernelGGL(smooth_forward_kernel, grid, block, 0, st, g, part);
-  hipLaunchKernelGGL(fold_kernel<2>, dim3(1), block, 0, st, (const double*)part, (long long)B * grid.x * grid.y, n, hw, stats, out);
+  dpf_launch_head_fold<2>(part, B, n, H, W, hw, stats, out, st);
   return dpf_check_launch();
 }
 
@@ -506,11 +453,11 @@ int dpf_smoothness_backward(const float* pred, const float* guide_rgb, const flo
                             const float* gout, float* dpred, void* stream) {
   dpf_clear_error();
   Smooth g;
-  HeadW hw;
+  DpfHeadW hw;
   const int rc = prepare_smooth(pred, guide_rgb, mask, B, n, H, W, gamma, eps, norm_host, head_weights_host, luma, g, hw);
   if (rc != DPF_OK) return rc;
   if (!stats || !gout || !dpred) return DPF_ERR_INVALID_ARG;
-  const dim3 grid(dpf_div_up(W, kTW), dpf_div_up(H, kTH), B * n), block(kBlock);
+  const dim3 grid = dpf_tile_grid(B, n, H, W), block(kBlock);
   hipLaunchKernelGGL(smooth_backward_kernel, grid, block, 0, (hipStream_t)stream, g, hw, stats, gout, dpred);
   return dpf_check_launch();
 }

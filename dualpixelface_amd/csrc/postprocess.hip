@@ -1,6 +1,6 @@
 // Edge-aware post-processing of a predicted disparity map (option key post_process; dualpixelface_amd/postprocess.py): the guided filter
 // of He et al. with a grey guide, and the joint bilateral filter.  The reference declares the two switches and implements neither, so
-// the definitions below are this project's own (DESIGN.md section 7).
+// the definitions below are this project's own (DESIGN.md section 11).
 //
 // Guide: I = 0.299 R + 0.587 G + 0.114 B with R = x_0 * std_0 + mean_0 and so on, formed on the device from the normalised image
 // [B, 3, H, W]; mean and std arrive by value from the host (the data path's Normalizer constants).
@@ -23,6 +23,7 @@
 // sum w; I and p tiles with halo and the (r+1)^2 table of w_s sit in LDS; taps run row by row, left to right.
 // No floating-point atomics, no hand-off between workgroups but kernel boundaries, every sum in a fixed order: the bits repeat.
 #include "dpf_common.h"
+#include "dpf_image.h"
 #include <math.h>
 
 namespace {
@@ -36,20 +37,13 @@ constexpr int kBilateralMaxR = 16;
 constexpr int kMaxPlanes = 65535;        // B * n rides on gridDim.z
 constexpr int kMaxBands = 65535;         // and the bands of rows on gridDim.y
 constexpr int kBTH = 16, kBTW = 32;      // bilateral output tile (two rows per thread)
-constexpr float kLumaR = 0.299f, kLumaG = 0.587f, kLumaB = 0.114f;
-
-struct Norm { float mean[3], std[3]; };
-
-__device__ __forceinline__ float luma(float x0, float x1, float x2, const Norm& nm) {
-  return kLumaR * (x0 * nm.std[0] + nm.mean[0]) + kLumaG * (x1 * nm.std[1] + nm.mean[1]) + kLumaB * (x2 * nm.std[2] + nm.mean[2]);
-}
 
 // guide [B][3][HW] -> I [B][HW]; grid (blocks, B)
-__global__ __launch_bounds__(256) void luma_kernel(const float* __restrict__ guide, long long HW, Norm nm, float* __restrict__ I) {
+__global__ __launch_bounds__(256) void luma_kernel(const float* __restrict__ guide, long long HW, DpfNorm nm, float* __restrict__ I) {
   const float* g = guide + (size_t)blockIdx.y * 3 * (size_t)HW;
   float* o = I + (size_t)blockIdx.y * (size_t)HW;
   for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < HW; i += (long long)gridDim.x * kBlock)
-    o[i] = luma(g[i], g[i + HW], g[i + 2 * HW], nm);
+    o[i] = dpf_luma(g[i], g[i + HW], g[i + 2 * HW], nm);
 }
 
 // The two guided passes.  grid (strips, bands, B * n), 256 threads; TW = 256 - 2r output columns per strip, BH (a multiple of kChunk) rows
@@ -221,7 +215,7 @@ __global__ __launch_bounds__(256) void guided_kernel(const float* __restrict__ u
 
 // grid (ceil(W / 32), ceil(H / 16), B * n), 256 threads = 8 rows x 32 columns, each thread the pixels (ty, tx) and (ty + 8, tx) of the tile.
 __global__ __launch_bounds__(256) void bilateral_kernel(const float* __restrict__ p, long long pstride, const float* __restrict__ guide, int n,
-                                                        int H, int W, int r, float inv2ss, float inv2sc, Norm nm, float* __restrict__ q) {
+                                                        int H, int W, int r, float inv2ss, float inv2sc, DpfNorm nm, float* __restrict__ q) {
   constexpr int kMaxRows = kBTH + 2 * kBilateralMaxR, kMaxCols = kBTW + 2 * kBilateralMaxR;
   __shared__ float sI[kMaxRows * kMaxCols], sP[kMaxRows * kMaxCols];
   __shared__ float sW[(kBilateralMaxR + 1) * (kBilateralMaxR + 1)];
@@ -238,7 +232,7 @@ __global__ __launch_bounds__(256) void bilateral_kernel(const float* __restrict_
     float vi = 0.f, vp = 0.f;
     if (y >= 0 && y < H && x >= 0 && x < W) {
       const size_t o = (size_t)y * W + x;
-      vi = luma(gb[o], gb[o + HW], gb[o + 2 * HW], nm);
+      vi = dpf_luma(gb[o], gb[o + HW], gb[o + 2 * HW], nm);
       vp = pb[o];
     }
     sI[i] = vi;
@@ -284,15 +278,6 @@ int band_rows(int B, int n, int H, int W, int r) {
   return bh;
 }
 
-Norm norm_of(const float* norm_host) {
-  Norm nm;
-  for (int c = 0; c < 3; ++c) {
-    nm.mean[c] = norm_host[c];
-    nm.std[c] = norm_host[3 + c];
-  }
-  return nm;
-}
-
 }  // namespace
 
 extern "C" {
@@ -314,7 +299,7 @@ int dpf_guided_filter(const float* p, long long p_batch_stride, const float* gui
   if (r > kGuidedMaxR || (long long)B * n > kMaxPlanes || dpf_div_up(H, kChunk) > kMaxBands) return DPF_ERR_UNSUPPORTED;
   if (ws_bytes < dpf_guided_filter_workspace_bytes(B, n, H, W, r) || ((uintptr_t)ws & 7u)) return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const Norm nm = norm_of(norm_host);
+  const DpfNorm nm = dpf_norm_of(norm_host);
   float* I = (float*)ws;
   float* a = I + (size_t)B * HW;
   float* bq = a + (size_t)B * n * HW;
@@ -341,7 +326,7 @@ int dpf_joint_bilateral_filter(const float* p, long long p_batch_stride, const f
   if (!(inv2ss < INFINITY) || !(inv2sc < INFINITY)) return DPF_ERR_INVALID_ARG;      // a sigma too small for fp32
   const dim3 grid(dpf_div_up(W, kBTW), dpf_div_up(H, kBTH), B * n);
   hipLaunchKernelGGL(bilateral_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, p, p_batch_stride, guide_rgb, n, H, W, r, inv2ss, inv2sc,
-                     norm_of(norm_host), q);
+                     dpf_norm_of(norm_host), q);
   return dpf_check_launch();
 }
 

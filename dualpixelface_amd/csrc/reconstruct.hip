@@ -1,6 +1,6 @@
 // Camera-space surface of a predicted map at evaluation time (option key reconstruct; dualpixelface_amd/reconstruct.py): the point map, the
 // geometric normals of the depth, and a compacted triangle mesh with per-vertex normal and colour.  The reference defines none of this, so
-// the definitions below are this project's own (DESIGN.md section 7).  They follow anm.hip's conventions: pixel grid x = 0..W-1,
+// the definitions below are this project's own (DESIGN.md section 11).  They follow anm.hip's conventions: pixel grid x = 0..W-1,
 // y = 0..H-1, rays r(x, y) = Kinv [x, y, 1] (no quarter scale here), depth = a / (pred - b) with a non-finite value -> 0.
 //
 //   dpf_backproject      points = z r, valid                                             1 launch
@@ -19,6 +19,7 @@
 // No floating-point atomics, no workgroup waits for another inside a launch, every count in a fixed order: the bits repeat.
 #include "dpf_common.h"
 #include "dpf_geometry.h"      // Cam, cam_setup, ray_of, connected: shared with normal_geo.hip
+#include "dpf_image.h"         // DpfNorm: the vertex colours de-normalise the view
 #include <math.h>
 
 namespace {
@@ -29,8 +30,6 @@ constexpr int kPerThread = 4;                  // mesh: grid nodes per thread
 constexpr int kNodes = kBlock * kPerThread;    // and per workgroup
 constexpr int kMaxBatch = 65535;               // B rides on gridDim.y / gridDim.z
 constexpr int kMaxTileRows = 65535;            // and the normals' tile rows on gridDim.y
-
-struct Norm { float mean[3], std[3]; };
 
 struct Scene {        // the operands backproject, depth_normals and depth_mesh share
   const float* pred;
@@ -241,7 +240,7 @@ __global__ __launch_bounds__(256) void mesh_scan_kernel(int nb, const int* __res
 
 // grid (nb, B): the vertex index of every node (-1: none) and the vertex records
 __global__ __launch_bounds__(256) void mesh_vertex_kernel(Scene sc, Grid g, const int* __restrict__ blockoff, const float* __restrict__ nmap,
-                                                          const float* __restrict__ view, Norm nm, int* __restrict__ vidx,
+                                                          const float* __restrict__ view, DpfNorm nm, int* __restrict__ vidx,
                                                           float* __restrict__ vertices, float* __restrict__ vnormals,
                                                           unsigned char* __restrict__ vcolours) {
   __shared__ Cam scam;
@@ -418,7 +417,7 @@ int dpf_depth_mesh(const float* pred, long long pred_batch_stride, int target_ty
   if (ws_bytes < dpf_depth_mesh_workspace_bytes(B, H, W, stride) || ((uintptr_t)ws & 7u)) return DPF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   const Scene sc = scene_of(pred, pred_batch_stride, target_type, ab, Kmat, mask, H, W, z_near, z_far);
-  Norm nm;
+  DpfNorm nm;
   for (int c = 0; c < 3; ++c) {
     nm.mean[c] = view ? norm_host[c] : 0.f;
     nm.std[c] = view ? norm_host[3 + c] : 0.f;

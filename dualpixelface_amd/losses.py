@@ -6,6 +6,7 @@ Class names follow the reference's lookup rule ``<NAME.upper()>Loss`` (loss_sele
 import torch
 
 from . import normal_geo, ops, photometric
+from .core import reference_key
 
 
 TARGET_TYPES = ('disp', 'depth', 'idepth')
@@ -17,40 +18,57 @@ def takes_least_square(batch):
     return 'abvalue' not in batch
 
 
-def _fit(preds, batch):
-    """The fitted conversion (src/utils/geometry.py::regress_affine on the device, ops.affine_fit): [b, a] per sample between head 0 of the
-    raw prediction and batch['idepth'], whatever the target type; detached, as the reference fits under no_grad."""
-    missing = [k for k in ('idepth', 'depth') if k not in batch]
-    if missing:
-        raise NotImplementedError("a batch without 'abvalue' takes the 'least_square' disparity conversion, which needs batch[%s]"
-                                  % "] and batch[".join(repr(k) for k in missing))
-    return ops.affine_fit(preds['pred_depth'], batch['idepth'])
+def conversion(preds, batch):
+    """THE (a, b) rule of every loss, as a function of no arguments that a loss calls where it needs the conversion: batch['abvalue'],
+    else the fitted one (src/utils/geometry.py::regress_affine on the device, ops.affine_fit): [b, a] per sample between head 0 of the
+    raw prediction and batch['idepth'], whatever the target type; detached, as the reference fits under no_grad.  The fit is enqueued
+    at the first call and kept: loss_selector.forward hands one such function to all its losses, so a step fits once."""
+    kept = []
+
+    def ab():
+        if not takes_least_square(batch):
+            return batch['abvalue']
+        if not kept:
+            missing = [k for k in ('idepth', 'depth') if k not in batch]
+            if missing:
+                raise NotImplementedError("a batch without 'abvalue' takes the 'least_square' disparity conversion, which needs batch[%s]"
+                                          % "] and batch[".join(repr(k) for k in missing))
+            kept.append(ops.affine_fit(preds['pred_depth'], batch['idepth']))
+        return kept[0]
+    return ab
 
 
-class _DepthLoss(object):
-    """What the two depth losses share: the conversion rule, and one weight per prediction head (smoothL1.py:22, silog.py:23)."""
+class _HeadWeights(object):
+    """What every loss over the heads of pred_depth shares: one weight per prediction head (smoothL1.py:22, silog.py:23)."""
 
     def __init__(self, option):
-        if option.dataset.dp_conversion != 'given':
-            # the fit itself is built and every batch without 'abvalue' takes it; ignoring an 'abvalue' the batch does bring is not switched on
-            raise NotImplementedError("dp_conversion=%r is not built as a dataset setting (a batch without 'abvalue' takes the 'least_square' "
-                                      "fit under 'given')" % (option.dataset.dp_conversion,))
         self.weights = list(option.model.loss_weight)
 
     def head_weights(self, n):
         return [1.0] if n == 1 else self.weights[:n]
 
 
+class _DepthLoss(_HeadWeights):
+    """What the losses that read a label share: the dp_conversion they refuse."""
+
+    def __init__(self, option):
+        super(_DepthLoss, self).__init__(option)
+        if option.dataset.dp_conversion != 'given':
+            # the fit itself is built and every batch without 'abvalue' takes it; ignoring an 'abvalue' the batch does bring is not switched on
+            raise NotImplementedError("dp_conversion=%r is not built as a dataset setting (a batch without 'abvalue' takes the 'least_square' "
+                                      "fit under 'given')" % (option.dataset.dp_conversion,))
+
+
 class SMOOTHL1Loss(_DepthLoss):
     """Masked smooth-L1 over the prediction heads (src/loss/depth/smoothL1.py:15-49)."""
 
-    def forward(self, preds, batch, target_type='disp'):
+    def forward(self, preds, batch, target_type='disp', ab_of=None):
         assert target_type in TARGET_TYPES
         pd = preds['pred_depth']
         transform = 'reciprocal' if target_type == 'depth' else 'identity'          # smoothL1.py:27
         if takes_least_square(batch):
             # smoothL1.py:29-30 with the [B, H, W] target the class lacks: depth2disp(batch['depth'], ab) is formed inside the loss kernels
-            ab = _fit(preds, batch)
+            ab = (ab_of or conversion(preds, batch))()
             loss = ops.depth_loss(pd, batch['depth'], batch.get('mask'), batch.get('conf'), self.head_weights(pd.shape[1]), 'smoothL1',
                                   transform, target_ab=ab)
             return {'loss': loss, 'abvalue': ab}
@@ -76,11 +94,11 @@ class SILOGLoss(_DepthLoss):
         super(SILOGLoss, self).__init__(option)
         self.variance_focus = option.model.variance_focus
 
-    def forward(self, preds, batch, target_type='disp'):
+    def forward(self, preds, batch, target_type='disp', ab_of=None):
         assert target_type in TARGET_TYPES
         pd = preds['pred_depth']
         fitted = takes_least_square(batch)
-        abvalue = _fit(preds, batch) if fitted else batch['abvalue']
+        abvalue = (ab_of or conversion(preds, batch))()
         if fitted and target_type != 'depth':
             # silog.py:30-31 with the [B, H, W] target; a non-positive a / depth + b gives NaN as in the reference (no clamp)
             loss = ops.depth_loss(pd, batch['depth'], batch.get('mask'), batch.get('conf'), self.head_weights(pd.shape[1]), 'silog',
@@ -99,7 +117,7 @@ class COSINELoss(object):
     def __init__(self, option):
         self.weights = list(option.model.loss_weight)
 
-    def forward(self, preds, batch, target_type=None):
+    def forward(self, preds, batch, target_type=None, ab_of=None):
         pn = preds['pred_normal']
         if pn.shape[1] != 1:
             raise NotImplementedError('one normal prediction per sample (mainmodel.py:95)')
@@ -109,7 +127,7 @@ class COSINELoss(object):
 
 
 class NORMAL_GEOLoss(_DepthLoss):
-    """The geometric-normal loss (not in the reference; DESIGN.md section 7, csrc/normal_geo.hip): the normals of the depth every head of
+    """The geometric-normal loss (not in the reference; DESIGN.md section 11, csrc/normal_geo.hip): the normals of the depth every head of
     pred_depth predicts against batch['normal'], the gradient going back into pred_depth.  Settings: the model config block normal_geo
     (normal_geo.settings).  The conversion is the depth losses': batch['abvalue'], else the fit."""
 
@@ -117,7 +135,7 @@ class NORMAL_GEOLoss(_DepthLoss):
         super(NORMAL_GEOLoss, self).__init__(option)
         self.settings = normal_geo.settings(option)
 
-    def forward(self, preds, batch, target_type='disp'):
+    def forward(self, preds, batch, target_type='disp', ab_of=None):
         assert target_type in TARGET_TYPES
         for key in ('K', 'depth', 'normal'):
             if key not in batch:
@@ -125,7 +143,7 @@ class NORMAL_GEOLoss(_DepthLoss):
         pd = preds['pred_depth']
         out, ab = {}, None
         if target_type != 'depth':
-            ab = out['abvalue'] = _fit(preds, batch) if takes_least_square(batch) else batch['abvalue']
+            ab = out['abvalue'] = (ab_of or conversion(preds, batch))()
         elif 'abvalue' in batch:
             out['abvalue'] = batch['abvalue']              # (a depth prediction needs no conversion; handed on as the depth losses do)
         s = self.settings
@@ -136,26 +154,23 @@ class NORMAL_GEOLoss(_DepthLoss):
         return out
 
 
-class _LabelFreeLoss(object):
-    """What the two label-free losses share (not in the reference; DESIGN.md section 7, csrc/photometric.hip): the settings of the model
+class _LabelFreeLoss(_HeadWeights):
+    """What the two label-free losses share (not in the reference; DESIGN.md section 11, csrc/photometric.hip): the settings of the model
     config block photometric (photometric.settings), one weight per prediction head, and the two views, swapped under dataset.flip_lr
     as the training branch of core._views swaps them.  Neither reads a label, so neither refuses a dp_conversion."""
     name = None
 
     def __init__(self, option):
+        super(_LabelFreeLoss, self).__init__(option)
         self.settings = photometric.settings(option)
-        self.weights = list(option.model.loss_weight)
-        self.flip = bool(option.dataset.flip_lr)
-
-    def head_weights(self, n):
-        return [1.0] if n == 1 else self.weights[:n]
+        self.reference = reference_key(option)
 
     def views(self, batch):
         """(reference view, target view)"""
         for key in ('left', 'right'):
             if key not in batch:
                 raise NotImplementedError("the %r loss needs batch[%r], which is missing from the batch" % (self.name, key))
-        return (batch['right'], batch['left']) if self.flip else (batch['left'], batch['right'])
+        return batch[self.reference], batch['left' if self.reference == 'right' else 'right']
 
 
 class PHOTOMETRICLoss(_LabelFreeLoss):
@@ -163,13 +178,13 @@ class PHOTOMETRICLoss(_LabelFreeLoss):
     (a, b) is needed for target_type 'depth' only: batch['abvalue'], else the fit, as in NORMAL_GEOLoss."""
     name = 'photometric'
 
-    def forward(self, preds, batch, target_type='disp'):
+    def forward(self, preds, batch, target_type='disp', ab_of=None):
         assert target_type in TARGET_TYPES
         ref, tgt = self.views(batch)
         pd = preds['pred_depth']
         out, ab = {}, None
         if target_type == 'depth':
-            ab = out['abvalue'] = _fit(preds, batch) if takes_least_square(batch) else batch['abvalue']
+            ab = out['abvalue'] = (ab_of or conversion(preds, batch))()
         s = self.settings
         out['loss'] = ops.photometric_loss(pd, ref, tgt, ab=ab, mask=batch.get('mask'), head_weights=self.head_weights(pd.shape[1]),
                                            target_type=target_type, shift=s.shift, alpha=s.alpha, eps=s.charbonnier_eps)
@@ -180,7 +195,7 @@ class SMOOTHNESSLoss(_LabelFreeLoss):
     """The edge-aware smoothness of every head of pred_depth under the luminance of the reference view."""
     name = 'smoothness'
 
-    def forward(self, preds, batch, target_type='disp'):
+    def forward(self, preds, batch, target_type='disp', ab_of=None):
         assert target_type in TARGET_TYPES
         ref, _ = self.views(batch)
         pd = preds['pred_depth']
@@ -219,9 +234,9 @@ class loss_selector(object):
             out = ops.stereo_losses(pd, pn[:, 0], batch['disp'], batch['normal'], batch['mask'],
                                     self.loss_func[0].head_weights(pd.shape[1]), self.lambda_[0], self.lambda_[1])
             return {'smoothL1_loss': out[0], 'abvalue': batch['abvalue'], 'cosine_loss': out[1], 'final_loss': out[2]}
-        result, total = {}, []
+        result, total, ab_of = {}, [], conversion(results, batch)
         for name, lam, fn in zip(self.loss_name, self.lambda_, self.loss_func):
-            out = fn.forward(results, batch, target_type)
+            out = fn.forward(results, batch, target_type, ab_of)
             result[name + '_loss'] = out['loss']
             if 'abvalue' in out:
                 result['abvalue'] = out['abvalue']

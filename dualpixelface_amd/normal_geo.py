@@ -1,5 +1,5 @@
 """The ``normal_geo`` block of a model configuration: the settings of the geometric-normal loss (loss_type 'normal_geo',
-losses.NORMAL_GEOLoss, csrc/normal_geo.hip; DESIGN.md section 7).
+losses.NORMAL_GEOLoss, csrc/normal_geo.hip; DESIGN.md section 11).
 
 The loss takes the normals of the PREDICTED depth (the stencil of csrc/reconstruct.hip, neighbours ``step`` pixels away), compares them
 with batch['normal'] and sends the gradient into pred_depth, so every model with a depth head is supervised by the ground-truth normals.
@@ -17,37 +17,22 @@ max_edge_ratio is a conventional value; nobody has tuned it on face data.
 """
 import collections
 
+from .settings_block import Block
+
 Settings = collections.namedtuple('Settings', ['max_edge_ratio', 'step', 'towards_camera', 'target_signs'])
 DEFAULTS = Settings(0.01, 1, True, (1, 1, 1))
 STEPS = (1, 2, 4)
 
 
-def _get(block, key):
-    default = getattr(DEFAULTS, key)
-    if block is None:
-        return default
-    if isinstance(block, dict):
-        return block.get(key, default)
-    return getattr(block, key, default)
-
-
 def settings(option):
     """The validated normal_geo record of an option object (config.Option, or anything whose ``model`` has a ``normal_geo`` attribute that
     is a dict, an attribute object or None).  A missing block or key takes DEFAULTS; a malformed value raises ValueError naming its key."""
-    block = getattr(getattr(option, 'model', None), 'normal_geo', None)
-    if block is not None and not isinstance(block, dict) and not hasattr(block, '__dict__'):
-        raise ValueError('normal_geo must be a block of keys, got %r' % (block,))
-    ratio = _get(block, 'max_edge_ratio')
-    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or ratio != ratio or ratio == float('inf') or not ratio > 0:
-        raise ValueError('normal_geo.max_edge_ratio must be a positive finite number, got %r' % (ratio,))
-    step = _get(block, 'step')
-    if isinstance(step, bool) or not isinstance(step, int) or step not in STEPS:
-        raise ValueError('normal_geo.step must be 1, 2 or 4, got %r' % (step,))
-    towards = _get(block, 'towards_camera')
-    if not isinstance(towards, bool):
-        raise ValueError('normal_geo.towards_camera must be true or false, got %r' % (towards,))
-    signs = _get(block, 'target_signs')
+    block = Block(getattr(option, 'model', None), 'normal_geo', 'normal_geo', DEFAULTS)
+    ratio = block.positive('max_edge_ratio')
+    step = block.integer('step', STEPS, '1, 2 or 4')
+    towards = block.switch('towards_camera')
+    signs = block.get('target_signs')
     if not isinstance(signs, (list, tuple)) or len(signs) != 3 or \
             any(isinstance(v, bool) or not isinstance(v, (int, float)) or v not in (1, -1) for v in signs):
-        raise ValueError('normal_geo.target_signs must be three values of 1 or -1, got %r' % (signs,))
-    return Settings(float(ratio), step, towards, tuple(int(v) for v in signs))
+        block.refuse('target_signs', 'three values of 1 or -1', signs)
+    return Settings(ratio, step, towards, tuple(int(v) for v in signs))

@@ -1684,44 +1684,56 @@ LOSS_TRANSFORM = {'identity': 0, 'reciprocal': 1}
 LOSS_STATS = 17             # doubles the forward leaves for the backward: M, mean d per head, sqrt of the variance term per head
 
 
-class DepthLossFn(torch.autograd.Function):
-    """The loss bank (csrc/loss_bank.hip) -> 0-dim loss.  Workspace and stats are fresh tensors and nothing is read on the host, so the
-    call is capturable inside the train-step graph like LossFn."""
+# What one head loss is to HeadLossFn.  name: the public function's, for messages; stem: the C symbols are <stem>_workspace_bytes, _forward
+# and _backward; dims: which of B, n, H, W the workspace query takes; stats: doubles the forward leaves for the backward; aux: the
+# (B, n, H, W) -> shapes of the float32 planes the forward fills and the backward reads again; extras: likewise -> (shape, dtype) of the
+# non-differentiable outputs a caller may ask for.
+class _HeadLoss(object):
+    def __init__(self, name, stem, dims, stats, aux=None, extras=None):
+        self.query, self.fwd, self.bwd = stem + '_workspace_bytes', stem + '_forward', stem + '_backward'
+        self.what = '%s: shape %s is not supported' % (name, ' '.join(d + '=%d' for d in dims))
+        self.dims = tuple('BnHW'.index(d) for d in dims)
+        self.stats, self.aux, self.extras = stats, aux, extras
+
+
+class HeadLossFn(torch.autograd.Function):
+    """The four losses over the heads of pred [B, n, H, W] (csrc/loss_bank.hip, normal_geo.hip, photometric.hip) -> 0-dim loss, and with
+    want_extras the operator's extras (for tests and tools).  The C argument orders agree: forward `lead | ws, nbytes | aux | stats, out |
+    extras`, backward `lead | aux | stats, gout, dpred`; `lead` is built once by the caller and `held` are the tensors it points into
+    beside pred.  Workspace, stats and the auxiliary planes are fresh tensors (planes and stats are saved for the backward, the workspace
+    is not needed again), gout is read on the device and nothing is read on the host, so the call is capturable inside the train-step
+    graph like LossFn.  Only pred receives a gradient."""
 
     @staticmethod
-    def forward(ctx, pred, target, mask, conf, head_weights, kind, transform, variance_focus, target_ab=None):
-        pred, target = _c(pred), _c(target)
-        mask = None if mask is None else _c(mask)
-        conf = None if conf is None else _c(conf)
-        target_ab = None if target_ab is None else _c(target_ab.detach())
-        _need(pred, target, mask, conf, target_ab)
-        B, n, H, W = pred.shape
-        if target_ab is not None and (tuple(target_ab.shape) != (B, 2) or target_ab.dtype != torch.float32):
-            raise DpfError('depth_loss: target_ab %s %s, float32 [%d, 2] expected' % (tuple(target_ab.shape), target_ab.dtype, B))
-        _match_pred('depth_loss', pred, ('target', target, (B, H, W)), ('mask', mask, (B, H, W)), ('conf', conf, (B, H, W)))
-        if len(head_weights) != n:
-            raise DpfError('depth_loss: %d head weights for %d heads' % (len(head_weights), n))
-        ws, nbytes = _workspace('dpf_depth_loss_workspace_bytes', 'depth_loss: shape B=%d H=%d W=%d is not supported', B, H, W,
-                                device=pred.device)
-        stats = torch.empty(LOSS_STATS, dtype=torch.float64, device=pred.device)
-        out = torch.empty((), dtype=torch.float32, device=pred.device)
-        cfg = (LOSS_KIND[kind], LOSS_TRANSFORM[transform], B, n, H, W, tuple(float(w) for w in head_weights), float(variance_focus))
-        lib().call('dpf_depth_loss_forward', cfg[0], cfg[1], _ptr(pred), _ptr(target), _ptr(target_ab), _ptr(mask), _ptr(conf), B, n, H, W,
-                   _host_floats(cfg[6]), cfg[7], _ptr(ws), nbytes, _ptr(stats), _ptr(out), _stream())
-        ctx.save_for_backward(pred, target, mask, conf, stats, target_ab)
-        ctx.cfg = cfg
+    def forward(ctx, pred, op, held, lead, want_extras):
+        shape, dev = pred.shape, pred.device
+        ws, nbytes = _workspace(op.query, op.what, *[shape[i] for i in op.dims], device=dev)
+        stats = torch.empty(op.stats, dtype=torch.float64, device=dev)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        aux = [torch.empty(s, dtype=torch.float32, device=dev) for s in op.aux(*shape)] if op.aux else []
+        extras = []
+        if op.extras:
+            extras = [torch.empty(s, dtype=dtype, device=dev) if want_extras else None for s, dtype in op.extras(*shape)]
+        lib().call(op.fwd, *lead, _ptr(ws), nbytes, *[_ptr(t) for t in aux], _ptr(stats), _ptr(out), *[_ptr(t) for t in extras], _stream())
+        ctx.save_for_backward(pred, stats, *aux, *held)
+        ctx.op, ctx.lead, ctx.naux = op, lead, len(aux)
+        if want_extras:
+            ctx.mark_non_differentiable(*extras)
+            return (out,) + tuple(extras)
         return out
 
     @staticmethod
-    def backward(ctx, gout):
-        pred, target, mask, conf, stats, target_ab = ctx.saved_tensors
-        kind, transform, B, n, H, W, weights, vf = ctx.cfg
+    def backward(ctx, gout, *unused):
+        saved = ctx.saved_tensors
+        pred, stats, aux = saved[0], saved[1], saved[2:2 + ctx.naux]
         gout = _c(gout)
         _need(gout)
         dpred = torch.empty_like(pred)
-        lib().call('dpf_depth_loss_backward', kind, transform, _ptr(pred), _ptr(target), _ptr(target_ab), _ptr(mask), _ptr(conf), B, n, H, W,
-                   _host_floats(weights), vf, _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
-        return dpred, None, None, None, None, None, None, None, None
+        lib().call(ctx.op.bwd, *ctx.lead, *[_ptr(t) for t in aux], _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
+        return dpred, None, None, None, None
+
+
+_DEPTH_LOSS = _HeadLoss('depth_loss', 'dpf_depth_loss', 'BHW', LOSS_STATS)
 
 
 def depth_loss(pred, target, mask=None, conf=None, head_weights=(1.0,), kind='smoothL1', transform='identity', variance_focus=0.0,
@@ -1730,17 +1742,31 @@ def depth_loss(pred, target, mask=None, conf=None, head_weights=(1.0,), kind='sm
     kind 'smoothL1' | 'silog', transform 'identity' | 'reciprocal' (of pred; non-finite -> 0 with a zero gradient) -> 0-dim loss.
     With target_ab [B, 2] = [b, a], `target` is the depth map and the kernels compare against a / depth + b (non-finite -> -100); no
     gradient reaches target_ab."""
-    return DepthLossFn.apply(pred, target, mask, conf, tuple(head_weights), kind, transform, variance_focus, target_ab)
+    pred, target = _c(pred), _c(target)
+    mask = None if mask is None else _c(mask)
+    conf = None if conf is None else _c(conf)
+    target_ab = None if target_ab is None else _c(target_ab.detach())
+    _need(pred, target, mask, conf, target_ab)
+    B, n, H, W = pred.shape
+    if target_ab is not None and (tuple(target_ab.shape) != (B, 2) or target_ab.dtype != torch.float32):
+        raise DpfError('depth_loss: target_ab %s %s, float32 [%d, 2] expected' % (tuple(target_ab.shape), target_ab.dtype, B))
+    _match_pred('depth_loss', pred, ('target', target, (B, H, W)), ('mask', mask, (B, H, W)), ('conf', conf, (B, H, W)))
+    if len(head_weights) != n:
+        raise DpfError('depth_loss: %d head weights for %d heads' % (len(head_weights), n))
+    held = (target, target_ab, mask, conf)
+    lead = (LOSS_KIND[kind], LOSS_TRANSFORM[transform], _ptr(pred), *[_ptr(t) for t in held], B, n, H, W, _host_floats(head_weights),
+            float(variance_focus))
+    return HeadLossFn.apply(pred, _DEPTH_LOSS, held, lead, False)
 
 
-AFFINE_FIT_F_SCALE, AFFINE_FIT_MAX_ITERS, AFFINE_FIT_TOL = 0.1, 48, 1e-7      # DESIGN.md section 7 has the probe behind the last two
+AFFINE_FIT_F_SCALE, AFFINE_FIT_MAX_ITERS, AFFINE_FIT_TOL = 0.1, 48, 1e-7      # DESIGN.md section 11 has the probe behind the last two
 AFFINE_FIT_INFO = 6         # doubles per sample: A, B, reweighted solves used, valid pixels, objective at (A, B), objective at the start
 
 
 def affine_fit(pred, idepth, f_scale=AFFINE_FIT_F_SCALE, max_iters=AFFINE_FIT_MAX_ITERS, tol=AFFINE_FIT_TOL, return_info=False):
     """src/utils/geometry.py::regress_affine on the device (csrc/affine_fit.hip): per sample the soft-L1 line pred[:, 0] = a * idepth + b over
     the pixels with idepth > 0 -> detached float32 [B, 2] = [b, a]; with return_info also the fp64 [B, 6] record.  Workspace and results are
-    fresh tensors and nothing is read on the host, so the call is capturable inside the train-step graph like DepthLossFn."""
+    fresh tensors and nothing is read on the host, so the call is capturable inside the train-step graph like HeadLossFn."""
     pred, idepth = _c(pred.detach()), _c(idepth.detach())
     _need(pred, idepth, dtypes=_F32)
     if pred.dim() != 4:
@@ -1902,50 +1928,14 @@ NORMAL_GEO_STEPS = (1, 2, 4)
 NORMAL_GEO_STATS = 16       # doubles the forward leaves for the backward: count per head [0, 8), term sum per head [8, 16)
 
 
-class NormalGeoFn(torch.autograd.Function):
-    """The geometric-normal loss (csrc/normal_geo.hip) -> 0-dim loss (and, for tests and tools, the normals and the counted map).  Like
-    DepthLossFn: workspace and stats are fresh tensors, gout is read on the device and nothing is read on the host, so the call is
-    capturable inside the train-step graph.  Only pred receives a gradient."""
-
-    @staticmethod
-    def forward(ctx, pred, depth, normal, Kmat, ab, mask, cfg, return_normals):
-        B, n, H, W = pred.shape
-        ws, nbytes = _workspace('dpf_normal_geo_workspace_bytes', 'normal_geo_loss: shape B=%d n=%d H=%d W=%d is not supported', B, n, H, W,
-                                device=pred.device)
-        stats = torch.empty(NORMAL_GEO_STATS, dtype=torch.float64, device=pred.device)
-        out = torch.empty((), dtype=torch.float32, device=pred.device)
-        nrm = cnt = None
-        if return_normals:
-            nrm = torch.empty((B, n, 3, H, W), dtype=torch.float32, device=pred.device)
-            cnt = torch.empty((B, n, H, W), dtype=torch.uint8, device=pred.device)
-        target_type, ratio, step, towards, signs, weights = cfg
-        lib().call('dpf_normal_geo_forward', _ptr(pred), _ptr(depth), _ptr(normal), _ptr(Kmat), _ptr(ab), _ptr(mask), B, n, H, W, target_type,
-                   ratio, step, towards, _host_floats(signs), _host_floats(weights), _ptr(ws), nbytes, _ptr(stats), _ptr(out), _ptr(nrm),
-                   _ptr(cnt), _stream())
-        ctx.save_for_backward(pred, depth, normal, Kmat, ab, mask, stats)
-        ctx.cfg = cfg
-        if return_normals:
-            ctx.mark_non_differentiable(nrm, cnt)
-            return out, nrm, cnt
-        return out
-
-    @staticmethod
-    def backward(ctx, gout, *unused):
-        pred, depth, normal, Kmat, ab, mask, stats = ctx.saved_tensors
-        target_type, ratio, step, towards, signs, weights = ctx.cfg
-        gout = _c(gout)
-        _need(gout)
-        B, n, H, W = pred.shape
-        dpred = torch.empty_like(pred)
-        lib().call('dpf_normal_geo_backward', _ptr(pred), _ptr(depth), _ptr(normal), _ptr(Kmat), _ptr(ab), _ptr(mask), B, n, H, W, target_type,
-                   ratio, step, towards, _host_floats(signs), _host_floats(weights), _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
-        return dpred, None, None, None, None, None, None, None
+_NORMAL_GEO = _HeadLoss('normal_geo_loss', 'dpf_normal_geo', 'BnHW', NORMAL_GEO_STATS,
+                        extras=lambda B, n, H, W: (((B, n, 3, H, W), torch.float32), ((B, n, H, W), torch.uint8)))
 
 
 def normal_geo_loss(pred, depth, normal, Kmat, ab=None, mask=None, head_weights=(1.0,), target_type='disp', max_edge_ratio=0.01, step=1,
                     towards_camera=True, target_signs=(1, 1, 1), return_normals=False):
     """csrc/normal_geo.hip: the normals of the depth every head of pred [B, n <= 8, H, W] predicts against normal [B, 3, H, W] -> the 0-dim
-    loss sum_h w_h mean over the counted pixels of 1 - clamp(n . g^, -1, 1), g = target_signs * normal (DESIGN.md section 7).  depth
+    loss sum_h w_h mean over the counted pixels of 1 - clamp(n . g^, -1, 1), g = target_signs * normal (DESIGN.md section 11).  depth
     [B, H, W] is the target depth: it decides which pixels are usable and which neighbours (`step` = 1, 2 or 4 pixels away) lie on one
     surface, the predicted depth a / (pred - b) (ab [B, 2] = [b, a]; pred itself for target type 'depth') gives the step vectors.  The
     gradient reaches pred only.  With return_normals also normal [B, n, 3, H, W] fp32 and counted [B, n, H, W] uint8."""
@@ -1964,57 +1954,21 @@ def normal_geo_loss(pred, depth, normal, Kmat, ab=None, mask=None, head_weights=
         raise DpfError('normal_geo_loss: target_signs must be three values of +1 or -1, got %r' % (target_signs,))
     if not float(max_edge_ratio) > 0:
         raise DpfError('normal_geo_loss: max_edge_ratio must be positive, got %r' % (max_edge_ratio,))
-    cfg = (code, float(max_edge_ratio), step, int(bool(towards_camera)), signs,
-           tuple(float(w) for w in head_weights))
-    held = [None if t is None else _c(t.detach()) for t in (depth, normal, Kmat, None if target_type == 'depth' else ab, mask)]
-    return NormalGeoFn.apply(_c(pred), held[0], held[1], held[2], held[3], held[4], cfg, bool(return_normals))
+    pred = _c(pred)
+    held = tuple(None if t is None else _c(t.detach()) for t in (depth, normal, Kmat, None if target_type == 'depth' else ab, mask))
+    lead = (_ptr(pred), *[_ptr(t) for t in held], B, n, H, W, code, float(max_edge_ratio), step, int(bool(towards_camera)),
+            _host_floats(signs), _host_floats(head_weights))
+    return HeadLossFn.apply(pred, _NORMAL_GEO, held, lead, bool(return_normals))
 
 
 PHOTOMETRIC_STATS = 16      # doubles: count per head [0, 8), term sum per head [8, 16)
 SMOOTHNESS_STATS = 32       # doubles: x-pair count [0, 8) and sum [8, 16), y-pair count [16, 24) and sum [24, 32)
 
 
-class PhotometricFn(torch.autograd.Function):
-    """The photometric loss (csrc/photometric.hip) -> 0-dim loss (and, for tests and tools, the warped luminance and the counted map).
-    Like NormalGeoFn: workspace, stats and the luminance planes are fresh tensors (the planes and the stats are saved for the backward, the
-    workspace is not needed again), gout is read on the device and nothing is read on the host, so the call is capturable inside the
-    train-step graph.  Only pred receives a gradient."""
-
-    @staticmethod
-    def forward(ctx, pred, ref_rgb, tgt_rgb, ab, mask, cfg, return_warped):
-        B, n, H, W = pred.shape
-        ws, nbytes = _workspace('dpf_photometric_workspace_bytes', 'photometric_loss: shape B=%d n=%d H=%d W=%d is not supported', B, n, H, W,
-                                device=pred.device)
-        stats = torch.empty(PHOTOMETRIC_STATS, dtype=torch.float64, device=pred.device)
-        luma = torch.empty((2, B, H, W), dtype=torch.float32, device=pred.device)
-        out = torch.empty((), dtype=torch.float32, device=pred.device)
-        warped = cnt = None
-        if return_warped:
-            warped = torch.empty((B, n, H, W), dtype=torch.float32, device=pred.device)
-            cnt = torch.empty((B, n, H, W), dtype=torch.uint8, device=pred.device)
-        target_type, shift, alpha, eps, weights = cfg
-        lib().call('dpf_photometric_forward', _ptr(pred), _ptr(ref_rgb), _ptr(tgt_rgb), _ptr(ab), _ptr(mask), B, n, H, W, target_type, shift[0],
-                   shift[1], alpha, eps, _normalizer_floats(), _host_floats(weights), _ptr(ws), nbytes, _ptr(luma), _ptr(stats), _ptr(out),
-                   _ptr(warped), _ptr(cnt), _stream())
-        ctx.save_for_backward(pred, ref_rgb, tgt_rgb, ab, mask, luma, stats)
-        ctx.cfg = cfg
-        if return_warped:
-            ctx.mark_non_differentiable(warped, cnt)
-            return out, warped, cnt
-        return out
-
-    @staticmethod
-    def backward(ctx, gout, *unused):
-        pred, ref_rgb, tgt_rgb, ab, mask, luma, stats = ctx.saved_tensors
-        target_type, shift, alpha, eps, weights = ctx.cfg
-        gout = _c(gout)
-        _need(gout)
-        B, n, H, W = pred.shape
-        dpred = torch.empty_like(pred)
-        lib().call('dpf_photometric_backward', _ptr(pred), _ptr(ref_rgb), _ptr(tgt_rgb), _ptr(ab), _ptr(mask), B, n, H, W, target_type, shift[0],
-                   shift[1], alpha, eps, _normalizer_floats(), _host_floats(weights), _ptr(luma), _ptr(stats), _ptr(gout), _ptr(dpred),
-                   _stream())
-        return dpred, None, None, None, None, None, None
+_PHOTOMETRIC = _HeadLoss('photometric_loss', 'dpf_photometric', 'BnHW', PHOTOMETRIC_STATS,
+                         aux=lambda B, n, H, W: ((2, B, H, W),),      # the luminance planes of both views
+                         extras=lambda B, n, H, W: (((B, n, H, W), torch.float32), ((B, n, H, W), torch.uint8)))
+_SMOOTHNESS = _HeadLoss('smoothness_loss', 'dpf_smoothness', 'BnHW', SMOOTHNESS_STATS, aux=lambda B, n, H, W: ((B, H, W),))
 
 
 def _label_free_operands(name, pred, images, ab, mask, head_weights):
@@ -2038,7 +1992,7 @@ def photometric_loss(pred, ref_rgb, tgt_rgb, ab=None, mask=None, head_weights=(1
                      eps=1e-3, return_warped=False):
     """csrc/photometric.hip: the luminance of tgt_rgb [B, 3, H, W] sampled bilinearly at (x + shift[0] D, y + shift[1] D) against the
     luminance of ref_rgb, for every head of pred [B, n <= 8, H, W] -> the 0-dim loss sum_h w_h mean over the counted pixels of
-    alpha clamp((1 - SSIM_3x3) / 2, 0, 1) + (1 - alpha) sqrt((J - I)^2 + eps^2) (DESIGN.md section 7).  D = pred for 'disp' / 'idepth',
+    alpha clamp((1 - SSIM_3x3) / 2, 0, 1) + (1 - alpha) sqrt((J - I)^2 + eps^2) (DESIGN.md section 11).  D = pred for 'disp' / 'idepth',
     a / pred + b for 'depth' (ab [B, 2] = [b, a], needed then only).  A pixel is counted when the nine pixels of its window are warpable:
     pred finite, mask (None: everywhere) > 0, the sample point inside the image.  The gradient reaches pred only.  With return_warped also
     the warped luminance [B, n, H, W] fp32 (0 where not warpable) and counted [B, n, H, W] uint8."""
@@ -2054,39 +2008,10 @@ def photometric_loss(pred, ref_rgb, tgt_rgb, ab=None, mask=None, head_weights=(1
         raise DpfError('photometric_loss: alpha must lie in [0, 1], got %r' % (alpha,))
     if not 0.0 < float(eps) < float('inf'):
         raise DpfError('photometric_loss: eps must be positive, got %r' % (eps,))
-    cfg = (code, shift, float(alpha), float(eps), weights)
-    return PhotometricFn.apply(pred, ref_rgb, tgt_rgb, ab, mask, cfg, bool(return_warped))
-
-
-class SmoothnessFn(torch.autograd.Function):
-    """The edge-aware smoothness loss (csrc/photometric.hip) -> 0-dim loss; built as PhotometricFn is."""
-
-    @staticmethod
-    def forward(ctx, pred, guide_rgb, mask, cfg):
-        B, n, H, W = pred.shape
-        ws, nbytes = _workspace('dpf_smoothness_workspace_bytes', 'smoothness_loss: shape B=%d n=%d H=%d W=%d is not supported', B, n, H, W,
-                                device=pred.device)
-        stats = torch.empty(SMOOTHNESS_STATS, dtype=torch.float64, device=pred.device)
-        luma = torch.empty((B, H, W), dtype=torch.float32, device=pred.device)
-        out = torch.empty((), dtype=torch.float32, device=pred.device)
-        gamma, eps, weights = cfg
-        lib().call('dpf_smoothness_forward', _ptr(pred), _ptr(guide_rgb), _ptr(mask), B, n, H, W, gamma, eps, _normalizer_floats(),
-                   _host_floats(weights), _ptr(ws), nbytes, _ptr(luma), _ptr(stats), _ptr(out), _stream())
-        ctx.save_for_backward(pred, guide_rgb, mask, luma, stats)
-        ctx.cfg = cfg
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        pred, guide_rgb, mask, luma, stats = ctx.saved_tensors
-        gamma, eps, weights = ctx.cfg
-        gout = _c(gout)
-        _need(gout)
-        B, n, H, W = pred.shape
-        dpred = torch.empty_like(pred)
-        lib().call('dpf_smoothness_backward', _ptr(pred), _ptr(guide_rgb), _ptr(mask), B, n, H, W, gamma, eps, _normalizer_floats(),
-                   _host_floats(weights), _ptr(luma), _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
-        return dpred, None, None, None
+    held = (ref_rgb, tgt_rgb, ab, mask)
+    lead = (_ptr(pred), *[_ptr(t) for t in held], *pred.shape, code, shift[0], shift[1], float(alpha), float(eps), _normalizer_floats(),
+            _host_floats(weights))
+    return HeadLossFn.apply(pred, _PHOTOMETRIC, held, lead, bool(return_warped))
 
 
 def smoothness_loss(pred, guide_rgb, mask=None, head_weights=(1.0,), gamma=10.0, eps=1e-3):
@@ -2099,7 +2024,9 @@ def smoothness_loss(pred, guide_rgb, mask=None, head_weights=(1.0,), gamma=10.0,
         raise DpfError('smoothness_loss: gamma must be a finite number >= 0, got %r' % (gamma,))
     if not 0.0 < float(eps) < float('inf'):
         raise DpfError('smoothness_loss: eps must be positive, got %r' % (eps,))
-    return SmoothnessFn.apply(pred, guide_rgb, mask, (float(gamma), float(eps), weights))
+    held = (guide_rgb, mask)
+    lead = (_ptr(pred), *[_ptr(t) for t in held], *pred.shape, float(gamma), float(eps), _normalizer_floats(), _host_floats(weights))
+    return HeadLossFn.apply(pred, _SMOOTHNESS, held, lead, False)
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-5, gscale=1.0):

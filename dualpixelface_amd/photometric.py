@@ -1,5 +1,5 @@
 """The ``photometric`` block of a model configuration: the settings of the two label-free losses (loss_type 'photometric' and
-'smoothness', losses.PHOTOMETRICLoss / SMOOTHNESSLoss, csrc/photometric.hip; DESIGN.md section 7).
+'smoothness', losses.PHOTOMETRICLoss / SMOOTHNESSLoss, csrc/photometric.hip; DESIGN.md section 11).
 
 The photometric loss samples the luminance of the target view at (x + shift[0] D, y + shift[1] D), D the predicted displacement, and
 compares it with the reference view (3 x 3 SSIM and a Charbonnier intensity term); the smoothness loss penalises first differences of
@@ -20,41 +20,21 @@ alpha, charbonnier_eps and smooth_gamma are conventional values, not tuned.
 """
 import collections
 
+from .settings_block import Block, is_number
+
 Settings = collections.namedtuple('Settings', ['shift', 'alpha', 'charbonnier_eps', 'smooth_gamma'])
 DEFAULTS = Settings((0.0, -2.0), 0.85, 1e-3, 10.0)
-INF = float('inf')
-
-
-def _get(block, key):
-    default = getattr(DEFAULTS, key)
-    if block is None:
-        return default
-    if isinstance(block, dict):
-        return block.get(key, default)
-    return getattr(block, key, default)
-
-
-def _number(v):
-    return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and v not in (INF, -INF)
 
 
 def settings(option):
     """The validated photometric record of an option object (config.Option, or anything whose ``model`` has a ``photometric`` attribute
     that is a dict, an attribute object or None).  A missing block or key takes DEFAULTS; a malformed value raises ValueError naming its
     key."""
-    block = getattr(getattr(option, 'model', None), 'photometric', None)
-    if block is not None and not isinstance(block, dict) and not hasattr(block, '__dict__'):
-        raise ValueError('photometric must be a block of keys, got %r' % (block,))
-    shift = _get(block, 'shift')
-    if not isinstance(shift, (list, tuple)) or len(shift) != 2 or not all(_number(v) for v in shift) or all(v == 0 for v in shift):
-        raise ValueError('photometric.shift must be two finite numbers [x, y], not both 0, got %r' % (shift,))
-    alpha = _get(block, 'alpha')
-    if not _number(alpha) or not 0 <= alpha <= 1:
-        raise ValueError('photometric.alpha must be a number in [0, 1], got %r' % (alpha,))
-    eps = _get(block, 'charbonnier_eps')
-    if not _number(eps) or not eps > 0:
-        raise ValueError('photometric.charbonnier_eps must be a positive finite number, got %r' % (eps,))
-    gamma = _get(block, 'smooth_gamma')
-    if not _number(gamma) or not gamma >= 0:
-        raise ValueError('photometric.smooth_gamma must be a finite number >= 0, got %r' % (gamma,))
-    return Settings(tuple(float(v) for v in shift), float(alpha), float(eps), float(gamma))
+    block = Block(getattr(option, 'model', None), 'photometric', 'photometric', DEFAULTS)
+    shift = block.get('shift')
+    if not isinstance(shift, (list, tuple)) or len(shift) != 2 or not all(is_number(v) for v in shift) or all(v == 0 for v in shift):
+        block.refuse('shift', 'two finite numbers [x, y], not both 0', shift)
+    alpha = block.number('alpha', 'a number in [0, 1]', lambda v: 0 <= v <= 1)
+    eps = block.positive('charbonnier_eps')
+    gamma = block.number('smooth_gamma', 'a finite number >= 0', lambda v: v >= 0)
+    return Settings(tuple(float(v) for v in shift), alpha, eps, gamma)

@@ -1,7 +1,7 @@
 """The ``post_process`` block of the configuration: edge-aware filtering of the predicted disparity at evaluation time.
 
 The reference's configs declare ``"post_process": {"use_bilateral": false, "use_guided": false}`` and nothing in the reference reads the
-block (its src/utils/visualizer.py is empty), so the behaviour is defined here and in DESIGN.md section 7: with a switch on, every head of
+block (its src/utils/visualizer.py is empty), so the behaviour is defined here and in DESIGN.md section 11: with a switch on, every head of
 ``results['pred_depth']`` is filtered by csrc/postprocess.hip under the guidance of the luminance of the reference view -- the joint
 bilateral filter first, then the guided filter, whichever are on -- and the unfiltered map stays as ``results['pred_depth_raw']``.
 
@@ -14,6 +14,8 @@ These defaults are conventional starting values for a guide in [0, 1]; nobody ha
 import collections
 
 from . import ops
+from .core import reference_key
+from .settings_block import Block
 
 Settings = collections.namedtuple('Settings', ['use_bilateral', 'use_guided', 'guided_radius', 'guided_eps', 'bilateral_radius',
                                                'bilateral_sigma_space', 'bilateral_sigma_color'])
@@ -21,45 +23,20 @@ DEFAULTS = Settings(False, False, 8, 1e-3, 5, 3.0, 0.1)
 GUIDED_MAX_RADIUS, BILATERAL_MAX_RADIUS = 32, 16          # what csrc/postprocess.hip supports
 
 
-def _get(block, key, default):
-    if block is None:
-        return default
-    if isinstance(block, dict):
-        return block.get(key, default)
-    return getattr(block, key, default)
-
-
-def _switch(block, key):
-    v = _get(block, key, getattr(DEFAULTS, key))
-    if not isinstance(v, bool):
-        raise ValueError('post_process.%s must be true or false, got %r' % (key, v))
-    return v
-
-
-def _radius(block, key, most):
-    v = _get(block, key, getattr(DEFAULTS, key))
-    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= most:
-        raise ValueError('post_process.%s must be an integer in [1, %d], got %r' % (key, most, v))
-    return v
-
-
-def _positive(block, key):
-    v = _get(block, key, getattr(DEFAULTS, key))
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0 or v == float('inf'):
-        raise ValueError('post_process.%s must be a positive number, got %r' % (key, v))
-    return float(v)
-
-
 def settings(option):
     """The validated post_process record of an option object (config.Option, or anything with a ``post_process`` attribute that is a
     dict, an attribute object or None).  A missing block means both switches off; missing parameter keys take DEFAULTS.  A malformed value
     raises ValueError naming its key, whether or not its filter is switched on."""
-    block = getattr(option, 'post_process', None)
-    if block is not None and not isinstance(block, dict) and not hasattr(block, '__dict__'):
-        raise ValueError('post_process must be a block of keys, got %r' % (block,))
-    return Settings(_switch(block, 'use_bilateral'), _switch(block, 'use_guided'), _radius(block, 'guided_radius', GUIDED_MAX_RADIUS),
-                    _positive(block, 'guided_eps'), _radius(block, 'bilateral_radius', BILATERAL_MAX_RADIUS),
-                    _positive(block, 'bilateral_sigma_space'), _positive(block, 'bilateral_sigma_color'))
+    block = Block(option, 'post_process', 'post_process', DEFAULTS)
+
+    def radius(key, most):
+        return block.integer(key, range(1, most + 1), 'an integer in [1, %d]' % most)
+
+    def positive(key):
+        return block.positive(key, 'a positive number')
+    return Settings(block.switch('use_bilateral'), block.switch('use_guided'), radius('guided_radius', GUIDED_MAX_RADIUS),
+                    positive('guided_eps'), radius('bilateral_radius', BILATERAL_MAX_RADIUS), positive('bilateral_sigma_space'),
+                    positive('bilateral_sigma_color'))
 
 
 def active(option):
@@ -73,7 +50,7 @@ def _guide(option, results, batch, guide):
     if pred is None:
         raise NotImplementedError("post_process is switched on but the model returned no results['pred_depth'] to filter")
     if guide is None:
-        key = 'right' if getattr(getattr(option, 'dataset', None), 'flip_lr', False) else 'left'
+        key = reference_key(option)
         guide = batch.get(key)
         name = "batch['%s']" % key
     else:

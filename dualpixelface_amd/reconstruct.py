@@ -1,7 +1,7 @@
 """The ``reconstruct`` block of the configuration: the camera-space surface of an evaluation forward, and its export as PLY files.
 
 The reference stops at a disparity map and a normal map (its save_result_fig_depth call is commented out, its src/utils/visualizer.py is
-empty), so the behaviour is defined here and in DESIGN.md section 7.  With the block on, an evaluation forward also returns
+empty), so the behaviour is defined here and in DESIGN.md section 11.  With the block on, an evaluation forward also returns
 
     results['points']            [B, 3, H, W]  z K^-1 [x, y, 1] of head 0 of results['pred_depth'] (the filtered map when post_process is on)
     results['points_valid']      [B, H, W]     uint8
@@ -23,6 +23,8 @@ import collections
 import os
 
 from . import ops
+from .core import reference_key
+from .settings_block import Block
 
 Settings = collections.namedtuple('Settings', ['enabled', 'write_ply', 'stride', 'near', 'far', 'max_edge_ratio', 'use_mask', 'normals',
                                                'towards_camera', 'colour'])
@@ -31,56 +33,29 @@ NORMAL_SOURCES = ('auto', 'predicted', 'geometric')
 RESULT_KEYS = ('points', 'points_valid', 'normal_geo', 'normal_geo_valid')
 
 
-def _get(block, key):
-    default = getattr(DEFAULTS, key)
-    if block is None:
-        return default
-    if isinstance(block, dict):
-        return block.get(key, default)
-    return getattr(block, key, default)
-
-
-def _switch(block, key):
-    v = _get(block, key)
-    if not isinstance(v, bool):
-        raise ValueError('reconstruct.%s must be true or false, got %r' % (key, v))
-    return v
-
-
-def _number(block, key):
-    v = _get(block, key)
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float('inf'), float('-inf')):
-        raise ValueError('reconstruct.%s must be a finite number, got %r' % (key, v))
-    return float(v)
-
-
 def settings(option):
     """The validated reconstruct record of an option object (config.Option, or anything with a ``reconstruct`` attribute that is a dict, an
     attribute object or None).  A missing block is off; missing keys take DEFAULTS; write_ply switches enabled on.  A malformed value raises
     ValueError naming its key, whether or not the block is enabled."""
-    block = getattr(option, 'reconstruct', None)
-    if block is not None and not isinstance(block, dict) and not hasattr(block, '__dict__'):
-        raise ValueError('reconstruct must be a block of keys, got %r' % (block,))
-    write = _switch(block, 'write_ply')
-    stride = _get(block, 'stride')
-    if isinstance(stride, bool) or not isinstance(stride, int) or stride not in ops.MESH_STRIDES:
-        raise ValueError('reconstruct.stride must be 1, 2, 4 or 8, got %r' % (stride,))
-    near = _number(block, 'near')
+    block = Block(option, 'reconstruct', 'reconstruct', DEFAULTS)
+    write = block.switch('write_ply')
+    stride = block.integer('stride', ops.MESH_STRIDES, '1, 2, 4 or 8')
+    near = block.number('near')
     if near < 0:
         raise ValueError('reconstruct.near must not be negative, got %r' % (near,))
-    far = _get(block, 'far')
+    far = block.get('far')
     if far is not None:
-        far = _number(block, 'far')
+        far = block.number('far')
         if not far > near:
-            raise ValueError('reconstruct.far must be null or larger than near = %r, got %r' % (near, far))
-    ratio = _number(block, 'max_edge_ratio')
+            block.refuse('far', 'null or larger than near = %r' % (near,), far)
+    ratio = block.number('max_edge_ratio')
     if not ratio > 0:
-        raise ValueError('reconstruct.max_edge_ratio must be positive, got %r' % (ratio,))
-    normals = _get(block, 'normals')
+        block.refuse('max_edge_ratio', 'positive', ratio)
+    normals = block.get('normals')
     if normals not in NORMAL_SOURCES:
-        raise ValueError('reconstruct.normals must be one of %s, got %r' % (', '.join(repr(n) for n in NORMAL_SOURCES), normals))
-    return Settings(_switch(block, 'enabled') or write, write, stride, near, far, ratio, _switch(block, 'use_mask'), normals,
-                    _switch(block, 'towards_camera'), _switch(block, 'colour'))
+        block.refuse('normals', 'one of %s' % ', '.join(repr(n) for n in NORMAL_SOURCES), normals)
+    return Settings(block.switch('enabled') or write, write, stride, near, far, ratio, block.switch('use_mask'), normals,
+                    block.switch('towards_camera'), block.switch('colour'))
 
 
 def active(option):
@@ -151,7 +126,7 @@ def extract(option, results, batch, guide=None):
     view = None
     if s.colour:
         if guide is None:
-            key = 'right' if getattr(getattr(option, 'dataset', None), 'flip_lr', False) else 'left'
+            key = reference_key(option)
             guide = batch.get(key)
             if guide is None:
                 raise NotImplementedError("reconstruct.colour is on but batch['%s'], the view the vertices take their colour from, is missing "

@@ -495,7 +495,7 @@ int dpf_metric_affine_dp(const float* pred, const float* target, const float* we
 
 /* ---- edge-aware post-processing of a prediction (csrc/postprocess.hip; option key post_process, dualpixelface_amd/postprocess.py).  The
  * reference declares the switches use_guided / use_bilateral and implements neither: the definitions are this project's (DESIGN.md
- * section 7).  Both filters are out of place (q must not overlap p) and take the same operands: p [B, n, H, W] fp32, samples
+ * section 11).  Both filters are out of place (q must not overlap p) and take the same operands: p [B, n, H, W] fp32, samples
  * p_batch_stride floats apart (n H W for a contiguous tensor), every head filtered with the same guide; guide_rgb [B, 3, H, W] fp32, the
  * normalised image as the batch holds it; norm_host: six host floats mean[3], std[3] of that normalisation, read during the call;
  * q [B, n, H, W] contiguous.  The guide plane is the luminance I = 0.299 R + 0.587 G + 0.114 B, R = x_0 std_0 + mean_0 and so on, formed
@@ -518,7 +518,7 @@ int dpf_joint_bilateral_filter(const float* p, long long p_batch_stride, const f
                                double sigma_space, double sigma_color, const float* norm_host, float* q, void* stream);
 
 /* ---- camera-space surface of a prediction (csrc/reconstruct.hip; option key reconstruct, dualpixelface_amd/reconstruct.py).  The
- * reference defines none of it: the definitions are this project's (DESIGN.md section 7).  Shared operands: pred, head 0 of a prediction as
+ * reference defines none of it: the definitions are this project's (DESIGN.md section 11).  Shared operands: pred, head 0 of a prediction as
  * an H W plane per sample, pred_batch_stride floats apart; target_type 0 = disp, 1 = idepth, 2 = depth; ab [B, 2] fp32 = [b, a] (may be
  * NULL for target type 2); Kmat [B, 3, 3] fp32; mask [B, H, W] fp32 or NULL, valid where mask > 0; 0 <= z_near < z_far, z_far = +inf for
  * no limit.
@@ -559,7 +559,7 @@ int dpf_depth_mesh(const float* pred, long long pred_batch_stride, int target_ty
                    float z_far, float max_edge_ratio, int towards_camera, void* ws, long long ws_bytes, float* vertices,
                    float* vertex_normals, unsigned char* vertex_colours, int* faces, int* counts, void* stream);
 
-/* ---- geometric-normal loss (csrc/normal_geo.hip; loss_type 'normal_geo', dualpixelface_amd/losses.py; DESIGN.md section 7): the normals
+/* ---- geometric-normal loss (csrc/normal_geo.hip; loss_type 'normal_geo', dualpixelface_amd/losses.py; DESIGN.md section 11): the normals
  * of the PREDICTED depth against target normals, and the gradient into the prediction.  The geometry is the surface export's above
  * (rays, Kinv, connected; csrc/dpf_geometry.h).  pred [B, n <= 8, H, W]; depth [B, H, W], the target depth z_t; normal [B, 3, H, W];
  * Kmat [B, 3, 3]; ab [B, 2] = [b, a] (NULL allowed for target type 2); mask [B, H, W] or NULL; target_signs_host: three host floats,
@@ -600,7 +600,7 @@ int dpf_normal_geo_backward(const float* pred, const float* depth, const float* 
                             float* dpred, void* stream);
 
 /* ---- photometric and smoothness losses (csrc/photometric.hip; loss_type 'photometric' / 'smoothness', dualpixelface_amd/losses.py;
- * DESIGN.md section 7): the two views of a dual-pixel pair as their own supervision.  pred [B, n <= 8, H, W]; ref_rgb, tgt_rgb,
+ * DESIGN.md section 11): the two views of a dual-pixel pair as their own supervision.  pred [B, n <= 8, H, W]; ref_rgb, tgt_rgb,
  * guide_rgb [B, 3, H, W], normalised images; ab [B, 2] = [b, a] (needed for target type 2 only, else NULL allowed); mask [B, H, W] or
  * NULL; norm_host: six host floats, the Normalizer's mean then std (as dpf_guided_filter takes them); head_weights_host: n host floats;
  * both read during the call.  luma: device floats the CALLER owns, [2, B, H, W] (photometric: reference plane, target plane) or

@@ -321,6 +321,8 @@ CASES = {
     'horizontal': dict(B=2, n=3, H=19, W=70, seed=13, shift=(1.5, 0.0), masked=True),
     'diagonal-33x40': dict(B=1, n=2, H=33, W=40, seed=14, shift=(-1.0, 0.5), masked=False),
     'depth-type': dict(B=2, n=1, H=16, W=35, seed=15, shift=(0.0, -2.0), target_type='depth', masked=False),
+    # 9 x 16 tiles x 2 samples = 288 partial rows per head: the fold's r += 256 loop runs twice in some threads
+    'rows288-65x500': dict(B=2, n=2, H=65, W=500, seed=16, shift=(0.0, -2.0), masked=True, bad=True),
 }
 
 _cache = {}

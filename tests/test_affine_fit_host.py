@@ -155,6 +155,57 @@ def test_fused_pass_is_for_batches_that_bring_abvalue(monkeypatch):
     assert set(out) == {'smoothL1_loss', 'abvalue', 'cosine_loss', 'final_loss'}
 
 
+THREE = ['smoothL1', 'normal_geo', 'photometric']
+
+
+def _three_losses(monkeypatch):
+    """The selector of three losses that all convert, on stubs that record the ab each operator receives."""
+    from dualpixelface_amd import ops
+    from dualpixelface_amd.losses import loss_selector
+    calls, fit = _stubs(monkeypatch)
+
+    def normal_geo_loss(pred, depth, normal, Kmat, ab=None, **k):
+        calls.append(('normal_geo', ab))
+        return torch.zeros(())
+
+    def photometric_loss(pred, ref_rgb, tgt_rgb, ab=None, **k):
+        calls.append(('photometric', ab))
+        return torch.zeros(())
+
+    monkeypatch.setattr(ops, 'normal_geo_loss', normal_geo_loss)
+    monkeypatch.setattr(ops, 'photometric_loss', photometric_loss)
+    sel = loss_selector(_option(loss_type=THREE, lambdas=[1.0, 0.5, 0.25]))
+    z, img = torch.ones(1, 2, 2), torch.ones(1, 3, 2, 2)
+    extra = {'K': torch.eye(3).unsqueeze(0), 'normal': img, 'left': img, 'right': img}
+    return sel, calls, fit, extra
+
+
+def test_three_losses_fit_once_per_forward(monkeypatch):
+    """One step enqueues the fit once however many losses convert with it, and again at the next step; every loss gets that tensor."""
+    sel, calls, fit, extra = _three_losses(monkeypatch)
+    batch, pred = dict(_batch(False), **extra), torch.ones(1, 1, 2, 2)
+    for _ in range(2):
+        del calls[:]
+        out = sel.forward({'pred_depth': pred}, batch, 'depth')
+        assert [c[0] for c in calls] == ['fit', 'bank', 'normal_geo', 'photometric']
+        assert calls[0][1] is pred and calls[0][2] is batch['idepth']
+        assert calls[1][4] is fit and calls[3][1] is fit and out['abvalue'] is fit
+        assert calls[2][1] is None                                     # (a depth prediction: normal_geo converts nothing)
+        assert set(out) == {n + '_loss' for n in THREE} | {'abvalue', 'final_loss'}
+    del calls[:]
+    out = sel.forward({'pred_depth': pred}, batch, 'idepth')           # here normal_geo converts and photometric does not
+    assert [c[0] for c in calls] == ['fit', 'bank', 'normal_geo', 'photometric']
+    assert calls[1][4] is fit and calls[2][1] is fit and calls[3][1] is None and out['abvalue'] is fit
+
+
+def test_three_losses_with_abvalue_do_not_fit(monkeypatch):
+    sel, calls, fit, extra = _three_losses(monkeypatch)
+    batch = dict(_batch(), **extra)
+    out = sel.forward({'pred_depth': torch.ones(1, 1, 2, 2)}, batch, 'depth')
+    assert [c[0] for c in calls] == ['bank', 'normal_geo', 'photometric'] and calls[2][1] is batch['abvalue']
+    assert out['abvalue'] is batch['abvalue']
+
+
 @pytest.mark.parametrize('what', ['stereodpnet', 'nnet'])
 def test_geometry_models_name_the_missing_key(what):
     from dualpixelface_amd.core import geometry_abvalue

@@ -295,6 +295,52 @@ def test_hook_silog_depth_returns_the_fit():
     assert torch.equal(res['abvalue'], _ops().affine_fit(far, batch['idepth']))
 
 
+def test_three_losses_share_one_fit_bit_for_bit():
+    """smoothL1 + normal_geo + photometric on a batch without 'abvalue': the selector fits once and hands the result to all three; each
+    loss class called alone fits for itself.  Same kernels on the same inputs, so losses, abvalue and the gradient are equal bit for
+    bit.  The fields are made so that every loss counts pixels under the fit: head 0 is exactly 2000 batch['idepth'] - 1.5, which sends
+    the photometric displacement a / pred + b into [-0.2, 1.4] pixels."""
+    from dualpixelface_amd import load_option, losses
+    names, lambdas, B, n, H, W = ['smoothL1', 'normal_geo', 'photometric'], [1.0, 0.5, 0.25], 2, 3, 32, 48
+    g = torch.Generator().manual_seed(41)
+    y, x = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing='ij')
+    depth = (1000.0 + 120.0 * torch.sin(x / 7.0) * torch.cos(y / 5.0)).expand(B, H, W) + torch.rand(B, 1, 1, generator=g) * 200.0
+    pred = depth.unsqueeze(1) * (1.0 + 0.002 * torch.randn(B, n, H, W, generator=g))
+    normal = torch.randn(B, 3, H, W, generator=g)
+    batch = {'depth': depth, 'idepth': (pred[:, 0] + 1.5) / 2000.0, 'normal': normal / normal.norm(dim=1, keepdim=True),
+             'K': torch.tensor([[60.0, 0.0, W / 2.0], [0.0, 60.0, H / 2.0], [0.0, 0.0, 1.0]]).expand(B, 3, 3).contiguous(),
+             'mask': (torch.rand(B, H, W, generator=g) > 0.1).float(), 'left': torch.rand(B, 3, H, W, generator=g),
+             'right': torch.rand(B, 3, H, W, generator=g)}
+    batch = {k: v.to(DEV).contiguous() for k, v in batch.items()}
+    option = load_option('train_faceDP_dpnet', loss_type=names, lambdas=lambdas, loss_weight=[1.0, 0.7, 0.5])
+
+    def run(forward):
+        p = pred.to(DEV).requires_grad_()
+        res = forward({'pred_depth': p}, batch, 'depth')
+        return res, torch.autograd.grad(res['final_loss'], p)[0]
+
+    def one_by_one(results, batch, target_type):
+        res, total = {}, []
+        for name, lam in zip(names, lambdas):
+            out = losses._BANK[name](option).forward(results, batch, target_type)
+            res[name + '_loss'] = out['loss']
+            if 'abvalue' in out:
+                res['abvalue'] = out['abvalue']
+            total.append(lam * out['loss'])
+        res['final_loss'] = sum(total)
+        return res
+
+    shared, gs = run(losses.loss_selector(option).forward)
+    alone, ga = run(one_by_one)
+    assert set(shared) == set(alone) == {'smoothL1_loss', 'normal_geo_loss', 'photometric_loss', 'abvalue', 'final_loss'}
+    for k in sorted(shared):
+        print(k, shared[k].detach().cpu().tolist())
+        assert torch.equal(shared[k], alone[k]), k
+        assert bool(torch.isfinite(shared[k]).all()) and bool((shared[k] != 0).any()), k
+    assert torch.equal(shared['abvalue'], _ops().affine_fit(pred.to(DEV), batch['idepth']))
+    assert torch.equal(gs, ga) and bool(torch.isfinite(gs).all()) and bool((gs != 0).any())
+
+
 # ---- 4. the whole step
 def _dpnet(config, **model_over):
     from dualpixelface_amd import load_option
