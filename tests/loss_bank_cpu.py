@@ -80,26 +80,3 @@ class Fixture(object):
 
     def expected(self, case):
         return torch.from_numpy(self.g[case[0] + '::loss']), torch.from_numpy(self.g[case[0] + '::grad'])
-
-
-def close(a, b, tol, name=''):
-    a = torch.as_tensor(a).detach().cpu().double()
-    b = torch.as_tensor(b).detach().cpu().double()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    scale = max(b.abs().max().item(), 1e-6)
-    err = (a - b).abs().max().item()
-    print('%s: max err %.3e / scale %.3e = %.3e (bound %.1e)' % (name, err, scale, err / scale, tol))
-    assert err <= tol * scale, '%s: max err %.3e vs scale %.3e (rel %.3e)' % (name, err, scale, err / scale)
-
-
-def close_elem(a, b, name='', rtol=1e-4, atol=1e-5):
-    """tests/test_gpu_ops.py::close_elem's rule: every element within atol * rms(b) + rtol * |b|."""
-    a = torch.as_tensor(a).detach().cpu().double()
-    b = torch.as_tensor(b).detach().cpu().double()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    rms = max(b.pow(2).mean().sqrt().item(), 1e-30)
-    excess = (a - b).abs() - (atol * rms + rtol * b.abs())
-    worst = excess.max().item()
-    print('%s: worst excess %.3e over atol %.0e x rms %.3e + rtol %.0e' % (name, worst, atol, rms, rtol))
-    assert worst <= 0, '%s: %d of %d elements outside rtol %.0e / atol %.0e x rms %.3e (worst excess %.3e)' % (
-        name, int((excess > 0).sum()), excess.numel(), rtol, atol, rms, worst)

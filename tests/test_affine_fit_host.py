@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from tests import affine_fit_cpu as af
-from tests import loss_bank_cpu as lb
+from tests import support
 
 
 @pytest.fixture(scope='module')
@@ -61,16 +61,11 @@ def test_restatement_loss_against_reference_fixture(fixture):
         pred, batch, ab = fixture.inputs(case)
         loss, grad = af.branch_call(kind, tt, pred, batch, fixture.head_weights(n), fixture.variance_focus, ab)
         ref_loss, ref_grad = fixture.expected(case)
-        lb.close(loss, ref_loss, 1e-6, name + ' loss')
-        lb.close_elem(grad, ref_grad, name + ' grad')
+        support.close(loss, ref_loss, 1e-6, name + ' loss')
+        support.close_elem(grad, ref_grad, name + ' grad')
 
 
 # ---- the hooks on stubs
-def _option(**over):
-    from dualpixelface_amd import load_option
-    return load_option('train_faceDP_dpnet', **over)
-
-
 def _stubs(monkeypatch):
     from dualpixelface_amd import ops
     calls, fit = [], torch.tensor([[5.0, 6.0]])
@@ -108,7 +103,7 @@ def test_batch_without_abvalue_selects_the_fit_branch(loss, target_type, monkeyp
     """A batch without 'abvalue' used to be refused; it now fits (a, b) on head 0 and batch['idepth'] and compares against the depth map."""
     from dualpixelface_amd.losses import loss_selector
     calls, fit = _stubs(monkeypatch)
-    sel = loss_selector(_option(loss_type=[loss], variance_focus=0.6))
+    sel = loss_selector(support.option('train_faceDP_dpnet', loss_type=[loss], variance_focus=0.6))
     batch, pred = _batch(False), torch.ones(1, 1, 2, 2)
     out = sel.forward({'pred_depth': pred}, batch, target_type)
     assert set(out) == {loss + '_loss', 'abvalue', 'final_loss'} and out['abvalue'] is fit
@@ -127,13 +122,14 @@ def test_batch_with_abvalue_is_not_fitted(loss, monkeypatch):
     from dualpixelface_amd.losses import loss_selector
     calls, fit = _stubs(monkeypatch)
     batch = _batch()
-    out = loss_selector(_option(loss_type=[loss], variance_focus=0.6)).forward({'pred_depth': torch.ones(1, 1, 2, 2)}, batch, 'disp')
+    sel = loss_selector(support.option('train_faceDP_dpnet', loss_type=[loss], variance_focus=0.6))
+    out = sel.forward({'pred_depth': torch.ones(1, 1, 2, 2)}, batch, 'disp')
     assert [c[0] for c in calls] in (['bank'], ['stereo']) and calls[0][4] is None and out['abvalue'] is batch['abvalue']
 
 
 def test_fit_branch_names_the_keys_it_needs():
     from dualpixelface_amd.losses import loss_selector
-    sel = loss_selector(_option(loss_type=['smoothL1']))
+    sel = loss_selector(support.option('train_faceDP_dpnet', loss_type=['smoothL1']))
     with pytest.raises(NotImplementedError, match="least_square.*batch\\['idepth'\\] and batch\\['depth'\\]"):
         sel.forward({'pred_depth': torch.ones(1, 1, 2, 2)}, {'disp': torch.ones(1, 2, 2)}, 'disp')
 
@@ -174,7 +170,7 @@ def _three_losses(monkeypatch):
 
     monkeypatch.setattr(ops, 'normal_geo_loss', normal_geo_loss)
     monkeypatch.setattr(ops, 'photometric_loss', photometric_loss)
-    sel = loss_selector(_option(loss_type=THREE, lambdas=[1.0, 0.5, 0.25]))
+    sel = loss_selector(support.option('train_faceDP_dpnet', loss_type=THREE, lambdas=[1.0, 0.5, 0.25]))
     z, img = torch.ones(1, 2, 2), torch.ones(1, 3, 2, 2)
     extra = {'K': torch.eye(3).unsqueeze(0), 'normal': img, 'left': img, 'right': img}
     return sel, calls, fit, extra

@@ -2,6 +2,7 @@
 independent statements of the operator, and the argument checks of the drop-in module, the workspace queries and the header run without a GPU.
 """
 import ctypes
+import functools
 import os
 
 import pytest
@@ -9,13 +10,12 @@ import torch
 import torch.nn.functional as F
 
 from tests import dcn2d_cpu as ref2d
+from tests import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g, dtype=torch.float64) * scale
+rnd = functools.partial(support.rnd, dtype=torch.float64)
 
 
 def maxerr(a, b):

@@ -13,16 +13,12 @@ import torch
 
 from tests import affine_fit_cpu as af
 from tests import loss_bank_cpu as lb
+from tests import support
+from tests.support import DEV
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
 A0, B0 = -26996.49, 63.0
-
-
-def _ops():
-    from dualpixelface_amd import ops
-    return ops
 
 
 @pytest.fixture(scope='module')
@@ -31,7 +27,7 @@ def fixture(golden_dir):
 
 
 def _fit(pred, idepth, **kw):
-    ab, info = _ops().affine_fit(pred.to(DEV), idepth.to(DEV), return_info=True, **kw)
+    ab, info = support.ops().affine_fit(pred.to(DEV), idepth.to(DEV), return_info=True, **kw)
     assert ab.dtype == torch.float32 and tuple(ab.shape) == (pred.shape[0], 2) and not ab.requires_grad
     assert info.dtype == torch.float64 and tuple(info.shape) == (pred.shape[0], 6)
     return ab.cpu(), info.cpu()
@@ -51,12 +47,12 @@ def _against_restatement(pred, idepth, info, tag, max_iters=af.MAX_ITERS, tol=af
     for i, r in enumerate(ref):
         assert abs(its[i] - r['iters']) <= 1 and int(info[i, 3]) == r['count']
         f64 = lambda v: torch.tensor(v, dtype=torch.float64)
-        lb.close(info[i, 4], f64(r['objective']), 1e-9, '%s objective[%d]' % (tag, i))
-        lb.close(info[i, 5], f64(r['objective0']), 1e-9, '%s objective0[%d]' % (tag, i))
+        support.close(info[i, 4], f64(r['objective']), 1e-9, '%s objective[%d]' % (tag, i))
+        support.close(info[i, 5], f64(r['objective0']), 1e-9, '%s objective0[%d]' % (tag, i))
     return ref_ab, ref
 
 
-def _fields(B, n, H, W, seed, sigma=0.05, frac=0.1, zeros=0.15):
+def _fit_fields(B, n, H, W, seed, sigma=0.05, frac=0.1, zeros=0.15):
     g = torch.Generator().manual_seed(seed)
     depth = (torch.rand(B, H, W, generator=g) * 800.0 + 700.0) * (torch.rand(B, H, W, generator=g) >= zeros).float()
     idepth = torch.where(depth > 0, 1.0 / torch.where(depth > 0, depth, torch.ones_like(depth)), torch.zeros_like(depth))
@@ -81,7 +77,7 @@ def test_fit_against_reference_fixture(fixture):
 def test_fit_shapes(shape):
     """Odd sizes with several workgroups per sample and a head stride (one pixel per load); sizes the 16-byte loads take, with and without
     further heads behind head 0."""
-    pred, idepth, _ = _fields(*shape, seed=11)
+    pred, idepth, _ = _fit_fields(*shape, seed=11)
     _, info = _fit(pred, idepth)
     _against_restatement(pred, idepth, info, str(shape))
 
@@ -100,8 +96,8 @@ def test_fit_two_pixels_exact_line():
 def test_fit_mixed_batch_stops_per_sample():
     """A clean sample, a heavy-outlier sample and one without a valid pixel: each stops at its own count, the empty one gives (0, 0) and
     leaves its neighbours as they are on their own."""
-    clean, idc, _ = _fields(1, 2, 40, 56, seed=12, sigma=0.05, frac=0.0)
-    heavy, idh, _ = _fields(1, 2, 40, 56, seed=13, sigma=0.3, frac=0.2)
+    clean, idc, _ = _fit_fields(1, 2, 40, 56, seed=12, sigma=0.05, frac=0.0)
+    heavy, idh, _ = _fit_fields(1, 2, 40, 56, seed=13, sigma=0.3, frac=0.2)
     pred = torch.cat([clean, torch.full_like(clean, 7.0), heavy])
     idepth = torch.cat([idc, torch.zeros_like(idc), idh])
     ab, info = _fit(pred, idepth)
@@ -115,7 +111,7 @@ def test_fit_mixed_batch_stops_per_sample():
 
 
 def test_fit_iteration_cap():
-    pred, idepth, _ = _fields(2, 1, 40, 56, seed=14, sigma=0.3, frac=0.2)
+    pred, idepth, _ = _fit_fields(2, 1, 40, 56, seed=14, sigma=0.3, frac=0.2)
     _, info = _fit(pred, idepth, max_iters=2)
     assert [int(v) for v in info[:, 2]] == [2, 2]
     # (no threshold is involved in two forced steps, so only the order of the fp64 sums separates the two: 1e-9 disparity units is ample)
@@ -128,14 +124,14 @@ def test_fit_iteration_cap():
 def test_fit_fold_of_more_rows_than_threads():
     """1024 x 1028: 257 partial rows in the sample's fold, so its first thread adds two of them (every other shape here folds <= 3).
     Two forced steps, as above: only the order of the fp64 sums separates the two sides."""
-    pred, idepth, _ = _fields(1, 1, 1024, 1028, seed=17)
+    pred, idepth, _ = _fit_fields(1, 1, 1024, 1028, seed=17)
     _, info = _fit(pred, idepth, max_iters=2)
     assert [int(v) for v in info[:, 2]] == [2]
     _against_restatement(pred, idepth, info, '1024x1028', max_iters=2, bar=1e-9)
 
 
 def test_fit_ignores_what_lies_at_invalid_pixels():
-    pred, idepth, _ = _fields(2, 2, 40, 56, seed=15)
+    pred, idepth, _ = _fit_fields(2, 2, 40, 56, seed=15)
     ab, info = _fit(pred, idepth)
     bad = pred.clone()
     bad[:, 0][idepth == 0] = float('nan')
@@ -149,7 +145,7 @@ def test_fit_ignores_what_lies_at_invalid_pixels():
 
 
 def test_fit_repeats_bit_for_bit():
-    pred, idepth, _ = _fields(3, 5, 67, 129, seed=16, sigma=0.3, frac=0.2)
+    pred, idepth, _ = _fit_fields(3, 5, 67, 129, seed=16, sigma=0.3, frac=0.2)
     a, b = _fit(pred, idepth), _fit(pred, idepth)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
 
@@ -192,12 +188,12 @@ def test_loss_kernel_against_reference_fixture(fixture):
         pred, batch, ab = fixture.inputs(case, DEV)
         pred.requires_grad_()
         transform = 'reciprocal' if (kind == 'smoothL1' and tt == 'depth') else 'identity'
-        loss = _ops().depth_loss(pred, batch['depth'], batch.get('mask'), None, fixture.head_weights(n), kind, transform,
+        loss = support.ops().depth_loss(pred, batch['depth'], batch.get('mask'), None, fixture.head_weights(n), kind, transform,
                                  fixture.variance_focus, target_ab=ab)
         grad, = torch.autograd.grad(loss, pred)
         ref_loss, ref_grad = fixture.expected(case)
-        lb.close(loss, ref_loss, 1e-5, name + ' loss')
-        lb.close_elem(grad, ref_grad, name + ' grad')
+        support.close(loss, ref_loss, 1e-5, name + ' loss')
+        support.close_elem(grad, ref_grad, name + ' grad')
         zero = batch['depth'] == 0
         on = batch['mask'] > 0 if masked else torch.ones_like(zero)
         counted_zero += int((zero & on).sum())
@@ -212,21 +208,21 @@ def test_loss_kernel_against_reference_fixture(fixture):
 
 def test_loss_kernel_shapes_and_refusals():
     from dualpixelface_amd._lib import DpfError
-    pred, idepth, depth = _fields(3, 5, 67, 129, seed=17)
+    pred, idepth, depth = _fit_fields(3, 5, 67, 129, seed=17)
     mask = (torch.rand(3, 67, 129, generator=torch.Generator().manual_seed(18)) < 0.6).float()
     ab = torch.tensor([[63.0, -26996.49], [61.5, -25000.0], [64.0, -28000.0]])
     weights = [1.0, 0.9, 0.8, 0.7, 0.6]
     for kind in ('smoothL1', 'silog'):
         d = depth if kind == 'smoothL1' else torch.where(depth > 0, depth, torch.full_like(depth, 900.0))     # silog: every target positive
         p = (pred if kind == 'smoothL1' else pred.clamp(min=5.0)).to(DEV).requires_grad_()
-        loss = _ops().depth_loss(p, d.to(DEV), mask.to(DEV), None, weights, kind, 'identity', 0.85, target_ab=ab.to(DEV))
+        loss = support.ops().depth_loss(p, d.to(DEV), mask.to(DEV), None, weights, kind, 'identity', 0.85, target_ab=ab.to(DEV))
         grad, = torch.autograd.grad(loss, p)
         ref_loss, ref_grad = lb.depth_loss(p, af.depth2disp(d, ab), mask, None, weights, kind, 'identity', 0.85)
         assert torch.isfinite(ref_loss)
-        lb.close(loss, ref_loss, 1e-5, kind + ' loss')
-        lb.close_elem(grad, ref_grad, kind + ' grad')
+        support.close(loss, ref_loss, 1e-5, kind + ' loss')
+        support.close_elem(grad, ref_grad, kind + ' grad')
     with pytest.raises(DpfError, match='target_ab'):
-        _ops().depth_loss(pred.to(DEV), depth.to(DEV), None, None, weights, 'smoothL1', 'identity', 0.0, target_ab=ab[:2].to(DEV))
+        support.ops().depth_loss(pred.to(DEV), depth.to(DEV), None, None, weights, 'smoothL1', 'identity', 0.0, target_ab=ab[:2].to(DEV))
 
 
 # ---- 3. the hooks end to end
@@ -268,14 +264,14 @@ def test_hooks_against_restatement_and_fixture(fixture):
         res = _selector(kind, fixture.loss_weight, fixture.variance_focus).forward({'pred_depth': pred}, batch, tt)
         ab = res['abvalue']
         assert tuple(ab.shape) == (pred.shape[0], 2) and ab.dtype == torch.float32 and not ab.requires_grad
-        assert torch.equal(ab, _ops().affine_fit(pred, batch['idepth'])) and res['final_loss'].dim() == 0
+        assert torch.equal(ab, support.ops().affine_fit(pred, batch['idepth'])) and res['final_loss'].dim() == 0
         d = af.dd(ab.cpu().numpy(), ref_ab.cpu().numpy(), batch['idepth'].cpu().numpy())
         assert d <= 2 * fixture.ref_dd, (name, d)
         grad, = torch.autograd.grad(res['final_loss'], pred)
         own_loss, own_grad = af.branch_call(kind, tt, pred, batch, weights, fixture.variance_focus, ab)      # at the device's own ab
-        lb.close(res[kind + '_loss'], own_loss, 1e-5, name + ' loss at its own ab')
-        lb.close(res['final_loss'], own_loss, 1e-5, name + ' final_loss at its own ab')
-        lb.close_elem(grad, own_grad, name + ' grad at its own ab')
+        support.close(res[kind + '_loss'], own_loss, 1e-5, name + ' loss at its own ab')
+        support.close(res['final_loss'], own_loss, 1e-5, name + ' final_loss at its own ab')
+        support.close_elem(grad, own_grad, name + ' grad at its own ab')
         ref_loss, _ = fixture.expected(case)
         bar = 1e-5 * abs(float(ref_loss)) + _silog_shift_bound(kind, tt, pred, batch, weights, fixture.variance_focus, ref_ab, 2 * fixture.ref_dd)
         err = abs(float(res['final_loss'].detach()) - float(ref_loss))
@@ -285,14 +281,14 @@ def test_hooks_against_restatement_and_fixture(fixture):
 
 def test_hook_silog_depth_returns_the_fit():
     """silog against 'depth' overwrites prediction and target (silog.py:35-37): the loss is the 'given' one, the abvalue the fit's."""
-    pred, idepth, depth = _fields(2, 3, 40, 56, seed=19, zeros=0.0)
+    pred, idepth, depth = _fit_fields(2, 3, 40, 56, seed=19, zeros=0.0)
     far = (torch.rand(2, 3, 40, 56, generator=torch.Generator().manual_seed(20)) * 800.0 + 700.0).to(DEV).requires_grad_()
     batch = {'idepth': idepth.to(DEV), 'depth': depth.to(DEV)}
     res = _selector('silog', [1.0, 0.7, 0.5], 0.85).forward({'pred_depth': far}, batch, 'depth')
     ref_loss, ref_grad = lb.depth_loss(far, depth, None, None, [1.0, 0.7, 0.5], 'silog', 'identity', 0.85)
-    lb.close(res['final_loss'], ref_loss, 1e-5, 'loss')
-    lb.close_elem(torch.autograd.grad(res['final_loss'], far)[0], ref_grad, 'grad')
-    assert torch.equal(res['abvalue'], _ops().affine_fit(far, batch['idepth']))
+    support.close(res['final_loss'], ref_loss, 1e-5, 'loss')
+    support.close_elem(torch.autograd.grad(res['final_loss'], far)[0], ref_grad, 'grad')
+    assert torch.equal(res['abvalue'], support.ops().affine_fit(far, batch['idepth']))
 
 
 def test_three_losses_share_one_fit_bit_for_bit():
@@ -337,20 +333,11 @@ def test_three_losses_share_one_fit_bit_for_bit():
         print(k, shared[k].detach().cpu().tolist())
         assert torch.equal(shared[k], alone[k]), k
         assert bool(torch.isfinite(shared[k]).all()) and bool((shared[k] != 0).any()), k
-    assert torch.equal(shared['abvalue'], _ops().affine_fit(pred.to(DEV), batch['idepth']))
+    assert torch.equal(shared['abvalue'], support.ops().affine_fit(pred.to(DEV), batch['idepth']))
     assert torch.equal(gs, ga) and bool(torch.isfinite(gs).all()) and bool((gs != 0).any())
 
 
 # ---- 4. the whole step
-def _dpnet(config, **model_over):
-    from dualpixelface_amd import load_option
-    from dualpixelface_amd.plugin import DPNET
-    from dualpixelface_amd.recipe import fill_by_recipe
-    model = DPNET(load_option(config, **model_over))
-    fill_by_recipe(model)
-    return model.to(DEV).train()
-
-
 def _batch(strip):
     from dualpixelface_amd.recipe import synthetic_batch
     batch = {k: v.to(DEV) for k, v in synthetic_batch(2, 64, 96, seed=7, mask_mode='bern').items()}
@@ -365,20 +352,20 @@ def test_dpnet_trains_without_abvalue_graph_equals_eager(monkeypatch):
     config, batch = 'train_faceDP_dpnet', _batch(True)
     with ops.deterministic_mode():
         monkeypatch.setenv('DPF_STEP_GRAPH', '1')
-        a = _dpnet(config)
+        a = support.dpnet(config)
         assert a.option.dataset.dp_conversion == 'given'
         before = a.flat_parameters().clone()
         ra = [a.train_step(batch, None, lr=1e-3) for _ in range(4)]                      # two warm-up steps, the capture, one replay
         la = [float(r['final_loss'].detach()) for r in ra]
         assert a._graph_state.get('graph') is not None and not a._graph_state.get('failed')
         monkeypatch.setenv('DPF_STEP_GRAPH', '0')
-        b = _dpnet(config)
+        b = support.dpnet(config)
         lb_, weights = [], b.loss_model.loss_func[0].head_weights(5)
         for _ in range(4):
             res = b.train_step(batch, None, lr=1e-3)
             assert res['pred_depth'].shape == (2, 5, 64, 96) and tuple(res['abvalue'].shape) == (2, 2)
             ref_loss, _ = af.branch_call('smoothL1', 'disp', res['pred_depth'], batch, weights, 0.0, res['abvalue'])
-            lb.close(res['final_loss'], ref_loss, 1e-5, 'step %d final_loss' % len(lb_))
+            support.close(res['final_loss'], ref_loss, 1e-5, 'step %d final_loss' % len(lb_))
             lb_.append(float(res['final_loss'].detach()))
     assert all(np.isfinite(la)) and la == lb_, (la, lb_)
     assert float((a.flat_parameters() - before).abs().max()) > 0
@@ -391,7 +378,7 @@ def test_dpnet_evaluates_a_batch_without_abvalue():
     is that shared step.  affine_dp compares against batch['disp'], which such a batch does not have, so absolute_dp is the metric configured.)"""
     from dualpixelface_amd import metrics, ops
     batch = _batch(True)
-    model = _dpnet('train_faceDP_dpnet', metric_type=['absolute_dp']).eval()
+    model = support.dpnet('train_faceDP_dpnet', metric_type=['absolute_dp']).eval()
     bench = model.metric_model.metric_func[0]
     res = model.test_step(batch, 0)
     assert 'final_loss' not in res and tuple(res['abvalue'].shape) == (2, 2) and res['abvalue'].dtype == torch.float32

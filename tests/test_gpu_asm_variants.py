@@ -18,23 +18,15 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.test_gpu_e2e import GRAD_FLOOR, K_SPREAD, build_model, close
+from tests import support
+from tests.support import DEV, close, rnd
+from tests.test_gpu_e2e import GRAD_FLOOR, K_SPREAD, build_model
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
 MODES = ('nearest', 'bilinear', 'phase')
 SUBSETS = [s for s in itertools.product((False, True), repeat=3) if any(s)]
 SUBSET_IDS = ['+'.join(m for m, on in zip(MODES, s) if on) for s in SUBSETS]
 EPS = 2.0 ** -24
-
-
-def _ops():
-    from dualpixelface_amd import ops
-    return ops
-
-
-def rnd(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
 
 
 def _device_tables(h, w, delta, subset):
@@ -67,7 +59,7 @@ def test_shift_copies_forward_and_gather_adjoint(golden_dir, subset):
     then a random 10 x 13 map (a row tail below the 8-row block, w % 4 != 0: the scalar column path) against the fp64 table evaluation."""
     from dualpixelface_amd.sampler_tables import apply_tables_reference, is_fractional
     from oracle.stereodpnet import StereoDPNetOracle
-    ops = _ops()
+    ops = support.ops()
     g = np.load(golden_dir + '/shift_fractional.npz')
     names = [m for m, on in zip(MODES, subset) if on]
     for ci in range(3):
@@ -136,7 +128,7 @@ def _within(a, ref, terms, name):
 @pytest.mark.parametrize('fetch', [False, True], ids=['mean', 'fetch'])
 @pytest.mark.parametrize('M', [1, 2, 3])
 def test_cv_select_copies_and_fetch(M, fetch):
-    ops = _ops()
+    ops = support.ops()
     B, C, L, h = 2, 5, 8, 10
     for w, masks in ((13, (0xFF, 0x01, 0xA4)), (24, (0xA4,))):
         xs = [rnd(B, C, M, h, w, seed=80 + M + i) for i in range(2)]
@@ -165,7 +157,7 @@ def test_cv_select_copies_and_fetch(M, fetch):
 
 def test_instance_norm_prelu_gate():
     """The PReLU gate: instance norm (affine) + PReLU with ONE slope over [B,C,M,h,w]; the slope gradient sums over the whole tensor."""
-    ops = _ops()
+    ops = support.ops()
     x = rnd(2, 4, 3, 6, 9, seed=60)
     w = torch.rand(4, generator=torch.Generator().manual_seed(61)) + 0.5
     b = rnd(4, seed=62)
@@ -294,7 +286,7 @@ def test_variant_gradients_within_the_references_own_noise(golden_dir, tag):
 
 
 def test_v5_deterministic_mode_two_steps_equal_bits(golden_dir):
-    ops = _ops()
+    ops = support.ops()
     g, over, batch = _fixture(golden_dir, 'v5_no_nearest_relu_fetch_fix')
     runs = []
     with ops.deterministic_mode():

@@ -13,31 +13,12 @@ import torch
 import torch.nn.functional as F
 
 from tests import dcn2d_cpu as ref2d
+from tests import support
+from tests.support import DEV, close, rnd
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
 GRADS = ('grad_input', 'grad_offset', 'grad_mask', 'grad_weight', 'grad_bias')
-
-
-def _ops():
-    from dualpixelface_amd import ops
-    return ops
-
-
-def close(a, b, tol=1e-4, name=''):
-    a = a.detach().cpu().double()
-    b = b.detach().cpu().double()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    scale = max(b.abs().max().item(), 1e-6)
-    err = (a - b).abs().max().item()
-    print('%s: max err %.3e, scale %.3e, rel %.3e (bound %.1e)' % (name, err, scale, err / scale, tol))
-    assert err <= tol * scale, '%s: max err %.3e vs scale %.3e (rel %.3e)' % (name, err, scale, err / scale)
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
 
 
 # (B, C, K, H, W), (kh, kw), stride, pad, dil, (group, dg)
@@ -115,7 +96,7 @@ def _compare_grads(got, g_ref, tol, tag, names=GRADS):
 def test_parity_forward_and_gradients(case, modulated):
     """Forward and every gradient against the fp64 helper; the inputs put 5-40 % of the samples wholly outside the image and at least 5 % on
     its border (some corners outside), asserted here on the CPU."""
-    ops = _ops()
+    ops = support.ops()
     (B, C, K, H, W), (kh, kw), s, p, d, (group, dg) = case
     (x, off, mask, w, b, go), y_ref, g_ref = _problem(case, modulated)
     out_all, out_some = ref2d.outside_fractions(off, H, W, kh, kw, s, p, d, dg)
@@ -138,7 +119,7 @@ def test_zero_offsets_and_unit_mask_equal_the_plain_convolution(group, dg):
         off, mask = torch.zeros(B, dg * 18, Ho, Wo), torch.ones(B, dg * 9, Ho, Wo)
         xg, og, mg, wg, bg = _gpu((x, off, mask, w, b))
         for m in (None, mg):
-            y = _ops().deform_conv2d_forward_raw(xg, wg, bg, og, m, (s, s), (d, d), (d, d), group, dg)
+            y = support.ops().deform_conv2d_forward_raw(xg, wg, bg, og, m, (s, s), (d, d), (d, d), group, dg)
             close(y, ref, 1e-5, 'zero offsets s%d d%d %s' % (s, d, 'plain' if m is None else 'mask 1'))
 
 
@@ -146,7 +127,7 @@ def test_zero_offsets_and_unit_mask_equal_the_plain_convolution(group, dg):
 def test_integer_offsets_and_the_validity_rule(modulated):
     """Integer offsets in [-2, 2] put samples on pixel centres, on coordinate -1 and on the far border.  Every sample is one pixel or nothing:
     forward, grad_input and grad_weight to 1e-5.  (The coordinate gradient is one-sided there and is left to the parity cases.)"""
-    ops = _ops()
+    ops = support.ops()
     _, _, s, p, d, (group, dg) = INT_CASE
     (x, off, mask, w, b, go), y_ref, g_ref = _problem(INT_CASE, modulated, True)
     xg, og, mg, wg, bg, gg = _gpu((x, off, mask, w, b, go))
@@ -158,7 +139,7 @@ def test_integer_offsets_and_the_validity_rule(modulated):
 def test_plain_operator_equals_the_3d_entry_at_depth_one():
     """One plain case through dpf_deform_conv3d_* on a depth-1 volume with zero depth offsets, on the GPU: the same bars, and the forward bit for
     bit (corners 0-3 of the depth-1 trilinear rule carry the weight 1 a b in the bilinear rule's order, and a tile accumulates in one order)."""
-    ops = _ops()
+    ops = support.ops()
     case = CASES[1]
     (B, C, K, H, W), (kh, kw), s, p, d, (group, dg) = case
     T = kh * kw
@@ -185,7 +166,7 @@ def test_plain_operator_equals_the_3d_entry_at_depth_one():
 
 def test_null_mask_and_null_bias():
     """mask = NULL with bias = NULL: the plain operator without a bias; grad_mask and grad_bias are not produced."""
-    ops = _ops()
+    ops = support.ops()
     case = CASES[1]
     _, _, s, p, d, (group, dg) = case
     (x, off, _, w, b, go), y_ref, g_ref = _problem(case, False)
@@ -230,7 +211,7 @@ def test_refusals_write_nothing(C, K, kh, kw, group, dg, code):
 def test_reproducibility(modulated):
     """Three tiles: grad_offset and grad_mask are stored once per element, so two backward calls agree bitwise in every mode; grad_input and
     grad_weight agree bitwise under deterministic mode, where the first call also meets the parity bars.  The mode is restored."""
-    ops = _ops()
+    ops = support.ops()
     _, _, s, p, d, (group, dg) = THREE_TILES
     (x, off, mask, w, b, go), _, g_ref = _problem(THREE_TILES, modulated)
     xg, og, mg, wg, bg, gg = _gpu((x, off, mask, w, b, go))
@@ -251,7 +232,7 @@ def test_reproducibility(modulated):
 def test_autograd_equals_the_raw_backward(modulated):
     """ops.deform_conv2d(...).backward(): the tensors' .grad are the raw backward's results (same kernels; grad_offset and grad_mask, which are
     reproducible in every mode, bitwise)."""
-    ops = _ops()
+    ops = support.ops()
     _, _, s, p, d, (group, dg) = THREE_TILES
     (x, off, mask, w, b, go), y_ref, g_ref = _problem(THREE_TILES, modulated)
     ts = _gpu((x, off, mask, w, b))
@@ -368,7 +349,7 @@ def test_grad_bias_of_a_batch_beyond_one_channel_sum_launch():
     """B K = 256 x 256 > 65535 rows: grad_bias is reduced in two slices of whole images (255 + 1) and equals the plain sum of grad_output
     (2e-4 of its maximum, the bar of every gradient here); outside deterministic mode its partial sums meet in float atomics, so it is
     compared, not required to repeat bitwise."""
-    ops = _ops()
+    ops = support.ops()
     B, C, K, H, W = 256, 2, 256, 3, 3
     x, off, w, b = rnd(B, C, H, W, seed=380), rnd(B, 2, H, W, seed=381), rnd(K, C, 1, 1, seed=382, scale=0.1), rnd(K, seed=383)
     go = rnd(B, K, H, W, seed=384)

@@ -12,30 +12,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import support
+from tests.support import DEV, close, rnd
+
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
 GRADS = ('grad_input', 'grad_offset', 'grad_weight', 'grad_bias')
-
-
-def _ops():
-    from dualpixelface_amd import ops
-    return ops
-
-
-def close(a, b, tol=1e-4, name=''):
-    a = a.detach().cpu().double()
-    b = b.detach().cpu().double()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    scale = max(b.abs().max().item(), 1e-6)
-    err = (a - b).abs().max().item()
-    print('%s: max err %.3e, scale %.3e, rel %.3e (bound %.1e)' % (name, err, scale, err / scale, tol))
-    assert err <= tol * scale, '%s: max err %.3e vs scale %.3e (rel %.3e)' % (name, err, scale, err / scale)
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
 
 
 K3, ONE = (3, 3, 3), (1, 1, 1)
@@ -99,7 +81,7 @@ def _gpu(ts):
 
 
 def _check_case(case, integer_offsets=False):
-    ops = _ops()
+    ops = support.ops()
     _, _, s, p, d, (group, dg) = case
     (x, off, w, b, go), y_ref, g_ref = _problem(case, integer_offsets)
     xg, og, wg, bg, gg = _gpu((x, off, w, b, go))
@@ -117,7 +99,7 @@ def test_grouped_parity_forward_and_gradients(case):
 
 
 def _fwd(x, off, w, b, group, dg):
-    return _ops().deform_conv_forward_raw(x.to(DEV), w.to(DEV), b.to(DEV), off.to(DEV), ONE, ONE, ONE, group, dg)
+    return support.ops().deform_conv_forward_raw(x.to(DEV), w.to(DEV), b.to(DEV), off.to(DEV), ONE, ONE, ONE, group, dg)
 
 
 @pytest.mark.parametrize('group', [2, 4])
@@ -158,7 +140,7 @@ def test_integer_offsets_and_the_validity_rule():
 def test_grad_input_channels_cut_inside_a_group(case):
     """gi_channels = 10 of 16 with (2, 2): the cut falls inside conv group 1 and offset group 1; with (1, 1) on the single-group fallback it
     falls inside the one group.  grad_input[:, :10] is the oracle's, grad_input[:, 10:] exactly zero, the other three gradients are unchanged."""
-    ops = _ops()
+    ops = support.ops()
     (x, off, w, b, go), _, g_ref = _problem(case)
     xg, og, wg, bg, gg = _gpu((x, off, w, b, go))
     gi, goff, gw, gb = ops.deform_conv_backward_raw(xg, wg, bg, og, gg, ONE, ONE, ONE, *case[5], gi_channels=10)
@@ -172,7 +154,7 @@ def test_grad_input_channels_cut_inside_a_group(case):
 def test_deterministic_mode_is_bitwise_reproducible(case):
     """Under ops.deterministic_mode() five backward launches return the same bits for all four gradients (the first meets the parity
     tolerances); outside it grad_offset is still bitwise equal over five launches: every element is written once, by one workgroup."""
-    ops = _ops()
+    ops = support.ops()
     groups = case[5]
     (x, off, w, b, go), _, g_ref = _problem(case)
     xg, og, wg, bg, gg = _gpu((x, off, w, b, go))
@@ -194,7 +176,7 @@ def test_refused_groupings_write_nothing(C, K, group, dg):
     output buffers keep their contents."""
     import ctypes
     from dualpixelface_amd._lib import DpfError, lib
-    ops = _ops()
+    ops = support.ops()
     B, D, H, W = 1, 2, 4, 6
     x, off = rnd(B, C, D, H, W, seed=360).to(DEV), rnd(B, dg * 81, D, H, W, seed=361).to(DEV)
     w, b = rnd(K, max(C // group, 1), 3, 3, 3, seed=362).to(DEV), rnd(K, seed=363).to(DEV)
@@ -222,7 +204,7 @@ def test_refused_groupings_write_nothing(C, K, group, dg):
 
 def test_autograd_surface_takes_the_grouping():
     """ops.deform_conv3d(..., group=2, deformable_group=2): torch.autograd.grad matches the oracle's gradients."""
-    ops = _ops()
+    ops = support.ops()
     case = (BASE, K3, ONE, ONE, ONE, (2, 2))
     (x, off, w, b, go), y_ref, g_ref = _problem(case)
     xg, og, wg, bg = [t.to(DEV).requires_grad_() for t in (x, off, w, b)]

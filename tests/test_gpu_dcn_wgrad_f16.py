@@ -9,7 +9,9 @@ import functools
 import pytest
 import torch
 
-from tests.test_gpu_ops import DEV, _ops, _spread, close, rnd
+from tests import support
+from tests.support import DEV, close, rnd
+from tests.test_gpu_ops import _spread
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +20,7 @@ LAYOUTS = ['xchan', 'gochan', 'xwbands', 'plain']
 
 
 @functools.lru_cache(maxsize=None)
-def _case(cfg, layout):
+def _wgrad_case(cfg, layout):
     """Inputs and fp64 references of one (shape, layout); computed once, shared, never modified."""
     from oracle import dcn3d
     B, C, K, D, H, W = cfg
@@ -44,7 +46,7 @@ def _case(cfg, layout):
 
 
 def _backward(c):
-    ops = _ops()
+    ops = support.ops()
     xg, og, wg, bg = [c[k].to(DEV).requires_grad_() for k in ('x', 'off', 'wt', 'bs')]
     y = ops.deform_conv3d(xg, og, wg, bg)
     return torch.autograd.grad(y, (xg, og, wg, bg), c['go'].to(DEV))
@@ -74,7 +76,7 @@ def test_grad_weight_f16_component_path_relative_to_own_inputs(cfg, layout):
     """x channels / go rows / x column bands at 1 .. 2^-34 of the tile's maximum, and plain data: every grad_weight element within 2 x the
     worst element of the fp32 matrix instruction (+ 1e-7) relative to sum |go| S(|x|); grad_input and grad_offset keep the bars of
     test_deform_conv_backward_f16_component_path_in_block_dynamic_range (the packed sample tile feeds neither)."""
-    c = _case(cfg, layout)
+    c = _wgrad_case(cfg, layout)
     assert (c['dw_den'] > 0).all()               # a condition on the inputs: every element has a non-zero scale of its own
     errs = {path: _on_path(path, lambda: _errors(c, _backward(c))) for path in (0, 2)}
     print('grad_weight / grad_input / grad_offset errors, path 0 and path 2:', cfg, layout, errs)
@@ -122,8 +124,8 @@ def test_grad_weight_f16_component_path_reproducible(cfg, layout):
     exponents are found through LDS atomics; an integer max does not depend on their order), and the first one meets the accuracy bar.
     (The spread sits in ONE operand per case: deterministic mode sums in fixed point with a unit of 2^-56, on every matrix path, so
     products of two operands that are both 2^-34 down lie below what it can hold.)"""
-    ops = _ops()
-    c = _case(cfg, layout)
+    ops = support.ops()
+    c = _wgrad_case(cfg, layout)
     assert (c['dw_den'] > 0).all()
 
     def five():
@@ -148,7 +150,7 @@ def test_grad_weight_f16_component_path_slow_samples_beyond_the_channel_scale(de
     directly -- in default mode with float atomics, in deterministic mode through the integer shadow.  All gradients within
     test_deform_conv's 2e-4, and grad_weight per element within 2 x the fp32 matrix instruction relative to sum |go| S(|x|)."""
     from oracle import dcn3d
-    ops = _ops()
+    ops = support.ops()
     B, C, K, D, H, W = 1, 16, 24, 4, 7, 44
     c = dict(x=rnd(B, C, D, H, W, seed=460), off=rnd(B, 81, D, H, W, seed=461, scale=4.0), wt=rnd(K, C, 3, 3, 3, seed=462, scale=0.1),
              bs=rnd(K, seed=463), go=rnd(B, K, D, H, W, seed=464))

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from tests import device_metrics_fixture as fx
+from tests import support
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -71,13 +72,9 @@ def _raw(name, *args):
     return getattr(lib().cdll, name)(*args)
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def test_refusals_launch_nothing():
     from dualpixelface_amd._lib import lib
-    L = lib()
+    L, _p = lib(), support.ptr
     B, n = 2, 300
     x = torch.rand(B, n, device=DEV) + 1.0
     x3 = torch.rand(B, 3, n, device=DEV)
@@ -124,7 +121,7 @@ def test_refusals_launch_nothing():
 
 # ------------------------------------------------------------------------------------------------------- the three families
 @functools.lru_cache(maxsize=None)
-def _case(shape, mask):
+def _metrics_case(shape, mask):
     pred_, batch = fx.make_case(*shape, mask=mask, seed=sum(shape))
     return pred_, batch, fx.reference_rows(pred_, batch)
 
@@ -141,7 +138,7 @@ def _device_rows(pred_, batch, target_type='disp'):
 @pytest.mark.parametrize('mask', fx.MASKS)
 @pytest.mark.parametrize('shape', fx.SHAPES)
 def test_families_within_the_yardstick(shape, mask):
-    pred_, batch, ref = _case(shape, mask)
+    pred_, batch, ref = _metrics_case(shape, mask)
     rows = _device_rows(pred_, batch)
     for name in ('absolute_dp', 'normal_dp', 'affine_dp'):
         T, F = ref[name]
@@ -269,7 +266,7 @@ def test_ten_calls_return_identical_bits():
 def test_deferred_forward_never_waits_on_the_host():
     from dualpixelface_amd.config import load_option
     from dualpixelface_amd.selectors import metric_selector
-    pred_, batch, ref = _case((2, 16, 24), 'bern')
+    pred_, batch, ref = _metrics_case((2, 16, 24), 'bern')
     pred_d, batch_d = fx.cast(pred_, device=DEV), fx.cast(batch, device=DEV)
     sel = metric_selector(load_option())
     with sel.deferred():

@@ -11,18 +11,11 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from tests import support
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H, W = 32, 48
-
-
-def _model():
-    from dualpixelface_amd import load_option
-    from dualpixelface_amd.plugin import STEREODPNET
-    from dualpixelface_amd.recipe import fill_by_recipe
-    m = STEREODPNET(load_option())
-    fill_by_recipe(m)
-    return m.to('cuda').train()
 
 
 def _full_batch():
@@ -37,7 +30,7 @@ def _worker(rank, world, port, sync_bn, out):
     from dualpixelface_amd.distributed import init_from_env, make_reducer, broadcast_flat
     torch.cuda.set_device(0)
     init_from_env('gloo')
-    model = _model()
+    model = support.build('STEREODPNET', support.option())
     if rank == 1:                                  # broadcast must repair this
         with torch.no_grad():
             model.flat_parameters().mul_(1.5)
@@ -68,17 +61,17 @@ def _worker(rank, world, port, sync_bn, out):
     dist.destroy_process_group()
 
 
-def _run(sync_bn):
+def _run_two_ranks(sync_bn):
     port = 33500 + (os.getpid() % 2000) + (7 if sync_bn else 0)
     mgr = mp.Manager()
     out = mgr.dict()
     mp.spawn(_worker, args=(2, port, sync_bn, out), nprocs=2, join=True)
-    _run.logs = (out['log0'], out['log1'])
+    _run_two_ranks.logs = (out['log0'], out['log1'])
     return out[0], out[1]
 
 
 def test_two_ranks_per_rank_batchnorm():
-    (p0, g0, l0, _), (p1, g1, l1, _) = _run(False)
+    (p0, g0, l0, _), (p1, g1, l1, _) = _run_two_ranks(False)
     assert torch.equal(g0, g1), 'both ranks must hold the same summed gradient'
     assert torch.equal(p0, p1), 'parameters must stay replicated after the fused Adam step'
     assert l0 != l1                                 # different samples
@@ -86,7 +79,7 @@ def test_two_ranks_per_rank_batchnorm():
     full = _full_batch()
     ref = torch.zeros_like(g0)
     for r in range(2):
-        m = _model()
+        m = support.build('STEREODPNET', support.option())
         m.flat_gradients(zero=True)
         res = m.forward({k: v[2 * r:2 * r + 2].cuda() for k, v in full.items()})
         res['final_loss'].backward()
@@ -95,16 +88,16 @@ def test_two_ranks_per_rank_batchnorm():
     assert (g0 - ref).abs().max().item() <= 2e-3 * scale
     # the exchange overlaps the backward pass: the normal head's bucket (2) and the aggregation + cost-volume bucket (1) are
     # all-reduced from tensor hooks BEFORE backward() returns, the feature extractor's (0) after it; 3 collectives per step in all
-    for log, counts in _run.logs:
+    for log, counts in _run_two_ranks.logs:
         assert log == [('launch', 2), ('launch', 1), ('backward_done',), ('launch', 0)], log
         assert counts == {'all_reduce': 3, 'all_gather': 0}, counts
 
 
 def test_two_ranks_sync_batchnorm_equals_single_process_full_batch():
-    (p0, g0, l0, rm0), (p1, g1, l1, rm1) = _run(True)
+    (p0, g0, l0, rm0), (p1, g1, l1, rm1) = _run_two_ranks(True)
     assert torch.equal(p0, p1) and torch.equal(g0, g1)
     assert torch.allclose(rm0, rm1, rtol=0, atol=1e-7), 'running statistics follow the global batch on every rank'
-    m = _model()
+    m = support.build('STEREODPNET', support.option())
     res = m.train_step({k: v.cuda() for k, v in _full_batch().items()}, None, lr=1e-3)
     ref_p = m.flat_parameters().detach().cpu()
     ref_g = m.flat_gradients(zero=False).detach().cpu()
@@ -121,7 +114,7 @@ def test_two_ranks_sync_batchnorm_equals_single_process_full_batch():
     # stack, 2 in the normal head); the three dilated branches of a DPBlock are independent and travel in ONE packed exchange (10
     # DPBlock calls: -20) -> 99.  A BatchNorm's statistics are needed before the next layer can run and its gradient sums before its dx,
     # so exchanges of consecutive layers cannot be merged.
-    for log, counts in _run.logs:
+    for log, counts in _run_two_ranks.logs:
         assert counts == {'all_gather': 99, 'all_reduce': 102}, counts
 
 
@@ -174,7 +167,7 @@ def _nccl_one_rank_worker(port, out):
     try:
         from dualpixelface_amd.recipe import synthetic_batch
         batch = {k: v.cuda() for k, v in synthetic_batch(2, 64, 96, seed=11).items()}
-        model = _model()
+        model = support.build('STEREODPNET', support.option())
         reducer = make_reducer(model, force_collectives=True)
         assert reducer.collectives and reducer.world_size == 1 and reducer.stage_of == {'aggregation': 1, 'normal': 2}
         sent = {}
@@ -191,7 +184,7 @@ def _nccl_one_rank_worker(port, out):
         flat = model.flat_gradients(zero=False)
         same = all(torch.equal(flat[lo:hi], sent[bi]) for bi, (lo, hi) in enumerate(reducer.buckets))
         # the twin without a reducer (no collectives at all): same weights, same batch
-        twin = _model()
+        twin = support.build('STEREODPNET', support.option())
         res2 = twin.train_step(batch)
         torch.cuda.synchronize()
         g1, g2 = flat.double().cpu(), twin.flat_gradients(zero=False).double().cpu()

@@ -10,33 +10,17 @@ import numpy as np
 import pytest
 import torch
 
+from tests import support
+from tests.support import DEV, close
+
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 K_SPREAD = 4          # the project's multiple of the reference's own fp32 noise
 
 
-def close(a, b, tol, name):
-    a = a.detach().cpu().double()
-    b = torch.as_tensor(b).detach().cpu().double()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    scale = max(b.abs().max().item(), 1e-6)
-    err = (a - b).abs().max().item()
-    print('%s: max err %.3e / scale %.3e = %.3e (bound %.1e)' % (name, err, scale, err / scale, tol))
-    assert err <= tol * scale, '%s: max err %.3e vs scale %.3e (rel %.3e)' % (name, err, scale, err / scale)
-
-
 def _model(config='train_faceDP_dpnet', **over):
-    from dualpixelface_amd import load_option
-    from dualpixelface_amd.plugin import DPNET
-    from dualpixelface_amd.recipe import fill_by_recipe
-    opt = load_option(config)
-    for k, v in over.items():
-        setattr(opt, k, v)
-    model = DPNET(opt)
-    fill_by_recipe(model)
-    return model.to(DEV).train()
+    return support.build('DPNET', support.option_set(config, **over))
 
 
 def test_dpnet_plugin_against_reference_golden(golden_dir):

@@ -6,44 +6,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import support
+from tests.support import DEV, close, close_elem, rnd
+
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
 
-
-def _ops():
-    from dualpixelface_amd import ops
-    return ops
-
-
-def close(a, b, tol=1e-4, name=''):
-    a = a.detach().cpu().double()
-    b = torch.as_tensor(b).detach().cpu().double()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    scale = max(b.abs().max().item(), 1e-6)
-    err = (a - b).abs().max().item()
-    print('%s: max err %.3e / scale %.3e = %.3e (bound %.1e)' % (name, err, scale, err / scale, tol))
-    assert err <= tol * scale, '%s: max err %.3e vs scale %.3e (rel %.3e)' % (name, err, scale, err / scale)
-
-
-def close_elem(a, b, name='', rtol=1e-4, atol=1e-5):
-    a = a.detach().cpu().double()
-    b = torch.as_tensor(b).detach().cpu().double()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    rms = max(b.pow(2).mean().sqrt().item(), 1e-30)
-    excess = (a - b).abs() - (atol * rms + rtol * b.abs())
-    worst = excess.max().item()
-    print('%s: worst excess %.3e (rms %.3e)' % (name, worst, rms))
-    assert worst <= 0, '%s: %d of %d elements outside rtol %.0e / atol %.0e x rms %.3e (worst excess %.3e)' % (
-        name, int((excess > 0).sum()), excess.numel(), rtol, atol, rms, worst)
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def bits(t):
+def int_bits(t):
     return t.detach().cpu().contiguous().view(torch.int32)
 
 
@@ -71,7 +40,7 @@ def _pool_input(kind, shape, seed):
 @pytest.mark.parametrize('shape', POOL_SIZES)
 @pytest.mark.parametrize('k,s,p', POOLS)
 def test_maxpool_bitwise(k, s, p, shape, kind):
-    ops = _ops()
+    ops = support.ops()
     x = _pool_input(kind, shape, seed=3).requires_grad_()
     y_ref, i_ref = F.max_pool2d(x, k, s, p, return_indices=True)
     g = torch.randint(-3, 4, y_ref.shape, generator=torch.Generator().manual_seed(4)).float()   # integer-valued: every sum is exact
@@ -79,23 +48,23 @@ def test_maxpool_bitwise(k, s, p, shape, kind):
     xg = x.detach().to(DEV).requires_grad_()
     y, idx = ops.max_pool2d(xg, k, s, p, return_indices=True)
     assert y.shape == y_ref.shape
-    assert torch.equal(bits(y), bits(y_ref))
+    assert torch.equal(int_bits(y), int_bits(y_ref))
     assert torch.equal(idx.cpu().long(), i_ref)
     gx, = torch.autograd.grad(y, xg, g.to(DEV), retain_graph=True)
-    assert torch.equal(bits(gx), bits(gx_ref))
+    assert torch.equal(int_bits(gx), int_bits(gx_ref))
     gx2, = torch.autograd.grad(y, xg, g.to(DEV))                      # (no deterministic mode: the backward is a gather)
-    assert torch.equal(bits(gx), bits(gx2))
+    assert torch.equal(int_bits(gx), int_bits(gx2))
 
 
 def test_maxpool_backward_reproducible_on_real_gradients():
-    ops = _ops()
+    ops = support.ops()
     assert not ops.deterministic()
     x = _pool_input('ties', (2, 16, 64, 260), seed=5).to(DEV).requires_grad_()
     g = rnd(2, 16, 31, 129, seed=6).to(DEV)
     y = ops.max_pool2d(x, 3, 2, 0)
     a, = torch.autograd.grad(y, x, g, retain_graph=True)
     b, = torch.autograd.grad(y, x, g)
-    assert torch.equal(bits(a), bits(b))
+    assert torch.equal(int_bits(a), int_bits(b))
     xc = x.detach().cpu().requires_grad_()
     ref, = torch.autograd.grad(F.max_pool2d(xc, 3, 2, 0), xc, g.cpu())
     close_elem(a, ref, 'pool backward')
@@ -103,7 +72,7 @@ def test_maxpool_backward_reproducible_on_real_gradients():
 
 def test_maxpool_refuses_unsupported_windows():
     from dualpixelface_amd._lib import DpfError
-    ops = _ops()
+    ops = support.ops()
     x = rnd(1, 1, 16, 16).to(DEV)
     for k, s, p in ((9, 1, 0), (3, 3, 0), (3, 1, 2)):
         with pytest.raises(DpfError):
@@ -114,7 +83,7 @@ def test_maxpool_refuses_unsupported_windows():
 @pytest.mark.parametrize('C', [11, 16, 128])
 @pytest.mark.parametrize('k,pad', [(3, 0), (3, 1), (3, 2), (3, 3), (1, 0), (1, 1)])
 def test_depthwise_general(k, pad, C):
-    ops = _ops()
+    ops = support.ops()
     x = rnd(2, C, 9, 14, seed=8).requires_grad_()
     w = rnd(C, 1, k, k, seed=9).requires_grad_()
     y_ref = F.conv2d(x, w, None, 1, pad, 1, C)
@@ -129,17 +98,17 @@ def test_depthwise_general(k, pad, C):
     with ops.deterministic_mode():
         a = torch.autograd.grad(ops.depthwise_conv2d(xg, wg, pad), wg, go.to(DEV))[0]
         b = torch.autograd.grad(ops.depthwise_conv2d(xg, wg, pad), wg, go.to(DEV))[0]
-        assert torch.equal(bits(a), bits(b))
+        assert torch.equal(int_bits(a), int_bits(b))
         close(a, gw_r, 1e-4, 'dw wgrad (deterministic)')
     if (k, pad) == (3, 1):                 # the existing call keeps its kernels: the same bits through either entry
         y3 = ops.depthwise_conv3x3(xg, wg)
-        assert torch.equal(bits(y), bits(y3))
+        assert torch.equal(int_bits(y), int_bits(y3))
         gx3, _ = torch.autograd.grad(y3, (xg, wg), go.to(DEV))
-        assert torch.equal(bits(gx), bits(gx3))
+        assert torch.equal(int_bits(gx), int_bits(gx3))
 
 
 def test_depthwise_wide_rows():
-    ops = _ops()
+    ops = support.ops()
     x = rnd(1, 16, 6, 301, seed=18).requires_grad_()
     w = rnd(16, 1, 3, 3, seed=19).requires_grad_()
     y_ref = F.conv2d(x, w, None, 1, 3, 1, 16)
@@ -165,7 +134,7 @@ WIDE_IDS = ['stem', 'head5', 'head4', 'head3', 'head2', 'head1', 'k6x6', 'k5x7']
 @pytest.mark.parametrize('hw', [(20, 28), (33, 71)])
 @pytest.mark.parametrize('case', WIDE, ids=WIDE_IDS)
 def test_wide_conv(case, hw, bias, path):
-    ops = _ops()
+    ops = support.ops()
     C, K, (kh, kw), s, p = case
     x = rnd(2, C, hw[0], hw[1], seed=30).requires_grad_()
     w = rnd(K, C, kh, kw, seed=31, scale=(2.0 / (C * kh * kw)) ** 0.5).requires_grad_()
@@ -182,7 +151,7 @@ def test_wide_conv(case, hw, bias, path):
         got = torch.autograd.grad(y, (xg, wg) + ((bg,) if bias else ()), go.to(DEV))
         st = {}
         y_st = ops.conv2d(xg, wg, bg, s, p, stats=st)               # a BatchNorm's statistics request is declined, not mishandled
-        assert not st and torch.equal(bits(y_st), bits(y))
+        assert not st and torch.equal(int_bits(y_st), int_bits(y))
         with ops.deterministic_mode():
             a = torch.autograd.grad(ops.conv2d(xg, wg, bg, s, p), wg, go.to(DEV))[0]
             c = torch.autograd.grad(ops.conv2d(xg, wg, bg, s, p), wg, go.to(DEV))[0]
@@ -193,12 +162,12 @@ def test_wide_conv(case, hw, bias, path):
     close(got[1], refs[1], 2e-4, 'wide wgrad')
     if bias:
         close(got[2], refs[2], 1e-4, 'wide bias grad')
-    assert torch.equal(bits(a), bits(c))
+    assert torch.equal(int_bits(a), int_bits(c))
     close(a, refs[1], 2e-4, 'wide wgrad (deterministic)')
 
 
 def test_wide_conv_same_bits_on_every_matrix_path():
-    ops = _ops()
+    ops = support.ops()
     x, w = rnd(1, 8, 24, 40, seed=34).to(DEV), rnd(1, 8, 7, 7, seed=35).to(DEV)
     prev = ops.f32_matrix_path()
     try:
@@ -208,14 +177,14 @@ def test_wide_conv_same_bits_on_every_matrix_path():
             outs.append(ops.conv2d(x, w, None, 1, 1))
     finally:
         ops.set_f32_matrix_path(prev)
-    assert torch.equal(bits(outs[0]), bits(outs[1])) and torch.equal(bits(outs[0]), bits(outs[2]))
+    assert torch.equal(int_bits(outs[0]), int_bits(outs[1])) and torch.equal(int_bits(outs[0]), int_bits(outs[2]))
 
 
 # ------------------------------------------------------------------------------------------------ transposed 2-D conv, padded 1x1
 @pytest.mark.parametrize('hw', [(6, 8), (9, 13)])
 @pytest.mark.parametrize('cin,cout,pad', [(128, 32, 1), (128, 16, 2), (64, 16, 4), (32, 8, 4)])
 def test_conv_transpose2d(cin, cout, pad, hw):
-    ops = _ops()
+    ops = support.ops()
     x = rnd(2, cin, hw[0], hw[1], seed=40).requires_grad_()
     w = rnd(cin, cout, 4, 4, seed=41, scale=(2.0 / (cin * 4)) ** 0.5).requires_grad_()
     y_ref = F.conv_transpose2d(x, w, None, 2, pad)
@@ -233,7 +202,7 @@ def test_conv_transpose2d(cin, cout, pad, hw):
 @pytest.mark.parametrize('hw', [(8, 12), (7, 10)])
 @pytest.mark.parametrize('cin,cout,pad', [(16, 32, 1), (32, 128, 1), (32, 64, 2), (14, 11, 1)])
 def test_padded_pointwise_conv(cin, cout, pad, hw):
-    ops = _ops()
+    ops = support.ops()
     x = rnd(2, cin, hw[0], hw[1], seed=50).requires_grad_()
     w = rnd(cout, cin, 1, 1, seed=51, scale=(2.0 / cin) ** 0.5).requires_grad_()
     y_ref = F.conv2d(x, w, None, 1, pad)
@@ -251,7 +220,7 @@ def test_padded_pointwise_conv(cin, cout, pad, hw):
 # ------------------------------------------------------------------------------------------------ loss heads
 @pytest.mark.parametrize('n', [5, 8])
 def test_smooth_l1_many_heads(n):
-    ops = _ops()
+    ops = support.ops()
     wts = [1.0, 0.75294, 0.18824, 0.047059, 0.011765, 0.5, 0.25, 0.125][:n]
     pd = (rnd(2, n, 24, 36, seed=60) * 2).requires_grad_()
     disp = rnd(2, 24, 36, seed=61)
@@ -270,7 +239,7 @@ def test_smooth_l1_many_heads(n):
 
 def test_more_than_eight_heads_is_an_error():
     from dualpixelface_amd._lib import DpfError
-    ops = _ops()
+    ops = support.ops()
     with pytest.raises(DpfError):
         ops.stereo_losses(torch.zeros(1, 9, 8, 8, device=DEV), None, torch.zeros(1, 8, 8, device=DEV), None, torch.ones(1, 8, 8, device=DEV),
                           [1.0] * 9, 1.0, 0.0)
@@ -280,7 +249,7 @@ def test_more_than_eight_heads_is_an_error():
 def test_up_to_four_heads_keep_their_bits(mode, golden_dir):
     """tests/golden/loss.npz through the eight-head build: the fixture's values at the fixture's bound (the per-head sums are formed
     and added in the same order as before), and the same bits on a second run in deterministic mode."""
-    ops = _ops()
+    ops = support.ops()
     g = np.load(golden_dir + '/loss.npz')
     t = lambda k: torch.from_numpy(g[mode + '_' + k]).to(DEV)
     with ops.deterministic_mode():
@@ -288,4 +257,4 @@ def test_up_to_four_heads_keep_their_bits(mode, golden_dir):
         again = ops.stereo_losses(t('pred_depth'), t('pred_normal')[:, 0], t('disp'), t('normal'), t('mask'), [1.0, 0.7, 0.5], 1.0, 1.0)
     for i, k in enumerate(('smoothL1_loss', 'cosine_loss', 'final_loss')):
         close(out[i], torch.from_numpy(g[mode + '_' + k]), 1e-5, k)
-    assert torch.equal(bits(out), bits(again))
+    assert torch.equal(int_bits(out), int_bits(again))

@@ -13,32 +13,18 @@ import numpy as np
 import pytest
 import torch
 
+from tests import support
+from tests.support import DEV, close
+
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
 
 
 def build_model(training=True, **model_overrides):
-    from dualpixelface_amd import load_option
-    from dualpixelface_amd.plugin import STEREODPNET
-    from dualpixelface_amd.recipe import fill_by_recipe
-    model = STEREODPNET(load_option(**model_overrides))
-    fill_by_recipe(model)
-    model.to(DEV)
-    model.train(training)
-    return model
+    return support.build('STEREODPNET', support.option(**model_overrides), training)
 
 
 def load_batch(g):
     return {k[3:]: torch.from_numpy(g[k]).to(DEV) for k in g.files if k.startswith('in_')}
-
-
-def close(a, b, tol, name, atol=None):
-    a = a.detach().cpu().double()
-    b = torch.as_tensor(b).double()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    err = (a - b).abs().max().item()
-    lim = atol if atol is not None else tol * max(b.abs().max().item(), 1e-6)
-    assert err <= lim, '%s: max err %.3e > %.3e' % (name, err, lim)
 
 
 def test_train_forward_stages_and_losses(golden_dir):
@@ -1042,7 +1028,7 @@ def test_graph_state_keeps_the_workspaces_it_was_captured_with_alive():
         assert not dead, 'freed while a graph captured with them can still replay: %s' % dead
 
 
-def _assert_twins_equal(a, b, ra, rb, what):
+def _assert_adam_twins_equal(a, b, ra, rb, what):
     """Graph-mode model `a` and eager twin `b` after the same call: results, parameters, Adam state and every state_dict tensor, bitwise."""
     assert set(ra) == set(rb), (what, sorted(ra), sorted(rb))
     for k, v in rb.items():
@@ -1096,7 +1082,7 @@ def test_graph_replays_across_shape_changes_equal_an_eager_twin():
                         r.update(m(_dev(batch)))
                     m.train()
             torch.cuda.synchronize()
-            _assert_twins_equal(a, b, ra, rb, what)
+            _assert_adam_twins_equal(a, b, ra, rb, what)
             if i == 3:
                 assert a._graph_state['graph'] is not None
                 refs = _workspace_refs(a)

@@ -17,36 +17,14 @@ import numpy as np
 import pytest
 import torch
 
+from tests import support
+from tests.support import DEV
+
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STATES = {'adam': ('m', 'v'), 'sgd': ('buf',), 'rmsprop': ('sq',)}
 STATES_TORCH = {'adam': ('exp_avg', 'exp_avg_sq'), 'sgd': ('momentum_buffer',), 'rmsprop': ('square_avg',)}
 LR = 1e-3
-
-
-def _option(optim, name=None, **kw):
-    from dualpixelface_amd import load_option
-    opt = load_option(name) if name else load_option()
-    opt.optim = optim
-    for k, v in kw.items():
-        setattr(opt, k, v)
-    return opt
-
-
-def within_bound(got, ref, what, p_before=None):
-    """Every element of `got` inside the bound of the module docstring around the fp64 `ref`; prints the worst excess (<= 0 passes)."""
-    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    rms = ref.pow(2).mean().sqrt().item()
-    lim = 1e-4 * ref.abs() + 1e-5 * rms
-    if p_before is not None:
-        lim = lim + 2.0 ** -23 * p_before.detach().cpu().double().abs()
-    excess = (got - ref).abs() - lim
-    worst = excess.max().item()
-    print('%s: worst excess %.3e (rms %.3e, %d of %d outside)' % (what, worst, rms, int((excess > 0).sum()), excess.numel()))
-    assert worst <= 0, '%s: %d of %d elements outside the bound (worst excess %.3e, rms %.3e)' % (
-        what, int((excess > 0).sum()), excess.numel(), worst, rms)
 
 
 def one_ulp(norm32, norm64, what):
@@ -64,7 +42,7 @@ class Reference(object):
         from dualpixelface_amd.selectors import optimizer_selector
         self.optim = optim
         self.params = {k: torch.nn.Parameter(torch.zeros(shape, dtype=torch.float64)) for k, shape in shapes.items()}
-        self.opt = optimizer_selector(list(self.params.values()), _option(optim, init_lr=lr))
+        self.opt = optimizer_selector(list(self.params.values()), support.option_set(optim=optim, init_lr=lr))
 
     def step(self, before, grads, clip, lr=None):
         """before: {name: fp32 tensor}; grads: {name: fp64 tensor or None (= no gradient)}; clip: max norm, 0 = none
@@ -87,7 +65,7 @@ class Reference(object):
         return st[which] if which in st else torch.zeros_like(self.params[name])
 
 
-def _gradient(n, seed):
+def _gradient_zeros_from_3(n, seed):
     """magnitudes over six decades, both signs, every 7th element exactly 0"""
     g = torch.Generator().manual_seed(seed)
     mag = 10.0 ** (-6.0 * torch.rand(n, generator=g))
@@ -133,7 +111,7 @@ def _hyper(optim):
     return [float(x) for x in ops.adam_hyper(1, LR)] if optim == 'adam' else [LR, 0.0]
 
 
-def _run(optim, n, off, grads, p0, clip, gscale, apply=1.0):
+def _run_fold_finish_step(optim, n, off, grads, p0, clip, gscale, apply=1.0):
     """Three folds into an accumulation arena (the third with the sums in its pass), finish, the optimiser behind the record: every arena
     `off` floats into its allocation -> (acc, ctl, p, states) on the CPU."""
     from dualpixelface_amd import ops
@@ -162,20 +140,20 @@ def _same(a, b):
 @pytest.mark.parametrize('optim', ['adam', 'sgd', 'rmsprop'])
 def test_kernels_against_torch(optim, n):
     from dualpixelface_amd import ops
-    grads = [_gradient(n, 300 + k) for k in range(3)]
+    grads = [_gradient_zeros_from_3(n, 300 + k) for k in range(3)]
     p0 = torch.randn(n, generator=torch.Generator().manual_seed(7))
     total = (grads[0] + grads[1]) + grads[2]               # fp32, left to right
     norm64 = float(total.double().pow(2).sum().sqrt())
     assert norm64 > 0
     lo, hi = 0.3 * norm64, 10.0 * norm64                   # below 0.5 * norm: clipping is active at gscale 1 and 0.5
     for gscale in (1.0, 0.5):
-        base = _run(optim, n, 0, grads, p0, lo, gscale)
+        base = _run_fold_finish_step(optim, n, 0, grads, p0, lo, gscale)
         acc, ctl, p, states = base
         what = '%s n %d gscale %g' % (optim, n, gscale)
         # the fold: bitwise the fp32 sum; aligned, offset and repeated runs: the same bits everywhere
         assert torch.equal(acc.view(torch.int32), total.view(torch.int32)), what
-        assert _same(base, _run(optim, n, 0, grads, p0, lo, gscale)), what + ': two runs differ'
-        assert _same(base, _run(optim, n, 1, grads, p0, lo, gscale)), what + ': aligned and offset arenas differ'
+        assert _same(base, _run_fold_finish_step(optim, n, 0, grads, p0, lo, gscale)), what + ': two runs differ'
+        assert _same(base, _run_fold_finish_step(optim, n, 1, grads, p0, lo, gscale)), what + ': aligned and offset arenas differ'
         # the norm, the multiplier, the clipped step
         one_ulp(float(ctl[ops.GRAD_CTL_NORM]), gscale * norm64, what + ' grad_norm')
         ref = Reference(optim, {'p': (n,)}, LR)
@@ -183,11 +161,11 @@ def test_kernels_against_torch(optim, n):
         assert abs(measured - gscale * norm64) <= 1e-12 * norm64 and lo < measured
         coef = lo / (gscale * norm64 + 1e-6)
         assert abs(float(ctl[ops.GRAD_CTL_GMUL]) - gscale * coef) <= 2.0 ** -23 * gscale * coef, what
-        within_bound(p.double() - p0.double(), d64['p'], what + ' clipped update', p_before=p0)
+        support.within_bound(p.double() - p0.double(), d64['p'], what + ' clipped update', p_before=p0)
         for s, name in zip(states, STATES_TORCH[optim]):
-            within_bound(s, ref.state('p', name), what + ' state ' + name)
+            support.within_bound(s, ref.state('p', name), what + ' state ' + name)
     # c above the norm: coef is exactly 1 and the step is bitwise the unclipped entry point's on the same gradient
-    acc, ctl, p, states = _run(optim, n, 0, grads, p0, hi, 0.5)
+    acc, ctl, p, states = _run_fold_finish_step(optim, n, 0, grads, p0, hi, 0.5)
     assert float(ctl[ops.GRAD_CTL_GMUL]) == 0.5
     one_ulp(float(ctl[ops.GRAD_CTL_NORM]), 0.5 * norm64, '%s n %d unclipped grad_norm' % (optim, n))
     pp, gg, ss = p0.clone().to(DEV), total.to(DEV), [torch.zeros(n, device=DEV) for _ in STATES[optim]]
@@ -196,11 +174,11 @@ def test_kernels_against_torch(optim, n):
     assert torch.equal(p, pp.cpu()) and all(torch.equal(a, b.cpu()) for a, b in zip(states, ss)), (optim, n)
     assert not torch.equal(p, p0)
     # clipping off, tracking on: the same step, the norm still reported
-    acc0, ctl0, p_0, states0 = _run(optim, n, 0, grads, p0, 0.0, 0.5)
+    acc0, ctl0, p_0, states0 = _run_fold_finish_step(optim, n, 0, grads, p0, 0.0, 0.5)
     assert torch.equal(p_0, p) and torch.equal(ctl0[4:6], ctl[4:6])
     # apply = 0: the fold still happens, nothing else changes by a bit -- for aligned and offset arenas
     for off in (0, 1):
-        acc, ctl, p, states = _run(optim, n, off, grads, p0, lo, 1.0, apply=0.0)
+        acc, ctl, p, states = _run_fold_finish_step(optim, n, off, grads, p0, lo, 1.0, apply=0.0)
         assert torch.equal(acc.view(torch.int32), total.view(torch.int32))
         assert torch.equal(p.view(torch.int32), p0.view(torch.int32)) and all(int((s != 0).sum()) == 0 and not torch.signbit(s).any() for s in states)
         assert ctl[4:6].tolist() == [-7.0, -7.0]
@@ -208,7 +186,7 @@ def test_kernels_against_torch(optim, n):
     bad = [g.clone() for g in grads]
     bad[1][n // 2] = float('inf')
     for off in (0, 1):
-        _, ctl, _, _ = _run(optim, n, off, bad, p0, lo, 1.0)
+        _, ctl, _, _ = _run_fold_finish_step(optim, n, off, bad, p0, lo, 1.0)
         want = torch.linalg.vector_norm(((bad[0] + bad[1]) + bad[2]).double(), 2)
         assert not torch.isfinite(want) and not np.isfinite(float(ctl[ops.GRAD_CTL_NORM]))
         assert float(ctl[ops.GRAD_CTL_NORM]) == float(want) or (np.isnan(float(ctl[ops.GRAD_CTL_NORM])) and torch.isnan(want))
@@ -216,7 +194,7 @@ def test_kernels_against_torch(optim, n):
     if optim == 'rmsprop':
         zeros = [torch.zeros(n)] * 3
         for off in (0, 1):
-            acc, ctl, p, states = _run(optim, n, off, zeros, p0, 1.0, 1.0)
+            acc, ctl, p, states = _run_fold_finish_step(optim, n, off, zeros, p0, 1.0, 1.0)
             assert float(ctl[ops.GRAD_CTL_NORM]) == 0.0 and float(ctl[ops.GRAD_CTL_GMUL]) == 1.0
             assert torch.equal(p.view(torch.int32), p0.view(torch.int32)) and int((states[0] != 0).sum()) == 0
 
@@ -228,7 +206,7 @@ def test_stand_alone_sums_equal_the_fused_pass_and_refusals():
     from dualpixelface_amd import ops
     from dualpixelface_amd._lib import DpfError, lib
     n = 256 * 1024 + 5
-    g = _gradient(n, 11)
+    g = _gradient_zeros_from_3(n, 11)
     want = float(g.double().pow(2).sum().sqrt())
     got = []
     for off in (0, 1):
@@ -274,21 +252,9 @@ def test_stand_alone_sums_equal_the_fused_pass_and_refusals():
 
 
 # ------------------------------------------------------------------------------------------------------------------ whole steps
-def _plugin(optim, cls='STEREODPNET', config=None, **kw):
-    from dualpixelface_amd import plugin
-    from dualpixelface_amd.recipe import fill_by_recipe
-    model = getattr(plugin, cls)(_option(optim, config, **kw))
-    fill_by_recipe(model)
-    return model.to(DEV).train()
-
-
 def _batch(seed, B=2, H=32, W=48):
     from dualpixelface_amd.recipe import synthetic_batch
     return {k: v.to(DEV) for k, v in synthetic_batch(B, H, W, seed=seed, mask_mode='bern').items()}
-
-
-def _named(model, flat):
-    return {name: flat[off:off + numel].view(shape).detach().cpu().clone() for name, off, numel, shape in model._layout}
 
 
 def test_eager_groups_against_a_twin_by_hand():
@@ -299,8 +265,8 @@ def test_eager_groups_against_a_twin_by_hand():
     from dualpixelface_amd import ops
     N, lr = 3, 1e-4
     with ops.deterministic_mode():
-        model = _plugin('adam', step_graph=False, accumulate_grad_batches=N, gradient_clip_val=1.0)
-        twin = _plugin('adam', step_graph=False)
+        model = support.plugin('adam', step_graph=False, accumulate_grad_batches=N, gradient_clip_val=1.0)
+        twin = support.plugin('adam', step_graph=False)
         layout = model._layout
         pd = dict(twin.named_parameters())
         ref = Reference('adam', {name: shape for name, _, _, shape in layout}, lr)
@@ -324,7 +290,7 @@ def test_eager_groups_against_a_twin_by_hand():
                 model.option.gradient_clip_val = 0.5 * norm64          # below the measured norm of the first group
             clip = model.option.gradient_clip_val
             # the model: the same micro-batches through train_step
-            before = _named(model, model.flat_parameters())
+            before = support.named(model, model.flat_parameters())
             for k, b in enumerate(batches):
                 last = k == size - 1
                 res = model.train_step(b, lr=lr, last_in_epoch=(last and size < N))
@@ -336,17 +302,17 @@ def test_eager_groups_against_a_twin_by_hand():
             what = 'group %d' % gi
             assert torch.equal(model._adam['acc'].view(torch.int32), total.view(torch.int32)), what + ': accumulation arena'
             one_ulp(float(res['grad_norm']), norm64, what + ' grad_norm')
-            grads = _named(model, total.double() / N)
+            grads = support.named(model, total.double() / N)
             d64, measured = ref.step(before, {k: (g if k in had else None) for k, g in grads.items()}, clip)
             assert abs(measured - norm64) <= 1e-9 * norm64
             if gi == 0:
                 assert clip < measured
-            after = _named(model, model.flat_parameters())
-            m, v = _named(model, model._adam['m']), _named(model, model._adam['v'])
+            after = support.named(model, model.flat_parameters())
+            m, v = support.named(model, model._adam['m']), support.named(model, model._adam['v'])
             for name in before:
-                within_bound(after[name].double() - before[name].double(), d64[name], '%s %s' % (what, name), p_before=before[name])
-                within_bound(m[name], ref.state(name, 'exp_avg'), '%s m %s' % (what, name))
-                within_bound(v[name], ref.state(name, 'exp_avg_sq'), '%s v %s' % (what, name))
+                support.within_bound(after[name].double() - before[name].double(), d64[name], '%s %s' % (what, name), p_before=before[name])
+                support.within_bound(m[name], ref.state(name, 'exp_avg'), '%s m %s' % (what, name))
+                support.within_bound(v[name], ref.state(name, 'exp_avg_sq'), '%s v %s' % (what, name))
             assert model._adam['step'] == gi + 1
             with torch.no_grad():
                 twin.flat_parameters().copy_(model.flat_parameters())
@@ -366,7 +332,7 @@ def test_stereonet_sgd_parameter_without_gradient_is_left_alone_under_accumulati
     """The live-mask path under accumulation: StereoNet's unused conv2 weight (no gradient in any micro-step) keeps its bits over two
     groups of N = 2, weight decay included, and its momentum buffer stays zero; a used weight moves."""
     name, used = 'feature_extraction.residual_blocks.0.conv2.0.weight', 'feature_extraction.residual_blocks.0.conv1.0.0.weight'
-    model = _plugin('sgd', 'STEREONET', 'train_faceDP_stereonet', accumulate_grad_batches=2, gradient_clip_val=1.0)
+    model = support.plugin('sgd', 'STEREONET', 'train_faceDP_stereonet', accumulate_grad_batches=2, gradient_clip_val=1.0)
     pd = dict(model.named_parameters())
     before = {k: pd[k].detach().clone() for k in (name, used)}
     norms = []
@@ -391,8 +357,8 @@ def test_graph_replays_equal_an_eager_twin(optim):
     from dualpixelface_amd import ops
     clip = 0.05
     with ops.deterministic_mode():
-        a = _plugin(optim, step_graph=True, accumulate_grad_batches=2, gradient_clip_val=clip)
-        b = _plugin(optim, step_graph=False, accumulate_grad_batches=2, gradient_clip_val=clip)
+        a = support.plugin(optim, step_graph=True, accumulate_grad_batches=2, gradient_clip_val=clip)
+        b = support.plugin(optim, step_graph=False, accumulate_grad_batches=2, gradient_clip_val=clip)
         norms = []
         for i in range(12):
             batch, lr = _batch(60 + i), 1e-4 * 0.5 ** (i // 4)
@@ -429,7 +395,7 @@ def test_trainer_fit_groups_logs_and_checkpoints(tmp_path):
     from dualpixelface_amd.trainer import Trainer
     loader = synthetic_loader(14, 32, 48, batch_size=2, seed=3)
     kw = dict(epoch=1, scheduler='none', accumulate_grad_batches=3, gradient_clip_val=0.05)
-    a = _plugin('adam', **kw)
+    a = support.plugin('adam', **kw)
     ta = Trainer(a.option, str(tmp_path / 'a'), log_every=1, rank=0, world_size=1)
     ta.fit(a, loader, None)
     steps = [r for r in ta.history if 'step' in r]
@@ -437,7 +403,7 @@ def test_trainer_fit_groups_logs_and_checkpoints(tmp_path):
     assert all(np.isfinite(r['grad_norm']) and r['grad_norm'] > 0 and np.isfinite(r['final_loss']) for r in steps), steps
     ck = torch.load(ta.checkpoint_path(0), map_location='cpu', weights_only=False)
     assert set(ck['optimizer_states'][0]) == {'kind', 'step', 'm', 'v'} and ck['optimizer_states'][0]['step'] == 3
-    b = _plugin('adam', **kw)
+    b = support.plugin('adam', **kw)
     with torch.no_grad():
         b.flat_parameters().mul_(0.5)
     tb = Trainer(b.option, str(tmp_path / 'b'), rank=0, world_size=1)
@@ -446,7 +412,7 @@ def test_trainer_fit_groups_logs_and_checkpoints(tmp_path):
     sa, sb = a.state_dict(), b.state_dict()
     assert set(sa) == set(sb) and all(torch.equal(sa[k], sb[k]) for k in sa)
     assert torch.equal(a._adam['m'], b._adam['m']) and torch.equal(a._adam['v'], b._adam['v'])
-    c = _plugin('adam', epoch=1, scheduler='none')
+    c = support.plugin('adam', epoch=1, scheduler='none')
     tc = Trainer(c.option, str(tmp_path / 'c'), log_every=1, rank=0, world_size=1)
     tc.fit(c, loader, None)
     steps = [r for r in tc.history if 'step' in r]
@@ -476,7 +442,7 @@ def _accum_rank(rank, world, port, out_dir):
     torch.cuda.set_device(0)
     init_from_env(BACKEND)
     try:
-        model = _plugin('adam', accumulate_grad_batches=2, gradient_clip_val=0.05)
+        model = support.plugin('adam', accumulate_grad_batches=2, gradient_clip_val=0.05)
         if rank == 1:                                      # broadcast must repair this
             with torch.no_grad():
                 model.flat_parameters().mul_(1.5)
@@ -538,7 +504,7 @@ def _nccl_one_rank(port, out_dir):
     try:
         with ops.deterministic_mode():
             kw = dict(step_graph=False, accumulate_grad_batches=2, gradient_clip_val=0.05)
-            model, twin = _plugin('adam', **kw), _plugin('adam', **kw)
+            model, twin = support.plugin('adam', **kw), support.plugin('adam', **kw)
             reducer = make_reducer(model, force_collectives=True)
             assert reducer.collectives and reducer.world_size == 1
             calls, norms, same = [], [], []

@@ -11,26 +11,18 @@ import torch
 import torch.nn.functional as F
 
 from tests import norm_act_cpu as na
+from tests import support
+from tests.support import DEV, rnd
 from tests.test_gpu_ops import _TwoRankExchange
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
 FWD, GRAD = 1e-5, 2e-4
 GRADS = ('dx', 'dw', 'db', 'dslope', 'dres', 'dres2')
 
 
-def _ops():
-    from dualpixelface_amd import ops
-    return ops
-
-
 def _gen(seed):
     return torch.Generator().manual_seed(seed)
-
-
-def rnd(*shape, seed):
-    return torch.randn(*shape, generator=_gen(seed))
 
 
 def _params(C, seed):
@@ -81,13 +73,13 @@ def _reference_off_the_kink(t, mode, act, slope_const=0.0):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(N, C, S, mode, act, wb=True, res=False, res2=False):
+def _norm_act_case(N, C, S, mode, act, wb=True, res=False, res2=False):
     """(operands, fp64 reference) of one case: built once, shared by the default-mode and the deterministic-mode run, never modified."""
     t = _inputs(N, C, S, 1000 * mode + 10 * act + S % 97, wb, res, res2, act == na.ACT_PRELU)
     return t, _reference_off_the_kink(t, mode, act, 0.1)
 
 
-def _run(ops, t, mode, act, slope_const=0.0, want=('x', 'w', 'b', 'slope', 'res', 'res2'), exchange=None, x=None, go=None, repeat=False):
+def _run_norm_act(ops, t, mode, act, slope_const=0.0, want=('x', 'w', 'b', 'slope', 'res', 'res2'), exchange=None, x=None, go=None, repeat=False):
     """ops.norm_act on the device copies of t; gradients for the operands named in `want` that exist.  -> dict like the reference's;
     repeat: a second backward of the same graph, under 'again'."""
     dev = {}
@@ -142,11 +134,11 @@ def test_row_chunks(mode, act, S, det):
     """N = 2, C = 5.  S = 4100: 16-byte path, last chunk of 4 elements; 4099: scalar path, last chunk of 3; 8192: exactly two chunks;
     12292: three full chunks and a tail.  Forward, running statistics and every gradient per channel; in deterministic mode a second
     backward returns the same bits."""
-    ops = _ops()
+    ops = support.ops()
     full = mode == 1
-    t, ref = _case(2, 5, S, mode, act, True, full, full)
+    t, ref = _norm_act_case(2, 5, S, mode, act, True, full, full)
     with ops.deterministic_mode(det):
-        got = _run(ops, t, mode, act, repeat=det)
+        got = _run_norm_act(ops, t, mode, act, repeat=det)
     expect = ('dx', 'dw', 'db') + (('dslope', 'dres', 'dres2') if full else ())
     _compare(got, ref, 'mode %d S %d' % (mode, S), expect=expect)
     if det:
@@ -165,9 +157,9 @@ def test_reduce_chunk_differs_from_apply_chunk(S):
     piece of 32).  S = 131076 still gives 4096 (the integer division S * rows / 4096 yields 4096, not 4097): 32 full pieces and one of 4,
     on rows 32 times as long as in test_row_chunks."""
     assert reduce_chunk(128, 131104) == 5120 and reduce_chunk(128, 131100) == 4096 and reduce_chunk(128, 131076) == 4096
-    ops = _ops()
-    t, ref = _case(4, 32, S, 1, na.ACT_RELU)
-    got = _run(ops, t, 1, na.ACT_RELU)
+    ops = support.ops()
+    t, ref = _norm_act_case(4, 32, S, 1, na.ACT_RELU)
+    got = _run_norm_act(ops, t, 1, na.ACT_RELU)
     _compare(got, ref, 'S %d' % S, expect=('dx', 'dw', 'db'))
 
 
@@ -177,7 +169,7 @@ def test_reduce_chunk_differs_from_apply_chunk(S):
 def test_norm_act_concat_long_rows(S, det):
     """norm_act_concat with branch widths (8, 5, 16), training and eval, against torch.cat of the per-branch reference: the slice base
     ((n * Ctot + c0 + c) - row) * S of the forward's y and the backward's dy, on rows of two chunks."""
-    ops = _ops()
+    ops = support.ops()
     N, Cs = 2, (8, 5, 16)
     for mode in (1, 2):
         go = rnd(N, sum(Cs), S, seed=77) + 0.5
@@ -208,7 +200,7 @@ def test_sync_batchnorm_long_rows(det):
     """The two-rank emulation of test_gpu_ops.py::test_sync_batchnorm_matches_full_batch at S = 4100: rank 0 holds 2 samples, the emulated
     rank 1 three more.  Local moments, the merge, phase 1 (local reductions) and phase 2 (dx with the device-side global count) on rows of
     two chunks, against batch norm over all 5 samples; dw / db are this rank's partial sums."""
-    ops = _ops()
+    ops = support.ops()
     C, S = 6, 4100
     t = _inputs(5, C, S, 500)
     ref = _reference_off_the_kink(t, 1, na.ACT_RELU)
@@ -219,7 +211,7 @@ def test_sync_batchnorm_long_rows(det):
     dz = go * (xh * t['w'].double().view(1, C, 1) + t['b'].double().view(1, C, 1) > 0)
     ex = _TwoRankExchange(t['x'][2:].to(DEV), dz[2:].float().to(DEV), mean.reshape(C).float().to(DEV), invstd.reshape(C).float().to(DEV))
     with ops.deterministic_mode(det):
-        got = _run(ops, t, 1, na.ACT_RELU, exchange=ex, x=t['x'][:2].contiguous(), go=t['go'][:2].contiguous())
+        got = _run_norm_act(ops, t, 1, na.ACT_RELU, exchange=ex, x=t['x'][:2].contiguous(), go=t['go'][:2].contiguous())
     local = dict(ref, y=ref['y'][:2], dx=ref['dx'][:2], dw=(dz * xh)[:2].sum((0, 2)), db=dz[:2].sum((0, 2)))
     _compare(got, local, 'syncbn', expect=('dx', 'dw', 'db'))
 
@@ -244,11 +236,11 @@ SUBSETS = {
 def test_operand_and_output_subsets(name, det):
     """S = 4100, N = 2, C = 5: the <ACT, RES> specialisations and the wanted-output branches that the training test (both residuals, every
     gradient) never takes.  Exactly the wanted gradients come back, each within the bars."""
-    ops = _ops()
+    ops = support.ops()
     mode, act, wb, res, res2, want = SUBSETS[name]
-    t, ref = _case(2, 5, 4100, mode, act, wb, res, res2)
+    t, ref = _norm_act_case(2, 5, 4100, mode, act, wb, res, res2)
     with ops.deterministic_mode(det):
-        got = _run(ops, t, mode, act, 0.1, want=want, repeat=det)
+        got = _run_norm_act(ops, t, mode, act, 0.1, want=want, repeat=det)
     expect = [n for n, k in zip(GRADS, ('x', 'w', 'b', 'slope', 'res', 'res2')) if k in want]
     _compare(got, ref, name, expect=expect)
     if det:
@@ -259,7 +251,7 @@ def test_zero_slot_arena_wrap():
     """Mode 3 backwards with N = 4, C = 4096, S = 4: 3 * N * C = 49152 floats of the pre-zeroed 2^20-float arena per call, so 50 calls
     refill it twice after the first fill.  The reductions add into their slot without clearing it: every call's gradients must equal the
     first call's (whose dx is held to the reference), also right after a refill."""
-    ops = _ops()
+    ops = support.ops()
     N, C, S = 4, 4096, 4
     # every row is a permutation of (-1.5, -0.5, 0.5, 1.5) * scale + offset: no row of four has a vanishing variance
     base = torch.tensor([-1.5, -0.5, 0.5, 1.5])
@@ -352,10 +344,10 @@ def test_hard_statistics_batch_norm(det):
       dw, torch fp32 CPU:                                 2.1e-5 2.6e-3 1.2e-2 1.5e-2 0      | 7.1e-6 1.8e-6 3.2e-7 7.9e-5 | 3.2e-6
       running_mean, running_var, db now, both modes:      <= 1.6e-7 on every channel (torch: <= 2.4e-7)
     On the offset channels the kernels and torch meet the same fp32 limit (the mean, and bias - mean * scale, rounded to fp32)."""
-    ops = _ops()
+    ops = support.ops()
     t, ref, bars = _hard_case()
     with ops.deterministic_mode(det):
-        got = _run(ops, t, 1, na.ACT_NONE, want=('x', 'w', 'b'), repeat=det)
+        got = _run_norm_act(ops, t, 1, na.ACT_NONE, want=('x', 'w', 'b'), repeat=det)
     _compare(got, ref, 'hard', bars=bars, expect=('dx', 'dw', 'db'))
     if det:
         _same_bits(got, 'hard')
@@ -370,13 +362,13 @@ def test_hard_statistics_instance_norm(det):
       y before, default 4.9e-6 1.4e-4 1.5e-5 1.7e-5, deterministic 2.1e-6 1.4e-4 2.4e-4 1.7e-5 (three of four over the bar)
       y now,    default 1.6e-7 6.2e-8 5.0e-8 7.0e-8, deterministic 8.7e-8 5.3e-9 5.0e-8 4.5e-8
       now, both modes: dx <= 3.1e-6, dw <= 8.2e-5, db <= 6.1e-8"""
-    ops = _ops()
+    ops = support.ops()
     t, _, _ = _hard_case()
     sl = slice(OUTLIERS[0], OUTLIERS[-1] + 1)
     sub = {k: None if v is None else (v[:, sl] if v.dim() == 3 else v[sl]).contiguous() for k, v in t.items()}
     ref = _reference(sub, 3, na.ACT_NONE)
     with ops.deterministic_mode(det):
-        got = _run(ops, sub, 3, na.ACT_NONE, want=('x', 'w', 'b'))
+        got = _run_norm_act(ops, sub, 3, na.ACT_NONE, want=('x', 'w', 'b'))
     _compare(got, ref, 'hard instance norm', expect=('dx', 'dw', 'db'))
 
 
@@ -387,7 +379,7 @@ def test_conv_epilogue_statistics_under_an_offset():
 
     Measured on an MI355X over the 35 channels: y err / scale <= 2.0e-5, at most 0.27 of the channel's bar (torch's fp32 error on that
     channel is 1.8e-5: values near 1e3 in fp32 limit both); running_mean <= 5.1e-8, running_var <= 4.7e-8."""
-    ops = _ops()
+    ops = support.ops()
     N, C, K, D, H, W, ks = 3, 12, 35, 1, 33, 68, (1, 3, 3)
     x = rnd(N, C, D, H, W, seed=70)
     w = rnd(K, C, *ks, seed=71) * 0.2

@@ -9,43 +9,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import support
+from tests.support import DEV, close, close_elem, rnd
+
 pytestmark = pytest.mark.gpu
-
-DEV = 'cuda'
-
-
-def _ops():
-    from dualpixelface_amd import ops
-    return ops
-
-
-def close(a, b, tol=1e-4, name=''):
-    a = a.detach().cpu().double()
-    b = b.detach().cpu().double()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    scale = max(b.abs().max().item(), 1e-6)
-    err = (a - b).abs().max().item()
-    assert err <= tol * scale, '%s: max err %.3e vs scale %.3e (rel %.3e)' % (name, err, scale, err / scale)
-
-
-def close_elem(a, b, name='', rtol=1e-4, atol=1e-5):
-    """Element-wise bound (rtol 1e-4 / atol 1e-5) for operators without a long reduction: every element has to satisfy
-    |a - b| <= atol * rms(b) + rtol * |b|  (rms(b) = 1 for unit-scale data, so small-magnitude elements are held to an absolute 1e-5 instead
-    of disappearing under the tensor's maximum as in close())."""
-    a = a.detach().cpu().double()
-    b = torch.as_tensor(b).detach().cpu().double()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    rms = max(b.pow(2).mean().sqrt().item(), 1e-30)
-    excess = (a - b).abs() - (atol * rms + rtol * b.abs())
-    worst = excess.max().item()
-    assert worst <= 0, '%s: %d of %d elements outside rtol %.0e / atol %.0e x rms %.3e (worst excess %.3e)' % (
-        name, int((excess > 0).sum()), excess.numel(), rtol, atol, rms, worst)
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
 
 CONV_CASES = [
     # N, C, D, H, W, K, k(3), stride(3), pad(3), dil(3)
@@ -92,7 +59,7 @@ CONV_CASES = [
 
 @pytest.mark.parametrize('case', CONV_CASES)
 def test_conv_forward_backward(case):
-    ops = _ops()
+    ops = support.ops()
     N, C, D, H, W, K, ks, st, pd, dl = case
     x = rnd(N, C, D, H, W, seed=1).requires_grad_()
     w = rnd(K, C, *ks, seed=2, scale=0.1).requires_grad_()
@@ -112,7 +79,7 @@ def test_conv_forward_backward(case):
 def test_conv_data_gradient_of_leading_channels_only():
     """conv3d(gi_channels=n): the data gradient is computed for the first n input channels only (the rest is zero) -- the constant XYZ
     channels of the ANM volume have no gradient consumer (normal_module.py:166)."""
-    ops = _ops()
+    ops = support.ops()
     x = rnd(2, 35, 3, 10, 24, seed=1)
     w = rnd(81, 35, 3, 3, 3, seed=2, scale=0.1)
     go = rnd(2, 81, 3, 10, 24, seed=3)
@@ -128,7 +95,7 @@ def test_conv_data_gradient_of_leading_channels_only():
 @pytest.mark.parametrize('shape', [(2, 64, 2, 4, 6, 64), (1, 64, 4, 8, 12, 32), (2, 64, 1, 3, 5, 32), (1, 64, 3, 5, 8, 32), (2, 35, 2, 6, 36, 64),
                                    (1, 32, 5, 9, 40, 96)])
 def test_conv_transpose3d(shape):
-    ops = _ops()
+    ops = support.ops()
     N, Ci, D, H, W, Co = shape
     x = rnd(N, Ci, D, H, W, seed=5).requires_grad_()
     w = rnd(Ci, Co, 3, 3, 3, seed=6, scale=0.1).requires_grad_()
@@ -144,7 +111,7 @@ def test_conv_transpose3d(shape):
 
 
 def test_depthwise():
-    ops = _ops()
+    ops = support.ops()
     x = rnd(2, 64, 9, 14, seed=8).requires_grad_()
     w = rnd(64, 1, 3, 3, seed=9).requires_grad_()
     y_ref = F.conv2d(x, w, None, 1, 1, 1, 64)
@@ -161,7 +128,7 @@ def test_depthwise():
 @pytest.mark.parametrize('act', ['none', 'relu', 'prelu'])
 @pytest.mark.parametrize('shape', [(2, 32, 7, 9), (3, 64, 4, 6, 10)])
 def test_batchnorm_train(act, shape):
-    ops = _ops()
+    ops = support.ops()
     x = (rnd(*shape, seed=11) * 2 + 0.7).requires_grad_()
     C = shape[1]
     w = (torch.rand(C, generator=torch.Generator().manual_seed(12)) + 0.5).requires_grad_()
@@ -220,7 +187,7 @@ class _TwoRankExchange(object):
 def test_sync_batchnorm_matches_full_batch(shape):
     """rank 0 holds the first 2 samples, the emulated rank 1 three more: outputs, running statistics and dx must equal batch norm
     over all 5 samples (torch.nn.SyncBatchNorm semantics); dw/db are this rank's partial sums (DDP averages them afterwards)."""
-    ops = _ops()
+    ops = support.ops()
     C = shape[1]
     full = (5,) + tuple(shape[1:])
     x = (rnd(*full, seed=21) * 1.5 - 0.3).requires_grad_()
@@ -252,7 +219,7 @@ def test_sync_batchnorm_matches_full_batch(shape):
 
 
 def test_batchnorm_eval_and_instance_norm_and_leaky():
-    ops = _ops()
+    ops = support.ops()
     x = rnd(2, 32, 3, 6, 8, seed=20)
     w, b = torch.rand(32) + 0.5, rnd(32, seed=21)
     rm, rv = rnd(32, seed=22) * 0.2, torch.rand(32) + 0.5
@@ -284,7 +251,7 @@ def test_batchnorm_eval_and_instance_norm_and_leaky():
 
 @pytest.mark.parametrize('scale', [2, 4])
 def test_bilinear_and_nearest(scale):
-    ops = _ops()
+    ops = support.ops()
     x = rnd(2, 5, 7, 11, seed=30).requires_grad_()
     y_ref = F.interpolate(x, scale_factor=scale, mode='bilinear', align_corners=True)
     go = rnd(*y_ref.shape, seed=31)
@@ -320,7 +287,7 @@ def _device_tables(h, w, delta):
 def test_shift_triple(delta, shape):
     """nearest / bilinear / Fourier-phase triple incl. fractional shifts (row circulant on MFMA + Hilbert term) and its adjoint."""
     from oracle.stereodpnet import StereoDPNetOracle
-    ops = _ops()
+    ops = support.ops()
     fea = rnd(*shape, seed=40).requires_grad_()
     ref = torch.stack(StereoDPNetOracle.shift_triple(fea, delta), 2)
     go = rnd(*ref.shape, seed=41)
@@ -340,7 +307,7 @@ def test_shift_triple(delta, shape):
 def test_shift_triple_many_planes(delta):
     """B*C*3 > 65535 planes (the plane index rides in gridDim.y): the launchers slice; every plane still equals the oracle's."""
     from oracle.stereodpnet import StereoDPNetOracle
-    ops = _ops()
+    ops = support.ops()
     shape = (2, 33000, 4, 8)                               # 66 000 (b, c) planes, 198 000 output planes
     fea = rnd(*shape, seed=44)
     tables, phase = _device_tables(shape[2], shape[3], delta)
@@ -360,7 +327,7 @@ def test_shift_triple_many_planes(delta):
 
 def test_shift_triple_fractional_vs_reference_fixture(golden_dir):
     """Fractional shifts against outputs of the reference's own subpixel_shift (fresh module instance per delta)."""
-    ops = _ops()
+    ops = support.ops()
     g = np.load(golden_dir + '/shift_fractional.npz')
     for ci in range(3):
         fea = torch.from_numpy(g['fea%d' % ci]).to(DEV)
@@ -373,7 +340,7 @@ def test_shift_triple_fractional_vs_reference_fixture(golden_dir):
 
 
 def test_cv_select():
-    ops = _ops()
+    ops = support.ops()
     B, C, h, w, L = 2, 8, 6, 10, 8
     ts = [rnd(B, C, 3, h, w, seed=50 + i).requires_grad_() for i in range(4)]
     ts[1] = torch.sigmoid(ts[1].detach()).requires_grad_()
@@ -393,7 +360,7 @@ def test_cv_select():
 
 
 def test_softargmin():
-    ops = _ops()
+    ops = support.ops()
     B, D, h, w = 2, 8, 6, 10
     logits = rnd(B, 1, D, h, w, seed=60, scale=2.0).requires_grad_()
     disp = [-4 + 0.5 * i for i in range(32)]
@@ -422,7 +389,7 @@ def test_softargmin():
                                  (1, 60, 24, 2, 6, 12), (1, 84, 16, 3, 5, 8, 2.0)])
 def test_deform_conv(cfg):
     from oracle import dcn3d
-    ops = _ops()
+    ops = support.ops()
     B, C, K, D, H, W = cfg[:6]
     x = rnd(B, C, D, H, W, seed=70)
     off = rnd(B, 81, D, H, W, seed=71, scale=cfg[6] if len(cfg) > 6 else 1.5)
@@ -448,7 +415,7 @@ def test_weight_gradient_f32_matrix_paths_agree(cfg):
     matrix pipe (dpf_set_f32_matrix_path).  Both are fp32 arithmetic: against an fp64 reference neither may be worse than 2 x the other,
     and each is within 1e-5 of the tensor scale."""
     from dualpixelface_amd._lib import lib
-    ops = _ops()
+    ops = support.ops()
     N, C, K, D, H, W, ks, stride, dil = cfg
     pad = tuple(((k - 1) * dil) // 2 if k > 1 else 0 for k in ks)
     dl = tuple(dil if k > 1 else 1 for k in ks)
@@ -501,7 +468,7 @@ def test_conv_f32_matrix_paths_agree(cfg):
     dropped lo x lo term is below 2^-32 of a product).  Both are fp32 arithmetic: against an fp64 reference neither may be worse than
     2 x the other, each is within 1e-5 of the tensor scale -- also on all-positive data, where a truncation bias would add up."""
     from dualpixelface_amd._lib import lib
-    ops = _ops()
+    ops = support.ops()
     N, C, K, D, H, W, ks, dil, transposed = cfg
     pad = tuple(((k - 1) * dil) // 2 if k > 1 else 0 for k in ks)
     dl = tuple(dil if k > 1 else 1 for k in ks)
@@ -543,7 +510,7 @@ def test_conv_f16_component_path_block_scaling(cfg):
     own scale) as with the fp32 instruction -- the scale follows the tile, not the tensor.  (c) zeros, and a single
     non-zero value in an otherwise zero tensor."""
     from dualpixelface_amd._lib import lib
-    ops = _ops()
+    ops = support.ops()
     N, C, K, D, H, W, ks, transposed = cfg
     pad = tuple((k - 1) // 2 for k in ks)
     one = (1, 1, 1)
@@ -634,7 +601,7 @@ def test_conv_f16_component_path_in_block_dynamic_range(cfg, layout):
     within 2 x the worst element of path 0.  Negative control: with the range guard
     switched off (block scaling without residual passes -- round 5's kernel) the banded layouts miss the bar by orders of magnitude."""
     from dualpixelface_amd._lib import lib
-    ops = _ops()
+    ops = support.ops()
     N, C, K, D, H, W, ks, dil, transposed = cfg
     pad = tuple(((k - 1) * dil) // 2 if k > 1 else 0 for k in ks)
     dl = tuple(dil if k > 1 else 1 for k in ks)
@@ -697,7 +664,7 @@ def test_conv_range_guard_is_run_to_run_bitwise_reproducible(cfg, layout):
     most chunks, ten launches each of forward and data gradient: the same bits every time, and the same bits as the launch checked against
     fp64 (max error within the fp32-instruction bar of test_conv_f16_component_path_in_block_dynamic_range)."""
     from dualpixelface_amd._lib import lib
-    ops = _ops()
+    ops = support.ops()
     N, C, K, D, H, W, ks, dil = cfg
     pad = tuple(((k - 1) * dil) // 2 if k > 1 else 0 for k in ks)
     dl = tuple(dil if k > 1 else 1 for k in ks)
@@ -734,7 +701,7 @@ def test_weight_gradient_f16_component_path_in_block_dynamic_range(cfg, layout, 
     2 x the worst element of the fp32 matrix instruction (path 0).  (Round 5's kernel -- one exponent per tile and operand -- misses the
     bar on the 'chan' layout by four orders of magnitude: profiles/r06_range_guard_before_after.txt.)"""
     from dualpixelface_amd._lib import lib
-    ops = _ops()
+    ops = support.ops()
     N, C, K, D, H, W, ks, dil = cfg
     pad = tuple(((k - 1) * dil) // 2 if k > 1 else 0 for k in ks)
     dl = tuple(dil if k > 1 else 1 for k in ks)
@@ -772,7 +739,7 @@ def test_weight_gradient_range_guard_is_bitwise_reproducible_in_deterministic_mo
     committed in a fixed order) ten launches on data whose channels sit at 1 .. 2^-34 and whose magnitudes also vary along W return the
     same bits."""
     from dualpixelface_amd._lib import lib
-    ops = _ops()
+    ops = support.ops()
     N, C, K, D, H, W, ks, dil = cfg
     pad = tuple(((k - 1) * dil) // 2 if k > 1 else 0 for k in ks)
     dl = tuple(dil if k > 1 else 1 for k in ks)
@@ -800,7 +767,7 @@ def test_deform_conv_backward_f16_component_path_in_block_dynamic_range(cfg):
     (|W|, |go|).  fp64 oracle; bar: the worst element within 2 x the worst element on the fp32 matrix instruction (path 0)."""
     from dualpixelface_amd._lib import lib
     from oracle import dcn3d
-    ops = _ops()
+    ops = support.ops()
     B, C, K, D, H, W = cfg
     x, off = rnd(B, C, D, H, W, seed=330), rnd(B, 81, D, H, W, seed=331, scale=0.7)
     wt, bs = rnd(K, C, 3, 3, 3, seed=332, scale=0.1), rnd(K, seed=333)
@@ -861,7 +828,7 @@ def test_deform_conv_integer_offsets_and_the_validity_rule(shape):
     sample outside the OPEN interval (-1, size) invalid -- no value and no coordinate derivative -- although its high corner would still
     sit inside the volume.  (The lean kernels read a zero-padded image, which alone would hand such a sample a derivative.)"""
     from oracle import dcn3d
-    ops = _ops()
+    ops = support.ops()
     B, C, K, D, H, W = shape
     x = rnd(B, C, D, H, W, seed=170)
     off = torch.randint(-2, 3, (B, 81, D, H, W), generator=torch.Generator().manual_seed(171)).float()
@@ -884,7 +851,7 @@ def test_deform_conv_collapsed_samples(gi):
     bound the packed fixed-point scatter assumes for its first pass -- it must measure that and repeat the pass (no wrap-around).  `gi`
     exercises grad_input for a channel prefix (odd counts split a packed channel pair)."""
     from oracle import dcn3d
-    ops = _ops()
+    ops = support.ops()
     B, C, K, D, H, W = 1, 20, 8, 4, 4, 64
     x = rnd(B, C, D, H, W, seed=75)
     zz, yy, xx = torch.meshgrid(torch.arange(D), torch.arange(H), torch.arange(W), indexing='ij')
@@ -916,7 +883,7 @@ def test_anm_volume_and_sigmoid_mean():
     from oracle import recipe_state
     from oracle.stereodpnet import StereoDPNetOracle
     from dualpixelface_amd.recipe import synthetic_batch
-    ops = _ops()
+    ops = support.ops()
     B, C, L, h, w = 2, 32, 8, 6, 10
     orc = StereoDPNetOracle({}, training=True)
     cost = rnd(B, C, L, h, w, seed=80).requires_grad_()
@@ -951,7 +918,7 @@ def test_anm_level_indices_full_size_ties_and_boundaries():
     index among the equal ones) is the stated behaviour (oracle topk_ties='cuda'), everywhere else the literal torch.topk call decides."""
     from oracle.stereodpnet import StereoDPNetOracle
     from dualpixelface_amd.recipe import synthetic_batch
-    ops = _ops()
+    ops = support.ops()
     B, C, L, h, w = 4, 4, 8, 256, 384
     orc = StereoDPNetOracle({}, training=True)
     cr = torch.tensor(orc.cfg.costrange, dtype=torch.float32)
@@ -987,7 +954,7 @@ def test_anm_level_indices_full_size_ties_and_boundaries():
 
 @pytest.mark.parametrize('mode', ['ones', 'bern'])
 def test_losses_against_reference_fixture(mode, golden_dir):
-    ops = _ops()
+    ops = support.ops()
     g = np.load(golden_dir + '/loss.npz')
     t = lambda k: torch.from_numpy(g[mode + '_' + k]).to(DEV)
     pd, pn = t('pred_depth').requires_grad_(), t('pred_normal').requires_grad_()
@@ -1019,7 +986,7 @@ def test_confidence_weighted_loss_against_reference_fixture(golden_dir):
 
 def test_adam_step():
     from oracle.stereodpnet import adam_step as adam_ref
-    ops = _ops()
+    ops = support.ops()
     n = 10007
     p, g = rnd(n, seed=90), rnd(n, seed=91, scale=0.01)
     pr, m, v = {'p': p.clone()}, {'p': torch.zeros(n)}, {'p': torch.zeros(n)}
@@ -1033,7 +1000,7 @@ def test_adam_step():
 
 
 def test_psm_volume_against_reference_fixture(golden_dir):
-    ops = _ops()
+    ops = support.ops()
     g = np.load(golden_dir + '/psmnet_volume.npz')
     ref, tar = torch.from_numpy(g['ref']).to(DEV), torch.from_numpy(g['tar']).to(DEV)
     costrange = [i * 0.5 - 1.0 for i in range(8)]
@@ -1049,7 +1016,7 @@ def test_psm_volume_full_size_bit_exact():
     device tensors as well: the concat volume must be BIT-EXACT (403 MB), the group-wise correlation channels and the backward element-wise
     close."""
     from oracle.psmnet_volume import psm_volume
-    ops = _ops()
+    ops = support.ops()
     g = torch.Generator().manual_seed(31)
     ref = torch.randn(2, 32, 256, 384, generator=g).to(DEV)
     tar = torch.randn(2, 32, 256, 384, generator=g).to(DEV)
@@ -1073,7 +1040,7 @@ def test_psm_volume_full_size_bit_exact():
 
 
 def test_layout_kernels():
-    ops = _ops()
+    ops = support.ops()
     a, b, c = rnd(2, 5, 3, 7, seed=100).requires_grad_(), rnd(2, 8, 3, 7, seed=101).requires_grad_(), rnd(2, 1, 3, 7, seed=102).requires_grad_()
     ref = torch.cat([a, b, c], 1)
     go = rnd(*ref.shape, seed=103)
@@ -1115,7 +1082,7 @@ BF16_CASES = [
 def test_conv2d_bf16_operands(case):
     """bf16-operand conv == fp32 conv of the bf16-rounded operands (products are exact in fp32; only the summation order
     differs): 1e-5 of the tensor scale.  The weight gradient runs on the fp32 kernel with unrounded operands."""
-    ops = _ops()
+    ops = support.ops()
     N, C, H, W, K, k, st, pd, dl = case
     x = rnd(N, C, H, W, seed=90).requires_grad_()
     w = rnd(K, C, k, k, seed=91, scale=0.1).requires_grad_()
@@ -1148,7 +1115,7 @@ def test_conv_operands_bf16(case):
     the tensor scale for forward / data gradient, 2e-4 for the weight gradient -- or, for the launches the bf16 kernels do not cover
     (8-channel stride-2 patches do not fit the LDS; > 128 output rows; the class-fused stride-2 data gradient), the exact fp32 result.
     The 3x3x3 stride-1 cases must take the bf16 kernels in all three directions."""
-    ops = _ops()
+    ops = support.ops()
     N, C, D, H, W, K, ks, st, pd, dl = case
     x = rnd(N, C, D, H, W, seed=1)
     w = rnd(K, C, *ks, seed=2, scale=0.1)
@@ -1191,7 +1158,7 @@ def test_avg_pool_and_resize_and_psm_volume_backward():
     """PSMNet-specific operators: AvgPool2d(k, k), bilinear resize to an arbitrary size (align_corners=True, incl. from 1x1), and the
     gradient of the integer-shift volume (concat and group-wise correlation) against autograd through the oracle."""
     from oracle.psmnet_volume import psm_volume
-    ops = _ops()
+    ops = support.ops()
     x = rnd(2, 8, 19, 33, seed=100).requires_grad_()
     for k in (8, 4, 16):
         y_ref = F.avg_pool2d(x, (k, k), (k, k))
@@ -1231,7 +1198,7 @@ def test_full_size_properties():
     """BASELINE-size tensors (4 x 32 x 8 x 256 x 384 aggregation conv, 4 x 35 x 4 x 256 x 384 deformable conv) through properties that
     need no CPU reference: linearity of the forward, the adjoint identities <conv(x), g> = <x, dgrad(g)> = <w, wgrad(x, g)> that tie the
     three conv kernels together, and the deformable conv's known answer (zero offsets == plain conv3d) plus its adjoints."""
-    ops = _ops()
+    ops = support.ops()
     gen = torch.Generator(device=DEV).manual_seed(5)
     r = lambda *s: torch.randn(*s, device=DEV, generator=gen)
     dot = lambda a, b: float((a.double() * b.double()).sum())
@@ -1294,7 +1261,7 @@ def test_full_size_properties_2d_head_norm_bf16():
     the prediction is their expectation, the gradient matches a central difference), BatchNorm forward / backward at the hourglass
     shape (4 x 32 x 8 x 256 x 384: zero mean, unit variance, sum dx = sum dx * xhat = 0 per channel), and the bf16-operand 3x3x3 kernel,
     which must equal the exact-fp32 kernel run on bf16-rounded operands (same accumulation type, only the summation order differs)."""
-    ops = _ops()
+    ops = support.ops()
     gen = torch.Generator(device=DEV).manual_seed(6)
     r = lambda *s: torch.randn(*s, device=DEV, generator=gen)
     dot = lambda a, b: float((a.double() * b.double()).sum())
@@ -1368,7 +1335,7 @@ def test_full_size_properties_2d_head_norm_bf16():
 def test_conv_epilogue_batchnorm_statistics(shape):
     """dpf_conv_forward_stats + dpf_bn_finalize_partials (BatchNorm statistics from the conv epilogue) against the separate
     statistics pass and against torch's batch_norm on the CPU; running statistics included; bitwise reproducible."""
-    ops = _ops()
+    ops = support.ops()
     N, C, K, D, H, W, ks, stride, has_bias = shape
     x = rnd(N, C, D, H, W, seed=70)
     w = rnd(K, C, *ks, seed=71) * 0.2
@@ -1404,7 +1371,7 @@ def test_conv_epilogue_batchnorm_statistics(shape):
 def test_resize_bilinear_half_pixel(shape):
     """F.interpolate(size, mode='bilinear', align_corners=False) (nnet/modules.py:110-120) and its adjoint, incl. 1x1 sources,
     downsampling and non-integer ratios."""
-    ops = _ops()
+    ops = support.ops()
     N, C, h, w, H, W = shape
     x = rnd(N, C, h, w, seed=80).requires_grad_()
     ref = F.interpolate(x, size=(H, W), mode='bilinear', align_corners=False)
@@ -1418,7 +1385,7 @@ def test_resize_bilinear_half_pixel(shape):
 
 
 def test_l2_normalize_and_xyz_volume():
-    ops = _ops()
+    ops = support.ops()
     x = rnd(2, 3, 9, 14, seed=82)
     x[0, :, 0, 0] = 0.0                                              # zero vector: eps branch
     x = x.requires_grad_()
@@ -1460,7 +1427,7 @@ def test_l2_normalize_and_xyz_volume():
 @pytest.mark.parametrize('dims', [(2, 8, 6, 10), (1, 8, 16, 40), (1, 5, 7, 9)])
 def test_softargmin_head_half_pixel(dims):
     """x4 trilinear (align_corners=False) + softmax + expectation (nnet/mainmodel.py:150-153, modules.py:196-217) and its gradient."""
-    ops = _ops()
+    ops = support.ops()
     B, D, h, w = dims
     k = rnd(B, 1, D, h, w, seed=90).requires_grad_()
     L = 4 * D
@@ -1480,7 +1447,7 @@ def test_softargmin_head_half_pixel(dims):
 
 def test_diff_volume():
     """StereoNet's difference volume (stereonet/mainmodel.py:97-112) and its adjoint, positive / zero / negative shifts."""
-    ops = _ops()
+    ops = support.ops()
     B, C, h, w = 2, 5, 9, 14
     shifts = [-2, -1, 0, 0, 1, 3]
     ref = rnd(B, C, h, w, seed=95).requires_grad_()
@@ -1509,7 +1476,7 @@ def test_diff_volume():
 def test_norm_act_concat_matches_separate_norm_and_cat():
     """BatchNorm branches written straight into their slice of the concatenation (y_channels / dy_channels of dpf_norm_act_*) against
     torch.cat([batch_norm(x_i)]) with autograd, training and eval, running statistics included."""
-    ops = _ops()
+    ops = support.ops()
     N, H, W = 2, 12, 20
     Cs = (8, 5, 16)
     xs = [rnd(N, C, H, W, seed=100 + i).requires_grad_() for i, C in enumerate(Cs)]
@@ -1538,7 +1505,7 @@ def test_norm_act_concat_matches_separate_norm_and_cat():
 def test_conv_bn_concat_node(training):
     """cat([batch_norm(conv2d(x, w_i, dilation d_i))]) as one autograd node (no cat copies, data gradients summed in the
     transposed-conv epilogue) against torch autograd."""
-    ops = _ops()
+    ops = support.ops()
     N, C, H, W = 2, 8, 20, 36
     dils = (1, 3, 5)
     x = rnd(N, C, H, W, seed=200).requires_grad_()

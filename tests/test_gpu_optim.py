@@ -19,35 +19,13 @@ import numpy as np
 import pytest
 import torch
 
+from tests import support
+from tests.support import DEV
+
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STATE = {'sgd': 'buf', 'rmsprop': 'sq'}
 STATE_TORCH = {'sgd': 'momentum_buffer', 'rmsprop': 'square_avg'}
-
-
-def _option(optim, name=None, **kw):
-    from dualpixelface_amd import load_option
-    opt = load_option(name) if name else load_option()
-    opt.optim = optim
-    for k, v in kw.items():
-        setattr(opt, k, v)
-    return opt
-
-
-def within_bound(got, ref, what, p_before=None):
-    """Every element of `got` inside the bound of the module docstring around the fp64 `ref`; prints the worst excess (<= 0 passes)."""
-    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    rms = ref.pow(2).mean().sqrt().item()
-    lim = 1e-4 * ref.abs() + 1e-5 * rms
-    if p_before is not None:
-        lim = lim + 2.0 ** -23 * p_before.detach().cpu().double().abs()
-    excess = (got - ref).abs() - lim
-    worst = excess.max().item()
-    print('%s: worst excess %.3e (rms %.3e, %d of %d outside)' % (what, worst, rms, int((excess > 0).sum()), excess.numel()))
-    assert worst <= 0, '%s: %d of %d elements outside the bound (worst excess %.3e, rms %.3e)' % (
-        what, int((excess > 0).sum()), excess.numel(), worst, rms)
 
 
 class Reference(object):
@@ -58,7 +36,7 @@ class Reference(object):
         from dualpixelface_amd.selectors import optimizer_selector
         self.optim = optim
         self.params = {k: torch.nn.Parameter(torch.zeros(shape, dtype=torch.float64)) for k, shape in shapes.items()}
-        self.opt = optimizer_selector(list(self.params.values()), _option(optim, init_lr=lr))
+        self.opt = optimizer_selector(list(self.params.values()), support.option_set(optim=optim, init_lr=lr))
 
     def step(self, before, grads, lr=None):
         """before: {name: fp32 tensor}; grads: {name: tensor or None (= the parameter had no gradient)} -> {name: delta in fp64}."""
@@ -78,7 +56,7 @@ class Reference(object):
         return st[STATE_TORCH[self.optim]] if STATE_TORCH[self.optim] in st else torch.zeros_like(self.params[name])
 
 
-def _gradient(n, seed):
+def _gradient_zeros_from_0(n, seed):
     """magnitudes over six decades, both signs, every 7th element exactly 0"""
     g = torch.Generator().manual_seed(seed)
     mag = 10.0 ** (-6.0 * torch.rand(n, generator=g))
@@ -113,7 +91,7 @@ def test_kernels_against_torch_optim(case, lr, gscale):
             live[lo:hi] = 0
     p0 = p.clone()
     for step in range(4):
-        g = _gradient(N, 100 + step)
+        g = _gradient_zeros_from_0(N, 100 + step)
         before = p.clone()
         if optim == 'sgd':
             ops.sgd_step(p, g.to(DEV), state, lr, gscale=gscale, live=live)
@@ -123,8 +101,8 @@ def test_kernels_against_torch_optim(case, lr, gscale):
         d64 = ref.step({seg: before[seg[0]:seg[1]] for seg in segs},
                        {seg: (None if seg in dead else g[seg[0]:seg[1]].double() * gscale) for seg in segs})
         what = '%s lr %g gscale %g step %d' % (case, lr, gscale, step)
-        within_bound(p.double() - before.double(), torch.cat([d64[seg] for seg in segs]), what + ' update', p_before=before)
-        within_bound(state, torch.cat([ref.state(seg) for seg in segs]), what + ' state')
+        support.within_bound(p.double() - before.double(), torch.cat([d64[seg] for seg in segs]), what + ' update', p_before=before)
+        support.within_bound(state, torch.cat([ref.state(seg) for seg in segs]), what + ' state')
     for lo, hi in dead:
         assert torch.equal(p[lo:hi], p0[lo:hi]) and int((state[lo:hi] != 0).sum()) == 0 and not torch.signbit(state[lo:hi]).any()
     assert not torch.equal(p[:1001], p0[:1001])
@@ -151,7 +129,7 @@ def test_device_lr_variant_and_unaligned_arenas_are_bitwise_the_same(optim):
                 live[lo:hi] = 0
         lr_dev = torch.full((1,), lr, dtype=torch.float32, device=DEV)
         for step in range(3):
-            g.copy_(_gradient(N, 200 + step))
+            g.copy_(_gradient_zeros_from_0(N, 200 + step))
             if optim == 'sgd':
                 if device_lr:
                     ops.sgd_step_lr(p, g, state, lr_dev, gscale=0.5, live=live)
@@ -171,14 +149,6 @@ def test_device_lr_variant_and_unaligned_arenas_are_bitwise_the_same(optim):
         assert torch.equal(got[0], base[0]) and torch.equal(got[1], base[1]), (optim, device_lr, offsets)
 
 
-def _plugin(optim, cls='STEREODPNET', config=None, **kw):
-    from dualpixelface_amd import plugin
-    from dualpixelface_amd.recipe import fill_by_recipe
-    model = getattr(plugin, cls)(_option(optim, config, **kw))
-    fill_by_recipe(model)
-    return model.to(DEV).train()
-
-
 def _without_gradient(model, batch):
     """Names of the parameters autograd leaves without a gradient on this batch -- asked of autograd itself, on a model of its own:
     every .grad cleared, one forward + backward, which .grad is still None."""
@@ -187,10 +157,6 @@ def _without_gradient(model, batch):
     model(batch)['final_loss'].backward()
     torch.cuda.synchronize()
     return {name for name, _, _, _ in model._layout if dict(model.named_parameters())[name].grad is None}
-
-
-def _named(model, flat):
-    return {name: flat[off:off + numel].view(shape).detach().cpu().clone() for name, off, numel, shape in model._layout}
 
 
 def _golden_batch(golden_dir):
@@ -204,24 +170,24 @@ def test_whole_eager_step_against_torch_optim(golden_dir, optim):
     torch.optim in fp64 from the same parameters (no gradient where autograd gave none): every parameter tensor's update must meet the
     bound, which isolates the optimiser from the network's own gradient noise."""
     batch = _golden_batch(golden_dir)
-    unused = _without_gradient(_plugin(optim, step_graph=False), batch)
-    model = _plugin(optim, step_graph=False)
+    unused = _without_gradient(support.plugin(optim, step_graph=False), batch)
+    model = support.plugin(optim, step_graph=False)
     lr = float(model.option.init_lr)
     ref = Reference(optim, {name: shape for name, _, _, shape in model._layout}, lr)
     for step in range(3):
-        before = _named(model, model.flat_parameters())
+        before = support.named(model, model.flat_parameters())
         res = model.train_step(batch)
         torch.cuda.synchronize()
         assert torch.isfinite(res['final_loss'])
-        grads = _named(model, model.flat_gradients(zero=False))
-        after = _named(model, model.flat_parameters())
+        grads = support.named(model, model.flat_gradients(zero=False))
+        after = support.named(model, model.flat_parameters())
         d64 = ref.step(before, {k: (None if k in unused else g) for k, g in grads.items()})
         for name in before:
             what = '%s step %d %s' % (optim, step, name)
-            within_bound(after[name].double() - before[name].double(), d64[name], what, p_before=before[name])
-        state = _named(model, model._optim[STATE[optim]])
+            support.within_bound(after[name].double() - before[name].double(), d64[name], what, p_before=before[name])
+        state = support.named(model, model._optim[STATE[optim]])
         for name in before:
-            within_bound(state[name], ref.state(name), '%s step %d state %s' % (optim, step, name))
+            support.within_bound(state[name], ref.state(name), '%s step %d state %s' % (optim, step, name))
     assert model._adam is None and model._optim['kind'] == optim
     assert not getattr(model, '_graph_states', None)
 
@@ -233,8 +199,8 @@ def test_stereonet_parameter_without_gradient_is_left_alone(optim):
     from dualpixelface_amd.recipe import synthetic_batch
     name, used = 'feature_extraction.residual_blocks.0.conv2.0.weight', 'feature_extraction.residual_blocks.0.conv1.0.0.weight'
     batch = {k: v.to(DEV) for k, v in synthetic_batch(2, 64, 96, seed=13).items()}
-    model = _plugin(optim, 'STEREONET', 'train_faceDP_stereonet')
-    assert name in _without_gradient(_plugin(optim, 'STEREONET', 'train_faceDP_stereonet'), batch)
+    model = support.plugin(optim, 'STEREONET', 'train_faceDP_stereonet')
+    assert name in _without_gradient(support.plugin(optim, 'STEREONET', 'train_faceDP_stereonet'), batch)
     pd = dict(model.named_parameters())
     before = {k: pd[k].detach().clone() for k in (name, used)}
     for _ in range(2):
@@ -248,7 +214,7 @@ def test_stereonet_parameter_without_gradient_is_left_alone(optim):
     assert model._adam is None
 
 
-def _assert_twins_equal(a, b, ra, rb, what, optim):
+def _assert_optim_twins_equal(a, b, ra, rb, what, optim):
     """Graph-mode model `a` and eager twin `b` after the same call: results, parameters, optimiser state and every state_dict tensor, bitwise."""
     assert set(ra) == set(rb), (what, sorted(ra), sorted(rb))
     for k, v in rb.items():
@@ -273,13 +239,13 @@ def test_graph_replays_equal_an_eager_twin(optim):
     from dualpixelface_amd.recipe import synthetic_batch
     lrs = [1e-4] * 4 + [5e-5, 2.5e-5, 2.5e-5]
     with ops.deterministic_mode():
-        a, b = _plugin(optim, step_graph=True), _plugin(optim, step_graph=False)
+        a, b = support.plugin(optim, step_graph=True), support.plugin(optim, step_graph=False)
         for i, lr in enumerate(lrs):
             batch = {k: v.to(DEV) for k, v in synthetic_batch(2, 32, 48, seed=60 + i, mask_mode='bern').items()}
             ra = a.train_step(batch, lr=lr)
             rb = b.train_step(batch, lr=lr)
             torch.cuda.synchronize()
-            _assert_twins_equal(a, b, ra, rb, '%s call %d' % (optim, i), optim)
+            _assert_optim_twins_equal(a, b, ra, rb, '%s call %d' % (optim, i), optim)
             if i == 2:
                 assert a._graph_state['graph'] is None
         states = [(st['calls'], st['graph'] is not None, bool(st.get('failed'))) for st in a._graph_states]
@@ -293,9 +259,9 @@ def test_trainer_resume_under_sgd_and_refusal_under_adam(tmp_path):
     nothing restored."""
     from dualpixelface_amd.synthetic_data import synthetic_loader
     from dualpixelface_amd.trainer import Trainer
-    opt = _option('sgd', epoch=3, init_lr=1e-3, scheduler='explr')
+    opt = support.option_set(optim='sgd', epoch=3, init_lr=1e-3, scheduler='explr')
     loader = synthetic_loader(4, 32, 48, batch_size=2, seed=3)
-    a = _plugin('sgd', epoch=3, init_lr=1e-3, scheduler='explr')
+    a = support.plugin('sgd', epoch=3, init_lr=1e-3, scheduler='explr')
     ta = Trainer(opt, str(tmp_path / 'a'), rank=0, world_size=1)
     ta.fit(a, loader, None)
     assert ta.global_step == 6 and all(os.path.exists(ta.checkpoint_path(e)) for e in range(3))
@@ -304,7 +270,7 @@ def test_trainer_resume_under_sgd_and_refusal_under_adam(tmp_path):
     assert st['kind'] == 'flat_sgd' and set(st) == {'kind', 'buf'}
     assert st['buf'].shape == (a.flat_parameters().numel(),) and float(st['buf'].abs().max()) > 0
     opt.load_model = ta.checkpoint_path(1)
-    b = _plugin('sgd', epoch=3, init_lr=1e-3, scheduler='explr')
+    b = support.plugin('sgd', epoch=3, init_lr=1e-3, scheduler='explr')
     with torch.no_grad():
         b.flat_parameters().mul_(0.5)                      # the checkpoint must overwrite this
     tb = Trainer(opt, str(tmp_path / 'b'), rank=0, world_size=1)
@@ -321,8 +287,8 @@ def test_trainer_resume_under_sgd_and_refusal_under_adam(tmp_path):
     assert torch.allclose(sa[k].cpu(), sb[k].cpu(), rtol=1e-4)
     assert int(sa['feature_extraction.firstconv.0.1.num_batches_tracked']) == int(sb['feature_extraction.firstconv.0.1.num_batches_tracked'])
     # the same file under optim = 'adam'
-    opt_adam = _option('adam', epoch=3, init_lr=1e-3, scheduler='explr')
-    c = _plugin('adam')
+    opt_adam = support.option_set(optim='adam', epoch=3, init_lr=1e-3, scheduler='explr')
+    c = support.plugin('adam')
     with torch.no_grad():
         c.flat_parameters().mul_(0.5)
     before = {k: v.detach().clone() for k, v in c.state_dict().items()}
@@ -353,7 +319,7 @@ def _sgd_rank(rank, world, port, out_dir):
     torch.cuda.set_device(0)
     init_from_env('gloo')
     try:
-        model = _plugin('sgd')
+        model = support.plugin('sgd')
         if rank == 1:                                      # broadcast must repair this
             with torch.no_grad():
                 model.flat_parameters().mul_(1.5)
@@ -395,15 +361,15 @@ def test_two_ranks_on_one_gpu_sgd(tmp_path):
             p.join(30)
     assert [p.exitcode for p in procs] == [0, 0], [p.exitcode for p in procs]
     r0, r1 = (torch.load(str(tmp_path / ('rank%d.pt' % r)), weights_only=False) for r in range(2))
-    model = _plugin('sgd')
+    model = support.plugin('sgd')
     unused = _without_gradient(model, _rank_batch(0))
     ref = Reference('sgd', {name: shape for name, _, _, shape in model._layout}, 1e-3)
     for i, (s0, s1) in enumerate(zip(r0, r1)):
         assert torch.equal(s0['before'], s1['before']) and torch.equal(s0['grad_sum'], s1['grad_sum']), i
         assert torch.equal(s0['after'], s1['after']) and torch.equal(s0['buf'], s1['buf']), 'step %d: the ranks drifted apart' % i
-        before, grads, after, buf = (_named(model, s0[k]) for k in ('before', 'grad_sum', 'after', 'buf'))
+        before, grads, after, buf = (support.named(model, s0[k]) for k in ('before', 'grad_sum', 'after', 'buf'))
         d64 = ref.step(before, {k: (None if k in unused else g.double() * 0.5) for k, g in grads.items()})
         for name in before:
-            within_bound(after[name].double() - before[name].double(), d64[name], 'two ranks step %d %s' % (i, name), p_before=before[name])
-            within_bound(buf[name], ref.state(name), 'two ranks step %d buf %s' % (i, name))
+            support.within_bound(after[name].double() - before[name].double(), d64[name], 'two ranks step %d %s' % (i, name), p_before=before[name])
+            support.within_bound(buf[name], ref.state(name), 'two ranks step %d buf %s' % (i, name))
     assert not torch.equal(r0[0]['before'], r0[1]['after'])

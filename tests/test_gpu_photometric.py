@@ -11,28 +11,19 @@ import pytest
 import torch
 
 from tests import photometric_cpu as pc
+from tests import support
+from tests.support import DEV, bits, tensor
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
 
-
-def _ops():
-    from dualpixelface_amd import ops
-    return ops
-
-
-def _t(a):
-    return None if a is None else torch.tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def _call(c, gout=None, backward=True, **over):
+def _call_photometric(c, gout=None, backward=True, **over):
     """The photometric operator on a case dict (fields replaced by `over`) -> (loss as a float, warped, counted, d pred) as numpy arrays."""
     c = dict(c, **over)
-    p = _t(c['pred']).requires_grad_(True)
-    loss, warped, cnt = _ops().photometric_loss(p, _t(c['ref_rgb']), _t(c['tgt_rgb']), ab=_t(c['ab']), mask=_t(c['mask']),
-                                                head_weights=c['head_weights'], target_type=c['target_type'], shift=c['shift'],
-                                                alpha=c['alpha'], eps=c['eps'], return_warped=True)
+    p = tensor(c['pred']).requires_grad_(True)
+    loss, warped, cnt = support.ops().photometric_loss(p, tensor(c['ref_rgb']), tensor(c['tgt_rgb']), ab=tensor(c['ab']),
+                                                       mask=tensor(c['mask']), head_weights=c['head_weights'], target_type=c['target_type'],
+                                                       shift=c['shift'], alpha=c['alpha'], eps=c['eps'], return_warped=True)
     assert loss.shape == () and loss.dtype == torch.float32 and warped.dtype == torch.float32 and cnt.dtype == torch.uint8
     grad = None
     if backward:
@@ -44,24 +35,12 @@ def _call(c, gout=None, backward=True, **over):
 def _smooth(c, **over):
     """The smoothness operator on a case dict -> (loss as a float, d pred)."""
     c = dict(c, **over)
-    p = _t(c['pred']).requires_grad_(True)
-    loss = _ops().smoothness_loss(p, _t(c['ref_rgb']), mask=_t(c['mask']), head_weights=c['head_weights'], gamma=c['gamma'], eps=c['eps'])
+    p = tensor(c['pred']).requires_grad_(True)
+    loss = support.ops().smoothness_loss(p, tensor(c['ref_rgb']), mask=tensor(c['mask']), head_weights=c['head_weights'], gamma=c['gamma'],
+                                         eps=c['eps'])
     assert loss.shape == () and loss.dtype == torch.float32
     loss.backward()
     return float(loss.detach().double()), p.grad.cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _offset_ptr(t, nbytes):
-    import ctypes
-    return ctypes.c_void_p(t.data_ptr() + nbytes)
-
-
-def _ulp(v):
-    return float(np.spacing(np.float32(abs(v))))
 
 
 def _bounded(tag, ref, loss, grad, r32_loss):
@@ -72,9 +51,9 @@ def _bounded(tag, ref, loss, grad, r32_loss):
     bar = 2.0 * own + 1e-6 * float(np.abs(g64).max())
     err = float(np.abs(grad.astype(np.float64) - g64).max())
     print('%s: loss %.9g, |loss - fp64| %.3e (bar 2 x %.3e + ulp %.3e); max |d pred - fp64 autograd| %.3e (bar %.3e = 2 x %.3e + 1e-6 x %.3e)'
-          % (tag, loss, err_loss, own_loss, _ulp(ref['loss64']), err, bar, own, np.abs(g64).max()))
+          % (tag, loss, err_loss, own_loss, support.ulp_of(ref['loss64']), err, bar, own, np.abs(g64).max()))
     assert np.isfinite(grad).all()
-    assert err_loss <= 2.0 * own_loss + _ulp(ref['loss64'])
+    assert err_loss <= 2.0 * own_loss + support.ulp_of(ref['loss64'])
     assert (np.abs(grad.astype(np.float64) - g64) <= bar).all(), (err, bar)
     assert not grad[g64 == 0].any()                                  # every element is written: exactly 0 where nothing reaches it
 
@@ -83,21 +62,21 @@ def _bounded(tag, ref, loss, grad, r32_loss):
 @pytest.mark.parametrize('name', sorted(pc.CASES))
 def test_warped_values_and_counted_map_equal_the_fp32_restatement(name):
     ref = pc.case(name)
-    loss, warped, cnt, _ = _call(ref['case'], backward=False)
+    loss, warped, cnt, _ = _call_photometric(ref['case'], backward=False)
     r32 = ref['r32']
     assert np.array_equal(cnt, r32['counted'])
-    assert np.array_equal(_bits(warped), _bits(r32['warped'])), float(np.abs(warped - r32['warped']).max())
+    assert np.array_equal(bits(warped), bits(r32['warped'])), float(np.abs(warped - r32['warped']).max())
     print('forward %s: %d of %d pixels counted, loss %.9g (fp32 restatement %.9g)' % (name, cnt.sum(), cnt.size, loss, r32['loss']))
 
 
 def test_identical_views_at_zero_displacement_warp_to_the_reference_luminance():
     c = pc.case('multi-tile-19x70')['case']
     pred = np.zeros_like(c['pred'])
-    _, warped, cnt, _ = _call(c, tgt_rgb=c['ref_rgb'], pred=pred, backward=False)
+    _, warped, cnt, _ = _call_photometric(c, tgt_rgb=c['ref_rgb'], pred=pred, backward=False)
     Y = pc.luma(c['ref_rgb'])
     on = c['mask'] > 0                                               # pred = 0 sends every sample to its own pixel: warpable = the mask
     for h in range(pred.shape[1]):
-        assert np.array_equal(_bits(warped[:, h][on]), _bits(Y[on])) and not warped[:, h][~on].any()
+        assert np.array_equal(bits(warped[:, h][on]), bits(Y[on])) and not warped[:, h][~on].any()
     assert 0 < cnt.sum() < cnt.size
 
 
@@ -105,7 +84,7 @@ def test_identical_views_at_zero_displacement_warp_to_the_reference_luminance():
 @pytest.mark.parametrize('name', sorted(pc.CASES))
 def test_loss_and_gradient_against_the_fp64_restatement(name):
     ref = pc.case(name)
-    loss, _, cnt, grad = _call(ref['case'])
+    loss, _, cnt, grad = _call_photometric(ref['case'])
     _bounded('photometric ' + name, ref, loss, grad, ref['r32']['loss'])
     assert (ref['grad64'] == 0).any() and cnt.sum() < cnt.size
 
@@ -120,7 +99,7 @@ def test_identical_views_at_zero_displacement_give_one_minus_alpha_times_eps():
     """SSIM of a window with itself is exactly 1 in fp32 (numerator and denominator are the same numbers), the intensity term is
     sqrt(eps^2); what is left are the roundings of eps * eps, the root, the product with 1 - alpha and the fp32 result: 4 x 2^-24."""
     c = pc.case('multi-tile-19x70')['case']
-    loss, _, cnt, grad = _call(c, tgt_rgb=c['ref_rgb'], pred=np.zeros_like(c['pred']))
+    loss, _, cnt, grad = _call_photometric(c, tgt_rgb=c['ref_rgb'], pred=np.zeros_like(c['pred']))
     want = _closed(c)
     print('identical views: loss %.9g, closed form %.9g, relative error %.3e' % (loss, want, abs(loss - want) / want))
     assert cnt.any() and abs(loss - want) <= 4 * 2.0 ** -24 * want
@@ -150,16 +129,16 @@ def test_a_ramp_warped_by_the_true_field_gives_the_closed_form_and_offsets_pull_
     c = _ramp_case()
     want = _closed(c)
     r32, r64 = pc.run(c), pc.run(c, np.float64)
-    loss, _, cnt, _ = _call(c)
+    loss, _, cnt, _ = _call_photometric(c)
     own = abs(r32['loss'] - want)
     print('ramp at D0: loss %.9g, closed form %.9g, error %.3e (bar 2 x %.3e + ulp), fp64 restatement %.9g' % (loss, want, abs(loss - want), own,
                                                                                                             r64['loss']))
     assert cnt.sum() >= cnt.size // 4 and np.array_equal(cnt, r32['counted'])
     assert abs(r64['loss'] - want) <= 1e-3 * want                    # the scene does what it says
-    assert abs(loss - want) <= 2.0 * own + _ulp(want)
+    assert abs(loss - want) <= 2.0 * own + support.ulp_of(want)
     for sign in (1.0, -1.0):
         c = _ramp_case(0.25 * sign)
-        loss_o, _, cnt, grad = _call(c)
+        loss_o, _, cnt, grad = _call_photometric(c)
         r = pc.run(c, np.float64)
         assert not any(k.any() for k in r['clamped']) and cnt.any() and loss_o > 10 * want
         assert (grad[cnt > 0] * sign > 0).all()
@@ -167,12 +146,12 @@ def test_a_ramp_warped_by_the_true_field_gives_the_closed_form_and_offsets_pull_
 
 def test_a_displacement_that_throws_every_sample_out_gives_zero_loss_and_zero_gradient():
     c = pc.case('diagonal-33x40')['case']
-    loss, warped, cnt, grad = _call(c, pred=np.full_like(c['pred'], 1e4))
+    loss, warped, cnt, grad = _call_photometric(c, pred=np.full_like(c['pred'], 1e4))
     assert loss == 0.0 and not cnt.any() and not warped.any() and not grad.any() and np.isfinite(grad).all()
     # one head with pixels, one without: the empty head adds 0, not NaN
     pred = c['pred'].copy()
     pred[:, 1] = -1e4
-    loss2, _, cnt2, grad2 = _call(c, pred=pred)
+    loss2, _, cnt2, grad2 = _call_photometric(c, pred=pred)
     one = pc.run(dict(c, pred=pred[:, :1], head_weights=(1.0,)))
     assert cnt2[:, 0].any() and not cnt2[:, 1].any() and not grad2[:, 1].any() and grad2[:, 0].any()
     assert np.isfinite(loss2) and abs(loss2 - one['loss']) <= 2e-7 * one['loss']
@@ -181,17 +160,17 @@ def test_a_displacement_that_throws_every_sample_out_gives_zero_loss_and_zero_gr
 # ---- 4. what must not reach a sum
 def test_junk_under_the_mask_never_reaches_a_sum():
     c = pc.make_case(B=1, n=1, H=24, W=40, seed=44, masked=True)
-    clean = _call(c)
+    clean = _call_photometric(c)
     pred = c['pred'].copy()
     off = np.argwhere(~(c['mask'][0] > 0))
     assert len(off) >= 6
     for k, v in enumerate((np.nan, np.inf, -np.inf, 1e30, -1e30, 0.0)):
         pred[0, 0, off[k][0], off[k][1]] = v
-    junk = _call(c, pred=pred)
-    assert junk[0] == clean[0] and np.array_equal(_bits(junk[3]), _bits(clean[3])) and np.array_equal(junk[2], clean[2])
-    assert np.array_equal(_bits(junk[1]), _bits(clean[1]))
+    junk = _call_photometric(c, pred=pred)
+    assert junk[0] == clean[0] and np.array_equal(bits(junk[3]), bits(clean[3])) and np.array_equal(junk[2], clean[2])
+    assert np.array_equal(bits(junk[1]), bits(clean[1]))
     s_clean, s_junk = _smooth(c), _smooth(c, pred=pred)
-    assert s_junk[0] == s_clean[0] and np.array_equal(_bits(s_junk[1]), _bits(s_clean[1]))
+    assert s_junk[0] == s_clean[0] and np.array_equal(bits(s_junk[1]), bits(s_clean[1]))
 
 
 def test_a_nan_prediction_removes_its_pixel_and_the_nine_windows_through_it():
@@ -201,20 +180,20 @@ def test_a_nan_prediction_removes_its_pixel_and_the_nine_windows_through_it():
     y, x = inner[5]
     pred = c['pred'].copy()
     pred[0, 0, y, x] = np.nan
-    got = _call(c, pred=pred)
+    got = _call_photometric(c, pred=pred)
     mask = c['mask'].copy()
     mask[0, y, x] = 0.0
-    want = _call(c, mask=mask)                                       # the same pixel taken out by the mask instead
+    want = _call_photometric(c, mask=mask)                                       # the same pixel taken out by the mask instead
     assert np.isfinite(got[0]) and np.isfinite(got[3]).all() and np.isfinite(got[1]).all()
-    assert got[0] == want[0] and np.array_equal(got[2], want[2]) and np.array_equal(_bits(got[1]), _bits(want[1]))
-    assert np.array_equal(_bits(got[3]), _bits(want[3])) and got[3][0, 0, y, x] == 0.0 and got[1][0, 0, y, x] == 0.0
+    assert got[0] == want[0] and np.array_equal(got[2], want[2]) and np.array_equal(bits(got[1]), bits(want[1]))
+    assert np.array_equal(bits(got[3]), bits(want[3])) and got[3][0, 0, y, x] == 0.0 and got[1][0, 0, y, x] == 0.0
     assert not got[2][0, 0, y - 1:y + 2, x - 1:x + 2].any() and got[2].sum() == before.sum() - 9
 
 
 # ---- 5. the bits repeat
 def _abi_args(c):
-    ops = _ops()
-    held = [_t(c['pred']), _t(c['ref_rgb']), _t(c['tgt_rgb']), _t(c['ab']), _t(c['mask'])]
+    ops = support.ops()
+    held = [tensor(c['pred']), tensor(c['ref_rgb']), tensor(c['tgt_rgb']), tensor(c['ab']), tensor(c['mask'])]
     B, n, H, W = c['pred'].shape
     tail = (B, n, H, W, ops.TARGET_TYPES[c['target_type']], c['shift'][0], c['shift'][1], c['alpha'], c['eps'], ops._normalizer_floats(),
             ops._host_floats(c['head_weights']))
@@ -223,7 +202,7 @@ def _abi_args(c):
 
 def test_two_calls_return_the_same_bits_whatever_the_scratch_held():
     from dualpixelface_amd._lib import lib
-    ops = _ops()
+    ops = support.ops()
     ref = pc.case('multi-tile-19x70')
     c = ref['case']
     held, args = _abi_args(c)
@@ -245,44 +224,44 @@ def test_two_calls_return_the_same_bits_whatever_the_scratch_held():
         outs.append((out.cpu().numpy(), stats.cpu().numpy(), dpred.cpu().numpy(), luma.cpu().numpy()))
     (o1, s1, d1, l1), (o2, s2, d2, l2) = outs
     assert np.isfinite(o1) and np.isfinite(d1).all() and np.isfinite(s1).all()
-    assert _bits(o1) == _bits(o2) and np.array_equal(s1, s2) and np.array_equal(_bits(d1), _bits(d2)) and np.array_equal(_bits(l1), _bits(l2))
-    assert np.array_equal(_bits(l1[0]), _bits(ref['r32']['Y_ref'])) and np.array_equal(_bits(l1[1]), _bits(ref['r32']['Y_tgt']))
-    loss, _, _, grad = _call(c)                                      # and the operator, with whatever the allocator hands it
-    assert np.float32(loss) == o1 and np.array_equal(_bits(grad), _bits(d1))
+    assert bits(o1) == bits(o2) and np.array_equal(s1, s2) and np.array_equal(bits(d1), bits(d2)) and np.array_equal(bits(l1), bits(l2))
+    assert np.array_equal(bits(l1[0]), bits(ref['r32']['Y_ref'])) and np.array_equal(bits(l1[1]), bits(ref['r32']['Y_tgt']))
+    loss, _, _, grad = _call_photometric(c)                                      # and the operator, with whatever the allocator hands it
+    assert np.float32(loss) == o1 and np.array_equal(bits(grad), bits(d1))
     assert s1[:3].tolist() == ref['r32']['count'] and not s1[3:8].any()
 
 
 def test_another_operators_call_between_forward_and_backward_does_not_change_the_gradient():
-    ops = _ops()
+    ops = support.ops()
     ref = pc.case('multi-tile-19x70')
     c = ref['case']
-    _, _, _, plain = _call(c)
+    _, _, _, plain = _call_photometric(c)
     _, s_plain = _smooth(c)
-    p = _t(c['pred']).requires_grad_(True)
-    q = _t(c['pred']).requires_grad_(True)
-    fixed = [_t(c[k]) for k in ('ref_rgb', 'tgt_rgb', 'mask')]
+    p = tensor(c['pred']).requires_grad_(True)
+    q = tensor(c['pred']).requires_grad_(True)
+    fixed = [tensor(c[k]) for k in ('ref_rgb', 'tgt_rgb', 'mask')]
     loss = ops.photometric_loss(p, fixed[0], fixed[1], mask=fixed[2], head_weights=c['head_weights'], shift=c['shift'])
     sl = ops.smoothness_loss(q, fixed[0], mask=fixed[2], head_weights=c['head_weights'])
     # the same operators on other data, a filter that takes the shared scratch, and a sweep over whatever the allocator freed
     other = pc.case('horizontal')['case']
-    _call(other)
+    _call_photometric(other)
     _smooth(other)
-    ops.guided_filter(_t(other['pred']), _t(other['ref_rgb']), 2, 1e-2)
+    ops.guided_filter(tensor(other['pred']), tensor(other['ref_rgb']), 2, 1e-2)
     for buf in ops._scratch.values():                                # (not the zero arenas: their slots are promised to be 0)
         buf.fill_(float('nan'))
     torch.full((1 << 20,), float('nan'), device=DEV)
     loss.backward()
     sl.backward()
-    assert np.array_equal(_bits(p.grad.cpu().numpy()), _bits(plain)) and np.array_equal(_bits(q.grad.cpu().numpy()), _bits(s_plain))
+    assert np.array_equal(bits(p.grad.cpu().numpy()), bits(plain)) and np.array_equal(bits(q.grad.cpu().numpy()), bits(s_plain))
 
 
 def test_a_captured_call_replays_the_eager_bits():
-    ops = _ops()
+    ops = support.ops()
     c = pc.case('multi-tile-19x70')['case']
-    eager_loss, _, _, eager_grad = _call(c)
+    eager_loss, _, _, eager_grad = _call_photometric(c)
     s_loss, s_grad = _smooth(c)
-    p = _t(c['pred']).requires_grad_(True)
-    fixed = [_t(c[k]) for k in ('ref_rgb', 'tgt_rgb', 'mask')]
+    p = tensor(c['pred']).requires_grad_(True)
+    fixed = [tensor(c[k]) for k in ('ref_rgb', 'tgt_rgb', 'mask')]
 
     def run():
         loss = ops.photometric_loss(p, fixed[0], fixed[1], mask=fixed[2], head_weights=c['head_weights'], shift=c['shift'])
@@ -303,14 +282,14 @@ def test_a_captured_call_replays_the_eager_bits():
             t.fill_(float('nan'))
         graph.replay()
         torch.cuda.synchronize()
-        assert float(outs[0].detach().double()) == eager_loss and np.array_equal(_bits(outs[1].cpu().numpy()), _bits(eager_grad))
-        assert float(outs[2].detach().double()) == s_loss and np.array_equal(_bits(outs[3].cpu().numpy()), _bits(s_grad))
+        assert float(outs[0].detach().double()) == eager_loss and np.array_equal(bits(outs[1].cpu().numpy()), bits(eager_grad))
+        assert float(outs[2].detach().double()) == s_loss and np.array_equal(bits(outs[3].cpu().numpy()), bits(s_grad))
 
 
 def test_gout_scales_the_gradient_to_within_one_ulp():
     c = pc.case('diagonal-33x40')['case']
-    _, _, _, g1 = _call(c)
-    _, _, _, gs = _call(c, gout=0.37)
+    _, _, _, g1 = _call_photometric(c)
+    _, _, _, gs = _call_photometric(c, gout=0.37)
     want = g1.astype(np.float64) * 0.37
     assert (np.abs(gs.astype(np.float64) - want) <= np.spacing(np.abs(want).astype(np.float32))).all()
     assert np.array_equal(gs == 0, g1 == 0) and gs.any()
@@ -319,7 +298,7 @@ def test_gout_scales_the_gradient_to_within_one_ulp():
 # ---- 6. the C ABI's refusals
 def test_abi_refusals_leave_the_outputs_untouched():
     from dualpixelface_amd._lib import lib, DpfError
-    ops = _ops()
+    ops = support.ops()
     c = pc.case('tiny-7x9')['case']
     held, args = _abi_args(c)
     for name, per in (('dpf_photometric_workspace_bytes', 16), ('dpf_smoothness_workspace_bytes', 32)):
@@ -355,7 +334,7 @@ def test_abi_refusals_leave_the_outputs_untouched():
     refused(a[:2] + [None] + a[3:], tail, inv)
     refused(a[:14] + [None] + a[15:], tail, inv)
     refused(a, (ops._ptr(ws), 8) + tail[2:], inv)                                                  # workspace too small
-    refused(a, (_offset_ptr(ws, 4), 16) + tail[2:], inv)                                         # workspace misaligned
+    refused(a, (support.offset_ptr(ws, 4), 16) + tail[2:], inv)                                         # workspace misaligned
     refused(a, tail[:2] + (None,) + tail[3:], inv)                                                 # no luminance planes
     refused(a, tail[:5] + (ops._ptr(warped), None) + tail[7:], inv)                                # one of the optional pair
     refused(a[:5] + [40000] + a[6:], tail, 'DPF_ERR_UNSUPPORTED')                                  # the grid's limit
@@ -376,9 +355,9 @@ def test_abi_refusals_leave_the_outputs_untouched():
     for t in (out, luma, stats, stats32, warped, dpred):                                           # a refusal launches nothing
         assert (t == 7.0).all()
     with pytest.raises(DpfError, match='shift'):
-        _call(c, shift=(0.0, 0.0))
+        _call_photometric(c, shift=(0.0, 0.0))
     with pytest.raises(DpfError, match='alpha'):
-        _call(c, alpha=1.5)
+        _call_photometric(c, alpha=1.5)
     with pytest.raises(DpfError, match='gamma'):
         _smooth(c, gamma=-1.0)
 
@@ -441,42 +420,24 @@ def test_a_luminance_step_weights_exactly_the_pairs_across_it():
 
 
 # ---- 8. the whole step
-def _dpnet(**model_over):
-    from dualpixelface_amd import load_option
-    from dualpixelface_amd.plugin import DPNET
-    from dualpixelface_amd.recipe import fill_by_recipe
-    model = DPNET(load_option('train_faceDP_dpnet', **model_over))
-    fill_by_recipe(model)
-    return model.to(DEV).train()
-
-
-def _steps(model, batch, k):
-    out = []
-    for _ in range(k):
-        res = model.train_step(batch, None, lr=1e-3)
-        assert 'abvalue' not in res or 'abvalue' in batch
-        out.append({key: float(v.detach()) for key, v in res.items() if key.endswith('_loss')})
-    return out
-
-
 def _batch():
     from dualpixelface_amd.recipe import synthetic_batch
     return {k: v.to(DEV) for k, v in synthetic_batch(2, 64, 96, seed=7, mask_mode='bern').items()}
 
 
 def test_dpnet_trains_on_the_two_views_alone_graph_equals_eager(monkeypatch):
-    ops = _ops()
+    ops = support.ops()
     full = _batch()
     batch = {'left': full['left'], 'right': full['right']}
     cfg = dict(loss_type=['photometric', 'smoothness'], lambdas=[1.0, 0.1])
     with ops.deterministic_mode():
         monkeypatch.setenv('DPF_STEP_GRAPH', '0')
-        b = _dpnet(**cfg)
+        b = support.dpnet(**cfg)
         assert b.loss_model.label_free()
-        eager = _steps(b, batch, 4)
+        eager = support.loss_steps(b, batch, 4, abvalue_only_if_given=True)
         monkeypatch.setenv('DPF_STEP_GRAPH', '1')
-        a = _dpnet(**cfg)
-        graphed = _steps(a, batch, 4)                                # two warm-up steps, the capture, one replay
+        a = support.dpnet(**cfg)
+        graphed = support.loss_steps(a, batch, 4, abvalue_only_if_given=True)        # two warm-up steps, the capture, one replay
         assert a._graph_state.get('graph') is not None and not a._graph_state.get('failed')
     assert graphed == eager, (graphed, eager)
     assert torch.equal(a.flat_parameters(), b.flat_parameters())
@@ -489,17 +450,17 @@ def test_dpnet_trains_on_the_two_views_alone_graph_equals_eager(monkeypatch):
 
 
 def test_photometric_next_to_smoothl1_trains_and_changes_the_first_gradient(monkeypatch):
-    ops = _ops()
+    ops = support.ops()
     batch = _batch()
     monkeypatch.setenv('DPF_STEP_GRAPH', '0')
     with ops.deterministic_mode():
-        plain, both = _dpnet(), _dpnet(loss_type=['smoothL1', 'photometric'], lambdas=[1.0, 1.0])
+        plain, both = support.dpnet(), support.dpnet(loss_type=['smoothL1', 'photometric'], lambdas=[1.0, 1.0])
         assert not both.loss_model.label_free()
-        first_plain = _steps(plain, batch, 1)
+        first_plain = support.loss_steps(plain, batch, 1, abvalue_only_if_given=True)
         ga = plain.flat_gradients(zero=False).clone()
-        first = _steps(both, batch, 1)
+        first = support.loss_steps(both, batch, 1, abvalue_only_if_given=True)
         gb = both.flat_gradients(zero=False).clone()
-        more = _steps(both, batch, 2)
+        more = support.loss_steps(both, batch, 2, abvalue_only_if_given=True)
     assert set(first[0]) == {'smoothL1_loss', 'photometric_loss', 'final_loss'} and first[0]['smoothL1_loss'] == first_plain[0]['smoothL1_loss']
     assert all(np.isfinite(v) for step in first + more for v in step.values()) and more[0] != first[0]
     assert torch.isfinite(gb).all() and not torch.equal(ga, gb) and float((ga - gb).abs().max()) > 0

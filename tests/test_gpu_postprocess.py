@@ -16,19 +16,15 @@ import pytest
 import torch
 
 from tests import postprocess_cpu as pc
+from tests import support
+from tests.support import DEV, ptr, stream
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS, SIGMA_COLOR, ULP200 = pc.EPS, pc.SIGMA_COLOR, pc.ULP200
 GUIDED, BILATERAL = pc.GUIDED, pc.BILATERAL
 _id, _sigma_space, _case, _on_device, _run = pc.case_id, pc.sigma_space, pc.case, pc.on_device, pc.run_filter
-
-
-def _ops():
-    from dualpixelface_amd import ops
-    return ops
 
 
 def _check(kind, case):
@@ -63,7 +59,7 @@ def test_guided_hard_statistics():
     shifted = p + 200.0
     q64 = pc.guided_filter(shifted, guide, r, eps)
     naive = float((pc.guided_filter_fp32(shifted, guide, r, eps).double() - q64).abs().max())
-    q = _ops().guided_filter(shifted.to(DEV), guide.to(DEV), r, eps).cpu().double()
+    q = support.ops().guided_filter(shifted.to(DEV), guide.to(DEV), r, eps).cpu().double()
     err = float((q - q64).abs().max())
     flat = float((q - q64)[..., :W // 3 - 2 * r].abs().max())
     print('hard statistics: max |q - q64| %.3e (bar %.3e = 2 x %.3e + 2 ulp(200)); where the guide is constant %.3e; '
@@ -74,7 +70,7 @@ def test_guided_hard_statistics():
 # ---- 2. the same bits every time
 @pytest.mark.parametrize('kind', ['guided', 'bilateral'])
 def test_repeats_bit_for_bit_whatever_the_workspace_holds(kind):
-    ops = _ops()
+    ops = support.ops()
     case = (1, 1, 70, 131, 8, 1)
     p, guide, _, _ = _case(kind, case)
     p, guide = p.to(DEV), guide.to(DEV)
@@ -93,8 +89,8 @@ def test_repeats_bit_for_bit_whatever_the_workspace_holds(kind):
         for fill in (float('nan'), 1e30):
             ws = torch.full((nbytes // 4,), fill, device=DEV)
             out = torch.empty_like(p)
-            lib().call('dpf_guided_filter', _ptr(p), 70 * 131, _ptr(guide), 1, 1, 70, 131, 8, EPS, _norm(), _ptr(ws), nbytes, _ptr(out),
-                       _stream())
+            lib().call('dpf_guided_filter', ptr(p), 70 * 131, ptr(guide), 1, 1, 70, 131, 8, EPS, _norm(), ptr(ws), nbytes, ptr(out),
+                       stream())
             outs.append(out)
         assert torch.equal(outs[0], a) and torch.equal(outs[1], a)
 
@@ -121,14 +117,6 @@ def test_embedding_in_a_larger_image_moves_the_seams_not_the_result(kind, off):
 
 
 # ---- 4. refusals
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _norm():
     return (ctypes.c_float * 6)(0.485, 0.456, 0.406, 0.229, 0.224, 0.225)
 
@@ -146,16 +134,16 @@ def test_abi_refusals_launch_nothing():
         assert lib().call('dpf_guided_filter_workspace_bytes', *bad) == -1, bad
     assert lib().call('dpf_guided_filter_workspace_bytes', B, n, 3, 3, 32) > 0          # smaller than the window: supported
     ws = torch.full((nbytes // 4 + 2,), -7.0, device=DEV)
-    good = dict(p=_ptr(p), stride=n * H * W, guide=_ptr(guide), B=B, n=n, H=H, W=W, r=r, eps=1e-3, ss=3.0, sc=0.1, norm=_norm(), ws=_ptr(ws),
-                nbytes=nbytes, q=_ptr(q))
+    good = dict(p=ptr(p), stride=n * H * W, guide=ptr(guide), B=B, n=n, H=H, W=W, r=r, eps=1e-3, ss=3.0, sc=0.1, norm=_norm(), ws=ptr(ws),
+                nbytes=nbytes, q=ptr(q))
 
     def guided(a):
         lib().call('dpf_guided_filter', a['p'], a['stride'], a['guide'], a['B'], a['n'], a['H'], a['W'], a['r'], a['eps'], a['norm'], a['ws'],
-                   a['nbytes'], a['q'], _stream())
+                   a['nbytes'], a['q'], stream())
 
     def bilateral(a):
         lib().call('dpf_joint_bilateral_filter', a['p'], a['stride'], a['guide'], a['B'], a['n'], a['H'], a['W'], a['r'], a['ss'], a['sc'],
-                   a['norm'], a['q'], _stream())
+                   a['norm'], a['q'], stream())
 
     shared = [dict(p=None), dict(guide=None), dict(norm=None), dict(q=None), dict(B=0), dict(n=0), dict(H=0), dict(W=-3), dict(r=0), dict(r=-1),
               dict(stride=n * H * W - 1)]
@@ -179,7 +167,7 @@ def test_abi_refusals_launch_nothing():
 
 def test_ops_refuse_what_does_not_fit():
     from dualpixelface_amd._lib import DpfError
-    ops = _ops()
+    ops = support.ops()
     p, guide = torch.zeros(1, 1, 8, 12, device=DEV), torch.zeros(1, 3, 8, 12, device=DEV)
     for bad_guide in (torch.zeros(1, 3, 8, 11, device=DEV), torch.zeros(1, 3, 16, 24, device=DEV), torch.zeros(1, 1, 8, 12, device=DEV),
                       torch.zeros(2, 3, 8, 12, device=DEV)):
@@ -199,7 +187,7 @@ def test_ops_refuse_what_does_not_fit():
 
 # ---- 5. capture
 def test_both_filters_replay_from_a_graph():
-    ops = _ops()
+    ops = support.ops()
     case = (1, 1, 70, 131, 8, 1)
     inputs = [pc.scene(1, 1, 70, 131, seed=s) for s in (51, 52, 53)]
     eager = []
@@ -225,20 +213,11 @@ def test_both_filters_replay_from_a_graph():
 
 
 # ---- 6. the whole path
-def _model(cls_name, config, **block):
-    from dualpixelface_amd import load_option, plugin
-    from dualpixelface_amd.recipe import fill_by_recipe
-    opt = load_option(config)
+def _model_with_post_process(cls_name, config, **block):
+    opt = support.option(config)
     for k, v in block.items():
         setattr(opt.post_process, k, v)
-    model = getattr(plugin, cls_name)(opt)
-    fill_by_recipe(model)
-    return model.to(DEV)
-
-
-def _batch(B=1):
-    from dualpixelface_amd.recipe import synthetic_batch
-    return {k: v.to(DEV) for k, v in synthetic_batch(B, 64, 96, seed=9, mask_mode='bern').items()}
+    return support.build(cls_name, opt)
 
 
 def _switches(model, bilateral, guided):
@@ -248,7 +227,7 @@ def _switches(model, bilateral, guided):
 def _eval_path(model, step, bilateral, guided, filt):
     """Evaluation forward with the switches on against the same model with them off, then a deferred metric step on the filtered map."""
     from dualpixelface_amd import ops
-    batch = _batch()
+    batch = support.batch(1, 64, 96, seed=9, mask_mode='bern')
     model.eval()
     with torch.no_grad(), ops.deterministic_mode():
         _switches(model, False, False)
@@ -285,7 +264,7 @@ def _eval_path(model, step, bilateral, guided, filt):
 
 def test_stereodpnet_guided_config_end_to_end():
     from dualpixelface_amd import ops
-    model = _model('STEREODPNET', 'eval_faceDP_guided')
+    model = _model_with_post_process('STEREODPNET', 'eval_faceDP_guided')
     assert model.option.post_process.use_guided and model.option.dataset.flip_lr
     batch = _eval_path(model, model.validation_step, False, True, lambda raw, guide: ops.guided_filter(raw, guide, 8, 1e-3))
     # training mode: nothing is filtered and no key appears, whatever the block says
@@ -301,13 +280,13 @@ def test_stereodpnet_guided_config_end_to_end():
 
 def test_dpnet_bilateral_end_to_end():
     from dualpixelface_amd import ops
-    model = _model('DPNET', 'eval_faceDP_dpnet', use_bilateral=True)
+    model = _model_with_post_process('DPNET', 'eval_faceDP_dpnet', use_bilateral=True)
     _eval_path(model, model.test_step, True, False, lambda raw, guide: ops.joint_bilateral_filter(raw, guide, 5, 3.0, 0.1))
 
 
 def test_both_switches_run_bilateral_then_guided_and_a_missing_prediction_is_named():
     from dualpixelface_amd import ops, postprocess
-    batch = _batch()
+    batch = support.batch(1, 64, 96, seed=9, mask_mode='bern')
     p = (batch['disp'].unsqueeze(1) * 3.0).contiguous()
 
     class Opt(object):

@@ -17,17 +17,13 @@ import pytest
 import torch
 
 from tests import reconstruct_cpu as rc
+from tests import support
+from tests.support import DEV, ptr, stream
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MESH_CASES = [(c, s) for c in rc.CASES for s in c[7]]
-
-
-def _ops():
-    from dualpixelface_amd import ops
-    return ops
 
 
 def _dev(a):
@@ -42,21 +38,17 @@ def _operands(ref):
     return pred, _dev(sc['K']), kw
 
 
-def _ulp(x):
-    return float(np.spacing(np.float32(np.abs(x).max()))) if x.size else 0.0
-
-
 # ---- 1. against the restatement
 @pytest.mark.parametrize('case', rc.CASES, ids=rc.case_id)
 def test_backproject(case):
     ref = rc.case(case)
     assert ref['margin'] >= 1e-4 and ref['agree']
     pred, K, kw = _operands(ref)
-    points, valid = _ops().backproject(pred, K, **kw)
+    points, valid = support.ops().backproject(pred, K, **kw)
     assert points.dtype == torch.float32 and valid.dtype == torch.uint8 and points.shape == (case[0], 3, case[1], case[2])
     assert np.array_equal(valid.cpu().numpy(), ref['valid'])
     own = float(np.abs(ref['P32'] - ref['P64']).max())
-    bar = 2.0 * own + 2.0 * _ulp(ref['P64'])
+    bar = 2.0 * own + 2.0 * support.ulp_of_max(ref['P64'])
     err = float(np.abs(points.cpu().numpy().astype(np.float64) - ref['P64']).max())
     bits = bool(np.array_equal(points.cpu().numpy(), ref['P32']))
     print('backproject %s: max |P - P64| %.3e (bar %.3e = 2 x %.3e + 2 ulp), equal to the fp32 restatement bit for bit: %s, valid %.2f'
@@ -69,7 +61,7 @@ def test_backproject(case):
 def test_depth_normals(case):
     ref = rc.case(case)
     pred, K, kw = _operands(ref)
-    normal, nvalid = _ops().depth_normals(pred, K, max_edge_ratio=ref['ratio'], **kw)
+    normal, nvalid = support.ops().depth_normals(pred, K, max_edge_ratio=ref['ratio'], **kw)
     assert normal.dtype == torch.float32 and nvalid.dtype == torch.uint8 and normal.shape == (case[0], 3, case[1], case[2])
     assert np.array_equal(nvalid.cpu().numpy(), ref['nvalid'])
     n = np.moveaxis(normal.cpu().numpy(), 1, -1)
@@ -82,7 +74,7 @@ def test_depth_normals(case):
         print('depth_normals %s: worst angle to fp64 %.3e rad (bar 2 x %.3e + 1e-6), %d normals' % (rc.case_id(case), err, own, on.sum()))
         assert err <= 2.0 * own + 1e-6
         assert float(np.abs(np.linalg.norm(n[on].astype(np.float64), axis=-1) - 1.0).max()) <= 3e-7
-    away, avalid = _ops().depth_normals(pred, K, max_edge_ratio=ref['ratio'], towards_camera=False, **kw)
+    away, avalid = support.ops().depth_normals(pred, K, max_edge_ratio=ref['ratio'], towards_camera=False, **kw)
     assert torch.equal(avalid, nvalid) and torch.equal(away, -normal)
 
 
@@ -98,7 +90,7 @@ def test_depth_mesh(case, stride):
     out = (torch.full((B, Hs * Ws, 3), -7.0, device=DEV), torch.full((B, Hs * Ws, 3), -7.0, device=DEV),
            torch.full((B, Hs * Ws, 3), 7, dtype=torch.uint8, device=DEV),
            torch.full((B, 2 * (Hs - 1) * (Ws - 1), 3), -7, dtype=torch.int32, device=DEV), torch.full((B, 2), -7, dtype=torch.int32, device=DEV))
-    got = _ops().depth_mesh(pred, K, nmap, view=view, stride=stride, max_edge_ratio=ref['ratio'], out=out, **kw)
+    got = support.ops().depth_mesh(pred, K, nmap, view=view, stride=stride, max_edge_ratio=ref['ratio'], out=out, **kw)
     assert all(g is o for g, o in zip(got, out))
     vertices, vnormals, vcolours, faces, counts = [t.cpu().numpy() for t in got]
     worst = 0.0
@@ -108,7 +100,7 @@ def test_depth_mesh(case, stride):
         assert (nv, nf) == (len(v32), len(f32)), (b, counts[b], len(v32), len(f32))
         assert np.array_equal(faces[b, :nf], f32)
         assert np.array_equal(vcolours[b, :nv], c32) and np.array_equal(vnormals[b, :nv], n32)
-        bar = 2.0 * float(np.abs(v32.astype(np.float64) - v64).max() if nv else 0.0) + 2.0 * _ulp(v64)
+        bar = 2.0 * float(np.abs(v32.astype(np.float64) - v64).max() if nv else 0.0) + 2.0 * support.ulp_of_max(v64)
         err = float(np.abs(vertices[b, :nv].astype(np.float64) - v64).max()) if nv else 0.0
         worst = max(worst, err - bar)
         assert err <= bar, (b, err, bar)                             # (vertex k of the kernel is vertex k of the restatement: the order)
@@ -116,7 +108,7 @@ def test_depth_mesh(case, stride):
         assert (faces[b, nf:] == -7).all()
     print('depth_mesh %s stride %d: counts %s, worst (error - bar) %.3e' % (rc.case_id(case), stride, counts.tolist(), worst))
     # the other winding: the last two indices of every face swapped, nothing else
-    back = _ops().depth_mesh(pred, K, nmap, view=None, stride=stride, max_edge_ratio=ref['ratio'], towards_camera=False, **kw)
+    back = support.ops().depth_mesh(pred, K, nmap, view=None, stride=stride, max_edge_ratio=ref['ratio'], towards_camera=False, **kw)
     assert torch.equal(back[4], got[4])
     for b, (nv, nf) in enumerate(counts):
         assert torch.equal(back[3][b, :nf], got[3][b, :nf][:, [0, 2, 1]]) and torch.equal(back[0][b, :nv], got[0][b, :nv])
@@ -128,8 +120,8 @@ def test_tilted_plane_and_what_differencing_stored_points_would_cost():
     test_depth_normals; printed for information, the same normals from central differences of the stored fp32 points."""
     sc, n_true = rc.tilted_plane()
     pred, K = _dev(sc['pred']).unsqueeze(1), _dev(sc['K'])
-    normal, nvalid = _ops().depth_normals(pred, K, target_type='depth')
-    points, _ = _ops().backproject(pred, K, target_type='depth')
+    normal, nvalid = support.ops().depth_normals(pred, K, target_type='depth')
+    points, _ = support.ops().backproject(pred, K, target_type='depth')
     assert bool(nvalid.all())
     n = np.moveaxis(normal.cpu().numpy(), 1, -1)
     n64, _ = rc.depth_normals(sc['pred'], 'depth', None, sc['K'], None, dt=np.float64)
@@ -148,7 +140,7 @@ def test_tilted_plane_and_what_differencing_stored_points_would_cost():
 
 # ---- 2. the same bits every time
 def test_repeats_bit_for_bit_whatever_the_workspace_holds():
-    ops = _ops()
+    ops = support.ops()
     ref = rc.case(rc.CASES[2])
     pred, K, kw = _operands(ref)
     nmap, view = _dev(ref['n32']), _dev(ref['sc']['view'])
@@ -173,7 +165,7 @@ def test_repeats_bit_for_bit_whatever_the_workspace_holds():
 
 
 def test_calls_replay_from_a_graph():
-    ops = _ops()
+    ops = support.ops()
     ref = rc.case(rc.CASES[2])
     pred, K, kw = _operands(ref)
     nmap = _dev(ref['n32'])
@@ -204,14 +196,6 @@ def test_calls_replay_from_a_graph():
 
 
 # ---- 3. refusals
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def test_abi_refusals_launch_nothing():
     from dualpixelface_amd._lib import lib, DpfError
     B, H, W, s = 2, 9, 12, 2
@@ -235,30 +219,30 @@ def test_abi_refusals_launch_nothing():
         assert lib().call(query, *bad) == -1, bad
     ws = torch.full((nbytes // 4 + 2,), -7.0, device=DEV)
     norm = (ctypes.c_float * 6)(*(rc.MEAN + rc.STD))
-    good = dict(pred=_ptr(pred), pstride=H * W, tt=0, ab=_ptr(ab), K=_ptr(K), mask=_ptr(mask), B=B, H=H, W=W, near=0.0, far=float('inf'),
-                ratio=0.01, towards=1, nmap=_ptr(nmap), view=None, norm=norm, stride=s, ws=_ptr(ws), nbytes=nbytes,
-                **{k: _ptr(v) for k, v in outs.items()})
+    good = dict(pred=ptr(pred), pstride=H * W, tt=0, ab=ptr(ab), K=ptr(K), mask=ptr(mask), B=B, H=H, W=W, near=0.0, far=float('inf'),
+                ratio=0.01, towards=1, nmap=ptr(nmap), view=None, norm=norm, stride=s, ws=ptr(ws), nbytes=nbytes,
+                **{k: ptr(v) for k, v in outs.items()})
 
     def head(a):
         return (a['pred'], a['pstride'], a['tt'], a['ab'], a['K'], a['mask'])
 
     def backproject(a):
-        lib().call('dpf_backproject', *head(a), a['B'], a['H'], a['W'], a['near'], a['far'], a['points'], a['valid'], _stream())
+        lib().call('dpf_backproject', *head(a), a['B'], a['H'], a['W'], a['near'], a['far'], a['points'], a['valid'], stream())
 
     def normals(a):
         lib().call('dpf_depth_normals', *head(a), a['B'], a['H'], a['W'], a['near'], a['far'], a['ratio'], a['towards'], a['normal'],
-                   a['nvalid'], _stream())
+                   a['nvalid'], stream())
 
     def mesh(a):
         lib().call('dpf_depth_mesh', *head(a), a['nmap'], a['view'], a['norm'], a['B'], a['H'], a['W'], a['stride'], a['near'], a['far'],
                    a['ratio'], a['towards'], a['ws'], a['nbytes'], a['vertices'], a['vnormals'], a['vcolours'], a['faces'], a['counts'],
-                   _stream())
+                   stream())
 
     shared = [dict(pred=None), dict(K=None), dict(ab=None), dict(B=0), dict(H=0), dict(W=-3), dict(tt=3), dict(tt=-1), dict(pstride=H * W - 1),
               dict(near=-1.0), dict(near=float('nan')), dict(far=0.0), dict(far=float('nan')), dict(near=5.0, far=5.0)]
     invalid = {backproject: shared + [dict(points=None), dict(valid=None)],
                normals: shared + [dict(normal=None), dict(nvalid=None), dict(ratio=0.0), dict(ratio=-0.01), dict(ratio=float('nan'))],
-               mesh: shared + [dict(nmap=None), dict(view=_ptr(nmap), norm=None), dict(ws=None), dict(vertices=None), dict(vnormals=None),
+               mesh: shared + [dict(nmap=None), dict(view=ptr(nmap), norm=None), dict(ws=None), dict(vertices=None), dict(vnormals=None),
                                dict(vcolours=None), dict(faces=None), dict(counts=None), dict(ratio=0.0), dict(stride=0), dict(stride=-2),
                                dict(nbytes=nbytes - 8), dict(ws=ctypes.c_void_p(ws.data_ptr() + 4))]}
     unsupported = {backproject: [dict(B=65536)], normals: [dict(B=65536)], mesh: [dict(B=65536), dict(stride=3), dict(stride=16)]}
@@ -281,7 +265,7 @@ def test_abi_refusals_launch_nothing():
 
 def test_ops_refuse_what_does_not_fit():
     from dualpixelface_amd._lib import DpfError
-    ops = _ops()
+    ops = support.ops()
     pred, K, ab = torch.ones(2, 1, 8, 12, device=DEV), torch.eye(3, device=DEV).repeat(2, 1, 1), torch.ones(2, 2, device=DEV)
     nmap = torch.zeros(2, 3, 8, 12, device=DEV)
     for kw in (dict(Kmat=K[:1]), dict(ab=ab[:1]), dict(mask=torch.ones(2, 8, 11, device=DEV)), dict(ab=None)):
@@ -308,20 +292,11 @@ def test_ops_refuse_what_does_not_fit():
 
 
 # ---- 4. the whole path
-def _model(cls_name, config, **block):
-    from dualpixelface_amd import load_option, plugin
+def _model_with_reconstruct(cls_name, config, **block):
     from dualpixelface_amd.config import Option
-    from dualpixelface_amd.recipe import fill_by_recipe
-    opt = load_option(config)
+    opt = support.option(config)
     opt.reconstruct = Option(dict(block))
-    model = getattr(plugin, cls_name)(opt)
-    fill_by_recipe(model)
-    return model.to(DEV)
-
-
-def _batch(B=1):
-    from dualpixelface_amd.recipe import synthetic_batch
-    return {k: v.to(DEV) for k, v in synthetic_batch(B, 64, 96, seed=9, mask_mode='bern').items()}
+    return support.build(cls_name, opt)
 
 
 def _rays(K, H, W):
@@ -331,8 +306,8 @@ def _rays(K, H, W):
 
 def test_stereodpnet_evaluation_attaches_the_surface():
     from dualpixelface_amd import metrics, ops, reconstruct
-    model = _model('STEREODPNET', 'eval_faceDP', enabled=False)
-    batch = _batch()
+    model = _model_with_reconstruct('STEREODPNET', 'eval_faceDP', enabled=False)
+    batch = support.batch(1, 64, 96, seed=9, mask_mode='bern')
     model.eval()
     with torch.no_grad(), ops.deterministic_mode():
         off = model.forward(dict(batch))
@@ -371,8 +346,8 @@ def test_stereodpnet_evaluation_attaches_the_surface():
 
 def test_a_model_without_a_normal_head_gets_geometric_normals():
     from dualpixelface_amd import ops, reconstruct
-    model = _model('DPNET', 'eval_faceDP_dpnet', enabled=True)
-    batch = _batch()
+    model = _model_with_reconstruct('DPNET', 'eval_faceDP_dpnet', enabled=True)
+    batch = support.batch(1, 64, 96, seed=9, mask_mode='bern')
     model.eval()
     with torch.no_grad(), ops.deterministic_mode():
         res = model.forward(dict(batch))
@@ -400,7 +375,7 @@ def test_trainer_test_pass_writes_one_ply_per_sample(tmp_path):
     from dualpixelface_amd import ops, reconstruct
     from dualpixelface_amd.synthetic_data import synthetic_loader
     from dualpixelface_amd.trainer import Trainer
-    model = _model('STEREODPNET', 'eval_faceDP', write_ply=True, stride=2)
+    model = _model_with_reconstruct('STEREODPNET', 'eval_faceDP', write_ply=True, stride=2)
     model.option.mode = 'test'
     loader = synthetic_loader(3, 64, 96, 2, seed=4)                   # two batches: two samples, then one
     trainer = Trainer(model.option, str(tmp_path), rank=0, world_size=1)

@@ -7,16 +7,10 @@ import sys
 import pytest
 import torch
 
+from tests import support
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _model(opt):
-    from dualpixelface_amd.plugin import STEREODPNET
-    from dualpixelface_amd.recipe import fill_by_recipe
-    m = STEREODPNET(opt)
-    fill_by_recipe(m)
-    return m.to('cuda').train()
 
 
 def test_resume_matches_uninterrupted_training(tmp_path):
@@ -27,14 +21,14 @@ def test_resume_matches_uninterrupted_training(tmp_path):
     opt.epoch, opt.init_lr, opt.scheduler = 2, 1e-3, 'explr'
     loader = synthetic_loader(4, 32, 48, batch_size=2, seed=3)
     val = synthetic_loader(1, 32, 48, batch_size=1, seed=4)
-    a = _model(opt)
+    a = support.build('STEREODPNET', opt)
     ta = Trainer(opt, str(tmp_path / 'a'), rank=0, world_size=1)
     hist = ta.fit(a, loader, val)
     assert ta.global_step == 4 and os.path.exists(ta.checkpoint_path(0)) and os.path.exists(ta.checkpoint_path(1))
     assert any('metrics' in h and set(h['metrics']) == {'absolute_dp', 'affine_dp', 'normal_dp'} for h in hist)
     # a second model resumes after epoch 0 and must land on the same parameters, moments and running statistics
     opt.load_model = ta.checkpoint_path(0)
-    b = _model(opt)
+    b = support.build('STEREODPNET', opt)
     with torch.no_grad():
         b.flat_parameters().mul_(0.5)                      # the checkpoint must overwrite this
     tb = Trainer(opt, str(tmp_path / 'b'), rank=0, world_size=1)
@@ -84,7 +78,7 @@ def test_training_from_a_facedp_dataset_on_disk(tmp_path, monkeypatch):
     opt.dataset.viewpoint = [1, 2, 6]
     opt.crop_aug.soft_crop.crop_factor = 16                          # 48 x 64 frames -> 32 x 48 crops
     opt.use_raw, opt.workers, opt.batch_size, opt.epoch = False, 2, 2, 1
-    m = _model(opt)
+    m = support.build('STEREODPNET', opt)
     loader = m.train_dataloader()
     assert isinstance(loader, FaceDPBatcher) and len(loader.dataset) == 7 and os.path.exists('FaceDP_train_single.npy')
     val = m.val_dataloader()
@@ -119,7 +113,7 @@ def test_reference_entry_point_call_sequence_through_the_pl_shim(tmp_path, monke
     opt.use_raw, opt.workers, opt.batch_size, opt.epoch = False, 2, 2, 2
     opt.workspace_path, opt.logger_path = str(tmp_path / 'ws'), str(tmp_path / 'ws' / 'log')
     seed_everything(1)
-    model = _model(opt)
+    model = support.build('STEREODPNET', opt)
 
     def make_trainer(resume):
         logger = pl_loggers.TensorBoardLogger(str(opt.logger_path))
@@ -137,7 +131,7 @@ def test_reference_entry_point_call_sequence_through_the_pl_shim(tmp_path, monke
     assert os.path.exists(os.path.join(opt.logger_path, 'scalars.jsonl'))
     # resume from the first epoch's checkpoint: one more epoch is run, not two
     opt.load_model = None
-    model2 = _model(opt)
+    model2 = support.build('STEREODPNET', opt)
     runner2 = make_trainer(ck0)
     runner2.fit(model=model2)
     assert runner2.native.epoch == 2 and runner2.native.global_step == 8
@@ -200,7 +194,7 @@ def test_fit_with_step_graphs_equals_eager_fit_across_full_size_validation(tmp_p
         for graph in (True, False):
             opt = load_option()
             opt.epoch, opt.init_lr, opt.scheduler, opt.step_graph = 3, 1e-3, 'explr', graph
-            m = _model(opt)
+            m = support.build('STEREODPNET', opt)
             tr = Trainer(opt, str(tmp_path / ('graph' if graph else 'eager')), log_every=1, rank=0, world_size=1)
             hist = tr.fit(m, synthetic_loader(7, 32, 48, batch_size=2, seed=5), synthetic_loader(2, 64, 96, batch_size=1, seed=6))
             torch.cuda.synchronize()

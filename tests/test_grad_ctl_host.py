@@ -10,24 +10,19 @@ from dualpixelface_amd import optim
 from dualpixelface_amd.config import load_option
 from dualpixelface_amd.trainer import Trainer
 
+from tests import support
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _option(**kw):
-    opt = load_option()
-    for k, v in kw.items():
-        setattr(opt, k, v)
-    return opt
 
 
 def test_defaults_and_parsing():
     kn = optim.knobs(load_option())
     assert kn == (1, 0.0, False) and not kn.on and not kn.reports
-    kn = optim.knobs(_option(accumulate_grad_batches=4, gradient_clip_val=1, gradient_clip_algorithm='norm', track_grad_norm=-1))
+    kn = optim.knobs(support.option_set(accumulate_grad_batches=4, gradient_clip_val=1, gradient_clip_algorithm='norm', track_grad_norm=-1))
     assert kn == (4, 1.0, False) and kn.on and kn.reports and isinstance(kn.clip, float)
-    kn = optim.knobs(_option(track_grad_norm=2))
+    kn = optim.knobs(support.option_set(track_grad_norm=2))
     assert kn == (1, 0.0, True) and kn.on and kn.reports
-    kn = optim.knobs(_option(accumulate_grad_batches=3))
+    kn = optim.knobs(support.option_set(accumulate_grad_batches=3))
     assert kn.on and not kn.reports
 
 
@@ -46,23 +41,23 @@ def test_every_shipped_config_keeps_the_knobs_off_except_the_accumulation_one():
 def test_accumulate_grad_batches_refusals(bad):
     from dualpixelface_amd.config import Option
     with pytest.raises(ValueError, match='accumulate_grad_batches'):
-        optim.knobs(_option(accumulate_grad_batches=bad))
+        optim.knobs(support.option_set(accumulate_grad_batches=bad))
     if isinstance(bad, dict):                              # the form a JSON config gives a dict
         with pytest.raises(ValueError, match='accumulate_grad_batches'):
-            optim.knobs(_option(accumulate_grad_batches=Option(bad)))
+            optim.knobs(support.option_set(accumulate_grad_batches=Option(bad)))
 
 
 def test_clip_and_track_refusals():
     with pytest.raises(NotImplementedError, match="'value'"):
-        optim.knobs(_option(gradient_clip_val=0.5, gradient_clip_algorithm='value'))
+        optim.knobs(support.option_set(gradient_clip_val=0.5, gradient_clip_algorithm='value'))
     with pytest.raises(ValueError, match='gradient_clip_algorithm'):
-        optim.knobs(_option(gradient_clip_algorithm='max'))
+        optim.knobs(support.option_set(gradient_clip_algorithm='max'))
     for bad in (-0.5, float('nan'), '1.0', None):
         with pytest.raises(ValueError, match='gradient_clip_val'):
-            optim.knobs(_option(gradient_clip_val=bad))
+            optim.knobs(support.option_set(gradient_clip_val=bad))
     for bad in (1, 'inf', float('inf'), 0, True):
         with pytest.raises(ValueError, match='track_grad_norm'):
-            optim.knobs(_option(track_grad_norm=bad))
+            optim.knobs(support.option_set(track_grad_norm=bad))
 
 
 def _cpu_batch():
@@ -75,15 +70,15 @@ def test_train_step_refuses_the_knobs_without_the_gather_scheme():
     surface from train_step too."""
     from dualpixelface_amd.plugin import STEREODPNET
     for kw in ({'accumulate_grad_batches': 2}, {'gradient_clip_val': 1.0}, {'track_grad_norm': 2}):
-        model = STEREODPNET(_option(**kw))
+        model = STEREODPNET(support.option_set(**kw))
         model.gather_grads = False
         with pytest.raises(NotImplementedError, match='gather'):
             model.train_step(_cpu_batch())
         assert model._flat_grad is None and model._adam is None and model._optim is None
-    model = STEREODPNET(_option(gradient_clip_val=1.0, gradient_clip_algorithm='value'))
+    model = STEREODPNET(support.option_set(gradient_clip_val=1.0, gradient_clip_algorithm='value'))
     with pytest.raises(NotImplementedError, match="'value'"):
         model.train_step(_cpu_batch())
-    model = STEREODPNET(_option(accumulate_grad_batches={'0': 2}))
+    model = STEREODPNET(support.option_set(accumulate_grad_batches={'0': 2}))
     with pytest.raises(ValueError, match='accumulate_grad_batches'):
         model.train_step(_cpu_batch())
     assert model._flat_grad is None and model._adam is None
@@ -122,7 +117,7 @@ def _batches(n):
 def test_trainer_group_arithmetic(tmp_path):
     """7 batches at N = 3: optimiser steps after batches 3, 6 and 7 (the short group is ended by last_in_epoch), global_step == 3, the log
     holds one record per optimiser step with grad_norm, and a second epoch starts a fresh group."""
-    opt = _option(accumulate_grad_batches=3, gradient_clip_val=1.0, epoch=1, scheduler='none')
+    opt = support.option_set(accumulate_grad_batches=3, gradient_clip_val=1.0, epoch=1, scheduler='none')
     m = _Stub(opt)
     tr = Trainer(opt, str(tmp_path), log_every=1, rank=0, world_size=1)
     tr.fit(m, _batches(7), None)
@@ -139,7 +134,7 @@ def test_trainer_group_arithmetic(tmp_path):
 
 
 def test_trainer_max_steps_and_log_every_count_optimiser_steps(tmp_path):
-    opt = _option(accumulate_grad_batches=2, epoch=5, scheduler='none')
+    opt = support.option_set(accumulate_grad_batches=2, epoch=5, scheduler='none')
     m = _Stub(opt)
     tr = Trainer(opt, str(tmp_path), log_every=2, max_steps=None, rank=0, world_size=1)
     tr.fit(m, _batches(8), None)
@@ -157,14 +152,14 @@ def test_trainer_with_the_knobs_off_calls_train_step_as_before(tmp_path):
         def train_step(self, batch, reducer=None, lr=None):
             self.calls.append(int(batch['x'][0]))
             return {'final_loss': batch['x'].float().mean()}
-    opt = _option(epoch=1, scheduler='none')
+    opt = support.option_set(epoch=1, scheduler='none')
     m = Old(opt)
     tr = Trainer(opt, str(tmp_path), log_every=1, rank=0, world_size=1)
     tr.fit(m, _batches(7), None)
     assert m.calls == list(range(1, 8)) and tr.global_step == 7
     assert [r['step'] for r in tr.history if 'step' in r] == list(range(1, 8))
     with pytest.raises(ValueError, match='accumulate_grad_batches'):
-        Trainer(_option(accumulate_grad_batches={'1': 2}), str(tmp_path), rank=0, world_size=1).fit(Old(opt), _batches(1), None)
+        Trainer(support.option_set(accumulate_grad_batches={'1': 2}), str(tmp_path), rank=0, world_size=1).fit(Old(opt), _batches(1), None)
 
 
 def test_shim_hands_the_keywords_through(tmp_path, monkeypatch):
@@ -173,7 +168,7 @@ def test_shim_hands_the_keywords_through(tmp_path, monkeypatch):
         monkeypatch.delitem(sys.modules, name)
     import pytorch_lightning as pl
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
-    opt = _option(gradient_clip_val=5.0, epoch=1, scheduler='none', workspace_path=str(tmp_path))
+    opt = support.option_set(gradient_clip_val=5.0, epoch=1, scheduler='none', workspace_path=str(tmp_path))
     m = _Stub(opt)
     shim = pl.Trainer(max_epochs=1, accumulate_grad_batches=3, gradient_clip_val=0.25, track_grad_norm=2, log_every_n_steps=1)
     shim.fit(m, _batches(7), None)
@@ -181,7 +176,7 @@ def test_shim_hands_the_keywords_through(tmp_path, monkeypatch):
     assert optim.knobs(opt) == (3, 0.25, True)
     assert shim.native.global_step == 3 and [c[0] for c in m.calls if c[2]] == [3, 6, 7]
     # what is not given leaves the option alone; what is given wrongly is refused by the same rules
-    opt2 = _option(gradient_clip_val=5.0, accumulate_grad_batches=2, epoch=1, scheduler='none', workspace_path=str(tmp_path / 'b'))
+    opt2 = support.option_set(gradient_clip_val=5.0, accumulate_grad_batches=2, epoch=1, scheduler='none', workspace_path=str(tmp_path / 'b'))
     pl.Trainer(max_epochs=1).fit(_Stub(opt2), _batches(2), None)
     assert optim.knobs(opt2) == (2, 5.0, False)
     with pytest.raises(NotImplementedError, match="'value'"):

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import loss_bank_cpu as lb
+from tests import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,18 +24,13 @@ def test_restatement_against_reference_fixture(golden_dir):
         assert ('mask' in batch) == masked and ('conf' in batch) == with_conf
         loss, grad = lb.hook_call(kind, tt, pred, batch, fx.head_weights(n), fx.variance_focus)
         ref_loss, ref_grad = fx.expected(case)
-        lb.close(loss, ref_loss, 1e-6, name + ' loss')
-        lb.close_elem(grad, ref_grad, name + ' grad')
-
-
-def _option(**over):
-    from dualpixelface_amd import load_option
-    return load_option('train_faceDP_dpnet', **over)
+        support.close(loss, ref_loss, 1e-6, name + ' loss')
+        support.close_elem(grad, ref_grad, name + ' grad')
 
 
 def test_silog_selects_and_reads_its_options():
     from dualpixelface_amd.losses import SILOGLoss, loss_selector
-    sel = loss_selector(_option(loss_type=['silog'], variance_focus=0.6))
+    sel = loss_selector(support.option('train_faceDP_dpnet', loss_type=['silog'], variance_focus=0.6))
     assert sel.loss_name == ['silog'] and isinstance(sel.loss_func[0], SILOGLoss)
     assert sel.loss_func[0].variance_focus == 0.6
     assert sel.loss_func[0].head_weights(1) == [1.0] and sel.loss_func[0].head_weights(3) == [1.0, 0.75294, 0.18824]
@@ -43,7 +39,7 @@ def test_silog_selects_and_reads_its_options():
 def test_folded_is_still_refused():
     from dualpixelface_amd.losses import loss_selector
     with pytest.raises(NotImplementedError, match='wrong loss type : folded'):
-        loss_selector(_option(loss_type=['folded']))
+        loss_selector(support.option('train_faceDP_dpnet', loss_type=['folded']))
 
 
 def test_reference_path_exposes_silog():
@@ -54,7 +50,7 @@ def test_reference_path_exposes_silog():
 @pytest.mark.parametrize('loss', ['silog', 'smoothL1'])
 def test_bad_target_type_asserts(loss):
     from dualpixelface_amd.losses import loss_selector
-    sel = loss_selector(_option(loss_type=[loss], variance_focus=0.6))
+    sel = loss_selector(support.option('train_faceDP_dpnet', loss_type=[loss], variance_focus=0.6))
     z = torch.ones(1, 1, 2, 2)
     batch = {'disp': z[0], 'idepth': z[0], 'depth': z[0], 'abvalue': torch.zeros(1, 2)}
     with pytest.raises(AssertionError):
@@ -64,7 +60,7 @@ def test_bad_target_type_asserts(loss):
 @pytest.mark.parametrize('loss', ['silog', 'smoothL1'])
 def test_least_square_is_refused(loss):
     from dualpixelface_amd.losses import loss_selector
-    opt = _option(loss_type=[loss], variance_focus=0.6)
+    opt = support.option('train_faceDP_dpnet', loss_type=[loss], variance_focus=0.6)
     opt.dataset.dp_conversion = 'least_square'
     with pytest.raises(NotImplementedError, match='least_square'):
         loss_selector(opt)
@@ -72,7 +68,7 @@ def test_least_square_is_refused(loss):
 
 def test_silog_refuses_a_batch_without_abvalue():
     from dualpixelface_amd.losses import loss_selector
-    sel = loss_selector(_option(loss_type=['silog'], variance_focus=0.6))
+    sel = loss_selector(support.option('train_faceDP_dpnet', loss_type=['silog'], variance_focus=0.6))
     z = torch.ones(1, 1, 2, 2)
     with pytest.raises(NotImplementedError, match='least_square'):
         sel.forward({'pred_depth': z}, {'disp': z[0]}, target_type='disp')

@@ -107,7 +107,7 @@ def test_checkpoint_before_the_first_step_names_the_kind(tmp_path):
     assert m._optim is None
 
 
-def _plugin(optim):
+def _cpu_plugin(optim):
     from dualpixelface_amd.plugin import STEREODPNET
     opt = load_option()
     opt.optim = optim
@@ -119,7 +119,7 @@ def test_configure_optimizers_under_each_optim():
               'sgd': (torch.optim.SGD, {'momentum': 0.9, 'weight_decay': 2e-4, 'dampening': 0, 'nesterov': False}),
               'rmsprop': (torch.optim.RMSprop, {'eps': 1e-5, 'alpha': 0.99, 'momentum': 0, 'centered': False, 'weight_decay': 0})}
     for optim, (cls, hyper) in expect.items():
-        model = _plugin(optim)
+        model = _cpu_plugin(optim)
         optimizers, schedulers = model.configure_optimizers()
         assert len(optimizers) == 1 and type(optimizers[0]) is cls, optim
         group = optimizers[0].param_groups[0]
@@ -131,7 +131,7 @@ def test_configure_optimizers_under_each_optim():
 
 
 def test_unknown_optim_raises_before_any_gpu_call():
-    model = _plugin('lbfgs')
+    model = _cpu_plugin('lbfgs')
     with pytest.raises(NotImplementedError, match='optimizer is not defined'):
         model.configure_optimizers()
     # CPU tensors, and nothing of the step has run when the name is refused: no gradient arena, no optimiser state

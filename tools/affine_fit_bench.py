@@ -24,6 +24,9 @@ import time
 
 import torch
 
+import bench_support
+from bench_support import fmt
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -55,30 +58,6 @@ def torch_fit(pred, idepth, steps, f=0.1):
             A, B = (sw * sxy - sx * sy) / det, (sxx * sy - sx * sxy) / det
         out.append(torch.stack([B, A]))
     return torch.stack(out).float()
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def rounds_of(fns, reps, rounds):
-    for fn in fns:
-        timed(fn, 2)
-    times = [[] for _ in fns]
-    for _ in range(rounds):
-        for t, fn in zip(times, fns):
-            t.append(timed(fn, reps))
-    return times
-
-
-def fmt(t):
-    return '%.3f ms (min %.3f, max %.3f)' % (statistics.median(t), min(t), max(t))
 
 
 def step_times(shape, reps, rounds):
@@ -145,7 +124,7 @@ def main():
                 return torch_fit(pred.detach(), idepth, steps)
 
             diff = float((ref() - ab).abs().div(ab.abs()).max())
-            tf, tl, tr = rounds_of((fit, fit_loss, ref), args.reps, args.rounds)
+            tf, tl, tr = bench_support.rounds_of((fit, fit_loss, ref), args.reps, args.rounds, warm=2)
             traffic = 8.0 * H * W * sum(2 + i for i in iters)
             mf = statistics.median(tf)
             lines.append('%-14s %-5s iterations %s | fit %s | fit+loss fwd+bwd %s | torch %d steps %s | torch / fit %.1fx | %.1f MB per fit = '

@@ -3,6 +3,8 @@ import os
 import sys
 import torch
 
+import bench_support
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dualpixelface_amd import ops  # noqa: E402
 
@@ -22,16 +24,10 @@ SHAPES = [
 REPS = 10
 
 
-def timed(fn):
+def timed_after_warmup(fn):
     fn()
     torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(REPS):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / REPS
+    return bench_support.timed(fn, REPS)
 
 
 def main():
@@ -47,9 +43,9 @@ def main():
         for name, fn in (('fwd', lambda: ops._conv_fwd_raw(x, w, None, s3, pd, d3)),
                          ('dgrad', lambda: ops._conv_transpose_raw(g, w, None, x.shape[2:], ks, s3, pd, d3)),
                          ('wgrad', lambda: ops._conv_wgrad_raw(g, x, w.shape, s3, pd, d3))):
-            t32 = timed(fn)
+            t32 = timed_after_warmup(fn)
             with ops.conv_operands(True):
-                t16 = timed(fn)
+                t16 = timed_after_warmup(fn)
             row += '  %s %6.3f -> %6.3f ms (%5.1f -> %6.1f TF)' % (name, t32, t16, flops / t32 / 1e9, flops / t16 / 1e9)
         print(row, flush=True)
 

@@ -19,6 +19,8 @@ import sys
 import torch
 import torch.nn.functional as F
 
+import bench_support
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -26,21 +28,12 @@ if ROOT not in sys.path:
 DEV = 'cuda'
 
 
-def timed(fn, warmup, iters, repeats):
+def median_min_max(fn, warmup, iters, repeats):
     """-> (median, min, max) ms per call."""
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
-    vals = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        vals.append(a.elapsed_time(b) / iters)
-    vals.sort()
+    vals = sorted(bench_support.timed(fn, iters) for _ in range(repeats))
     return vals[len(vals) // 2], vals[0], vals[-1]
 
 
@@ -54,7 +47,7 @@ def row(name, mine, ref, nbytes):
 def kernel_rows(args):
     from dualpixelface_amd import ops
     rows = []
-    t = lambda f: timed(f, args.warmup, args.steps, args.repeats)
+    t = lambda f: median_min_max(f, args.warmup, args.steps, args.repeats)
     g = torch.Generator(device=DEV).manual_seed(0)
     rn = lambda *s: torch.randn(*s, device=DEV, generator=g)
     # max-pool: Encoder2's pool of the raw input (k7 s2 p1) and the largest encoder skip (11 channels, k3 s1, 512 x 768)
@@ -110,7 +103,7 @@ def model_rows(args):
             fill_by_recipe(model)
             model.to(DEV).train()
             batch = {k: v.to(DEV) for k, v in synthetic_batch(B, H, W, seed=1, mask_mode='bern').items()}
-            ms = timed(lambda: model.train_step(batch, None, lr=1e-4), max(args.warmup, 4), args.steps, args.repeats)
+            ms = median_min_max(lambda: model.train_step(batch, None, lr=1e-4), max(args.warmup, 4), args.steps, args.repeats)
             r = {'name': 'DPNET train_step %dx%dx%d %s' % (B, H, W, 'graph' if graph else 'eager'), 'ms': ms[0], 'ms_min': ms[1], 'ms_max': ms[2],
                  'samples_per_s': B / ms[0] * 1e3}
             print(json.dumps(r))

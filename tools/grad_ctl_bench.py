@@ -28,22 +28,11 @@ import time
 
 import torch
 
+import bench_support
+from bench_support import fmt
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONFIGS = {'off': {}, 'clip': {'gradient_clip_val': 1.0}, 'accum4': {'accumulate_grad_batches': 4}, 'accum4_clip': {'accumulate_grad_batches': 4, 'gradient_clip_val': 1.0}}
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def fmt(t):
-    return '%.4f ms (min %.4f, max %.4f)' % (statistics.median(t), min(t), max(t))
 
 
 def kernel_lines(n, reps, rounds, copy_tbs):
@@ -66,7 +55,7 @@ def kernel_lines(n, reps, rounds, copy_tbs):
     side = torch.cuda.Stream()
     graphs = []
     for _, _, fn in forms:
-        timed(fn, 5)
+        bench_support.timed(fn, 5)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             fn()                                           # (the scratch of this stream exists before the capture)
@@ -81,14 +70,14 @@ def kernel_lines(n, reps, rounds, copy_tbs):
         for t, e, graph, (_, _, fn) in zip(times, eager, graphs, forms):
             acc.mul_(0.0)
             graph.replay()
-            t.append(timed(graph.replay, 1) / reps)
-            e.append(timed(fn, reps))
+            t.append(bench_support.timed(graph.replay, 1) / reps)
+            e.append(bench_support.timed(fn, reps))
     torch.cuda.synchronize()
     out = []
     for t, e, (name, per, _) in zip(times, eager, forms):
         med = statistics.median(t)
         rate = per * n / (med * 1e-3) / 1e12
-        out.append('%-38s %s%s | one by one from Python %.4f ms' % (name, fmt(t), ' | %5.1f MB = %.2f TB/s = %3.0f %% of the %.1f TB/s copy rate'
+        out.append('%-38s %s%s | one by one from Python %.4f ms' % (name, fmt(t, 4), ' | %5.1f MB = %.2f TB/s = %3.0f %% of the %.1f TB/s copy rate'
                                                                     % (per * n / 1e6, rate, 100 * rate / copy_tbs, copy_tbs) if per else '',
                                                                     statistics.median(e)))
     return out
@@ -179,7 +168,7 @@ def main():
             % (shape + (args.step_reps, args.step_rounds))]
     for k, label in (('off', 'knobs off'), ('clip', 'gradient_clip_val 1.0'), ('accum4', 'accumulate_grad_batches 4, per micro-step'),
                      ('accum4_clip', 'accumulate_grad_batches 4 + clip 1.0, per micro-step')):
-        more.append('%-56s %s' % (label, fmt(times[k])))
+        more.append('%-56s %s' % (label, fmt(times[k], 4)))
     more += ['(b) clipping on - off: %+.4f ms = %+.2f %% of the step' % (med['clip'] - med['off'], 100 * (med['clip'] - med['off']) / med['off']),
              '(c) N = 4 - N = 1 per micro-step: %+.4f ms = %+.2f %%' % (med['accum4'] - med['off'], 100 * (med['accum4'] - med['off']) / med['off'])]
     print('\n'.join(more), flush=True)
@@ -193,7 +182,7 @@ def main():
             ours.append(spawn(ROOT, args))
         mo, mt = statistics.median(ours), statistics.median(theirs)
         lines += ['', '(a) knobs off, fresh processes alternating (each the median of %d rounds of %d replays): parent commit %s | this build %s'
-                  % (args.step_rounds, args.step_reps, fmt(theirs), fmt(ours)),
+                  % (args.step_rounds, args.step_reps, fmt(theirs, 4), fmt(ours, 4)),
                   '    this build - parent: %+.4f ms = %+.2f %%; the parent\'s own run-to-run spread (max - min): %.4f ms = %.2f %%'
                   % (mo - mt, 100 * (mo - mt) / mt, max(theirs) - min(theirs), 100 * (max(theirs) - min(theirs)) / mt)]
     else:

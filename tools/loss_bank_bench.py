@@ -19,6 +19,8 @@ import sys
 import torch
 import torch.nn.functional as F
 
+import bench_support
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -34,16 +36,6 @@ def torch_loss(kind, pred, target, mask, weights):
         dist = [weights[i] * (torch.log(pred[:, i][sel]) - torch.log(gt)) for i in range(pred.shape[1])]
         return sum(torch.sqrt((d ** 2).mean() - VARIANCE_FOCUS * (d.mean() ** 2)) * 10.0 for d in dist)
     return sum(weights[i] * F.smooth_l1_loss(pred[:, i][sel], gt) for i in range(pred.shape[1]))
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
 
 
 def main():
@@ -83,11 +75,11 @@ def main():
         loss_rel = abs(float(lh.detach()) - float(lr.detach())) / abs(float(lr.detach()))
         grad_rel = float((gh - gr).abs().max() / gr.abs().max())
         for fn in (hip, ref):
-            timed(fn, 10)
+            bench_support.timed(fn, 10)
         th, tr = [], []
         for _ in range(args.rounds):
-            th.append(timed(hip, args.reps))
-            tr.append(timed(ref, args.reps))
+            th.append(bench_support.timed(hip, args.reps))
+            tr.append(bench_support.timed(ref, args.reps))
         mh, mr = statistics.median(th), statistics.median(tr)
         bw = nbytes / (mh * 1e-3)
         lines.append('%-16s hip %.4f ms (min %.4f, max %.4f) | torch %.4f ms (min %.4f, max %.4f) | torch / hip %.1fx | hip %.2f TB/s = %.0f %% of HBM peak'

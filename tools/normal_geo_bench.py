@@ -25,18 +25,10 @@ import sys
 
 import torch
 
+import bench_support
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WEIGHTS = [1.0, 0.75294, 0.18824, 0.047059, 0.011765]
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
 
 
 def _shift(z, dy, dx):
@@ -143,27 +135,9 @@ def agreement(args):
           % (what, 1.0 - float(loss), int(counted.sum()), counted.numel(), dict(s._asdict())))
 
 
-def _dpnet(losses, H, W):
-    from dualpixelface_amd import load_option
-    from dualpixelface_amd.plugin import DPNET
-    from dualpixelface_amd.recipe import fill_by_recipe, synthetic_batch
+def _step_with(losses):
     lambdas = [1.0] + [0.1] * (len(losses) - 1)
-    model = DPNET(load_option('train_faceDP_dpnet', loss_type=list(losses), lambdas=lambdas))
-    fill_by_recipe(model)
-    model.to('cuda').train()
-    batch = {k: v.cuda() for k, v in synthetic_batch(2, H, W, seed=7, mask_mode='bern').items()}
-    for _ in range(5):                                             # two warm-up steps, the capture, two replays
-        model.train_step(batch, None, lr=1e-4)
-    assert model._graph_state.get('graph') is not None, 'the step was not captured'
-    return lambda: model.train_step(batch, None, lr=1e-4)
-
-
-def step_line(args):
-    sys.path.insert(0, os.path.abspath(args.root))
-    fn = _dpnet(args.losses.split(','), 256, 384)
-    t = [timed(fn, args.reps) for _ in range(args.rounds)]
-    print('dpnet step 2x256x384 loss_type %s root %s: median %.4f ms (min %.4f, max %.4f), %d replays x %d rounds'
-          % (args.losses, args.root, statistics.median(t), min(t), max(t), args.reps, args.rounds))
+    return bench_support.captured_dpnet_step('train_faceDP_dpnet', 256, 384, loss_type=list(losses), lambdas=lambdas)
 
 
 def main():
@@ -180,7 +154,8 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'normal_geo_bench needs an MI355X'
     if args.step:
-        return step_line(args)
+        sys.path.insert(0, os.path.abspath(args.root))
+        return bench_support.step_line('loss_type %s' % args.losses, _step_with(args.losses.split(',')), args.reps, args.rounds, args.root)
     sys.path.insert(0, ROOT)
     if args.agreement:
         return agreement(args)
@@ -207,11 +182,11 @@ def main():
         loss_rel = abs(float(lh.detach()) - float(lr.detach())) / abs(float(lr.detach()))
         grad_rel = float((gh - gr).abs().max() / gr.abs().max())
         for fn in (hip, ref):
-            timed(fn, 5)
+            bench_support.timed(fn, 5)
         th, tr = [], []
         for _ in range(args.rounds):
-            th.append(timed(hip, args.reps))
-            tr.append(timed(ref, max(args.reps // 10, 3)))
+            th.append(bench_support.timed(hip, args.reps))
+            tr.append(bench_support.timed(ref, max(args.reps // 10, 3)))
         mh, mr = statistics.median(th), statistics.median(tr)
         nbytes = 4.0 * B * H * W * ((n + 5) + (2 * n + 5))
         lines.append('%dx%dx%dx%d  hip %.4f ms (min %.4f, max %.4f) | torch %.3f ms (min %.3f, max %.3f) | torch / hip %.0fx | %.1f MB -> %.2f TB/s'
@@ -220,11 +195,11 @@ def main():
                         float(lh.detach()), loss_rel, grad_rel))
     lines += ['', 'Captured DPNet train step at 2x256x384 (synthetic batch, fp32), loss_type [smoothL1] against [smoothL1, normal_geo] (lambdas 1.0, 0.1),',
               '%d replays between two events, alternating, %d rounds:' % (args.reps, args.rounds)]
-    plain, both = _dpnet(['smoothL1'], 256, 384), _dpnet(['smoothL1', 'normal_geo'], 256, 384)
+    plain, both = _step_with(['smoothL1']), _step_with(['smoothL1', 'normal_geo'])
     tp, tb = [], []
     for _ in range(args.rounds):
-        tp.append(timed(plain, args.reps))
-        tb.append(timed(both, args.reps))
+        tp.append(bench_support.timed(plain, args.reps))
+        tb.append(bench_support.timed(both, args.reps))
     mp, mb = statistics.median(tp), statistics.median(tb)
     lines.append('smoothL1 %.4f ms (min %.4f, max %.4f) | smoothL1 + normal_geo %.4f ms (min %.4f, max %.4f) | + %.4f ms = %.2f %% of the step'
                  % (mp, min(tp), max(tp), mb, min(tb), max(tb), mb - mp, 100.0 * (mb - mp) / mp))

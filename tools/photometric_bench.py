@@ -28,20 +28,12 @@ import sys
 
 import torch
 
+import bench_support
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WEIGHTS = [1.0, 0.75294, 0.18824, 0.047059, 0.011765]
 COPY_TBS = 6.29
 SHIFTS = [(0.0, 1.0), (0.0, -1.0), (0.0, 2.0), (0.0, -2.0), (1.0, 0.0), (-1.0, 0.0), (2.0, 0.0), (-2.0, 0.0)]
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
 
 
 def synthetic_pair(B, n, H, W, seed=3, device='cuda'):
@@ -91,30 +83,6 @@ def agreement(args):
         print('  %-18s mean term %.6f over %d of %d pixels%s' % (name, loss, cnt, total, '   <- smallest' if name == best[0] else ''))
 
 
-def _dpnet(config, H, W, views_only, **over):
-    from dualpixelface_amd import load_option
-    from dualpixelface_amd.plugin import DPNET
-    from dualpixelface_amd.recipe import fill_by_recipe, synthetic_batch
-    model = DPNET(load_option(config, **over))
-    fill_by_recipe(model)
-    model.to('cuda').train()
-    batch = {k: v.cuda() for k, v in synthetic_batch(2, H, W, seed=7, mask_mode='bern').items()}
-    if views_only:
-        batch = {k: batch[k] for k in ('left', 'right')}
-    for _ in range(5):                                             # two warm-up steps, the capture, two replays
-        model.train_step(batch, None, lr=1e-4)
-    assert model._graph_state.get('graph') is not None, 'the step was not captured'
-    return lambda: model.train_step(batch, None, lr=1e-4)
-
-
-def step_line(args):
-    sys.path.insert(0, os.path.abspath(args.root))
-    fn = _dpnet(args.config, 256, 384, 'photometric' in args.config)
-    t = [timed(fn, args.reps) for _ in range(args.rounds)]
-    print('dpnet step 2x256x384 config %s root %s: median %.4f ms (min %.4f, max %.4f), %d replays x %d rounds'
-          % (args.config, args.root, statistics.median(t), min(t), max(t), args.reps, args.rounds))
-
-
 def _row(tag, shape, times, nbytes, extra=''):
     m = statistics.median(times)
     floor = nbytes / (COPY_TBS * 1e12) * 1e3
@@ -135,7 +103,9 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'photometric_bench needs an MI355X'
     if args.step:
-        return step_line(args)
+        sys.path.insert(0, os.path.abspath(args.root))
+        fn = bench_support.captured_dpnet_step(args.config, 256, 384, 'photometric' in args.config)
+        return bench_support.step_line('config %s' % args.config, fn, args.reps, args.rounds, args.root)
     sys.path.insert(0, ROOT)
     if args.agreement:
         return agreement(args)
@@ -160,21 +130,22 @@ def main():
             grad = bwd()
             assert math.isfinite(float(loss)) and bool(torch.isfinite(grad).all())
             for fn in (fwd, bwd):
-                timed(fn, 5)
+                bench_support.timed(fn, 5)
             tf, tb = [], []
             for _ in range(args.rounds):
-                tf.append(timed(fwd, args.reps))
-                tb.append(timed(bwd, args.reps))
+                tf.append(bench_support.timed(fwd, args.reps))
+                tb.append(bench_support.timed(bwd, args.reps))
             lines.append(_row(name + ' forward', (B, n, H, W), tf, fbytes, ' | loss %.6f' % float(loss)))
             lines.append(_row(name + ' backward', (B, n, H, W), tb, bbytes, ' | max |d pred| %.3e' % float(grad.abs().max())))
     lines += ['', 'Captured DPNet train step at 2x256x384 (synthetic batch, fp32): train_faceDP_dpnet (loss_type [smoothL1], the full batch) against',
               'train_faceDP_dpnet_photometric (loss_type [photometric, smoothness], lambdas 1.0, 0.1, a batch of the two views only),',
               '%d replays between two events, alternating, %d rounds:' % (args.reps, args.rounds)]
-    plain, ours = _dpnet('train_faceDP_dpnet', 256, 384, False), _dpnet('train_faceDP_dpnet_photometric', 256, 384, True)
+    plain = bench_support.captured_dpnet_step('train_faceDP_dpnet', 256, 384)
+    ours = bench_support.captured_dpnet_step('train_faceDP_dpnet_photometric', 256, 384, views_only=True)
     tp, to = [], []
     for _ in range(args.rounds):
-        tp.append(timed(plain, args.reps))
-        to.append(timed(ours, args.reps))
+        tp.append(bench_support.timed(plain, args.reps))
+        to.append(bench_support.timed(ours, args.reps))
     mp, mo = statistics.median(tp), statistics.median(to)
     lines.append('smoothL1 %.4f ms (min %.4f, max %.4f) | photometric + smoothness %.4f ms (min %.4f, max %.4f) | %+.4f ms = %+.2f %% of the step'
                  % (mp, min(tp), max(tp), mo, min(to), max(to), mo - mp, 100.0 * (mo - mp) / mp))

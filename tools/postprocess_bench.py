@@ -25,6 +25,9 @@ import sys
 import torch
 import torch.nn.functional as F
 
+import bench_support
+from bench_support import fmt
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -56,46 +59,6 @@ def torch_bilateral(p, guide, r, ss, sc):
     w = ws * inside * torch.exp(-(F.unfold(I, k, padding=r) - I.reshape(B, 1, H * W)) ** 2 / (2 * sc * sc))
     den = w.sum(1)
     return torch.stack([(w * F.unfold(p[:, h:h + 1], k, padding=r)).sum(1) / den for h in range(n)], 1).reshape(B, n, H, W)
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def rounds_of(fns, reps, rounds):
-    for fn in fns:
-        timed(fn, 3)
-    times = [[] for _ in fns]
-    for _ in range(rounds):
-        for t, fn in zip(times, fns):
-            t.append(timed(fn, reps))
-    return times
-
-
-def replayed(fn, reps, rounds):
-    """`reps` calls captured into one graph on a side stream and replayed: the device time of a call without the host's enqueue."""
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        fn()
-    side.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
-        for _ in range(reps):
-            fn()
-    graph.replay()
-    torch.cuda.synchronize()
-    return [timed(graph.replay, 1) / reps for _ in range(rounds)]
-
-
-def fmt(t):
-    return '%.3f ms (min %.3f, max %.3f)' % (statistics.median(t), min(t), max(t))
 
 
 def accuracy_lines():
@@ -136,15 +99,15 @@ def forward_share(shape, reps, rounds):
             with torch.no_grad():
                 model.forward(batch)
         return fn
-    times = rounds_of((run(False, False), run(True, False), run(False, True)), reps, rounds)
+    times = bench_support.rounds_of((run(False, False), run(True, False), run(False, True)), reps, rounds)
     # the filters alone on this forward's own prediction and guide, as device time
     from dualpixelface_amd import ops
     run(False, False)()
     with torch.no_grad():
         raw = model.forward(batch)['pred_depth'].contiguous()
     guide = model._views(batch)[0]
-    alone = (replayed(lambda: ops.guided_filter(raw, guide, G_R, G_EPS), 20, rounds),
-             replayed(lambda: ops.joint_bilateral_filter(raw, guide, B_R, B_SS, B_SC), 20, rounds))
+    alone = (bench_support.replayed(lambda: ops.guided_filter(raw, guide, G_R, G_EPS), 20, rounds),
+             bench_support.replayed(lambda: ops.joint_bilateral_filter(raw, guide, B_R, B_SS, B_SC), 20, rounds))
     return times, alone, tuple(raw.shape)
 
 
@@ -187,8 +150,8 @@ def main():
         p, guide = p.cuda(), guide.cuda()
         tag = '%dx%dx%dx%d' % (B, n, H, W)
         guided = lambda: ops.guided_filter(p, guide, G_R, G_EPS)
-        tg, tt = rounds_of((guided, lambda: torch_guided(p, guide, G_R, G_EPS)), args.reps, args.rounds)
-        tr = replayed(guided, args.reps, args.rounds)
+        tg, tt = bench_support.rounds_of((guided, lambda: torch_guided(p, guide, G_R, G_EPS)), args.reps, args.rounds)
+        tr = bench_support.replayed(guided, args.reps, args.rounds)
         diff = float((guided() - torch_guided(p, guide, G_R, G_EPS)).abs().max())
         traffic = 16.0 * B * H * W + 32.0 * B * n * H * W
         mg = statistics.median(tr)
@@ -198,9 +161,9 @@ def main():
                         100.0 * traffic / (mg * 1e-3) / COPY_RATE, diff))
         print(lines[-1], flush=True)
         bilateral = lambda: ops.joint_bilateral_filter(p, guide, B_R, B_SS, B_SC)
-        tr = replayed(bilateral, args.reps, args.rounds)
+        tr = bench_support.replayed(bilateral, args.reps, args.rounds)
         try:
-            tb, tu = rounds_of((bilateral, lambda: torch_bilateral(p, guide, B_R, B_SS, B_SC)), max(1, args.reps // 5), args.rounds)
+            tb, tu = bench_support.rounds_of((bilateral, lambda: torch_bilateral(p, guide, B_R, B_SS, B_SC)), max(1, args.reps // 5), args.rounds)
             diff = float((bilateral() - torch_bilateral(p, guide, B_R, B_SS, B_SC)).abs().max())
             lines.append('%-14s bilateral hip, graph replay %s | hip, eager calls %s | torch unfold (%d x the image) %s | torch / hip replay '
                          '%.1fx | max diff to torch %.1e'

@@ -23,6 +23,9 @@ import sys
 import numpy as np
 import torch
 
+import bench_support
+from bench_support import fmt
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -103,46 +106,6 @@ def torch_mesh(pred, K, ab, mask, nmap, view, stride):
     return out
 
 
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def rounds_of(fns, reps, rounds):
-    for fn in fns:
-        timed(fn, 3)
-    times = [[] for _ in fns]
-    for _ in range(rounds):
-        for t, fn in zip(times, fns):
-            t.append(timed(fn, reps))
-    return times
-
-
-def replayed(fn, reps, rounds):
-    """`reps` calls captured into one graph on a side stream and replayed: the device time of a call without the host's enqueue."""
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        fn()
-    side.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
-        for _ in range(reps):
-            fn()
-    graph.replay()
-    torch.cuda.synchronize()
-    return [timed(graph.replay, 1) / reps for _ in range(rounds)]
-
-
-def fmt(t):
-    return '%.3f ms (min %.3f, max %.3f)' % (statistics.median(t), min(t), max(t))
-
-
 def operands(B, H, W, seed=3):
     from tests import reconstruct_cpu as rc
     sc = rc.scene(B, H, W, seed)
@@ -163,7 +126,7 @@ def forward_time(shape, reps, rounds):
     def fn():
         with torch.no_grad():
             model.forward(batch)
-    return rounds_of((fn,), reps, rounds)[0]
+    return bench_support.rounds_of((fn,), reps, rounds)[0]
 
 
 def main():
@@ -228,8 +191,8 @@ def main():
         rows.append(('all three s=%d' % args.stride, hip_all, torch_all, 0.0, max(1, args.reps // 5)))
         lines.append('%-11s hip against torch on this scene: %s' % (tag, agree))
         for name, hip, tor, traffic, reps in rows:
-            tr = replayed(hip, args.reps, args.rounds)
-            th, tt = rounds_of((hip, tor), reps, args.rounds)
+            tr = bench_support.replayed(hip, args.reps, args.rounds)
+            th, tt = bench_support.rounds_of((hip, tor), reps, args.rounds)
             m = statistics.median(tr)
             bw = '' if not traffic else ' | %.1f MB algorithmic = %.3f TB/s = %.1f %% of the copy rate' % (
                 traffic / 1e6, traffic / (m * 1e-3) / 1e12, 100.0 * traffic / (m * 1e-3) / COPY_RATE)
