@@ -4,6 +4,7 @@ PyTorch is plumbing here (device memory, the current HIP stream, the autograd ta
 step runs in the hand-written HIP kernels reached through the C ABI (include/dpf_hip.h).  No function in
 this file has a CPU or eager-PyTorch fallback: tensors must be fp32, contiguous and on the GPU.
 """
+import collections
 import ctypes
 import os
 
@@ -713,6 +714,100 @@ def _bn_stats(x, mode, running_mean, running_var, holder=None, sync=None):
     return mean, invstd, read_x
 
 
+# One normalised tensor, as both directions of a node need it.  The first _NORM_TENSORS fields are the tensors a node saves (any of them
+# None), the rest is plain data: view = (n, c, S) as the kernels see x (instance norm: (1, N * C, S)), training = the backward's flag,
+# dy_slice = (Ctot, c0) when the tensor is the channel slice [c0, c0 + c) of a concatenation, (0, 0) when it is dense.
+_Norm = collections.namedtuple('_Norm', 'x mean invstd weight bias slope res wmod view training act slope_const dy_slice')
+_NORM_TENSORS = 7
+# The outputs a backward call writes; None: not wanted.
+_NormGrads = collections.namedtuple('_NormGrads', 'dx dres dweight dbias dslope', defaults=(None,) * 5)
+
+
+def _norm_apply(x, mean, invstd, weight, bias, wmod, view, res=None, res2=None, slope=None, slope_const=0.0, act=ACT_NONE, into=None):
+    """y = act((x - mean) * invstd * weight + bias + res) + res2, THE dpf_norm_act_forward call.  into = (cat, Ctot, c0): y is the channel
+    slice [c0, c0 + c) of cat [N, Ctot, ...]; without it a new dense tensor.  -> y (cat in the slice form)."""
+    y, Ctot, c0 = into if into is not None else (torch.empty_like(x), 0, 0)
+    n, c, S = view
+    lib().call('dpf_norm_act_forward', _ptr(x), _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias), wmod, _ptr(res), _ptr(res2), act,
+               _ptr(slope), float(slope_const), _ptr(y), Ctot, c0, n, c, S, _stream())
+    return y
+
+
+def _norm_backward(r, dy, grads, ws, phase, count):
+    """THE dpf_norm_act_backward call for the record r: dy is read dense or as r.dy_slice of the concatenation's gradient, the outputs of
+    `grads` (_NormGrads) that are not None are written.  phase / ws / count as in include/dpf_hip.h: 0 everything (ws: 3c floats), 3 the
+    same on a ws that is zero already, 1 the local reductions into ws, 2 dx / dres from the summed ws (count -1: the global element
+    count is in ws[3c])."""
+    x, mean, invstd, weight, bias, slope, res, wmod, (n, c, S), training, act, slope_const, (Ctot, c0) = r
+    dx, dres, dweight, dbias, dslope = grads
+    lib().call('dpf_norm_act_backward', _ptr(x), _ptr(dy), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias), wmod, _ptr(res),
+               act, _ptr(slope), slope_const, training, _ptr(dx), _ptr(dres), _ptr(dweight), _ptr(dbias), _ptr(dslope), _ptr(ws), n, c, S,
+               phase, count, _stream())
+
+
+def _norm_backward_local(r, dy, grads):
+    """One branch of a concatenation without an exchange: phase 0 on the stream's scratch slab."""
+    _norm_backward(r, dy, grads, scratch(3 * r.view[1], r.x.device), 0, 0.0)
+
+
+def _norm_backward_sync(records, dy, grads, exchange):
+    """SyncBatchNorm backward of independent tensors (one, or the branches of a concatenation): the local reductions of every record go
+    into its [3c + 1] slice of ONE packed vector, whose last slot carries this rank's element count through the same all-reduce -- uneven
+    per-rank batches need no extra collective and no host synchronisation -- then dx with the global counts.  grads: per record its
+    _NormGrads.  The vector crosses a collective: a fresh tensor, not a scratch slab."""
+    offs, tot = [], 0
+    for r in records:
+        offs.append(tot)
+        tot += 3 * r.view[1] + 1
+    ws = torch.empty(tot, dtype=torch.float32, device=dy.device)
+    for r, g, off in zip(records, grads, offs):
+        n, c, S = r.view
+        _norm_backward(r, dy, g, ws[off:], 1, 0.0)
+        ws[off + 3 * c] = float(n) * float(S)
+    exchange.all_reduce_sum_(ws)
+    for r, g, off in zip(records, grads, offs):
+        _norm_backward(r, dy, g, ws[off:], 2, -1.0)
+
+
+def _bn_into_concat(cat, mode, act, branches, moments=None):
+    """Every branch's BatchNorm writes its channel slice of cat [N, sum C_i, ...].  branches: (x, weight, bias, running_mean, running_var,
+    stats holder or None) each; moments: per branch its entry of _bn_sync_gather.  -> the branches' records."""
+    N, Ctot = cat.shape[0], cat.shape[1]
+    records, c0 = [], 0
+    for i, (x, w, b, rm, rv, holder) in enumerate(branches):
+        C = x.shape[1]
+        view = (N, C, x.numel() // (N * C))
+        mean, invstd, _ = _bn_stats(x, mode, rm, rv, holder, moments[i] if moments else None)
+        _norm_apply(x, mean, invstd, w, b, C, view, act=act, into=(cat, Ctot, c0))
+        records.append(_Norm(x, mean, invstd, w, b, None, None, C, view, 1 if mode == 1 else 0, act, 0.0, (Ctot, c0)))
+        c0 += C
+    return records
+
+
+def _save_norms(ctx, records, *first):
+    """ctx keeps `first` and the records' tensors as saved tensors, the records' plain fields beside them."""
+    for r in records:
+        first += r[:_NORM_TENSORS]
+    ctx.save_for_backward(*first)
+    ctx.norm_fields = [r[_NORM_TENSORS:] for r in records]
+
+
+def _saved_norms(ctx):
+    """-> (the `first` of _save_norms, the records), from one read of saved_tensors."""
+    sv, fields = ctx.saved_tensors, ctx.norm_fields
+    k = len(sv) - _NORM_TENSORS * len(fields)
+    return sv[:k], [_Norm._make(sv[k + _NORM_TENSORS * i:k + _NORM_TENSORS * (i + 1)] + f) for i, f in enumerate(fields)]
+
+
+def _groups(seq, k):
+    return [seq[i:i + k] for i in range(0, len(seq), k)]
+
+
+def _like(t, wanted):
+    """An output the finalize kernel writes (not accumulates): no zero fill."""
+    return torch.empty_like(t) if (t is not None and wanted) else None
+
+
 class NormActFn(torch.autograd.Function):
     """y = act(norm(x) * w + b + res) + res2 with norm = batch norm (training/eval) or instance norm, or no norm."""
 
@@ -726,55 +821,42 @@ class NormActFn(torch.autograd.Function):
         _need(x, weight, bias, slope, res, res2)
         N, C = x.shape[0], x.shape[1]
         S = x.numel() // (N * C)
-        L = lib()
-        n_, c_ = (1, N * C) if mode == 3 else (N, C)
-        wmod = C
+        view = (1, N * C, S) if mode == 3 else (N, C, S)
         sync = exchange if mode == 1 else None
         with _detail('naf') as timer:
             moments = _bn_sync_gather([x], sync)[0] if sync is not None else None
             mean, invstd, read_x = _bn_stats(x, mode, running_mean, running_var, stats, moments)
             # algorithmic bytes: statistics pass (unless the conv epilogue made them) + apply (x and residuals in, y out)
             timer.nbytes = 4.0 * x.numel() * (read_x + 2 + (res is not None) + (res2 is not None))
-            y = torch.empty_like(x)
-            L.call('dpf_norm_act_forward', _ptr(x), _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias), wmod, _ptr(res), _ptr(res2), act,
-                   _ptr(slope), float(slope_const), _ptr(y), 0, 0, n_, c_, S, _stream())
-        ctx.save_for_backward(x, weight, bias, slope, res, mean, invstd)
-        ctx.cfg = (mode, act, float(slope_const), n_, c_, S, wmod, res2 is not None)
+            y = _norm_apply(x, mean, invstd, weight, bias, C, view, res=res, res2=res2, slope=slope, slope_const=slope_const, act=act)
+        r = _Norm(x, mean, invstd, weight, bias, slope, res, C, view, 1 if mode in (1, 3) else 0, act, float(slope_const), (0, 0))
+        # one record, saved and rebuilt in place: the list form (_save_norms / _saved_norms) costs this node, the one behind most of the
+        # step's norm launches, 2 us of Python each way
+        ctx.save_for_backward(*r[:_NORM_TENSORS])
+        ctx.norm_fields = r[_NORM_TENSORS:]
+        ctx.has_res2 = res2 is not None
         ctx.exchange = sync
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        x, weight, bias, slope, res, mean, invstd = ctx.saved_tensors
-        mode, act, slope_const, n_, c_, S, wmod, has_res2 = ctx.cfg
+        r = _Norm._make(ctx.saved_tensors + ctx.norm_fields)
         gy = _c(gy)
-        L = lib()
-        need_dx = ctx.needs_input_grad[0]
-        dx = torch.empty_like(x) if need_dx else None
-        dres = torch.empty_like(x) if (res is not None and ctx.needs_input_grad[4]) else None
-        # written (not accumulated) by the finalize kernel: no zero fill
-        dweight = torch.empty_like(weight) if (weight is not None and ctx.needs_input_grad[1]) else None
-        dbias = torch.empty_like(bias) if (bias is not None and ctx.needs_input_grad[2]) else None
-        dslope = torch.empty_like(slope) if (slope is not None and ctx.needs_input_grad[3]) else None
-        training = 1 if mode in (1, 3) else 0
-        args = (_ptr(x), _ptr(gy), 0, 0, _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias), wmod, _ptr(res), act, _ptr(slope), slope_const,
-                training, _ptr(dx), _ptr(dres), _ptr(dweight), _ptr(dbias), _ptr(dslope))
+        need = ctx.needs_input_grad
+        x, weight, bias, slope = r.x, r.weight, r.bias, r.slope
+        g = _NormGrads(torch.empty_like(x) if need[0] else None,
+                       torch.empty_like(x) if (r.res is not None and need[4]) else None,
+                       torch.empty_like(weight) if (weight is not None and need[1]) else None,
+                       torch.empty_like(bias) if (bias is not None and need[2]) else None,
+                       torch.empty_like(slope) if (slope is not None and need[3]) else None)
         # algorithmic bytes: reduce pass (x, gy) when the norm trains + apply pass (x, gy in; dx, dres out)
-        with _detail('nab', 4.0 * x.numel() * ((2 if training else 0) + 2 + (dx is not None) + (dres is not None))):
+        with _detail('nab', 4.0 * x.numel() * ((2 if r.training else 0) + 2 + (g.dx is not None) + (g.dres is not None))):
             if ctx.exchange is not None:
-                # SyncBatchNorm: local reductions, sum over the ranks, then dx with the global element count
-                # ws[3C] carries this rank's element count through the same all-reduce: uneven per-rank batches need no extra
-                # collective and no host synchronisation
-                ws = torch.empty(3 * c_ + 1, dtype=torch.float32, device=x.device)
-                L.call('dpf_norm_act_backward', *args, _ptr(ws), n_, c_, S, 1, 0.0, _stream())
-                ws[3 * c_:].fill_(float(n_) * float(S))
-                ctx.exchange.all_reduce_sum_(ws)
-                L.call('dpf_norm_act_backward', *args, _ptr(ws), n_, c_, S, 2, -1.0, _stream())
+                _norm_backward_sync([r], gy, [g], ctx.exchange)
             else:
-                ws = zero_slot(3 * c_, x.device)                               # pre-zeroed: phase 3 skips the per-layer memset
-                L.call('dpf_norm_act_backward', *args, _ptr(ws), n_, c_, S, 3, 0.0, _stream())
-        dres2 = gy if (has_res2 and ctx.needs_input_grad[5]) else None
-        return dx, dweight, dbias, dslope, dres, dres2, None, None, None, None, None, None, None
+                _norm_backward(r, gy, g, zero_slot(3 * r.view[1], x.device), 3, 0.0)      # pre-zeroed: phase 3 skips the per-layer memset
+        dres2 = gy if (ctx.has_res2 and need[5]) else None
+        return g.dx, g.dweight, g.dbias, g.dslope, g.dres, dres2, None, None, None, None, None, None, None
 
 
 def norm_act(x, weight=None, bias=None, slope=None, res=None, res2=None, running_mean=None, running_var=None, mode=0, act=ACT_NONE,
@@ -788,82 +870,34 @@ class NormActCatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mode, act, holders, exchange, *tensors):
-        n = len(tensors) // 5
-        xs = [_c(tensors[5 * i]) for i in range(n)]
-        ws = [tensors[5 * i + 1] for i in range(n)]
-        bs = [tensors[5 * i + 2] for i in range(n)]
-        rms = [tensors[5 * i + 3] for i in range(n)]
-        rvs = [tensors[5 * i + 4] for i in range(n)]
+        branches = [(_c(x), w, b, rm, rv) for x, w, b, rm, rv in _groups(tensors, 5)]
+        xs = [br[0] for br in branches]
         _need(*xs)
-        N = xs[0].shape[0]
-        Cs = [x.shape[1] for x in xs]
-        S = xs[0].numel() // (N * Cs[0])
-        Ctot = sum(Cs)
-        cat = torch.empty((N, Ctot) + tuple(xs[0].shape[2:]), dtype=torch.float32, device=xs[0].device)
-        L = lib()
-        saved, c0 = [], 0
+        cat = torch.empty((xs[0].shape[0], sum(x.shape[1] for x in xs)) + tuple(xs[0].shape[2:]), dtype=torch.float32, device=xs[0].device)
         sync = exchange if mode == 1 else None
         with _detail('ncf', 4.0 * sum(x.numel() for x in xs) * 2):
-            moments = _bn_sync_gather(xs, sync) if sync is not None else [None] * n
-            for i in range(n):
-                x, C = xs[i], Cs[i]
-                mean, invstd, _ = _bn_stats(x, mode, rms[i], rvs[i], holders[i] if holders else None, moments[i])
-                L.call('dpf_norm_act_forward', _ptr(x), _ptr(mean), _ptr(invstd), _ptr(ws[i]), _ptr(bs[i]), C, None, None, act, None, 0.0,
-                       _ptr(cat), Ctot, c0, N, C, S, _stream())
-                saved += [x, ws[i], bs[i], mean, invstd]
-                c0 += C
-        ctx.save_for_backward(*saved)
-        ctx.cfg = (mode, act, n, N, tuple(Cs), S, Ctot)
+            moments = _bn_sync_gather(xs, sync) if sync is not None else None
+            records = _bn_into_concat(cat, mode, act, [br + (h,) for br, h in zip(branches, holders or [None] * len(xs))], moments)
+        _save_norms(ctx, records)
         ctx.exchange = sync
         return cat
 
     @staticmethod
     def backward(ctx, gcat):
-        mode, act, n, N, Cs, S, Ctot = ctx.cfg
+        _, records = _saved_norms(ctx)
         gcat = _c(gcat)
-        sv = ctx.saved_tensors
-        L = lib()
-        grads, c0 = [], 0
         with _detail('ncb', 4.0 * gcat.numel() * 5):
-            outs = []
-            for i in range(n):
-                x, w, b, mean, invstd = sv[5 * i:5 * i + 5]
-                outs.append((torch.empty_like(x) if ctx.needs_input_grad[4 + 5 * i] else None,
-                             torch.empty_like(w) if ctx.needs_input_grad[4 + 5 * i + 1] else None,
-                             torch.empty_like(b) if ctx.needs_input_grad[4 + 5 * i + 2] else None))
+            grads = [_NormGrads(dx=_like(r.x, nx), dweight=_like(r.weight, nw), dbias=_like(r.bias, nb))
+                     for r, (nx, nw, nb, _, _) in zip(records, _groups(ctx.needs_input_grad[4:], 5))]
             if ctx.exchange is not None:
-                # SyncBatchNorm: local reductions of every branch, ONE all-reduce of the packed [3 C_i + 1] vectors (the last slot of each
-                # carries this rank's element count), then dx with the global counts
-                offs, tot = [], 0
-                for C in Cs:
-                    offs.append(tot)
-                    tot += 3 * C + 1
-                ws_all = torch.empty(tot, dtype=torch.float32, device=gcat.device)
-                for phase in (1, 2):
-                    c0 = 0
-                    for i in range(n):
-                        x, w, b, mean, invstd = sv[5 * i:5 * i + 5]
-                        dx, dw, db = outs[i]
-                        L.call('dpf_norm_act_backward', _ptr(x), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(w), _ptr(b), Cs[i], None,
-                               act, None, 0.0, 1, _ptr(dx), None, _ptr(dw), _ptr(db), None, _ptr(ws_all[offs[i]:]), N, Cs[i], S, phase,
-                               0.0 if phase == 1 else -1.0, _stream())
-                        if phase == 1:
-                            ws_all[offs[i] + 3 * Cs[i]] = float(N) * float(S)
-                        c0 += Cs[i]
-                    if phase == 1:
-                        ctx.exchange.all_reduce_sum_(ws_all)
+                _norm_backward_sync(records, gcat, grads, ctx.exchange)
             else:
-                for i in range(n):
-                    x, w, b, mean, invstd = sv[5 * i:5 * i + 5]
-                    C = Cs[i]
-                    dx, dw, db = outs[i]
-                    wsb = scratch(3 * C, x.device)
-                    L.call('dpf_norm_act_backward', _ptr(x), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(w), _ptr(b), C, None, act,
-                           None, 0.0, 1 if mode == 1 else 0, _ptr(dx), None, _ptr(dw), _ptr(db), None, _ptr(wsb), N, C, S, 0, 0.0, _stream())
-                    c0 += C
-            for dx, dw, db in outs:
-                grads += [dx, dw, db, None, None]
-        return (None, None, None, None) + tuple(grads)
+                for r, g in zip(records, grads):
+                    _norm_backward_local(r, gcat, g)
+        flat = []
+        for g in grads:
+            flat += [g.dx, g.dweight, g.dbias, None, None]
+        return (None, None, None, None) + tuple(flat)
 
 
 def _conv_transpose_acc(x, w, out, ksize, stride, pad, dil):
@@ -888,59 +922,35 @@ class ConvBnCatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mode, dils, x, *params):
-        n = len(dils)
         x = _c(x)
         _need(x)
         x5 = x.unsqueeze(2)
-        N = x.shape[0]
-        L = lib()
-        ys, saved, Cs = [], [], []
-        for i in range(n):
-            w, bw, bb, rm, rv = params[5 * i:5 * i + 5]
-            d = dils[i]
+        branches = []
+        for d, (w, bw, bb, rm, rv) in zip(dils, _groups(params, 5)):
             st = {} if mode == 1 else None
-            ys.append(_conv_fwd_raw(x5, _c(w).unsqueeze(2), None, (1, 1, 1), (0, d, d), (1, d, d), st))
-            Cs.append(w.shape[0])
-            saved.append(st)
-        S = ys[0].numel() // (N * Cs[0])
-        Ctot = sum(Cs)
-        cat = torch.empty((N, Ctot) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
-        keep, c0 = [x], 0
-        for i in range(n):
-            w, bw, bb, rm, rv = params[5 * i:5 * i + 5]
-            y, C, st = ys[i], Cs[i], saved[i]
-            mean, invstd, _ = _bn_stats(y, mode, rm, rv, st)
-            L.call('dpf_norm_act_forward', _ptr(y), _ptr(mean), _ptr(invstd), _ptr(bw), _ptr(bb), C, None, None, ACT_NONE, None, 0.0,
-                   _ptr(cat), Ctot, c0, N, C, S, _stream())
-            keep += [w, y, bw, bb, mean, invstd]
-            c0 += C
-        ctx.save_for_backward(*keep)
-        ctx.cfg = (mode, tuple(dils), n, N, tuple(Cs), S, Ctot)
+            y = _conv_fwd_raw(x5, _c(w).unsqueeze(2), None, (1, 1, 1), (0, d, d), (1, d, d), st)
+            branches.append((y, bw, bb, rm, rv, st))
+        cat = torch.empty((x.shape[0], sum(br[0].shape[1] for br in branches)) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+        _save_norms(ctx, _bn_into_concat(cat, mode, ACT_NONE, branches), x, *params[0::5])
+        ctx.dils = tuple(dils)
         return cat
 
     @staticmethod
     def backward(ctx, gcat):
-        mode, dils, n, N, Cs, S, Ctot = ctx.cfg
+        (x, *ws), records = _saved_norms(ctx)
         gcat = _c(gcat)
-        sv = ctx.saved_tensors
-        x = sv[0]
         x5 = x.unsqueeze(2)
-        L = lib()
         need_dx = ctx.needs_input_grad[2]
         dx5 = None
-        grads, c0 = [], 0
-        for i in range(n):
-            w, y, bw, bb, mean, invstd = sv[1 + 6 * i:7 + 6 * i]
-            C, d = Cs[i], dils[i]
-            dy = torch.empty_like(y)
-            dbw = torch.empty_like(bw) if ctx.needs_input_grad[3 + 5 * i + 1] else None
-            dbb = torch.empty_like(bb) if ctx.needs_input_grad[3 + 5 * i + 2] else None
-            wsb = scratch(3 * C, x.device)
-            L.call('dpf_norm_act_backward', _ptr(y), _ptr(gcat), Ctot, c0, _ptr(mean), _ptr(invstd), _ptr(bw), _ptr(bb), C, None, ACT_NONE,
-                   None, 0.0, 1 if mode == 1 else 0, _ptr(dy), None, _ptr(dbw), _ptr(dbb), None, _ptr(wsb), N, C, S, 0, 0.0, _stream())
+        grads = []
+        for r, w, d, (nw, nbw, nbb, _, _) in zip(records, ws, ctx.dils, _groups(ctx.needs_input_grad[3:], 5)):
+            dy = torch.empty_like(r.x)
+            dbw, dbb = _like(r.weight, nbw), _like(r.bias, nbb)
+            _norm_backward_local(r, gcat, _NormGrads(dx=dy, dweight=dbw, dbias=dbb))
+            # the weight gradient in line, on the main stream's slab: not deferred to the side stream
             w5 = w.unsqueeze(2)
             gw = None
-            if ctx.needs_input_grad[3 + 5 * i]:
+            if nw:
                 gw = _conv_wgrad_raw(dy, x5, w5.shape, (1, 1, 1), (0, d, d), (1, d, d)).squeeze(2)
             if need_dx:
                 if dx5 is None:
@@ -948,7 +958,6 @@ class ConvBnCatFn(torch.autograd.Function):
                 else:
                     _conv_transpose_acc(dy, w5, dx5, w5.shape[2:], (1, 1, 1), (0, d, d), (1, d, d))
             grads += [gw, dbw, dbb, None, None]
-            c0 += C
         return (None, None, dx5.squeeze(2) if dx5 is not None else None) + tuple(grads)
 
 

@@ -97,6 +97,77 @@ def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# ---- stand-ins around the operator layer
+class TwoRankExchange(object):
+    """Stands in for distributed.StatExchange on a one-GPU box: plays the other rank of a 2-rank SyncBatchNorm with plain torch math, so
+    the local kernels + merge / phase-2 kernels can be checked against full-batch batch norm.  One tensor, or a list per argument for the
+    branches of a norm_act_concat: the other rank's slices are packed as the operator packs its own ([2C+1] per branch in the gather,
+    [3C+1] in the reduce).  log: every collective appends its name (a list of the caller's, to interleave them with other records)."""
+    world_size = 2
+
+    def __init__(self, x1, dz1, mean_g, invstd_g, log=None):
+        listed = lambda v: list(v) if isinstance(v, (list, tuple)) else [v]
+        self.branches = list(zip(listed(x1), listed(dz1), listed(mean_g), listed(invstd_g)))
+        self.log = [] if log is None else log
+
+    @staticmethod
+    def _dims(x1):
+        return [0] + list(range(2, x1.dim())), [1, -1] + [1] * (x1.dim() - 2), x1.numel() // x1.shape[1]
+
+    def all_gather(self, packed):
+        self.log.append('all_gather')
+        parts = []
+        for x1, _, _, _ in self.branches:
+            dims, bshape, count1 = self._dims(x1)
+            m1 = x1.mean(dims)
+            M2 = ((x1 - m1.view(bshape)) ** 2).sum(dims)
+            parts += [torch.stack([m1, M2], 1).reshape(-1), torch.tensor([float(count1)], device=packed.device)]
+        other = torch.cat(parts)
+        assert other.shape == packed.shape, (other.shape, packed.shape)
+        return torch.stack([packed, other.to(packed.dtype)])
+
+    def all_reduce_sum_(self, ws):
+        self.log.append('all_reduce_sum_')
+        off = 0
+        for x1, dz1, mean_g, invstd_g in self.branches:
+            dims, bshape, count1 = self._dims(x1)
+            xh = (x1 - mean_g.view(bshape)) * invstd_g.view(bshape)
+            C = x1.shape[1]
+            v = ws[off:off + 3 * C].view(-1, 3)
+            v[:, 0] += dz1.sum(dims)
+            v[:, 1] += (dz1 * xh).sum(dims)
+            ws[off + 3 * C] += float(count1)           # the other rank's element count rides in the slice's last slot
+            off += 3 * C + 1
+        assert off == ws.numel(), (off, ws.numel())
+        return ws
+
+
+class CallRecorder(object):
+    """Stands around the ctypes library of dualpixelface_amd._lib: every dpf_* entry reached through it -- lib().call and the direct
+    lib().cdll.NAME(...) alike -- leaves (name, args) in `calls` and then runs.  record_calls() puts one in place."""
+
+    def __init__(self, cdll):
+        self.cdll, self.calls = cdll, []
+
+    def __getattr__(self, name):
+        fn = getattr(self.cdll, name)
+        if not name.startswith('dpf_'):
+            return fn
+
+        def recorded(*args):
+            self.calls.append((name, args))
+            return fn(*args)
+        return recorded
+
+
+def record_calls(monkeypatch):
+    """A CallRecorder around the loaded library until the test ends."""
+    L = ops().lib()
+    rec = CallRecorder(L.cdll)
+    monkeypatch.setattr(L, 'cdll', rec)
+    return rec
+
+
 # ---- options and models
 def option(config=None, **over):
     """load_option(config, **over): the overrides are merged into the model block before the Option is built."""

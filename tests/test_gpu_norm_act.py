@@ -1,6 +1,7 @@
 """csrc/norm_act.hip on the GPU (run with ``-m gpu``) against the closed-form fp64 reference tests/norm_act_cpu.py: rows longer than one
 chunk, ragged tails, the scalar path, every operand / output subset, the pre-zeroed arena after it wrapped, and inputs whose statistics
-are hard in fp32.  x is passed as [N, C, S] so that S is free.
+are hard in fp32.  x is passed as [N, C, S] so that S is free.  Sections 6 and 7 are about the operator layer above the kernels: the
+multi-branch SyncBatchNorm exchange of norm_act_concat, and the C entries every path of the three normalisation nodes reaches.
 
 Bars, the ones test_gpu_ops.py uses for these kernels: forward and running statistics 1e-5 of the scale, gradients 2e-4 -- applied per
 channel (every [:, c] slice, every element of dw / db), so that one large channel cannot hide a wrong small one."""
@@ -12,8 +13,8 @@ import torch.nn.functional as F
 
 from tests import norm_act_cpu as na
 from tests import support
-from tests.support import DEV, rnd
-from tests.test_gpu_ops import _TwoRankExchange
+from tests.support import DEV, close, rnd
+from tests.support import TwoRankExchange as _TwoRankExchange
 
 pytestmark = pytest.mark.gpu
 
@@ -404,3 +405,161 @@ def test_conv_epilogue_statistics_under_an_offset():
     for name, a, v in (('y', z, z_t), ('running_mean', rm, rm_t), ('running_var', rv, rv_t)):
         err, scale = na.channel_errors(v, ref[name])
         na.close_channels(a, ref[name], FWD, 'conv epilogue ' + name, bars=4.0 * err / scale.clamp(min=1e-6))
+
+
+# ---- 6. SyncBatchNorm over the branches of a concatenation
+SYNC_CAT = (8, 5, 16)
+
+
+@functools.lru_cache(maxsize=None)
+def _sync_concat_case():
+    """Branch widths (8, 5, 16), 5 samples of 12 x 20, operands as in test_gpu_ops.py::test_norm_act_concat_matches_separate_norm_and_cat.
+    The reference is torch.cat of F.batch_norm over all 5 samples on the CPU with autograd.  Built once, never modified."""
+    H, W = 12, 20
+    xs = [rnd(5, C, H, W, seed=100 + i).requires_grad_() for i, C in enumerate(SYNC_CAT)]
+    ws = [(rnd(C, seed=110 + i).abs() + 0.5).requires_grad_() for i, C in enumerate(SYNC_CAT)]
+    bs = [rnd(C, seed=120 + i).requires_grad_() for i, C in enumerate(SYNC_CAT)]
+    rms = [rnd(C, seed=130 + i) * 0.1 for i, C in enumerate(SYNC_CAT)]
+    rvs = [rnd(C, seed=140 + i).abs() + 0.5 for i, C in enumerate(SYNC_CAT)]
+    rms_r, rvs_r = [t.clone() for t in rms], [t.clone() for t in rvs]
+    y = torch.cat([F.batch_norm(x, rm, rv, w, b, True, 0.1, 1e-5) for x, w, b, rm, rv in zip(xs, ws, bs, rms_r, rvs_r)], 1)
+    go = rnd(*y.shape, seed=150)
+    dxs = torch.autograd.grad(y, xs, go)
+    case = {'x': [x.detach() for x in xs], 'w': [w.detach() for w in ws], 'b': [b.detach() for b in bs], 'rm': rms, 'rv': rvs, 'go': go,
+            'y': y.detach(), 'dx': dxs, 'running_mean': rms_r, 'running_var': rvs_r, 'dz': [], 'mean': [], 'invstd': [], 'dw': [], 'db': []}
+    c0 = 0
+    for x, C in zip(case['x'], SYNC_CAT):
+        dz = go[:, c0:c0 + C]                                          # no activation: dz is the upstream gradient's slice
+        mean = x.mean((0, 2, 3))
+        invstd = 1.0 / torch.sqrt(x.var((0, 2, 3), unbiased=False) + 1e-5)
+        xh = (x - mean.view(1, C, 1, 1)) * invstd.view(1, C, 1, 1)
+        case['dz'].append(dz)
+        case['mean'].append(mean)
+        case['invstd'].append(invstd)
+        case['dw'].append((dz * xh)[:2].sum((0, 2, 3)))               # this rank's partial sums (DDP averages them afterwards)
+        case['db'].append(dz[:2].sum((0, 2, 3)))
+        c0 += C
+    return case
+
+
+@pytest.mark.parametrize('det', [False, True], ids=['default', 'deterministic'])
+def test_sync_batchnorm_concat_matches_full_batch(det):
+    """norm_act_concat, mode 1, no activation, with the two-rank emulation: rank 0 holds 2 samples, the emulated rank 1 three more.  Three
+    unequal widths put the gather slices [2C+1] at offsets 0, 17, 28 and the reduce slices [3C+1] at 0, 25, 41, so a swapped offset or a
+    wrong count slot shows.  Output, the six running statistics and dx of the local samples against batch norm over all 5 samples, dw / db
+    against this rank's partial sums; bars of the two tests this combines (forward and running statistics 1e-5, gradients 2e-4), and
+    the branches travel in ONE all-gather and ONE all-reduce."""
+    ops = support.ops()
+    t = _sync_concat_case()
+    ex = _TwoRankExchange([x[2:].to(DEV) for x in t['x']], [dz[2:].to(DEV) for dz in t['dz']], [m.to(DEV) for m in t['mean']],
+                          [s.to(DEV) for s in t['invstd']])
+    xs, ws, bs = [[v[:2].to(DEV).requires_grad_() for v in t['x']]] + [[v.to(DEV).requires_grad_() for v in t[k]] for k in ('w', 'b')]
+    rms, rvs = [[v.to(DEV) for v in t[k]] for k in ('rm', 'rv')]
+    with ops.deterministic_mode(det):
+        out = ops.norm_act_concat([(x, w, b, rm, rv, None) for x, w, b, rm, rv in zip(xs, ws, bs, rms, rvs)], 1, ops.ACT_NONE, exchange=ex)
+        gg = torch.autograd.grad(out, xs + ws + bs, t['go'][:2].to(DEV))
+    torch.cuda.synchronize()
+    close(out, t['y'][:2], FWD, 'sync concat y')
+    for i in range(3):
+        close(rms[i], t['running_mean'][i], FWD, 'sync concat running_mean branch %d' % i)
+        close(rvs[i], t['running_var'][i], FWD, 'sync concat running_var branch %d' % i)
+        close(gg[i], t['dx'][i][:2], GRAD, 'sync concat dx branch %d' % i)
+        close(gg[3 + i], t['dw'][i], GRAD, 'sync concat dw (local part) branch %d' % i)
+        close(gg[6 + i], t['db'][i], GRAD, 'sync concat db (local part) branch %d' % i)
+    assert ex.log == ['all_gather', 'all_reduce_sum_'], ex.log
+
+
+# ---- 7. the launch protocol of every path
+FWD_ENTRY, BWD_ENTRY = 'dpf_norm_act_forward', 'dpf_norm_act_backward'
+
+
+def _entries(ops, rec):
+    """What the recorder holds, as names: 'dpf_norm_act_backward <phase>' for the backward, the collective's name for an exchange; cleared."""
+    phase = [n for _, n in ops.lib().protos[BWD_ENTRY][1]].index('phase')
+    out = [c if isinstance(c, str) else (c[0] if c[0] != BWD_ENTRY else '%s %d' % (BWD_ENTRY, c[1][phase])) for c in rec.calls]
+    del rec.calls[:]
+    return out
+
+
+def _protocol_single(ops, rec, mode, exchange):
+    N, C, H, W = 2, 5, 6, 8
+    x, w, b = [v.to(DEV).requires_grad_() for v in (rnd(N, C, H, W, seed=1) + 0.7, rnd(C, seed=2).abs() + 0.5, rnd(C, seed=3))]
+    rm, rv = (torch.zeros(C, device=DEV), torch.ones(C, device=DEV)) if mode in (1, 2) else (None, None)
+    ex = None
+    if exchange:
+        ex = _TwoRankExchange(rnd(3, C, H, W, seed=4).to(DEV), rnd(3, C, H, W, seed=5).to(DEV), torch.zeros(C, device=DEV),
+                              torch.ones(C, device=DEV), log=rec.calls)
+    if mode == 0:
+        w = b = None
+    del rec.calls[:]
+    y = ops.norm_act(x, w, b, None, None, None, rm, rv, mode, ops.ACT_RELU, exchange=ex)
+    fwd = _entries(ops, rec)
+    torch.autograd.grad(y, [v for v in (x, w, b) if v is not None], torch.ones_like(y))
+    return fwd, _entries(ops, rec)
+
+
+def _protocol_concat(ops, rec, exchange):
+    N, H, W = 2, 6, 8
+    dev = lambda v: v.to(DEV).requires_grad_()
+    br = [(dev(rnd(N, C, H, W, seed=10 + i)), dev(rnd(C, seed=20 + i).abs() + 0.5), dev(rnd(C, seed=30 + i)), torch.zeros(C, device=DEV),
+           torch.ones(C, device=DEV), None) for i, C in enumerate(SYNC_CAT)]
+    ex = None
+    if exchange:
+        ex = _TwoRankExchange([rnd(3, C, H, W, seed=40 + i).to(DEV) for i, C in enumerate(SYNC_CAT)],
+                              [rnd(3, C, H, W, seed=50 + i).to(DEV) for i, C in enumerate(SYNC_CAT)],
+                              [torch.zeros(C, device=DEV) for C in SYNC_CAT], [torch.ones(C, device=DEV) for C in SYNC_CAT], log=rec.calls)
+    del rec.calls[:]
+    y = ops.norm_act_concat(br, 1, ops.ACT_NONE, exchange=ex)
+    fwd = _entries(ops, rec)
+    torch.autograd.grad(y, [v for b in br for v in b[:3]], torch.ones_like(y))
+    return fwd, _entries(ops, rec)
+
+
+def _protocol_conv_bn_concat(ops, rec):
+    N, C, H, W = 2, 8, 20, 36
+    dev = lambda v: v.to(DEV).requires_grad_()
+    x = dev(rnd(N, C, H, W, seed=200))
+    br = [(dev(rnd(C, C, 3, 3, seed=201 + i) * 0.2), dev(rnd(C, seed=210 + i).abs() + 0.5), dev(rnd(C, seed=220 + i)),
+           torch.zeros(C, device=DEV), torch.ones(C, device=DEV)) for i in range(3)]
+    del rec.calls[:]
+    y = ops.conv_bn_concat(x, br, (1, 3, 5), True)
+    fwd = _entries(ops, rec)
+    torch.autograd.grad(y, [x] + [v for b in br for v in b[:3]], torch.ones_like(y))
+    return fwd, _entries(ops, rec)
+
+
+# the dense convolutions ask the library for their workspace sizes before every launch: C entries too, so they are part of the record
+_CONV = ['dpf_conv_workspace_floats', 'dpf_conv_stats_slab_doubles', 'dpf_conv_forward_stats']
+_WGRAD = ['dpf_conv_wgrad_workspace_floats', 'dpf_conv_wgrad_ws']
+_DGRAD = ['dpf_conv_workspace_floats', 'dpf_conv_transpose']
+PROTOCOL = {
+    # path: (run, entries of the forward, entries of the backward)
+    'single mode 0': (lambda o, r: _protocol_single(o, r, 0, False), [FWD_ENTRY], [BWD_ENTRY + ' 3']),
+    'single mode 1': (lambda o, r: _protocol_single(o, r, 1, False), ['dpf_bn_stats', FWD_ENTRY], [BWD_ENTRY + ' 3']),
+    'single mode 2': (lambda o, r: _protocol_single(o, r, 2, False), ['dpf_bn_eval_stats', FWD_ENTRY], [BWD_ENTRY + ' 3']),
+    'single mode 3': (lambda o, r: _protocol_single(o, r, 3, False), ['dpf_bn_stats', FWD_ENTRY], [BWD_ENTRY + ' 3']),
+    'single mode 1 exchange': (lambda o, r: _protocol_single(o, r, 1, True),
+                               ['dpf_bn_local_moments', 'all_gather', 'dpf_bn_merge_moments', FWD_ENTRY],
+                               [BWD_ENTRY + ' 1', 'all_reduce_sum_', BWD_ENTRY + ' 2']),
+    'concat': (lambda o, r: _protocol_concat(o, r, False), ['dpf_bn_stats', FWD_ENTRY] * 3, [BWD_ENTRY + ' 0'] * 3),
+    'concat exchange': (lambda o, r: _protocol_concat(o, r, True),
+                        ['dpf_bn_local_moments'] * 3 + ['all_gather'] + ['dpf_bn_merge_moments', FWD_ENTRY] * 3,
+                        [BWD_ENTRY + ' 1'] * 3 + ['all_reduce_sum_'] + [BWD_ENTRY + ' 2'] * 3),
+    'conv_bn_concat': (_protocol_conv_bn_concat, _CONV * 3 + ['dpf_bn_finalize_partials', FWD_ENTRY] * 3,
+                       ([BWD_ENTRY + ' 0'] + _WGRAD + _DGRAD) * 3),
+}
+
+
+@pytest.mark.parametrize('path', sorted(PROTOCOL))
+def test_launch_protocol(path, monkeypatch):
+    """The C entries every path of the three normalisation nodes reaches (lib().call and the direct cdll route alike, recorded around the
+    library object), with the backward's phase and the collectives of an exchange in their places: literals, read off a run."""
+    ops = support.ops()
+    rec = support.record_calls(monkeypatch)
+    run, fwd, bwd = PROTOCOL[path]
+    got = run(ops, rec)
+    torch.cuda.synchronize()
+    print('%s forward: %r' % (path, got[0]))
+    print('%s backward: %r' % (path, got[1]))
+    assert got[0] == fwd, (path, got[0])
+    assert got[1] == bwd, (path, got[1])

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 from tests import support
 from tests.support import DEV, close, close_elem, rnd
+from tests.support import TwoRankExchange as _TwoRankExchange
 
 pytestmark = pytest.mark.gpu
 
@@ -152,35 +153,6 @@ def test_batchnorm_train(act, shape):
     grads = torch.autograd.grad(y, (xg, wg, bg, rg, r2g) + ((sg,) if act == 'prelu' else ()), go.to(DEV))
     for g, gr, nm in zip(grads, grads_r, ('dx', 'dw', 'db', 'dres', 'dres2', 'dslope')):
         close(g, gr, 2e-4, 'bn ' + nm)
-
-
-class _TwoRankExchange(object):
-    """Stands in for distributed.StatExchange on a one-GPU box: plays the other rank of a 2-rank SyncBatchNorm with plain
-    torch math, so the local kernels + merge / phase-2 kernels can be checked against full-batch batch norm."""
-    world_size = 2
-
-    def __init__(self, x1, dz1, mean_g, invstd_g):
-        self.x1, self.dz1, self.mean_g, self.invstd_g = x1, dz1, mean_g, invstd_g
-        C = x1.shape[1]
-        self.dims = [0] + list(range(2, x1.dim()))
-        self.count1 = x1.numel() // C
-
-    def all_gather(self, packed):
-        m1 = self.x1.mean(self.dims)
-        bshape = [1, -1] + [1] * (self.x1.dim() - 2)
-        M2 = ((self.x1 - m1.view(bshape)) ** 2).sum(self.dims)
-        other = torch.cat([torch.stack([m1, M2], 1).reshape(-1), torch.tensor([float(self.count1)], device=packed.device)])
-        return torch.stack([packed, other.to(packed.dtype)])
-
-    def all_reduce_sum_(self, ws):
-        bshape = [1, -1] + [1] * (self.x1.dim() - 2)
-        xh = (self.x1 - self.mean_g.view(bshape)) * self.invstd_g.view(bshape)
-        C = self.x1.shape[1]
-        v = ws[:3 * C].view(-1, 3)
-        v[:, 0] += self.dz1.sum(self.dims)
-        v[:, 1] += (self.dz1 * xh).sum(self.dims)
-        ws[3 * C] += float(self.count1)           # the other rank's element count rides in the last slot
-        return ws
 
 
 @pytest.mark.parametrize('shape', [(2, 32, 7, 9), (2, 16, 4, 6, 12)])
