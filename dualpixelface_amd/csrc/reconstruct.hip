@@ -18,7 +18,7 @@
 // nearly equal parts cancelled analytically; rows below use Kinv[:, 1].
 // No floating-point atomics, no workgroup waits for another inside a launch, every count in a fixed order: the bits repeat.
 #include "dpf_common.h"
-#include "dpf_geometry.h"      // Cam, cam_setup, ray_of, connected: shared with normal_geo.hip
+#include "dpf_geometry.h"      // Cam, cam_setup, ray_of, connected: shared with normal_geo.hip; Scene, valid_depth: with normal_refine.hip
 #include "dpf_image.h"         // DpfNorm: the vertex colours de-normalise the view
 #include <math.h>
 
@@ -30,27 +30,6 @@ constexpr int kPerThread = 4;                  // mesh: grid nodes per thread
 constexpr int kNodes = kBlock * kPerThread;    // and per workgroup
 constexpr int kMaxBatch = 65535;               // B rides on gridDim.y / gridDim.z
 constexpr int kMaxTileRows = 65535;            // and the normals' tile rows on gridDim.y
-
-struct Scene {        // the operands backproject, depth_normals and depth_mesh share
-  const float* pred;
-  long long pstride;
-  const float* ab;
-  const float* Kmat;
-  const float* mask;
-  int target_type, H, W;
-  float z_near, z_far;
-};
-
-// the depth of pixel (y, x) of sample s where it is valid, else 0
-__device__ __forceinline__ float valid_depth(const Scene& sc, const Cam& cam, int s, int y, int x) {
-  const size_t o = (size_t)y * sc.W + x;
-  const float p = sc.pred[(size_t)s * (size_t)sc.pstride + o];
-  float z = sc.target_type == 2 ? p : cam.a / (p - cam.b);
-  if (!isfinite(z)) z = 0.f;
-  bool ok = cam.ok && z > sc.z_near && z < sc.z_far;
-  if (sc.mask) ok = ok && sc.mask[(size_t)s * sc.H * sc.W + o] > 0.f;
-  return ok ? z : 0.f;
-}
 
 // grid (blocks, B)
 __global__ __launch_bounds__(256) void backproject_kernel(Scene sc, float* __restrict__ points, unsigned char* __restrict__ valid) {
@@ -342,21 +321,7 @@ __global__ __launch_bounds__(256) void mesh_face_kernel(Scene sc, Grid g, float 
   }
 }
 
-bool scene_ok(const float* pred, long long pstride, int target_type, const float* ab, const float* Kmat, int B, int H, int W, float z_near,
-              float z_far) {
-  return pred && Kmat && B > 0 && H > 0 && W > 0 && target_type >= 0 && target_type <= 2 && (target_type == 2 || ab) &&
-         pstride >= (long long)H * W && z_near >= 0.f && z_far > z_near;      // (a NaN limit fails both comparisons)
-}
-
 bool scene_supported(int B, int H, int W) { return B <= kMaxBatch && (long long)H * W <= 0x7fffffffLL; }
-
-Scene scene_of(const float* pred, long long pstride, int target_type, const float* ab, const float* Kmat, const float* mask, int H, int W,
-               float z_near, float z_far) {
-  Scene sc;
-  sc.pred = pred, sc.pstride = pstride, sc.ab = ab, sc.Kmat = Kmat, sc.mask = mask;
-  sc.target_type = target_type, sc.H = H, sc.W = W, sc.z_near = z_near, sc.z_far = z_far;
-  return sc;
-}
 
 bool grid_of(int B, int H, int W, int stride, Grid* g) {
   if (B <= 0 || H <= 0 || W <= 0 || !(stride == 1 || stride == 2 || stride == 4 || stride == 8) || !scene_supported(B, H, W)) return false;

@@ -179,6 +179,7 @@ class DPNetCore(ArenaModule):
         P = self._P
         x = ops.concat_channels(list(self._views(batch)))
         H, W = x.shape[2], x.shape[3]
+        dpnet_shapes(H, W)      # a size whose decoders and skips do not meet is refused here, before a join reads past the smaller of the two
         # Encoder2 (modules.py:48-56): the stem beside a max-pool of the raw input
         x = ops.concat_channels([self._basic(x, 'enc_layer1_1.conv1', 2, 1), ops.max_pool2d(x, 7, 2, 1)])
         xs = {}

@@ -1933,6 +1933,52 @@ def depth_mesh(pred, Kmat, normal_map, ab=None, mask=None, view=None, target_typ
     return vertices, vnormals, vcolours, faces, counts
 
 
+NORMAL_REFINE_MAX_ITERATIONS = 256
+NORMAL_REFINE_STATS = 3     # doubles per sample ahead of rho_1 .. rho_iterations: valid pixels, edges, rho_0
+
+
+def normal_refine(pred, Kmat, normal, ab=None, mask=None, target_type='disp', near=0.0, far=None, max_edge_ratio=0.01, min_cos=0.1, lam=0.1,
+                  iterations=32, normal_signs=(1, 1, 1), stats=False, out=None):
+    """csrc/normal_refine.hip: head 0 of pred [B, n, H, W] (or [B, H, W]) brought into agreement with normal [B, 3, H, W] -> a fresh tensor of
+    pred's shape (or `out`, a contiguous one of that shape), the other heads copied.  Per sample the log-depth correction delta minimising
+    lam sum delta^2 + sum over the edges of (delta_q - delta_p - e_pq)^2, e_pq the difference between the step the normals predict and the
+    one the depth takes (include/dpf_hip.h), by `iterations` (1 .. 256) of Jacobi-preconditioned conjugate gradients on the device; edges
+    join valid neighbours within max_edge_ratio of each other whose normal (normal_signs * normal) meets both rays at a cosine of at
+    least min_cos.  Invalid pixels keep their value bit for bit.  With stats also float64 [B, 3 + iterations]: valid pixels, edges,
+    rho_0 .. rho_iterations.  An inference-time operator: detached, no gradient, nothing read on the host."""
+    iterations = _int_arg('normal_refine', 'iterations', iterations)
+    signs = tuple(float(v) for v in normal_signs)
+    if len(signs) != 3 or any(v not in (1.0, -1.0) for v in signs):
+        raise DpfError('normal_refine: normal_signs must be three values of +1 or -1, got %r' % (normal_signs,))
+    for name, v, ok in (('max_edge_ratio', max_edge_ratio, float(max_edge_ratio) > 0), ('lam', lam, 0 < float(lam) < float('inf')),
+                        ('min_cos', min_cos, 0 <= float(min_cos) < 1),
+                        ('iterations', iterations, 1 <= iterations <= NORMAL_REFINE_MAX_ITERATIONS)):
+        if not ok:
+            raise DpfError('normal_refine: %s = %r is outside its range (max_edge_ratio > 0, lam > 0, 0 <= min_cos < 1, iterations 1 .. %d)'
+                           % (name, v, NORMAL_REFINE_MAX_ITERATIONS))
+    with torch.no_grad():
+        head, held, (B, H, W) = _scene_operands('normal_refine', pred, target_type, ab, Kmat, mask, near, far)
+        _need(normal, out, dtypes=_F32, contiguous=False)
+        if normal is None:
+            raise DpfError('normal_refine: normal [B, 3, H, W] is needed')
+        _match_pred('normal_refine', held[0], ('normal', normal, (B, 3, H, W)))
+        shape = tuple(pred.shape)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=held[0].device)
+        elif tuple(out.shape) != shape or not out.is_contiguous():
+            raise DpfError('normal_refine: out %s is not a contiguous tensor of pred\'s shape %s' % (tuple(out.shape), shape))
+        nmap = _c(normal.detach())
+        planes = out.view(B, -1, H, W)
+        if planes.shape[1] > 1:
+            planes[:, 1:].copy_(pred.detach()[:, 1:])
+        ws, nbytes = _workspace('dpf_normal_refine_workspace_bytes', 'normal_refine: B=%d H=%d W=%d is not supported', B, H, W,
+                                device=held[0].device, tag='normal_refine')
+        record = torch.empty((B, NORMAL_REFINE_STATS + iterations), dtype=torch.float64, device=held[0].device) if stats else None
+        lib().call('dpf_normal_refine', *head[:6], _ptr(nmap), _host_floats(signs), *head[6:], float(max_edge_ratio), float(min_cos),
+                   float(lam), iterations, _ptr(ws), nbytes, _ptr(out), planes.shape[1] * H * W, _ptr(record), _stream())
+    return (out, record) if stats else out
+
+
 NORMAL_GEO_STEPS = (1, 2, 4)
 NORMAL_GEO_STATS = 16       # doubles the forward leaves for the backward: count per head [0, 8), term sum per head [8, 16)
 

@@ -11,7 +11,7 @@ import warnings
 
 import torch
 
-from . import ops, optim, postprocess, reconstruct
+from . import normal_refine, ops, optim, postprocess, reconstruct
 from .losses import loss_selector
 from .selectors import metric_selector, optimizer_selector, scheduler_selector
 from .dpnet import DPNetCore
@@ -46,6 +46,8 @@ class _PluginHooks(object):
             results.update(self.loss_model.forward(results, batch, target_type=self._target_type()))
         elif not self.training and 'idepth' in batch and 'abvalue' not in batch and results.get('pred_depth') is not None:
             results['abvalue'] = ops.affine_fit(results['pred_depth'], batch['idepth'])       # what metrics.absolute_dp converts with
+        if not self.training and normal_refine.active(self.option):  # filter -> fit -> refine -> surface: metrics and mesh see the refined map
+            normal_refine.apply(self.option, results, batch)
         if not self.training and reconstruct.active(self.option):   # the surface of the filtered map, placed with the fitted (a, b)
             reconstruct.apply(self.option, results, batch, guide=self._views(batch)[0])
         return results

@@ -655,6 +655,46 @@ int dpf_smoothness_backward(const float* pred, const float* guide_rgb, const flo
                             const float* norm_host, const float* head_weights_host, const float* luma, const double* stats,
                             const float* gout, float* dpred, void* stream);
 
+/* ---- normal-guided depth refinement (csrc/normal_refine.hip; option key normal_refine, dualpixelface_amd/normal_refine.py; DESIGN.md
+ * section 11): the correction of head 0 of a prediction that a normal map asks for, one sparse linear system per sample (Nehab et al.
+ * 2005, in log-depth, where a pinhole camera makes it linear).  The geometry is the surface export's above: pred, pred_batch_stride,
+ * target_type, ab, Kmat, mask, z_near, z_far, depth, valid, rays, Kinv, connected (from the INPUT depth, so discontinuities are kept).
+ * normal [B, 3, H, W] fp32; normal_signs_host: three host floats, each +1 or -1, read during the call; n = normal_signs * normal.
+ *   edges     q is the right neighbour of p (axis 0) or the one below (axis 1); k = Kinv[:, axis]; r_p, r_q the rays.  An edge exists
+ *             iff p and q are connected and at least one of n_p, n_q is usable on it
+ *   usable    |n| finite and > 1e-6; n . r_p and n . r_q both > 0 or both < 0; |n . r_p| >= (min_cos |n|) |r_p| and the same at q; the
+ *             step below finite
+ *   step      from n_p: -log1p((n_p . k) / (n_p . r_p)); from n_q: log1p(-((n_q . k) / (n_q . r_q))); g_pq the usable one, or
+ *             (g_p + g_q) 0.5 of both.  Exact for a plane; the same for n and -n
+ *   mismatch  e_pq = g_pq - log1p((z_q - z_p) / z_p)
+ *   system    per sample minimise lambda sum_valid delta_p^2 + sum_edges (delta_q - delta_p - e_pq)^2 over the fp32 log-depth correction
+ *             delta: A = lambda I + L, (A v)_p = lambda v_p + sum over the edges at p of (v_p - v_neighbour), D_p = lambda + degree_p,
+ *             b_p = + e of the edge from the left - e of the edge to the right + e of the edge from above - e of the edge down, summed in
+ *             that order; every neighbour sum runs left, right, up, down
+ *   solver    Jacobi-preconditioned conjugate gradients, exactly `iterations` of them: delta = 0, r = b, s = r (1 / D), p = s,
+ *             rho = sum r s; then q = A p, sigma = sum p q, alpha = sigma > 0 and rho > 0 ? rho / sigma : 0, delta += alpha p,
+ *             r -= alpha q, s = r (1 / D), rho' = sum r s, beta = rho > 0 ? rho' / rho : 0, p = s + beta p, rho = rho'.  Vectors fp32, 1 / D
+ *             rounded once; sums of fp64 products in two phases and a fixed order; alpha and beta rounded to fp32 once.  An empty,
+ *             edgeless or consistent sample returns delta = 0, never NaN; the scalars are per sample, so a sample's result does not
+ *             depend on the rest of the batch
+ *   out       the plane of head 0, out_batch_stride floats apart: z expf(delta) for target type 2, a / (z expf(delta)) + b otherwise,
+ *             where the pixel is valid; pred, bit for bit, where it is not (every pixel of a sample with a singular K)
+ *   stats     [B, 3 + iterations] doubles or NULL: valid pixels, edges, rho_0 .. rho_iterations
+ * Launches: setup (32 x 8 tiles with a 1-pixel halo: z, one byte of flags per pixel -- valid, edge right, edge down --, 1 / D, r, p,
+ * delta = 0), then per iteration the stencil (the p update folded in, recomputed on the halo), a fold to alpha, the vector update, a fold
+ * to beta and rho, and last the output pass.  The scalars stay in the workspace; nothing is read on the host.
+ * ws: dpf_normal_refine_workspace_bytes() bytes of 16-byte aligned device scratch (-1: shape refused); it needs no initialisation.
+ * No floating-point atomics, no workgroup waits for another, nothing allocates or waits on the host: the bits repeat and the call can be
+ * captured.  Refusals launch nothing: DPF_ERR_INVALID_ARG for a NULL pointer (but mask, stats, and ab with target type 2), B, H or W <= 0,
+ * a target_type outside 0..2, a batch stride < H W, z_near < 0, z_far <= z_near, max_edge_ratio <= 0, min_cos outside [0, 1),
+ * lambda <= 0 or not finite, iterations < 1, a sign that is not +-1, or a workspace that is too small or misaligned;
+ * DPF_ERR_UNSUPPORTED for iterations > 256, B > 65535, H W >= 2^31 or H beyond 65535 tiles of 8 rows. */
+long long dpf_normal_refine_workspace_bytes(int B, int H, int W);
+int dpf_normal_refine(const float* pred, long long pred_batch_stride, int target_type, const float* ab, const float* Kmat, const float* mask,
+                      const float* normal, const float* normal_signs_host, int B, int H, int W, float z_near, float z_far,
+                      float max_edge_ratio, float min_cos, float lambda, int iterations, void* ws, long long ws_bytes, float* out,
+                      long long out_batch_stride, double* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
