@@ -6,68 +6,18 @@
 // (reference: src/model/stereodpnet/modules.py:327-334 and :341-362).
 // Backward scatters d(logit) into the low-resolution volume through an LDS-privatised tile (one LDS atomic per
 // contribution, one global atomic per touched low-res cell and tile).
-#include "dpf_common.h"
+#include "dpf_softargmin.h"
 #include <type_traits>
 
 namespace {
 
-constexpr int MAXD = 8;     // low-res depth levels
-constexpr int MAXL = 32;    // upsampled hypotheses
 constexpr int TY = 8, TX = 32;
 
-struct HeadP {
-  int B, D, h, w, L, H, W;
-  long long pbs;        // batch stride of the probability output (0: L * H * W, dense)
-  float off;            // 0: align_corners=True (ratio (in-1)/(out-1)); 0.5: align_corners=False (ratio in/out, half-pixel centres)
-  float disp[MAXL];
-};
-
-__device__ __forceinline__ float head_ratio(int in, int out, float off) {
-  return off > 0.f ? (float)in / (float)out : (out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f);
-}
-
-__device__ __forceinline__ void ac_src(int dst, float ratio, int in, int& i0, int& i1, float& lam, float off = 0.f) {
-  float src = ratio * ((float)dst + off) - off;       // ATen area_pixel_compute_source_index
-  if (src < 0.f) src = 0.f;
-  i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  lam = src - (float)i0;
-}
-
+// (HeadP, head_ratio, ac_src, head_bilinear, level_taps_8x32 and pixel_logits: dpf_softargmin.h)
 __device__ __forceinline__ void pixel_probs(const float* __restrict__ k, const HeadP& p, int b, int Y, int X, float rd, float ry, float rx,
                                             float* prob, float& pred, int& y0, int& y1, int& x0, int& x1, float& ly, float& lx) {
-  ac_src(Y, ry, p.h, y0, y1, ly, p.off);
-  ac_src(X, rx, p.w, x0, x1, lx, p.off);
-  const float hy = 1.f - ly, hx = 1.f - lx;
-  float bl[MAXD];
-  const float* kb = k + (long long)b * p.D * p.h * p.w;
-#pragma unroll
-  for (int d = 0; d < MAXD; ++d) {
-    if (d < p.D) {
-      const float* q = kb + (long long)d * p.h * p.w;
-      bl[d] = hy * (hx * q[y0 * p.w + x0] + lx * q[y0 * p.w + x1]) + ly * (hx * q[y1 * p.w + x0] + lx * q[y1 * p.w + x1]);
-    } else {
-      bl[d] = 0.f;
-    }
-  }
-  float mx = -3.4e38f;
-#pragma unroll
-  for (int l = 0; l < MAXL; ++l) {
-    if (l < p.L) {
-      int d0, d1;
-      float ld;
-      ac_src(l, rd, p.D, d0, d1, ld, p.off);
-      float v0 = 0.f, v1 = 0.f;
-#pragma unroll
-      for (int d = 0; d < MAXD; ++d) {   // register-resident select (no runtime-indexed array)
-        v0 = (d == d0) ? bl[d] : v0;
-        v1 = (d == d1) ? bl[d] : v1;
-      }
-      prob[l] = (1.f - ld) * v0 + ld * v1;
-      mx = fmaxf(mx, prob[l]);
-    }
-  }
+  float mx;
+  pixel_logits(k, p, b, Y, X, rd, ry, rx, prob, mx, y0, y1, x0, x1, ly, lx);
   float sum = 0.f;
 #pragma unroll
   for (int l = 0; l < MAXL; ++l)
@@ -110,7 +60,6 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
 // (d0, d1, lambda of every hypothesis) folds to constants, i.e. 32 FMAs on registers instead of 512 register-select instructions
 __global__ __launch_bounds__(256) void head_fwd_8x32_kernel(const float* __restrict__ k, float* __restrict__ pred, float* __restrict__ prob, HeadP p) {
   constexpr int D = 8, L = 32;
-  constexpr float rd = (float)(D - 1) / (float)(L - 1);
   const float ry = p.H > 1 ? (float)(p.h - 1) / (float)(p.H - 1) : 0.f;
   const float rx = p.W > 1 ? (float)(p.w - 1) / (float)(p.W - 1) : 0.f;
   const long long total = (long long)p.B * p.H * p.W;
@@ -129,17 +78,15 @@ __global__ __launch_bounds__(256) void head_fwd_8x32_kernel(const float* __restr
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       const float* q = kb + (long long)d * lplane;
-      bl[d] = hy * (hx * q[y0 * p.w + x0] + lx * q[y0 * p.w + x1]) + ly * (hx * q[y1 * p.w + x0] + lx * q[y1 * p.w + x1]);
+      bl[d] = head_bilinear(q, p.w, y0, y1, x0, x1, hy, ly, hx, lx);
     }
     float pr[L];
     float mx = -3.4e38f;
 #pragma unroll
     for (int l = 0; l < L; ++l) {
-      const float src = rd * (float)l;                      // same expression as ac_src: folded at compile time
-      int d0 = (int)src;
-      if (d0 > D - 1) d0 = D - 1;
-      const int d1 = d0 + (d0 < D - 1 ? 1 : 0);
-      const float ld = src - (float)d0;
+      int d0, d1;
+      float ld;
+      level_taps_8x32(l, d0, d1, ld);
       pr[l] = (1.f - ld) * bl[d0] + ld * bl[d1];
       mx = fmaxf(mx, pr[l]);
     }
@@ -204,7 +151,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
     const float* kb = k + (long long)b * p.D * p.h * p.w;
     for (int d = 0; d < p.D; ++d) {
       const float* q = kb + (long long)d * p.h * p.w;
-      s_bl[d][tid] = hy * (hx * q[y0 * p.w + x0] + lx * q[y0 * p.w + x1]) + ly * (hx * q[y1 * p.w + x0] + lx * q[y1 * p.w + x1]);
+      s_bl[d][tid] = head_bilinear(q, p.w, y0, y1, x0, x1, hy, ly, hx, lx);
       s_db[d][tid] = 0.f;
     }
     float mx = -3.4e38f;
@@ -284,7 +231,6 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 // backward for the shipped geometry: level interpolation folded at compile time, per-thread values in registers (no LDS arrays)
 __global__ __launch_bounds__(256) void head_bwd_8x32_kernel(const float* __restrict__ k, const float* __restrict__ gpred, float* __restrict__ dk, HeadP p) {
   constexpr int D = 8, L = 32;
-  constexpr float rd = (float)(D - 1) / (float)(L - 1);
   __shared__ double tile[D][TY + 2][TX + 2];      // fp64 cells: ds_add_f64 (3.1 lanes/clk/CU) instead of ds_add_f32 (0.33)
   const float ry = p.H > 1 ? (float)(p.h - 1) / (float)(p.H - 1) : 0.f;
   const float rx = p.W > 1 ? (float)(p.w - 1) / (float)(p.W - 1) : 0.f;
@@ -315,18 +261,16 @@ __global__ __launch_bounds__(256) void head_bwd_8x32_kernel(const float* __restr
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       const float* q = kb + (long long)d * lplane;
-      bl[d] = hy * (hx * q[y0 * p.w + x0] + lx * q[y0 * p.w + x1]) + ly * (hx * q[y1 * p.w + x0] + lx * q[y1 * p.w + x1]);
+      bl[d] = head_bilinear(q, p.w, y0, y1, x0, x1, hy, ly, hx, lx);
       db[d] = 0.f;
     }
     float pr[L];
     float mx = -3.4e38f;
 #pragma unroll
     for (int l = 0; l < L; ++l) {
-      const float src = rd * (float)l;
-      int d0 = (int)src;
-      if (d0 > D - 1) d0 = D - 1;
-      const int d1 = d0 + (d0 < D - 1 ? 1 : 0);
-      const float ld = src - (float)d0;
+      int d0, d1;
+      float ld;
+      level_taps_8x32(l, d0, d1, ld);
       pr[l] = (1.f - ld) * bl[d0] + ld * bl[d1];
       mx = fmaxf(mx, pr[l]);
     }
@@ -341,11 +285,9 @@ __global__ __launch_bounds__(256) void head_bwd_8x32_kernel(const float* __restr
     const float g = gpred[((long long)b * p.H + Y) * p.W + X] / sum;
 #pragma unroll
     for (int l = 0; l < L; ++l) {
-      const float src = rd * (float)l;
-      int d0 = (int)src;
-      if (d0 > D - 1) d0 = D - 1;
-      const int d1 = d0 + (d0 < D - 1 ? 1 : 0);
-      const float ld = src - (float)d0;
+      int d0, d1;
+      float ld;
+      level_taps_8x32(l, d0, d1, ld);
       const float dl = pr[l] * (p.disp[l] - pred) * g;      // softmax-expectation gradient w.r.t. logit l
       db[d0] += (1.f - ld) * dl;
       db[d1] += ld * dl;

@@ -5,7 +5,7 @@ Class names follow the reference's lookup rule ``<NAME.upper()>Loss`` (loss_sele
 """
 import torch
 
-from . import normal_geo, ops, photometric
+from . import normal_geo, ops, photometric, unimodal
 from .core import reference_key
 
 
@@ -204,9 +204,43 @@ class SMOOTHNESSLoss(_LabelFreeLoss):
                                             gamma=s.smooth_gamma, eps=s.charbonnier_eps)}
 
 
+class UNIMODALLoss(_DepthLoss):
+    """The unimodal loss (not in the reference; DESIGN.md section 11, csrc/unimodal.hip): the cross-entropy between the hypothesis
+    distribution of every disparity head and a Laplace distribution centred on the label, the gradient going into the heads' logits.
+    It reads the private record results['_heads'] the models with a hypothesis volume at the output resolution leave (stereodpnet,
+    psmnet, nnet), not pred_depth.  Settings: the model config block unimodal (unimodal.settings).  The target rule is SMOOTHL1Loss's:
+    batch['disp'], or under the fitted conversion batch['depth'] with the shared (a, b)."""
+    MODELS = ('stereodpnet', 'psmnet', 'nnet')
+    WHY_NOT = {'dpnet': 'it regresses its output and has no hypothesis volume',
+               'stereonet': 'its volume is at low resolution and in other units than the prediction'}
+
+    def __init__(self, option):
+        super(UNIMODALLoss, self).__init__(option)
+        model = getattr(option, 'model_name', None)
+        if model not in self.MODELS:
+            raise NotImplementedError("the 'unimodal' loss is not built for the model %r%s (it needs the disparity hypotheses of %s)"
+                                      % (model, ': ' + self.WHY_NOT[model] if model in self.WHY_NOT else '', ', '.join(self.MODELS)))
+        self.settings = unimodal.settings(option)
+
+    def forward(self, preds, batch, target_type='disp', ab_of=None):
+        if target_type != 'disp':
+            raise NotImplementedError("the 'unimodal' loss needs target_type 'disp', got %r: the hypotheses are disparities" % (target_type,))
+        heads = preds.get('_heads')
+        if heads is None:
+            raise NotImplementedError("the 'unimodal' loss needs results['_heads'], which this network does not leave")
+        common = dict(head_weights=self.head_weights(len(heads['logits'])), scale=heads['scale'], align_corners=heads['align_corners'],
+                      laplace_scale=self.settings.laplace_scale)
+        if takes_least_square(batch):
+            ab = (ab_of or conversion(preds, batch))()
+            loss = ops.unimodal_loss(heads['logits'], heads['disp_values'], batch['depth'], batch.get('mask'), target_ab=ab, **common)
+            return {'loss': loss, 'abvalue': ab}
+        loss = ops.unimodal_loss(heads['logits'], heads['disp_values'], batch['disp'], batch.get('mask'), **common)
+        return {'loss': loss, 'abvalue': batch['abvalue']}
+
+
 LABEL_FREE = ('photometric', 'smoothness')
 _BANK = {'smoothL1': SMOOTHL1Loss, 'silog': SILOGLoss, 'cosine': COSINELoss, 'normal_geo': NORMAL_GEOLoss, 'photometric': PHOTOMETRICLoss,
-         'smoothness': SMOOTHNESSLoss}
+         'smoothness': SMOOTHNESSLoss, 'unimodal': UNIMODALLoss}
 
 
 class loss_selector(object):

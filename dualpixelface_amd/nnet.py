@@ -134,4 +134,5 @@ class NNetCore(PSMFeatures, ArenaModule):
         return {'pred_depth': pred_all, 'prob_depth': prob_all,
                 'pred_normal': normal.unsqueeze(1) if normal is not None else None,
                 'ref_feature': ops.channel_max(ref),
-                '_taps': {'fea_ref': ref, 'fea_tar': tar, 'volume': vol, 'cost0': c, 'costs': costs, 'costss': costss}}
+                '_taps': {'fea_ref': ref, 'fea_tar': tar, 'volume': vol, 'cost0': c, 'costs': costs, 'costss': costss},
+                '_heads': {'logits': [costs, costss], 'disp_values': self.disp_values, 'scale': 4, 'align_corners': False}}

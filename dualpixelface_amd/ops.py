@@ -2084,6 +2084,104 @@ def smoothness_loss(pred, guide_rgb, mask=None, head_weights=(1.0,), gamma=10.0,
     return HeadLossFn.apply(pred, _SMOOTHNESS, held, lead, False)
 
 
+UNIMODAL_STATS = 16         # doubles: count per head [0, 8), term sum per head [8, 16)
+UNIMODAL_MAX_HEADS, UNIMODAL_MAX_D, UNIMODAL_MAX_L = 8, 8, 32
+
+
+def _host_ptrs(ts):
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+class UnimodalFn(torch.autograd.Function):
+    """HeadLossFn for a loss that reads the heads' logits, a list of separate tensors, instead of pred [B, n, H, W] (csrc/unimodal.hip):
+    -> 0-dim loss, and with want_extras counted and expect.  The C argument orders agree as in that family: forward `lead | ws, nbytes |
+    logsum | stats, out | extras`, backward `lead | logsum | stats, gout, dlogits`.  Workspace, stats and the log-sum planes are fresh tensors (planes
+    and stats are saved for the backward, the workspace is not needed again), gout is read on the device and nothing is read on the host,
+    so the call is capturable inside the train-step graph.  One gradient per logit tensor, every element written; nothing else gets one."""
+
+    @staticmethod
+    def forward(ctx, held, tail, want_extras, *logits):
+        B, _, D, h, w = logits[0].shape
+        n, (L, H, W) = len(logits), tail[:3]
+        dev = logits[0].device
+        ws, nbytes = _workspace('dpf_unimodal_workspace_bytes', 'unimodal_loss: shape B=%d n=%d H=%d W=%d is not supported', B, n, H, W,
+                                device=dev)
+        stats = torch.empty(UNIMODAL_STATS, dtype=torch.float64, device=dev)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        logsum = torch.empty((B, n, H, W), dtype=torch.float32, device=dev)
+        extras = [None, None]
+        if want_extras:
+            extras = [torch.empty((B, n, H, W), dtype=torch.uint8, device=dev), torch.empty((B, n, H, W), dtype=torch.float32, device=dev)]
+        lead = (*[_ptr(t) for t in held], B, n, D, h, w, *tail)
+        lib().call('dpf_unimodal_forward', _host_ptrs(logits), *lead, _ptr(ws), nbytes, _ptr(logsum), _ptr(stats), _ptr(out),
+                   *[_ptr(t) for t in extras], _stream())
+        ctx.save_for_backward(logsum, stats, *[t for t in held if t is not None], *logits)
+        ctx.lead, ctx.n = lead, n
+        if want_extras:
+            ctx.mark_non_differentiable(*extras)
+            return (out,) + tuple(extras)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout, *unused):
+        saved = ctx.saved_tensors
+        logsum, stats, logits = saved[0], saved[1], saved[len(saved) - ctx.n:]
+        gout = _c(gout)
+        _need(gout)
+        grads = [torch.empty_like(t) for t in logits]
+        lib().call('dpf_unimodal_backward', _host_ptrs(logits), *ctx.lead, _ptr(logsum), _ptr(stats), _ptr(gout), _host_ptrs(grads), _stream())
+        return (None, None, None) + tuple(grads)
+
+
+def unimodal_loss(logits, disp_values, target, mask=None, target_ab=None, head_weights=(1.0,), scale=4, align_corners=True,
+                  laplace_scale=None, return_extras=False):
+    """csrc/unimodal.hip (not in the reference): the cross-entropy between the hypothesis distribution of every
+    disparity head and a Laplace distribution centred on the label -> the 0-dim loss sum_h w_h mean over the counted pixels of
+    -sum_l P_l log p_l.  logits: a list of n <= 8 tensors [B, 1, D <= 8, h, w], the heads' cost logits; p is the softmax over the
+    L = scale * D <= 32 hypotheses of their trilinear upsample, exactly the soft-argmin's (ops.softargmin with the same disp_values, scale
+    and align_corners), recomputed inside the kernels; P_l ~ exp(-|d_l - t| / laplace_scale) over the strictly ascending disp_values
+    (None: d_1 - d_0).  t is target [B, H, W], or with target_ab [B, 2] = [b, a] a / target + b of the depth map `target`.  A pixel is
+    counted when mask (None: everywhere) > 0, t is finite and d_0 <= t <= d_{L-1}.  One gradient per logit tensor, every element written,
+    the same bits on every call; nothing flows to target, mask, target_ab or disp_values.  With return_extras also counted
+    [B, n, H, W] uint8 and expect [B, n, H, W] fp32, the soft-argmin's value sum_l p_l d_l."""
+    name = 'unimodal_loss'
+    if not isinstance(logits, (list, tuple)) or not 1 <= len(logits) <= UNIMODAL_MAX_HEADS:
+        raise DpfError('%s: logits must be a list of 1..%d tensors [B, 1, D, h, w], got %r' %
+                       (name, UNIMODAL_MAX_HEADS, len(logits) if isinstance(logits, (list, tuple)) else type(logits).__name__))
+    _need(*logits, target, mask, target_ab, dtypes=_F32, contiguous=False)
+    first = logits[0]
+    if first.dim() != 5 or first.shape[1] != 1:
+        raise DpfError('%s: logits[0] %s is not [B, 1, D, h, w]' % (name, tuple(first.shape)))
+    for i, t in enumerate(logits):
+        if tuple(t.shape) != tuple(first.shape):
+            raise DpfError('%s: logits[%d] %s does not match logits[0] %s' % (name, i, tuple(t.shape), tuple(first.shape)))
+    B, _, D, h, w = first.shape
+    scale = _int_arg(name, 'scale', scale)
+    disp = [float(v) for v in disp_values]
+    L, H, W = scale * D, scale * h, scale * w
+    if scale < 1 or D > UNIMODAL_MAX_D or L > UNIMODAL_MAX_L:
+        raise DpfError('%s: D=%d levels at scale %r are not supported (D <= %d, scale * D <= %d)' % (name, D, scale, UNIMODAL_MAX_D,
+                                                                                                       UNIMODAL_MAX_L))
+    if len(disp) != L:
+        raise DpfError('%s: %d disp_values for %d hypotheses (scale %d x D %d)' % (name, len(disp), L, scale, D))
+    if any(v != v or v in (float('inf'), -float('inf')) for v in disp) or any(b <= a for a, b in zip(disp, disp[1:])):
+        raise DpfError('%s: disp_values must be finite and strictly ascending' % name)
+    if target is None:
+        raise DpfError('%s: target [B, H, W] is needed' % name)
+    _match_pred(name, first, ('target', target, (B, H, W)), ('mask', mask, (B, H, W)), ('target_ab', target_ab, (B, 2)))
+    if len(head_weights) != len(logits):
+        raise DpfError('%s: %d head weights for %d heads' % (name, len(head_weights), len(logits)))
+    if laplace_scale is None:
+        if L < 2:
+            raise DpfError('%s: one hypothesis has no spacing, laplace_scale is needed' % name)
+        laplace_scale = disp[1] - disp[0]
+    if not 0.0 < float(laplace_scale) < float('inf'):
+        raise DpfError('%s: laplace_scale must be a positive finite number, got %r' % (name, laplace_scale))
+    held = tuple(None if t is None else _c(t.detach()) for t in (target, mask, target_ab))
+    tail = (L, H, W, int(bool(align_corners)), _host_floats(disp), float(laplace_scale), _host_floats(head_weights))
+    return UnimodalFn.apply(held, tail, bool(return_extras), *[_c(t) for t in logits])
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-5, gscale=1.0):
     _need(param, grad, exp_avg, exp_avg_sq)
     lib().call('dpf_adam_step', _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), int(step), float(lr), float(beta1),

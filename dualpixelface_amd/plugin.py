@@ -50,6 +50,7 @@ class _PluginHooks(object):
             normal_refine.apply(self.option, results, batch)
         if not self.training and reconstruct.active(self.option):   # the surface of the filtered map, placed with the fitted (a, b)
             reconstruct.apply(self.option, results, batch, guide=self._views(batch)[0])
+        results.pop('_heads', None)                         # (the heads' logits, for the loss hook only: losses.UNIMODALLoss)
         return results
 
     def _target_type(self):

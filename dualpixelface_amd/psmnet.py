@@ -110,4 +110,5 @@ class PSMNetCore(HourglassAggregation, PSMFeatures, ArenaModule):
         logits, costs = self._aggregate(vol)
         _, pred_all, prob_all = ops.softargmin_heads(logits, self.disp_values, 4, True)
         return {'pred_depth': pred_all, 'prob_depth': prob_all, 'ref_feature': ops.channel_max(ref),
-                '_taps': {'fea_ref': ref, 'fea_tar': tar, 'volume': vol, 'out3': costs[0]}}
+                '_taps': {'fea_ref': ref, 'fea_tar': tar, 'volume': vol, 'out3': costs[0]},
+                '_heads': {'logits': logits, 'disp_values': self.disp_values, 'scale': 4, 'align_corners': True}}

@@ -429,4 +429,5 @@ class StereoDPNetCore(HourglassAggregation, ArenaModule):
             normal, _, _ = self._normals(costs[0], preds[0], batch)
         return {'pred_depth': pred_all, 'prob_depth': prob_all,
                 'pred_normal': normal.unsqueeze(1) if normal is not None else None,
-                'ref_feature': ops.channel_max(ref), '_taps': {'fea_ref': ref, 'fea_tar': tar, 'volume': vol, 'out3': costs[0]}}
+                'ref_feature': ops.channel_max(ref), '_taps': {'fea_ref': ref, 'fea_tar': tar, 'volume': vol, 'out3': costs[0]},
+                '_heads': {'logits': logits, 'disp_values': self.disp_values, 'scale': 4, 'align_corners': True}}

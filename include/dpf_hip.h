@@ -655,6 +655,47 @@ int dpf_smoothness_backward(const float* pred, const float* guide_rgb, const flo
                             const float* norm_host, const float* head_weights_host, const float* luma, const double* stats,
                             const float* gout, float* dpred, void* stream);
 
+/* ---- unimodal loss (csrc/unimodal.hip; loss_type 'unimodal', dualpixelface_amd/losses.py; not in the reference):
+ * the cross-entropy between the hypothesis distribution of every disparity head and a Laplace distribution over the hypotheses centred
+ * on the label.  Neither pass reads or writes a [B, n, L, H, W] volume: both recompute the distribution of a pixel from the
+ * low-resolution logits with the arithmetic of dpf_softargmin_forward (csrc/dpf_softargmin.h holds it for both files).
+ * logits_host: n host pointers, read during the call, to the device tensors [B, 1, D, h, w] of the heads (separate allocations);
+ * target [B, H, W]; mask [B, H, W] or NULL; target_ab [B, 2] = [b, a] or NULL; disp_host: the L hypothesis values, strictly ascending,
+ * head_weights_host: n floats, both host memory read during the call.  L = scale D, H = scale h, W = scale w for an integer scale.
+ *   u_l      the trilinear upsample of the logits at (l, Y, X), l < L, as dpf_softargmin_forward forms it (align_corners likewise)
+ *   t        target, or with target_ab a / target + b (target is the depth map then)
+ *   counted  mask NULL or > 0, t finite, d_0 <= t <= d_{L-1}
+ *   P_l      e_l / Z, e_l = exp(-((|d_l - t| - m) / laplace_scale)), m = min_j |d_j - t|, Z = sum_l e_l
+ *   term     log(S) - sum_l P_l (u_l - mx), mx = max_j u_j, S = sum_l exp(u_l - mx): -sum_l P_l log p_l, p the soft-argmin's softmax
+ *   loss     sum_h w_h (sum over the counted pixels of head h of term) / count_h, count_h over the whole batch; a head with
+ *            count_h = 0 adds 0
+ * dpf_unimodal_forward: out[0] = the loss (fp32), stats = 16 doubles: count_h [0, 8), the term sum of head h [8, 16).  logsum: device floats
+ * the CALLER owns, [B, n, H, W]; the forward fills every element with log(S) and the backward reads it, so it has to live from one
+ * to the other (ws need not).  counted_out [B, n, H, W] uint8 and expect_out [B, n, H, W] fp32 (sum_l p_l d_l, the soft-argmin's value):
+ * both NULL or both given.  Two launches: one workgroup per 32 x 8 tile of one head of one sample leaves (term sum, count) in ws, one
+ * workgroup folds the rows head by head.  ws: dpf_unimodal_workspace_bytes() bytes of 8-byte aligned device scratch (-1: shape refused);
+ * it needs no initialisation.
+ * dpf_unimodal_backward: dlogits_host: n host pointers to [B, 1, D, h, w], EVERY element written = gout[0] (a device float) *
+ * d loss / d logits: d loss / d u_l = w_h / count_h (p_l - P_l) on the counted pixels, p_l = exp((u_l - mx) - log(S)), through the adjoint of the
+ * upsample.  One launch, a gather: one thread per low-resolution cell (b, y, x) of a head walks the pixels whose taps name the cell, Y
+ * then X ascending, per pixel the hypotheses ascending (the first level tap before the second), then the taps (y0, x0), (y0, x1),
+ * (y1, x0), (y1, x1) that name the cell; at a clamped last row, column or level both taps name one cell and both are added.  Nothing
+ * flows to target, mask, target_ab or the hypothesis values.
+ * No floating-point atomics, no workgroup waits for another, nothing allocates or waits on the host: the bits repeat whatever
+ * dpf_set_deterministic says, and the calls can be captured.  Refusals launch nothing: DPF_ERR_INVALID_ARG for a NULL pointer (but mask,
+ * target_ab and the optional output pair), B, D, h, w <= 0, n outside 1..8, laplace_scale not positive and finite, hypothesis values that
+ * are not finite and strictly ascending, or a workspace that is too small or misaligned; DPF_ERR_UNSUPPORTED for D > 8, L > 32, L no
+ * multiple of D, H or W not scale h, scale w, B n > 65535, H W >= 2^31, H or W > 2^24, or H beyond 65535 tiles of 8 rows. */
+long long dpf_unimodal_workspace_bytes(int B, int n, int H, int W);
+int dpf_unimodal_forward(const float* const* logits_host, const float* target, const float* mask, const float* target_ab, int B, int n, int D,
+                         int h, int w, int L, int H, int W, int align_corners, const float* disp_host, float laplace_scale,
+                         const float* head_weights_host, void* ws, long long ws_bytes, float* logsum, double* stats, float* out,
+                         unsigned char* counted_out, float* expect_out, void* stream);
+int dpf_unimodal_backward(const float* const* logits_host, const float* target, const float* mask, const float* target_ab, int B, int n, int D,
+                          int h, int w, int L, int H, int W, int align_corners, const float* disp_host, float laplace_scale,
+                          const float* head_weights_host, const float* logsum, const double* stats, const float* gout,
+                          float* const* dlogits_host, void* stream);
+
 /* ---- normal-guided depth refinement (csrc/normal_refine.hip; option key normal_refine, dualpixelface_amd/normal_refine.py; DESIGN.md
  * section 11): the correction of head 0 of a prediction that a normal map asks for, one sparse linear system per sample (Nehab et al.
  * 2005, in log-depth, where a pinhole camera makes it linear).  The geometry is the surface export's above: pred, pred_batch_stride,
