@@ -1,5 +1,6 @@
-// What the disparity head (softargmin.hip) and the losses on its hypothesis distribution (unimodal.hip) share: THE index arithmetic of
-// the trilinear upsampling of the [B, 1, D, h, w] cost logits and the expression order of the upsampled logits, stated once.  A file that
+// What the disparity head (softargmin.hip), the loss on its hypothesis distribution (unimodal.hip) and the confidence planes read off it
+// (head_confidence.hip) share: THE index arithmetic of the trilinear upsampling of the [B, 1, D, h, w] cost logits and the expression
+// order of the upsampled logits, stated once, and for the latter two the work of one pixel (Pixel<FAST>).  A file that
 // includes this computes the same u_l from the same logits, operation for operation (the rounding of the products and sums still follows
 // the including file's -ffp-contract setting).
 #pragma once
@@ -109,5 +110,45 @@ __device__ __forceinline__ void pixel_logits_8x32(const float* kb, long long lpl
     mx = fmaxf(mx, u[l]);
   }
 }
+
+// The work of one pixel (unimodal.hip, head_confidence.hip), for the shipped geometry (FAST: D = 8, L = 32, align_corners; every loop over the hypotheses unrolled, the level
+// taps constants) and for any other (loops over the hypotheses rolled, u_l formed again in each from the D level values in registers:
+// no register array is indexed at run time, and the level taps of 32 hypotheses are not all held in scalar registers at once).  Both
+// state the same operations in the same order.
+template <bool FAST>
+struct Pixel {
+  float bl[MAXD];      // the bilinear value of every cost level
+  float u[FAST ? MAXL : 1];
+
+  // (general geometry) u_l
+  __device__ __forceinline__ float logit(const HeadP& p, float rd, int l) const {
+    int d0, d1;
+    float ld;
+    ac_src(l, rd, p.D, d0, d1, ld, p.off);
+    return level_value(bl, d0, d1, ld);
+  }
+
+  // the level values, and mx = max_l u_l
+  __device__ __forceinline__ float upsample(const float* __restrict__ k, const HeadP& p, int b, float rd, int y0, int y1, int x0, int x1, float ly,
+                                            float lx) {
+    const long long lplane = (long long)p.h * p.w;
+    const float* kb = k + (long long)b * p.D * lplane;
+    float mx;
+    if (FAST) {
+      pixel_logits_8x32(kb, lplane, p.w, y0, y1, x0, x1, ly, lx, bl, u, mx);
+    } else {
+      const float hy = 1.f - ly, hx = 1.f - lx;
+#pragma unroll
+      for (int d = 0; d < MAXD; ++d)      // (past the D levels in use: the last one again, never selected)
+        bl[d] = head_bilinear(kb + (long long)min(d, p.D - 1) * lplane, p.w, y0, y1, x0, x1, hy, ly, hx, lx);
+      mx = -3.4e38f;
+#pragma unroll 1
+      for (int l = 0; l < p.L; ++l) mx = fmaxf(mx, logit(p, rd, l));
+    }
+    return mx;
+  }
+};
+
+#define UNI_FOR_L(l) _Pragma("unroll") for (int l = 0; l < MAXL; ++l)
 
 }  // namespace

@@ -2182,6 +2182,84 @@ def unimodal_loss(logits, disp_values, target, mask=None, target_ab=None, head_w
     return UnimodalFn.apply(held, tail, bool(return_extras), *[_c(t) for t in logits])
 
 
+CONFIDENCE_PLANES = ('peak', 'entropy', 'mass', 'spread', 'modal', 'lstar')      # the output order of dpf_head_confidence
+CONFIDENCE_MAX_WINDOW, CONFIDENCE_MAX_BINS = 32, 64
+
+
+def head_confidence(logit_list, disp_values, scale=4, align_corners=True, window=1, want=CONFIDENCE_PLANES):
+    """csrc/head_confidence.hip (not in the reference): confidence measures and a modal estimate from the hypothesis
+    distribution p of every disparity head, the softmax the soft-argmin takes its expectation of, recomputed inside the kernel from the
+    n <= 8 logit tensors [B, 1, D <= 8, h, w] (operands as in unimodal_loss) -> a dict of the planes named in `want`, each [B, n, H, W]:
+    'peak' max_l p_l, 'entropy' 1 - H(p) / log(L) in [0, 1], 'mass' the probability within `window` hypotheses of the peak, 'spread' the
+    standard deviation of p in disparity units, 'modal' the expectation over that window alone (fp32), and 'lstar' the peak's index
+    (int32).  A pixel whose distribution is not finite gets peak = entropy = mass = 0 and spread = modal = NaN.  One launch, no host
+    read; what a plane holds does not depend on which others are asked for.  No gradient."""
+    name = 'head_confidence'
+    if not isinstance(logit_list, (list, tuple)) or not 1 <= len(logit_list) <= UNIMODAL_MAX_HEADS:
+        raise DpfError('%s: logits must be a list of 1..%d tensors [B, 1, D, h, w], got %r' %
+                       (name, UNIMODAL_MAX_HEADS, len(logit_list) if isinstance(logit_list, (list, tuple)) else type(logit_list).__name__))
+    _need(*logit_list, dtypes=_F32, contiguous=False)
+    first = logit_list[0]
+    if first.dim() != 5 or first.shape[1] != 1:
+        raise DpfError('%s: logits[0] %s is not [B, 1, D, h, w]' % (name, tuple(first.shape)))
+    for i, t in enumerate(logit_list):
+        if tuple(t.shape) != tuple(first.shape):
+            raise DpfError('%s: logits[%d] %s does not match logits[0] %s' % (name, i, tuple(t.shape), tuple(first.shape)))
+    B, _, D, h, w = first.shape
+    scale = _int_arg(name, 'scale', scale)
+    window = _int_arg(name, 'window', window)
+    if not 0 <= window <= CONFIDENCE_MAX_WINDOW:
+        raise DpfError('%s: window must be an integer from 0 to %d, got %r' % (name, CONFIDENCE_MAX_WINDOW, window))
+    disp = [float(v) for v in disp_values]
+    L, H, W = scale * D, scale * h, scale * w
+    if scale < 1 or D > UNIMODAL_MAX_D or L > UNIMODAL_MAX_L or L < 2:
+        raise DpfError('%s: D=%d levels at scale %r are not supported (D <= %d, 2 <= scale * D <= %d)' % (name, D, scale, UNIMODAL_MAX_D,
+                                                                                                            UNIMODAL_MAX_L))
+    if len(disp) != L:
+        raise DpfError('%s: %d disp_values for %d hypotheses (scale %d x D %d)' % (name, len(disp), L, scale, D))
+    if any(v != v or v in (float('inf'), -float('inf')) for v in disp) or any(b <= a for a, b in zip(disp, disp[1:])):
+        raise DpfError('%s: disp_values must be finite and strictly ascending' % name)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in CONFIDENCE_PLANES for k in want):
+        raise DpfError('%s: want must name at least one of %s, got %r' % (name, ', '.join(CONFIDENCE_PLANES), want))
+    logits = [_c(t.detach()) for t in logit_list]
+    out = {k: torch.empty((B, len(logits), H, W), dtype=torch.int32 if k == 'lstar' else torch.float32, device=first.device)
+           for k in CONFIDENCE_PLANES if k in want}
+    lib().call('dpf_head_confidence', _host_ptrs(logits), B, len(logits), D, h, w, L, H, W, int(bool(align_corners)), _host_floats(disp),
+               window, *[_ptr(out.get(k)) for k in CONFIDENCE_PLANES], _stream())
+    return out
+
+
+def confidence_curve(conf, pred, target, mask=None, target_ab=None, bins=16, into=None):
+    """csrc/head_confidence.hip: the sparsification table of a confidence map -> curve [bins, 2] float64 = (count, sum |pred - t|) per
+    confidence bin, bin = min(bins - 1, int(conf * bins)).  conf and pred [B, H, W] (a head of a [B, n, H, W] tensor is read in place),
+    target [B, H, W], t = target or with target_ab [B, 2] = [b, a] a / target + b; a pixel is counted when mask (None: everywhere) > 0
+    and t, pred, conf are finite.  `into`: a [bins, 2] float64 table the result is ADDED to (and which is returned); without it a fresh
+    table.  The same bits on every call; nothing is read on the host.  No gradient."""
+    name = 'confidence_curve'
+    _need(conf, pred, target, mask, target_ab, dtypes=_F32, contiguous=False)
+    _need(into, dtypes=(torch.float64,))
+    if conf is None or pred is None or target is None:
+        raise DpfError('%s: conf, pred and target [B, H, W] are needed' % name)
+    if conf.dim() != 3:
+        raise DpfError('%s: conf %s is not [B, H, W]' % (name, tuple(conf.shape)))
+    B, H, W = conf.shape
+    bins = _int_arg(name, 'bins', bins)
+    if not 1 <= bins <= CONFIDENCE_MAX_BINS:
+        raise DpfError('%s: bins must be an integer from 1 to %d, got %r' % (name, CONFIDENCE_MAX_BINS, bins))
+    _match_pred(name, conf, ('pred', pred, (B, H, W)), ('target', target, (B, H, W)), ('mask', mask, (B, H, W)), ('target_ab', target_ab, (B, 2)),
+                ('into', into, (bins, 2)))
+    conf, cbs = _batch_view(conf.detach(), H * W)
+    pred, pbs = _batch_view(pred.detach(), H * W)
+    target, mask, target_ab = [None if t is None else _c(t.detach()) for t in (target, mask, target_ab)]
+    ws, nbytes = _workspace('dpf_confidence_curve_workspace_bytes', 'confidence_curve: shape B=%d H=%d W=%d bins=%d is not supported',
+                            B, H, W, bins, device=conf.device)
+    curve = into if into is not None else torch.empty((bins, 2), dtype=torch.float64, device=conf.device)
+    lib().call('dpf_confidence_curve', _ptr(conf), cbs, _ptr(pred), pbs, _ptr(target), _ptr(mask), _ptr(target_ab), B, H, W, bins,
+               int(into is not None), _ptr(ws), nbytes, _ptr(curve), _stream())
+    return curve
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-5, gscale=1.0):
     _need(param, grad, exp_avg, exp_avg_sq)
     lib().call('dpf_adam_step', _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), int(step), float(lr), float(beta1),

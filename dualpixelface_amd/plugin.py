@@ -11,7 +11,7 @@ import warnings
 
 import torch
 
-from . import normal_refine, ops, optim, postprocess, reconstruct
+from . import confidence, normal_refine, ops, optim, postprocess, reconstruct
 from .losses import loss_selector
 from .selectors import metric_selector, optimizer_selector, scheduler_selector
 from .dpnet import DPNetCore
@@ -28,6 +28,8 @@ class _PluginHooks(object):
         super(_PluginHooks, self).__init__(option)         # the model family's core (core.ArenaModule)
         self.loss_model = loss_selector(option)
         self.metric_model = metric_selector(option)
+        confidence.check_model(option)                     # (block on: a model without disparity hypotheses is refused by name)
+        self.confidence_table = None                       # the sparsification table of a validation pass (confidence.report), on the device
         self._adam = None                                  # the fused optimiser's state, kept by optim.py: 'adam' here,
         self._optim = None                                 # 'sgd' / 'rmsprop' here
 
@@ -40,6 +42,8 @@ class _PluginHooks(object):
         self.last_taps = results.pop('_taps')
         # (a batch without 'abvalue': the loss fits (a, b) and needs depth and inverse depth, not 'disp')
         fitted = self.loss_model.least_square(batch) and 'depth' in batch and 'idepth' in batch
+        if not self.training and confidence.active(self.option):    # estimate -> filter -> fit -> refine -> surface: all see the estimator's map
+            confidence.apply(self.option, results, batch)
         if not self.training and postprocess.active(self.option):   # the fit and the metric hooks below see the filtered map
             postprocess.apply(self.option, results, batch, guide=self._views(batch)[0])
         if self.training and ('disp' in batch or fitted or self.loss_model.label_free()):     # (label-free: the two views are enough)
@@ -49,7 +53,7 @@ class _PluginHooks(object):
         if not self.training and normal_refine.active(self.option):  # filter -> fit -> refine -> surface: metrics and mesh see the refined map
             normal_refine.apply(self.option, results, batch)
         if not self.training and reconstruct.active(self.option):   # the surface of the filtered map, placed with the fitted (a, b)
-            reconstruct.apply(self.option, results, batch, guide=self._views(batch)[0])
+            reconstruct.apply(self.option, results, confidence.gated(self.option, results, batch, 'reconstruct'), guide=self._views(batch)[0])
         results.pop('_heads', None)                         # (the heads' logits, for the loss hook only: losses.UNIMODALLoss)
         return results
 
@@ -87,7 +91,8 @@ class _PluginHooks(object):
     def validation_step(self, batch, batch_idx):
         results = self.forward(batch)
         if 'depth' in batch:
-            self.metric_model.forward(results, batch, target_type=self._target_type())
+            self.metric_model.forward(results, confidence.gated(self.option, results, batch, 'metrics'), target_type=self._target_type())
+        self.confidence_table = confidence.accumulate(self.option, results, batch, self.confidence_table, target_type=self._target_type())
         return results
 
     def validation_epoch_end(self, outputs):

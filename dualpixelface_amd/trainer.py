@@ -29,7 +29,7 @@ import torch
 
 from . import distributed as dd
 from . import optim
-from . import reconstruct
+from . import confidence, reconstruct
 
 
 def epoch_lr(option, epoch):
@@ -195,7 +195,8 @@ class Trainer(object):
                 outputs.append(None if results is None else i)
                 if write and results is not None:
                     guide = model._views(batch)[0] if hasattr(model, '_views') else None
-                    self.written_meshes += reconstruct.write_batch(self.option, self.workspace_path, i, results, batch, guide)
+                    self.written_meshes += reconstruct.write_batch(self.option, self.workspace_path, i, results,
+                                                                   confidence.gated(self.option, results, batch, 'reconstruct'), guide)
                 self.validated_batches.append(i)
         sel.flush()
         (model.test_epoch_end if test else model.validation_epoch_end)(outputs)
@@ -205,8 +206,32 @@ class Trainer(object):
             rows = {n: f.get_value() for n, f in zip(sel.metric_name, sel.metric_func) if f.index > 0}
         for f in sel.metric_func:
             f.clear()
+        self._confidence_report(model, device, share)
         model.train()
         return rows
+
+    def _confidence_report(self, model, device, share):
+        """option.confidence.report: the sparsification table the validation steps added into model.confidence_table, read ONCE here (summed
+        over the ranks by one all-reduce that every rank issues, whatever it counted) -> self.confidence_curve, the rows of
+        confidence.curve_rows, logged per bin edge; None with the report off.  The model's table is cleared for the next pass."""
+        s = confidence.settings(self.option)
+        self.confidence_curve = None
+        if not (s.enabled and s.report):
+            return
+        table = getattr(model, 'confidence_table', None)
+        model.confidence_table = None
+        if table is None:
+            table = confidence.new_table(s, device)
+        if share:
+            import torch.distributed as dist
+            dist.all_reduce(table, op=dist.ReduceOp.SUM)
+        self.confidence_curve = confidence.curve_rows(table.tolist())
+        self._log({'epoch': self.epoch, 'confidence_curve': self.confidence_curve})
+        if self.rank == 0:
+            print('confidence >= edge: coverage, mean |pred - label| (%s, %d bins)' % (s.measure, s.bins))
+            for row in self.confidence_curve:
+                err = 'none' if row['mean_error'] is None else '%.4f' % row['mean_error']
+                print('%10.4f %10.4f %10s' % (row['edge'], row['coverage'], err))
 
     def _all_rank_rows(self, sel, device):
         import torch.distributed as dist

@@ -696,6 +696,47 @@ int dpf_unimodal_backward(const float* const* logits_host, const float* target, 
                           const float* head_weights_host, const float* logsum, const double* stats, const float* gout,
                           float* const* dlogits_host, void* stream);
 
+/* ---- confidence maps and a modal estimate from the heads' hypothesis distribution (csrc/head_confidence.hip; option key confidence,
+ * dualpixelface_amd/confidence.py; not in the reference).  logits_host, B, n, D, h, w, L, H, W, align_corners and
+ * disp_host as in dpf_unimodal_forward: the distribution of a pixel is recomputed from the low-resolution logits, no [B, n, L, H, W]
+ * volume is read.  Per head and pixel, every sum in ascending l, in fp32, operation by operation (the file is built without contraction):
+ *   u_l, mx   the trilinear upsample of the logits and its maximum, exactly as dpf_unimodal_forward forms them
+ *   x_l       u_l - mx;  e_l = exp(x_l) (v_exp_f32 of x log2(e));  S = sum_l e_l;  p_l = e_l / S
+ *   lstar     the smallest l with u_l == mx (exact ties exist: under align_corners = 0 u_0 == u_1 bit for bit on whole regions); 0 where
+ *             every u_l is NaN
+ *   peak      1 / S, the probability of hypothesis lstar
+ *   Hent      logf(S) - sum_l p_l x_l;  entropy = 1 - Hent / logf((float)L), clamped to [0, 1]: 1 for a one-hot distribution, 0 for the
+ *             uniform one
+ *   mu        sum_l p_l d_l, the soft-argmin's value;  var = sum_l p_l ((d_l - mu) (d_l - mu));  spread = sqrtf(var)
+ *   M         sum of p_l over lo = max(0, lstar - window) .. hi = min(L - 1, lstar + window);  mass = fminf(M, 1)
+ *   modal     (sum of p_l d_l over lo .. hi) / M, the local expectation around the peak (M >= 1 / S > 0)
+ *   bad       any of S, Hent, var, modal not finite: peak = entropy = mass = 0, spread = modal = NaN
+ * peak, entropy, mass, spread, modal (fp32) and lstar (int32): each [B, n, H, W] device memory or NULL, at least one given; what a plane
+ * holds does not depend on which others are asked for.  One launch, one pixel per thread of a 32 x 8 tile, no workspace, no atomics, no
+ * host wait: the bits repeat and the call can be captured.  Refusals launch nothing: DPF_ERR_INVALID_ARG for a NULL logits_host, logits
+ * pointer or disp_host, no output at all, B, D, h, w, L, H, W <= 0, n outside 1..8, window outside 0..32, hypothesis values that are not
+ * finite and strictly ascending; DPF_ERR_UNSUPPORTED for D > 8, L > 32, L < 2, L no multiple of D, H or W not scale h, scale w,
+ * B n > 65535, H W >= 2^31, H or W > 2^24, or H beyond 65535 tiles of 8 rows.
+ *
+ * dpf_confidence_curve: the sparsification table of a confidence map, curve[bins][2] fp64 = (count, sum |pred - t|) per bin.  conf and
+ * pred: [H, W] planes of B samples, conf_batch_stride / pred_batch_stride floats apart (>= H W: head 0 of a [B, n, H, W] tensor is passed
+ * as it is); target [B, H, W]; mask [B, H, W] or NULL; target_ab [B, 2] = [b, a] or NULL: t = target, or a / target + b.  A pixel is
+ * counted when mask is NULL or > 0 and t, pred, conf are finite; its bin is (int) min(bins - 1, max(0, conf bins)) with conf bins one
+ * fp32 product, so conf = 1 lands in the last bin; |pred - t| is taken in fp32 and summed in fp64.  accumulate = 0 overwrites curve,
+ * otherwise the table is added to it.  Two launches: a workgroup walks 8 chunks of 256 consecutive pixels of a sample -- (bin, err) of a
+ * chunk to LDS, thread k < bins adds the entries of bin k in pixel order -- and leaves one row of 2 bins doubles in ws; one workgroup per
+ * table entry folds the rows in a fixed order.  No atomics: the same bits on every call.  ws: dpf_confidence_curve_workspace_bytes()
+ * bytes of 8-byte aligned device scratch (-1: shape refused), no initialisation needed.  DPF_ERR_INVALID_ARG for a NULL conf, pred, target
+ * or curve, B, H, W <= 0, bins outside 1..64, a batch stride below H W, a workspace too small or misaligned; DPF_ERR_UNSUPPORTED for
+ * B > 65535 or H W >= 2^31. */
+int dpf_head_confidence(const float* const* logits_host, int B, int n, int D, int h, int w, int L, int H, int W, int align_corners,
+                        const float* disp_host, int window, float* peak, float* entropy, float* mass, float* spread, float* modal,
+                        int* lstar, void* stream);
+long long dpf_confidence_curve_workspace_bytes(int B, int H, int W, int bins);
+int dpf_confidence_curve(const float* conf, long long conf_batch_stride, const float* pred, long long pred_batch_stride, const float* target,
+                         const float* mask, const float* target_ab, int B, int H, int W, int bins, int accumulate, void* ws,
+                         long long ws_bytes, double* curve, void* stream);
+
 /* ---- normal-guided depth refinement (csrc/normal_refine.hip; option key normal_refine, dualpixelface_amd/normal_refine.py; DESIGN.md
  * section 11): the correction of head 0 of a prediction that a normal map asks for, one sparse linear system per sample (Nehab et al.
  * 2005, in log-depth, where a pinhole camera makes it linear).  The geometry is the surface export's above: pred, pred_batch_stride,
