@@ -1,4 +1,4 @@
-// What the per-head tile losses share (normal_geo.hip, photometric.hip): a loss over pred [B, n <= 8, H, W] that is
+// What the per-head tile losses share (normal_geo.hip, photometric.hip, multiview.hip): a loss over pred [B, n <= 8, H, W] that is
 // sum_h w_h (sum of terms_h / count_h).  One workgroup per 32 x 8 tile of one head of one sample leaves one row of NP (sum, count) pairs
 // of fp64 in the workspace, part [n][B tiles][2 NP]; one workgroup folds the rows head by head (dpf_reduce.h) into the loss and the
 // stats record the backward reads its counts from.  A new loss of this family writes its per-tile kernel and its parameter checks, and

@@ -33,6 +33,7 @@
 // Backward: every pixel gathers its left, right, upper and lower pair, in that order.
 #include "dpf_head_loss.h"
 #include "dpf_image.h"
+#include "dpf_window.h"
 #include <math.h>
 
 extern "C" long long dpf_photometric_workspace_bytes(int B, int n, int H, int W);
@@ -42,7 +43,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kTW = kDpfTileW, kTH = kDpfTileH;      // output tile, one pixel per thread (dpf_head_loss.h has the plan)
-constexpr float kC1 = 0.0001f, kC2 = 0.0009f;  // 0.01^2, 0.03^2
 
 struct Photo {
   const float* pred;       // [B, n, H, W]
@@ -105,49 +105,6 @@ __device__ __forceinline__ bool warp_at(const Photo& g, const float* __restrict_
     *dJdpred = (g.sx * gx + g.sy * dv) * dD;
   }
   return true;
-}
-
-struct Window {
-  float muI, muJ, vI, vJ, cov, A1, A2, B1, B2, ssim;
-};
-
-// the window whose centre is (ly, lx) of the LDS tiles (row pitch LW): sums in row-major order of the values less the centre's I, so
-// that the variances are differences of small numbers
-template <int LW>
-__device__ __forceinline__ void window_of(const float* __restrict__ tI, const float* __restrict__ tJ, int ly, int lx, Window& w) {
-  const float c = tI[ly * LW + lx];
-  float sI = 0.f, sJ = 0.f, sII = 0.f, sJJ = 0.f, sIJ = 0.f;
-#pragma unroll
-  for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) {
-      const float i = tI[(ly + dy) * LW + lx + dx] - c, j = tJ[(ly + dy) * LW + lx + dx] - c;
-      sI = sI + i;
-      sJ = sJ + j;
-      sII = sII + i * i;
-      sJJ = sJJ + j * j;
-      sIJ = sIJ + i * j;
-    }
-  const float mI = sI / 9.f, mJ = sJ / 9.f;
-  w.muI = c + mI, w.muJ = c + mJ;
-  w.vI = sII / 9.f - mI * mI;
-  w.vJ = sJJ / 9.f - mJ * mJ;
-  w.cov = sIJ / 9.f - mI * mJ;
-  w.A1 = (2.f * w.muI) * w.muJ + kC1;
-  w.A2 = 2.f * w.cov + kC2;
-  w.B1 = (w.muI * w.muI + w.muJ * w.muJ) + kC1;
-  w.B2 = (w.vI + w.vJ) + kC2;
-  w.ssim = (w.A1 * w.A2) / (w.B1 * w.B2);
-}
-
-template <int LW>
-__device__ __forceinline__ bool all_nine(const unsigned char* __restrict__ tw, int ly, int lx) {
-  bool ok = true;
-#pragma unroll
-  for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) ok = ok && tw[(ly + dy) * LW + lx + dx];
-  return ok;
 }
 
 // grid (ceil(W / 32), ceil(H / 8), B n), 256 threads = 8 rows x 32 columns.  part: [n][B tiles][2]

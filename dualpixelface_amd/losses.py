@@ -5,7 +5,7 @@ Class names follow the reference's lookup rule ``<NAME.upper()>Loss`` (loss_sele
 """
 import torch
 
-from . import normal_geo, ops, photometric, unimodal
+from . import multiview, normal_geo, ops, photometric, unimodal
 from .core import reference_key
 
 
@@ -238,9 +238,51 @@ class UNIMODALLoss(_DepthLoss):
         return {'loss': loss, 'abvalue': batch['abvalue']}
 
 
-LABEL_FREE = ('photometric', 'smoothness')
+class MULTIVIEWLoss(_HeadWeights):
+    """The multi-view photometric loss (csrc/multiview.hip; it stands where the reference has
+    src/loss/depth/folded.py, which cannot run): batch['centers'], the centre images of the neighbouring cameras, warped into the target
+    view through the depth every head of pred_depth predicts, batch['K'] / batch['P'] and batch['Ks'] / batch['Ps'], against
+    batch['center'].  Settings: the model config block multiview (multiview.settings); the first select_view views are used.  It reads
+    calibration but no label map, so it refuses no dp_conversion.  (a, b) is needed for target_type 'disp' only: batch['abvalue'], else
+    the fit, as in PHOTOMETRICLoss.  batch['conf'] is not read."""
+    name = 'multiview'
+    KEYS = ('center', 'centers', 'K', 'P', 'Ks', 'Ps')
+
+    def __init__(self, option):
+        super(MULTIVIEWLoss, self).__init__(option)
+        self.settings = multiview.settings(option)
+
+    def forward(self, preds, batch, target_type='disp', ab_of=None):
+        assert target_type in TARGET_TYPES
+        missing = [key for key in self.KEYS if key not in batch]
+        if missing:
+            raise NotImplementedError("the 'multiview' loss needs batch[%s], which %s missing from the batch (the FaceDP loader produces "
+                                      "them under use_multi with use_center_img and multi_view.use_center_img)"
+                                      % ("] and batch[".join(repr(k) for k in missing), 'is' if len(missing) == 1 else 'are'))
+        s = self.settings
+        pd, centers, Ks, Ps = preds['pred_depth'], batch['centers'], batch['Ks'], batch['Ps']
+        views = min(centers.shape[1] // 3, Ks.shape[1], Ps.shape[1])
+        if centers.dim() != 4 or centers.shape[1] % 3 or views < s.select_view:
+            raise NotImplementedError("the 'multiview' loss is set to select_view = %d, but the batch carries %d views (centers %s, Ks %s, Ps %s)"
+                                      % (s.select_view, views, tuple(centers.shape), tuple(Ks.shape), tuple(Ps.shape)))
+        S = s.select_view
+        src = centers[:, :3 * S].view(centers.shape[0], S, 3, centers.shape[2], centers.shape[3])
+        out, ab = {}, None
+        if target_type == 'disp':
+            ab = out['abvalue'] = (ab_of or conversion(preds, batch))()
+        elif 'abvalue' in batch:
+            out['abvalue'] = batch['abvalue']
+        f32 = lambda t: t if t.dtype == torch.float32 else t.to(torch.float32)                        # noqa: E731
+        out['loss'] = ops.multiview_loss(pd, f32(batch['center']), f32(src), f32(batch['K']), f32(batch['P']), f32(Ks[:, :S]), f32(Ps[:, :S]),
+                                         ab=None if ab is None else f32(ab), mask=batch.get('mask'),
+                                         head_weights=self.head_weights(pd.shape[1]), target_type=target_type, weight_ssim=s.weight_ssim,
+                                         alpha=s.alpha, scale=s.scale, min_depth=s.min_depth)
+        return out
+
+
+LABEL_FREE = ('photometric', 'smoothness', 'multiview')
 _BANK = {'smoothL1': SMOOTHL1Loss, 'silog': SILOGLoss, 'cosine': COSINELoss, 'normal_geo': NORMAL_GEOLoss, 'photometric': PHOTOMETRICLoss,
-         'smoothness': SMOOTHNESSLoss, 'unimodal': UNIMODALLoss}
+         'smoothness': SMOOTHNESSLoss, 'unimodal': UNIMODALLoss, 'multiview': MULTIVIEWLoss}
 
 
 class loss_selector(object):
@@ -258,7 +300,8 @@ class loss_selector(object):
         return takes_least_square(batch)
 
     def label_free(self):
-        """Every configured loss is one of the two that read no label: a batch of only the two views trains."""
+        """Every configured loss is one of those that read no label map: a batch of only the views (and, for 'multiview', the rig's
+        calibration) trains."""
         return bool(self.loss_name) and all(name in LABEL_FREE for name in self.loss_name)
 
     def forward(self, results, batch, target_type='disp'):

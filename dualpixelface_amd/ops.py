@@ -2084,6 +2084,111 @@ def smoothness_loss(pred, guide_rgb, mask=None, head_weights=(1.0,), gamma=10.0,
     return HeadLossFn.apply(pred, _SMOOTHNESS, held, lead, False)
 
 
+MULTIVIEW_STATS = 136       # doubles: count per (head, view) [8 h + v], term sums [64 + 8 h + v], views counted per head [128 + h]
+MULTIVIEW_MAX_VIEWS = 8
+
+
+class MultiviewFn(torch.autograd.Function):
+    """HeadLossFn for the loss whose shape has a view axis beside pred's (csrc/multiview.hip): -> 0-dim loss, and with want_extras
+    warped, counted, sample_xy and the luminance planes.  The C argument orders agree as in that family: forward `lead | ws, nbytes | luma
+    | stats, out | extras`, backward `lead | luma | stats, gout, dpred`.  The rig, the workspace, stats and the planes are fresh tensors
+    (rig, planes and stats are saved for the backward), gout is read on the device and nothing is read on the host, so the call is
+    capturable inside the train-step graph.  Only pred receives a gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, held, rig, lead, dims, want_extras):
+        B, n, S, H, W, Hs, Ws = dims
+        dev = pred.device
+        ws, nbytes = _workspace('dpf_multiview_workspace_bytes', 'multiview_loss: shape B=%d n=%d S=%d H=%d W=%d is not supported', B, n, S, H, W,
+                                device=dev)
+        stats = torch.empty(MULTIVIEW_STATS, dtype=torch.float64, device=dev)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        luma = torch.empty(B * H * W + B * S * Hs * Ws, dtype=torch.float32, device=dev)
+        extras = [None, None, None]
+        if want_extras:
+            extras = [torch.empty((B, n, S, H, W), dtype=torch.float32, device=dev), torch.empty((B, n, S, H, W), dtype=torch.uint8, device=dev),
+                      torch.empty((B, n, S, 2, H, W), dtype=torch.float32, device=dev)]
+        lib().call('dpf_multiview_forward', *lead, _ptr(ws), nbytes, _ptr(luma), _ptr(stats), _ptr(out), *[_ptr(t) for t in extras], _stream())
+        ctx.save_for_backward(pred, stats, luma, rig, *held)
+        ctx.lead = lead
+        if want_extras:
+            planes = (luma[:B * H * W].view(B, H, W), luma[B * H * W:].view(B, S, Hs, Ws))
+            ctx.mark_non_differentiable(*extras, *planes)
+            return (out,) + tuple(extras) + planes
+        return out
+
+    @staticmethod
+    def backward(ctx, gout, *unused):
+        pred, stats, luma = ctx.saved_tensors[:3]
+        gout = _c(gout)
+        _need(gout)
+        dpred = torch.empty_like(pred)
+        lib().call('dpf_multiview_backward', *ctx.lead, _ptr(luma), _ptr(stats), _ptr(gout), _ptr(dpred), _stream())
+        return dpred, None, None, None, None, None
+
+
+def multiview_rig(Kmat, Pmat, Ks, Ps):
+    """csrc/multiview.hip: the twelve fp32 numbers per (sample, view) that carry a pixel of the target view and its depth into a
+    neighbouring view, from K [B, 3, 3], P [B, 4, 4], Ks [B, S, 3, 3], Ps [B, S, 4, 4] (device float32) -> rig [B, S, 12] = (M row-major,
+    t), M = Ks T[:3, :3] K^-1 and t = Ks T[:3, 3] with T = Ps P^-1, formed in fp64 on the device.  Nothing is read on the host."""
+    _need(Kmat, Pmat, Ks, Ps, dtypes=_F32, contiguous=False)
+    if Ks is None or Ks.dim() != 4:
+        raise DpfError('multiview_rig: Ks %s is not [B, S, 3, 3]' % (None if Ks is None else tuple(Ks.shape),))
+    B, S = Ks.shape[:2]
+    if not 1 <= S <= MULTIVIEW_MAX_VIEWS:
+        raise DpfError('multiview_rig: %d views, 1 to %d are supported' % (S, MULTIVIEW_MAX_VIEWS))
+    for name, t, shape in (('K', Kmat, (B, 3, 3)), ('P', Pmat, (B, 4, 4)), ('Ks', Ks, (B, S, 3, 3)), ('Ps', Ps, (B, S, 4, 4))):
+        if t is None or tuple(t.shape) != shape:
+            raise DpfError('multiview_rig: %s %s, %s expected' % (name, None if t is None else tuple(t.shape), list(shape)))
+    held = [_c(t.detach()) for t in (Kmat, Pmat, Ks, Ps)]
+    rig = torch.empty((B, S, 12), dtype=torch.float32, device=Ks.device)
+    lib().call('dpf_multiview_rig', *[_ptr(t) for t in held], B, S, _ptr(rig), _stream())
+    return rig
+
+
+def multiview_loss(pred, tgt_rgb, src_rgb, Kmat, Pmat, Ks, Ps, ab=None, mask=None, head_weights=(1.0,), target_type='disp', weight_ssim=0.8,
+                   alpha=1.0, scale=0.1, min_depth=1e-3, return_warped=False):
+    """csrc/multiview.hip: the luminance of the source images src_rgb [B, S <= 8, 3, Hs, Ws] (a slice along dim 1 of a wider tensor is
+    taken as it is) sampled bilinearly where the depth every head of pred [B, n <= 8, H, W] predicts sends the pixels of the target
+    view, against the luminance of tgt_rgb [B, 3, H, W] -> the 0-dim loss sum_h w_h mean over the views that count a pixel of (mean over
+    the counted pixels of weight_ssim clamp((1 - SSIM_3x3) / 2, 0, 1) + (1 - weight_ssim) rho(J - I; alpha, scale)), rho Barron's general
+    robust loss.  The depth is a / (pred - b) for 'disp' (ab [B, 2] = [b, a], needed then only), 1 / pred for
+    'idepth', pred for 'depth'; a pixel is usable where pred and the depth are finite, the depth >= min_depth and mask (None: everywhere)
+    > 0; the geometry is multiview_rig's.  The gradient reaches pred only.  With return_warped also warped [B, n, S, H, W] fp32 (0 where
+    not warpable), counted [B, n, S, H, W] uint8, sample_xy [B, n, S, 2, H, W] fp32 and the luminance planes [B, H, W], [B, S, Hs, Ws]."""
+    code = _target_code('multiview_loss', target_type, ())
+    if target_type == 'disp' and ab is None:
+        raise DpfError("multiview_loss: target_type 'disp' needs ab [B, 2] = [b, a]")
+    ab = ab if target_type == 'disp' else None
+    _need(pred, tgt_rgb, src_rgb, ab, mask, dtypes=_F32, contiguous=False)
+    if pred.dim() != 4:
+        raise DpfError('multiview_loss: pred %s is not [B, n, H, W]' % (tuple(pred.shape),))
+    if tgt_rgb is None or src_rgb is None or src_rgb.dim() != 5 or src_rgb.shape[2] != 3:
+        raise DpfError('multiview_loss: tgt_rgb [B, 3, H, W] and src_rgb [B, S, 3, Hs, Ws] are needed')
+    B, n, H, W = pred.shape
+    S, Hs, Ws = src_rgb.shape[1], src_rgb.shape[3], src_rgb.shape[4]
+    _match_pred('multiview_loss', pred, ('tgt_rgb', tgt_rgb, (B, 3, H, W)), ('src_rgb', src_rgb, (B, S, 3, Hs, Ws)), ('ab', ab, (B, 2)),
+                ('mask', mask, (B, H, W)))
+    if len(head_weights) != n:
+        raise DpfError('multiview_loss: %d head weights for %d heads' % (len(head_weights), n))
+    if not 0.0 <= float(weight_ssim) <= 1.0:
+        raise DpfError('multiview_loss: weight_ssim must lie in [0, 1], got %r' % (weight_ssim,))
+    if float(alpha) != float(alpha) or float(alpha) in (float('inf'), -float('inf')):
+        raise DpfError('multiview_loss: alpha must be finite (the limits at +-infinity are not built), got %r' % (alpha,))
+    for name, v in (('scale', scale), ('min_depth', min_depth)):
+        if not 0.0 < float(v) < float('inf'):
+            raise DpfError('multiview_loss: %s must be positive, got %r' % (name, v))
+    rig = multiview_rig(Kmat, Pmat, Ks, Ps)
+    if tuple(rig.shape[:2]) != (B, S):
+        raise DpfError('multiview_loss: Ks %s does not match src_rgb %s' % (tuple(Ks.shape), tuple(src_rgb.shape)))
+    pred = _c(pred)
+    src, stride = _batch_view(src_rgb.detach(), S * 3 * Hs * Ws)
+    held = (_c(tgt_rgb.detach()), src, None if ab is None else _c(ab.detach()), None if mask is None else _c(mask.detach()))
+    lead = (_ptr(pred), _ptr(held[0]), _ptr(src), stride, _ptr(rig), _ptr(held[2]), _ptr(held[3]), B, n, S, H, W, Hs, Ws, code,
+            float(weight_ssim), float(alpha), float(scale), float(min_depth), _normalizer_floats(), _host_floats(head_weights))
+    return MultiviewFn.apply(pred, held, rig, lead, (B, n, S, H, W, Hs, Ws), bool(return_warped))
+
+
 UNIMODAL_STATS = 16         # doubles: count per head [0, 8), term sum per head [8, 16)
 UNIMODAL_MAX_HEADS, UNIMODAL_MAX_D, UNIMODAL_MAX_L = 8, 8, 32
 

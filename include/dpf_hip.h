@@ -655,6 +655,42 @@ int dpf_smoothness_backward(const float* pred, const float* guide_rgb, const flo
                             const float* norm_host, const float* head_weights_host, const float* luma, const double* stats,
                             const float* gout, float* dpred, void* stream);
 
+/* ---- multi-view photometric loss (csrc/multiview.hip; loss_type 'multiview', dualpixelface_amd/losses.py): the
+ * centre images of S <= 8 neighbouring cameras warped into the target view through the predicted depth and compared with the target
+ * image.  pred [B, n <= 8, H, W]; tgt_rgb [B, 3, H, W] and src_rgb [B, S, 3, Hs, Ws] (samples src_stride floats apart, >= 3 S Hs Ws),
+ * normalised images; K [B, 3, 3] the target intrinsics of the crop, P [B, 4, 4], Ks [B, S, 3, 3], Ps [B, S, 4, 4], all device fp32;
+ * ab [B, 2] = [b, a] (needed for target type 0 only); mask [B, H, W] or NULL; norm_host and head_weights_host as the photometric loss
+ * takes them.  rig [B, S, 12] and luma (B H W + B S Hs Ws floats: target planes, then source planes) are device floats the CALLER
+ * owns: dpf_multiview_rig fills rig, the forward fills luma, forward and backward read both.
+ *   rig      in fp64: T = Ps[s, v] P[s]^-1 (general inverse), M = Ks[s, v] T[:3, :3] K[s]^-1, t = Ks[s, v] T[:3, 3]; M row-major, then t
+ *   z        pred (target type 2), 1 / pred (1), a / (pred - b) (0); usable: pred and z finite, z >= min_depth, mask NULL or > 0
+ *   sample   q = z M [x, y, 1] + t; warpable: q_z > 0 and (u, v) = (q_x, q_y) / q_z in [0, Ws - 1] x [0, Hs - 1]; J the bilinear sample
+ *            of the photometric loss; counted: the 3 x 3 window lies in the image and its nine pixels are warpable
+ *   term     weight_ssim clamp((1 - SSIM) / 2, 0, 1) + (1 - weight_ssim) rho(J - I; alpha, scale), rho Barron's general loss with its
+ *            own cases at alpha = 2 and alpha = 0 (csrc/multiview.hip)
+ *   loss     sum_h w_h mean over the views with count_hv > 0 of (sum terms_hv / count_hv)
+ * dpf_multiview_forward: out[0] = the loss, stats = 136 doubles: count_hv at [8 h + v], the term sums at [64 + 8 h + v], the views
+ * counted per head at [128 + h].  warped_out [B, n, S, H, W] fp32 and counted_out [B, n, S, H, W] uint8: both NULL or both given;
+ * sample_xy_out [B, n, S, 2, H, W] fp32 (u then v, 0 where not warpable) only with them.  Three launches; ws:
+ * dpf_multiview_workspace_bytes() bytes, 8-byte aligned, no initialisation.  dpf_multiview_backward: dpred [B, n, H, W], every element
+ * written = gout[0] * d loss / d pred, one launch, a gather with the view loop inside the thread.  No atomics, nothing allocates or waits
+ * on the host.  Refusals launch nothing: DPF_ERR_INVALID_ARG for a NULL pointer (but mask, ab unless the target type is 0, and the
+ * optional outputs), a size <= 0, n or S outside 1..8, a target_type outside 0..2, weight_ssim outside [0, 1], alpha not finite, scale
+ * or min_depth <= 0 or not finite, src_stride < 3 S Hs Ws, or a bad workspace; DPF_ERR_UNSUPPORTED for B n S > 65535, B (S + 1) > 65535,
+ * H W or Hs Ws >= 2^31, or H beyond 65535 tiles of 8 rows. */
+long long dpf_multiview_workspace_bytes(int B, int n, int S, int H, int W);
+int dpf_multiview_rig(const float* K, const float* P, const float* Ks, const float* Ps, int B, int S, float* rig, void* stream);
+int dpf_multiview_forward(const float* pred, const float* tgt_rgb, const float* src_rgb, long long src_stride, const float* rig,
+                          const float* ab, const float* mask, int B, int n, int S, int H, int W, int Hs, int Ws, int target_type,
+                          float weight_ssim, float alpha, float scale, float min_depth, const float* norm_host,
+                          const float* head_weights_host, void* ws, long long ws_bytes, float* luma, double* stats, float* out,
+                          float* warped_out, unsigned char* counted_out, float* sample_xy_out, void* stream);
+int dpf_multiview_backward(const float* pred, const float* tgt_rgb, const float* src_rgb, long long src_stride, const float* rig,
+                           const float* ab, const float* mask, int B, int n, int S, int H, int W, int Hs, int Ws, int target_type,
+                           float weight_ssim, float alpha, float scale, float min_depth, const float* norm_host,
+                           const float* head_weights_host, const float* luma, const double* stats, const float* gout, float* dpred,
+                           void* stream);
+
 /* ---- unimodal loss (csrc/unimodal.hip; loss_type 'unimodal', dualpixelface_amd/losses.py; not in the reference):
  * the cross-entropy between the hypothesis distribution of every disparity head and a Laplace distribution over the hypotheses centred
  * on the label.  Neither pass reads or writes a [B, n, L, H, W] volume: both recompute the distribution of a pixel from the

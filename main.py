@@ -5,7 +5,8 @@
 builds the layered option object, instantiates the plugin through ``src/model/model_selector.py`` and runs fit / test with the
 native trainer (dualpixelface_amd/trainer.py) instead of pytorch_lightning.  One process per GPU under torchrun.
 ``--synthetic N`` replaces the FaceDP loaders by N synthetic samples (no dataset is needed for a smoke run): N to train on and N // 4 to
-evaluate, or all N to evaluate where the config writes a mesh per sample (reconstruct.write_ply).
+evaluate, or all N to evaluate where the config writes a mesh per sample (reconstruct.write_ply).  Under ``use_multi`` the samples are
+those of the plane scene with its neighbouring cameras (dualpixelface_amd/synthetic_multiview.py).
 """
 import argparse
 import os
@@ -51,6 +52,13 @@ def main():
     train_loader = val_loader = None
     if args.synthetic:
         from dualpixelface_amd.synthetic_data import synthetic_loader
+        if getattr(opt, 'use_multi', False):
+            from dualpixelface_amd import multiview
+            from dualpixelface_amd.synthetic_multiview import synthetic_multiview_loader
+            views = multiview.settings(opt).select_view
+
+            def synthetic_loader(length, height, width, batch_size, shuffle=False, seed=0):
+                return synthetic_multiview_loader(length, height, width, batch_size, views=views, shuffle=shuffle, seed=seed)
         train_loader = synthetic_loader(args.synthetic, args.height, args.width, opt.batch_size, shuffle=True, seed=1)
         from dualpixelface_amd import reconstruct
         held_out = args.synthetic if reconstruct.settings(opt).write_ply else max(1, args.synthetic // 4)
