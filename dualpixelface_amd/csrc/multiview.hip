@@ -29,6 +29,16 @@
 // own window, times d J / d z = g_x (m_x q_z - q_x m_z) / q_z^2 + g_y (m_y q_z - q_y m_z) / q_z^2 of its bilinear sample and the view's
 // share w_h / (views counted_h count_hv); the views add up in their order, and d z / d pred (1, -1 / pred^2, -a / (pred - b)^2) and gout
 // multiply the sum.  No atomics and no scratch: the bits repeat.
+//
+// Occlusion handling (dpf_multiview_occ_*, dpf_multiview_zbuffer; ops.multiview_loss(reduce=, visibility=); off in the entry points above):
+//   zbuffer  visibility 'zbuffer': per (sample, head, view) Hc x Wc cells of cell x cell source pixels, each the smallest q_z any warpable
+//            pixel splats into it (an integer atomicMin on the bits of the positive float: whatever the order of arrival, the same bits);
+//            visible: q_z <= zmin + tolerance * zmin of the pixel's own cell; seen = warpable and visible stands for warpable in `counted`
+//   min      reduce 'min': per head and pixel the smallest term over the views that count it, the lowest view at a tie; loss =
+//            sum_h w_h (sum of those terms / count_h), count_h the pixels some view counts
+// Fill and splat are launches of their own ahead of the tile kernel (a cell's minimum comes from pixels anywhere in the image).  The
+// tile kernels are the ones above as templates: forward_tile<kVis>, backward_tile<kVis, kMin> (the plain kernels are the <false>
+// instances), and for 'min' a forward with the view loop inside that writes the selection plane the backward reads with a halo of 1.
 #include "dpf_head_loss.h"
 #include "dpf_image.h"
 #include "dpf_window.h"
@@ -196,18 +206,28 @@ __device__ __forceinline__ bool depth_at(const MV& g, const float* __restrict__ 
   return true;
 }
 
-// the warp of the usable pixel (y, x) of depth z into the source plane ys: -> warpable; J, the sample point, and where asked d J / d z
-__device__ __forceinline__ bool warp_at(const MV& g, const Rig& r, const float* __restrict__ ys, float z, int y, int x, float& J, float& u,
-                                        float& v, float* dJdz) {
-  J = 0.f, u = 0.f, v = 0.f;
+// the projection of the usable pixel (y, x) of depth z into a source view: -> warpable; m = M [x, y, 1], q = z m + t, the sample point
+struct Proj { float mx, my, mz, qx, qy, qz, su, sv; };
+
+__device__ __forceinline__ bool project_at(const MV& g, const Rig& r, float z, int y, int x, Proj& p) {
   const float xf = (float)x, yf = (float)y;
-  const float mx = (r.m[0] * xf + r.m[1] * yf) + r.m[2];
-  const float my = (r.m[3] * xf + r.m[4] * yf) + r.m[5];
-  const float mz = (r.m[6] * xf + r.m[7] * yf) + r.m[8];
-  const float qx = z * mx + r.t[0], qy = z * my + r.t[1], qz = z * mz + r.t[2];
-  if (!(qz > 0.f)) return false;
-  const float su = qx / qz, sv = qy / qz;
-  if (!(su >= 0.f && su <= (float)(g.Ws - 1) && sv >= 0.f && sv <= (float)(g.Hs - 1))) return false;
+  p.mx = (r.m[0] * xf + r.m[1] * yf) + r.m[2];
+  p.my = (r.m[3] * xf + r.m[4] * yf) + r.m[5];
+  p.mz = (r.m[6] * xf + r.m[7] * yf) + r.m[8];
+  p.qx = z * p.mx + r.t[0], p.qy = z * p.my + r.t[1], p.qz = z * p.mz + r.t[2];
+  if (!(p.qz > 0.f)) return false;
+  p.su = p.qx / p.qz, p.sv = p.qy / p.qz;
+  return p.su >= 0.f && p.su <= (float)(g.Ws - 1) && p.sv >= 0.f && p.sv <= (float)(g.Hs - 1);
+}
+
+// the warp of the usable pixel (y, x) of depth z into the source plane ys: -> warpable; J, the sample point, where asked d J / d z and
+// q_z (the occlusion modes compare it with the z-buffer)
+__device__ __forceinline__ bool warp_at(const MV& g, const Rig& r, const float* __restrict__ ys, float z, int y, int x, float& J, float& u,
+                                        float& v, float* dJdz, float* qz_out = nullptr) {
+  J = 0.f, u = 0.f, v = 0.f;
+  Proj p;
+  if (!project_at(g, r, z, y, x, p)) return false;
+  const float mx = p.mx, my = p.my, mz = p.mz, qx = p.qx, qy = p.qy, qz = p.qz, su = p.su, sv = p.sv;
   const float fx0 = floorf(su), fy0 = floorf(sv);
   const float fx = su - fx0, fy = sv - fy0;
   const int x0 = min((int)fx0, g.Ws - 1), y0 = min((int)fy0, g.Hs - 1);      // (the clamp acts only where Ws - 1 is no fp32 number)
@@ -219,6 +239,7 @@ __device__ __forceinline__ bool warp_at(const MV& g, const Rig& r, const float* 
   const float top = v00 + fx * dt, bot = v10 + fx * db;
   const float dv = bot - top;
   J = top + fy * dv, u = su, v = sv;
+  if (qz_out) *qz_out = qz;
   if (dJdz) {
     const float gx = dt + fy * (db - dt);
     const float qz2 = qz * qz;
@@ -228,25 +249,61 @@ __device__ __forceinline__ bool warp_at(const MV& g, const Rig& r, const float* 
   return true;
 }
 
-// grid (ceil(W / 32), ceil(H / 8), B n S), 256 threads = 8 rows x 32 columns.  part: [n][S][B tiles][2]
-__global__ __launch_bounds__(256) void mv_forward_kernel(MV g, double* __restrict__ part, float* __restrict__ warped_out,
-                                                         unsigned char* __restrict__ counted_out, float* __restrict__ xy_out) {
-  constexpr int LW = kTW + 2, LH = kTH + 2;
-  __shared__ float tI[LH * LW], tJ[LH * LW];
-  __shared__ unsigned char tw[LH * LW];
-  const int t = threadIdx.x;
+// ---- occlusion (visibility 'zbuffer'): one z-buffer of Hc x Wc cells per (sample, head, view), the bits of the smallest q_z splatted
+// into each cell.  A warpable pixel is visible where q_z <= zmin + tolerance * zmin of its own cell, and "seen" = warpable and visible
+// stands wherever the loss says warpable.  The buffer is the caller's: forward and backward read the same bits.
+struct Occ {
+  const unsigned* zbuf;    // [B, n, S, Hc, Wc], or NULL: visibility off
+  int cell, Hc, Wc;
+  float tol;
+};
+
+__device__ __forceinline__ size_t cell_of(const Occ& oc, float su, float sv) {
+  const int cx = min(max((int)floorf(su + 0.5f) / oc.cell, 0), oc.Wc - 1);
+  const int cy = min(max((int)floorf(sv + 0.5f) / oc.cell, 0), oc.Hc - 1);
+  return (size_t)cy * oc.Wc + cx;
+}
+
+// zb: the z-buffer of this (sample, head, view)
+__device__ __forceinline__ bool visible_at(const Occ& oc, const unsigned* __restrict__ zb, float qz, float su, float sv) {
+  const float zmin = __uint_as_float(zb[cell_of(oc, su, sv)]);
+  const float slack = oc.tol * zmin;
+  return qz <= zmin + slack;
+}
+
+// grid (blocks, B n S): every cell to +infinity
+__global__ __launch_bounds__(256) void mv_zfill_kernel(unsigned* __restrict__ zbuf, long long cells) {
+  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < cells; i += (long long)gridDim.x * kBlock) zbuf[i] = 0x7f800000u;
+}
+
+// grid (ceil(W / 32), ceil(H / 8), B n S): every warpable pixel splats q_z into its cell.  Positive floats order like their bit patterns,
+// so the integer minimum is the float minimum whatever the order of arrival.
+__global__ __launch_bounds__(256) void mv_zsplat_kernel(MV g, Occ oc, unsigned* __restrict__ zbuf) {
   const int sh = blockIdx.z / g.S, v = blockIdx.z - sh * g.S;
   const int s = sh / g.n, h = sh - s * g.n;
-  const int B = gridDim.z / (g.n * g.S);
+  const int x = blockIdx.x * kTW + (threadIdx.x & (kTW - 1)), y = blockIdx.y * kTH + threadIdx.x / kTW;
+  if (x >= g.W || y >= g.H) return;
+  const size_t HW = (size_t)g.H * g.W;
+  const float b = g.target_type == 0 ? g.ab[2 * (size_t)s] : 0.f, a = g.target_type == 0 ? g.ab[2 * (size_t)s + 1] : 0.f;
+  float z;
+  if (!depth_at(g, g.pred + ((size_t)s * g.n + h) * HW, (size_t)s * HW, a, b, (size_t)y * g.W + x, z, nullptr)) return;
+  Proj p;
+  if (!project_at(g, load_rig(g, s, v), z, y, x, p)) return;
+  atomicMin(zbuf + (size_t)blockIdx.z * ((size_t)oc.Hc * oc.Wc) + cell_of(oc, p.su, p.sv), __float_as_uint(p.qz));
+}
+
+// the tile of the forward kernels: I, J and the seen flag of view v in LDS with a halo of 1 (seen = warpable where kVis is false)
+template <bool kVis>
+__device__ __forceinline__ void load_view_tile(const MV& g, const Occ& oc, int s, int h, int v, const float* __restrict__ predh, float a, float b,
+                                               int x0, int y0, float* __restrict__ tI, float* __restrict__ tJ, unsigned char* __restrict__ tw,
+                                               float* __restrict__ xy_out) {
+  constexpr int LW = kTW + 2, LH = kTH + 2;
   const size_t HW = (size_t)g.H * g.W, sbase = (size_t)s * HW;
-  const float* __restrict__ predh = g.pred + ((size_t)s * g.n + h) * HW;
+  const size_t shv = ((size_t)s * g.n + h) * g.S + v, obase = shv * HW;
   const float* __restrict__ yr = g.ytgt + sbase;
   const float* __restrict__ ys = g.ysrc + ((size_t)s * g.S + v) * ((size_t)g.Hs * g.Ws);
-  const float b = g.target_type == 0 ? g.ab[2 * (size_t)s] : 0.f, a = g.target_type == 0 ? g.ab[2 * (size_t)s + 1] : 0.f;
   const Rig r = load_rig(g, s, v);
-  const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
-  const size_t obase = (((size_t)s * g.n + h) * g.S + v) * HW;
-  for (int i = t; i < LH * LW; i += kBlock) {
+  for (int i = threadIdx.x; i < LH * LW; i += kBlock) {
     const int ly = i / LW, lx = i - ly * LW;
     const int y = y0 - 1 + ly, x = x0 - 1 + lx;
     float I = 0.f, J = 0.f, su = 0.f, sv = 0.f;
@@ -254,15 +311,125 @@ __global__ __launch_bounds__(256) void mv_forward_kernel(MV g, double* __restric
     if (y >= 0 && y < g.H && x >= 0 && x < g.W) {
       const size_t o = (size_t)y * g.W + x;
       I = yr[o];
-      float z;
-      ok = depth_at(g, predh, sbase, a, b, o, z, nullptr) && warp_at(g, r, ys, z, y, x, J, su, sv, nullptr);
+      float z, qz = 0.f;
+      ok = depth_at(g, predh, sbase, a, b, o, z, nullptr) && warp_at(g, r, ys, z, y, x, J, su, sv, nullptr, kVis ? &qz : nullptr);
       if (xy_out && ly >= 1 && ly <= kTH && lx >= 1 && lx <= kTW) {
         xy_out[2 * obase + o] = su;
         xy_out[2 * obase + HW + o] = sv;
       }
+      if (kVis) ok = ok && visible_at(oc, oc.zbuf + shv * ((size_t)oc.Hc * oc.Wc), qz, su, sv);
     }
     tI[i] = I, tJ[i] = J, tw[i] = ok ? 1 : 0;
   }
+}
+
+// the term of the window whose centre is (ly, lx) of the forward tiles
+__device__ __forceinline__ float term_at(const MV& g, const float* __restrict__ tI, const float* __restrict__ tJ, int ly, int lx) {
+  constexpr int LW = kTW + 2;
+  Window w;
+  window_of<LW>(tI, tJ, ly, lx, w);
+  const float ds = fminf(fmaxf((1.f - w.ssim) / 2.f, 0.f), 1.f);
+  const float d = tJ[ly * LW + lx] - tI[ly * LW + lx];
+  return g.wssim * ds + (1.f - g.wssim) * rho_of(g.rho, d);
+}
+
+// reduce 'min': grid (ceil(W / 32), ceil(H / 8), B n), the view loop inside.  Per pixel the smallest term over the views that count it
+// (the lowest view wins a tie) and that view into sel (255: none).  part: [n][B tiles][kMinRow] = term sum, count, pixels won per view
+constexpr int kMinRow = 2 + kMaxViews;
+
+template <bool kVis>
+__global__ __launch_bounds__(256) void mv_forward_min_kernel(MV g, Occ oc, double* __restrict__ part, unsigned char* __restrict__ sel,
+                                                             float* __restrict__ warped_out, unsigned char* __restrict__ counted_out,
+                                                             float* __restrict__ xy_out, unsigned char* __restrict__ visible_out) {
+  constexpr int LW = kTW + 2, LH = kTH + 2;
+  __shared__ float tI[LH * LW], tJ[LH * LW];
+  __shared__ unsigned char tw[LH * LW];
+  const int t = threadIdx.x;
+  const int s = blockIdx.z / g.n, h = blockIdx.z - s * g.n;
+  const size_t HW = (size_t)g.H * g.W;
+  const float* __restrict__ predh = g.pred + ((size_t)s * g.n + h) * HW;
+  const float b = g.target_type == 0 ? g.ab[2 * (size_t)s] : 0.f, a = g.target_type == 0 ? g.ab[2 * (size_t)s + 1] : 0.f;
+  const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+  const int tx = t & (kTW - 1), ty = t / kTW;
+  const int x = x0 + tx, y = y0 + ty, ly = ty + 1, lx = tx + 1;
+  const bool inside = x < g.W && y < g.H;
+  float best = 0.f;
+  int won = 255;
+  for (int v = 0; v < g.S; ++v) {
+    __syncthreads();                                       // the last view's readers are done
+    load_view_tile<kVis>(g, oc, s, h, v, predh, a, b, x0, y0, tI, tJ, tw, xy_out);
+    __syncthreads();
+    if (inside) {
+      const bool counted = x >= 1 && x + 1 < g.W && y >= 1 && y + 1 < g.H && all_nine<LW>(tw, ly, lx);
+      if (counted) {
+        const float term = term_at(g, tI, tJ, ly, lx);
+        if (won == 255 || term < best) best = term, won = v;
+      }
+      if (warped_out) {
+        const size_t o = (((size_t)s * g.n + h) * g.S + v) * HW + (size_t)y * g.W + x;
+        warped_out[o] = tJ[ly * LW + lx];
+        counted_out[o] = counted ? 1 : 0;
+        visible_out[o] = tw[ly * LW + lx];
+      }
+    }
+  }
+  double acc[kMinRow];
+#pragma unroll
+  for (int k = 0; k < kMinRow; ++k) acc[k] = 0.0;
+  if (inside) {
+    sel[((size_t)s * g.n + h) * HW + (size_t)y * g.W + x] = (unsigned char)won;
+    if (won != 255) {
+      acc[0] = (double)best, acc[1] = 1.0;
+#pragma unroll
+      for (int k = 0; k < kMaxViews; ++k) acc[2 + k] = won == k ? 1.0 : 0.0;
+    }
+  }
+  dpf_block_reduce_d<kMinRow>(acc, part + dpf_tile_part_row(s, h, g.n) * kMinRow);
+}
+
+// one block: folds the rows of reduce 'min' head by head.  stats: the pixels view v won at [8 h + v], the term sum at [64 + 8 h], the
+// pixels counted in some view at [128 + h]
+__global__ __launch_bounds__(256) void mv_fold_min_kernel(const double* __restrict__ part, long long rows, int n, DpfHeadW hw,
+                                                          double* __restrict__ stats, float* __restrict__ out) {
+  __shared__ double tot[kMinRow];
+  double loss = 0.0;
+  for (int k = 0; k < kDpfMaxHeads; ++k) {
+    double row[kMinRow];
+#pragma unroll
+    for (int q = 0; q < kMinRow; ++q) row[q] = 0.0;
+    if (k < n) {
+      dpf_fold_rows_d<kMinRow>(part + (size_t)k * (size_t)rows * kMinRow, rows, kMinRow, tot);
+#pragma unroll
+      for (int q = 0; q < kMinRow; ++q) row[q] = tot[q];
+      if (row[1] > 0.0) loss += (double)hw.w[k] * (row[0] / row[1]);
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int v = 0; v < kMaxViews; ++v) stats[kStatCount + kMaxViews * k + v] = row[2 + v], stats[kStatSum + kMaxViews * k + v] = v == 0 ? row[0] : 0.0;
+      stats[kStatViews + k] = row[1];
+    }
+  }
+  if (threadIdx.x == 0) out[0] = (float)loss;
+}
+
+// reduce 'mean': grid (ceil(W / 32), ceil(H / 8), B n S), 256 threads = 8 rows x 32 columns.  part: [n][S][B tiles][2]
+template <bool kVis>
+__device__ __forceinline__ void forward_tile(const MV& g, const Occ& oc, double* __restrict__ part, float* __restrict__ warped_out,
+                                             unsigned char* __restrict__ counted_out, float* __restrict__ xy_out,
+                                             unsigned char* __restrict__ visible_out) {
+  constexpr int LW = kTW + 2, LH = kTH + 2;
+  __shared__ float tI[LH * LW], tJ[LH * LW];
+  __shared__ unsigned char tw[LH * LW];
+  const int t = threadIdx.x;
+  const int sh = blockIdx.z / g.S, v = blockIdx.z - sh * g.S;
+  const int s = sh / g.n, h = sh - s * g.n;
+  const int B = gridDim.z / (g.n * g.S);
+  const size_t HW = (size_t)g.H * g.W;
+  const float* __restrict__ predh = g.pred + ((size_t)s * g.n + h) * HW;
+  const float b = g.target_type == 0 ? g.ab[2 * (size_t)s] : 0.f, a = g.target_type == 0 ? g.ab[2 * (size_t)s + 1] : 0.f;
+  const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+  const size_t obase = (((size_t)s * g.n + h) * g.S + v) * HW;
+  load_view_tile<kVis>(g, oc, s, h, v, predh, a, b, x0, y0, tI, tJ, tw, xy_out);
   __syncthreads();
   const int tx = t & (kTW - 1), ty = t / kTW;
   const int x = x0 + tx, y = y0 + ty;
@@ -271,22 +438,30 @@ __global__ __launch_bounds__(256) void mv_forward_kernel(MV g, double* __restric
     const int ly = ty + 1, lx = tx + 1;
     const bool counted = x >= 1 && x + 1 < g.W && y >= 1 && y + 1 < g.H && all_nine<LW>(tw, ly, lx);
     if (counted) {
-      Window w;
-      window_of<LW>(tI, tJ, ly, lx, w);
-      const float ds = fminf(fmaxf((1.f - w.ssim) / 2.f, 0.f), 1.f);
-      const float d = tJ[ly * LW + lx] - tI[ly * LW + lx];
-      acc[0] = (double)(g.wssim * ds + (1.f - g.wssim) * rho_of(g.rho, d));
+      acc[0] = (double)term_at(g, tI, tJ, ly, lx);
       acc[1] = 1.0;
     }
     if (warped_out) {
       const size_t o = obase + (size_t)y * g.W + x;
       warped_out[o] = tJ[ly * LW + lx];
       counted_out[o] = counted ? 1 : 0;
+      if (kVis) visible_out[o] = tw[ly * LW + lx];
     }
   }
   const size_t tiles = (size_t)gridDim.x * gridDim.y;
   const size_t row = (((size_t)h * g.S + v) * B + s) * tiles + (size_t)blockIdx.y * gridDim.x + blockIdx.x;
   dpf_block_reduce_d<2>(acc, part + row * 2);
+}
+
+__global__ __launch_bounds__(256) void mv_forward_kernel(MV g, double* __restrict__ part, float* __restrict__ warped_out,
+                                                         unsigned char* __restrict__ counted_out, float* __restrict__ xy_out) {
+  forward_tile<false>(g, Occ{}, part, warped_out, counted_out, xy_out, nullptr);
+}
+
+__global__ __launch_bounds__(256) void mv_forward_vis_kernel(MV g, Occ oc, double* __restrict__ part, float* __restrict__ warped_out,
+                                                             unsigned char* __restrict__ counted_out, float* __restrict__ xy_out,
+                                                             unsigned char* __restrict__ visible_out) {
+  forward_tile<true>(g, oc, part, warped_out, counted_out, xy_out, visible_out);
 }
 
 // one block: folds the rows (per head and view: B tiles) in a fixed order, writes the stats record and the loss
@@ -311,14 +486,18 @@ __global__ __launch_bounds__(256) void mv_fold_kernel(const double* __restrict__
   if (threadIdx.x == 0) out[0] = (float)loss;
 }
 
-// grid (ceil(W / 32), ceil(H / 8), B n): the view loop runs inside, so a pixel's gradient is one sum in one order
-__global__ __launch_bounds__(256) void mv_backward_kernel(MV g, DpfHeadW hw, const double* __restrict__ stats, const float* __restrict__ gout,
-                                                          float* __restrict__ dpred) {
+// grid (ceil(W / 32), ceil(H / 8), B n): the view loop runs inside, so a pixel's gradient is one sum in one order.  kVis: seen stands
+// for warpable (the z-buffer is the forward's).  kMin: the window at centre c owes its nine pixels in view sel[c] only, the robust term of
+// a pixel's own window is taken in its selected view only, and the share is w_h / count_h; stats is mv_fold_min_kernel's record
+template <bool kVis, bool kMin>
+__device__ __forceinline__ void backward_tile(const MV& g, const Occ& oc, const unsigned char* __restrict__ sel, const DpfHeadW& hw,
+                                              const double* __restrict__ stats, const float* __restrict__ gout, float* __restrict__ dpred) {
   constexpr int ZW = kTW + 4, ZH = kTH + 4;               // I, z, J, warpable: halo 2
   constexpr int CW = kTW + 2, CH = kTH + 2;               // windows: halo 1
   __shared__ float tI[ZH * ZW], tZ[ZH * ZW], tJ[ZH * ZW];
   __shared__ unsigned char tu[ZH * ZW], tw[ZH * ZW];      // usable (per pixel), warpable (per pixel and view)
   __shared__ float coef[5][CH * CW];
+  __shared__ unsigned char tsel[kMin ? CH * CW : 1];      // the selected view of the window centres
   const int t = threadIdx.x;
   const int s = blockIdx.z / g.n, h = blockIdx.z - s * g.n;
   const size_t HW = (size_t)g.H * g.W, sbase = (size_t)s * HW;
@@ -326,6 +505,14 @@ __global__ __launch_bounds__(256) void mv_backward_kernel(MV g, DpfHeadW hw, con
   const float* __restrict__ yr = g.ytgt + sbase;
   const float b = g.target_type == 0 ? g.ab[2 * (size_t)s] : 0.f, a = g.target_type == 0 ? g.ab[2 * (size_t)s + 1] : 0.f;
   const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+  if (kMin) {
+    const unsigned char* __restrict__ selh = sel + ((size_t)s * g.n + h) * HW;
+    for (int i = t; i < CH * CW; i += kBlock) {
+      const int wy = i / CW, wx = i - wy * CW;
+      const int py = y0 - 1 + wy, px = x0 - 1 + wx;
+      tsel[i] = py >= 0 && py < g.H && px >= 0 && px < g.W ? selh[(size_t)py * g.W + px] : 255;
+    }
+  }
   for (int i = t; i < ZH * ZW; i += kBlock) {
     const int ly = i / ZW, lx = i - ly * ZW;
     const int y = y0 - 2 + ly, x = x0 - 2 + lx;
@@ -354,7 +541,9 @@ __global__ __launch_bounds__(256) void mv_backward_kernel(MV g, DpfHeadW hw, con
       const int py = i / ZW, px = i - py * ZW;
       float J = 0.f, su, sv;
       bool ok = false;
-      if (tu[i]) ok = warp_at(g, r, ys, tZ[i], y0 - 2 + py, x0 - 2 + px, J, su, sv, nullptr);
+      float qz = 0.f;
+      if (tu[i]) ok = warp_at(g, r, ys, tZ[i], y0 - 2 + py, x0 - 2 + px, J, su, sv, nullptr, kVis ? &qz : nullptr);
+      if (kVis) ok = ok && visible_at(oc, oc.zbuf + (((size_t)s * g.n + h) * g.S + v) * ((size_t)oc.Hc * oc.Wc), qz, su, sv);
       tJ[i] = J, tw[i] = ok ? 1 : 0;
     }
     __syncthreads();
@@ -362,7 +551,7 @@ __global__ __launch_bounds__(256) void mv_backward_kernel(MV g, DpfHeadW hw, con
       const int wy = i / CW, wx = i - wy * CW;
       const int py = y0 - 1 + wy, px = x0 - 1 + wx;
       float c0 = 0.f, cI = 0.f, cJ = 0.f, mI = 0.f, mJ = 0.f;
-      if (px >= 1 && px + 1 < g.W && py >= 1 && py + 1 < g.H && all_nine<ZW>(tw, wy + 1, wx + 1)) {
+      if (px >= 1 && px + 1 < g.W && py >= 1 && py + 1 < g.H && (!kMin || tsel[i] == v) && all_nine<ZW>(tw, wy + 1, wx + 1)) {
         Window w;
         window_of<ZW>(tI, tJ, wy + 1, wx + 1, w);
         window_coef(w, g.wssim, c0, cI, cJ, mI, mJ);
@@ -380,11 +569,12 @@ __global__ __launch_bounds__(256) void mv_backward_kernel(MV g, DpfHeadW hw, con
           const int c = (cy + dy) * CW + cx + dx;
           sum = sum + ((coef[0][c] + coef[1][c] * (I - coef[3][c])) + coef[2][c] * (J - coef[4][c]));
         }
-      if (x >= 1 && x + 1 < g.W && y >= 1 && y + 1 < g.H && all_nine<ZW>(tw, ly, lx)) sum = sum + (1.f - g.wssim) * drho_of(g.rho, J - I);
+      if (x >= 1 && x + 1 < g.W && y >= 1 && y + 1 < g.H && (!kMin || tsel[cy * CW + cx] == v) && all_nine<ZW>(tw, ly, lx))
+        sum = sum + (1.f - g.wssim) * drho_of(g.rho, J - I);
       if (sum != 0.f) {
         float dJ = 0.f, Jagain, su, sv;
         warp_at(g, r, ys, tZ[ly * ZW + lx], y, x, Jagain, su, sv, &dJ);
-        const float wk = (float)((double)hw.w[h] / (views * cnt));
+        const float wk = (float)((double)hw.w[h] / (kMin ? views : views * cnt));
         total = total + (sum * dJ) * wk;
       }
     }
@@ -397,6 +587,18 @@ __global__ __launch_bounds__(256) void mv_backward_kernel(MV g, DpfHeadW hw, con
     out = (total * dz) * gout[0];
   }
   dpred[((size_t)s * g.n + h) * HW + (size_t)y * g.W + x] = out;
+}
+
+__global__ __launch_bounds__(256) void mv_backward_kernel(MV g, DpfHeadW hw, const double* __restrict__ stats, const float* __restrict__ gout,
+                                                          float* __restrict__ dpred) {
+  backward_tile<false, false>(g, Occ{}, nullptr, hw, stats, gout, dpred);
+}
+
+template <bool kVis, bool kMin>
+__global__ __launch_bounds__(256) void mv_backward_occ_kernel(MV g, Occ oc, const unsigned char* __restrict__ sel, DpfHeadW hw,
+                                                              const double* __restrict__ stats, const float* __restrict__ gout,
+                                                              float* __restrict__ dpred) {
+  backward_tile<kVis, kMin>(g, oc, sel, hw, stats, gout, dpred);
 }
 
 // the tile plan of the sibling (dpf_head_loss.h), refused as well where B n S does not fit on gridDim.z of the forward, the B + B S
@@ -434,6 +636,30 @@ int prepare(const float* pred, const float* tgt_rgb, const float* src_rgb, long 
   g.wssim = weight_ssim, g.min_depth = min_depth, g.rho = rho_params(alpha, scale);
   dpf_fill_head_weights(hw.w, weights, n);
   return DPF_OK;
+}
+
+bool cell_ok(int cell) { return cell == 1 || cell == 2 || cell == 4; }
+
+Occ occ_of(const unsigned* zbuf, int cell, float tol, int Hs, int Ws) {
+  Occ oc;
+  oc.zbuf = zbuf, oc.cell = cell, oc.Hc = dpf_div_up(Hs, cell), oc.Wc = dpf_div_up(Ws, cell), oc.tol = tol;
+  return oc;
+}
+
+// what the occlusion entry points add to prepare(): one of the two modes is on (the plain entry points serve the call with both off)
+bool occ_args_ok(int reduce, int visibility, int cell, float tolerance, const float* zbuffer, const unsigned char* selected) {
+  return reduce >= 0 && reduce <= 1 && visibility >= 0 && visibility <= 1 && (reduce || visibility) && cell_ok(cell) && tolerance >= 0.f &&
+         isfinite(tolerance) && (!visibility || zbuffer) && (!reduce || selected);
+}
+
+// fill, then splat: two launches ahead of the forward on its stream (a cell's minimum comes from pixels anywhere in the image)
+void launch_zbuffer(const MV& g, const Occ& oc, int B, hipStream_t st) {
+  const long long cells = (long long)B * g.n * g.S * oc.Hc * oc.Wc;
+  long long blocks = (cells + kBlock - 1) / kBlock;
+  if (blocks > 4096) blocks = 4096;
+  unsigned* zb = const_cast<unsigned*>(oc.zbuf);
+  hipLaunchKernelGGL(mv_zfill_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, zb, cells);
+  hipLaunchKernelGGL(mv_zsplat_kernel, dim3(dpf_div_up(g.W, kTW), dpf_div_up(g.H, kTH), B * g.n * g.S), dim3(kBlock), 0, st, g, oc, zb);
 }
 
 }  // namespace
@@ -493,6 +719,94 @@ int dpf_multiview_backward(const float* pred, const float* tgt_rgb, const float*
   if (rc != DPF_OK) return rc;
   if (!stats || !gout || !dpred) return DPF_ERR_INVALID_ARG;
   hipLaunchKernelGGL(mv_backward_kernel, dpf_tile_grid(B, n, H, W), dim3(kBlock), 0, (hipStream_t)stream, g, hw, stats, gout, dpred);
+  return dpf_check_launch();
+}
+
+long long dpf_multiview_occ_workspace_bytes(int B, int n, int S, int H, int W, int reduce) {
+  const long long rows = plan_rows(B, n, S, H, W);
+  if (rows < 0 || reduce < 0 || reduce > 1) return -1;
+  return (reduce == 1 ? rows / S * kMinRow : rows * 2) * (long long)sizeof(double);
+}
+
+int dpf_multiview_zbuffer(const float* pred, const float* rig, const float* ab, const float* mask, int B, int n, int S, int H, int W, int Hs,
+                          int Ws, int target_type, float min_depth, int cell, float* zbuffer, void* stream) {
+  dpf_clear_error();
+  if (!pred || !rig || !zbuffer || B <= 0 || n < 1 || n > kDpfMaxHeads || S < 1 || S > kMaxViews || H <= 0 || W <= 0 || Hs <= 0 || Ws <= 0 ||
+      target_type < 0 || target_type > 2 || (target_type == 0 && !ab) || !(min_depth > 0.f) || !isfinite(min_depth) || !cell_ok(cell))
+    return DPF_ERR_INVALID_ARG;
+  if (plan_rows(B, n, S, H, W) < 0 || (long long)Hs * Ws > 0x7fffffffLL) return DPF_ERR_UNSUPPORTED;
+  MV g = {};
+  g.pred = pred, g.rig = rig, g.ab = ab, g.mask = mask;
+  g.n = n, g.S = S, g.H = H, g.W = W, g.Hs = Hs, g.Ws = Ws, g.target_type = target_type, g.min_depth = min_depth;
+  launch_zbuffer(g, occ_of((unsigned*)zbuffer, cell, 0.f, Hs, Ws), B, (hipStream_t)stream);
+  return dpf_check_launch();
+}
+
+int dpf_multiview_occ_forward(const float* pred, const float* tgt_rgb, const float* src_rgb, long long src_stride, const float* rig,
+                              const float* ab, const float* mask, int B, int n, int S, int H, int W, int Hs, int Ws, int target_type,
+                              float weight_ssim, float alpha, float scale, float min_depth, const float* norm_host,
+                              const float* head_weights_host, int reduce, int visibility, int cell, float tolerance, void* ws,
+                              long long ws_bytes, float* luma, float* zbuffer, unsigned char* selected, double* stats, float* out,
+                              float* warped_out, unsigned char* counted_out, float* sample_xy_out, unsigned char* visible_out,
+                              void* stream) {
+  dpf_clear_error();
+  MV g;
+  DpfHeadW hw;
+  const int rc = prepare(pred, tgt_rgb, src_rgb, src_stride, rig, ab, mask, B, n, S, H, W, Hs, Ws, target_type, weight_ssim, alpha, scale,
+                         min_depth, norm_host, head_weights_host, luma, g, hw);
+  if (rc != DPF_OK) return rc;
+  if (!occ_args_ok(reduce, visibility, cell, tolerance, zbuffer, selected) || !stats || !out ||
+      (warped_out != nullptr) != (counted_out != nullptr) || (warped_out != nullptr) != (visible_out != nullptr) ||
+      (sample_xy_out && !warped_out) || !dpf_ws_ok(ws, ws_bytes, dpf_multiview_occ_workspace_bytes(B, n, S, H, W, reduce), 8))
+    return DPF_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const long long HW = (long long)H * W, HsWs = (long long)Hs * Ws;
+  long long blocks = ((HW > HsWs ? HW : HsWs) + kBlock - 1) / kBlock;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(mv_luma_kernel, dim3((unsigned)blocks, B * (S + 1)), dim3(kBlock), 0, st, tgt_rgb, src_rgb, src_stride, B, S, HW, HsWs,
+                     dpf_norm_of(norm_host), luma);
+  const Occ oc = occ_of(visibility ? (unsigned*)zbuffer : nullptr, cell, tolerance, Hs, Ws);
+  if (visibility) launch_zbuffer(g, oc, B, st);
+  double* part = (double*)ws;
+  const long long rows = dpf_tile_rows(B, n, H, W) / n;
+  if (reduce == 1) {
+    if (visibility)
+      hipLaunchKernelGGL(mv_forward_min_kernel<true>, dpf_tile_grid(B, n, H, W), dim3(kBlock), 0, st, g, oc, part, selected, warped_out,
+                         counted_out, sample_xy_out, visible_out);
+    else
+      hipLaunchKernelGGL(mv_forward_min_kernel<false>, dpf_tile_grid(B, n, H, W), dim3(kBlock), 0, st, g, oc, part, selected, warped_out,
+                         counted_out, sample_xy_out, visible_out);
+    hipLaunchKernelGGL(mv_fold_min_kernel, dim3(1), dim3(256), 0, st, part, rows, n, hw, stats, out);
+  } else {
+    hipLaunchKernelGGL(mv_forward_vis_kernel, dim3(dpf_div_up(W, kTW), dpf_div_up(H, kTH), B * n * S), dim3(kBlock), 0, st, g, oc, part,
+                       warped_out, counted_out, sample_xy_out, visible_out);
+    hipLaunchKernelGGL(mv_fold_kernel, dim3(1), dim3(256), 0, st, part, rows, n, S, hw, stats, out);
+  }
+  return dpf_check_launch();
+}
+
+int dpf_multiview_occ_backward(const float* pred, const float* tgt_rgb, const float* src_rgb, long long src_stride, const float* rig,
+                               const float* ab, const float* mask, int B, int n, int S, int H, int W, int Hs, int Ws, int target_type,
+                               float weight_ssim, float alpha, float scale, float min_depth, const float* norm_host,
+                               const float* head_weights_host, int reduce, int visibility, int cell, float tolerance, const float* luma,
+                               const float* zbuffer, const unsigned char* selected, const double* stats, const float* gout, float* dpred,
+                               void* stream) {
+  dpf_clear_error();
+  MV g;
+  DpfHeadW hw;
+  const int rc = prepare(pred, tgt_rgb, src_rgb, src_stride, rig, ab, mask, B, n, S, H, W, Hs, Ws, target_type, weight_ssim, alpha, scale,
+                         min_depth, norm_host, head_weights_host, luma, g, hw);
+  if (rc != DPF_OK) return rc;
+  if (!occ_args_ok(reduce, visibility, cell, tolerance, zbuffer, selected) || !stats || !gout || !dpred) return DPF_ERR_INVALID_ARG;
+  const Occ oc = occ_of(visibility ? (const unsigned*)zbuffer : nullptr, cell, tolerance, Hs, Ws);
+  const dim3 grid = dpf_tile_grid(B, n, H, W);
+  hipStream_t st = (hipStream_t)stream;
+  if (reduce == 1 && visibility)
+    hipLaunchKernelGGL((mv_backward_occ_kernel<true, true>), grid, dim3(kBlock), 0, st, g, oc, selected, hw, stats, gout, dpred);
+  else if (reduce == 1)
+    hipLaunchKernelGGL((mv_backward_occ_kernel<false, true>), grid, dim3(kBlock), 0, st, g, oc, selected, hw, stats, gout, dpred);
+  else
+    hipLaunchKernelGGL((mv_backward_occ_kernel<true, false>), grid, dim3(kBlock), 0, st, g, oc, selected, hw, stats, gout, dpred);
   return dpf_check_launch();
 }
 

@@ -5,7 +5,7 @@ Class names follow the reference's lookup rule ``<NAME.upper()>Loss`` (loss_sele
 """
 import torch
 
-from . import multiview, normal_geo, ops, photometric, unimodal
+from . import multiview, multiview_occlusion, normal_geo, ops, photometric, unimodal
 from .core import reference_key
 
 
@@ -244,13 +244,15 @@ class MULTIVIEWLoss(_HeadWeights):
     view through the depth every head of pred_depth predicts, batch['K'] / batch['P'] and batch['Ks'] / batch['Ps'], against
     batch['center'].  Settings: the model config block multiview (multiview.settings); the first select_view views are used.  It reads
     calibration but no label map, so it refuses no dp_conversion.  (a, b) is needed for target_type 'disp' only: batch['abvalue'], else
-    the fit, as in PHOTOMETRICLoss.  batch['conf'] is not read."""
+    the fit, as in PHOTOMETRICLoss.  batch['conf'] is not read.  Occlusion handling (per-pixel minimum over the views, visibility from a
+    z-buffer of the prediction) is the block multiview_occlusion (multiview_occlusion.settings), off by default: .occlusion."""
     name = 'multiview'
     KEYS = ('center', 'centers', 'K', 'P', 'Ks', 'Ps')
 
     def __init__(self, option):
         super(MULTIVIEWLoss, self).__init__(option)
         self.settings = multiview.settings(option)
+        self.occlusion = multiview_occlusion.settings(option)
 
     def forward(self, preds, batch, target_type='disp', ab_of=None):
         assert target_type in TARGET_TYPES
@@ -276,7 +278,7 @@ class MULTIVIEWLoss(_HeadWeights):
         out['loss'] = ops.multiview_loss(pd, f32(batch['center']), f32(src), f32(batch['K']), f32(batch['P']), f32(Ks[:, :S]), f32(Ps[:, :S]),
                                          ab=None if ab is None else f32(ab), mask=batch.get('mask'),
                                          head_weights=self.head_weights(pd.shape[1]), target_type=target_type, weight_ssim=s.weight_ssim,
-                                         alpha=s.alpha, scale=s.scale, min_depth=s.min_depth)
+                                         alpha=s.alpha, scale=s.scale, min_depth=s.min_depth, **self.occlusion._asdict())
         return out
 
 

@@ -14,6 +14,9 @@ Keys, all optional:
     image compared; "left" and "right" are refused by name: the loader produces no 'lefts' / 'rights' pairing that was checked),
     min_depth 1e-3 (> 0: a predicted depth below it is not usable)
 
+Occlusion handling (per-pixel minimum over the views, visibility from a z-buffer of the prediction) has a block of its own,
+``multiview_occlusion`` (dualpixelface_amd/multiview_occlusion.py), off by default.
+
 A key missing from the block falls back to the top-level key of the same name in the model configuration (select_view, weight_ssim,
 alpha, scale), so src/model/dpnet/config_multi.json's own keys mean what they say, and then to the default.
 

@@ -2127,6 +2127,58 @@ class MultiviewFn(torch.autograd.Function):
         return dpred, None, None, None, None, None
 
 
+MULTIVIEW_REDUCE = {'mean': 0, 'min': 1}
+MULTIVIEW_VISIBILITY = {'none': 0, 'zbuffer': 1}
+MULTIVIEW_CELLS = (1, 2, 4)
+
+
+class MultiviewOccFn(torch.autograd.Function):
+    """MultiviewFn with occlusion handling on (reduce 'min' and / or visibility 'zbuffer'; csrc/multiview.hip): the same argument orders
+    with `mode` = (reduce, visibility, cell, tolerance) after the lead, the z-buffer and the selection plane after luma.  Both are fresh
+    tensors saved for the backward beside the planes (None where their mode is off); the workspace may be overwritten between the passes.
+    With want_extras the plain extras, then visible, selected (reduce 'min') and zbuffer (visibility 'zbuffer')."""
+
+    @staticmethod
+    def forward(ctx, pred, held, rig, lead, dims, mode, want_extras):
+        B, n, S, H, W, Hs, Ws = dims
+        reduce, visibility, cell, tolerance = mode
+        dev = pred.device
+        ws, nbytes = _workspace('dpf_multiview_occ_workspace_bytes', 'multiview_loss: shape B=%d n=%d S=%d H=%d W=%d (reduce %d) is not supported',
+                                B, n, S, H, W, reduce, device=dev)
+        stats = torch.empty(MULTIVIEW_STATS, dtype=torch.float64, device=dev)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        luma = torch.empty(B * H * W + B * S * Hs * Ws, dtype=torch.float32, device=dev)
+        zbuf = torch.empty((B, n, S, -(-Hs // cell), -(-Ws // cell)), dtype=torch.float32, device=dev) if visibility else None
+        sel = torch.empty((B, n, H, W), dtype=torch.uint8, device=dev) if reduce else None
+        extras = [None, None, None, None]
+        if want_extras:
+            extras = [torch.empty((B, n, S, H, W), dtype=torch.float32, device=dev), torch.empty((B, n, S, H, W), dtype=torch.uint8, device=dev),
+                      torch.empty((B, n, S, 2, H, W), dtype=torch.float32, device=dev), torch.empty((B, n, S, H, W), dtype=torch.uint8, device=dev)]
+        lib().call('dpf_multiview_occ_forward', *lead, *mode, _ptr(ws), nbytes, _ptr(luma), _ptr(zbuf), _ptr(sel), _ptr(stats), _ptr(out),
+                   *[_ptr(t) for t in extras], _stream())
+        ctx.save_for_backward(pred, stats, luma, rig, *[t for t in (zbuf, sel) + tuple(held) if t is not None])
+        ctx.lead, ctx.mode = lead, mode
+        if want_extras:
+            planes = (luma[:B * H * W].view(B, H, W), luma[B * H * W:].view(B, S, Hs, Ws))
+            more = tuple(t for t in (sel, zbuf) if t is not None)
+            ctx.mark_non_differentiable(*extras, *planes, *more)
+            return (out,) + tuple(extras[:3]) + planes + (extras[3],) + more
+        return out
+
+    @staticmethod
+    def backward(ctx, gout, *unused):
+        pred, stats, luma = ctx.saved_tensors[:3]
+        rest = list(ctx.saved_tensors[4:])
+        zbuf = rest.pop(0) if ctx.mode[1] else None
+        sel = rest.pop(0) if ctx.mode[0] else None
+        gout = _c(gout)
+        _need(gout)
+        dpred = torch.empty_like(pred)
+        lib().call('dpf_multiview_occ_backward', *ctx.lead, *ctx.mode, _ptr(luma), _ptr(zbuf), _ptr(sel), _ptr(stats), _ptr(gout), _ptr(dpred),
+                   _stream())
+        return dpred, None, None, None, None, None, None
+
+
 def multiview_rig(Kmat, Pmat, Ks, Ps):
     """csrc/multiview.hip: the twelve fp32 numbers per (sample, view) that carry a pixel of the target view and its depth into a
     neighbouring view, from K [B, 3, 3], P [B, 4, 4], Ks [B, S, 3, 3], Ps [B, S, 4, 4] (device float32) -> rig [B, S, 12] = (M row-major,
@@ -2147,7 +2199,7 @@ def multiview_rig(Kmat, Pmat, Ks, Ps):
 
 
 def multiview_loss(pred, tgt_rgb, src_rgb, Kmat, Pmat, Ks, Ps, ab=None, mask=None, head_weights=(1.0,), target_type='disp', weight_ssim=0.8,
-                   alpha=1.0, scale=0.1, min_depth=1e-3, return_warped=False):
+                   alpha=1.0, scale=0.1, min_depth=1e-3, return_warped=False, reduce='mean', visibility='none', cell=2, tolerance=0.01):
     """csrc/multiview.hip: the luminance of the source images src_rgb [B, S <= 8, 3, Hs, Ws] (a slice along dim 1 of a wider tensor is
     taken as it is) sampled bilinearly where the depth every head of pred [B, n <= 8, H, W] predicts sends the pixels of the target
     view, against the luminance of tgt_rgb [B, 3, H, W] -> the 0-dim loss sum_h w_h mean over the views that count a pixel of (mean over
@@ -2155,8 +2207,24 @@ def multiview_loss(pred, tgt_rgb, src_rgb, Kmat, Pmat, Ks, Ps, ab=None, mask=Non
     robust loss.  The depth is a / (pred - b) for 'disp' (ab [B, 2] = [b, a], needed then only), 1 / pred for
     'idepth', pred for 'depth'; a pixel is usable where pred and the depth are finite, the depth >= min_depth and mask (None: everywhere)
     > 0; the geometry is multiview_rig's.  The gradient reaches pred only.  With return_warped also warped [B, n, S, H, W] fp32 (0 where
-    not warpable), counted [B, n, S, H, W] uint8, sample_xy [B, n, S, 2, H, W] fp32 and the luminance planes [B, H, W], [B, S, Hs, Ws]."""
+    not warpable), counted [B, n, S, H, W] uint8, sample_xy [B, n, S, 2, H, W] fp32 and the luminance planes [B, H, W], [B, S, Hs, Ws].
+
+    Occlusion handling, off by default (then the call is MultiviewFn's, as it was).  visibility 'zbuffer': a warpable pixel is seen by a
+    view where its depth in that view is at most (1 + tolerance) x the smallest depth any usable pixel of the head splats into its cell
+    of cell x cell source pixels (cell 1, 2 or 4), and 'seen' stands for 'warpable' in the rule above; only usable pixels splat, so a
+    masked-out occluder hides nothing.  reduce 'min': per head and pixel the smallest term over the views that count it (the lowest view
+    wins a tie), averaged over the pixels some view counts.  cell 2 and tolerance 0.01 are conventional starting values, not tuned on
+    face data.  With return_warped and one of them on the tuple goes on with visible [B, n, S, H, W] uint8 (seen), selected [B, n, H, W]
+    uint8 (reduce 'min': the winning view, 255 none) and zbuffer [B, n, S, ceil(Hs / cell), ceil(Ws / cell)] fp32 (visibility
+    'zbuffer'; +inf where nothing landed)."""
     code = _target_code('multiview_loss', target_type, ())
+    if reduce not in MULTIVIEW_REDUCE:
+        raise DpfError("multiview_loss: reduce must be 'mean' or 'min', got %r" % (reduce,))
+    if visibility not in MULTIVIEW_VISIBILITY:
+        raise DpfError("multiview_loss: visibility must be 'none' or 'zbuffer', got %r" % (visibility,))
+    cell = _int_arg('multiview_loss', 'cell', cell, MULTIVIEW_CELLS)
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float)) or not 0.0 <= float(tolerance) < float('inf'):
+        raise DpfError('multiview_loss: tolerance must be a finite number >= 0, got %r' % (tolerance,))
     if target_type == 'disp' and ab is None:
         raise DpfError("multiview_loss: target_type 'disp' needs ab [B, 2] = [b, a]")
     ab = ab if target_type == 'disp' else None
@@ -2186,6 +2254,9 @@ def multiview_loss(pred, tgt_rgb, src_rgb, Kmat, Pmat, Ks, Ps, ab=None, mask=Non
     held = (_c(tgt_rgb.detach()), src, None if ab is None else _c(ab.detach()), None if mask is None else _c(mask.detach()))
     lead = (_ptr(pred), _ptr(held[0]), _ptr(src), stride, _ptr(rig), _ptr(held[2]), _ptr(held[3]), B, n, S, H, W, Hs, Ws, code,
             float(weight_ssim), float(alpha), float(scale), float(min_depth), _normalizer_floats(), _host_floats(head_weights))
+    mode = (MULTIVIEW_REDUCE[reduce], MULTIVIEW_VISIBILITY[visibility], cell, float(tolerance))
+    if mode[0] or mode[1]:
+        return MultiviewOccFn.apply(pred, held, rig, lead, (B, n, S, H, W, Hs, Ws), mode, bool(return_warped))
     return MultiviewFn.apply(pred, held, rig, lead, (B, n, S, H, W, Hs, Ws), bool(return_warped))
 
 

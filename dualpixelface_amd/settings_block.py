@@ -1,4 +1,4 @@
-"""What the settings modules share (normal_geo, photometric, multiview, postprocess, reconstruct): the lookup of a configuration block and the
+"""What the settings modules share (normal_geo, photometric, multiview, multiview_occlusion, postprocess, reconstruct): the lookup of a configuration block and the
 validators of its values.  Each module keeps its Settings, its DEFAULTS and the rules only it has; every refusal is a ValueError
 '<block>.<key> must be <what>, got <value>'."""
 INF = float('inf')

@@ -691,6 +691,41 @@ int dpf_multiview_backward(const float* pred, const float* tgt_rgb, const float*
                            const float* head_weights_host, const float* luma, const double* stats, const float* gout, float* dpred,
                            void* stream);
 
+/* ---- occlusion handling for the multi-view loss (csrc/multiview.hip): two mechanisms that compose, each off in
+ * the entry points above, which stay as they are.  The leading 21 arguments are dpf_multiview_forward's.
+ *   visibility 1  one z-buffer per (sample, head, view) of Hc x Wc cells, Hc = ceil(Hs / cell), Wc = ceil(Ws / cell), cell in {1, 2, 4}:
+ *                 every warpable pixel splats q_z into the cell (floor(v + 0.5) / cell, floor(u + 0.5) / cell) by an integer atomic
+ *                 minimum on the bits of the positive float (order-independent); a warpable pixel is visible where
+ *                 q_z <= zmin + tolerance * zmin of its own cell, and "seen" = warpable and visible stands wherever the loss says
+ *                 warpable.  Only usable pixels splat: a masked-out occluder hides nothing.  Constant in the backward.
+ *   reduce 1      per head and pixel the smallest term over the views that count the pixel (the lowest view wins a tie);
+ *                 loss = sum_h w_h (sum of those terms / count_h), count_h the pixels counted in some view; 0 for count_h = 0
+ * zbuffer [B, n, S, Hc, Wc] floats (needed with visibility 1) and selected [B, n, H, W] uint8 (needed with reduce 1: the winning view,
+ * 255 = none) are the CALLER's, as rig and luma are: the forward fills them and the backward reads them.  dpf_multiview_zbuffer is the
+ * pre-pass alone (two launches: fill, splat); dpf_multiview_occ_forward runs it ahead of its tile kernel on the same stream.  stats (136
+ * doubles) is the plain record with reduce 0; with reduce 1: the pixels view v won at [8 h + v], the term sum at [64 + 8 h], count_h at
+ * [128 + h].  ws: dpf_multiview_occ_workspace_bytes() bytes, 8-byte aligned.  warped_out, counted_out and visible_out [B, n, S, H, W]
+ * (uint8: seen; warpable with visibility 0): all NULL or all given; sample_xy_out only with them.  No floating-point atomics: the bits
+ * repeat.  Refusals launch nothing: DPF_ERR_INVALID_ARG for what the plain entry points refuse, reduce or visibility outside {0, 1} or
+ * both 0, a cell outside {1, 2, 4}, a tolerance that is negative or not finite, a missing zbuffer / selected, a bad workspace;
+ * DPF_ERR_UNSUPPORTED for the plain entry points' limits. */
+long long dpf_multiview_occ_workspace_bytes(int B, int n, int S, int H, int W, int reduce);
+int dpf_multiview_zbuffer(const float* pred, const float* rig, const float* ab, const float* mask, int B, int n, int S, int H, int W, int Hs,
+                          int Ws, int target_type, float min_depth, int cell, float* zbuffer, void* stream);
+int dpf_multiview_occ_forward(const float* pred, const float* tgt_rgb, const float* src_rgb, long long src_stride, const float* rig,
+                              const float* ab, const float* mask, int B, int n, int S, int H, int W, int Hs, int Ws, int target_type,
+                              float weight_ssim, float alpha, float scale, float min_depth, const float* norm_host,
+                              const float* head_weights_host, int reduce, int visibility, int cell, float tolerance, void* ws,
+                              long long ws_bytes, float* luma, float* zbuffer, unsigned char* selected, double* stats, float* out,
+                              float* warped_out, unsigned char* counted_out, float* sample_xy_out, unsigned char* visible_out,
+                              void* stream);
+int dpf_multiview_occ_backward(const float* pred, const float* tgt_rgb, const float* src_rgb, long long src_stride, const float* rig,
+                               const float* ab, const float* mask, int B, int n, int S, int H, int W, int Hs, int Ws, int target_type,
+                               float weight_ssim, float alpha, float scale, float min_depth, const float* norm_host,
+                               const float* head_weights_host, int reduce, int visibility, int cell, float tolerance, const float* luma,
+                               const float* zbuffer, const unsigned char* selected, const double* stats, const float* gout, float* dpred,
+                               void* stream);
+
 /* ---- unimodal loss (csrc/unimodal.hip; loss_type 'unimodal', dualpixelface_amd/losses.py; not in the reference):
  * the cross-entropy between the hypothesis distribution of every disparity head and a Laplace distribution over the hypotheses centred
  * on the label.  Neither pass reads or writes a [B, n, L, H, W] volume: both recompute the distribution of a pixel from the

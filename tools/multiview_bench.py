@@ -4,6 +4,7 @@
     python tools/multiview_bench.py --agreement [--config train_faceDP_dpnet_multiview] [--loader]
     python tools/multiview_bench.py [--reps 100] [--rounds 3] [--out profiles/multiview_timings.txt]
     python tools/multiview_bench.py --step [--config train_faceDP_dpnet_multiview] [--root DIR]
+    python tools/multiview_bench.py --occlusion [--reps 100] [--rounds 3] [--out profiles/multiview_occlusion_timings.txt]
 
 --agreement  prints the mean term under the depth the batch brings (pred = batch['depth'], target type 'depth') for the pose matrices as
              stored and inverted (P and Ps both), and for the depth in its units, x1e-3 and x1e3: the combination whose term is the
@@ -18,6 +19,11 @@
              is an upper bound of the device time.
 --step       one line: the median time of the captured DPNet train step at 2x256x384 under --config, package imported from --root (so
              the same script times another checkout of the project; a config without use_multi steps on the plain synthetic batch).
+--occlusion  the occlusion modes (reduce 'min', visibility 'zbuffer', both) against the plain call at the two shapes above in one process,
+             the sides alternating; the z-buffer pre-pass (dpf_multiview_zbuffer: fill + splat) on its own; the captured DPNet step under
+             train_faceDP_dpnet_multiview_occlusion against train_faceDP_dpnet_multiview, alternating; and on the occluder scene
+             (synthetic_multiview.occluder_sample) at the true depth the loss of every mode with the share of pixels each view sees and
+             wins.
 Needs a GPU; there is no CPU fallback.
 """
 import argparse
@@ -32,6 +38,7 @@ import bench_support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WEIGHTS = [1.0, 0.75294, 0.18824, 0.047059, 0.011765]
+DEFAULT_OUT = os.path.join(ROOT, 'profiles', 'multiview_timings.txt')
 
 
 def captured_step(config, H, W):
@@ -102,6 +109,78 @@ def agreement(args):
         print('  %-28s mean term %.6f over %d of %d pixels%s' % (name, loss, cnt, total, '   <- smallest' if name == best[0] else ''))
 
 
+OCC_MODES = (('min', dict(reduce='min')), ('zbuffer', dict(visibility='zbuffer')), ('min + zbuffer', dict(reduce='min', visibility='zbuffer')))
+
+
+def occlusion(args):
+    from dualpixelface_amd import ops
+    from dualpixelface_amd._lib import lib
+    from dualpixelface_amd.synthetic_multiview import occluder_sample
+    lines = ['Multi-view loss, occlusion handling: python tools/multiview_bench.py --occlusion --reps %d --rounds %d' % (args.reps, args.rounds),
+             'One MI355X (gfx950), one process.  ops.multiview_loss on the synthetic plane scene with S = 3 neighbours whose images are 1.25 x',
+             'the target\'s, target type depth, cell 2, tolerance 0.01: the plain call (mean / none) and the three occlusion modes, %d calls' % args.reps,
+             'between two events on one stream, the sides alternating, median of %d rounds (min, max); enqueued from Python launch by' % args.rounds,
+             'launch, so an upper bound of the device time.  zbuffer pre-pass: dpf_multiview_zbuffer alone (fill + splat, two launches).', '']
+    for B, n, H, W in ((4, 1, 1024, 1536), (2, 5, 256, 384)):
+        sc = scene(B, n, H, W, 3)
+        pred = sc['pred'].requires_grad_()
+        weights = WEIGHTS[:n] if n > 1 else [1.0]
+        call = lambda kw: ops.multiview_loss(pred, sc['center'], sc['src'], sc['K'], sc['P'], sc['Ks'], sc['Ps'], mask=sc['mask'],   # noqa: E731
+                                             head_weights=weights, target_type='depth', **kw)
+        names, sides, notes = [], [], []
+        for name, kw in (('mean / none', {}),) + OCC_MODES:
+            fwd = lambda kw=kw: call(kw)                                                            # noqa: E731
+            loss = fwd()
+            bwd = lambda loss=loss: torch.autograd.grad(loss, pred, retain_graph=True)[0]           # noqa: E731
+            grad = bwd()
+            assert math.isfinite(float(loss)) and bool(torch.isfinite(grad).all())
+            names += [name + ' forward', name + ' backward']
+            sides += [fwd, bwd]
+            notes += [' | loss %.6f' % float(loss), ' | max |d pred| %.3e' % float(grad.abs().max())]
+        S, Hs, Ws = sc['src'].shape[1], sc['src'].shape[3], sc['src'].shape[4]
+        rig = ops.multiview_rig(sc['K'], sc['P'], sc['Ks'], sc['Ps'])
+        zbuf = torch.empty((B, n, S, -(-Hs // 2), -(-Ws // 2)), dtype=torch.float32, device='cuda')
+        held = (pred.detach().contiguous(), sc['mask'].contiguous())
+        names.append('zbuffer pre-pass')
+        sides.append(lambda: lib().call('dpf_multiview_zbuffer', ops._ptr(held[0]), ops._ptr(rig), None, ops._ptr(held[1]), B, n, S, H, W, Hs, Ws,
+                                        ops.TARGET_TYPES['depth'], 1e-3, 2, ops._ptr(zbuf), ops._stream()))
+        sides[-1]()
+        notes.append(' | %d of %d cells hit' % (int(torch.isfinite(zbuf).sum()), zbuf.numel()))
+        for name, t, note in zip(names, bench_support.rounds_of(sides, args.reps, args.rounds, warm=5), notes):
+            lines.append(_row(name, (B, n, H, W), t, note))
+        lines.append('')
+    lines += ['Captured DPNet train step at 2x256x384 (fp32) on the synthetic multi-view batch without its label maps:',
+              'train_faceDP_dpnet_multiview (mean / none) against train_faceDP_dpnet_multiview_occlusion (min + zbuffer), %d replays between' % args.reps,
+              'two events, alternating, %d rounds:' % args.rounds]
+    tp, to = bench_support.rounds_of((captured_step('train_faceDP_dpnet_multiview', 256, 384),
+                                      captured_step('train_faceDP_dpnet_multiview_occlusion', 256, 384)), args.reps, args.rounds)
+    mp, mo = statistics.median(tp), statistics.median(to)
+    lines.append('mean / none %s | min + zbuffer %s | %+.4f ms = %+.2f %% of the step'
+                 % (bench_support.fmt(tp, 4), bench_support.fmt(to, 4), mo - mp, 100.0 * (mo - mp) / mp))
+    s = occluder_sample(48, 64, 2)
+    dev = lambda k: s[k][None].cuda()                                                              # noqa: E731
+    Hs, Ws = s['centers'].shape[1:]
+    src = dev('centers').view(1, 2, 3, Hs, Ws)
+    pred = dev('depth')[:, None].contiguous()
+    lines += ['', 'The occluder scene (48x64, two opposed views) at the true depth, cell 2, tolerance 0.01; closed form: view 0 sees %.1f %% of the'
+              % (100.0 * s['visible'][0].mean()), 'target\'s pixels, view 1 %.1f %%:' % (100.0 * s['visible'][1].mean())]
+    for name, kw in (('mean / none', {}),) + OCC_MODES:
+        out = ops.multiview_loss(pred, dev('center'), src, dev('K'), dev('P'), dev('Ks'), dev('Ps'), target_type='depth', return_warped=True, **kw)
+        row = '%-14s loss %.6e | counted per view %s' % (name, float(out[0]), out[2].sum(dim=(0, 1, 3, 4)).tolist())
+        if kw:
+            row += ' | seen per view %s %%' % ['%.1f' % v for v in (100.0 * out[6].float().mean(dim=(0, 1, 3, 4))).tolist()]
+        if 'reduce' in kw:
+            row += ' | selected per view %s %%, none %.1f %%' % (['%.1f' % (100.0 * float((out[7] == v).float().mean())) for v in range(2)],
+                                                               100.0 * float((out[7] == 255).float().mean()))
+        lines.append(row)
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, 'profiles', 'multiview_occlusion_timings.txt')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+        f.write(text)
+
+
 def _row(tag, shape, times, extra=''):
     return '%-16s %-22s %s%s' % ('x'.join(str(v) for v in shape), tag, bench_support.fmt(times, 4), extra)
 
@@ -115,7 +194,8 @@ def main():
     ap.add_argument('--root', default=ROOT)
     ap.add_argument('--reps', type=int, default=100)
     ap.add_argument('--rounds', type=int, default=3)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'multiview_timings.txt'))
+    ap.add_argument('--occlusion', action='store_true')
+    ap.add_argument('--out', default=DEFAULT_OUT)
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'multiview_bench needs an MI355X'
     if args.step:
@@ -124,6 +204,8 @@ def main():
     sys.path.insert(0, ROOT)
     if args.agreement:
         return agreement(args)
+    if args.occlusion:
+        return occlusion(args)
     from dualpixelface_amd import ops
     lines = ['Multi-view photometric loss: python tools/multiview_bench.py --reps %d --rounds %d' % (args.reps, args.rounds),
              'One MI355X (gfx950), one process.  ops.multiview_loss (csrc/multiview.hip: rig + 3 launches forward, 1 backward) on the synthetic',
