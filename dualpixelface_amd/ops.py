@@ -1979,8 +1979,117 @@ def normal_refine(pred, Kmat, normal, ab=None, mask=None, target_type='disp', ne
     return (out, record) if stats else out
 
 
+SHADING_STATS = 16          # doubles per sample: counted, valid, passes, sum w, RMS pass 0 [4, 7), RMS last [7, 10), albedo error [10, 13), compared
+SHADING_MAX_ITERATIONS = 8
+SHADING_ORDERS = (1, 2)
+SHADING_SIGN_PARITY = (1, -1, 1, 1, -1, -1, 1, 1, 1)      # what normal_signs [1, -1, 1] does to the nine coefficients: the basis odd in y
+SHADING_CHUNK, SHADING_MAX_ROWS, SHADING_FOLD = 1024, 512, 256      # kChunk, kMaxRows of csrc/shading.hip and the fold's threads (dpf_reduce.h)
+
+
+def shading_rows(H, W):
+    """(partial rows per sample, pixels per workgroup) of csrc/shading.hip's passes over an H x W plane: a workgroup walks at least
+    SHADING_CHUNK pixels, more (a multiple of 256) once a sample would need more than SHADING_MAX_ROWS rows."""
+    n = H * W
+    rows = min(max(-(-n // SHADING_CHUNK), 1), SHADING_MAX_ROWS)
+    per_block = -(-(-(-n // rows)) // 256) * 256
+    return -(-n // per_block), per_block
+
+
+def _shading_operands(name, view, normal, mask, normal_signs, order, gamma, min_value, max_value):
+    """The operands both shading calls share -> (the leading arguments of the C call, the tensors behind its pointers, (B, H, W)):
+    the normalised view and the normal map, both [B, 3, H, W], mask [B, H, W] or None, the Normalizer's six host floats and the signs."""
+    order = _int_arg(name, 'order', order, SHADING_ORDERS)
+    signs = tuple(float(v) for v in normal_signs)
+    if len(signs) != 3 or any(v not in (1.0, -1.0) for v in signs):
+        raise DpfError('%s: normal_signs must be three values of +1 or -1, got %r' % (name, normal_signs))
+    _need(view, normal, mask, dtypes=_F32, contiguous=False)
+    if view is None or normal is None or view.dim() != 4 or view.shape[1] != 3:
+        raise DpfError('%s: view [B, 3, H, W] and normal [B, 3, H, W] are needed' % name)
+    B, _, H, W = view.shape
+    _match_pred(name, view, ('normal', normal, (B, 3, H, W)), ('mask', mask, (B, H, W)))
+    held = (_c(view.detach()), _c(normal.detach()), None if mask is None else _c(mask.detach()))
+    head = (_ptr(held[0]), _ptr(held[1]), _ptr(held[2]), _normalizer_floats(), _host_floats(signs))
+    return head, held, (B, H, W), (order, float(gamma), float(min_value), float(max_value))
+
+
+def shading_fit(view, normal, mask=None, order=2, gamma=2.2, min_value=0.02, max_value=0.98, iterations=3, f_scale=0.05, ridge=1e-6,
+                min_pixels=72, normal_signs=(1, 1, 1), gram=False):
+    """csrc/shading.hip: per sample the spherical-harmonics lighting (order 1: 4 coefficients, order 2: 9) that explains the linear
+    intensity of the normalised view [B, 3, H, W] under normal [B, 3, H, W] (normal_signs * normal, normalised) -> (light [B, 3, 9] fp32,
+    stats [B, 16] fp64), and with `gram` also the [B, 16, 16] fp64 Gram matrix of the last pass.  Iteratively reweighted least squares
+    with `iterations` (0 .. 8) reweighted passes over the pixels with mask > 0 (None: all), a usable normal and every channel within
+    [min_value, max_value]; the definitions are in include/dpf_hip.h.  A sample with fewer than min_pixels such pixels, or a singular
+    system, gets light 0 and stats[:, 1] = 0.  An inference-time operator: detached, nothing read on the host."""
+    iterations, min_pixels = _int_arg('shading_fit', 'iterations', iterations), _int_arg('shading_fit', 'min_pixels', min_pixels)
+    with torch.no_grad():
+        head, held, (B, H, W), pix = _shading_operands('shading_fit', view, normal, mask, normal_signs, order, gamma, min_value, max_value)
+        dev = held[0].device
+        ws, nbytes = _workspace('dpf_shading_workspace_bytes', 'shading_fit: B=%d H=%d W=%d is not supported', B, H, W, device=dev, tag='shading')
+        light = torch.empty((B, 3, 9), dtype=torch.float32, device=dev)
+        stats = torch.empty((B, SHADING_STATS), dtype=torch.float64, device=dev)
+        G = torch.empty((B, 16, 16), dtype=torch.float64, device=dev) if gram else None
+        lib().call('dpf_shading_fit', *head, B, H, W, *pix, iterations, float(f_scale), float(ridge), min_pixels, _ptr(ws), nbytes,
+                   _ptr(light), _ptr(stats), _ptr(G), _stream())
+    return (light, stats, G) if gram else (light, stats)
+
+
+def shading_rotation(rotate_deg):
+    """R = Rz Ry Rx of the three angles in degrees, formed in fp64 -> nine row-major numbers."""
+    import math
+    ax, ay, az = (math.radians(float(v)) for v in rotate_deg)
+    cx, sx, cy, sy, cz, sz = math.cos(ax), math.sin(ax), math.cos(ay), math.sin(ay), math.cos(az), math.sin(az)
+    Rx = ((1.0, 0.0, 0.0), (0.0, cx, -sx), (0.0, sx, cx))
+    Ry = ((cy, 0.0, sy), (0.0, 1.0, 0.0), (-sy, 0.0, cy))
+    Rz = ((cz, -sz, 0.0), (sz, cz, 0.0), (0.0, 0.0, 1.0))
+    mul = lambda P, Q: tuple(tuple(sum(P[i][k] * Q[k][j] for k in range(3)) for j in range(3)) for i in range(3))
+    return tuple(v for row in mul(Rz, mul(Ry, Rx)) for v in row)
+
+
+def shading_apply(view, normal, light, mask=None, stats=None, albedo_label=None, order=2, gamma=2.2, min_value=0.02, max_value=0.98,
+                  shade_floor=0.05, albedo_max=4.0, normal_signs=(1, 1, 1), relight=False, rotate_deg=(0, 0, 0), coefficients=None, gain=1.0):
+    """csrc/shading.hip: the planes of light [B, 3, 9] (shading_fit's) over the view and the normals it was fitted to -> a dict of
+    'shading' and 'albedo' [B, 3, H, W] fp32, 'shading_valid' [B, H, W] uint8 and, with `relight`, 'relit' [B, 3, H, W]: the encoded view
+    in [0, 1] under the light rotated by rotate_deg (degrees about x, y, z; R = Rz Ry Rx) or replaced by `coefficients` ([3][9] numbers),
+    times gain.  stats: shading_fit's record -- samples it flags invalid get planes of 0 and keep their view -- and with albedo_label
+    ([B, 3, H, W] or [B, H, W]) its entries 10..13 receive the scale-invariant albedo error.  Detached, nothing read on the host."""
+    with torch.no_grad():
+        head, held, (B, H, W), pix = _shading_operands('shading_apply', view, normal, mask, normal_signs, order, gamma, min_value, max_value)
+        _need(light, albedo_label, dtypes=_F32, contiguous=False)
+        _need(stats, dtypes=(torch.float64,))
+        if light is None:
+            raise DpfError('shading_apply: light [B, 3, 9] is needed')
+        _match_pred('shading_apply', held[0], ('light', light, (B, 3, 9)), ('stats', stats, (B, SHADING_STATS)))
+        channels = 3
+        if albedo_label is not None:
+            if albedo_label.dim() == 3:
+                albedo_label = albedo_label.unsqueeze(1)
+            channels = albedo_label.shape[1] if albedo_label.dim() == 4 else 0
+            if channels not in (1, 3):
+                raise DpfError('shading_apply: albedo_label %s is neither [B, 3, H, W] nor [B, H, W]' % (tuple(albedo_label.shape),))
+            _match_pred('shading_apply', held[0], ('albedo_label', albedo_label, (B, channels, H, W)))
+            albedo_label = _c(albedo_label.detach())
+        coeff = None
+        if coefficients is not None:
+            flat = [float(v) for row in coefficients for v in row]
+            if len(coefficients) != 3 or len(flat) != 27:
+                raise DpfError('shading_apply: coefficients must be [3][9] numbers')
+            coeff = _host_floats(flat)
+        dev = held[0].device
+        light = _c(light.detach())
+        ws, nbytes = _workspace('dpf_shading_workspace_bytes', 'shading_apply: B=%d H=%d W=%d is not supported', B, H, W, device=dev, tag='shading')
+        out = {'shading': torch.empty((B, 3, H, W), dtype=torch.float32, device=dev),
+               'albedo': torch.empty((B, 3, H, W), dtype=torch.float32, device=dev),
+               'shading_valid': torch.empty((B, H, W), dtype=torch.uint8, device=dev)}
+        if relight:
+            out['relit'] = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        lib().call('dpf_shading_apply', *head, _ptr(light), _ptr(stats), _ptr(albedo_label), channels, B, H, W, *pix, float(shade_floor),
+                   float(albedo_max), int(bool(relight)), coeff, _host_floats(shading_rotation(rotate_deg)), float(gain), _ptr(ws), nbytes,
+                   _ptr(out['shading']), _ptr(out['albedo']), _ptr(out['shading_valid']), _ptr(out.get('relit')), _stream())
+    return out
+
+
 NORMAL_GEO_STEPS = (1, 2, 4)
-NORMAL_GEO_STATS = 16       # doubles the forward leaves for the backward: count per head [0, 8), term sum per head [8, 16)
+NORMAL_GEO_STATS = 16      # doubles the forward leaves for the backward: count per head [0, 8), term sum per head [8, 16)
 
 
 _NORMAL_GEO = _HeadLoss('normal_geo_loss', 'dpf_normal_geo', 'BnHW', NORMAL_GEO_STATS,

@@ -11,7 +11,7 @@ import warnings
 
 import torch
 
-from . import confidence, normal_refine, ops, optim, postprocess, reconstruct
+from . import confidence, normal_refine, ops, optim, postprocess, reconstruct, shading
 from .losses import loss_selector
 from .selectors import metric_selector, optimizer_selector, scheduler_selector
 from .dpnet import DPNetCore
@@ -30,6 +30,8 @@ class _PluginHooks(object):
         self.metric_model = metric_selector(option)
         confidence.check_model(option)                     # (block on: a model without disparity hypotheses is refused by name)
         self.confidence_table = None                       # the sparsification table of a validation pass (confidence.report), on the device
+        shading.check_model(option)                        # (block on with normals "predicted": a model without a normal head is refused by name)
+        self.shading_table = None                          # the sums of a validation pass (shading.report), on the device
         self._adam = None                                  # the fused optimiser's state, kept by optim.py: 'adam' here,
         self._optim = None                                 # 'sgd' / 'rmsprop' here
 
@@ -54,6 +56,8 @@ class _PluginHooks(object):
             normal_refine.apply(self.option, results, batch)
         if not self.training and reconstruct.active(self.option):   # the surface of the filtered map, placed with the fitted (a, b)
             reconstruct.apply(self.option, results, confidence.gated(self.option, results, batch, 'reconstruct'), guide=self._views(batch)[0])
+        if not self.training and shading.active(self.option):       # ... -> surface -> shade: the lighting under the final normals
+            shading.apply(self.option, results, batch, guide=self._views(batch)[0])
         results.pop('_heads', None)                         # (the heads' logits, for the loss hook only: losses.UNIMODALLoss)
         return results
 
@@ -93,6 +97,7 @@ class _PluginHooks(object):
         if 'depth' in batch:
             self.metric_model.forward(results, confidence.gated(self.option, results, batch, 'metrics'), target_type=self._target_type())
         self.confidence_table = confidence.accumulate(self.option, results, batch, self.confidence_table, target_type=self._target_type())
+        self.shading_table = shading.accumulate(self.option, results, self.shading_table)
         return results
 
     def validation_epoch_end(self, outputs):

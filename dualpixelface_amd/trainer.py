@@ -29,7 +29,7 @@ import torch
 
 from . import distributed as dd
 from . import optim
-from . import confidence, reconstruct
+from . import confidence, reconstruct, shading
 
 
 def epoch_lr(option, epoch):
@@ -207,8 +207,29 @@ class Trainer(object):
         for f in sel.metric_func:
             f.clear()
         self._confidence_report(model, device, share)
+        self._shading_report(model, device, share)
         model.train()
         return rows
+
+    def _shading_report(self, model, device, share):
+        """option.shading.report: the sums the validation steps added into model.shading_table, read ONCE here (summed over the ranks by one
+        all-reduce that every rank issues, whatever it counted) -> self.shading_report, the dict of shading.report_rows, logged; None with
+        the report off.  The model's table is cleared for the next pass."""
+        s = shading.settings(self.option)
+        self.shading_report = None
+        if not (s.enabled and s.report):
+            return
+        table = getattr(model, 'shading_table', None)
+        model.shading_table = None
+        if table is None:
+            table = shading.new_table(device)
+        if share:
+            import torch.distributed as dist
+            dist.all_reduce(table, op=dist.ReduceOp.SUM)
+        self.shading_report = shading.report_rows(table.tolist())
+        self._log({'epoch': self.epoch, 'shading_report': self.shading_report})
+        if self.rank == 0:
+            print('shading: %s' % (self.shading_report,))
 
     def _confidence_report(self, model, device, share):
         """option.confidence.report: the sparsification table the validation steps added into model.confidence_table, read ONCE here (summed

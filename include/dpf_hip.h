@@ -848,6 +848,63 @@ int dpf_normal_refine(const float* pred, long long pred_batch_stride, int target
                       float max_edge_ratio, float min_cos, float lambda, int iterations, void* ws, long long ws_bytes, float* out,
                       long long out_batch_stride, double* stats, void* stream);
 
+/* ---- shading at evaluation (csrc/shading.hip; option key shading, dualpixelface_amd/shading.py; not in the
+ * reference): per sample, spherical-harmonics lighting fitted to the reference view under a normal map, then shading, relative albedo
+ * and the view under rotated or replaced light.  view [B, 3, H, W] fp32: the normalised reference view x; norm_host: the Normalizer's
+ * six host floats (mean_0..2, std_0..2); normal [B, 3, H, W] fp32; normal_signs_host: three host floats, each +1 or -1; mask [B, H, W] or
+ * NULL.  Host arrays are read during the call.
+ *   value      v_c = fminf(fmaxf(x_c std_c + mean_c, 0), 1) in fp32 (a NaN reads 0); I_c = v_c for gamma == 1 (no powf is called), else
+ *              powf(v_c, gamma)
+ *   normal     n = normal_signs * map; usable where the three components are finite and len = sqrt((x x + y y) + z z) > 0.5, in fp64;
+ *              nh = n / len in fp64
+ *   applicable mask NULL or > 0, and the normal usable;  counted: applicable and min_value <= v_c <= max_value for every c
+ *   basis      Y0 = 0.282095, Y1 = 0.488603 y, Y2 = 0.488603 z, Y3 = 0.488603 x, Y4 = 1.092548 (x y), Y5 = 1.092548 (y z),
+ *              Y6 = 0.315392 (3 (z z) - 1), Y7 = 1.092548 (x z), Y8 = 0.546274 (x x - y y); K = 4 (order 1) or 9 (order 2) of them
+ *   row        Z = [Y0 .. Y8, I_r, I_g, I_b, 1, 0, 0, 0] in fp64 for a counted pixel, 0 otherwise
+ *   pass       G = sum_p w_p Z_p Z_p^T (16 x 16, row major), the products (w z_i) z_j; pass 0: w = 1; pass i > 0:
+ *              w = 1 / sqrt(1 + q q), q = sqrt(((r_r r_r + r_g r_g) + r_b r_b) / 3) / f_scale, r_c = I_c - sum_{k < K} L_ck Y_k added left
+ *              to right under the fp64 L of the pass before.  1 + iterations passes, always all of them
+ *   solve      A = G[0:K, 0:K] (lower triangle) + ridge G[12][12] on the diagonal entries 1 .. K - 1; fp64 Cholesky, the three columns
+ *              G[0:K, 9 + c] as right-hand sides.  The sample is invalid when pass 0 counted fewer than min_pixels pixels or a pivot is
+ *              <= 1e-12 x the largest diagonal entry of A, in any pass: light 0, stats entry 1 = 0
+ *   light      [B, 3, 9] fp32, the last pass's L rounded once; entries K .. 8 are 0
+ *   stats      [B, 16] fp64: 0 counted pixels, 1 valid flag, 2 passes run (1 + iterations), 3 the last pass's sum of w, 4..6 the RMS
+ *              residual per channel of pass 0, sqrt(max(0, G[9+c][9+c] - 2 L.b + L^T G L) / G[12][12]), 7..9 the same of the last pass
+ *              under its own weights, 10..12 = -1 and 13 = 0 until dpf_shading_apply fills them, 14..15 = 0
+ *   gram_out   [B, 16, 16] fp64 or NULL: G of the last pass
+ * dpf_shading_fit launches, per pass, the Gram kernel (v_mfma_f64_16x16x4_f64: a wave stages 64 rows in LDS and adds four per
+ * instruction into one tile; a workgroup leaves one partial tile per >= 1024 pixels, at most 512 per sample) and the solve (one
+ * workgroup per sample folds the partial tiles in a fixed order).
+ * dpf_shading_apply, per applicable pixel of a valid sample (stats NULL: every sample is valid; else entry 1 decides), in fp32 from light,
+ * with n = (float) nh and the basis evaluated in fp32 as written above:
+ *   shading_c  sum_{k < K} L_ck Y_k(n), products added left to right
+ *   albedo_c   fminf(I_c / fmaxf(shading_c, shade_floor), albedo_max)
+ *   relit_c    with relight: m_i = (R[0][i] n_x + R[1][i] n_y) + R[2][i] n_z (rotation_host: R row major, nine host floats);
+ *              lin = (albedo_c gain) fmaxf(sum_{k < K} L'_ck Y_k(m), 0); cl = fminf(fmaxf(lin, 0), 1); relit_c = cl for gamma == 1, else
+ *              powf(cl, 1.f / gamma).  L' = relight_light_host ([3][9] host floats) or, where that is NULL, light
+ *   valid      uint8 [B, H, W]: 1 at these pixels.  Everywhere else shading = albedo = 0, valid = 0 and relit = v
+ *   check      with albedo_label ([B, label_channels, H, W], label_channels 1 or 3; one plane serves every channel) and stats: over the
+ *              counted pixels of a valid sample whose label is finite and > 0 in every channel, sum a a, sum a l, sum l l per channel in
+ *              fp64 and the count -> stats 10..12 = sqrt(max(0, 1 - (sum a l)^2 / (sum a a  sum l l))) (-1 where nothing was compared),
+ *              13 = the count
+ * relit is NULL exactly when relight is 0.  ws: dpf_shading_workspace_bytes() bytes of 8-byte aligned device scratch for either call
+ * (-1: shape refused), no initialisation needed.  No floating-point atomics, nothing allocates or waits on the host: the bits repeat,
+ * a sample does not depend on its batch, and both calls can be captured.  Refusals launch nothing: DPF_ERR_INVALID_ARG for a NULL
+ * pointer (but mask, gram_out, albedo_label, relight_light_host, and stats of the apply call), B, H, W <= 0, order outside 1..2,
+ * gamma <= 0, not 0 <= min_value < max_value <= 1, iterations outside 0..8, f_scale <= 0, ridge < 0, min_pixels < 1, shade_floor or
+ * albedo_max <= 0, gain < 0, a sign that is not +-1, a workspace too small or misaligned; DPF_ERR_UNSUPPORTED for B > 65535 or
+ * H W >= 2^31. */
+long long dpf_shading_workspace_bytes(int B, int H, int W);
+int dpf_shading_fit(const float* view, const float* normal, const float* mask, const float* norm_host, const float* normal_signs_host,
+                    int B, int H, int W, int order, float gamma, float min_value, float max_value, int iterations, double f_scale,
+                    double ridge, int min_pixels, void* ws, long long ws_bytes, float* light, double* stats, double* gram_out,
+                    void* stream);
+int dpf_shading_apply(const float* view, const float* normal, const float* mask, const float* norm_host, const float* normal_signs_host,
+                      const float* light, double* stats, const float* albedo_label, int label_channels, int B, int H, int W, int order,
+                      float gamma, float min_value, float max_value, float shade_floor, float albedo_max, int relight,
+                      const float* relight_light_host, const float* rotation_host, float gain, void* ws, long long ws_bytes,
+                      float* shading, float* albedo, unsigned char* valid, float* relit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
