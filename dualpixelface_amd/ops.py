@@ -2088,6 +2088,70 @@ def shading_apply(view, normal, light, mask=None, stats=None, albedo_label=None,
     return out
 
 
+REFOCUS_STATS = 8           # doubles per sample: d_f, counted pixels, valid flag, near sign used, min c, max c, then 0
+REFOCUS_FOCUS = {'mask_mean': 0, 'point': 1, 'value': 2}      # the focus codes of csrc/refocus.hip
+REFOCUS_RADII = range(1, 33)
+REFOCUS_TILE = 16           # kCell of csrc/refocus.hip: the side of a plan cell and of a render tile
+
+
+def refocus_focus_pixel(focus_point, H, W):
+    """The pixel (x, y) nearest focus_point = [u, v], fractions of width and height (pixel centres at (x + 0.5) / W)."""
+    import math
+    u, v = (float(f) for f in focus_point)
+    return min(W - 1, max(0, int(math.floor(u * W)))), min(H - 1, max(0, int(math.floor(v * H))))
+
+
+def refocus(view, disparity, mask=None, ab=None, target_type='disp', source=None, focus='mask_mean', focus_point=(0.5, 0.5), focus_value=0.0,
+            aperture=4.0, max_radius=16, near_sign='auto', gamma=2.2, gain=1.0):
+    """csrc/refocus.hip: the normalised view [B, 3, H, W] rendered again through a virtual aperture, from head 0 of disparity [B, n, H, W]
+    (or [B, H, W]; a slice of a wider tensor is taken as it is) -> a dict of 'refocused' [B, 3, H, W] fp32 in [0, 1], 'defocus' [B, H, W]
+    fp32 (the signed blur radius c in pixels) and 'refocus_stats' [B, 8] fp64 (REFOCUS_STATS).  Under target_type 'disp' the map is the
+    defocus disparity d = a / z + b itself, and so it is under 'idepth' (backproject reads both as z = a / (map - b)); under 'depth'
+    d = a / map + b.  ab [B, 2] = [b, a] is needed for 'idepth' and 'depth', and decides the near sign under 'auto'.  `source`: an encoded image [B, 3, H, W] in
+    [0, 1] (results['relit']) that is refocused in place of the view.  focus: 'mask_mean' (d_f = the mean of d over mask > 0 and finite),
+    'point' (d at the pixel nearest focus_point) or 'value' (focus_value).  near_sign: 'auto' (the sign of a where ab is given, else +1),
+    1 or -1.  The definitions are in include/dpf_hip.h.  An inference-time operator: detached, scratch through scratch(), nothing read
+    on the host."""
+    max_radius = _int_arg('refocus', 'max_radius', max_radius)
+    if max_radius not in REFOCUS_RADII:
+        raise DpfError('refocus: max_radius must be an integer from 1 to 32, got %r' % (max_radius,))
+    if focus not in REFOCUS_FOCUS:
+        raise DpfError('refocus: focus must be one of %s, got %r' % (sorted(REFOCUS_FOCUS), focus))
+    if near_sign != 'auto' and (isinstance(near_sign, bool) or near_sign not in (1, -1)):
+        raise DpfError("refocus: near_sign must be 'auto', 1 or -1, got %r" % (near_sign,))
+    if target_type not in TARGET_TYPES:
+        raise DpfError('refocus: target_type must be one of %s, got %r' % (sorted(TARGET_TYPES), target_type))
+    if ab is None and target_type != 'disp':
+        raise DpfError('refocus: target_type %r needs ab [B, 2] = [b, a] to become a defocus disparity' % (target_type,))
+    code = TARGET_TYPES[target_type]
+    with torch.no_grad():
+        _need(view, disparity, mask, ab, source, dtypes=_F32, contiguous=False)
+        if view is None or disparity is None or view.dim() != 4 or view.shape[1] != 3:
+            raise DpfError('refocus: view [B, 3, H, W] and disparity [B, n, H, W] are needed')
+        B, _, H, W = view.shape
+        pred = disparity.detach()
+        if pred.dim() == 3:
+            pred = pred.unsqueeze(1)
+        if pred.dim() != 4 or (pred.shape[0], pred.shape[2], pred.shape[3]) != (B, H, W):
+            raise DpfError('refocus: disparity %s is neither [B, n, H, W] nor [B, H, W] of view %s' % (tuple(disparity.shape), tuple(view.shape)))
+        _match_pred('refocus', view, ('mask', mask, (B, H, W)), ('ab', ab, (B, 2)), ('source', source, (B, 3, H, W)))
+        pred, stride = _batch_view(pred, H * W)
+        image = _c((view if source is None else source).detach())
+        mask, ab = None if mask is None else _c(mask.detach()), None if ab is None else _c(ab.detach())
+        fx, fy = refocus_focus_pixel(focus_point, H, W)
+        dev = image.device
+        ws, nbytes = _workspace('dpf_refocus_workspace_bytes', 'refocus: B=%d H=%d W=%d is not supported', B, H, W, device=dev, tag='refocus')
+        out = {'refocused': torch.empty((B, 3, H, W), dtype=torch.float32, device=dev),
+               'defocus': torch.empty((B, H, W), dtype=torch.float32, device=dev),
+               'refocus_stats': torch.empty((B, REFOCUS_STATS), dtype=torch.float64, device=dev)}
+        lib().call('dpf_refocus_plan', _ptr(pred), stride, code, _ptr(ab), _ptr(mask), B, H, W, REFOCUS_FOCUS[focus], fx, fy, float(focus_value),
+                   float(aperture), max_radius, 0 if near_sign == 'auto' else int(near_sign), _ptr(ws), nbytes, _ptr(out['defocus']),
+                   _ptr(out['refocus_stats']), _stream())
+        lib().call('dpf_refocus_render', _ptr(image), int(source is None), _normalizer_floats(), _ptr(out['defocus']), _ptr(out['refocus_stats']),
+                   B, H, W, max_radius, float(gamma), float(gain), _ptr(ws), nbytes, _ptr(out['refocused']), _stream())
+    return out
+
+
 NORMAL_GEO_STEPS = (1, 2, 4)
 NORMAL_GEO_STATS = 16      # doubles the forward leaves for the backward: count per head [0, 8), term sum per head [8, 16)
 

@@ -11,7 +11,7 @@ import warnings
 
 import torch
 
-from . import confidence, normal_refine, ops, optim, postprocess, reconstruct, shading
+from . import confidence, normal_refine, ops, optim, postprocess, reconstruct, refocus, shading
 from .losses import loss_selector
 from .selectors import metric_selector, optimizer_selector, scheduler_selector
 from .dpnet import DPNetCore
@@ -58,6 +58,8 @@ class _PluginHooks(object):
             reconstruct.apply(self.option, results, confidence.gated(self.option, results, batch, 'reconstruct'), guide=self._views(batch)[0])
         if not self.training and shading.active(self.option):       # ... -> surface -> shade: the lighting under the final normals
             shading.apply(self.option, results, batch, guide=self._views(batch)[0])
+        if not self.training and refocus.active(self.option):       # ... -> shade -> refocus: the view (or the relit one) through a virtual aperture
+            refocus.apply(self.option, results, batch, guide=self._views(batch)[0])
         results.pop('_heads', None)                         # (the heads' logits, for the loss hook only: losses.UNIMODALLoss)
         return results
 

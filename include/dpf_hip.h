@@ -905,6 +905,47 @@ int dpf_shading_apply(const float* view, const float* normal, const float* mask,
                       const float* relight_light_host, const float* rotation_host, float gain, void* ws, long long ws_bytes,
                       float* shading, float* albedo, unsigned char* valid, float* relit, void* stream);
 
+/* ---- synthetic depth of field at evaluation (csrc/refocus.hip; option key refocus, dualpixelface_amd/refocus.py; DESIGN.md section 11;
+ * not in the reference): the view rendered again through a virtual aperture.  pred: head 0 of a prediction, [H W] floats per sample,
+ * pred_batch_stride floats apart; target_type 0 'disp', 1 'idepth', 2 'depth' (the codes of dpf_backproject); ab [B, 2] = [b, a] or NULL
+ * (needed for 1 and 2); mask [B, H, W] or NULL.  Per sample, in fp32 and operation by operation:
+ *   d(p)       the defocus disparity a / z + b: pred for 'disp' and for 'idepth' (dpf_backproject reads both as z = a / (pred - b), so the
+ *              map is d itself and ab only decides the near sign), a / pred + b for 'depth'.  A pixel whose d is not finite is not
+ *              renderable: c = 0 there, it is copied through and contributes to nobody
+ *   d_f        the focus, fp64.  focus_mode 0 (mask_mean): the mean of d over the finite pixels with mask > 0 (NULL: all finite pixels), a
+ *              two-phase fixed-order fp64 sum (one partial row per >= 2048 pixels, at most 512 per sample; dpf_reduce.h); no counted
+ *              pixel: d_f = 0, flag 0.  1 (point): d at (focus_x, focus_y); not finite there: d_f = 0, flag 0, else counted = 1.
+ *              2 (value): focus_value, counted = 0, flag 1
+ *   near sign  near_sign where it is +1 or -1; 0 ('auto'): -1 where ab is given and a < 0, else +1
+ *   c(p)       fminf(fmaxf(aperture (d - (float) d_f), -max_radius), max_radius), r = |c|                           -> defocus [B, H, W]
+ *   stats      [B, 8] fp64: 0 d_f, 1 counted pixels, 2 valid flag, 3 near sign used, 4 min c, 5 max c (over every pixel), 6..7 = 0
+ * dpf_refocus_plan also leaves d and, per 16 x 16 cell of the image, the largest r in the workspace; dpf_refocus_render reads both, so
+ * it takes the workspace, the defocus plane and the stats of the plan call before it, untouched.
+ * dpf_refocus_render: image [B, 3, H, W], normalised (normalised != 0; norm_host: the Normalizer's six host floats, as for shading) or
+ * already encoded in [0, 1].  v = the encoded value clamped to [0, 1], L = v for gamma == 1, else powf(v, gamma).  Source q is behind
+ * receiver p iff near_sign (d(q) - d(p)) < 0, compared on the stored fp32 values.  For every renderable p, over the renderable q inside
+ * the image with |q - p|_inf <= max_radius:
+ *   r_eff      r(q) if q is not behind p, else fminf(r(q), r(p))
+ *   w(q, p)    clamp(r_eff + 1 - |q - p|_2, 0, 1) / fmaxf(1, pi r_eff^2)
+ *   O_c(p)     sum_q w L_c(q) / sum_q w: the taps of a window row are summed left to right, then the rows top to bottom, in fp32
+ *   out_c(p)   clamp(e gain, 0, 1), e = O_c for gamma == 1, else powf(O_c, 1 / gamma).  A pixel that is not renderable, or that received
+ *              from nobody but itself (sum_q w equals its own weight), keeps e = v: r = 0 everywhere returns the view
+ * One workgroup owns a 16 x 16 tile, stages its halo (linear RGB, r, near_sign d) in LDS once and gathers from there.  Its window is
+ * R_tile, not max_radius: the largest ceil(r) among the SOURCES in the cells within reach of the tile, narrowed until it no longer
+ * shrinks (a source further than R_tile away would need r > R_tile to arrive).  Up to 132356 bytes of LDS at max_radius 32.
+ * ws: dpf_refocus_workspace_bytes() bytes of 8-byte aligned device scratch (-1: shape refused), no initialisation needed.  No atomics,
+ * nothing allocates or waits on the host: the bits repeat, a sample does not depend on its batch, and both calls can be captured on one
+ * stream.  Refusals launch nothing: DPF_ERR_INVALID_ARG for a NULL pointer (but ab under 'disp', mask, and norm_host of an encoded image),
+ * B, H, W <= 0, a batch stride below H W, an unknown target_type or focus_mode, a focus point outside the image, a focus_value that is
+ * not finite, aperture < 0, max_radius outside 1..32, near_sign outside -1..1, gamma <= 0, gain < 0, a workspace too small or
+ * misaligned; DPF_ERR_UNSUPPORTED for B > 65535, H W >= 2^31 or H > 16 x 65535. */
+long long dpf_refocus_workspace_bytes(int B, int H, int W);
+int dpf_refocus_plan(const float* pred, long long pred_batch_stride, int target_type, const float* ab, const float* mask, int B, int H,
+                     int W, int focus_mode, int focus_x, int focus_y, double focus_value, float aperture, int max_radius, int near_sign,
+                     void* ws, long long ws_bytes, float* defocus, double* stats, void* stream);
+int dpf_refocus_render(const float* image, int normalised, const float* norm_host, const float* defocus, const double* stats, int B,
+                       int H, int W, int max_radius, float gamma, float gain, void* ws, long long ws_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
