@@ -2152,6 +2152,65 @@ def refocus(view, disparity, mask=None, ab=None, target_type='disp', source=None
     return out
 
 
+DP_RENDER_STATS = 8         # doubles per sample: finite pixels, pixels clamped at max_radius, min c, max c, then 0
+DP_RENDER_RADII = range(1, 33)
+DP_RENDER_TILE = 16         # kCell of csrc/dp_render.hip: the side of a plan cell and of a render tile
+DP_RENDER_OUTPUTS = ('normalised', 'encoded')
+DP_RENDER_SHIFT = (0.0, -2.0)                                   # the photometric block's default
+DP_RENDER_HALF_DISC = 3.0 * 3.14159265358979323846 / 8.0       # radius_scale / |shift|: the centroid of a half disc is 4 r / (3 pi) off centre
+
+
+def dp_render_radius_scale(shift, radius_scale=None):
+    """rho: radius_scale, or (3 pi / 8) |shift| for None -- the half discs of radius rho |d| then have centroids |shift| |d| apart."""
+    import math
+    return DP_RENDER_HALF_DISC * math.hypot(float(shift[0]), float(shift[1])) if radius_scale is None else float(radius_scale)
+
+
+def dp_render(image, disparity, shift=DP_RENDER_SHIFT, radius_scale=None, max_radius=16, near_sign=1, gamma=2.2, normalised=True,
+              output='normalised'):
+    """csrc/dp_render.hip: the two half-aperture views of the all-in-focus image [B, 3, H, W] (normalised, or encoded in [0, 1] under
+    normalised=False) under the signed defocus disparity [B, H, W] (zero in focus; a pixel that is not finite is copied through) -> a dict
+    of 'reference' and 'target' [B, 3, H, W] fp32 (normalised again, or encoded under output 'encoded'), 'radius' [B, H, W] fp32 (the
+    signed blur radius c in pixels) and 'dp_stats' [B, 8] fp64 (DP_RENDER_STATS).  reference(p) is target(p + shift d): what
+    photometric_loss samples under the same shift.  near_sign (+1: larger d is nearer) enters the occlusion rule only.  The definitions
+    are in include/dpf_hip.h.  No gradient: detached, scratch through scratch(), nothing read on the host."""
+    import math
+    max_radius = _int_arg('dp_render', 'max_radius', max_radius)
+    if max_radius not in DP_RENDER_RADII:
+        raise DpfError('dp_render: max_radius must be an integer from 1 to 32, got %r' % (max_radius,))
+    if isinstance(near_sign, bool) or near_sign not in (1, -1):
+        raise DpfError('dp_render: near_sign must be 1 or -1, got %r' % (near_sign,))
+    if output not in DP_RENDER_OUTPUTS:
+        raise DpfError('dp_render: output must be one of %s, got %r' % (list(DP_RENDER_OUTPUTS), output))
+    try:
+        sx, sy = (float(v) for v in shift)
+    except (TypeError, ValueError):
+        raise DpfError('dp_render: shift must be two finite numbers (x, y), not both 0, got %r' % (shift,))
+    if not (math.isfinite(sx) and math.isfinite(sy)) or (sx == 0 and sy == 0):
+        raise DpfError('dp_render: shift must be two finite numbers (x, y), not both 0, got %r' % (shift,))
+    rho = dp_render_radius_scale((sx, sy), radius_scale)
+    with torch.no_grad():
+        _need(image, disparity, dtypes=_F32, contiguous=False)
+        if image is None or disparity is None or image.dim() != 4 or image.shape[1] != 3:
+            raise DpfError('dp_render: image [B, 3, H, W] and disparity [B, H, W] are needed')
+        B, _, H, W = image.shape
+        if tuple(disparity.shape) != (B, H, W):
+            raise DpfError('dp_render: disparity %s is not [B, H, W] of image %s' % (tuple(disparity.shape), tuple(image.shape)))
+        image, disparity = _c(image.detach()), _c(disparity.detach())
+        dev = image.device
+        ws, nbytes = _workspace('dpf_dp_render_workspace_bytes', 'dp_render: B=%d H=%d W=%d is not supported', B, H, W, device=dev, tag='dp_render')
+        out = {'reference': torch.empty((B, 3, H, W), dtype=torch.float32, device=dev),
+               'target': torch.empty((B, 3, H, W), dtype=torch.float32, device=dev),
+               'radius': torch.empty((B, H, W), dtype=torch.float32, device=dev),
+               'dp_stats': torch.empty((B, DP_RENDER_STATS), dtype=torch.float64, device=dev)}
+        lib().call('dpf_dp_render_plan', _ptr(disparity), B, H, W, rho, max_radius, _ptr(ws), nbytes, _ptr(out['radius']), _ptr(out['dp_stats']),
+                   _stream())
+        lib().call('dpf_dp_render', _ptr(image), int(bool(normalised)), _normalizer_floats(), _ptr(disparity), _ptr(out['radius']), B, H, W, sx, sy,
+                   max_radius, int(near_sign), float(gamma), int(output == 'normalised'), _ptr(ws), nbytes, _ptr(out['reference']),
+                   _ptr(out['target']), _stream())
+    return out
+
+
 NORMAL_GEO_STEPS = (1, 2, 4)
 NORMAL_GEO_STATS = 16      # doubles the forward leaves for the backward: count per head [0, 8), term sum per head [8, 16)
 

@@ -946,6 +946,48 @@ int dpf_refocus_plan(const float* pred, long long pred_batch_stride, int target_
 int dpf_refocus_render(const float* image, int normalised, const float* norm_host, const float* defocus, const double* stats, int B,
                        int H, int W, int max_radius, float gamma, float gain, void* ws, long long ws_bytes, float* out, void* stream);
 
+/* ---- dual-pixel image formation (csrc/dp_render.hip; ops.dp_render; option key dp_render, dualpixelface_amd/dp_render.py; DESIGN.md
+ * section 11; not in the reference): the two half-aperture views of an all-in-focus image under a signed defocus disparity -- the half-disc
+ * model of Punnappurath et al. (ICCP 2020) and Abuolaim et al. (ICCV 2021) over the disc of the refocus block above.
+ * disparity [B, H, W]: the signed defocus disparity d, zero in focus; a pixel whose d is not finite is not renderable: c = 0 there, it is
+ * copied through and contributes to nobody.  dpf_dp_render_plan, per pixel, in fp32 and operation by operation:
+ *   r(p)       fminf(fmaxf(radius_scale |d| - 0.5, 0), max_radius).  The - 0.5: the coverage below gives a disc an effective radius of
+ *              r + 0.5.  With radius_scale = (3 pi / 8) |shift| the centroids of the two half discs are |shift| |d| apart
+ *   c(p)       r where d > 0, -r where d < 0 and r > 0, else +0                                                    -> radius [B, H, W]
+ *   stats      [B, 8] fp64: 0 finite pixels, 1 pixels with radius_scale |d| - 0.5 > max_radius (clamped), 2 min c, 3 max c (over every
+ *              pixel), 4..7 = 0.  The counts are fp64 sums of one partial row per 16 x 16 cell, folded in a fixed order (dpf_reduce.h)
+ * and it leaves, per 16 x 16 cell of the image, the largest r in the workspace; dpf_dp_render reads that, so it takes the workspace, the
+ * radius plane and the disparity of the plan call before it, untouched.
+ * dpf_dp_render: image [B, 3, H, W], normalised (normalised != 0; norm_host: the Normalizer's six host floats) or encoded in [0, 1].
+ * v = the encoded value clamped to [0, 1], L = v for gamma == 1, else powf(v, gamma).  u = shift / |shift|, formed once in fp32 on the
+ * host.  Source q is behind receiver p iff near_sign (d(q) - d(p)) < 0, on the stored fp32 values.  For every renderable p, over the
+ * renderable q inside the image with |q - p|_inf <= max_radius, o = p - q, sigma = the sign of c(q):
+ *   t          o_x u_x + o_y u_y (multiply, multiply, add)
+ *   r_eff      r(q) if q is not behind p, else fminf(r(q), r(p))                                       (the rule of dpf_refocus_render)
+ *   base       clamp(r_eff + 1 - |o|_2, 0, 1) / fmaxf(1, pi r_eff^2)
+ *   w_ref      base clamp(0.5 - sigma t, 0, 1);  w_tgt = base clamp(0.5 + sigma t, 0, 1), each computed on its own
+ *   O_v,c(p)   sum_q w_v L_c(q) / sum_q w_v: the taps of a window row are summed left to right, then the rows top to bottom, in fp32
+ *   out_v,c(p) e = O for gamma == 1, else powf(O, 1 / gamma); (e - mean_c) / std_c where output_normalised != 0
+ * A pixel that is not renderable, or that in view v received from nobody but itself (sum_q w_v equals its own weight), keeps its input
+ * value in that view: bit for bit where the output has the input's form, else v in the output's form.  d = 0 returns the image twice.
+ * The reference view's point-spread function has its centroid at -shift d / 2, the target view's at +shift d / 2: reference(p) is
+ * target(p + shift d), what dpf_photometric samples, and d is aligned to the centre (all-in-focus) view.  Negating shift, or negating
+ * d together with near_sign, swaps the two views bit for bit.  Below radius_scale |d| = 0.5 the two views coincide (a dead zone; no
+ * sub-pixel area coverage).
+ * One workgroup owns a 16 x 16 tile of both views, stages its halo in LDS once (the layout and the R_tile window of dpf_refocus_render,
+ * up to 132356 bytes at max_radius 32) and carries two weight sums and six colour sums per lane.
+ * ws: dpf_dp_render_workspace_bytes() bytes of 8-byte aligned device scratch (-1: shape refused), no initialisation needed.  No atomics,
+ * nothing allocates or waits on the host: the bits repeat, a sample does not depend on its batch, and both calls can be captured on one
+ * stream.  Refusals launch nothing: DPF_ERR_INVALID_ARG for a NULL pointer (but norm_host where neither side is normalised), B, H,
+ * W <= 0, radius_scale < 0 or not finite, a shift that is not finite or (0, 0), max_radius outside 1..32, near_sign other than +-1,
+ * gamma <= 0, a workspace too small or misaligned; DPF_ERR_UNSUPPORTED for B > 65535, H W >= 2^31 or H > 16 x 65535. */
+long long dpf_dp_render_workspace_bytes(int B, int H, int W);
+int dpf_dp_render_plan(const float* disparity, int B, int H, int W, float radius_scale, int max_radius, void* ws, long long ws_bytes,
+                       float* radius, double* stats, void* stream);
+int dpf_dp_render(const float* image, int normalised, const float* norm_host, const float* disparity, const float* radius, int B, int H,
+                  int W, float shift_x, float shift_y, int max_radius, int near_sign, float gamma, int output_normalised, void* ws,
+                  long long ws_bytes, float* reference, float* target, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

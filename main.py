@@ -6,7 +6,8 @@ builds the layered option object, instantiates the plugin through ``src/model/mo
 native trainer (dualpixelface_amd/trainer.py) instead of pytorch_lightning.  One process per GPU under torchrun.
 ``--synthetic N`` replaces the FaceDP loaders by N synthetic samples (no dataset is needed for a smoke run): N to train on and N // 4 to
 evaluate, or all N to evaluate where the config writes a mesh per sample (reconstruct.write_ply).  Under ``use_multi`` the samples are
-those of the plane scene with its neighbouring cameras (dualpixelface_amd/synthetic_multiview.py).
+those of the plane scene with its neighbouring cameras (dualpixelface_amd/synthetic_multiview.py); with ``dp_render.enabled`` they are face
+scenes whose dual-pixel pair is rendered on the device (dualpixelface_amd/synthetic_dp.py).
 """
 import argparse
 import os
@@ -59,6 +60,13 @@ def main():
 
             def synthetic_loader(length, height, width, batch_size, shuffle=False, seed=0):
                 return synthetic_multiview_loader(length, height, width, batch_size, views=views, shuffle=shuffle, seed=seed)
+        else:
+            from dualpixelface_amd import dp_render
+            if dp_render.active(opt):
+                from dualpixelface_amd.synthetic_dp import rendered_loader
+
+                def synthetic_loader(length, height, width, batch_size, shuffle=False, seed=0):
+                    return rendered_loader(length, height, width, batch_size, option=opt, shuffle=shuffle, seed=seed, device=device)
         train_loader = synthetic_loader(args.synthetic, args.height, args.width, opt.batch_size, shuffle=True, seed=1)
         from dualpixelface_amd import reconstruct
         held_out = args.synthetic if reconstruct.settings(opt).write_ply else max(1, args.synthetic // 4)
